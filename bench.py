@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: chain-steps/s of jump_mala + RealNVP on a synthetic Gaussian target (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W [--config C3|C2|C4|C5] [--reps R] [--fit-nf]
+    python bench.py --gpus N --steps K --warmup W [--config C3|C2|C4|C5] [--reps R] [--fit-nf] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -19,12 +19,21 @@ any timing by `Flow.fit` on draws of the target -- the state the reference's war
 random initialisation of rounds 1-2, which accepts ~0.2 % of the jumps; same arithmetic per transition either way),
 store_samples=False, x0 ~ N(0, I) from torch.manual_seed(0) on the CPU, uploaded before the timed region.  One bench
 "step" = one outer iteration = 101 Markov transitions of every chain.  W untimed warm-up steps carry the state from
-x0 to stationarity; then R (>= 5) timed repetitions of EXACTLY K steps each, every repetition bracketed by barrier +
-synchronize on both sides and reduced by MAX over ranks; `value` / `ms_per_step` come from the MEDIAN repetition
-(median of >= 5 runs), all repetitions are listed in `rep_ms`.  One further repetition of the same K
-steps carries HIP events around every launch of the dominant kernel (`events_rep_ms`; the events cost 3-4 % of a
-step, so it is not one of the R).
+x0 to stationarity.  Untimed repetitions of the K-step call follow until the GPU has been busy for --settle-s seconds
+(the clocks ramp over the first tens of ms of load); every repetition starts from the same state with the same seed,
+so they compute exactly what the timed one does.  Then R (--reps, default 1) timed repetitions of EXACTLY K steps
+each: with the defaults the timed steps are exactly K.  Every repetition is bracketed by barrier + synchronize on
+both sides and reduced by MAX over ranks; `value` / `ms_per_step` come from the MEDIAN repetition, all repetitions
+are listed in `rep_ms`.
   value = n_chains_total * transitions_per_step * K / t_median.
+--dump-outputs DIR writes what the last timed repetition returned to its caller (final chain states, running moments,
+counters; with --fit-nf the refitted flow) as DIR/<name>.npy: same arguments, same inputs, so two builds can be
+compared output for output.
+--full-report adds the side measurements of the earlier rounds' line, and with it their protocol (R = 5, repetitions
+until 6 s of timed GPU work, SURVEY 8d: median of >= 5 runs): one further repetition of the same K steps with HIP
+events around every launch of the dominant kernel (`events_rep_ms`, the roofline's launch time; the events cost 3-4 %
+of a step, so it is not one of the R), the Philox4x32-7 stream, and on the single-GPU C3 run the other configs and
+the unfitted-flow variants.  --no-other-configs, which only ever trimmed that line, implies it.
 
 roofline.  The dominant kernel of C3 is `mala_kernel`: it keeps the state in VGPRs for the 100 transitions of a
 launch, so its HBM traffic is ~1 % of the per-transition algorithmic bytes of SURVEY 8d and the roof that BINDS is
@@ -535,10 +544,42 @@ def roofline(cfg_name, cfg, n_local, mean_ms, launches, transitions_per_launch):
     return r
 
 
-def measure(name, args, env, reps, min_busy_s, philox7=True, cpu_legs=True, unfitted=False):
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, out, sampler, d, fit_nf):
+    """What the timed call returned to its caller in the last timed repetition, as `path`/<name>.npy (float32 stays
+    float32, everything else float64): the final state of every chain of this rank, the running moments, the integer
+    counters of the statistics (not the rates per second: those are timings), and with --fit-nf the flow the refits left.
+    Returns {'dir', 'files', 'bytes'} for the JSON line (files: the .npy files)."""
+    import numpy as np
+    import torch
+    st = out.statistics
+    arrays = {'last_state': out.running_samples.last_sample.reshape(-1, d), 'mean': out.mean,
+              'second_moment': out.second_moment, 'variance': out.variance}
+    arrays.update(('statistics.' + k, getattr(st, k)) for k in st.COUNTERS)
+    if fit_nf:
+        arrays.update(('flow.' + k, v) for k, v in sampler.kernel.flow.state_dict().items())
+    arrays = {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in arrays.items()}
+    arrays = {k: v.astype(np.float32 if v.dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError('--dump-outputs: %d bytes exceed the %d-byte budget' % (total, DUMP_MAX_BYTES))
+    if not os.path.isdir(path):
+        # a directory made here holds nothing but the dump: it keeps itself out of git wherever it lies in a checkout
+        os.makedirs(path)
+        with open(os.path.join(path, '.gitignore'), 'w') as fh:
+            fh.write('*\n')
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + '.npy'), v)
+    return {'dir': path, 'files': len(arrays), 'bytes': total}
+
+
+def measure(name, args, env, reps, min_busy_s, philox7=True, cpu_legs=True, unfitted=False, dump_dir=None):
     """One config measured by the protocol of the module docstring; returns the JSON line's dict on rank 0 (None elsewhere).
     `reps` timed repetitions of exactly K steps at least, more of the same until the repetitions add up to `min_busy_s`
-    seconds of back-to-back GPU work (so that an outside sampler of GPU utilisation sees the run); value = their median."""
+    seconds of back-to-back GPU work (so that an outside sampler of GPU utilisation sees the run); value = their median.
+    `dump_dir`: write the outputs of the last timed repetition there (dump_outputs)."""
     import torch
     dev, world, rank, dist, shard = env['dev'], env['world'], env['rank'], env['dist'], env['shard']
     distributed = dist is not None
@@ -593,9 +634,17 @@ def measure(name, args, env, reps, min_busy_s, philox7=True, cpu_legs=True, unfi
         _dt, wout, _s = run(args.warmup, x_start)
         x_start = carried(wout, x_start)
     label = cfg['label']
+    # untimed repetitions of the timed call until the GPU has been busy for settle_s: with 5 warm-up steps (~1.5 ms of C3
+    # work) the first repetitions ran up to 13 % slower than the median of a 6 s run (r04: 6.74 ms, then 6.53, 6.41, ...
+    # against 5.96) while the clocks ramped.  Same start state, same seed: they compute what the timed repetition does.
+    settled = 0.0
+    while settled < args.settle_s:
+        dt, _o, _s = run(args.steps, x_start)
+        settled += _reduce_times(dt, world, dist, dev)[0]
     # R (or more, see min_busy_s) repetitions WITHOUT events give `value` (an event pair per launch costs ~6 us of stream
-    # time: 3-4 % of a C3 step, measured); one more repetition of the same K steps, same brackets, WITH HIP events on the
-    # launch stream around every launch of the dominant kernel gives the roofline's launch duration (`events_rep_ms`)
+    # time: 3-4 % of a C3 step, measured); with --full-report one more repetition of the same K steps, same brackets, WITH
+    # HIP events on the launch stream around every launch of the dominant kernel gives the roofline's launch duration
+    # (`events_rep_ms`)
     reps_dt, reps_rank, out, sampler = [], [], None, None
     busy = 0.0
     while len(reps_dt) < reps or busy < min_busy_s:   # every rank sees the same max-reduced times: same decision everywhere
@@ -607,13 +656,14 @@ def measure(name, args, env, reps, min_busy_s, philox7=True, cpu_legs=True, unfi
         if len(reps_dt) >= 100000:
             break
     events_rep = (None, [])
-    if not args.no_kernel_events:
+    if args.full_report and not args.no_kernel_events:
         dt, eout, _s = run(args.steps, x_start, time_kernels=label)
         dt_max, _pr = _reduce_times(dt, world, dist, dev)
         events_rep = (dt_max, [a.elapsed_time(b) for (l, a, b) in (getattr(eout, 'kernel_events', None) or []) if l == label])
     # the opt-in Philox4x32-7 stream next to the default (three repetitions, same protocol): a reported side figure
     alt = None
-    if philox7 and args.rng_rounds == 10 and cfg['strategy'] in ('jump_mala', 'jump_hmc') and not args.fit_nf:
+    if (philox7 and args.full_report and args.rng_rounds == 10 and cfg['strategy'] in ('jump_mala', 'jump_hmc')
+            and not args.fit_nf):
         alt_reps, ev_all7 = [], []
         for i7 in range(3 if args.no_kernel_events else 4):
             timed_launches = (i7 == 3)
@@ -635,6 +685,7 @@ def measure(name, args, env, reps, min_busy_s, philox7=True, cpu_legs=True, unfi
     gc.enable()
     if rank != 0:
         return None
+    dumped = dump_outputs(dump_dir, out, sampler, cfg['d'], args.fit_nf) if dump_dir is not None else None
 
     order = sorted(range(len(reps_dt)), key=lambda i: reps_dt[i])
     med = order[len(order) // 2]
@@ -673,7 +724,7 @@ def measure(name, args, env, reps, min_busy_s, philox7=True, cpu_legs=True, unfi
         'events_rep_ms': (1e3 * events_rep[0]) if events_rep[0] is not None else None,
         'rep_ms_min': min(rep_ms), 'rep_ms_max': max(rep_ms),
         'rep_ms_p10_p90': [sorted(rep_ms)[len(rep_ms) // 10], sorted(rep_ms)[(9 * len(rep_ms)) // 10]],
-        'timed_busy_s': busy,
+        'timed_busy_s': busy, 'settle_s': settled, 'dump_outputs': dumped,
         'world_size_reported_by_backend': dist.get_world_size() if dist is not None else 1,
         'backend': dist.get_backend() if dist is not None else None,
         'per_rank_ms': [1e3 * v for v in per_rank],
@@ -725,32 +776,52 @@ def main():
     ap.add_argument('--warmup', type=int, default=50,
                     help='untimed steps before the timed repetitions; the default covers the ~30 ms the clocks take to ramp '
                          'under load (with 2 the first two of five repetitions were 5-12 %% slower than the last)')
-    ap.add_argument('--reps', type=int, default=5, help='timed repetitions of K steps at least; value = median (SURVEY 8d)')
-    ap.add_argument('--min-busy-s', type=float, default=6.0,
+    ap.add_argument('--reps', type=int, default=None,
+                    help='timed repetitions of K steps at least; value = median (default 1: the timed steps are exactly K; '
+                         '5 with --full-report, SURVEY 8d)')
+    ap.add_argument('--min-busy-s', type=float, default=None,
                     help='keep repeating the K-step repetition until the timed repetitions add up to this many seconds of '
                          'back-to-back GPU work (the headline config; value stays the median of ALL repetitions): a 6 ms '
-                         'repetition x 5 is invisible to a utilisation sampler')
+                         'repetition x 5 is invisible to a utilisation sampler (default 0; 6 with --full-report)')
+    ap.add_argument('--settle-s', type=float, default=0.2,
+                    help='untimed repetitions of the K-step call, after the warm-up steps and before timing, until the GPU '
+                         'has been busy this many seconds: the clocks ramp over the first tens of ms of load')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed repetition computed (final chain states, moments, counters) to '
+                         'DIR/<name>.npy')
+    ap.add_argument('--full-report', action='store_true',
+                    help='the line of the earlier rounds: R = 5 and 6 s of timed work unless given, the HIP-event repetition '
+                         'of the roofline, the Philox4x32-7 stream and, on the single-GPU C3 run, the other configs and the '
+                         'unfitted-flow variants')
     ap.add_argument('--config', choices=sorted(CONFIGS), default='C3')
     ap.add_argument('--fit-nf', action='store_true', help='jump strategies: refit the flow every outer iteration, so the '
                                                           'all-gather of the refit buffer (C1) is on the measured path')
     ap.add_argument('--rng-rounds', type=int, choices=[10, 7], default=10,
                     help='Philox4x32 rounds of the noise stream: 10 = the library default (what `value` is quoted on); 7 = the '
-                         'opt-in stream.  With the default, C3 / C5 also time the 7-round stream and report it as `philox7`')
+                         'opt-in stream.  With the default and --full-report, C3 / C5 also time the 7-round stream and report '
+                         'it as `philox7`')
     ap.add_argument('--unfitted-flow', action='store_true',
                     help='jump configs: keep the randomly initialised proposal flow (round 1-2 behaviour: ~0.2 %% of the jumps '
                          'accepted) instead of fitting it once, before any timing, as `warmup=True` would')
     ap.add_argument('--no-other-configs', action='store_true',
-                    help='the default single-GPU C3 run also measures C2, C4 and the C5 shard (3 repetitions each, >= 1 s of GPU '
-                         'work each, same protocol) and the unfitted-flow variants of C3 / C4, and attaches them to the ONE '
-                         'JSON line as `other_configs` / `unfitted_flow`; this switch keeps the line to the headline config')
+                    help='--full-report without the other configs: the --full-report single-GPU C3 run also measures C2, C4 '
+                         'and the C5 shard (3 repetitions each, >= 1 s of GPU work each, same protocol) and the unfitted-flow '
+                         'variants of C3 / C4, and attaches them to the ONE JSON line as `other_configs` / `unfitted_flow`; '
+                         'this switch keeps the line to the headline config (and so implies --full-report: the commands of '
+                         'tools/ and profiles/README.md that pass it measure what they did before --full-report existed)')
     ap.add_argument('--backend', choices=['nccl', 'gloo'], default='nccl')
     ap.add_argument('--rehearse', action='store_true', help='launcher / rendezvous / reduction only, no GPU work')
     ap.add_argument('--share-device', action='store_true',
                     help='(rehearsal on a one-GPU box, with --backend gloo) every rank computes on cuda:0: the whole N-rank '
                          'bench path -- launcher, sharding, collectives, reductions -- with real kernels; not a measurement')
     ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-kernel-events', action='store_true', help='(experiment) no HIP events in the timed region')
+    ap.add_argument('--no-kernel-events', action='store_true', help='(experiment, with --full-report) no HIP-event repetition')
     args = ap.parse_args()
+    args.full_report = args.full_report or args.no_other_configs
+    if args.reps is None:
+        args.reps = 5 if args.full_report else 1
+    if args.min_busy_s is None:
+        args.min_busy_s = 6.0 if args.full_report else 0.0
     args.reps = max(1, args.reps)
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
@@ -776,9 +847,10 @@ def main():
     shard = Shard(rank=rank, world=world) if distributed else None
     env = {'dev': dev, 'world': world, 'rank': rank, 'dist': dist, 'shard': shard}
 
-    line = measure(args.config, args, env, args.reps, args.min_busy_s, unfitted=args.unfitted_flow)
-    extras = (world == 1 and args.config == 'C3' and not args.fit_nf and not args.unfitted_flow and not args.no_other_configs
-              and args.rng_rounds == 10)
+    line = measure(args.config, args, env, args.reps, args.min_busy_s, unfitted=args.unfitted_flow,
+                   dump_dir=args.dump_outputs)
+    extras = (args.full_report and world == 1 and args.config == 'C3' and not args.fit_nf and not args.unfitted_flow
+              and not args.no_other_configs and args.rng_rounds == 10)
     if extras:
         # driver-visible evidence for every GPU config of BASELINE.json: same protocol, 3+ repetitions and
         # >= 1 s of GPU work each, roofline and the same-seed CPU-oracle leg; no CPU throughput baseline (the headline has it)
