@@ -406,13 +406,11 @@ class DeviceFit:
 
     def state_later(self, n_calls_done):
         """The same without stalling the stream: the state is copied to pinned host memory behind the run's kernels and an
-        event recorded; `PendingFit.result()` waits for THAT event only (kernels enqueued after the run keep the GPU busy)."""
+        event recorded; `PendingFit.result()` waits for THAT event only (kernels enqueued after the run keep the GPU busy).
+        Every PendingFit owns its pinned buffer (torch's caching host allocator hands it out again only once the copy into
+        it has completed and the PendingFit is gone): a later fit on the same flow can never overwrite an unread state."""
         half = (n_calls_done & 1) * self.hip.FIT_STATE_FLOATS
-        if self.__dict__.get('_pinned') is None:
-            self._pinned = [torch.empty(self.hip.FIT_STATE_FLOATS, dtype=torch.float32).pin_memory() for _ in range(2)]
-            self._pin_turn = 0
-        self._pin_turn ^= 1
-        host = self._pinned[self._pin_turn]
+        host = torch.empty(self.hip.FIT_STATE_FLOATS, dtype=torch.float32, pin_memory=True)
         host.copy_(self.run_state[half:half + self.hip.FIT_STATE_FLOATS], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
@@ -443,24 +441,26 @@ class DeviceFit:
 
 
 class PendingFit:
-    """Outcome of a device fit whose check was deferred (`Flow.fit(..., defer_check=True)`): `result()` waits for the fit's
-    own kernels (not for what was enqueued after them), raises the ValueError of a diverged run (jump.py:150) and returns
-    the best monitored loss."""
+    """Outcome of a fit whose check was deferred (`Flow.fit(..., defer_check=True)`): `result()` waits for the fit's own
+    kernels (not for what was enqueued after them), raises the ValueError of a diverged run (jump.py:150) and returns the
+    best monitored loss.  Made by every path of `fit`: a device run still in flight (`host_state` + `event`), a device run
+    the host has read already (`state`), the torch loop (`loss`, or the `error` it raised), an empty batch (inf)."""
 
-    def __init__(self, host_state=None, event=None, state=None):
-        self._host, self._event, self._state = host_state, event, state
+    def __init__(self, host_state=None, event=None, state=None, loss=math.inf, error=None):
+        self._host, self._event, self._state, self._loss, self._error = host_state, event, state, loss, error
 
     def result(self):
         from . import hip
-        if self._state is None:
-            if self._event is not None:
-                self._event.synchronize()
-            self._state = self._host.tolist() if self._host is not None else None
+        if self._error is not None:
+            raise self._error
+        if self._host is not None:
+            self._event.synchronize()
+            self._state = self._host.tolist()
             self._host = self._event = None
         st = self._state
         if st is not None and st[hip.FIT_DIVERGED]:
             raise ValueError('flow training diverged (non-finite loss)')
-        return st[hip.FIT_BEST_LOSS] if st is not None else math.inf
+        return st[hip.FIT_BEST_LOSS] if st is not None else self._loss
 
 
 def _run_chunk(time_limit_seconds, early_stopping):
@@ -511,13 +511,15 @@ def _fit_device(flow, xt, xv, n_epochs, lr, early_stopping, early_stopping_thres
                 if st[hip.FIT_STOPPED] or st[hip.FIT_DIVERGED]:
                     break
         st = fitter.state_after(done) if done else None
-        if st is not None and st[hip.FIT_DIVERGED]:
+        if st is not None and st[hip.FIT_DIVERGED] and not defer:
             raise ValueError('flow training diverged (non-finite loss)')
     finally:
         # whatever happened, the nn.Parameters end up as the best weights seen (or the last ones): callers that catch the
         # ValueError restore their own saved state_dict on top (jump.py:150-151).  Without best-weights bookkeeping the
         # weights after the last epoch that counted are the current vector (an early stop applies no further step).
         fitter.write_back(fitter.best if (keep_best_weights and done) else None)
+    if defer:      # the run has been read already (early stopping / time limit): result() raises or returns from it
+        return PendingFit(state=st)
     return st[hip.FIT_BEST_LOSS] if st is not None else math.inf
 
 
@@ -526,9 +528,9 @@ def fit(flow, x_train, x_val=None, n_epochs: int = 500, lr: float = 0.05, batch_
         early_stopping: bool = False, early_stopping_threshold: int = 50, time_limit_seconds=None, defer_check: bool = False,
         **_ignored):
     """Maximum-likelihood fit: minimise -mean log q(x_train).
-    `defer_check` (beyond the reference's keywords): on the device path, return a `PendingFit` instead of waiting for the
-    run -- its `result()` raises the ValueError of a diverged fit; the samplers' per-iteration refit uses it so that the GPU
-    is never idle behind a fit."""
+    `defer_check` (beyond the reference's keywords): return a `PendingFit` instead of raising -- its `result()` raises the
+    ValueError of a diverged fit or returns the best monitored loss, on every path; when nothing can end the device run
+    early it is not even waited for, so that the samplers' per-iteration refit never leaves the GPU idle behind a fit."""
     import os
     dev = _train_device(flow)
     resident = flow.bijection.__dict__.get('_device_fit')
@@ -536,7 +538,7 @@ def fit(flow, x_train, x_val=None, n_epochs: int = 500, lr: float = 0.05, batch_
     resident = resident is not None and resident.dev == dev and first_param is not None and first_param.device == dev
     if not resident:       # a flow that was fitted here before is on the device already (checked again by the fitter)
         flow.to(dev)
-    xt = x_train.detach().to(dev, torch.float32).reshape(x_train.shape[0], -1)
+    xt = x_train.detach().to(dev, torch.float32).reshape(x_train.shape[0], flow.bijection.d)   # (0, d) for no rows
     xv = x_val.detach().to(dev, torch.float32).reshape(x_val.shape[0], -1) if x_val is not None and len(x_val) else None
     n = xt.shape[0]
     if n == 0:
@@ -560,9 +562,14 @@ def fit(flow, x_train, x_val=None, n_epochs: int = 500, lr: float = 0.05, batch_
         return nll(xt[idx])
 
     val_fn = (lambda: nll(xv)) if xv is not None else None
-    _loop(flow, loss_fn, val_fn, n_epochs, lr, early_stopping, early_stopping_threshold, keep_best_weights,
-          show_progress, time_limit_seconds)
-    return PendingFit() if defer_check else None
+    try:
+        best = _loop(flow, loss_fn, val_fn, n_epochs, lr, early_stopping, early_stopping_threshold, keep_best_weights,
+                     show_progress, time_limit_seconds)
+    except ValueError as e:
+        if not defer_check:
+            raise
+        return PendingFit(error=e)     # the weights are those the non-deferred call leaves behind
+    return PendingFit(loss=best) if defer_check else None
 
 
 def _variational_fit_device(flow, potential, dev, n_epochs, lr, n_samples, early_stopping, early_stopping_threshold,

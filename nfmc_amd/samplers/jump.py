@@ -233,7 +233,13 @@ def split_flow_mh(run: Run, flow, target, event_shape, step, adjusted, stats_str
 
 
 class JumpNFMC(Sampler):
-    """Requires a flow with an efficient inverse (and forward, for adjusted jumps)."""
+    """Requires a flow with an efficient inverse (and forward, for adjusted jumps).
+
+    With `fit_nf` a refit that diverges raises ValueError out of `sample()`, as jump.py:201 does, but one outer iteration
+    later: the build's flow checks refit i when refit i + 1 starts, or when sampling ends after the last one (`_refit`,
+    `defer_check`).  The jump of iteration i and the inner block of iteration i + 1 have then already run on the weights
+    that refit wrote back.  A refit that returns early (early stopping, the reference's default, or a time limit) has been
+    read back before it returns, and `sample()` raises at the next refit or at its end all the same."""
 
     # Run the jump as the tail of the last inner launch (NfmcJumpTail) instead of its own kernel.  Correct and
     # tested, but off by default: the flow code raises the fused kernel's VGPR allocation from 91 to ~200

@@ -28,6 +28,7 @@ The build's RealNVP spec (DESIGN.md "RealNVP spec"), forward direction x -> z:
                       defaults H = max(4, int(3 log10 d_a)), n_hl = 2
 Events with more than one axis are flattened row-major.
 """
+import copy
 import math
 from typing import Sequence
 
@@ -290,6 +291,64 @@ def fit_(flow: Flow, x_train, n_epochs: int = 1, lr: float = 0.05):
         loss.backward()
         opt.step()
     return flow
+
+
+class FitTrace:
+    """What `fit_run` saw: per epoch e the batch loss at w_e (`train`) and the monitored loss (`val`: the validation loss at
+    w_{e+1}, or the batch loss at w_e without validation rows); the best monitored loss and its epoch (None when no epoch
+    improved on inf); the epoch the run stopped at (None when it ran all epochs); `best_state`, the weights of the best
+    loss (the starting weights when no epoch improved); `state`, the weights the run leaves (`best_state` with
+    keep_best_weights, else the last)."""
+
+    def __init__(self):
+        self.train, self.val = [], []
+        self.best_loss, self.best_epoch, self.stopped_at = math.inf, None, None
+        self.best_state, self.state = None, None
+
+
+def fit_run(flow: Flow, x_train, x_val=None, n_epochs: int = 500, lr: float = 0.05, early_stopping: bool = False,
+            early_stopping_threshold: int = 50, keep_best_weights: bool = True, dtype=torch.float64) -> FitTrace:
+    """The refit as the build specifies it (jump.py:139-151, 193-201 call `flow.fit(x_train, x_val, **kwargs)`; torchflows'
+    loop is not part of the reference): full-batch torch.optim.AdamW (default betas and eps, weight decay 0.01) on
+    -mean log q(x_train).  Epoch e: batch loss at w_e, the step w_e -> w_{e+1}, then the validation loss at w_{e+1} (without
+    validation rows the batch loss at w_e stands in, paired with w_{e+1}); a strictly lower monitored loss becomes the best
+    and its weights the best weights, any other epoch counts towards early stopping, which ends the run once more than
+    `early_stopping_threshold` epochs in a row did not improve.  A non-finite loss raises ValueError.  Runs on a deep copy of
+    `flow` in `dtype`; `flow` itself is left alone."""
+    f = copy.deepcopy(flow).to(dtype)
+    xt = x_train.detach().cpu().reshape(x_train.shape[0], -1).to(dtype)
+    xv = x_val.detach().cpu().reshape(x_val.shape[0], -1).to(dtype) if x_val is not None and len(x_val) else None
+
+    def nll(x):
+        return -f.log_prob(x.reshape(x.shape[0], *f.event_shape)).mean()
+
+    opt = torch.optim.AdamW(f.parameters(), lr=lr)
+    tr = FitTrace()
+    tr.best_state = copy.deepcopy(f.state_dict())
+    since = 0
+    for epoch in range(int(n_epochs)):
+        opt.zero_grad()
+        loss = nll(xt)
+        if not torch.isfinite(loss):
+            raise ValueError('flow training diverged (non-finite loss)')
+        loss.backward()
+        opt.step()
+        with torch.no_grad():
+            v = float(nll(xv)) if xv is not None else float(loss)
+        if not math.isfinite(v):
+            raise ValueError('flow training diverged (non-finite validation loss)')
+        tr.train.append(float(loss.detach()))
+        tr.val.append(v)
+        if v < tr.best_loss:
+            tr.best_loss, tr.best_epoch, since = v, epoch, 0
+            tr.best_state = copy.deepcopy(f.state_dict())
+        else:
+            since += 1
+            if early_stopping and since > early_stopping_threshold:
+                tr.stopped_at = epoch
+                break
+    tr.state = tr.best_state if keep_best_weights else copy.deepcopy(f.state_dict())
+    return tr
 
 
 def perturb_(flow: Flow, seed: int, scale: float = 0.3, target_std: float = None):

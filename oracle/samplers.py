@@ -268,11 +268,15 @@ def mcmc_sample(x0, target, kind, n_iterations, step_size, inv_mass_diag=None, n
 
 # --------------------------------------------------------------------------- A.3 jump loop
 def jump_sample(x0, target, flow, inner_kind, n_outer, n_inner, step_size, inv_mass_diag=None,
-                n_leapfrog=20, adjustment=True, adjusted_jumps=True, noise=None, store=True):
+                n_leapfrog=20, adjustment=True, adjusted_jumps=True, noise=None, store=True, refit=None):
     """`JumpNFMC.sample` (nfmc/algorithms/sampling/nfmc/jump.py:156-246), fit_nf=False.
 
     Transition numbering for PhiloxNoise: outer i, inner k -> i*(n_inner+1)+k; the jump is
     transition i*(n_inner+1)+n_inner.
+
+    `refit(i, flow, inner_states)`, when given, stands where fit_nf=True refits the flow (jump.py:193-201): after the
+    inner block of outer iteration i, before its jump, with that block's states (n_inner, n, d).  It may change `flow`
+    in place (e.g. load the weights a refit produced) and draws nothing from `noise`.
     """
     noise = noise or TorchNoise()
     n = x0.shape[0]
@@ -293,6 +297,9 @@ def jump_sample(x0, target, flow, inner_kind, n_outer, n_inner, step_size, inv_m
         tr.moments.update(inner.stacked())                                       # :188
         if store:
             tr.samples += inner.samples                                           # :189
+        if refit is not None:                                                     # :193-201
+            refit(i, flow, inner.stacked())
+            tr.n_refits += 1
         jstep = base + n_inner
         z = noise.normal(n, event, jstep, philox.TAG_LATENT)
         with torch.no_grad():
