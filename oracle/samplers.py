@@ -68,22 +68,30 @@ class RecordingNoise:
 
 
 class PhiloxNoise:
-    def __init__(self, seed, chain_offset=0, rounds=10):
+    """`dtype` (e.g. torch.float64 for an fp64 oracle run): the draws are still the fp32 values of oracle/philox.py --
+    the kernels' inputs --, promoted exactly to `dtype`.  None keeps them fp32."""
+
+    def __init__(self, seed, chain_offset=0, rounds=10, dtype=None):
         self.seed = seed
         self.chain_offset = chain_offset
         self.rounds = rounds   # 10: the library's stream; 7: the opt-in Philox4x32-7 stream
+        self.dtype = dtype
 
     def _ids(self, n):
         return np.arange(self.chain_offset, self.chain_offset + n, dtype=np.uint32)
 
+    def _out(self, v):
+        return v if self.dtype is None else v.to(self.dtype)
+
     def normal(self, n, shape, step, tag):
         d = int(math.prod(shape))
-        return torch.from_numpy(philox.normal_field(self.seed, self._ids(n), step, d, tag, self.rounds)).reshape(n, *shape)
+        return self._out(torch.from_numpy(philox.normal_field(self.seed, self._ids(n), step, d, tag,
+                                                              self.rounds)).reshape(n, *shape))
 
     def uniform(self, n, step, tag):
         if tag == philox.TAG_ACCEPT:
-            return torch.from_numpy(philox.accept_uniform(self.seed, self._ids(n), step, self.rounds))
-        return torch.from_numpy(philox.jump_uniform(self.seed, self._ids(n), step, self.rounds))
+            return self._out(torch.from_numpy(philox.accept_uniform(self.seed, self._ids(n), step, self.rounds)))
+        return self._out(torch.from_numpy(philox.jump_uniform(self.seed, self._ids(n), step, self.rounds)))
 
 
 # --------------------------------------------------------------------------- streaming moments
@@ -157,11 +165,12 @@ def proposal_potential(x_prime, x, grad_u_x, a_diag, tau):
     return (term * (1 / a_diag.view(1, -1)) * term).sum(dim=-1) / (4 * tau)
 
 
-def langevin_propose(x, target, step_size, inv_mass_diag, adjustment, noise, step):
+def langevin_propose(x, target, step_size, inv_mass_diag, adjustment, noise, step, info=None):
     """One `Langevin.propose` (langevin.py:61-122).  x: (n, d) (flattened events).
 
     Returns x_prime, mask, log_ratio (None for ULA), log_u (None for ULA).
     Draw order: randn_like(x) first (:63), rand(n) after the second target call (:106).
+    `info`, when a dict, receives the potentials 'u0' = U(x) and 'u1' = U(x_prime) of an adjusted step.
     """
     n = x.shape[0]
     eps = noise.normal(n, x.shape[1:], step, philox.TAG_NOISE)
@@ -176,6 +185,8 @@ def langevin_propose(x, target, step_size, inv_mass_diag, adjustment, noise, ste
     log_ratio = (-u_xp) - (-u_x) \
         + (-proposal_potential(x, x_prime, grad_u_xp, a_diag, step_size)) \
         - (-proposal_potential(x_prime, x, grad_u_x, a_diag, step_size))        # :88-105, util.py:392
+    if info is not None:
+        info.update(u0=u_x, u1=u_xp)
     log_u = torch.log(noise.uniform(n, step, philox.TAG_ACCEPT))                # :106
     return x_prime, log_u < log_ratio, log_ratio, log_u
 
@@ -193,8 +204,9 @@ def mh_propose(x, target, inv_mass_diag, adjustment, noise, step):
 
 
 # --------------------------------------------------------------------------- A.2 HMC / UHMC
-def hmc_propose(x, target, step_size, inv_mass_diag, n_leapfrog, adjustment, noise, step):
-    """One `HMC.propose` (hmc.py:96-126) with `hmc_trajectory` (:61-77).  x: (n, d)."""
+def hmc_propose(x, target, step_size, inv_mass_diag, n_leapfrog, adjustment, noise, step, info=None):
+    """One `HMC.propose` (hmc.py:96-126) with `hmc_trajectory` (:61-77).  x: (n, d).
+    `info`, when a dict, receives the Hamiltonians 'h0' and 'h1' of an adjusted step."""
     n = x.shape[0]
     p = noise.normal(n, x.shape[1:], step, philox.TAG_NOISE) * (1 / inv_mass_diag.sqrt())      # :100
     p0 = p
@@ -208,6 +220,8 @@ def hmc_propose(x, target, step_size, inv_mass_diag, n_leapfrog, adjustment, noi
     h0 = target(x) + 0.5 * _sum_event(p0 ** 2 * inv_mass_diag)                   # :103-106
     h1 = target(xq) + 0.5 * _sum_event(p ** 2 * inv_mass_diag)                   # :107-110
     log_ratio = -h1 - (-h0)                                                       # :111
+    if info is not None:
+        info.update(h0=h0.detach(), h1=h1.detach())
     log_u = torch.log(noise.uniform(n, step, philox.TAG_ACCEPT))                  # :112
     return xq, log_u < log_ratio, log_ratio.detach(), log_u
 
@@ -224,7 +238,7 @@ def mcmc_sample(x0, target, kind, n_iterations, step_size, inv_mass_diag=None, n
     x = x0.detach().clone().reshape(n, -1)
     d = x.shape[1]
     if inv_mass_diag is None:
-        inv_mass_diag = torch.ones(d)
+        inv_mass_diag = torch.ones(d, dtype=x.dtype)
     tr = Trace(moments=Moments.for_event((d,)))
     for it in range(n_iterations):
         step = step0 + it
@@ -301,30 +315,13 @@ def jump_sample(x0, target, flow, inner_kind, n_outer, n_inner, step_size, inv_m
             refit(i, flow, inner.stacked())
             tr.n_refits += 1
         jstep = base + n_inner
-        z = noise.normal(n, event, jstep, philox.TAG_LATENT)
-        with torch.no_grad():
-            x_prime, ld_inv = flow.bijection.inverse(z)                          # flow.sample, :205
-            f_x_prime = flow.base_log_prob(z) - ld_inv
-        x_prime = x_prime.reshape(n, -1)
         x = inner.last                                                            # :209
-        if adjusted_jumps:
-            try:                                                                  # :210-227
-                u_x = target(x)                                                   # :212
-                u_xp = target(x_prime)                                            # :213
-                tr.n_target_calls += 2 * n
-                with torch.no_grad():
-                    f_x = flow.log_prob(x.reshape(n, *event))                     # :218
-                log_alpha = (-u_xp) - (-u_x) + f_x - f_x_prime                    # :219-224, util.py:392
-                log_u = noise.uniform(n, jstep, philox.TAG_JUMP).log()            # :225
-                mask = log_u < log_alpha
-                tr.log_ratios.append(log_alpha.detach())
-                tr.uniforms.append(log_u)
-            except ValueError:                                                    # :226-227: reject all, no divergence
-                mask = torch.zeros(n, dtype=torch.bool)
-        else:
-            mask = torch.ones(n, dtype=torch.bool)
-        x = x.clone()
-        x[mask] = x_prime[mask]                                                   # :231
+        js = jump_transition(x, target, flow, jstep, noise, adjusted_jumps, event)
+        tr.n_target_calls += js.n_target_calls
+        if js.log_alpha is not None:
+            tr.log_ratios.append(js.log_alpha)
+            tr.uniforms.append(js.log_u)
+        x, mask = js.x, js.mask                                                   # :231
         tr.n_attempted_jumps += n
         tr.n_accepted_jumps += int(mask.sum())
         tr.masks.append(mask)
@@ -335,9 +332,56 @@ def jump_sample(x0, target, flow, inner_kind, n_outer, n_inner, step_size, inv_m
     return tr
 
 
+@dataclass
+class JumpStep:
+    """One flow-proposal MH transition (`jump_transition`).  `log_alpha` / `log_u` are None when the jump is unadjusted or
+    the target failed; u_x, u_xp (potentials) and f_x, f_xp (log q) are kept for the tie margin of the shadowing harness."""
+    x: torch.Tensor
+    x_prime: torch.Tensor
+    mask: torch.Tensor
+    log_alpha: Optional[torch.Tensor] = None
+    log_u: Optional[torch.Tensor] = None
+    u_x: Optional[torch.Tensor] = None
+    u_xp: Optional[torch.Tensor] = None
+    f_x: Optional[torch.Tensor] = None
+    f_xp: Optional[torch.Tensor] = None
+    n_target_calls: int = 0
+
+
+def jump_transition(x, target, flow, jstep, noise, adjusted=True, event=None):
+    """The jump of `jump_sample` (jump.py:205-231) from the states x (n, d): latent draw at transition `jstep`, flow inverse,
+    adjusted log-alpha, `TAG_JUMP` uniform.  Runs in the dtype of x, `flow` and `noise` (all fp64 for an fp64 oracle)."""
+    n = x.shape[0]
+    event = tuple(event) if event is not None else tuple(flow.event_shape)
+    z = noise.normal(n, event, jstep, philox.TAG_LATENT)
+    with torch.no_grad():
+        x_prime, ld_inv = flow.bijection.inverse(z)                              # flow.sample, :205
+        f_x_prime = flow.base_log_prob(z) - ld_inv
+    x_prime = x_prime.reshape(n, -1)
+    js = JumpStep(x=x, x_prime=x_prime, mask=torch.ones(n, dtype=torch.bool), f_xp=f_x_prime)
+    if adjusted:
+        try:                                                                      # :210-227
+            u_x = target(x)                                                       # :212
+            u_xp = target(x_prime)                                                # :213
+            js.n_target_calls = 2 * n
+            with torch.no_grad():
+                f_x = flow.log_prob(x.reshape(n, *event))                         # :218
+            log_alpha = (-u_xp) - (-u_x) + f_x - f_x_prime                        # :219-224, util.py:392
+            log_u = noise.uniform(n, jstep, philox.TAG_JUMP).log()                # :225
+            js.mask = log_u < log_alpha
+            js.log_alpha, js.log_u = log_alpha.detach(), log_u
+            js.u_x, js.u_xp, js.f_x = u_x.detach(), u_xp.detach(), f_x
+        except ValueError:                                                        # :226-227: reject all, no divergence
+            js.mask = torch.zeros(n, dtype=torch.bool)
+    js.x = x.clone()
+    js.x[js.mask] = x_prime[js.mask]                                              # :231
+    return js
+
+
 # --------------------------------------------------------------------------- A.4 FixedIMH
-def imh_sample(x0, target, flow, n_iterations, noise=None, store=True):
-    """`FixedIMH.sample` (nfmc/algorithms/sampling/nfmc/imh.py:200-255)."""
+def imh_sample(x0, target, flow, n_iterations, noise=None, store=True, step0=0):
+    """`FixedIMH.sample` (nfmc/algorithms/sampling/nfmc/imh.py:200-255).  Iteration `it` draws at transition step0 + it;
+    log q of the current states is computed from x0 and then carried (imh.py:214,233)."""
     noise = noise or TorchNoise()
     n = x0.shape[0]
     event = x0.shape[1:]
@@ -346,12 +390,13 @@ def imh_sample(x0, target, flow, n_iterations, noise=None, store=True):
     with torch.no_grad():
         f_x = flow.log_prob(x.reshape(n, *event))                                 # :214
         for it in range(n_iterations):
-            z = noise.normal(n, event, it, philox.TAG_LATENT)
+            step = step0 + it
+            z = noise.normal(n, event, step, philox.TAG_LATENT)
             x_prime, ld_inv = flow.bijection.inverse(z)                           # :221
             f_xp = flow.base_log_prob(z) - ld_inv
             x_prime = x_prime.reshape(n, -1)
             log_alpha = (-target(x_prime)) - (-target(x)) + f_x - f_xp           # :223-228
-            log_u = noise.uniform(n, it, philox.TAG_JUMP).log()                   # :229
+            log_u = noise.uniform(n, step, philox.TAG_JUMP).log()                 # :229
             mask = torch.less(log_u, log_alpha)                                   # :230
             x[mask] = x_prime[mask]                                               # :232
             f_x[mask] = f_xp[mask]                                                # :233
@@ -464,12 +509,13 @@ def neutra_adjusted_target(flow, target, event):
 
 
 def neutra_hmc_sample(z0, target, flow, n_iterations, step_size, inv_mass_diag=None, n_leapfrog=20,
-                      noise=None, store=True):
+                      noise=None, store=True, step0=0):
     """`NeuTra.sample` (neutra.py:109-129): HMC on the adjusted target; samples/moments stay latent
-    (the data_transform assigned at neutra.py:122 / mcmc/base.py:63 never reaches the moments: SURVEY App. C #1)."""
+    (the data_transform assigned at neutra.py:122 / mcmc/base.py:63 never reaches the moments: SURVEY App. C #1).
+    Trajectory `it` draws at transition step0 + it."""
     event = z0.shape[1:]
     return mcmc_sample(z0, neutra_adjusted_target(flow, target, event), 'hmc', n_iterations, step_size,
-                       inv_mass_diag, n_leapfrog, True, noise, 0, store)
+                       inv_mass_diag, n_leapfrog, True, noise, step0, store)
 
 
 # --------------------------------------------------------------------------- a12 refit buffer
