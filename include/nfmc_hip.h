@@ -353,6 +353,38 @@ int nfmc_neutra_hmc_steps_f32(const NfmcNeutraHmcArgs* args, nfmc_stream_t strea
 int nfmc_neutra_potential_grad_f32(const NfmcRealNVP* flow, const NfmcPotential* pot, const float* z, int64_t n,
                                    float* u_out, float* grad_out, nfmc_stream_t stream);
 
+/* ---- DLMC (nfmc/algorithms/sampling/nfmc/dlmc.py).  Replaces `compute_grad(lambda v: self.target(v) +
+ * flow_log_prob(v), x)` and the gradient step `x = x - self.kernel.step_size * grad` (dlmc.py:85-87), whose flow half
+ * is torch.autograd through `flow.log_prob` (dlmc.py:52-53).  Kernels (csrc/dlmc_kernels.hip): a reverse sweep through
+ * the forward map x -> z, one chain per lane, for affine / additive couplings with n_hidden <= 8 and d <= 512; other
+ * flows (splines, wider conditioners) answer NFMC_EUNSUPPORTED and the caller composes the step from autograd. */
+typedef struct {
+    NfmcRealNVP flow;
+    const float* x;           /* (n, d) */
+    int64_t n;
+    float* grad_out;          /* (n, d) grad_x log q(x), or NULL */
+    float* logq_out;          /* (n,) log q(x) (flow.log_prob, jump.py:218), or NULL; not both NULL */
+} NfmcFlowLogqGradArgs;
+
+int nfmc_flow_logq_grad_f32(const NfmcFlowLogqGradArgs* args, nfmc_stream_t stream);
+/* Dry run: 0 when nfmc_flow_logq_grad_f32 has a kernel for args, else the status it would return. */
+int nfmc_flow_logq_grad_supported_f32(const NfmcFlowLogqGradArgs* args);
+
+typedef struct {
+    NfmcRealNVP flow;
+    NfmcPotential pot;        /* closed-form U, used when grad_u is NULL (QUADRATIC or FUNNEL) */
+    float* x;                 /* (n, d) in place: x <- x - step_size (grad U(x) + grad_x log q(x))  (dlmc.py:85-87) */
+    const float* grad_u;      /* (n, d) grad U(x) computed by the caller (autograd targets), or NULL -> pot */
+    float* logq_out;          /* (n,) log q at the PRE-step x, or NULL */
+    int64_t n;
+    float step_size;          /* DLMCKernel.step_size (dlmc.py:14), >= 0 */
+    int32_t reserved;
+} NfmcDlmcStepArgs;
+
+int nfmc_dlmc_step_f32(const NfmcDlmcStepArgs* args, nfmc_stream_t stream);
+/* Dry run: 0 when nfmc_dlmc_step_f32 has a kernel for args, else the status it would return. */
+int nfmc_dlmc_step_supported_f32(const NfmcDlmcStepArgs* args);
+
 /* ---- split path for arbitrary Python targets (U and grad U come from torch autograd on the GPU).
  * K6: mask = log(u) < lp_t' - lp_t + lp_q - lp_q' (nfmc/util.py:382-392), x[mask] = x'[mask]
  * (mcmc/base.py:77), optional carried per-chain scalars, counters. */

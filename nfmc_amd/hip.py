@@ -96,6 +96,15 @@ class NfmcNeutraHmcArgs(C.Structure):
                 ('scratch_bytes', C.c_int64)]
 
 
+class NfmcFlowLogqGradArgs(C.Structure):
+    _fields_ = [('flow', NfmcRealNVP), ('x', c_fp), ('n', C.c_int64), ('grad_out', c_fp), ('logq_out', c_fp)]
+
+
+class NfmcDlmcStepArgs(C.Structure):
+    _fields_ = [('flow', NfmcRealNVP), ('pot', NfmcPotential), ('x', c_fp), ('grad_u', c_fp), ('logq_out', c_fp),
+                ('n', C.c_int64), ('step_size', C.c_float), ('reserved', C.c_int32)]
+
+
 class NfmcSelectArgs(C.Structure):
     _fields_ = [('x', c_fp), ('x_prime', c_fp), ('n', C.c_int64), ('d', C.c_int32), ('n_carry', C.c_int32),
                 ('log_ratio', c_fp), ('uniforms', c_fp), ('carry', c_fp * 2), ('carry_prime', c_fp * 2),
@@ -157,6 +166,10 @@ SYMBOLS = [
     ('nfmc_neutra_hmc_steps_f32', C.c_int, [C.POINTER(NfmcNeutraHmcArgs), c_fp]),
     ('nfmc_neutra_potential_grad_f32', C.c_int, [C.POINTER(NfmcRealNVP), C.POINTER(NfmcPotential), c_fp, C.c_int64,
                                                  c_fp, c_fp, c_fp]),
+    ('nfmc_flow_logq_grad_f32', C.c_int, [C.POINTER(NfmcFlowLogqGradArgs), c_fp]),
+    ('nfmc_flow_logq_grad_supported_f32', C.c_int, [C.POINTER(NfmcFlowLogqGradArgs)]),
+    ('nfmc_dlmc_step_f32', C.c_int, [C.POINTER(NfmcDlmcStepArgs), c_fp]),
+    ('nfmc_dlmc_step_supported_f32', C.c_int, [C.POINTER(NfmcDlmcStepArgs)]),
     ('nfmc_mh_accept_select_f32', C.c_int, [C.POINTER(NfmcSelectArgs), c_fp]),
     ('nfmc_langevin_propose_f32', C.c_int, [c_fp, c_fp, c_fp, C.c_float, C.c_int64, C.c_int32, C.POINTER(NfmcRng),
                                             c_fp, c_fp]),

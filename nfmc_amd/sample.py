@@ -4,9 +4,9 @@ plumbing (nfmc/sample.py:20-30, 243-314) for the strategies on this build's path
     mala, ula, hmc, uhmc, mh                              (inner samplers)
     imh / fixed_imh, jump_mala, jump_ula, jump_hmc, jump_uhmc, jump_mh, neutra_hmc, neutra_mh
 
-    adaptive_imh
+    adaptive_imh, dlmc (needs `negative_log_likelihood`, like the reference)
 
-Other reference strategies (ess, nuts, jump_ess, tess, dlmc) are outside the path and raise
+Other reference strategies (ess, nuts, jump_ess, tess) are outside the path and raise
 ValueError naming what is supported.
 """
 from typing import Optional, Tuple, Union
@@ -16,6 +16,7 @@ import torch
 from .containers import MCMCOutput, NFMCKernel, Sampler
 from .flows import Flow
 from .potentials import Potential
+from .samplers.dlmc import DLMC, DLMCKernel, DLMCParameters
 from .samplers.imh import AdaptiveIMH, FixedIMH, IMHKernel, IMHParameters
 from .samplers.jump import JumpHMC, JumpMALA, JumpMH, JumpNFMCParameters, JumpUHMC, JumpULA
 from .samplers.mcmc import (HMC, MALA, MH, UHMC, ULA, HMCKernel, HMCParameters, LangevinKernel, LangevinParameters,
@@ -63,8 +64,11 @@ def create_sampler(target: callable,
     if strategy == "mh":
         return MH(event_shape, target, MHKernel(event_size=event_size, **kernel_kwargs), MHParameters(**param_kwargs))
 
+    if strategy == "dlmc" and negative_log_likelihood is None:
+        raise ValueError("Unsupported sampling strategy: dlmc without a negative_log_likelihood "
+                         "(Negative log likelihood must be provided)")   # sample.py:221-222
     if strategy in ("imh", "fixed_imh", "adaptive_imh", "jump_mala", "jump_ula", "jump_hmc", "jump_uhmc", "jump_mh", "neutra_hmc",
-                    "neutra_mh"):
+                    "neutra_mh", "dlmc"):
         if flow is None:
             raise ValueError("Flow object must be provided")
         if isinstance(flow, str):
@@ -103,6 +107,9 @@ def create_sampler(target: callable,
                           params=JumpNFMCParameters(**param_kwargs),
                           inner_kernel=MHKernel(event_size=event_size, **inner_kernel_kwargs),
                           inner_params=MHParameters(**inner_param_kwargs))
+        if strategy == 'dlmc':   # sample.py:220-225
+            return DLMC(event_shape, target, negative_log_likelihood, DLMCKernel(event_shape, flow=flow_object),
+                        DLMCParameters(**param_kwargs))
         if strategy == 'neutra_mh':
             return NeuTraMH(event_shape, target, MHKernel(event_size=event_size, **inner_kernel_kwargs),
                             MHParameters(**inner_param_kwargs), NeuTraKernel(event_shape, flow=flow_object),
