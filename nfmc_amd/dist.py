@@ -93,10 +93,7 @@ class Shard:
             return st
         e1, e2 = st.expectations['first_moment'], st.expectations['second_moment']
         d = e1.total.numel()
-        names = ['n_accepted_trajectories', 'n_attempted_trajectories', 'n_divergences', 'n_target_gradient_calls',
-                 'n_target_calls', 'n_nonfinite_log_ratios']
-        if hasattr(st, 'n_accepted_jumps'):
-            names += ['n_accepted_jumps', 'n_attempted_jumps']
+        names = type(st).COUNTERS + ('n_nonfinite_log_ratios',)
         pack = torch.cat([e1.total.reshape(-1).double(), e2.total.reshape(-1).double(),
                           torch.tensor([float(e1.n_seen)] + [float(getattr(st, k)) for k in names],
                                        dtype=torch.float64)])

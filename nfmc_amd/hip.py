@@ -251,6 +251,15 @@ def check(rc, what):
     raise RuntimeError('%s: HIP error %d: %s' % (what, rc, msg))
 
 
+def supported(rc, what) -> bool:
+    """The answer of a `*_supported_f32` dry-run query: False for a valid request no fused kernel covers
+    (NfmcArgumentError.no_kernel), True for OK; any other status raises as `check` does."""
+    if rc in (EUNSUPPORTED, ESHAPE):
+        return False
+    check(rc, what)
+    return True
+
+
 def require_gpu():
     if not torch.cuda.is_available():
         raise RuntimeError('nfmc_amd needs a ROCm GPU (MI355X / gfx950); torch.cuda.is_available() is False. '

@@ -15,7 +15,7 @@ from dataclasses import dataclass
 import torch
 
 from .. import hip
-from ..containers import DeviceSampleStore, MCMCOutput, NFMCKernel, NFMCParameters, Sampler
+from ..containers import MCMCOutput, NFMCKernel, NFMCParameters, Sampler
 from ..tuning import train_val_split
 from .common import Run, progress, resolve_target
 from .jump import flow_is_native, flow_mh_supported, launch_flow_mh, split_flow_mh
@@ -62,7 +62,7 @@ def logq_grad_supported(flow, n=1, d=None) -> bool:
     x = torch.empty(1, flow.bijection.d, dtype=torch.float32, device=dev)
     a, _keep = logq_grad_args(flow, x, logq_out=torch.empty(1, dtype=torch.float32, device=dev))
     a.n = int(n)
-    return _supported(int(hip.lib().nfmc_flow_logq_grad_supported_f32(C.byref(a))), 'nfmc_flow_logq_grad_supported_f32')
+    return hip.supported(int(hip.lib().nfmc_flow_logq_grad_supported_f32(C.byref(a))), 'nfmc_flow_logq_grad_supported_f32')
 
 
 def logq_grad(flow, x):
@@ -110,7 +110,7 @@ def step_supported(flow, x, step_size, pot=None, grad_u=None) -> bool:
     if not flow_is_native(flow):
         return False
     a, _keep = step_args(flow, x, step_size, pot, grad_u if grad_u is not None else (x if pot is None else None))
-    return _supported(int(hip.lib().nfmc_dlmc_step_supported_f32(C.byref(a))), 'nfmc_dlmc_step_supported_f32')
+    return hip.supported(int(hip.lib().nfmc_dlmc_step_supported_f32(C.byref(a))), 'nfmc_dlmc_step_supported_f32')
 
 
 def launch_step(flow, x, step_size, pot=None, grad_u=None):
@@ -118,13 +118,6 @@ def launch_step(flow, x, step_size, pot=None, grad_u=None):
     the caller's `grad_u`."""
     a, _keep = step_args(flow, x, step_size, pot, grad_u)
     hip.check(hip.lib().nfmc_dlmc_step_f32(C.byref(a), hip.stream()), 'nfmc_dlmc_step_f32')
-
-
-def _supported(rc, what) -> bool:
-    if rc in (hip.EUNSUPPORTED, hip.ESHAPE):
-        return False
-    hip.check(rc, what)
-    return True
 
 
 class DLMC(Sampler):
@@ -192,15 +185,14 @@ class DLMC(Sampler):
     def sample(self, x0, show_progress: bool = True, time_limit_seconds=None) -> MCMCOutput:
         """dlmc.py:45-127 on the device."""
         run = Run(self, x0)
-        n, d, es = run.n, run.d, run.event_shape
+        n, es = run.n, run.event_shape
         flow = self.kernel.flow
         T = int(self.params.n_iterations)
         eps = float(self.kernel.step_size)
         pot = resolve_target(self.target, es, self.fuse, run.x)
         nll = resolve_target(self.negative_log_likelihood, es, self.fuse, run.x)
         native = flow_is_native(flow)
-        store = DeviceSampleStore(n, d, run.dev, T, getattr(self.params, 'thinning', 1),
-                                  getattr(self.params, 'max_samples', None)) if (self.params.store_samples and T > 0) else None
+        store = run.sample_store(T)
         logq = torch.empty(n, dtype=torch.float32, device=run.dev)
         target_calls = grad_calls = 0
 
@@ -257,20 +249,8 @@ class DLMC(Sampler):
                 bar.set_postfix_str(f'acc {int(run.stats.counters[hip.CNT_ACCEPTED])}/{n * done}')
         if pending_fit is not None:
             pending_fit.result()
-        last_sample = run.x.reshape(n, *es).clone()
-        sum_x, sum_x2, cnt, _jc = run.stats.host_totals()
-        out = MCMCOutput(es, store_samples=self.params.store_samples, max_samples=getattr(self.params, 'max_samples', None))
-        st = out.statistics
-        st.update_counters(n_accepted_trajectories=int(cnt[hip.CNT_ACCEPTED]), n_attempted_trajectories=n * done,
-                           n_target_calls=target_calls, n_target_gradient_calls=grad_calls)
-        st.n_nonfinite_log_ratios = int(cnt[hip.CNT_NONFINITE])
-        st.absorb_device_sums(sum_x.reshape(es), sum_x2.reshape(es), n * done)
-        if store is not None:
-            out.running_samples.adopt_store(store, getattr(self.params, 'spill_to_host', False))
-        out.running_samples.last_sample = last_sample
-        st.update_elapsed_time(time.time() - t0)
-        out.kernel = self.kernel
-        out.kernel_events = run.kernel_events
-        if run.shard is not None:
-            run.shard.merge_statistics(st)
-        return out
+        out = MCMCOutput(es, kernel=self.kernel, store_samples=self.params.store_samples,
+                         max_samples=getattr(self.params, 'max_samples', None))
+        # dlmc.py:112 books one attempt per chain and iteration on the host
+        return run.finish(out, t0, n * done, store, n_attempted_trajectories=n * done, n_target_calls=target_calls,
+                          n_target_gradient_calls=grad_calls)

@@ -11,7 +11,7 @@ import torch
 from tqdm import tqdm
 
 from .. import hip
-from ..containers import DeviceSampleStore, MCMCOutput, NFMCKernel, NFMCParameters, Sampler
+from ..containers import MCMCOutput, NFMCKernel, NFMCParameters, Sampler
 from .common import Run, chunks, progress, resolve_target
 from .jump import (flow_is_native, flow_mh_supported, imh_parallel_ok, launch_flow_mh, launch_imh_parallel,
                    split_flow_mh)
@@ -83,15 +83,14 @@ class FixedIMH(AbstractIMH):
     def sample(self, x0, show_progress: bool = True, time_limit_seconds=None) -> MCMCOutput:
         """imh.py:200-255 on the device."""
         run = Run(self, x0)
-        n, d, event_shape = run.n, run.d, run.event_shape
-        out = MCMCOutput(event_shape, store_samples=self.params.store_samples,
+        n, event_shape = run.n, run.event_shape
+        out = MCMCOutput(event_shape, kernel=self.kernel, store_samples=self.params.store_samples,
                          max_samples=getattr(self.params, 'max_samples', None))
         flow = self.kernel.flow
         T = int(self.params.n_iterations)
         pot = resolve_target(self.target, event_shape, self.fuse, run.x)
         fused = pot is not None and flow_is_native(flow)
-        store = DeviceSampleStore(n, d, run.dev, T, getattr(self.params, 'thinning', 1),
-                                  getattr(self.params, 'max_samples', None)) if (self.params.store_samples and T > 0) else None
+        store = run.sample_store(T)
         logq = torch.empty(n, dtype=torch.float32, device=run.dev)
         fused = fused and flow_mh_supported(run, flow, pot, logq)
         t0 = time.time()
@@ -122,24 +121,7 @@ class FixedIMH(AbstractIMH):
             done += k
             bar.update(k)
         bar.close()
-        # the final-state copy and the statistics fold go out right behind the last kernel; the one device-to-host
-        # copy of the totals is the only synchronisation of the call
-        last_sample = run.x.reshape(n, *event_shape).clone()
-        sum_x, sum_x2, cnt, _jc = run.stats.host_totals()
-        st = out.statistics
-        st.update_counters(n_target_calls=2 * n * done, n_accepted_trajectories=int(cnt[hip.CNT_ACCEPTED]),
-                           n_attempted_trajectories=int(cnt[hip.CNT_ATTEMPTED]))
-        st.n_nonfinite_log_ratios = int(cnt[hip.CNT_NONFINITE])
-        st.absorb_device_sums(sum_x.reshape(event_shape), sum_x2.reshape(event_shape), n * done)
-        if store is not None:
-            out.running_samples.adopt_store(store, getattr(self.params, 'spill_to_host', False))
-        out.running_samples.last_sample = last_sample
-        st.update_elapsed_time(time.time() - t0)
-        out.kernel = self.kernel
-        out.kernel_events = run.kernel_events
-        if run.shard is not None:
-            run.shard.merge_statistics(st)
-        return out
+        return run.finish(out, t0, n * done, store, n_target_calls=2 * n * done)
 
 
 class HostDraws:
@@ -203,7 +185,7 @@ class AdaptiveIMH(AbstractIMH):
         n, d, event_shape = run.n, run.d, run.event_shape
         if run.shard is not None and run.shard.world > 1 and run.n_global % run.shard.world != 0:
             raise ValueError('adaptive_imh with sharded chains needs n_chains divisible by the number of ranks')
-        out = MCMCOutput(event_shape, store_samples=True)
+        out = MCMCOutput(event_shape, kernel=self.kernel, store_samples=True)
         flow = self.kernel.flow
         T = int(self.params.n_iterations)
         pot = resolve_target(self.target, event_shape, self.fuse, run.x)
@@ -246,22 +228,9 @@ class AdaptiveIMH(AbstractIMH):
                     flow.load_state_dict(weights)                                       # :170
             bar.update(1)
         bar.close()
-        # the final-state copy and the statistics fold go out right behind the last kernel; the one device-to-host
-        # copy of the totals is the only synchronisation of the call
-        last_sample = run.x.reshape(n, *event_shape).clone()
-        sum_x, sum_x2, cnt, _jc = run.stats.host_totals()
-        st = out.statistics
-        # imh.py:140-144 books the 2n target evaluations as gradient calls; kept
-        st.update_counters(n_target_gradient_calls=2 * n * done, n_accepted_trajectories=int(cnt[hip.CNT_ACCEPTED]),
-                           n_attempted_trajectories=int(cnt[hip.CNT_ATTEMPTED]))
-        st.n_nonfinite_log_ratios = int(cnt[hip.CNT_NONFINITE])
-        st.absorb_device_sums(sum_x.reshape(event_shape), sum_x2.reshape(event_shape), n * done)
         if done > 0:
+            # no device store: the refit draws from every state, so the run keeps them all in `buf`
             out.running_samples.add(buf[:done].reshape(done, n, *event_shape))
-        out.running_samples.last_sample = last_sample
-        st.update_elapsed_time(time.time() - t0)
         self.n_refits = n_refits
-        out.kernel = self.kernel
-        if run.shard is not None:
-            run.shard.merge_statistics(st)
-        return out
+        # imh.py:140-144 books the 2n target evaluations as gradient calls; kept
+        return run.finish(out, t0, n * done, n_target_gradient_calls=2 * n * done)

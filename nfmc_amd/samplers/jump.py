@@ -15,8 +15,8 @@ import torch
 from tqdm import tqdm
 
 from .. import hip
-from ..containers import (DeviceSampleStore, MCMCKernel, MCMCOutput, MCMCParameters, MCMCStatistics, NFMCKernel,
-                          NFMCParameters, Sampler)
+from ..containers import (MCMCKernel, MCMCOutput, MCMCParameters, MCMCStatistics, NFMCKernel, NFMCParameters,
+                          Sampler)
 from ..flows import Flow, RealNVP
 from ..tuning import train_val_split
 from ..util import metropolis_acceptance_log_ratio
@@ -98,7 +98,7 @@ def flow_mh_supported(run: Run, flow, pot, logq, adjusted=True) -> bool:
     not (e.g. ragged d > ~300: neither the weight image nor the wave tiles fit the LDS) the samplers compose the
     transition from the flow's own kernels (split_flow_mh), like for a foreign flow object."""
     a, _keep = _flow_mh_probe_args(run, flow, pot, logq, adjusted)
-    return _supported(int(hip.lib().nfmc_flow_mh_supported_f32(C.byref(a))), 'nfmc_flow_mh_supported_f32')
+    return hip.supported(int(hip.lib().nfmc_flow_mh_supported_f32(C.byref(a))), 'nfmc_flow_mh_supported_f32')
 
 
 def launch_flow_mh(run: Run, flow, pot, logq, k, step0, cached, adjusted, stats_struct, samples=None,
@@ -131,13 +131,6 @@ def _flow_mh_probe_args(run: Run, flow, pot, logq, adjusted):
     return a, _keep
 
 
-def _supported(rc, what) -> bool:
-    if rc in (hip.EUNSUPPORTED, hip.ESHAPE):   # a valid request no fused kernel covers (NfmcArgumentError.no_kernel)
-        return False
-    hip.check(rc, what)
-    return True
-
-
 def imh_parallel_ok(run: Run, flow, pot, logq) -> bool:
     """FixedIMH as a data-parallel problem (csrc/imh_parallel.hip): register-layout flows whose weight image fits the
     LDS (nfmc_imh_parallel_supported_f32 decides).  It wins most when the chains alone do not fill the GPU (sequential
@@ -150,7 +143,7 @@ def imh_parallel_ok(run: Run, flow, pot, logq) -> bool:
     if os.environ.get('NFMC_IMH_PARALLEL') == '0':
         return False
     a, _keep = _flow_mh_probe_args(run, flow, pot, logq, True)
-    return _supported(int(hip.lib().nfmc_imh_parallel_supported_f32(C.byref(a))), 'nfmc_imh_parallel_supported_f32')
+    return hip.supported(int(hip.lib().nfmc_imh_parallel_supported_f32(C.byref(a))), 'nfmc_imh_parallel_supported_f32')
 
 
 def launch_imh_parallel(run: Run, flow, pot, logq, k, step0, cached, stats_struct, samples=None, masks_out=None,
@@ -310,10 +303,9 @@ class JumpNFMC(Sampler):
         inner._n_divergences = 0
         jump_target_calls = 0
 
-        # kept states of the whole run, T * (K + 1) offered: thinning / max_samples applied on the device (f3).  With
-        # fit_nf the inner states of one outer iteration are also needed as a dense block for the refit (fit_buf).
-        store = DeviceSampleStore(n, d, run.dev, T * (K + 1), getattr(self.params, 'thinning', 1),
-                                  getattr(self.params, 'max_samples', None)) if (self.params.store_samples and T > 0) else None
+        # kept states of the whole run, T * (K + 1) offered.  With fit_nf the inner states of one outer iteration are
+        # also needed as a dense block for the refit (fit_buf).
+        store = run.sample_store(T * (K + 1))
         fit_buf = torch.empty(K, n, d, dtype=torch.float32, device=run.dev) if self.params.fit_nf else None
         pending_fit = None     # the latest refit's deferred check (flow_training.PendingFit)
         logq = torch.empty(n, dtype=torch.float32, device=run.dev)
@@ -392,35 +384,17 @@ class JumpNFMC(Sampler):
                 run.sync()
                 bar.set_postfix_str(f'acc {int(run.stats.counters[hip.CNT_ACCEPTED])}/'
                                     f'{int(run.stats.counters[hip.CNT_ATTEMPTED])}')
-        # end of the call, ordered for the GPU: the copy of the final state and the statistics fold are enqueued right
-        # behind the last kernel, and the one device-to-host copy of the totals is the only synchronisation (with a
-        # synchronize first, then the fold, then host work, then the clone, the stream sat idle ~110 us per call)
         if pending_fit is not None:
             pending_fit.result()
-        last_sample = run.x.reshape(n, *event_shape).clone()
         inner._cur_run = None
-        sum_x, sum_x2, cnt, jc = run.stats.host_totals()
         calls, grads = inner._counts(n, K * done)
-        out = JumpNFMCOutput(event_shape, store_samples=self.params.store_samples,
+        out = JumpNFMCOutput(event_shape, kernel=self.kernel, store_samples=self.params.store_samples,
                              max_samples=getattr(self.params, 'max_samples', None))
-        st = out.statistics
-        st.update_counters(n_accepted_trajectories=int(cnt[hip.CNT_ACCEPTED]),
-                           n_attempted_trajectories=int(cnt[hip.CNT_ATTEMPTED]),
-                           n_divergences=inner._n_divergences,      # jump.py:183: the inner sampler's failed steps
-                           n_target_calls=calls + jump_target_calls,
-                           n_target_gradient_calls=grads,
-                           n_accepted_jumps=int(jc[hip.CNT_ACCEPTED]), n_attempted_jumps=n * done)
-        st.n_nonfinite_log_ratios = int(cnt[hip.CNT_NONFINITE]) + int(jc[hip.CNT_NONFINITE])
-        st.absorb_device_sums(sum_x.reshape(event_shape), sum_x2.reshape(event_shape), n * done * (K + 1))
-        if store is not None:
-            out.running_samples.adopt_store(store, getattr(self.params, 'spill_to_host', False))
-        out.running_samples.last_sample = last_sample
-        st.update_elapsed_time(time.time() - t0)
-        out.kernel = self.kernel
-        out.kernel_events = run.kernel_events
-        if run.shard is not None:
-            run.shard.merge_statistics(st)
-        return out
+        # jump.py:183: the divergences are the inner sampler's failed steps; every chain attempts one jump per iteration
+        # and offers K + 1 states to the moments
+        return run.finish(out, t0, n * done * (K + 1), store, n_divergences=inner._n_divergences,
+                          n_target_calls=calls + jump_target_calls, n_target_gradient_calls=grads,
+                          n_attempted_jumps=n * done)
 
 
 def _make(inner_cls):

@@ -18,7 +18,7 @@ import torch
 from tqdm import tqdm
 
 from .. import hip
-from ..containers import DeviceSampleStore, MCMCKernel, MCMCOutput, MCMCParameters, Sampler
+from ..containers import MCMCKernel, MCMCOutput, MCMCParameters, Sampler
 from ..tuning import DualAveraging, DualAveragingParams
 from .common import Run, chunks, imd_tensor, progress, resolve_target
 
@@ -204,16 +204,14 @@ class MCMCSampler(Sampler):
         """mcmc/base.py:56-102 on the device."""
         run = Run(self, x0)
         step0 = 0
-        n, d = run.n, run.d
+        n = run.n
         event_shape = run.event_shape
-        out = MCMCOutput(event_shape, store_samples=self.params.store_samples,
+        out = MCMCOutput(event_shape, kernel=self.kernel, store_samples=self.params.store_samples,
                          max_samples=getattr(self.params, 'max_samples', None))
         out.statistics.data_transform = self.data_transform
         K = int(self.params.n_iterations)
         pot = resolve_target(self.target, event_shape, self.fuse, run.x)
-        # kept states: thinning / max_samples window applied on the device, slab bounded by max_samples (f3)
-        store = DeviceSampleStore(n, d, run.dev, K, getattr(self.params, 'thinning', 1),
-                                  getattr(self.params, 'max_samples', None)) if (self.params.store_samples and K > 0) else None
+        store = run.sample_store(K)
         run.stats.zero_()
         self._n_divergences = 0
         t0 = time.time()
@@ -254,30 +252,13 @@ class MCMCSampler(Sampler):
             done += k
             bar.update(k)
         bar.close()
-        # the final-state copy and the statistics fold go out right behind the last kernel; the one device-to-host
-        # copy of the totals is the only synchronisation of the call
-        last_sample = run.x.reshape(n, *event_shape).clone()
-        if tune is not None:
-            tune.download(self.kernel)
-        sum_x, sum_x2, cnt, _jc = run.stats.host_totals()
         calls, grads = self._counts(n, done)
-        out.statistics.update_counters(n_target_calls=calls, n_target_gradient_calls=grads,
-                                       n_divergences=self._n_divergences,
-                                       n_accepted_trajectories=int(cnt[hip.CNT_ACCEPTED]),
-                                       n_attempted_trajectories=int(cnt[hip.CNT_ATTEMPTED]))
-        out.statistics.n_nonfinite_log_ratios = int(cnt[hip.CNT_NONFINITE])
-        out.statistics.absorb_device_sums(sum_x.reshape(event_shape), sum_x2.reshape(event_shape),
-                                          n * done)
-        rs = out.running_samples
-        if store is not None:
-            rs.adopt_store(store, getattr(self.params, 'spill_to_host', False))
-        rs.last_sample = last_sample
-        out.statistics.update_elapsed_time(time.time() - t0)
-        out.kernel = self.kernel
-        out.kernel_events = run.kernel_events
+        run.finish(out, t0, n * done, store, n_target_calls=calls, n_target_gradient_calls=grads,
+                   n_divergences=self._n_divergences)
+        if tune is not None:
+            # tuning launches fold their statistics per call: the controller state was final before the finish
+            tune.download(self.kernel)
         self._cur_run = None
-        if run.shard is not None:
-            run.shard.merge_statistics(out.statistics)
         return out
 
     def _rejected_step(self, xf, n_calls, n_grads):

@@ -17,7 +17,7 @@ import torch
 from tqdm import tqdm
 
 from .. import hip
-from ..containers import DeviceSampleStore, MCMCOutput, NFMCKernel, NFMCParameters, Sampler
+from ..containers import MCMCOutput, NFMCKernel, NFMCParameters, Sampler
 from .common import Run, chunks, imd_tensor, progress, resolve_target
 from .mcmc import (HMC, MH, HMCKernel, HMCParameters, MHKernel, MHParameters, MetropolisKernel, MetropolisParameters,
                    MetropolisSampler)
@@ -163,11 +163,10 @@ class NeuTra(Sampler):
 
         if not isinstance(inner, HMC) or pot is None or not self._flow_on_kernels():
             return split()
-        out = MCMCOutput(event_shape, store_samples=self.params.store_samples,
+        out = MCMCOutput(event_shape, kernel=inner.kernel, store_samples=self.params.store_samples,
                          max_samples=getattr(self.params, 'max_samples', None))
         T = int(self.params.n_iterations)
-        store = DeviceSampleStore(n, d, run.dev, T, getattr(self.params, 'thinning', 1),
-                                  getattr(self.params, 'max_samples', None)) if (self.params.store_samples and T > 0) else None
+        store = run.sample_store(T)
         st_flow, _keep = self.kernel.flow.bijection.packed(run.dev, self._min_hidden())
         imd = imd_tensor(inner.kernel, run.dev)
         bij = self.kernel.flow.bijection
@@ -210,26 +209,9 @@ class NeuTra(Sampler):
             done += k
             bar.update(k)
         bar.close()
-        # the final-state copy and the statistics fold go out right behind the last kernel; the one device-to-host
-        # copy of the totals is the only synchronisation of the call
-        last_sample = run.x.reshape(n, *event_shape).clone()
-        sum_x, sum_x2, cnt, _jc = run.stats.host_totals()
         calls, grads = inner._counts(n, done)
-        st = out.statistics
-        st.update_counters(n_target_calls=calls, n_target_gradient_calls=grads,
-                           n_accepted_trajectories=int(cnt[hip.CNT_ACCEPTED]),
-                           n_attempted_trajectories=int(cnt[hip.CNT_ATTEMPTED]))
-        st.n_nonfinite_log_ratios = int(cnt[hip.CNT_NONFINITE])
-        st.absorb_device_sums(sum_x.reshape(event_shape), sum_x2.reshape(event_shape), n * done)
-        if store is not None:
-            out.running_samples.adopt_store(store, getattr(self.params, 'spill_to_host', False))
-        out.running_samples.last_sample = last_sample
-        st.update_elapsed_time(time.time() - t0)
-        out.kernel = inner.kernel
+        run.finish(out, t0, n * done, store, n_target_calls=calls, n_target_gradient_calls=grads)
         out.kernel.flow = self.kernel.flow  # neutra.py:128
-        out.kernel_events = run.kernel_events
-        if run.shard is not None:
-            run.shard.merge_statistics(st)
         return out
 
 
