@@ -45,12 +45,21 @@ enum {
  * Replaces `self.target(x)` + `torch.autograd.grad` (langevin.py:66-68,80-82; hmc.py:40-48). */
 enum {
     NFMC_POT_QUADRATIC = 0, /* U = sum_j a_j (x_j - b_j)^2 ; a,b per coordinate or scalar */
-    NFMC_POT_FUNNEL = 1     /* U = x_0^2/(2 s^2) + sum_{i>=1} [x_i^2 / (2 e^{x_0}) + x_0/2], s = a_scalar */
+    NFMC_POT_FUNNEL = 1,    /* U = x_0^2/(2 s^2) + sum_{i>=1} [x_i^2 / (2 e^{x_0}) + x_0/2], s = a_scalar */
+    NFMC_POT_GAUSSIAN_MIXTURE = 2
+    /* Diagonal Gaussian mixture of K = n_components components:
+         U = -logsumexp_k [ c_k - 1/2 sum_j lam_kj (x_j - mu_kj)^2 ],  lam_kj = 1/sigma_kj^2,
+         c_k = log w_k + 1/2 sum_j log lam_kj   (the constant d/2 log 2 pi is dropped)
+       a -> fp32 block [lam (K, d) row-major | c (K)],  b -> means mu (K, d) row-major; both device memory, 16-byte
+       aligned; a_scalar / b_scalar unused.  K <= 8, and the kernel stages 2 K padded_d(d) floats of it in LDS beside its
+       flow image: a larger K, or a block that does not fit, gets NFMC_EUNSUPPORTED.  Served by nfmc_mala_steps_f32 /
+       nfmc_hmc_steps_f32 (general kernels, with or without a jump tail; not the Philox4x32-7 stream) and by the
+       register-layout kernels of nfmc_flow_mh_steps_f32; every other entry point answers NFMC_EUNSUPPORTED. */
 };
 
 typedef struct {
     int32_t kind;
-    int32_t reserved;
+    int32_t n_components; /* NFMC_POT_GAUSSIAN_MIXTURE: K; 0 for the other kinds (was `reserved`, same layout) */
     const float* a; /* (d,) or NULL -> a_scalar */
     const float* b; /* (d,) or NULL -> b_scalar */
     float a_scalar;

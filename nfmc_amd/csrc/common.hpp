@@ -232,6 +232,7 @@ template <int CPL, int LPC, bool FAST>
 struct QuadraticPot {
     // U = sum a_c (x_c - b_c)^2
     static constexpr bool kQuadratic = true;
+    static constexpr bool kStaged = false;   // parameters in registers (no LDS block, see MixturePot)
     float a_s, b_s;
     float a[FAST ? 1 : CPL], b[FAST ? 1 : CPL];
     struct Ctx {};
@@ -263,6 +264,7 @@ template <int CPL, int LPC, bool FAST>
 struct FunnelPot {
     // U = x0^2/(2 s^2) + sum_{i>=1} [ x_i^2 e^{-x0} / 2 + x0 / 2 ]
     static constexpr bool kQuadratic = false;
+    static constexpr bool kStaged = false;
     float inv_s2, half_dm1;
     bool lead;          // this lane holds coordinate 0 in register 0
     float valid[CPL];   // 1 for real coordinates, 0 for padding
@@ -296,6 +298,135 @@ struct FunnelPot {
         return (lead && i == 0) ? t0 : 0.5f * c.e * x * x;
     }
 };
+
+// Diagonal Gaussian mixture (NFMC_POT_GAUSSIAN_MIXTURE, K = p.n_components <= kMixMaxK):
+//   U = -logsumexp_k [ c_k - 1/2 sum_j lam_kj (x_j - mu_kj)^2 ]
+//   dU/dx_j = sum_k r_k lam_kj (x_j - mu_kj),   r_k = softmax_k(e_k)
+// Every chain group of a workgroup reads the same (lam, mu) rows, so they are staged ONCE per workgroup in LDS
+// (stage(), before init()), padded to the layout's DP coordinates with lam = mu = 0 -- padding lanes then add exactly
+// zero to every sum and get a zero gradient.  A lane reads its register quad q of row k as one ds_read_b128 at
+// coordinate 4 (q LPC + g): consecutive lanes read consecutive 16 bytes, the chain groups of a wave the same ones
+// (broadcast).  The c_k are wave-uniform and stay in registers.  prepare() does K group reductions (one butterfly
+// each), the logsumexp on the fast exp2 / log2 helpers, and the gradient of the lane's coordinates in a second pass
+// over the rows; term() puts the whole U on coordinate 0 of lane 0 (the FunnelPot trick).
+constexpr int kMixMaxK = 8;
+
+__host__ __device__ inline int mixture_floats(int k, int dp) { return 2 * k * dp; }
+
+// argument check of a kind-2 descriptor at the entry points that run it (0 for every other kind)
+inline int check_mixture(const NfmcPotential& p) {
+    if (p.kind != NFMC_POT_GAUSSIAN_MIXTURE) return NFMC_OK;
+    if (!p.a || !p.b || p.n_components < 1) return NFMC_EINVAL;
+    if ((((uintptr_t)p.a) & 15u) != 0 || (((uintptr_t)p.b) & 15u) != 0) return NFMC_EALIGN;
+    if (p.n_components > kMixMaxK) return NFMC_EUNSUPPORTED;
+    return NFMC_OK;
+}
+
+// LDS bytes a register-layout kernel with DP padded coordinates stages for `p` beside its flow image (0 unless kind 2)
+inline size_t staged_potential_bytes(const NfmcPotential& p, int dp) {
+    return p.kind == NFMC_POT_GAUSSIAN_MIXTURE ? (size_t)mixture_floats(p.n_components, dp) * sizeof(float) : 0;
+}
+
+template <int CPL, int LPC, bool FAST>
+struct MixturePot {
+    static constexpr bool kQuadratic = false;
+    static constexpr bool kStaged = true;
+    static constexpr int DP = CPL * LPC;
+    const float* tab;     // LDS: lam (K, DP) | mu (K, DP)
+    float c[kMixMaxK];    // log w_k + 1/2 sum_j log lam_kj
+    int nk;
+    bool lead;            // this lane holds coordinate 0 in register 0
+    struct Ctx {
+        float u;          // U of the chain (every lane of the group)
+        float gr[CPL];    // dU/dx of this lane's coordinates
+    };
+
+    // all threads of the workgroup; the caller synchronises before the first prepare()
+    __device__ __forceinline__ static void stage(float* __restrict__ lds, const NfmcPotential& p, int d) {
+        const int kd = p.n_components * DP;
+        for (int t = threadIdx.x; t < 2 * kd; t += kBlock) {
+            const int half = t >= kd, r = half ? t - kd : t;
+            const int k = r / DP, j = r - k * DP;
+            lds[t] = j < d ? (half ? p.b : p.a)[(int64_t)k * d + j] : 0.f;
+        }
+    }
+    __device__ __forceinline__ void init(const NfmcPotential& p, int g, int d, const float* lds) {
+        tab = lds;
+        nk = p.n_components;
+        lead = (g == 0);
+#pragma unroll
+        for (int k = 0; k < kMixMaxK; ++k) c[k] = k < nk ? p.a[(int64_t)nk * d + k] : 0.f;
+    }
+    __device__ __forceinline__ float4 row4(int k, int half, int q, int g) const {
+        return *reinterpret_cast<const float4*>(tab + (half * nk + k) * DP + 4 * (q * LPC + g));
+    }
+    __device__ __forceinline__ Ctx prepare(const float (&x)[CPL], int g, int) const {
+        float e[kMixMaxK];
+        float m = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < kMixMaxK; ++k) {
+            e[k] = -INFINITY;
+            if (k < nk) {
+                float s = 0.f;
+#pragma unroll
+                for (int q = 0; q < CPL / 4; ++q) {
+                    const float4 l = row4(k, 0, q, g), mu = row4(k, 1, q, g);
+                    const float t0 = x[4 * q] - mu.x, t1 = x[4 * q + 1] - mu.y, t2 = x[4 * q + 2] - mu.z,
+                                t3 = x[4 * q + 3] - mu.w;
+                    s = fmaf(l.x * t0, t0, s);
+                    s = fmaf(l.y * t1, t1, s);
+                    s = fmaf(l.z * t2, t2, s);
+                    s = fmaf(l.w * t3, t3, s);
+                }
+                e[k] = fmaf(-0.5f, group_allreduce<LPC>(s), c[k]);
+                m = fmaxf(m, e[k]);
+            }
+        }
+        float w[kMixMaxK], sum = 0.f;
+#pragma unroll
+        for (int k = 0; k < kMixMaxK; ++k) {
+            w[k] = k < nk ? fast_exp(e[k] - m) : 0.f;   // e_k - m <= 0: no overflow; NaN propagates through sum
+            sum += w[k];
+        }
+        Ctx cx;
+        cx.u = -(m + fast_ln(sum));
+        const float inv = 1.f / sum;
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) cx.gr[i] = 0.f;
+#pragma unroll
+        for (int k = 0; k < kMixMaxK; ++k) {
+            if (k < nk) {
+                const float r = w[k] * inv;
+#pragma unroll
+                for (int q = 0; q < CPL / 4; ++q) {
+                    const float4 l = row4(k, 0, q, g), mu = row4(k, 1, q, g);
+                    cx.gr[4 * q] = fmaf(r * l.x, x[4 * q] - mu.x, cx.gr[4 * q]);
+                    cx.gr[4 * q + 1] = fmaf(r * l.y, x[4 * q + 1] - mu.y, cx.gr[4 * q + 1]);
+                    cx.gr[4 * q + 2] = fmaf(r * l.z, x[4 * q + 2] - mu.z, cx.gr[4 * q + 2]);
+                    cx.gr[4 * q + 3] = fmaf(r * l.w, x[4 * q + 3] - mu.w, cx.gr[4 * q + 3]);
+                }
+            }
+        }
+        return cx;
+    }
+    __device__ __forceinline__ float grad(const Ctx& cx, int i, float) const { return cx.gr[i]; }
+    __device__ __forceinline__ float term(const Ctx& cx, int i, float) const { return (lead && i == 0) ? cx.u : 0.f; }
+};
+
+// Potentials with an LDS block (kStaged) stage it behind the `img_floats` floats of flow image a kernel keeps at the
+// start of its dynamic LDS (16-byte aligned), synchronise the workgroup and bind to it.  lds_with_potential() is the
+// host side: the kernel's dynamic LDS bytes for an image of `img_bytes`.
+template <class P>
+__device__ __forceinline__ void init_staged(P& pot, const NfmcPotential& p, int g, int d, float* lds, int img_floats) {
+    float* blk = lds + ((img_floats + 3) & ~3);
+    P::stage(blk, p, d);
+    __syncthreads();
+    pot.init(p, g, d, blk);
+}
+inline size_t lds_with_potential(size_t img_bytes, const NfmcPotential& p, int dp) {
+    const size_t blk = staged_potential_bytes(p, dp);
+    return blk ? ((img_bytes + 15) & ~(size_t)15) + blk : img_bytes;
+}
 
 // ------------------------------------------------------------------------------------------------
 // Row IO: register quad q of lane g <-> the 16 bytes at coordinate 4 * (q * LPC + g) of the row.

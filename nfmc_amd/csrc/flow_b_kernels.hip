@@ -28,7 +28,10 @@ __global__ void __launch_bounds__(kBlock, NFMC_FLOWB_WPE) flow_mh_b_kernel(NfmcF
     Flow fl;
     fl.init(lds, a.flow, g);
     Pot<CPL, LPC, FAST> pot;
-    pot.init(a.pot, g, d);
+    if constexpr (Pot<CPL, LPC, FAST>::kStaged)
+        init_staged(pot, a.pot, g, d, lds, Flow::Img::total_floats(a.flow.n_hidden_layers, a.flow.n_coupling));
+    else
+        pot.init(a.pot, g, d);
     const bool revl = (a.flow.n_coupling & 1) != 0;
     const float base_c = -0.5f * (float)d * kLog2Pi;
 
@@ -292,8 +295,9 @@ template <int CPL, int LPC, int HP>
 static int launch_b_rqs(const NfmcFlowMhArgs& a, bool fast, int64_t tiles, int grid, hipStream_t st, bool dry) {
 #define NFMC_LBR(POT, F)                                                                                          \
     {                                                                                                             \
-        const size_t lds = (size_t)FlowImage<CPL, LPC, HP, (F && CPL >= 8), kRqsBins>::total_floats(a.flow.n_hidden_layers, \
+        const size_t img = (size_t)FlowImage<CPL, LPC, HP, (F && CPL >= 8), kRqsBins>::total_floats(a.flow.n_hidden_layers, \
                                                                                                  a.flow.n_coupling) * sizeof(float); \
+        const size_t lds = lds_with_potential(img, a.pot, CPL * LPC);                                             \
         if (lds > 120 * 1024) return NFMC_EUNSUPPORTED;                                                           \
         if (rng_rounds(a.rng) == 7) return NFMC_EUNSUPPORTED;                                                     \
         if (dry) return 0;                                                                                        \
@@ -305,7 +309,8 @@ static int launch_b_rqs(const NfmcFlowMhArgs& a, bool fast, int64_t tiles, int g
         }                                                                                                         \
         hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, a, tiles);                                    \
     }
-    if (a.pot.kind == NFMC_POT_FUNNEL) NFMC_LBR(FunnelPot, false)
+    if (a.pot.kind == NFMC_POT_GAUSSIAN_MIXTURE) NFMC_LBR(MixturePot, false)
+    else if (a.pot.kind == NFMC_POT_FUNNEL) NFMC_LBR(FunnelPot, false)
     else if (fast) NFMC_LBR(QuadraticPot, true)
     else NFMC_LBR(QuadraticPot, false)
 #undef NFMC_LBR
@@ -316,8 +321,9 @@ template <int CPL, int LPC, int HP>
 static int launch_b(const NfmcFlowMhArgs& a, bool fast, int64_t tiles, int grid, hipStream_t st, bool dry) {
 #define NFMC_LB(POT, F)                                                                                         \
     {                                                                                                           \
-        const size_t lds = (size_t)FlowImage<CPL, LPC, HP, (F && CPL >= 8)>::total_floats(a.flow.n_hidden_layers, \
+        const size_t img = (size_t)FlowImage<CPL, LPC, HP, (F && CPL >= 8)>::total_floats(a.flow.n_hidden_layers, \
                                                                                        a.flow.n_coupling) * sizeof(float); \
+        const size_t lds = lds_with_potential(img, a.pot, CPL * LPC);                                           \
         if (lds > 120 * 1024) return NFMC_EUNSUPPORTED;                                                         \
         if (dry) return 0;                                                                                      \
         const bool diag = !F || wants_diag(a);                                                                  \
@@ -334,7 +340,8 @@ static int launch_b(const NfmcFlowMhArgs& a, bool fast, int64_t tiles, int grid,
         }                                                                                                       \
         hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, a, tiles);                                  \
     }
-    if (a.pot.kind == NFMC_POT_FUNNEL) NFMC_LB(FunnelPot, false)
+    if (a.pot.kind == NFMC_POT_GAUSSIAN_MIXTURE) NFMC_LB(MixturePot, false)
+    else if (a.pot.kind == NFMC_POT_FUNNEL) NFMC_LB(FunnelPot, false)
     else if (fast) NFMC_LB(QuadraticPot, true)
     else NFMC_LB(QuadraticPot, false)
 #undef NFMC_LB

@@ -192,7 +192,7 @@ __global__ void __launch_bounds__(kBlock, NFMC_WPE) mala_kernel(NfmcMalaArgs a, 
     MassCoef<CPL, LPC, FAST> mc;
     mc.init(h, sqrt2h, a.inv_mass_diag, g, d, rw);
     Pot<CPL, LPC, FAST> pot;
-    pot.init(a.pot, g, d);
+    if constexpr (!Pot<CPL, LPC, FAST>::kStaged) pot.init(a.pot, g, d);
     if constexpr (Pot<CPL, LPC, FAST>::kQuadratic) mc.init_quadratic(pot, rw);
     FlowB<CPL, LPC, JHP == 0 ? 4 : JHP, true, (FAST && CPL >= 8 && JHP > 0)> fl;
     if constexpr (JHP > 0) {
@@ -200,6 +200,9 @@ __global__ void __launch_bounds__(kBlock, NFMC_WPE) mala_kernel(NfmcMalaArgs a, 
         __syncthreads();
         fl.init(flow_lds, jd.flow, g);
     }
+    if constexpr (Pot<CPL, LPC, FAST>::kStaged)
+        init_staged(pot, a.pot, g, d, flow_lds,
+                    JHP > 0 ? decltype(fl)::Img::total_floats(jd.flow.n_hidden_layers, jd.flow.n_coupling) : 0);
 
     float sx[CPL], sxx[CPL];
 #pragma unroll
@@ -333,13 +336,16 @@ __global__ void __launch_bounds__(kBlock, NFMC_WPE) hmc_kernel(NfmcHmcArgs a, in
     MassCoef<CPL, LPC, FAST> mc;
     mc.init(h, 0.f, a.inv_mass_diag, g, d);
     Pot<CPL, LPC, FAST> pot;
-    pot.init(a.pot, g, d);
+    if constexpr (!Pot<CPL, LPC, FAST>::kStaged) pot.init(a.pot, g, d);
     FlowB<CPL, LPC, JHP == 0 ? 4 : JHP, true, (FAST && CPL >= 8 && JHP > 0)> fl;
     if constexpr (JHP > 0) {
         decltype(fl)::Img::stage(flow_lds, jd.flow, kBlock);
         __syncthreads();
         fl.init(flow_lds, jd.flow, g);
     }
+    if constexpr (Pot<CPL, LPC, FAST>::kStaged)
+        init_staged(pot, a.pot, g, d, flow_lds,
+                    JHP > 0 ? decltype(fl)::Img::total_floats(jd.flow.n_hidden_layers, jd.flow.n_coupling) : 0);
 
     float sx[CPL], sxx[CPL];
 #pragma unroll
@@ -477,6 +483,7 @@ int launch_mala_cfg(const NfmcMalaArgs& a, const JumpDev& jd, bool fast, int64_t
     size_t lds = 0;
     if constexpr (JHP > 0)
         lds = (size_t)FlowImage<CPL, LPC, JHP>::total_floats(jd.flow.n_hidden_layers, jd.flow.n_coupling) * sizeof(float);
+    lds = lds_with_potential(lds, a.pot, CPL * LPC);   // the mixture's parameter block behind the image
     if (lds > 120 * 1024) return NFMC_EUNSUPPORTED;
 #define NFMC_L(POT, F)                                                                                            \
     {                                                                                                             \
@@ -497,7 +504,9 @@ int launch_mala_cfg(const NfmcMalaArgs& a, const JumpDev& jd, bool fast, int64_t
         }
         return NFMC_EUNSUPPORTED;
     }
-    if (a.pot.kind == NFMC_POT_FUNNEL) {
+    if (a.pot.kind == NFMC_POT_GAUSSIAN_MIXTURE) {   // never exact-fit: a and b are tables
+        NFMC_L(MixturePot, false)
+    } else if (a.pot.kind == NFMC_POT_FUNNEL) {
         if (fast) NFMC_L(FunnelPot, true) else NFMC_L(FunnelPot, false)
     } else {
         if (fast) NFMC_L(QuadraticPot, true) else NFMC_L(QuadraticPot, false)
@@ -511,6 +520,7 @@ int launch_hmc_cfg(const NfmcHmcArgs& a, const JumpDev& jd, bool fast, int64_t t
     size_t lds = 0;
     if constexpr (JHP > 0)
         lds = (size_t)FlowImage<CPL, LPC, JHP>::total_floats(jd.flow.n_hidden_layers, jd.flow.n_coupling) * sizeof(float);
+    lds = lds_with_potential(lds, a.pot, CPL * LPC);   // the mixture's parameter block behind the image
     if (lds > 120 * 1024) return NFMC_EUNSUPPORTED;
 #define NFMC_L(POT, F)                                                                                            \
     {                                                                                                             \
@@ -531,7 +541,9 @@ int launch_hmc_cfg(const NfmcHmcArgs& a, const JumpDev& jd, bool fast, int64_t t
         }
         return NFMC_EUNSUPPORTED;
     }
-    if (a.pot.kind == NFMC_POT_FUNNEL) {
+    if (a.pot.kind == NFMC_POT_GAUSSIAN_MIXTURE) {   // never exact-fit: a and b are tables
+        NFMC_L(MixturePot, false)
+    } else if (a.pot.kind == NFMC_POT_FUNNEL) {
         if (fast) NFMC_L(FunnelPot, true) else NFMC_L(FunnelPot, false)
     } else {
         if (fast) NFMC_L(QuadraticPot, true) else NFMC_L(QuadraticPot, false)

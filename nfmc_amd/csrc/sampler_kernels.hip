@@ -40,7 +40,9 @@ static int check_common(const Args* a) {
     if (a->n_steps > NFMC_MAX_STEPS_PER_CALL) return NFMC_ESHAPE;
     if (a->d > 1024) return NFMC_ESHAPE;
     if (!(a->step_size > 0.f)) return NFMC_EINVAL;
-    if (a->pot.kind != NFMC_POT_QUADRATIC && a->pot.kind != NFMC_POT_FUNNEL) return NFMC_EUNSUPPORTED;
+    if (a->pot.kind != NFMC_POT_QUADRATIC && a->pot.kind != NFMC_POT_FUNNEL && a->pot.kind != NFMC_POT_GAUSSIAN_MIXTURE)
+        return NFMC_EUNSUPPORTED;
+    if (int rc = check_mixture(a->pot)) return rc;
     if (((uintptr_t)a->x & 3u) != 0) return NFMC_EALIGN;
     if (!store_ok(a->samples)) return NFMC_EINVAL;
     if (!rng_rounds_ok(a->rng, true)) return NFMC_EINVAL;

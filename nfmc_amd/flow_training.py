@@ -622,6 +622,7 @@ def variational_fit(flow, log_prob_fn, n_epochs: int = 500, lr: float = 0.05, n_
     n_samples = max(int(n_samples), 1)
     import os
     if (potential is not None and os.environ.get('NFMC_FIT_TORCH') != '1' and hasattr(potential, 'descriptor')
+            and (not hasattr(potential, 'fused_in') or potential.fused_in('fit'))   # the fit kernels' kinds only
             and int(getattr(potential, 'event_size', -1)) == d and DeviceFit.supported(flow.bijection, dev)):
         _variational_fit_device(flow, potential, dev, n_epochs, lr, n_samples, early_stopping, early_stopping_threshold,
                                 keep_best_weights, check_for_divergences, time_limit_seconds)

@@ -22,6 +22,16 @@ import torch
 from . import hip
 
 
+# Launch families a closed-form potential can be routed to (Potential.fused_in):
+#   'mcmc'          mala / ula / mh / hmc / uhmc, device warmup tuning, the jump_* inner loop and its fused jump tail
+#   'flow_mh'       the flow-MH step of imh / adaptive_imh / jump_* / dlmc (nfmc_flow_mh_steps_f32)
+#   'imh_parallel'  the data-parallel FixedIMH kernel (nfmc_imh_parallel_f32)
+#   'neutra'        the NeuTra gradient and HMC kernels
+#   'dlmc_step'     dlmc's fused gradient step (nfmc_dlmc_step_f32)
+#   'fit'           the device variational fit (nfmc_flow_variational_fit_step_f32)
+FAMILIES = ('mcmc', 'flow_mh', 'imh_parallel', 'neutra', 'dlmc_step', 'fit')
+
+
 class Potential:
     """Base: `event_shape`, `__call__(x) -> (n,)` in torch ops, `descriptor(device)` for the kernels."""
 
@@ -32,6 +42,14 @@ class Potential:
 
     def descriptor(self, device) -> hip.NfmcPotential:
         raise NotImplementedError
+
+    def fused_in(self, family: str) -> bool:
+        """Whether the kernels of launch family `family` (FAMILIES) may be handed this potential's descriptor.  False
+        sends the family to the split or composed path, exactly as for an arbitrary callable.  The quadratic and funnel
+        kinds answer True everywhere: their kernels decide by themselves, as before."""
+        if family not in FAMILIES:
+            raise ValueError('unknown launch family %r (one of %s)' % (family, ', '.join(FAMILIES)))
+        return True
 
     @property
     def event_size(self):
@@ -123,6 +141,96 @@ class Funnel(Potential):
 
     def descriptor(self, device):
         return hip.NfmcPotential(hip.POT_FUNNEL, 0, None, None, self.scale, 0.0)
+
+
+class GaussianMixture(Potential):
+    """Diagonal Gaussian mixture:  U(x) = -logsumexp_k [ c_k - 1/2 sum_j lam_kj (x_j - mu_kj)^2 ],
+    lam_kj = 1 / sigma_kj^2,  c_k = log w_k + 1/2 sum_j log lam_kj  (the constant d/2 log 2 pi is dropped).
+
+    means (K, *event_shape) or (K, d); scales (standard deviations) a scalar, (K,) or (K, d); weights None (uniform) or
+    (K,), normalised here.  The fused kernels take K <= 8 (hip.MIXTURE_MAX_COMPONENTS) in the mcmc and flow-MH launch
+    families; every other family, and a larger K, runs on the split or composed path (`fused_in`)."""
+
+    def __init__(self, event_shape, means, scales=1.0, weights=None):
+        if isinstance(event_shape, int):
+            event_shape = (event_shape,)
+        self.event_shape = tuple(event_shape)
+        d = self.event_size
+        mu = torch.as_tensor(means, dtype=torch.float64)
+        if mu.dim() < 1 or mu.shape[0] < 1:
+            raise ValueError('means must have a leading component axis with K >= 1 entries')
+        K = int(mu.shape[0])
+        if mu[0].numel() != d or (tuple(mu.shape[1:]) not in (self.event_shape, (d,))):
+            raise ValueError('means must be (K, *event_shape) or (K, d), got %s' % (tuple(mu.shape),))
+        mu = mu.reshape(K, d)
+        sg = torch.as_tensor(scales, dtype=torch.float64)
+        if sg.dim() == 0:
+            sg = sg.expand(K, d)
+        elif tuple(sg.shape) == (K,):
+            sg = sg[:, None].expand(K, d)
+        elif sg.shape[0] == K and sg[0].numel() == d:
+            sg = sg.reshape(K, d)
+        else:
+            raise ValueError('scales must be a scalar, (K,) or (K, d), got %s' % (tuple(sg.shape),))
+        if weights is None:
+            w = torch.full((K,), 1.0 / K, dtype=torch.float64)
+        else:
+            w = torch.as_tensor(weights, dtype=torch.float64).reshape(-1)
+            if w.numel() != K:
+                raise ValueError('weights must have K = %d entries' % K)
+        for name, v in (('means', mu), ('scales', sg), ('weights', w)):
+            if not bool(torch.isfinite(v).all()):
+                raise ValueError('%s must be finite' % name)
+        if not bool((sg > 0).all()):
+            raise ValueError('scales must be positive')
+        if not bool((w > 0).all()):
+            raise ValueError('weights must be positive')
+        w = w / w.sum()
+        lam = 1.0 / (sg * sg)
+        self.n_components = K
+        self.means = mu.contiguous()                                   # (K, d), fp64 masters; the kernels get fp32
+        self.lam = lam.contiguous()                                    # (K, d)
+        self.weights = w
+        self.log_norm = torch.log(w) + 0.5 * torch.log(lam).sum(1)   # c_k
+        self._dev = {}
+
+    def fused_in(self, family: str) -> bool:
+        return super().fused_in(family) and family in ('mcmc', 'flow_mh') and \
+            self.n_components <= hip.MIXTURE_MAX_COMPONENTS
+
+    def packed(self):
+        """The descriptor's two blocks on the host: a = [lam (K, d) row-major | c (K)], b = means (K, d) row-major."""
+        return torch.cat([self.lam.reshape(-1), self.log_norm]).float(), self.means.reshape(-1).float()
+
+    def _params_like(self, xf):
+        """(lam, mu, c) next to `xf`; fp32 device copies are kept (like QuadraticPotential._params_like)."""
+        if xf.dtype == torch.float32 and xf.is_cuda:
+            key = str(xf.device)
+            if key not in self._dev:
+                self._pack(xf.device)
+            return self._dev[key][2]
+        return tuple(v.to(xf) for v in (self.lam, self.means, self.log_norm))
+
+    def _pack(self, device):
+        a, b = self.packed()
+        a, b = a.to(device), b.to(device)
+        K, d = self.n_components, self.event_size
+        self._dev[str(device)] = (a, b, (a[:K * d].view(K, d), b.view(K, d), a[K * d:]))
+
+    def __call__(self, x):
+        n = x.shape[0]
+        xf = x.reshape(n, -1)
+        lam, mu, c = self._params_like(xf)
+        diff = xf[:, None, :] - mu                                                 # (n, K, d)
+        e = c - 0.5 * torch.sum(lam * diff * diff, dim=-1)                        # (n, K)
+        return -torch.logsumexp(e, dim=-1)
+
+    def descriptor(self, device):
+        key = str(device)
+        if key not in self._dev:
+            self._pack(device)
+        a, b, _ = self._dev[key]
+        return hip.NfmcPotential(hip.POT_GAUSSIAN_MIXTURE, self.n_components, hip.ptr(a), hip.ptr(b), 0.0, 0.0)
 
 
 _log = logging.getLogger('nfmc_amd')

@@ -11,12 +11,14 @@ from ..containers import DeviceSampleStore
 from ..potentials import Potential, recognize
 
 
-def resolve_target(target, event_shape, fuse='auto', x0=None) -> Optional[Potential]:
+def resolve_target(target, event_shape, fuse='auto', x0=None, family=None) -> Optional[Potential]:
     """A closed-form descriptor for `target`, or None (-> split path: torch autograd for U, grad U).
     fuse: 'auto' (default) probes plain callables (potentials.recognize; `x0` sets the radii the probes must also
-    cover); False / 'never' keeps every plain callable on the split path."""
+    cover); False / 'never' keeps every plain callable on the split path.
+    family: the launch family the descriptor is for (potentials.FAMILIES); a potential whose kind that family's kernels
+    do not evaluate (`Potential.fused_in`) resolves to None there, like an arbitrary callable."""
     if isinstance(target, Potential):
-        return target
+        return target if family is None or target.fused_in(family) else None
     if fuse in (False, 'never'):
         return None
     x_scale = None

@@ -189,7 +189,7 @@ class DLMC(Sampler):
         flow = self.kernel.flow
         T = int(self.params.n_iterations)
         eps = float(self.kernel.step_size)
-        pot = resolve_target(self.target, es, self.fuse, run.x)
+        pot = resolve_target(self.target, es, self.fuse, run.x, family='flow_mh')
         nll = resolve_target(self.negative_log_likelihood, es, self.fuse, run.x)
         native = flow_is_native(flow)
         store = run.sample_store(T)
@@ -220,7 +220,7 @@ class DLMC(Sampler):
             if route is None:
                 if self.params.latent_updates:
                     route = 'latent'
-                elif native and pot is not None and step_supported(flow, run.x, eps, pot=pot):
+                elif native and pot is not None and pot.fused_in('dlmc_step') and step_supported(flow, run.x, eps, pot=pot):
                     route = 'fused'
                 elif native and step_supported(flow, run.x, eps, grad_u=run.x):
                     route = 'borrowed'

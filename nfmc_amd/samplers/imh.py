@@ -62,7 +62,7 @@ class AbstractIMH(Sampler):
     def warmup(self, x0, show_progress: bool = True, time_limit_seconds=None) -> MCMCOutput:
         """imh.py:60-75: variational fit of the flow to the target, then one flow sample as state."""
         # the closed-form descriptor of the target, when there is one, lets the fit step run on the device (flow_training.py)
-        pot = resolve_target(self.target, tuple(x0.shape[1:]), getattr(self, 'fuse', 'auto'), x0)
+        pot = resolve_target(self.target, tuple(x0.shape[1:]), getattr(self, 'fuse', 'auto'), x0, family='fit')
         extra = {'potential': pot} if pot is not None and _accepts_potential(self.kernel.flow) else {}
         self.kernel.flow.variational_fit(lambda v: -self.target(v), **self.params.warmup_fit_kwargs,
                                          show_progress=show_progress, time_limit_seconds=time_limit_seconds, **extra)
@@ -88,7 +88,7 @@ class FixedIMH(AbstractIMH):
                          max_samples=getattr(self.params, 'max_samples', None))
         flow = self.kernel.flow
         T = int(self.params.n_iterations)
-        pot = resolve_target(self.target, event_shape, self.fuse, run.x)
+        pot = resolve_target(self.target, event_shape, self.fuse, run.x, family='flow_mh')
         fused = pot is not None and flow_is_native(flow)
         store = run.sample_store(T)
         logq = torch.empty(n, dtype=torch.float32, device=run.dev)
@@ -188,7 +188,7 @@ class AdaptiveIMH(AbstractIMH):
         out = MCMCOutput(event_shape, kernel=self.kernel, store_samples=True)
         flow = self.kernel.flow
         T = int(self.params.n_iterations)
-        pot = resolve_target(self.target, event_shape, self.fuse, run.x)
+        pot = resolve_target(self.target, event_shape, self.fuse, run.x, family='flow_mh')
         fused = pot is not None and flow_is_native(flow)
         host = HostDraws(run.shard, *(self.host_draws or (None, None)))
         buf = torch.empty(max(T, 1), n, d, dtype=torch.float32, device=run.dev)

@@ -140,7 +140,7 @@ def imh_parallel_ok(run: Run, flow, pot, logq) -> bool:
         return False
     # d = 64, 1000 steps, parallel vs sequential: 1.0 vs 3.0 ms at n = 1000, 1.98 vs 3.0 at 8192, 5.7 vs 6.7 at 32768,
     # 10.6 vs 12.3 at 65536 (one accept-uniform draw per row instead of per lane, no per-step select / moments)
-    if os.environ.get('NFMC_IMH_PARALLEL') == '0':
+    if os.environ.get('NFMC_IMH_PARALLEL') == '0' or not pot.fused_in('imh_parallel'):
         return False
     a, _keep = _flow_mh_probe_args(run, flow, pot, logq, True)
     return hip.supported(int(hip.lib().nfmc_imh_parallel_supported_f32(C.byref(a))), 'nfmc_imh_parallel_supported_f32')
@@ -295,8 +295,9 @@ class JumpNFMC(Sampler):
         T, K = int(self.params.n_iterations), int(inner.params.n_iterations)
         off = (False, 'never')
         pot = resolve_target(self.target, event_shape,
-                             'never' if (self.fuse in off or getattr(inner, 'fuse', 'auto') in off) else 'auto', run.x)
-        fused = pot is not None and flow_is_native(flow)
+                             'never' if (self.fuse in off or getattr(inner, 'fuse', 'auto') in off) else 'auto', run.x,
+                             family='mcmc')
+        fused = pot is not None and flow_is_native(flow) and pot.fused_in('flow_mh')
         tail_ok = (self.fuse_jump_tail and fused and flow_fits_jump_tail(flow) and not self.params.fit_nf
                    and isinstance(inner, (MALA, ULA, HMC, UHMC)))
         inner._cur_run = run

@@ -210,7 +210,7 @@ class MCMCSampler(Sampler):
                          max_samples=getattr(self.params, 'max_samples', None))
         out.statistics.data_transform = self.data_transform
         K = int(self.params.n_iterations)
-        pot = resolve_target(self.target, event_shape, self.fuse, run.x)
+        pot = resolve_target(self.target, event_shape, self.fuse, run.x, family='mcmc')
         store = run.sample_store(K)
         run.stats.zero_()
         self._n_divergences = 0

@@ -103,7 +103,7 @@ class NeuTra(Sampler):
     def _closed_form(self):
         """The target as a closed-form potential descriptor (None: an arbitrary callable, differentiated by autograd)."""
         if getattr(self, '_pot_cache', None) is None or self._pot_cache[0] is not self.target:
-            self._pot_cache = (self.target, resolve_target(self.target, self.event_shape, self.fuse))
+            self._pot_cache = (self.target, resolve_target(self.target, self.event_shape, self.fuse, family='neutra'))
         return self._pot_cache[1]
 
     def _potential_grad(self, z):
@@ -127,7 +127,7 @@ class NeuTra(Sampler):
         fit_limit = 0.3 * time_limit_seconds if time_limit_seconds is not None else None
         t0 = time.time()
         from .imh import _accepts_potential
-        pot = resolve_target(self.target, tuple(x0.shape[1:]), getattr(self, 'fuse', 'auto'), x0)
+        pot = resolve_target(self.target, tuple(x0.shape[1:]), getattr(self, 'fuse', 'auto'), x0, family='fit')
         extra = {'potential': pot} if pot is not None and _accepts_potential(self.kernel.flow) else {}
         self.kernel.flow.variational_fit(lambda v: -self.target(v),
                                          **{**dict(time_limit_seconds=fit_limit), **self.params.warmup_fit_kwargs},
@@ -148,7 +148,7 @@ class NeuTra(Sampler):
         inner.params.max_samples = getattr(self.params, 'max_samples', None)
         run = Run(self, x0)
         n, d, event_shape = run.n, run.d, run.event_shape
-        pot = resolve_target(self.target, event_shape, self.fuse)
+        pot = resolve_target(self.target, event_shape, self.fuse, family='neutra')
         def split():
             # NeuTraMH / arbitrary targets / shapes without a fused kernel: the inner sampler's split path on the
             # adjusted target (neutra.py:116-127)

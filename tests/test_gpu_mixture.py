@@ -1,0 +1,444 @@
+"""GPU: GaussianMixture (NFMC_POT_GAUSSIAN_MIXTURE) on the fused HIP kernels against the fp64 CPU oracle.
+
+Tolerances (fp32 kernels, fp64 oracle on the same noise):
+  states        atol 1e-3 + rtol 1e-4.  U is a logsumexp over K group sums of d terms; at d = 512 those sums are
+                O(d) and their fp32 rounding (~d * 6e-8 relative) moves U, the responsibilities and so the gradient by
+                ~1e-4 per transition.
+  decisions     tie-aware: a chain whose fp64 |log u - log ratio| falls under MARGIN at any of its transitions is
+                excluded (its decision is ill-conditioned in fp32 and a flip changes the rest of its trajectory).  The
+                excluded share is reported and must stay under 10 %; all other chains must match.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+MARGIN = 2e-3
+ATOL, RTOL = 1e-3, 1e-4
+
+
+@pytest.fixture(scope='module')
+def dev():
+    assert torch.cuda.is_available(), 'GPU tests need a ROCm device'
+    return torch.device('cuda', 0)
+
+
+def _mixture(K, d, seed, spread=2.0):
+    from nfmc_amd.potentials import GaussianMixture
+    g = torch.Generator().manual_seed(seed)
+    means = spread * torch.randn(K, d, generator=g, dtype=torch.float64)
+    scales = 0.6 + 0.8 * torch.rand(K, d, generator=g, dtype=torch.float64)
+    weights = 0.2 + torch.rand(K, generator=g, dtype=torch.float64)
+    return GaussianMixture((d,), means, scales, weights), g
+
+
+def _x0(pot, n, g):
+    k = torch.randint(0, pot.n_components, (n,), generator=g)
+    return (pot.means[k] + 0.7 * torch.randn(n, pot.event_size, generator=g, dtype=torch.float64)).float()
+
+
+def _compare(got, tr, what):
+    """got (T, n, d) fp32 from the kernels, tr an oracle Trace on the same noise; returns the excluded share."""
+    want = tr.stacked().float()
+    n = want.shape[1]
+    keep = torch.ones(n, dtype=torch.bool)
+    if tr.log_ratios:
+        lr = torch.stack([v.reshape(-1).double() for v in tr.log_ratios])
+        lu = torch.stack([v.reshape(-1).double() for v in tr.uniforms])
+        keep = ((lu - lr).abs() >= MARGIN).all(0)
+    excluded = 1.0 - float(keep.float().mean())
+    print('%s: %.1f %% of the chains excluded as near-ties' % (what, 100 * excluded))
+    assert excluded < 0.10, (what, excluded)
+    assert torch.isfinite(got).all()
+    np.testing.assert_allclose(got[:, keep].numpy(), want[:, keep].numpy(), atol=ATOL, rtol=RTOL, err_msg=what)
+    return excluded
+
+
+def _sampler(kind, d, pot, T, h, L=5):
+    from nfmc_amd.samplers import mcmc
+    if kind in ('mala', 'ula'):
+        cls = mcmc.MALA if kind == 'mala' else mcmc.ULA
+        return cls((d,), pot, mcmc.LangevinKernel(event_size=d, step_size=h), mcmc.LangevinParameters(n_iterations=T))
+    if kind == 'mh':
+        return mcmc.MH((d,), pot, None, mcmc.MHParameters(n_iterations=T))
+    cls = mcmc.HMC if kind == 'hmc' else mcmc.UHMC
+    return cls((d,), pot, mcmc.HMCKernel(event_size=d, n_leapfrog_steps=L, step_size=h), mcmc.HMCParameters(n_iterations=T))
+
+
+def _oracle(kind, x0, pot, T, h, noise, L=5, inv_mass_diag=None):
+    from oracle import samplers as osamp
+    okind = {'mala': 'langevin', 'ula': 'langevin', 'mh': 'mh', 'hmc': 'hmc', 'uhmc': 'hmc'}[kind]
+    return osamp.mcmc_sample(x0.double(), pot, okind, T, h, n_leapfrog=L, adjustment=kind not in ('ula', 'uhmc'),
+                             noise=noise, inv_mass_diag=inv_mass_diag)
+
+
+def _step(kind, d):
+    return {'mala': 0.3, 'ula': 0.05, 'mh': 0.0, 'hmc': 0.1, 'uhmc': 0.05}[kind] * d ** (-1 / 3) if kind != 'mh' else 0.0
+
+
+# ------------------------------------------------------------------------- 1. fused kernels vs fp64 oracle, replayed noise
+@pytest.mark.parametrize('kind', ['mala', 'ula', 'mh', 'hmc', 'uhmc'])
+@pytest.mark.parametrize('K', [1, 2, 5, 8])
+@pytest.mark.parametrize('d', [2, 7, 64, 256, 512])
+def test_mcmc_replay_matches_oracle(dev, kind, K, d):
+    from oracle import samplers as osamp
+    from nfmc_amd.samplers import mcmc
+    n, T = 96, 4
+    pot, g = _mixture(K, d, 1000 * K + d)
+    x0 = _x0(pot, n, g)
+    h = _step(kind, d)
+    s = _sampler(kind, d, pot, T, h)
+    imd = None
+    if kind == 'mh':
+        s.kernel.inv_mass_diag = torch.full((d,), 0.3 / math.sqrt(d))
+        imd = s.kernel.inv_mass_diag.double()
+    rec = osamp.RecordingNoise(osamp.TorchNoise())
+    torch.manual_seed(d + K)
+    tr = _oracle(kind, x0, pot, T, h, rec, inv_mass_diag=imd)
+    s.replay = (torch.stack([v.float() for v in rec.normals]),
+                torch.stack([v.float() for v in rec.uniforms]) if rec.uniforms else None)
+    assert mcmc.resolve_target(pot, (d,), family='mcmc') is pot     # the fused route
+    out = s.sample(x0, show_progress=False)
+    _compare(out.samples.reshape(T, n, d), tr, '%s K=%d d=%d' % (kind, K, d))
+
+
+# ------------------------------------------------------------------------- 2. native Philox streams
+def _flow_pair(d, seed=5):
+    from nfmc_amd.flows import Flow, RealNVP
+    from oracle import flow as oflow
+    of = oflow.perturb_(oflow.Flow(oflow.RealNVP((d,))), seed, 0.2, 0.7071)
+    f = Flow(RealNVP((d,)))
+    f.load_state_dict(of.state_dict())
+    return f, of.double()
+
+
+@pytest.mark.parametrize('kind,K,d', [('mala', 3, 64), ('ula', 2, 7), ('mh', 5, 33), ('hmc', 8, 256), ('uhmc', 4, 16)])
+def test_mcmc_native_stream_matches_oracle(dev, kind, K, d):
+    from oracle import samplers as osamp
+    n, T, seed = 160, 5, 777 + d
+    pot, g = _mixture(K, d, 7 * K + d)
+    x0 = _x0(pot, n, g)
+    h = _step(kind, d)
+    s = _sampler(kind, d, pot, T, h)
+    imd = None
+    if kind == 'mh':
+        s.kernel.inv_mass_diag = torch.full((d,), 0.3 / math.sqrt(d))
+        imd = s.kernel.inv_mass_diag.double()
+    s.seed = seed
+    out = s.sample(x0, show_progress=False)
+    tr = _oracle(kind, x0, pot, T, h, osamp.PhiloxNoise(seed, dtype=torch.float64), inv_mass_diag=imd)
+    _compare(out.samples.reshape(T, n, d), tr, 'native %s' % kind)
+
+
+@pytest.mark.parametrize('fuse_tail', [False, True])
+@pytest.mark.parametrize('K,d', [(2, 16), (5, 64)])
+def test_jump_mala_native_stream_matches_oracle(dev, fuse_tail, K, d):
+    """jump_mala on a fixed perturbed flow: inner MALA fused, the jump on the register flow-MH kernel (or as the tail of
+    the last inner launch)."""
+    from nfmc_amd.containers import NFMCKernel
+    from nfmc_amd.samplers import jump, mcmc
+    from oracle import samplers as osamp
+    n, T, Kin, seed = 192, 3, 4, 31337
+    pot, g = _mixture(K, d, 3 * K + d, spread=1.0)
+    x0 = _x0(pot, n, g)
+    f, of = _flow_pair(d)
+    h = 0.3 * d ** (-1 / 3)
+    s = jump.JumpMALA((d,), pot, NFMCKernel((d,), flow=f), jump.JumpNFMCParameters(n_iterations=T), None,
+                      mcmc.LangevinParameters(n_iterations=Kin))
+    s.inner_sampler.kernel.step_size = h
+    s.seed, s.fuse_jump_tail = seed, fuse_tail
+    out = s.sample(x0, show_progress=False)
+    tr = osamp.jump_sample(x0.double(), pot, of, 'langevin', T, Kin, h, noise=osamp.PhiloxNoise(seed, dtype=torch.float64))
+    got, want = out.samples.reshape(T * (Kin + 1), n, d), tr.stacked().float()
+    same = (got - want).abs().amax(dim=(0, 2)) < ATOL + RTOL * want.abs().amax(dim=(0, 2))
+    assert same.float().mean() > 0.95, float(same.float().mean())
+    assert out.statistics.n_attempted_jumps == n * T
+    assert abs(out.statistics.n_accepted_jumps - tr.n_accepted_jumps) <= max(2, int(0.03 * n * T))
+
+
+@pytest.mark.parametrize('K,d', [(1, 7), (4, 64), (8, 256)])
+def test_imh_native_stream_matches_oracle(dev, K, d):
+    from nfmc_amd.samplers import imh
+    from nfmc_amd.samplers import jump as jmod
+    from oracle import samplers as osamp
+    n, T, seed = 256, 6, 4711 + d
+    pot, g = _mixture(K, d, 5 * K + d, spread=0.5)
+    x0 = _x0(pot, n, g)
+    f, of = _flow_pair(d, 9)
+    s = imh.FixedIMH((d,), pot, imh.IMHKernel((d,), flow=f), imh.IMHParameters(n_iterations=T))
+    s.seed = seed
+    calls = []
+    orig = jmod.launch_imh_parallel
+    jmod.launch_imh_parallel = lambda *a, **k: calls.append(1) or orig(*a, **k)
+    try:
+        out = s.sample(x0, show_progress=False)
+    finally:
+        jmod.launch_imh_parallel = orig
+    assert not calls   # nfmc_imh_parallel_supported_f32 answers no for kind 2: the sequential flow-MH kernel ran
+    tr = osamp.imh_sample(x0.double(), pot, of, T, noise=osamp.PhiloxNoise(seed, dtype=torch.float64))
+    _compare(out.samples.reshape(T, n, d), tr, 'imh K=%d d=%d' % (K, d))
+
+
+# ------------------------------------------------------------------------- 3. K = 1 is a diagonal Gaussian
+@pytest.mark.parametrize('kind', ['mala', 'hmc', 'mh'])
+def test_one_component_equals_diagonal_gaussian(dev, kind):
+    from nfmc_amd.potentials import DiagonalGaussian, GaussianMixture
+    d, n, T = 48, 256, 8
+    g = torch.Generator().manual_seed(1)
+    mu = torch.randn(d, generator=g)
+    sig = 0.5 + torch.rand(d, generator=g)
+    mix = GaussianMixture(d, mu[None], sig[None], [3.0])
+    gau = DiagonalGaussian(d, mu, sig)
+    x0 = mu + sig * torch.randn(n, d, generator=g)
+    outs = []
+    for pot in (mix, gau):
+        s = _sampler(kind, d, pot, T, _step(kind, d))
+        if kind == 'mh':
+            s.kernel.inv_mass_diag = torch.full((d,), 0.1)
+        s.seed = 99
+        outs.append(s.sample(x0, show_progress=False))
+    a, b = (o.samples.reshape(T, n, d) for o in outs)
+    same = (a - b).abs().amax(dim=(0, 2)) < 1e-4
+    assert same.float().mean() > 0.97, float(same.float().mean())
+    np.testing.assert_allclose(a[:, same].numpy(), b[:, same].numpy(), atol=1e-4, rtol=1e-5)
+    assert abs(outs[0].statistics.n_accepted_trajectories - outs[1].statistics.n_accepted_trajectories) <= \
+        int((~same).sum()) * T
+
+
+# ------------------------------------------------------------------------- 4. fused equals split
+@pytest.mark.parametrize('kind,K,d', [('mala', 3, 64), ('hmc', 5, 20), ('mh', 2, 7)])
+def test_fused_equals_split(dev, kind, K, d):
+    n, T = 200, 6
+    pot, g = _mixture(K, d, 17 * K + d)
+    x0 = _x0(pot, n, g)
+    outs = []
+    for target, fuse in ((pot, 'auto'), (lambda x: pot(x), 'never')):
+        s = _sampler(kind, d, target, T, _step(kind, d))
+        if kind == 'mh':
+            s.kernel.inv_mass_diag = torch.full((d,), 0.3 / math.sqrt(d))
+        s.seed, s.fuse = 2024, fuse
+        outs.append(s.sample(x0, show_progress=False))
+    a, b = (o.samples.reshape(T, n, d) for o in outs)
+    same = (a - b).abs().amax(dim=(0, 2)) < ATOL
+    assert same.float().mean() > 0.95, float(same.float().mean())
+    np.testing.assert_allclose(a[:, same].numpy(), b[:, same].numpy(), atol=ATOL, rtol=RTOL)
+
+
+# ------------------------------------------------------------------------- 5. refused families take the split / composed path
+def test_nine_components_take_the_split_path_and_match_the_oracle(dev):
+    from oracle import samplers as osamp
+    from nfmc_amd.samplers import mcmc
+    d, n, T = 12, 128, 5
+    pot, g = _mixture(9, d, 9)
+    assert not pot.fused_in('mcmc') and not pot.fused_in('flow_mh')
+    x0 = _x0(pot, n, g)
+    h = _step('mala', d)
+    s = _sampler('mala', d, pot, T, h)
+    s.seed = 5
+    spy = []
+    orig = mcmc.MALA._split_step
+    mcmc.MALA._split_step = lambda self, *a, **k: spy.append(1) or orig(self, *a, **k)
+    try:
+        out = s.sample(x0, show_progress=False)
+    finally:
+        mcmc.MALA._split_step = orig
+    assert len(spy) == T
+    tr = _oracle('mala', x0, pot, T, h, osamp.PhiloxNoise(5, dtype=torch.float64))
+    _compare(out.samples.reshape(T, n, d), tr, 'mala K=9 split')
+
+
+def test_refused_families_run_split_or_composed(dev):
+    from nfmc_amd import flow_training
+    from nfmc_amd.sample import create_sampler
+    from nfmc_amd.samplers.dlmc import DLMC, DLMCKernel, DLMCParameters
+    d, n = 6, 64
+    pot, g = _mixture(3, d, 3, spread=1.0)
+    x0 = _x0(pot, n, g)
+    # NeuTra: no descriptor for kind 2 -> the inner sampler's split path on the adjusted target
+    s = create_sampler(pot, (d,), strategy='neutra_hmc', param_kwargs={'n_iterations': 4})
+    assert s._closed_form() is None
+    s.seed = 1
+    out = s.sample(x0, show_progress=False)
+    assert torch.isfinite(out.samples).all()
+    # dlmc: the gradient step is borrowed (grad U by autograd), the MH step runs on the flow-MH kernel
+    f, _ = _flow_pair(d)
+    ds = DLMC((d,), pot, lambda x: 0.5 * (x ** 2).sum(-1), DLMCKernel((d,), flow=f, step_size=0.05),
+              DLMCParameters(n_iterations=3))
+    ds.seed = 2
+    out = ds.sample(x0, show_progress=False)
+    assert ds.last_route == 'borrowed' and torch.isfinite(out.samples).all()
+    # imh with the variational warmup fit: the torch loop, not the device fit (which answers NFMC_EUNSUPPORTED)
+    loops = []
+    orig = flow_training._loop
+    flow_training._loop = lambda *a, **k: loops.append(1) or orig(*a, **k)
+    try:
+        si = create_sampler(pot, (d,), strategy='imh', param_kwargs={'n_iterations': 4})
+        si.params.warmup_fit_kwargs = dict(si.params.warmup_fit_kwargs, n_epochs=3)
+        si.seed = 3
+        si.warmup(x0, show_progress=False)
+    finally:
+        flow_training._loop = orig
+    assert loops
+    out = si.sample(x0, show_progress=False)
+    assert torch.isfinite(out.samples).all()
+
+
+def test_jump_mala_wide_conditioner_composes_the_jump(dev):
+    """Conditioner wider than 32: the flow-MH kernels answer no; inner MALA stays fused, the jump is composed from the
+    flow's own kernels and the mixture's torch U -- and still matches the oracle."""
+    from nfmc_amd.containers import NFMCKernel
+    from nfmc_amd.flows import Flow, RealNVP
+    from nfmc_amd.samplers import jump, mcmc
+    from oracle import flow as oflow, samplers as osamp
+    d, n, T, Kin, seed = 16, 128, 2, 3, 11
+    pot, g = _mixture(2, d, 21, spread=1.0)
+    x0 = _x0(pot, n, g)
+    of = oflow.perturb_(oflow.Flow(oflow.RealNVP((d,), conditioner_kwargs={'n_hidden': 48})), 5, 0.2, 0.7071)
+    f = Flow(RealNVP((d,), conditioner_kwargs={'n_hidden': 48}))
+    f.load_state_dict(of.state_dict())
+    spy = []
+    orig = jump.split_flow_mh
+    jump.split_flow_mh = lambda *a, **k: spy.append(1) or orig(*a, **k)
+    try:
+        s = jump.JumpMALA((d,), pot, NFMCKernel((d,), flow=f), jump.JumpNFMCParameters(n_iterations=T), None,
+                          mcmc.LangevinParameters(n_iterations=Kin))
+        s.seed = seed
+        out = s.sample(x0, show_progress=False)
+    finally:
+        jump.split_flow_mh = orig
+    assert len(spy) == T
+    tr = osamp.jump_sample(x0.double(), pot, of.double(), 'langevin', T, Kin, d ** (-1 / 3),
+                           noise=osamp.PhiloxNoise(seed, dtype=torch.float64))
+    got, want = out.samples.reshape(T * (Kin + 1), n, d), tr.stacked().float()
+    same = (got - want).abs().amax(dim=(0, 2)) < 2e-3
+    assert same.float().mean() > 0.95, float(same.float().mean())
+
+
+# ------------------------------------------------------------------------- 6. kind 2 on the refusing entry points
+def test_refusing_entry_points_answer_unsupported(dev):
+    from nfmc_amd import hip
+    from nfmc_amd.samplers import dlmc
+    from nfmc_amd.samplers.common import Run
+    from nfmc_amd.samplers.jump import _flow_mh_probe_args
+    d, n = 64, 256
+    pot, g = _mixture(3, d, 4)
+    x = _x0(pot, n, g).to(dev)
+    f, _ = _flow_pair(d)
+    f.to(dev)
+    pd = pot.descriptor(dev)
+    # dlmc's fused gradient step
+    a, _keep = dlmc.step_args(f, x, 0.05, pot=pot)
+    assert a.pot.kind == hip.POT_GAUSSIAN_MIXTURE
+    assert int(hip.lib().nfmc_dlmc_step_supported_f32(C.byref(a))) == hip.EUNSUPPORTED
+    # NeuTra gradient kernel: nothing written
+    st, _k2 = f.bijection.packed(dev)
+    u = torch.full((n,), 123.0, device=dev)
+    gr = torch.full_like(x, 123.0)
+    rc = int(hip.lib().nfmc_neutra_potential_grad_f32(C.byref(st), C.byref(pd), hip.ptr(x), n, hip.ptr(u), hip.ptr(gr),
+                                                        hip.stream()))
+    torch.cuda.synchronize()
+    assert rc == hip.EUNSUPPORTED and bool((u == 123.0).all()) and bool((gr == 123.0).all())
+    # imh_parallel and the flow-MH tile path (one chain per lane) through the same probe arguments as the samplers
+    from nfmc_amd.samplers import imh
+    s = imh.FixedIMH((d,), pot, imh.IMHKernel((d,), flow=f), imh.IMHParameters(n_iterations=1))
+    run = Run(s, x.cpu())
+    logq = torch.empty(n, device=dev)
+    pa, _k3 = _flow_mh_probe_args(run, f, pot, logq, True)
+    assert int(hip.lib().nfmc_imh_parallel_supported_f32(C.byref(pa))) == hip.EUNSUPPORTED
+    assert int(hip.lib().nfmc_flow_mh_supported_f32(C.byref(pa))) == hip.OK        # the register kernels take it
+    pa.pot.reserved = 9                                                             # K over the cap
+    assert int(hip.lib().nfmc_flow_mh_supported_f32(C.byref(pa))) == hip.EUNSUPPORTED
+    # a wide conditioner (one-chain-per-lane / matrix-core flow-MH kernels): refused, never evaluated as a quadratic
+    fw, _ = _flow_pair_wide(d)
+    fw.to(dev)
+    pw, _k4 = _flow_mh_probe_args(run, fw, pot, logq, True)
+    assert int(hip.lib().nfmc_flow_mh_supported_f32(C.byref(pw))) == hip.EUNSUPPORTED
+    pw.x, pw.logq, pw.n_steps = hip.ptr(x), hip.ptr(logq), 1
+    before = x.clone()
+    assert int(hip.lib().nfmc_flow_mh_steps_f32(C.byref(pw), hip.stream())) == hip.EUNSUPPORTED
+    torch.cuda.synchronize()
+    assert torch.equal(x, before)
+    # variational fit kernel
+    assert hip.EUNSUPPORTED < 0 and pot.fused_in('fit') is False
+
+
+def _flow_pair_wide(d):
+    from nfmc_amd.flows import Flow, RealNVP
+    from oracle import flow as oflow
+    of = oflow.perturb_(oflow.Flow(oflow.RealNVP((d,), conditioner_kwargs={'n_hidden': 48})), 5, 0.2, 0.7071)
+    f = Flow(RealNVP((d,), conditioner_kwargs={'n_hidden': 48}))
+    f.load_state_dict(of.state_dict())
+    return f, of
+
+
+# ------------------------------------------------------------------------- 7. determinism, sharding, store
+def test_determinism_sharding_and_store(dev):
+    from nfmc_amd.dist import Shard
+    d, n, T = 20, 300, 12
+    pot, g = _mixture(4, d, 44)
+    x0 = _x0(pot, n, g)
+    runs = []
+    for _ in range(2):
+        s = _sampler('mala', d, pot, T, _step('mala', d))
+        s.seed = 7
+        runs.append(s.sample(x0, show_progress=False))
+    assert torch.equal(runs[0].samples, runs[1].samples)
+    assert runs[0].statistics.n_accepted_trajectories == runs[1].statistics.n_accepted_trajectories
+    dense = runs[0].samples.reshape(T, n, d)
+    parts = []
+    for r in range(2):
+        sh = Shard(rank=r, world=2)
+        sh.merge_statistics = lambda s_: s_
+        s = _sampler('mala', d, pot, T, _step('mala', d))
+        s.seed, s.shard = 7, sh
+        parts.append(s.sample(x0, show_progress=False).samples.reshape(T, -1, d))
+    assert torch.equal(torch.cat(parts, 1), dense)
+    # thinning / max_samples keep states of the dense run, in order
+    s = _sampler('mala', d, pot, T, _step('mala', d))
+    s.seed = 7
+    s.params.thinning, s.params.max_samples = 3, 3
+    kept = s.sample(x0, show_progress=False).samples.reshape(-1, n, d)
+    assert kept.shape[0] == 3
+    idx = [next(t for t in range(T) if torch.equal(kept[i], dense[t])) for i in range(3)]
+    assert idx == sorted(idx) and len(set(idx)) == 3
+
+
+# ------------------------------------------------------------------------- 8. what the feature is for
+def test_imh_reaches_mode_weights_mala_stays(dev):
+    """Two modes 8 apart in each of d = 4 coordinates (weights 0.7 / 0.3, unit scales); every chain starts in the minor
+    mode.  MALA at h = 0.3 cannot cross a barrier of U ~ 8^2 * 4 / 8 = 32 nats in T = 200 steps (the minor-mode share
+    must stay above 0.99).  IMH with a flow fitted on exact mixture draws must reach the 0.7 / 0.3 split: with n = 4096
+    chains the share of the major mode after T steps is a binomial proportion with standard error
+    sqrt(0.7 * 0.3 / 4096) = 0.0072 (chains are independent; the fitted flow's leftover bias adds to it), and the test
+    allows 5 of them.  Seeded: the run, the fit and the draws are deterministic."""
+    from nfmc_amd.containers import NFMCKernel
+    from nfmc_amd.flows import Flow, RealNVP
+    from nfmc_amd.potentials import GaussianMixture
+    from nfmc_amd.samplers import imh
+    d, n = 4, 4096
+    mu = torch.tensor([[4.0] * d, [-4.0] * d])
+    pot = GaussianMixture(d, mu, 1.0, [0.7, 0.3])
+    g = torch.Generator().manual_seed(0)
+    x0 = mu[1] + torch.randn(n, d, generator=g)
+    s = _sampler('mala', d, pot, 200, 0.3)
+    s.seed = 1
+    s.params.store_samples = False
+    last = s.sample(x0, show_progress=False).running_samples.last_sample
+    minor = float((last.sum(1) < 0).float().mean())
+    assert minor > 0.99, minor
+    # exact draws of the mixture, a flow fitted on them
+    torch.manual_seed(2)
+    k = (torch.rand(20000, generator=g) < 0.3).long()
+    draws = mu[k] + torch.randn(20000, d, generator=g)
+    f = Flow(RealNVP((d,)))
+    f.fit(draws, n_epochs=100, show_progress=False)
+    si = imh.FixedIMH((d,), pot, imh.IMHKernel((d,), flow=f), imh.IMHParameters(n_iterations=200))
+    si.seed = 3
+    si.params.store_samples = False
+    last = si.sample(x0, show_progress=False).running_samples.last_sample
+    major = float((last.sum(1) > 0).float().mean())
+    assert abs(major - 0.7) < 5 * math.sqrt(0.21 / n), major
