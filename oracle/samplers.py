@@ -413,6 +413,54 @@ def imh_sample(x0, target, flow, n_iterations, noise=None, store=True, step0=0):
     return tr
 
 
+# --------------------------------------------------------------------------- A.6 DLMC
+def dlmc_sample(x0, target, nll, flow, n_iterations, step_size, latent=False, noise=None, refit=None, step0=0):
+    """`DLMC.sample` (nfmc/algorithms/sampling/nfmc/dlmc.py:45-127) in fp64: one gradient step on the likelihood, then
+    per iteration a gradient step on U + log q (or, with `latent`, on U - |z|^2 / 2 in the flow's latent space) followed
+    by one independent-MH step proposed by the flow (`jump_transition`).
+
+    The flow is converted to fp64 in place; x0 and the noise are promoted.  Iteration `it` draws at transition
+    step0 + it with TAG_LATENT / TAG_JUMP, as `DLMC.sample` passes step i to `launch_flow_mh` and `split_flow_mh`.
+    `refit(it, flow, x)`, when given, stands where the reference refits the flow (dlmc.py:73-78): at the start of
+    iteration `it`, on the states x (n, d).  It may change `flow` in place and draws nothing from `noise`."""
+    noise = noise or TorchNoise()
+    flow = flow.double()
+    n = x0.shape[0]
+    event = tuple(x0.shape[1:])
+    x = x0.detach().double().reshape(n, -1)
+    tr = Trace(moments=Moments.for_event((x.shape[1],)))
+    x = x - step_size * _value_and_grad(nll, x)[1]                                # :58-66
+    tr.n_target_calls = tr.n_target_gradient_calls = n
+    for it in range(n_iterations):
+        if refit is not None:                                                     # :73-78
+            refit(it, flow, x)
+            tr.n_refits += 1
+        if latent:                                                                # :80-84
+            with torch.no_grad():
+                z, _ = flow.bijection.forward(x.reshape(n, *event))
+            z = z.reshape(n, -1) - step_size * (_value_and_grad(target, x)[1] - z.reshape(n, -1))
+            with torch.no_grad():
+                x, _ = flow.bijection.inverse(z.reshape(n, *event))
+            x = x.reshape(n, -1)
+        else:                                                                     # :85-92
+            x = x - step_size * _value_and_grad(lambda v: target(v) + flow.log_prob(v.reshape(n, *event)), x)[1]
+        tr.n_target_calls += n
+        tr.n_target_gradient_calls += n
+        js = jump_transition(x, target, flow, step0 + it, noise, True, event)     # :93-119
+        tr.n_target_calls += js.n_target_calls
+        if js.log_alpha is not None:
+            tr.log_ratios.append(js.log_alpha)
+            tr.uniforms.append(js.log_u)
+        x, mask = js.x, js.mask
+        tr.n_accepted += int(mask.sum())
+        tr.n_attempted += n
+        tr.masks.append(mask)
+        tr.moments.update(x)
+        tr.samples.append(x.clone())
+        tr.last = x.clone()
+    return tr
+
+
 class TorchHostDraws:
     """Host-side scalar draws of AdaptiveIMH (imh.py:148,156-160) from torch's global generator."""
 

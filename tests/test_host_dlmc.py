@@ -1,6 +1,6 @@
-"""CPU: DLMC routing and defaults, and an fp64 restatement of the DLMC loop (dlmc.py:45-127) that reproduces the
-reference's fixtures (tests/golden/make_golden_dlmc.py).  The GPU tests (test_gpu_dlmc.py) compare against the same
-restatement."""
+"""CPU: DLMC routing and defaults, and the fp64 oracle of the DLMC loop (oracle.samplers.dlmc_sample, dlmc.py:45-127)
+reproducing the reference's fixtures (tests/golden/make_golden_dlmc.py).  The GPU tests (test_gpu_dlmc.py) compare
+against the same oracle."""
 import os
 import sys
 
@@ -10,46 +10,6 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from conftest import golden_flow, load_golden  # noqa: E402
-
-
-def _grad(fn, x):
-    with torch.enable_grad():
-        v = x.detach().clone().requires_grad_(True)
-        g, = torch.autograd.grad(fn(v).sum(), v)
-    return g.detach()
-
-
-def dlmc_restate(x0, flow, target, nll, eps, T, normals, uniforms, latent=False, refit=None):
-    """The DLMC loop in fp64 on the oracle flow, noise given: `normals[t]` the latents of iteration t's flow proposal,
-    `uniforms[t]` its accept uniforms.  `refit(t, x)` (optional) refits the flow at the start of iteration t.
-    Returns (samples (T, n, d), n_accepted, n_target_calls, n_gradient_calls)."""
-    flow = flow.double()
-    x = x0.double()
-    n = x.shape[0]
-    x = x - eps * _grad(nll, x)
-    calls, grads, acc, out = n, n, 0, []
-    for t in range(T):
-        if refit is not None:
-            refit(t, x)
-        if latent:
-            with torch.no_grad():
-                z, _ = flow.bijection.forward(x)
-            z = z - eps * (_grad(target, x) - z)
-            with torch.no_grad():
-                x, _ = flow.bijection.inverse(z)
-        else:
-            x = x - eps * _grad(lambda v: target(v) + flow.log_prob(v), x)
-        calls += n
-        grads += n
-        with torch.no_grad():
-            xt, _ = flow.bijection.inverse(torch.as_tensor(normals[t]).double())
-            la = -target(xt) + target(x) + flow.log_prob(x) - flow.log_prob(xt)
-        mask = torch.log(torch.as_tensor(uniforms[t]).double()) < la
-        x = torch.where(mask[:, None], xt, x)
-        acc += int(mask.sum())
-        calls += 2 * n
-        out.append(x.clone())
-    return torch.stack(out), acc, calls, grads
 
 
 def _sumsq(x):
@@ -62,17 +22,44 @@ def _nll(shift):
 
 @pytest.mark.parametrize('name', ['dlmc_d6', 'dlmc_latent_d6'])
 def test_restatement_reproduces_reference_fixture(name):
+    from oracle import samplers as osamp
     fx = load_golden(name)
     flow = golden_flow(fx, 6)
     T = int(fx['n_iterations'])
-    got, acc, calls, grads = dlmc_restate(torch.from_numpy(fx['x0']), flow, _sumsq, _nll(float(fx['nll_shift'])),
-                                          float(fx['step_size']), T, fx['noise/normals'], fx['noise/uniforms'],
-                                          latent=bool(fx['latent_updates']))
-    assert np.allclose(got.numpy(), fx['exp/samples'], atol=1e-5)
+    noise = osamp.ReplayNoise(torch.from_numpy(fx['noise/normals']).double(),
+                              torch.from_numpy(fx['noise/uniforms']).double())
+    tr = osamp.dlmc_sample(torch.from_numpy(fx['x0']), _sumsq, _nll(float(fx['nll_shift'])), flow, T,
+                           float(fx['step_size']), latent=bool(fx['latent_updates']), noise=noise)
+    assert np.allclose(tr.stacked().numpy(), fx['exp/samples'], atol=1e-5)
     c = fx['exp/counters']   # accepted, attempted, divergences, target calls, gradient calls
     n = fx['x0'].shape[0]
-    assert (acc, n * T, 0, calls, grads) == tuple(int(v) for v in c)
-    assert 0 < acc < n * T
+    assert (tr.n_accepted, tr.n_attempted, tr.n_divergences, tr.n_target_calls, tr.n_target_gradient_calls) == \
+        tuple(int(v) for v in c)
+    assert tr.n_attempted == n * T
+    assert 0 < tr.n_accepted < n * T
+    np.testing.assert_allclose(tr.moments.first.numpy(), fx['exp/first_moment'], atol=1e-5)
+    np.testing.assert_allclose(tr.moments.second.numpy(), fx['exp/second_moment'], atol=1e-5)
+
+
+def test_oracle_draws_the_flow_mh_stream_of_the_sampler():
+    """Under PhiloxNoise iteration t of dlmc_sample draws the latents at step step0 + t with TAG_LATENT and the accept
+    uniform with TAG_JUMP: the words DLMC.sample hands launch_flow_mh / split_flow_mh (step i, one transition)."""
+    from oracle import flow as oflow, philox, samplers as osamp
+    d, n, T, seed = 5, 7, 3, 123
+    torch.manual_seed(0)
+    of = oflow.perturb_(oflow.Flow(oflow.RealNVP((d,))), 4, 0.2, 0.8)
+    x0 = torch.randn(n, d)
+    rec = osamp.RecordingNoise(osamp.PhiloxNoise(seed, dtype=torch.float64))
+    tr = osamp.dlmc_sample(x0, _sumsq, _nll(0.0), of, T, 0.05, noise=rec, step0=2)
+    assert len(rec.normals) == len(rec.uniforms) == T
+    ids = np.arange(n, dtype=np.uint32)
+    for t in range(T):
+        want_z = philox.normal_field(seed, ids, 2 + t, d, philox.TAG_LATENT)
+        assert np.array_equal(rec.normals[t].numpy(), want_z.reshape(n, d).astype(np.float64))
+        assert np.array_equal(rec.uniforms[t].numpy(), philox.jump_uniform(seed, ids, 2 + t).astype(np.float64))
+    replay = osamp.dlmc_sample(x0, _sumsq, _nll(0.0), of, T, 0.05, noise=osamp.ReplayNoise(rec.normals, rec.uniforms))
+    assert torch.equal(replay.stacked(), tr.stacked()) and replay.n_accepted == tr.n_accepted
+    assert (tr.n_target_calls, tr.n_target_gradient_calls) == (n + 3 * n * T, n + n * T)
 
 
 def test_create_sampler_routes_dlmc_with_reference_defaults():
@@ -123,3 +110,53 @@ def test_warmup_returns_x0_only():
     x0 = torch.randn(4, 3)
     out = s.warmup(x0, show_progress=False)
     assert torch.equal(out.running_samples.last_sample.cpu(), x0)
+
+
+# ---- the launch geometry of csrc/dlmc_kernels.hip, restated for the GPU tests (test_gpu_dlmc.py) that pick shapes on
+# both sides of every rows-per-wave switch and past the grid-stride threshold
+LDS_BUDGET = 150 * 1024   # neutra_rows_per_wave (csrc/neutra_kernels.hpp)
+DLMC_TILES = 3            # x, w and g wave tiles (dlmc_launch)
+GRID_TILES = 4 * 2048     # 4 * kMaxGrid (csrc/common.hpp) workgroups per launch; more tiles grid-stride
+
+
+def tile_stride(d):
+    """tile_stride (csrc/flow_device.hpp): d rounded up to 4 floats, plus 4 when that is a multiple of 8."""
+    s = (d + 3) & ~3
+    return s + 4 if ((s >> 2) & 1) == 0 else s
+
+
+def dlmc_rows_per_wave(d):
+    for rpw in (64, 32, 16):
+        if DLMC_TILES * rpw * tile_stride(d) * 4 <= LDS_BUDGET:
+            return rpw
+    return 0
+
+
+def hp_bucket(n_hidden):
+    return 4 if n_hidden <= 4 else 8
+
+
+def test_launch_geometry_restated_from_the_kernel_source():
+    """The restatement above against the source it restates, and the switch points it puts at 196 | 197 (64 -> 32
+    rows) and 396 | 397 (32 -> 16 rows): a change to the formula fails here before it silently moves the GPU tests' shapes
+    off the boundaries."""
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'nfmc_amd', 'csrc')
+
+    def src(name):
+        with open(os.path.join(csrc, name)) as fh:
+            return ' '.join(fh.read().split())
+    dl, nk, fd, cm = (src(n) for n in ('dlmc_kernels.hip', 'neutra_kernels.hpp', 'flow_device.hpp', 'common.hpp'))
+    assert 'const int rpw = neutra_rows_per_wave(f.d, 3);' in dl
+    assert 'const size_t lds = (size_t)3 * rpw * tile_stride(f.d) * sizeof(float);' in dl
+    assert 'const int grid = (int)(tiles < 4 * kMaxGrid ? tiles : 4 * kMaxGrid);' in dl
+    assert 'const int hp = hp_bucket_n(f.n_hidden);' in dl
+    assert ('for (int rpw = 64; rpw >= 16; rpw >>= 1) if ((size_t)tiles_of_d * rpw * tile_stride(d) * sizeof(float) '
+            '<= 150 * 1024) return rpw;') in nk
+    assert 'static int hp_bucket_n(int h) { return h <= 4 ? 4 : (h <= 8 ? 8' in nk
+    assert 'int s = (d + 3) & ~3; if (((s >> 2) & 1) == 0) s += 4; return s;' in fd
+    assert 'constexpr int kMaxGrid = 2048;' in cm
+    assert [dlmc_rows_per_wave(d) for d in (2, 196, 197, 396, 397, 512)] == [64, 64, 32, 32, 16, 16]
+    assert all(dlmc_rows_per_wave(d) == 64 for d in range(2, 197))
+    assert all(dlmc_rows_per_wave(d) == 32 for d in range(197, 397))
+    assert all(dlmc_rows_per_wave(d) == 16 for d in range(397, 513))
+    assert [hp_bucket(h) for h in range(1, 9)] == [4, 4, 4, 4, 8, 8, 8, 8]
