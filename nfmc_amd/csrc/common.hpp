@@ -28,7 +28,10 @@ constexpr uint32_t kTagNoise = 0, kTagAccept = 1, kTagLatent = 2, kTagJump = 3;
 // smallest round count the Random123 authors report as passing BigCrush, 30 % fewer generator instructions).  The key
 // schedule is wave-uniform, so the compiler keeps the round keys in SGPRs; the 32x32->64 products become
 // v_mad_u64_u32, the two xors of a word one v_bitop3_b32.
-template <int R>
+// UC1: the caller guarantees c1 is wave-uniform (the step of a sampler transition).  Round 0's c1 ^ k0 is then one s_xor
+// on the SALU and the word one VOP2 v_xor_b32 with that SGPR: v_bitop3_b32 is VOP3, which reads one SGPR at most on gfx9,
+// so with c1 and k0 both in SGPRs it needs a v_mov first.  Same bits either way.
+template <int R, bool UC1 = false>
 __device__ __forceinline__ uint4 philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -37,7 +40,8 @@ __device__ __forceinline__ uint4 philox4x32(uint32_t c0, uint32_t c1, uint32_t c
         // gfx950's three-input bit op (truth table 0x96 = a ^ b ^ c): one VOP3 instead of two dependent v_xor --
         // the compiler does not form it by itself; mala_kernel 0.327 -> 0.291 ms per launch (tools/ubench.hip:
         // v_bitop3_b32 with an SGPR key issues at 1.31x a v_fma, the xor pair at 1.5x, and the chain is one op shorter)
-        const uint32_t n0 = __builtin_amdgcn_bitop3_b32((uint32_t)(p1 >> 32), c1, k0, 0x96);
+        const uint32_t n0 = (UC1 && r == 0) ? (uint32_t)(p1 >> 32) ^ (c1 ^ k0)
+                                            : __builtin_amdgcn_bitop3_b32((uint32_t)(p1 >> 32), c1, k0, 0x96);
         const uint32_t n2 = __builtin_amdgcn_bitop3_b32((uint32_t)(p0 >> 32), c3, k1, 0x96);
         c1 = (uint32_t)p1;
         c3 = (uint32_t)p0;
@@ -75,6 +79,17 @@ __device__ __forceinline__ void box_muller(uint32_t ra, uint32_t rb, float& za, 
     const float rad = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u1));
     za = rad * __builtin_amdgcn_cosf(u2);
     zb = rad * __builtin_amdgcn_sinf(u2);
+}
+
+// box_muller with each pair's two products rad * (cos, sin) as one v_pk_mul_f32: the same bits.  Written packed because
+// the SLP vectorizer forms the packed multiply in some instantiations of a kernel and not in others.
+typedef float nfmc_f2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ nfmc_f2 box_muller_pk(uint32_t ra, uint32_t rb) {
+    const float u1 = fmaf((float)ra, 0x1p-32f, 0x1p-33f);
+    const float u2 = (float)rb * 0x1p-32f;
+    const float rad = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u1));
+    const nfmc_f2 cs = {__builtin_amdgcn_cosf(u2), __builtin_amdgcn_sinf(u2)};
+    return cs * rad;
 }
 
 // Four normals for coordinate block `blk` of (chain, step) on stream `tag`.

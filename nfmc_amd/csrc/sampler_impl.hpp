@@ -71,11 +71,11 @@ struct MassCoef {
     __device__ __forceinline__ float RS(int i) const { return FAST ? 1.f : rs[FAST ? 0 : i]; }
 };
 
-// noise for this lane's CPL coordinates of (chain, step): native Philox or replay from HBM
-template <int CPL, int LPC, int R = 10>
+// noise for this lane's CPL coordinates of (chain, step): native Philox or (REPLAY) replay from HBM
+template <int CPL, int LPC, int R = 10, bool REPLAY = true>
 __device__ __forceinline__ void draw_normals(const NfmcRng& rng, uint32_t tag, uint32_t gchain, int64_t row, int64_t n,
                                              int d, int g, int s, float (&e)[CPL]) {
-    if (rng.replay_normals) {
+    if (REPLAY && rng.replay_normals) {
         const float* p = rng.replay_normals + ((int64_t)s * n + row) * d;
 #pragma unroll
         for (int i = 0; i < CPL; ++i) {
@@ -85,26 +85,52 @@ __device__ __forceinline__ void draw_normals(const NfmcRng& rng, uint32_t tag, u
     } else {
         const uint32_t k0 = (uint32_t)rng.seed, k1 = (uint32_t)(rng.seed >> 32);
 #pragma unroll
-        for (int b = 0; b < CPL / 4; ++b) {
-            float z[4];
-            philox_normal4<R>(gchain, rng.step0 + (uint32_t)s, (uint32_t)(b * LPC + g), tag, k0, k1, z);
-            e[4 * b] = z[0];
-            e[4 * b + 1] = z[1];
-            e[4 * b + 2] = z[2];
-            e[4 * b + 3] = z[3];
+        for (int b = 0; b < CPL / 4; ++b) {   // philox_normal4, with the step (wave-uniform) folded on the SALU
+            const uint4 r = philox4x32<R, true>(gchain, rng.step0 + (uint32_t)s, (uint32_t)(b * LPC + g), tag, k0, k1);
+            const nfmc_f2 z0 = box_muller_pk(r.x, r.y), z1 = box_muller_pk(r.z, r.w);
+            e[4 * b] = z0.x;
+            e[4 * b + 1] = z0.y;
+            e[4 * b + 2] = z1.x;
+            e[4 * b + 3] = z1.y;
         }
     }
 }
 
-template <int R = 10>
-struct AcceptUniformR {
-    uint4 r;
-    __device__ __forceinline__ float draw(const NfmcRng& rng, uint32_t gchain, int64_t row, int64_t n, int s) {
-        if (rng.replay_uniforms) return row < n ? rng.replay_uniforms[(int64_t)s * n + row] : 0.5f;
-        const uint32_t step = rng.step0 + (uint32_t)s;
-        if (s == 0 || (step & 3u) == 0u)
-            r = philox4x32<R>(gchain, step >> 2, 0u, kTagAccept, (uint32_t)rng.seed, (uint32_t)(rng.seed >> 32));
-        return u32_to_uniform(pick_word(r, step & 3u));
+// ln u of the Metropolis test of transition s: word step & 3 of Philox block step >> 2 on stream kTagAccept, or (REPLAY)
+// the replayed u.  LPC == 1: every lane draws its chain's block once per 4 transitions and picks the word.  LPC >= 2:
+// all lanes of a chain need the same value, so they share the work: lane g draws block q0 + g, converts its four words to
+// ln u once and leaves them in its 16 bytes of `slab` (LDS, one float4 per lane of the workgroup); one refresh covers the
+// chain's next 4 LPC transitions, each of which reads word step - 4 q0 of the chain's LPC float4 (a broadcast read, one
+// VALU address add).  Same block, same word, same conversion, same v_log as the per-lane draw: bitwise the same ln u.
+template <int LPC, int R = 10, bool REPLAY = true>
+struct AcceptLnU {
+    uint4 r;                 // LPC == 1: the current block
+    float4* mine;            // LPC >= 2: this lane's four ln u
+    const float* chain;      // ... and its chain's 4 LPC of them
+    uint32_t base;           // step of chain[0] (a multiple of 4; wave-uniform)
+    __device__ __forceinline__ AcceptLnU(float4* slab, int g) {
+        if constexpr (LPC > 1) {
+            mine = slab + threadIdx.x;
+            chain = reinterpret_cast<const float*>(slab + (threadIdx.x - g));
+        }
+    }
+    __device__ __forceinline__ float draw(const NfmcRng& rng, uint32_t gchain, int64_t row, int64_t n, int g, int s) {
+        if (REPLAY && rng.replay_uniforms) return fast_ln(row < n ? rng.replay_uniforms[(int64_t)s * n + row] : 0.5f);
+        const uint32_t step = rng.step0 + (uint32_t)s, k0 = (uint32_t)rng.seed, k1 = (uint32_t)(rng.seed >> 32);
+        if constexpr (LPC == 1) {
+            if (s == 0 || (step & 3u) == 0u) r = philox4x32<R>(gchain, step >> 2, 0u, kTagAccept, k0, k1);
+            return fast_ln(u32_to_uniform(pick_word(r, step & 3u)));
+        } else {
+            // refresh at the first transition, when the slab is used up, and where the 32-bit step wraps (block 0 next)
+            if (s == 0 || step - base == 4u * LPC || step == 0u) {
+                base = step & ~3u;
+                const uint4 w = philox4x32<R>(gchain, (base >> 2) + (uint32_t)g, 0u, kTagAccept, k0, k1);
+                *mine = make_float4(fast_ln(u32_to_uniform(w.x)), fast_ln(u32_to_uniform(w.y)),
+                                    fast_ln(u32_to_uniform(w.z)), fast_ln(u32_to_uniform(w.w)));
+                __builtin_amdgcn_wave_barrier();   // a chain's lanes write and read in one wave: keep the order, no s_barrier
+            }
+            return chain[step - base];
+        }
     }
 };
 
@@ -174,9 +200,13 @@ __device__ __forceinline__ bool jump_once(float (&x)[CPL], const FlowT& fl, cons
 }
 
 // ------------------------------------------------------------------------------------------------
-template <int CPL, int LPC, template <int, int, bool> class Pot, bool FAST, int JHP, int RR = 10>
+// LEAN: the launch has no per-step output and no replay (masks_out, log_ratio_out, samples.base, replay_normals and
+// replay_uniforms all null; launch_mala_cfg checks), so none of their pointers or branches is in the step loop.
+template <int CPL, int LPC, template <int, int, bool> class Pot, bool FAST, int JHP, int RR = 10, bool LEAN = false>
 __global__ void __launch_bounds__(kBlock, NFMC_WPE) mala_kernel(NfmcMalaArgs a, float sqrt2h, int64_t tiles, JumpDev jd) {
+    static_assert(!LEAN || JHP == 0, "the jump tail keeps its own outputs");
     extern __shared__ __attribute__((aligned(16))) float flow_lds[];
+    __shared__ float4 accept_slab[LPC > 1 ? kBlock : 1];
     constexpr int CPW = kWave / LPC;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int g = lane % LPC, cw = lane / LPC;
@@ -220,8 +250,9 @@ __global__ void __launch_bounds__(kBlock, NFMC_WPE) mala_kernel(NfmcMalaArgs a, 
         const uint32_t gchain = (uint32_t)(a.rng.chain_offset + (uint64_t)row);
         float x[CPL];
         load_row<CPL, LPC, FAST>(a.x, row, d, g, active, x);
-        AcceptUniformR<RR> au;
+        AcceptLnU<LPC, RR, !LEAN> au(accept_slab, g);
         StoreCursor keep(a.samples);
+        const uint64_t live = __ballot(active);   // the wave's lanes with a chain
         float sq = 0.f, sq_prop = 0.f;   // FAST quadratic: this lane's share of |x|^2 (current state / proposal)
         if constexpr (Pot<CPL, LPC, FAST>::kQuadratic && FAST) {
 #pragma unroll
@@ -230,23 +261,31 @@ __global__ void __launch_bounds__(kBlock, NFMC_WPE) mala_kernel(NfmcMalaArgs a, 
 
         for (int s = 0; s < a.n_steps; ++s) {
             float e[CPL], xp[CPL];
-            draw_normals<CPL, LPC, RR>(a.rng, kTagNoise, gchain, row, n, d, g, s, e);
-            bool accept = true;
+            draw_normals<CPL, LPC, RR, !LEAN>(a.rng, kTagNoise, gchain, row, n, d, g, s, e);
             float lr = 0.f;
             if constexpr (Pot<CPL, LPC, FAST>::kQuadratic && FAST) {
                 // FAST: scalar a, b = 0, unit mass.  The ratio below, a^2 h (sum_j x_j^2 - sum_j x'_j^2), needs only
                 // this lane's share of |x'|^2: the share of |x|^2 is carried from the previous transition (`sq`,
                 // replaced by the proposal's on acceptance).  3 VALU instructions per coordinate for proposal + ratio.
-                float sp0 = 0.f, sp1 = 0.f;
+                // Coordinate pairs as v_pk_fma_f32 (the even / odd partial sums of |x'|^2 are the two halves of sp).
+                nfmc_f2 sp = {0.f, 0.f};
+                const nfmc_f2 cg = {mc.CG(0), mc.CG(0)}, c2 = {mc.C2(0), mc.C2(0)};
 #pragma unroll
                 for (int i = 0; i < CPL; i += 2) {
-                    xp[i] = fmaf(mc.C2(i), e[i], fmaf(mc.CG(i), x[i], x[i]));              // langevin.py:74-76 / mh.py:55
-                    xp[i + 1] = fmaf(mc.C2(i + 1), e[i + 1], fmaf(mc.CG(i + 1), x[i + 1], x[i + 1]));
-                    sp0 = fmaf(xp[i], xp[i], sp0);
-                    sp1 = fmaf(xp[i + 1], xp[i + 1], sp1);
+                    const nfmc_f2 xi = {x[i], x[i + 1]}, ei = {e[i], e[i + 1]};
+                    // langevin.py:74-76 / mh.py:55
+                    const nfmc_f2 p = __builtin_elementwise_fma(c2, ei, __builtin_elementwise_fma(cg, xi, xi));
+                    xp[i] = p.x;
+                    xp[i + 1] = p.y;
+                    sp = __builtin_elementwise_fma(p, p, sp);
                 }
-                sq_prop = sp0 + sp1;
-                lr = mc.KAP(0) * (sq - sq_prop);
+                sq_prop = sp.x + sp.y;
+                // rounded product: where the compiler places this multiply in the reduction's block it would otherwise
+                // contract it with the reduction's first add into one fma, which changes the bits of log r
+                {
+#pragma clang fp contract(off)
+                    lr = mc.KAP(0) * (sq - sq_prop);
+                }
             } else if constexpr (Pot<CPL, LPC, FAST>::kQuadratic) {
                 // U = sum a (x-b)^2: with t = x - b, t' = x' - b the reference's ratio (langevin.py:88-105)
                 //   (u - u') + [q(x'|x) - q(x|x')]   collapses term by term to   a^2 (h/m^2) (t^2 - t'^2)
@@ -276,14 +315,15 @@ __global__ void __launch_bounds__(kBlock, NFMC_WPE) mala_kernel(NfmcMalaArgs a, 
                     }
                 }
             }
+            // accept mask of the wave.  Each ballot takes one compare, so its v_cmp writes the mask directly (a ballot of a
+            // combined bool went through a VGPR 0/1 and a compare back)
+            uint64_t am = live;
             if (adjust) {
                 lr = group_allreduce<LPC>(lr);
-                const float u = au.draw(a.rng, gchain, row, n, s);
-                accept = fast_ln(u) < lr;  // NaN -> reject (langevin.py:106, mh.py:59)
-                n_bad += (uint32_t)__popcll(__ballot(active && !(fabsf(lr) <= 3.0e38f)) & leaders);
+                const float ln_u = au.draw(a.rng, gchain, row, n, g, s);
+                am &= __ballot(ln_u < lr);  // NaN -> reject (langevin.py:106, mh.py:59)
+                n_bad += (uint32_t)__popcll(__ballot(!(fabsf(lr) <= 3.0e38f)) & live & leaders);
             }
-            accept = accept && active;
-            const uint64_t am = __ballot(accept);
             n_acc += (uint32_t)__popcll(am & leaders);
             if constexpr (Pot<CPL, LPC, FAST>::kQuadratic && FAST) sq = select_f32(am, sq_prop, sq);
 #pragma unroll
@@ -292,10 +332,12 @@ __global__ void __launch_bounds__(kBlock, NFMC_WPE) mala_kernel(NfmcMalaArgs a, 
                 sx[i] += x[i];
                 sxx[i] = fmaf(x[i], x[i], sxx[i]);
             }
-            if (float* kept = keep.next(n * d)) store_row<CPL, LPC, FAST>(kept, row, d, g, active, x);
-            if (g == 0 && active) {
-                if (a.masks_out) a.masks_out[(int64_t)s * n + row] = accept ? 1 : 0;
-                if (a.log_ratio_out) a.log_ratio_out[(int64_t)s * n + row] = lr;
+            if constexpr (!LEAN) {
+                if (float* kept = keep.next(n * d)) store_row<CPL, LPC, FAST>(kept, row, d, g, active, x);
+                if (g == 0 && active) {
+                    if (a.masks_out) a.masks_out[(int64_t)s * n + row] = (am >> lane) & 1u;
+                    if (a.log_ratio_out) a.log_ratio_out[(int64_t)s * n + row] = lr;
+                }
             }
         }
         if constexpr (JHP > 0) {
@@ -326,6 +368,7 @@ __global__ void __launch_bounds__(kBlock, NFMC_WPE) mala_kernel(NfmcMalaArgs a, 
 template <int CPL, int LPC, template <int, int, bool> class Pot, bool FAST, int JHP, int RR = 10>
 __global__ void __launch_bounds__(kBlock, NFMC_WPE) hmc_kernel(NfmcHmcArgs a, int64_t tiles, JumpDev jd) {
     extern __shared__ __attribute__((aligned(16))) float flow_lds[];
+    __shared__ float4 accept_slab[LPC > 1 ? kBlock : 1];
     constexpr int CPW = kWave / LPC;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int g = lane % LPC, cw = lane / LPC;
@@ -363,7 +406,7 @@ __global__ void __launch_bounds__(kBlock, NFMC_WPE) hmc_kernel(NfmcHmcArgs a, in
         const uint32_t gchain = (uint32_t)(a.rng.chain_offset + (uint64_t)row);
         float x[CPL];
         load_row<CPL, LPC, FAST>(a.x, row, d, g, active, x);
-        AcceptUniformR<RR> au;
+        AcceptLnU<LPC, RR> au(accept_slab, g);
         StoreCursor keep(a.samples);
 
         for (int s = 0; s < a.n_steps; ++s) {
@@ -427,8 +470,7 @@ __global__ void __launch_bounds__(kBlock, NFMC_WPE) hmc_kernel(NfmcHmcArgs a, in
 #pragma unroll
                 for (int i = 0; i < CPL; ++i) dh -= pot.term(ctx, i, q[i]) + 0.5f * (p[i] * p[i] * mc.M(i));  // :107-110
                 lr = group_allreduce<LPC>(dh);
-                const float u = au.draw(a.rng, gchain, row, n, s);
-                accept = fast_ln(u) < lr;  // hmc.py:111-113
+                accept = au.draw(a.rng, gchain, row, n, g, s) < lr;  // ln u < log r, hmc.py:111-113
                 n_bad += (uint32_t)__popcll(__ballot(active && !(fabsf(lr) <= 3.0e38f)) & leaders);
             }
             accept = accept && active;
@@ -485,6 +527,8 @@ int launch_mala_cfg(const NfmcMalaArgs& a, const JumpDev& jd, bool fast, int64_t
         lds = (size_t)FlowImage<CPL, LPC, JHP>::total_floats(jd.flow.n_hidden_layers, jd.flow.n_coupling) * sizeof(float);
     lds = lds_with_potential(lds, a.pot, CPL * LPC);   // the mixture's parameter block behind the image
     if (lds > 120 * 1024) return NFMC_EUNSUPPORTED;
+    // no per-step output and no replay: the FAST quadratic kernels without a jump tail have a LEAN instantiation
+    const bool lean = !a.masks_out && !a.log_ratio_out && !a.samples.base && !a.rng.replay_normals && !a.rng.replay_uniforms;
 #define NFMC_L(POT, F)                                                                                            \
     {                                                                                                             \
         auto kern = mala_kernel<CPL, LPC, POT, F, JHP>;                                                           \
@@ -497,7 +541,8 @@ int launch_mala_cfg(const NfmcMalaArgs& a, const JumpDev& jd, bool fast, int64_t
     if (rng_rounds(a.rng) == 7) {   // opt-in Philox4x32-7 stream: the exact-fit quadratic kernel without a jump tail
         if constexpr (JHP == 0) {
             if (fast && a.pot.kind == NFMC_POT_QUADRATIC) {
-                auto kern = mala_kernel<CPL, LPC, QuadraticPot, true, 0, 7>;
+                auto kern = lean ? mala_kernel<CPL, LPC, QuadraticPot, true, 0, 7, true>
+                                 : mala_kernel<CPL, LPC, QuadraticPot, true, 0, 7>;
                 hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, a, sqrt2h, tiles, jd);
                 return NFMC_OK;
             }
@@ -509,6 +554,13 @@ int launch_mala_cfg(const NfmcMalaArgs& a, const JumpDev& jd, bool fast, int64_t
     } else if (a.pot.kind == NFMC_POT_FUNNEL) {
         if (fast) NFMC_L(FunnelPot, true) else NFMC_L(FunnelPot, false)
     } else {
+        if constexpr (JHP == 0) {
+            if (fast && lean) {
+                auto kern = mala_kernel<CPL, LPC, QuadraticPot, true, 0, 10, true>;
+                hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, a, sqrt2h, tiles, jd);
+                return NFMC_OK;
+            }
+        }
         if (fast) NFMC_L(QuadraticPot, true) else NFMC_L(QuadraticPot, false)
     }
 #undef NFMC_L
