@@ -46,7 +46,7 @@ enum {
 enum {
     NFMC_POT_QUADRATIC = 0, /* U = sum_j a_j (x_j - b_j)^2 ; a,b per coordinate or scalar */
     NFMC_POT_FUNNEL = 1,    /* U = x_0^2/(2 s^2) + sum_{i>=1} [x_i^2 / (2 e^{x_0}) + x_0/2], s = a_scalar */
-    NFMC_POT_GAUSSIAN_MIXTURE = 2
+    NFMC_POT_GAUSSIAN_MIXTURE = 2,
     /* Diagonal Gaussian mixture of K = n_components components:
          U = -logsumexp_k [ c_k - 1/2 sum_j lam_kj (x_j - mu_kj)^2 ],  lam_kj = 1/sigma_kj^2,
          c_k = log w_k + 1/2 sum_j log lam_kj   (the constant d/2 log 2 pi is dropped)
@@ -55,11 +55,21 @@ enum {
        flow image: a larger K, or a block that does not fit, gets NFMC_EUNSUPPORTED.  Served by nfmc_mala_steps_f32 /
        nfmc_hmc_steps_f32 (general kernels, with or without a jump tail; not the Philox4x32-7 stream) and by the
        register-layout kernels of nfmc_flow_mh_steps_f32; every other entry point answers NFMC_EUNSUPPORTED. */
+    NFMC_POT_LOGISTIC_REGRESSION = 3
+    /* Bayesian logistic regression over N = n_components data rows, prior x ~ N(0, s^2 I):
+         U = sum_i [softplus(z_i) - y_i z_i] + |x|^2 / (2 s^2),  z_i = X_i . x,  softplus(z) = max(z, 0) + log1p(e^-|z|)
+         dU/dx = X^T (sigmoid(z) - y) + x / s^2   (constants dropped)
+       a -> X (N, d) fp32 row-major, device memory, 16-byte aligned;  b -> y (N,) fp32, values 0 or 1, device memory;
+       a_scalar = 1/s^2 > 0;  b_scalar unused.  No cap on N (each evaluation streams X through an LDS tile of 16 KB plus
+       the tile's labels; a flow image that leaves no room for it gets NFMC_EUNSUPPORTED).  Served by nfmc_mala_steps_f32
+       / nfmc_hmc_steps_f32 (general kernels, with or without a jump tail; not the Philox4x32-7 stream) and by the
+       register-layout kernels of nfmc_flow_mh_steps_f32; every other entry point answers NFMC_EUNSUPPORTED. */
 };
 
 typedef struct {
     int32_t kind;
-    int32_t n_components; /* NFMC_POT_GAUSSIAN_MIXTURE: K; 0 for the other kinds (was `reserved`, same layout) */
+    int32_t n_components; /* NFMC_POT_GAUSSIAN_MIXTURE: K; NFMC_POT_LOGISTIC_REGRESSION: N; 0 for the other kinds
+                             (was `reserved`, same layout) */
     const float* a; /* (d,) or NULL -> a_scalar */
     const float* b; /* (d,) or NULL -> b_scalar */
     float a_scalar;

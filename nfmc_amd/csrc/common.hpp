@@ -337,9 +337,38 @@ inline int check_mixture(const NfmcPotential& p) {
     return NFMC_OK;
 }
 
-// LDS bytes a register-layout kernel with DP padded coordinates stages for `p` beside its flow image (0 unless kind 2)
+// Bayesian logistic regression (NFMC_POT_LOGISTIC_REGRESSION; X (N, d) row-major in a, y (N,) in {0, 1} in b,
+// N = p.n_components, 1/s^2 = a_scalar):
+//   U = sum_i [softplus(z_i) - y_i z_i] + |x|^2 / (2 s^2),   z_i = X_i . x,   softplus(z) = max(z, 0) + log1p(e^-|z|)
+//   dU/dx = X^T (sigmoid(z) - y) + x / s^2
+// X does not fit in LDS, and every chain of a workgroup reads the same rows, so prepare() streams it through one LDS tile
+// of kLogRegTileFloats floats: logreg_tile_rows(DP) rows padded to DP coordinates with zeros, their labels behind them.
+// The whole workgroup loads a tile between two barriers, so every thread of the workgroup must call prepare() equally
+// often: the sampler and flow-MH kernels call it in workgroup-uniform control flow only.  Per batch of 4 rows a lane
+// forms its partial dot products from one ds_read_b128 per register quad and row (consecutive lanes read consecutive
+// 16 bytes, the chain groups of a wave the same ones: broadcast).  LPC >= 4: ONE reduce-scatter over the batch
+// (group_reduce_scatter<4>) leaves z of row g & 3 on lane g, which alone evaluates that row's softplus and sigmoid, and
+// four quad_perm broadcasts hand every lane the batch's residuals sigmoid(z) - y for the gradient pass over the same
+// rows.  LPC < 4: one butterfly per row.  No cap on N: the cost is 2 N d FMAs per chain and evaluation.
+constexpr int kLogRegTileFloats = 4096;   // the X part of a tile: 16 KB
+
+__host__ __device__ inline int logreg_tile_rows(int dp) { return kLogRegTileFloats / dp; }   // dp: a power of 2, 4 .. 1024
+__host__ __device__ inline int logreg_floats(int dp) { return logreg_tile_rows(dp) * (dp + 1); }
+
+// argument check of a kind-3 descriptor at the entry points that run it (0 for every other kind)
+inline int check_logreg(const NfmcPotential& p) {
+    if (p.kind != NFMC_POT_LOGISTIC_REGRESSION) return NFMC_OK;
+    if (!p.a || !p.b || p.n_components < 1 || !(p.a_scalar > 0.f && p.a_scalar <= 3.0e38f)) return NFMC_EINVAL;
+    if ((((uintptr_t)p.a) & 15u) != 0) return NFMC_EALIGN;
+    return NFMC_OK;
+}
+
+// LDS bytes a register-layout kernel with DP padded coordinates stages for `p` beside its flow image (0 unless kind 2
+// or 3)
 inline size_t staged_potential_bytes(const NfmcPotential& p, int dp) {
-    return p.kind == NFMC_POT_GAUSSIAN_MIXTURE ? (size_t)mixture_floats(p.n_components, dp) * sizeof(float) : 0;
+    if (p.kind == NFMC_POT_GAUSSIAN_MIXTURE) return (size_t)mixture_floats(p.n_components, dp) * sizeof(float);
+    if (p.kind == NFMC_POT_LOGISTIC_REGRESSION) return (size_t)logreg_floats(dp) * sizeof(float);
+    return 0;
 }
 
 template <int CPL, int LPC, bool FAST>
@@ -422,6 +451,143 @@ struct MixturePot {
                 }
             }
         }
+        return cx;
+    }
+    __device__ __forceinline__ float grad(const Ctx& cx, int i, float) const { return cx.gr[i]; }
+    __device__ __forceinline__ float term(const Ctx& cx, int i, float) const { return (lead && i == 0) ? cx.u : 0.f; }
+};
+
+// softplus(z) and sigmoid(z) from one e^-|z|: finite for every finite z.  log1p(e) is ln(1 + e) on v_log_f32 for
+// e >= 2^-8 and the series e - e^2/2 + e^3/3 below (relative error < 2e-8 there), where 1 + e would drop e's low bits
+__device__ __forceinline__ void softplus_sigmoid(float z, float& sp, float& sg) {
+    const float e = fast_exp(-fabsf(z));                 // (0, 1]; 0 for |z| past ~104
+    const float inv = __builtin_amdgcn_rcpf(1.f + e);
+    const float l1p = e < 0x1p-8f ? e * fmaf(e, fmaf(e, 1.f / 3.f, -0.5f), 1.f) : fast_ln(1.f + e);
+    sp = fmaxf(z, 0.f) + l1p;
+    sg = (z >= 0.f ? 1.f : e) * inv;
+}
+
+template <int CPL, int LPC, bool FAST>
+struct LogRegPot {
+    static constexpr bool kQuadratic = false;
+    static constexpr bool kStaged = true;
+    static constexpr int DP = CPL * LPC;
+    static constexpr int T = kLogRegTileFloats / DP;   // rows per tile
+    static constexpr int kPer = kLogRegTileFloats / kBlock;   // X floats per thread and tile
+    static_assert(T % 4 == 0 && kLogRegTileFloats % kBlock == 0, "batches of 4 rows, whole tiles per thread");
+    float* tile;          // LDS: X rows (T, DP) | y (T)
+    const float* X;
+    const float* y;
+    int nr, dd;
+    float inv_s2;
+    bool lead;            // this lane holds coordinate 0 in register 0
+    float valid[CPL];     // 1 for real coordinates, 0 for padding
+    struct Ctx {
+        float u;          // U of the chain (every lane of the group)
+        float gr[CPL];    // dU/dx of this lane's coordinates
+    };
+
+    __device__ __forceinline__ static void stage(float*, const NfmcPotential&, int) {}   // prepare() streams the tiles
+    __device__ __forceinline__ void init(const NfmcPotential& p, int g, int d, float* lds) {
+        tile = lds;
+        X = p.a;
+        y = p.b;
+        nr = p.n_components;
+        dd = d;
+        inv_s2 = p.a_scalar;
+        lead = (g == 0);
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) valid[i] = coord_of<CPL, LPC>(g, i) < d ? 1.f : 0.f;
+    }
+    __device__ __forceinline__ float4 row4(int r, int q, int g) const {
+        return *reinterpret_cast<const float4*>(tile + r * DP + 4 * (q * LPC + g));
+    }
+    // all threads of the workgroup: rows t0 .. t0 + rows - 1 into the tile, zeros past them
+    __device__ __forceinline__ void load_tile(int t0, int rows) const {
+        __syncthreads();   // every wave is done with the previous tile
+        float v[kPer];
+#pragma unroll
+        for (int k = 0; k < kPer; ++k) {   // all loads in flight before the first LDS write
+            const int e = threadIdx.x + k * kBlock, r = e / DP, j = e % DP;
+            v[k] = (j < dd && r < rows) ? X[(int64_t)(t0 + r) * dd + j] : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < kPer; ++k) tile[threadIdx.x + k * kBlock] = v[k];
+        for (int r = threadIdx.x; r < T; r += kBlock) tile[T * DP + r] = r < rows ? y[t0 + r] : 0.f;
+        __syncthreads();
+    }
+    __device__ __forceinline__ Ctx prepare(const float (&x)[CPL], int g, int) const {
+        Ctx cx;
+        float pr = 0.f;   // this lane's share of |x|^2
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) {
+            const float xv = valid[i] * x[i];
+            cx.gr[i] = inv_s2 * xv;
+            pr = fmaf(xv, xv, pr);
+        }
+        // this lane's share of the data term, summed in fp64: U is a sum of N terms of O(1), and fp32 partial sums over
+        // thousands of rows lose ~sqrt(N) ulps of U -- 1e-2 in a log ratio at N = 2500 -- which fp64 keeps to the one
+        // rounding of the result
+        double ul = 0.0;
+        const float* yt = tile + T * DP;
+        for (int t0 = 0; t0 < nr; t0 += T) {
+            const int rows = nr - t0 < T ? nr - t0 : T;
+            load_tile(t0, rows);
+            for (int r0 = 0; r0 < rows; r0 += 4) {
+                float h[4];
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    float s = 0.f;
+#pragma unroll
+                    for (int q = 0; q < CPL / 4; ++q) {
+                        const float4 w = row4(r0 + b, q, g);
+                        s = fmaf(w.x, x[4 * q], s);
+                        s = fmaf(w.y, x[4 * q + 1], s);
+                        s = fmaf(w.z, x[4 * q + 2], s);
+                        s = fmaf(w.w, x[4 * q + 3], s);
+                    }
+                    h[b] = s;
+                }
+                float rb[4];   // sigmoid(z) - y of the batch's rows (0 past the last row)
+                if constexpr (LPC >= 4) {
+                    const int b = g & 3;
+                    const float z = group_reduce_scatter<4, LPC>(h);   // z of row r0 + b
+                    const float yv = yt[r0 + b];
+                    float sp, sg;
+                    softplus_sigmoid(z, sp, sg);
+                    const bool ok = r0 + b < rows;
+                    if (ok && g < 4) ul += (double)(sp - yv * z);   // one lane per row
+                    const float res = ok ? sg - yv : 0.f;
+                    rb[0] = dpp_mov<0x00>(res);   // quad_perm [b, b, b, b]: the value of lane b of the quad
+                    rb[1] = dpp_mov<0x55>(res);
+                    rb[2] = dpp_mov<0xAA>(res);
+                    rb[3] = dpp_mov<0xFF>(res);
+                } else {
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) {
+                        const float z = group_allreduce<LPC>(h[b]);
+                        const float yv = yt[r0 + b];
+                        float sp, sg;
+                        softplus_sigmoid(z, sp, sg);
+                        const bool ok = r0 + b < rows;
+                        if (ok && g == 0) ul += (double)(sp - yv * z);
+                        rb[b] = ok ? sg - yv : 0.f;
+                    }
+                }
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+#pragma unroll
+                    for (int q = 0; q < CPL / 4; ++q) {
+                        const float4 w = row4(r0 + b, q, g);
+                        cx.gr[4 * q] = fmaf(rb[b], w.x, cx.gr[4 * q]);
+                        cx.gr[4 * q + 1] = fmaf(rb[b], w.y, cx.gr[4 * q + 1]);
+                        cx.gr[4 * q + 2] = fmaf(rb[b], w.z, cx.gr[4 * q + 2]);
+                        cx.gr[4 * q + 3] = fmaf(rb[b], w.w, cx.gr[4 * q + 3]);
+                    }
+                }
+            }
+        }
+        cx.u = group_allreduce<LPC>((float)(ul + (double)(0.5f * inv_s2 * pr)));
         return cx;
     }
     __device__ __forceinline__ float grad(const Ctx& cx, int i, float) const { return cx.gr[i]; }

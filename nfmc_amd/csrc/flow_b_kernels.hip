@@ -310,6 +310,7 @@ static int launch_b_rqs(const NfmcFlowMhArgs& a, bool fast, int64_t tiles, int g
         hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, a, tiles);                                    \
     }
     if (a.pot.kind == NFMC_POT_GAUSSIAN_MIXTURE) NFMC_LBR(MixturePot, false)
+    else if (a.pot.kind == NFMC_POT_LOGISTIC_REGRESSION) NFMC_LBR(LogRegPot, false)
     else if (a.pot.kind == NFMC_POT_FUNNEL) NFMC_LBR(FunnelPot, false)
     else if (fast) NFMC_LBR(QuadraticPot, true)
     else NFMC_LBR(QuadraticPot, false)
@@ -341,6 +342,7 @@ static int launch_b(const NfmcFlowMhArgs& a, bool fast, int64_t tiles, int grid,
         hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, a, tiles);                                  \
     }
     if (a.pot.kind == NFMC_POT_GAUSSIAN_MIXTURE) NFMC_LB(MixturePot, false)
+    else if (a.pot.kind == NFMC_POT_LOGISTIC_REGRESSION) NFMC_LB(LogRegPot, false)
     else if (a.pot.kind == NFMC_POT_FUNNEL) NFMC_LB(FunnelPot, false)
     else if (fast) NFMC_LB(QuadraticPot, true)
     else NFMC_LB(QuadraticPot, false)

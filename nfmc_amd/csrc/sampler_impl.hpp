@@ -519,13 +519,20 @@ struct Cfg {
     int cpl, lpc;
 };
 
+// The layouts choose_cfg picks without the NFMC_SAMPLER_CFG override: the smallest capacity CPL * LPC >= d, at equal
+// capacity the first in kCfgs.  (4, 16), (16, 4), (16, 8), (16, 16) and (16, 32) tie with an earlier layout and are
+// reachable only through the override; LogRegPot is not instantiated there (the override skips them for kind 3).
+constexpr bool is_default_cfg(int cpl, int lpc) {
+    return !((cpl == 4 && lpc == 16) || (cpl == 16 && lpc != 64));
+}
+
 template <int CPL, int LPC, int JHP>
 int launch_mala_cfg(const NfmcMalaArgs& a, const JumpDev& jd, bool fast, int64_t tiles, int grid, float sqrt2h,
                     hipStream_t st) {
     size_t lds = 0;
     if constexpr (JHP > 0)
         lds = (size_t)FlowImage<CPL, LPC, JHP>::total_floats(jd.flow.n_hidden_layers, jd.flow.n_coupling) * sizeof(float);
-    lds = lds_with_potential(lds, a.pot, CPL * LPC);   // the mixture's parameter block behind the image
+    lds = lds_with_potential(lds, a.pot, CPL * LPC);   // the mixture's parameter block / the X tile behind the image
     if (lds > 120 * 1024) return NFMC_EUNSUPPORTED;
     // no per-step output and no replay: the FAST quadratic kernels without a jump tail have a LEAN instantiation
     const bool lean = !a.masks_out && !a.log_ratio_out && !a.samples.base && !a.rng.replay_normals && !a.rng.replay_uniforms;
@@ -551,6 +558,12 @@ int launch_mala_cfg(const NfmcMalaArgs& a, const JumpDev& jd, bool fast, int64_t
     }
     if (a.pot.kind == NFMC_POT_GAUSSIAN_MIXTURE) {   // never exact-fit: a and b are tables
         NFMC_L(MixturePot, false)
+    } else if (a.pot.kind == NFMC_POT_LOGISTIC_REGRESSION) {
+        if constexpr (JHP > 0 || is_default_cfg(CPL, LPC)) {
+            NFMC_L(LogRegPot, false)
+        } else {
+            return NFMC_EUNSUPPORTED;   // not reached: choose_cfg never picks this layout for kind 3
+        }
     } else if (a.pot.kind == NFMC_POT_FUNNEL) {
         if (fast) NFMC_L(FunnelPot, true) else NFMC_L(FunnelPot, false)
     } else {
@@ -572,7 +585,7 @@ int launch_hmc_cfg(const NfmcHmcArgs& a, const JumpDev& jd, bool fast, int64_t t
     size_t lds = 0;
     if constexpr (JHP > 0)
         lds = (size_t)FlowImage<CPL, LPC, JHP>::total_floats(jd.flow.n_hidden_layers, jd.flow.n_coupling) * sizeof(float);
-    lds = lds_with_potential(lds, a.pot, CPL * LPC);   // the mixture's parameter block behind the image
+    lds = lds_with_potential(lds, a.pot, CPL * LPC);   // the mixture's parameter block / the X tile behind the image
     if (lds > 120 * 1024) return NFMC_EUNSUPPORTED;
 #define NFMC_L(POT, F)                                                                                            \
     {                                                                                                             \
@@ -595,6 +608,12 @@ int launch_hmc_cfg(const NfmcHmcArgs& a, const JumpDev& jd, bool fast, int64_t t
     }
     if (a.pot.kind == NFMC_POT_GAUSSIAN_MIXTURE) {   // never exact-fit: a and b are tables
         NFMC_L(MixturePot, false)
+    } else if (a.pot.kind == NFMC_POT_LOGISTIC_REGRESSION) {
+        if constexpr (JHP > 0 || is_default_cfg(CPL, LPC)) {
+            NFMC_L(LogRegPot, false)
+        } else {
+            return NFMC_EUNSUPPORTED;   // not reached: choose_cfg never picks this layout for kind 3
+        }
     } else if (a.pot.kind == NFMC_POT_FUNNEL) {
         if (fast) NFMC_L(FunnelPot, true) else NFMC_L(FunnelPot, false)
     } else {

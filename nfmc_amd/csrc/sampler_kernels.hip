@@ -10,14 +10,17 @@ namespace nfmc {
 static const Cfg kCfgs[] = {{4, 1}, {4, 2}, {4, 4}, {4, 8}, {8, 8}, {4, 16}, {16, 4}, {8, 16}, {16, 8}, {8, 32}, {16, 16}, {8, 64}, {16, 32}, {16, 64}};
 static const Cfg kBCfgs[] = {{4, 1}, {4, 2}, {4, 4}, {4, 8}, {8, 8}, {8, 16}, {8, 32}, {8, 64}};  // jump-tail variants
 
-static Cfg choose_cfg(int d, bool with_jump) {
+// default_only: the override may name only layouts the default choice picks (the potentials with no instantiation at
+// the other layouts, is_default_cfg)
+static Cfg choose_cfg(int d, bool with_jump, bool default_only = false) {
     if (const char* e = getenv("NFMC_SAMPLER_CFG")) {  // "cpl,lpc" override (tuning)
         int c = 0, l = 0;
         if (sscanf(e, "%d,%d", &c, &l) == 2) {
             const Cfg* list = with_jump ? kBCfgs : kCfgs;
             const int len = with_jump ? (int)(sizeof(kBCfgs) / sizeof(Cfg)) : (int)(sizeof(kCfgs) / sizeof(Cfg));
             for (int i = 0; i < len; ++i)
-                if (list[i].cpl == c && list[i].lpc == l && c * l >= d) return list[i];
+                if (list[i].cpl == c && list[i].lpc == l && c * l >= d && (!default_only || is_default_cfg(c, l)))
+                    return list[i];
         }
     }
     Cfg best = {0, 0};
@@ -40,9 +43,11 @@ static int check_common(const Args* a) {
     if (a->n_steps > NFMC_MAX_STEPS_PER_CALL) return NFMC_ESHAPE;
     if (a->d > 1024) return NFMC_ESHAPE;
     if (!(a->step_size > 0.f)) return NFMC_EINVAL;
-    if (a->pot.kind != NFMC_POT_QUADRATIC && a->pot.kind != NFMC_POT_FUNNEL && a->pot.kind != NFMC_POT_GAUSSIAN_MIXTURE)
+    if (a->pot.kind != NFMC_POT_QUADRATIC && a->pot.kind != NFMC_POT_FUNNEL && a->pot.kind != NFMC_POT_GAUSSIAN_MIXTURE &&
+        a->pot.kind != NFMC_POT_LOGISTIC_REGRESSION)
         return NFMC_EUNSUPPORTED;
     if (int rc = check_mixture(a->pot)) return rc;
+    if (int rc = check_logreg(a->pot)) return rc;
     if (((uintptr_t)a->x & 3u) != 0) return NFMC_EALIGN;
     if (!store_ok(a->samples)) return NFMC_EINVAL;
     if (!rng_rounds_ok(a->rng, true)) return NFMC_EINVAL;
@@ -286,7 +291,7 @@ extern "C" int nfmc_mala_steps_f32(const NfmcMalaArgs* args, nfmc_stream_t strea
     NfmcMalaArgs a = *args;
     hipStream_t st = (hipStream_t)stream;
     const int jhp = a.jump ? (a.jump->flow.n_hidden <= 4 ? 4 : 8) : 0;
-    const Cfg c = choose_cfg(a.d, jhp > 0);
+    const Cfg c = choose_cfg(a.d, jhp > 0, a.pot.kind == NFMC_POT_LOGISTIC_REGRESSION);
     if (!c.cpl) return NFMC_ESHAPE;
     const bool fast = fast_path(&a, c);
     const int dp = c.cpl * c.lpc;
@@ -344,7 +349,7 @@ extern "C" int nfmc_hmc_steps_f32(const NfmcHmcArgs* args, nfmc_stream_t stream)
     NfmcHmcArgs a = *args;
     hipStream_t st = (hipStream_t)stream;
     const int jhp = a.jump ? (a.jump->flow.n_hidden <= 4 ? 4 : 8) : 0;
-    const Cfg c = choose_cfg(a.d, jhp > 0);
+    const Cfg c = choose_cfg(a.d, jhp > 0, a.pot.kind == NFMC_POT_LOGISTIC_REGRESSION);
     if (!c.cpl) return NFMC_ESHAPE;
     const bool fast = fast_path(&a, c);
     const int dp = c.cpl * c.lpc;

@@ -233,6 +233,68 @@ class GaussianMixture(Potential):
         return hip.NfmcPotential(hip.POT_GAUSSIAN_MIXTURE, self.n_components, hip.ptr(a), hip.ptr(b), 0.0, 0.0)
 
 
+
+class BayesianLogisticRegression(Potential):
+    """Bayesian logistic regression, labels y in {0, 1}, prior theta ~ N(0, prior_scale^2 I):
+        U(theta) = sum_i [softplus(z_i) - y_i z_i] + |theta|^2 / (2 prior_scale^2),   z = X theta,
+        softplus(z) = max(z, 0) + log1p(exp(-|z|))   (finite for every finite z; constants dropped).
+    X (N, d), y (N,) of bools or numbers; an intercept is a column of ones in X.  The fused kernels evaluate it in the mcmc
+    and flow-MH launch families; every other family runs on the split or composed path (`fused_in`).  It is never
+    inferred from a plain callable: pass the object as the target."""
+
+    def __init__(self, X, y, prior_scale=1.0):
+        X = torch.as_tensor(X)
+        if X.dim() != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+            raise ValueError('X must be 2-D (N, d) with N, d >= 1, got shape %s' % (tuple(X.shape),))
+        X = X.detach().to('cpu', torch.float64)
+        if not bool(torch.isfinite(X).all()) or not bool(torch.isfinite(X.float()).all()):
+            raise ValueError('X must be finite, in fp32 too (the kernels read an fp32 copy)')
+        N, d = (int(v) for v in X.shape)
+        y = torch.as_tensor(y).detach().to('cpu')
+        if y.dim() != 1 or y.shape[0] != N:
+            raise ValueError('y must be a vector of N = %d labels, got shape %s' % (N, tuple(y.shape)))
+        y = y.to(torch.float64)
+        if not bool(((y == 0) | (y == 1)).all()):
+            raise ValueError('labels must be 0 or 1')
+        s = float(prior_scale)
+        if not (s > 0 and math.isfinite(s)):
+            raise ValueError('prior_scale must be positive and finite, got %r' % (prior_scale,))
+        iv32 = float(torch.tensor(1.0 / (s * s), dtype=torch.float32))
+        if not (iv32 > 0 and math.isfinite(iv32)):   # the kernels take 1/prior_scale^2 in fp32
+            raise ValueError('1 / prior_scale^2 must be a positive finite fp32 number, prior_scale = %r' % (prior_scale,))
+        self.event_shape = (d,)
+        self.n_rows = N
+        self.X = X.contiguous()          # fp64 masters; the kernels get fp32
+        self.y = y.contiguous()
+        self.prior_scale = s
+        self.inv_var = 1.0 / (s * s)
+        self._dev = {}
+
+    def fused_in(self, family: str) -> bool:
+        return super().fused_in(family) and family in ('mcmc', 'flow_mh')
+
+    def _copy(self, device):
+        """The fp32 (X, y) of `device`, made once per device (every shard of a sharded run gets its own)."""
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = (self.X.float().to(device).contiguous(), self.y.float().to(device).contiguous())
+        return self._dev[key]
+
+    def __call__(self, x):
+        n = x.shape[0]
+        xf = x.reshape(n, -1)
+        if xf.dtype == torch.float32 and xf.is_cuda:
+            X, y = self._copy(xf.device)
+        else:
+            X, y = self.X.to(xf), self.y.to(xf)
+        z = xf @ X.t()                                                            # (n, N)
+        data = torch.sum(torch.clamp(z, min=0) + torch.log1p(torch.exp(-z.abs())) - y * z, dim=1)
+        return data + (0.5 * self.inv_var) * torch.sum(xf * xf, dim=1)
+
+    def descriptor(self, device):
+        X, y = self._copy(device)
+        return hip.NfmcPotential(hip.POT_LOGISTIC_REGRESSION, self.n_rows, hip.ptr(X), hip.ptr(y), self.inv_var, 0.0)
+
 _log = logging.getLogger('nfmc_amd')
 _announced = set()
 
