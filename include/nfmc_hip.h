@@ -55,7 +55,7 @@ enum {
        flow image: a larger K, or a block that does not fit, gets NFMC_EUNSUPPORTED.  Served by nfmc_mala_steps_f32 /
        nfmc_hmc_steps_f32 (general kernels, with or without a jump tail; not the Philox4x32-7 stream) and by the
        register-layout kernels of nfmc_flow_mh_steps_f32; every other entry point answers NFMC_EUNSUPPORTED. */
-    NFMC_POT_LOGISTIC_REGRESSION = 3
+    NFMC_POT_LOGISTIC_REGRESSION = 3,
     /* Bayesian logistic regression over N = n_components data rows, prior x ~ N(0, s^2 I):
          U = sum_i [softplus(z_i) - y_i z_i] + |x|^2 / (2 s^2),  z_i = X_i . x,  softplus(z) = max(z, 0) + log1p(e^-|z|)
          dU/dx = X^T (sigmoid(z) - y) + x / s^2   (constants dropped)
@@ -64,12 +64,23 @@ enum {
        the tile's labels; a flow image that leaves no room for it gets NFMC_EUNSUPPORTED).  Served by nfmc_mala_steps_f32
        / nfmc_hmc_steps_f32 (general kernels, with or without a jump tail; not the Philox4x32-7 stream) and by the
        register-layout kernels of nfmc_flow_mh_steps_f32; every other entry point answers NFMC_EUNSUPPORTED. */
+    NFMC_POT_GAUSSIAN_FULL = 4
+    /* Full-rank Gaussian with precision Lambda (symmetric positive definite) and mean mu:
+         U = 1/2 (x - mu)^T Lambda (x - mu),   dU/dx = Lambda (x - mu)   (constants dropped)
+       a -> Lambda (d, d) fp32 row-major, device memory, 16-byte aligned;  b -> mu (d,) fp32, device memory;
+       n_components = d (a mismatch, a NULL a or b, or a misaligned a is NFMC_EINVAL);  a_scalar / b_scalar unused.
+       Each evaluation streams Lambda through an LDS tile of 16 KB (a flow image that leaves no room for it gets
+       NFMC_EUNSUPPORTED).  Served by nfmc_mala_steps_f32 / nfmc_hmc_steps_f32 (general kernels, with or without a jump
+       tail, device warmup tuning included), by the register-layout kernels of nfmc_flow_mh_steps_f32 and by the VALU
+       NeuTra kernels (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32 with conditioners of at most 32 units).
+       NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the fit kernels, the Philox4x32-7 stream and the
+       NeuTra matrix-core kernels (conditioners wider than 32). */
 };
 
 typedef struct {
     int32_t kind;
-    int32_t n_components; /* NFMC_POT_GAUSSIAN_MIXTURE: K; NFMC_POT_LOGISTIC_REGRESSION: N; 0 for the other kinds
-                             (was `reserved`, same layout) */
+    int32_t n_components; /* NFMC_POT_GAUSSIAN_MIXTURE: K; NFMC_POT_LOGISTIC_REGRESSION: N; NFMC_POT_GAUSSIAN_FULL: d;
+                             0 for the other kinds (was `reserved`, same layout) */
     const float* a; /* (d,) or NULL -> a_scalar */
     const float* b; /* (d,) or NULL -> b_scalar */
     float a_scalar;

@@ -363,11 +363,20 @@ inline int check_logreg(const NfmcPotential& p) {
     return NFMC_OK;
 }
 
-// LDS bytes a register-layout kernel with DP padded coordinates stages for `p` beside its flow image (0 unless kind 2
-// or 3)
+// argument check of a kind-4 descriptor at the entry points that run it (0 for every other kind): Lambda (d, d) and mu
+// (d,) present, n_components = d, Lambda 16-byte aligned
+inline int check_fullrank(const NfmcPotential& p, int d) {
+    if (p.kind != NFMC_POT_GAUSSIAN_FULL) return NFMC_OK;
+    if (!p.a || !p.b || p.n_components != d || (((uintptr_t)p.a) & 15u) != 0) return NFMC_EINVAL;
+    return NFMC_OK;
+}
+
+// LDS bytes a register-layout kernel with DP padded coordinates stages for `p` beside its flow image (0 unless kind 2,
+// 3 or 4)
 inline size_t staged_potential_bytes(const NfmcPotential& p, int dp) {
     if (p.kind == NFMC_POT_GAUSSIAN_MIXTURE) return (size_t)mixture_floats(p.n_components, dp) * sizeof(float);
     if (p.kind == NFMC_POT_LOGISTIC_REGRESSION) return (size_t)logreg_floats(dp) * sizeof(float);
+    if (p.kind == NFMC_POT_GAUSSIAN_FULL) return (size_t)kLogRegTileFloats * sizeof(float);
     return 0;
 }
 
@@ -467,14 +476,31 @@ __device__ __forceinline__ void softplus_sigmoid(float z, float& sp, float& sg) 
     sg = (z >= 0.f ? 1.f : e) * inv;
 }
 
+// All threads of the workgroup: rows t0 .. t0 + rows - 1 of the row-major matrix src (`cols` floats per row) into the
+// kLogRegTileFloats floats of `tile` as (kLogRegTileFloats / DP, DP), zero past column `cols` and past row `rows`.  Opens
+// with the barrier after which no wave reads the previous tile; the caller closes with one after its own stores.
+template <int DP>
+__device__ __forceinline__ void load_tile_rows(float* tile, const float* src, int cols, int t0, int rows) {
+    constexpr int kPer = kLogRegTileFloats / kBlock;   // floats per thread and tile
+    static_assert(kLogRegTileFloats % kBlock == 0, "whole tiles per thread");
+    __syncthreads();   // every wave is done with the previous tile
+    float v[kPer];
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) {   // all loads in flight before the first LDS write
+        const int e = threadIdx.x + k * kBlock, r = e / DP, j = e % DP;
+        v[k] = (j < cols && r < rows) ? src[(int64_t)(t0 + r) * cols + j] : 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) tile[threadIdx.x + k * kBlock] = v[k];
+}
+
 template <int CPL, int LPC, bool FAST>
 struct LogRegPot {
     static constexpr bool kQuadratic = false;
     static constexpr bool kStaged = true;
     static constexpr int DP = CPL * LPC;
     static constexpr int T = kLogRegTileFloats / DP;   // rows per tile
-    static constexpr int kPer = kLogRegTileFloats / kBlock;   // X floats per thread and tile
-    static_assert(T % 4 == 0 && kLogRegTileFloats % kBlock == 0, "batches of 4 rows, whole tiles per thread");
+    static_assert(T % 4 == 0, "batches of 4 rows");
     float* tile;          // LDS: X rows (T, DP) | y (T)
     const float* X;
     const float* y;
@@ -504,15 +530,7 @@ struct LogRegPot {
     }
     // all threads of the workgroup: rows t0 .. t0 + rows - 1 into the tile, zeros past them
     __device__ __forceinline__ void load_tile(int t0, int rows) const {
-        __syncthreads();   // every wave is done with the previous tile
-        float v[kPer];
-#pragma unroll
-        for (int k = 0; k < kPer; ++k) {   // all loads in flight before the first LDS write
-            const int e = threadIdx.x + k * kBlock, r = e / DP, j = e % DP;
-            v[k] = (j < dd && r < rows) ? X[(int64_t)(t0 + r) * dd + j] : 0.f;
-        }
-#pragma unroll
-        for (int k = 0; k < kPer; ++k) tile[threadIdx.x + k * kBlock] = v[k];
+        load_tile_rows<DP>(tile, X, dd, t0, rows);
         for (int r = threadIdx.x; r < T; r += kBlock) tile[T * DP + r] = r < rows ? y[t0 + r] : 0.f;
         __syncthreads();
     }
@@ -588,6 +606,108 @@ struct LogRegPot {
             }
         }
         cx.u = group_allreduce<LPC>((float)(ul + (double)(0.5f * inv_s2 * pr)));
+        return cx;
+    }
+    __device__ __forceinline__ float grad(const Ctx& cx, int i, float) const { return cx.gr[i]; }
+    __device__ __forceinline__ float term(const Ctx& cx, int i, float) const { return (lead && i == 0) ? cx.u : 0.f; }
+};
+
+// Full-rank Gaussian (NFMC_POT_GAUSSIAN_FULL; Lambda (d, d) row-major in a, mu (d,) in b, d = p.n_components):
+//   U = 1/2 r^T Lambda r,   dU/dx = Lambda r,   r = x - mu
+// Lambda streams through the same LDS tile as the logistic regression's X (load_tile_rows: T = kLogRegTileFloats / DP
+// rows of DP floats, zero-padded), so the same rule holds: every thread of the workgroup calls prepare() equally often.
+// One pass over the rows: rows 4 b .. 4 b + 3 of Lambda belong to coordinates 4 b .. 4 b + 3, which are register quad
+// b / LPC of lane b % LPC of the chain.  That lane's four r_i are broadcast to the chain's LPC lanes (ds_bpermute;
+// v_readlane when one chain fills the wave; nothing with one lane per chain), and every lane adds r_i Lambda_ij to its
+// own coordinates j: row i is column i (symmetry), read as one ds_read_b128 per register quad at 4 (q LPC + g) -- the
+// gradient pass of LogRegPot with r_i in place of the residuals, no reduction per row.  U = 1/2 sum_j r_j g_j is
+// lane-local, then ONE group_allreduce.  Padding coordinates have r = 0 and zero rows / columns, so d need not be a
+// multiple of 4.  d^2 FMAs per chain and evaluation, d^2 / LPC per lane.
+template <int CPL, int LPC, bool FAST>
+struct GaussFullPot {
+    static constexpr bool kQuadratic = false;
+    static constexpr bool kStaged = true;
+    static constexpr int DP = CPL * LPC;
+    static constexpr int T = kLogRegTileFloats / DP;   // rows of Lambda per tile
+    static_assert(T % 4 == 0, "whole register quads per tile");
+    float* tile;          // LDS: Lambda rows (T, DP)
+    const float* lam;
+    int dd;
+    int grp;              // byte address of the chain's first lane for ds_bpermute
+    bool lead;            // this lane holds coordinate 0 in register 0
+    float mu[CPL];        // 0 for padding
+    struct Ctx {
+        float u;          // U of the chain (every lane of the group)
+        float gr[CPL];    // dU/dx of this lane's coordinates
+    };
+
+    __device__ __forceinline__ static void stage(float*, const NfmcPotential&, int) {}   // prepare() streams the tiles
+    __device__ __forceinline__ void init(const NfmcPotential& p, int g, int d, float* lds) {
+        tile = lds;
+        lam = p.a;
+        dd = d;
+        grp = 4 * ((int)(threadIdx.x & 63) - g);
+        lead = (g == 0);
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) {
+            const int c = coord_of<CPL, LPC>(g, i);
+            mu[i] = c < d ? p.b[c] : 0.f;
+        }
+    }
+    // value v of lane `src` (uniform) of this lane's chain group
+    __device__ __forceinline__ float from_lane(float v, int src) const {
+        if constexpr (LPC == 1) return v;
+        else if constexpr (LPC == 64) return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
+        else return __int_as_float(__builtin_amdgcn_ds_bpermute(grp + 4 * src, __float_as_int(v)));
+    }
+    __device__ __forceinline__ Ctx prepare(const float (&x)[CPL], int g, int) const {
+        Ctx cx;
+        float r[CPL];
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) {
+            r[i] = coord_of<CPL, LPC>(g, i) < dd ? x[i] - mu[i] : 0.f;
+            cx.gr[i] = 0.f;
+        }
+        for (int t0 = 0; t0 < dd; t0 += T) {
+            const int rows = dd - t0 < T ? dd - t0 : T;
+            load_tile_rows<DP>(tile, lam, dd, t0, rows);
+            __syncthreads();
+            const int b1 = (t0 + rows + 3) >> 2;   // register quads (4 rows each) of this tile: t0 / 4 .. b1 - 1
+            for (int b = t0 >> 2; b < b1;) {
+                const int q = b / LPC;             // the quad's register index, constant over LPC consecutive quads
+                float rq[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int k = 0; k < CPL / 4; ++k)
+                    if (k == q) {
+                        rq[0] = r[4 * k];
+                        rq[1] = r[4 * k + 1];
+                        rq[2] = r[4 * k + 2];
+                        rq[3] = r[4 * k + 3];
+                    }
+                const int bq = b1 < (q + 1) * LPC ? b1 : (q + 1) * LPC;
+                for (; b < bq; ++b) {
+                    const int src = b - q * LPC;   // the lane that holds coordinates 4 b .. 4 b + 3
+                    const float ri[4] = {from_lane(rq[0], src), from_lane(rq[1], src), from_lane(rq[2], src),
+                                         from_lane(rq[3], src)};
+                    const float* rows4 = tile + (4 * b - t0) * DP + 4 * g;
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+#pragma unroll
+                        for (int k = 0; k < CPL / 4; ++k) {
+                            const float4 w = *reinterpret_cast<const float4*>(rows4 + c * DP + 4 * k * LPC);
+                            cx.gr[4 * k] = fmaf(ri[c], w.x, cx.gr[4 * k]);
+                            cx.gr[4 * k + 1] = fmaf(ri[c], w.y, cx.gr[4 * k + 1]);
+                            cx.gr[4 * k + 2] = fmaf(ri[c], w.z, cx.gr[4 * k + 2]);
+                            cx.gr[4 * k + 3] = fmaf(ri[c], w.w, cx.gr[4 * k + 3]);
+                        }
+                    }
+                }
+            }
+        }
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) s = fmaf(r[i], cx.gr[i], s);
+        cx.u = 0.5f * group_allreduce<LPC>(s);
         return cx;
     }
     __device__ __forceinline__ float grad(const Ctx& cx, int i, float) const { return cx.gr[i]; }

@@ -1,0 +1,157 @@
+// flow_mh_b_kernel: the flow-proposal Metropolis transitions of flow_b_kernels.hip, in a header of its own so that the
+// full-rank Gaussian's instantiations (flow_b_fullrank.hip) compile in a translation unit of their own.
+#pragma once
+
+#include "flow_b.hpp"
+
+namespace nfmc {
+
+// DIAG = false is the production instantiation: no replayed noise, no sample store, no mask / log-ratio outputs --
+// the branches on those pointers (and the scalar registers that carry them through the tile loop: the DIAG kernel
+// spills SGPRs into VGPR lanes there) are compiled out.  The host picks it when all of those arguments are NULL.
+// NB = 8: rational-quadratic spline couplings ('c-rqnsf') on the same skeleton (round 3; before, spline flows ran the jump on
+// the one-chain-per-lane kernel of flow_kernels.hip only).
+template <int CPL, int LPC, int HP, template <int, int, bool> class Pot, bool FAST, bool DIAG, int RR = 10, int NB = 0>
+#ifndef NFMC_FLOWB_WPE
+#define NFMC_FLOWB_WPE 1
+#endif
+__global__ void __launch_bounds__(kBlock, NFMC_FLOWB_WPE) flow_mh_b_kernel(NfmcFlowMhArgs a, int64_t tiles) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr int CPW = kWave / LPC;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int g = lane % LPC, cw = lane / LPC;
+    const int d = a.flow.d;
+    const int64_t n = a.n;
+    using Flow = FlowB<CPL, LPC, HP, false, (FAST && CPL >= 8), NB>;
+    Flow::Img::stage(lds, a.flow, kBlock);
+    __syncthreads();
+    Flow fl;
+    fl.init(lds, a.flow, g);
+    Pot<CPL, LPC, FAST> pot;
+    if constexpr (Pot<CPL, LPC, FAST>::kStaged)
+        init_staged(pot, a.pot, g, d, lds, Flow::Img::total_floats(a.flow.n_hidden_layers, a.flow.n_coupling));
+    else
+        pot.init(a.pot, g, d);
+    const bool revl = (a.flow.n_coupling & 1) != 0;
+    const float base_c = -0.5f * (float)d * kLog2Pi;
+
+    float sx[CPL], sxx[CPL];
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) sx[i] = sxx[i] = 0.f;
+    uint32_t n_acc = 0, n_bad = 0;
+    const unsigned long long leaders = LPC == 64 ? 1ull : (LPC == 32 ? 0x0000000100000001ull
+                                       : LPC == 16 ? 0x0001000100010001ull
+                                       : LPC == 8 ? 0x0101010101010101ull
+                                       : LPC == 4 ? 0x1111111111111111ull
+                                       : LPC == 2 ? 0x5555555555555555ull : ~0ull);
+
+    for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int64_t row = (tile * kWavesPerBlock + wave) * CPW + cw;
+        const bool active = row < n;
+        const uint32_t gchain = (uint32_t)(a.rng.chain_offset + (uint64_t)row);
+        float x[CPL];
+        load_row<CPL, LPC, FAST>(a.x, row, d, g, active, x);
+        float u_x;
+        {
+            const auto ctx = pot.prepare(x, g, d);
+            float up = 0.f;
+#pragma unroll
+            for (int i = 0; i < CPL; ++i) up += pot.term(ctx, i, x[i]);
+            u_x = group_allreduce<LPC>(up);                                  // jump.py:212 / imh.py:224
+        }
+        float f_x;
+        if (a.logq_cached) {
+            f_x = active ? a.logq[row] : 0.f;
+        } else {                                                             // flow.log_prob(x): jump.py:218 / imh.py:214
+            float w[CPL];
+#pragma unroll
+            for (int i = 0; i < CPL; ++i) w[i] = x[i];
+            float part = fl.forward(w);
+#pragma unroll
+            for (int i = 0; i < CPL; ++i) part = fmaf(-0.5f * w[i], w[i], part);
+            f_x = group_allreduce<LPC>(part) + base_c;
+        }
+        StoreCursor keep(a.samples);
+        for (int s = 0; s < a.n_steps; ++s) {
+            float xp[CPL];
+            draw_latent<CPL, LPC, FAST, RR>(xp, (DIAG && a.rng.replay_normals) ? a.rng.replay_normals + (int64_t)s * n * d : nullptr, a.rng.seed,
+                                  a.rng.step0 + (uint32_t)s, gchain, row, n, d, g, revl);  // flow.sample: jump.py:205 / imh.py:221
+            float part = 0.f;
+#pragma unroll
+            for (int i = 0; i < CPL; ++i) part = fmaf(-0.5f * xp[i], xp[i], part);
+            part -= fl.inverse(xp);
+            const float f_xp = group_allreduce<LPC>(part) + base_c;
+            float up = 0.f;
+            {
+                const auto ctx = pot.prepare(xp, g, d);
+#pragma unroll
+                for (int i = 0; i < CPL; ++i) up += pot.term(ctx, i, xp[i]);
+            }
+            const float u_xp = group_allreduce<LPC>(up);                     // jump.py:213 / imh.py:225
+            const float lr = (-u_xp) - (-u_x) + f_x - f_xp;                  // util.py:392
+            bool accept = true;
+            if (a.adjusted) {
+                float u;
+                if (DIAG && a.rng.replay_uniforms) {
+                    u = active ? a.rng.replay_uniforms[(int64_t)s * n + row] : 0.5f;
+                } else {
+                    const uint4 r = philox4x32<RR>(gchain, a.rng.step0 + (uint32_t)s, 0u, kTagJump, (uint32_t)a.rng.seed,
+                                                  (uint32_t)(a.rng.seed >> 32));
+                    u = u32_to_uniform(r.x);
+                }
+                accept = fast_ln(u) < lr;                                     // jump.py:225 / imh.py:229-230
+                n_bad += (uint32_t)__popcll(__ballot(active && !(fabsf(lr) <= 3.0e38f)) & leaders);
+            }
+            accept = accept && active;
+            const uint64_t am = __ballot(accept);
+            n_acc += (uint32_t)__popcll(am & leaders);
+            f_x = select_f32(am, f_xp, f_x);
+            u_x = select_f32(am, u_xp, u_x);
+#pragma unroll
+            for (int i = 0; i < CPL; ++i) {
+                x[i] = select_f32(am, xp[i], x[i]);                                // jump.py:231 / imh.py:232-233
+                sx[i] += x[i];
+                sxx[i] = fmaf(x[i], x[i], sxx[i]);
+            }
+            if constexpr (DIAG) {
+                if (float* kept = keep.next(n * d)) store_row<CPL, LPC, FAST>(kept, row, d, g, active, x);
+            }
+            if (DIAG && g == 0 && active) {
+                if (a.masks_out) a.masks_out[(int64_t)s * n + row] = accept ? 1 : 0;
+                if (a.log_ratio_out) a.log_ratio_out[(int64_t)s * n + row] = lr;
+            }
+        }
+        store_row<CPL, LPC, FAST>(a.x, row, d, g, active, x);
+        if (g == 0 && active) a.logq[row] = f_x;
+    }
+    if (a.stats.sum_x) block_stats_flush<CPL, LPC>(sx, sxx, n_acc, n_bad, a.stats);
+}
+
+// the register layouts (CPL, LPC) of the flow-MH kernels (kBCfgs, flow_b_kernels.hip)
+#define NFMC_FOR_BCFG(M) M(4, 1) M(4, 2) M(4, 4) M(4, 8) M(8, 8) M(4, 16) M(8, 16) M(4, 32) M(8, 32) M(4, 64) M(8, 64)
+
+// kind 4 (GaussFullPot) at layout (cpl, lpc), conditioner bucket hp (4 / 8), affine or spline (rqs) couplings; the
+// arguments and NFMC_EUNSUPPORTED / dry as in flow_mh_b_launch.  Defined in flow_b_fullrank.hip (the spline couplings in
+// flow_b_fullrank_rqs.hip): one instantiation per layout and width, diagnostics compiled in, default stream.
+int flow_mh_b_fullrank(const NfmcFlowMhArgs& a, int cpl, int lpc, int hp, bool rqs, int64_t tiles, int grid, hipStream_t st,
+                       bool dry);
+int flow_mh_b_fullrank_rqs(const NfmcFlowMhArgs& a, int cpl, int lpc, int hp, int64_t tiles, int grid, hipStream_t st,
+                           bool dry);
+
+template <int CPL, int LPC, int HP, int NB>
+int launch_b_fullrank(const NfmcFlowMhArgs& a, int64_t tiles, int grid, hipStream_t st, bool dry) {
+    const size_t img =
+        (size_t)FlowImage<CPL, LPC, HP, false, NB>::total_floats(a.flow.n_hidden_layers, a.flow.n_coupling) * sizeof(float);
+    const size_t lds = lds_with_potential(img, a.pot, CPL * LPC);
+    if (lds > 120 * 1024 || rng_rounds(a.rng) != 10) return NFMC_EUNSUPPORTED;
+    if (dry) return 0;
+    auto kern = flow_mh_b_kernel<CPL, LPC, HP, GaussFullPot, false, true, 10, NB>;
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, a, tiles);
+    return 0;
+}
+
+}  // namespace nfmc

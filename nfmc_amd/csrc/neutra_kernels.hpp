@@ -150,6 +150,43 @@ __device__ __forceinline__ void coupling_inverse_backward(float* __restrict__ wr
     }
 }
 
+// Full-rank Gaussian (NFMC_POT_GAUSSIAN_FULL) for the row of one chain, as potential_value_grad_row:
+//   U = 1/2 r^T Lambda r,   grow = Lambda r,   r = x - mu
+// Lambda and mu are wave-uniform, so the compiler reads them with scalar loads.  A block of kFullRankJB outputs stays in
+// registers while the loop runs over i: one LDS read of x_i feeds kFullRankJB FMAs with row i of Lambda (= column i, by
+// symmetry).  Kept out of potential_value_grad_row, which the fit and DLMC kernels share and which never see kind 4.
+constexpr int kFullRankJB = 8;
+__device__ __forceinline__ float fullrank_value_grad_row(const float* __restrict__ row, float* __restrict__ grow,
+                                                         const NfmcPotential& p, int d) {
+    const float* __restrict__ lam = p.a;
+    const float* __restrict__ mu = p.b;
+    float u = 0.f;
+    int j0 = 0;
+    for (; j0 + kFullRankJB <= d; j0 += kFullRankJB) {
+        float acc[kFullRankJB];
+#pragma unroll
+        for (int k = 0; k < kFullRankJB; ++k) acc[k] = 0.f;
+        for (int i = 0; i < d; ++i) {
+            const float ri = row[i] - mu[i];
+            const float* __restrict__ li = lam + (int64_t)i * d + j0;
+#pragma unroll
+            for (int k = 0; k < kFullRankJB; ++k) acc[k] = fmaf(li[k], ri, acc[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < kFullRankJB; ++k) {
+            grow[j0 + k] = acc[k];
+            u = fmaf(row[j0 + k] - mu[j0 + k], acc[k], u);
+        }
+    }
+    for (; j0 < d; ++j0) {   // the last d % kFullRankJB outputs
+        float acc = 0.f;
+        for (int i = 0; i < d; ++i) acc = fmaf(lam[(int64_t)i * d + j0], row[i] - mu[i], acc);
+        grow[j0] = acc;
+        u = fmaf(row[j0] - mu[j0], acc, u);
+    }
+    return 0.5f * u;
+}
+
 // U~(z) and grad U~(z) for this lane's chain.  zrow: latent (tile columns in latent order), read only;
 // wrow: scratch, ends holding z again (rebuilt); grow: gradient in the same column order as zrow.
 template <int HP>
@@ -158,7 +195,8 @@ __device__ __forceinline__ float adjusted_potential_grad_row(const float* __rest
                                                              const FlowGeom& g, const NfmcPotential& pot) {
     for (int c = 0; c < g.d; ++c) wrow[c] = zrow[c];
     const float ld = flow_inverse_row<HP>(wrow, f, g);          // w = x, ld = logdet_inverse (neutra.py:60)
-    const float u = potential_value_grad_row(wrow, grow, pot, g.d);  // U(x), dU/dx (neutra.py:62)
+    const float u = pot.kind == NFMC_POT_GAUSSIAN_FULL ? fullrank_value_grad_row(wrow, grow, pot, g.d)
+                                                       : potential_value_grad_row(wrow, grow, pot, g.d);  // U(x), dU/dx (neutra.py:62)
     // reverse sweep, mirror image of flow_inverse_row
     for (int c = 0; c < g.d; ++c) {                               // EA0^-1
         const float s = fast_exp(-f.ea0_log_scale[c]);

@@ -521,29 +521,56 @@ struct Cfg {
 
 // The layouts choose_cfg picks without the NFMC_SAMPLER_CFG override: the smallest capacity CPL * LPC >= d, at equal
 // capacity the first in kCfgs.  (4, 16), (16, 4), (16, 8), (16, 16) and (16, 32) tie with an earlier layout and are
-// reachable only through the override; LogRegPot is not instantiated there (the override skips them for kind 3).
+// reachable only through the override; LogRegPot and GaussFullPot are not instantiated there (the override skips them
+// for kinds 3 and 4).
 constexpr bool is_default_cfg(int cpl, int lpc) {
     return !((cpl == 4 && lpc == 16) || (cpl == 16 && lpc != 64));
+}
+
+// dynamic LDS of a launch: the jump tail's flow image, then the potential's block (the mixture's parameters / the tile
+// of X or Lambda) behind it
+template <int CPL, int LPC, int JHP>
+size_t sampler_lds(const NfmcPotential& p, const JumpDev& jd) {
+    size_t lds = 0;
+    if constexpr (JHP > 0)
+        lds = (size_t)FlowImage<CPL, LPC, JHP>::total_floats(jd.flow.n_hidden_layers, jd.flow.n_coupling) * sizeof(float);
+    return lds_with_potential(lds, p, CPL * LPC);
+}
+
+template <int CPL, int LPC, template <int, int, bool> class POT, bool F, int JHP>
+int launch_mala_kernel(const NfmcMalaArgs& a, const JumpDev& jd, size_t lds, int64_t tiles, int grid, float sqrt2h,
+                       hipStream_t st) {
+    auto kern = mala_kernel<CPL, LPC, POT, F, JHP>;
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, a, sqrt2h, tiles, jd);
+    return NFMC_OK;
+}
+
+template <int CPL, int LPC, template <int, int, bool> class POT, bool F, int JHP>
+int launch_hmc_kernel(const NfmcHmcArgs& a, const JumpDev& jd, size_t lds, int64_t tiles, int grid, hipStream_t st) {
+    auto kern = hmc_kernel<CPL, LPC, POT, F, JHP>;
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, a, tiles, jd);
+    return NFMC_OK;
 }
 
 template <int CPL, int LPC, int JHP>
 int launch_mala_cfg(const NfmcMalaArgs& a, const JumpDev& jd, bool fast, int64_t tiles, int grid, float sqrt2h,
                     hipStream_t st) {
-    size_t lds = 0;
-    if constexpr (JHP > 0)
-        lds = (size_t)FlowImage<CPL, LPC, JHP>::total_floats(jd.flow.n_hidden_layers, jd.flow.n_coupling) * sizeof(float);
-    lds = lds_with_potential(lds, a.pot, CPL * LPC);   // the mixture's parameter block / the X tile behind the image
+    const size_t lds = sampler_lds<CPL, LPC, JHP>(a.pot, jd);
     if (lds > 120 * 1024) return NFMC_EUNSUPPORTED;
     // no per-step output and no replay: the FAST quadratic kernels without a jump tail have a LEAN instantiation
     const bool lean = !a.masks_out && !a.log_ratio_out && !a.samples.base && !a.rng.replay_normals && !a.rng.replay_uniforms;
 #define NFMC_L(POT, F)                                                                                            \
     {                                                                                                             \
-        auto kern = mala_kernel<CPL, LPC, POT, F, JHP>;                                                           \
-        if (lds > 48 * 1024) {                                                                                    \
-            hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            if (e != hipSuccess) return (int)e;                                                                   \
-        }                                                                                                         \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, a, sqrt2h, tiles, jd);                        \
+        const int rc_ = launch_mala_kernel<CPL, LPC, POT, F, JHP>(a, jd, lds, tiles, grid, sqrt2h, st);           \
+        if (rc_) return rc_;                                                                                      \
     }
     if (rng_rounds(a.rng) == 7) {   // opt-in Philox4x32-7 stream: the exact-fit quadratic kernel without a jump tail
         if constexpr (JHP == 0) {
@@ -564,6 +591,8 @@ int launch_mala_cfg(const NfmcMalaArgs& a, const JumpDev& jd, bool fast, int64_t
         } else {
             return NFMC_EUNSUPPORTED;   // not reached: choose_cfg never picks this layout for kind 3
         }
+    } else if (a.pot.kind == NFMC_POT_GAUSSIAN_FULL) {
+        return NFMC_EUNSUPPORTED;   // not reached: kind 4 launches from sampler_fullrank_*.hip
     } else if (a.pot.kind == NFMC_POT_FUNNEL) {
         if (fast) NFMC_L(FunnelPot, true) else NFMC_L(FunnelPot, false)
     } else {
@@ -582,19 +611,12 @@ int launch_mala_cfg(const NfmcMalaArgs& a, const JumpDev& jd, bool fast, int64_t
 
 template <int CPL, int LPC, int JHP>
 int launch_hmc_cfg(const NfmcHmcArgs& a, const JumpDev& jd, bool fast, int64_t tiles, int grid, hipStream_t st) {
-    size_t lds = 0;
-    if constexpr (JHP > 0)
-        lds = (size_t)FlowImage<CPL, LPC, JHP>::total_floats(jd.flow.n_hidden_layers, jd.flow.n_coupling) * sizeof(float);
-    lds = lds_with_potential(lds, a.pot, CPL * LPC);   // the mixture's parameter block / the X tile behind the image
+    const size_t lds = sampler_lds<CPL, LPC, JHP>(a.pot, jd);
     if (lds > 120 * 1024) return NFMC_EUNSUPPORTED;
 #define NFMC_L(POT, F)                                                                                            \
     {                                                                                                             \
-        auto kern = hmc_kernel<CPL, LPC, POT, F, JHP>;                                                            \
-        if (lds > 48 * 1024) {                                                                                    \
-            hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            if (e != hipSuccess) return (int)e;                                                                   \
-        }                                                                                                         \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, a, tiles, jd);                                \
+        const int rc_ = launch_hmc_kernel<CPL, LPC, POT, F, JHP>(a, jd, lds, tiles, grid, st);                    \
+        if (rc_) return rc_;                                                                                      \
     }
     if (rng_rounds(a.rng) == 7) {
         if constexpr (JHP == 0) {
@@ -614,6 +636,8 @@ int launch_hmc_cfg(const NfmcHmcArgs& a, const JumpDev& jd, bool fast, int64_t t
         } else {
             return NFMC_EUNSUPPORTED;   // not reached: choose_cfg never picks this layout for kind 3
         }
+    } else if (a.pot.kind == NFMC_POT_GAUSSIAN_FULL) {
+        return NFMC_EUNSUPPORTED;   // not reached: kind 4 launches from sampler_fullrank_*.hip
     } else if (a.pot.kind == NFMC_POT_FUNNEL) {
         if (fast) NFMC_L(FunnelPot, true) else NFMC_L(FunnelPot, false)
     } else {
@@ -623,11 +647,29 @@ int launch_hmc_cfg(const NfmcHmcArgs& a, const JumpDev& jd, bool fast, int64_t t
     return NFMC_OK;
 }
 
+// kind 4 (GaussFullPot): its own translation units (sampler_fullrank_*.hip), the layouts kind 3 gets, general kernels
+// on the default Philox4x32-10 stream only
+template <int CPL, int LPC, int JHP>
+int launch_mala_fullrank_cfg(const NfmcMalaArgs& a, const JumpDev& jd, int64_t tiles, int grid, float sqrt2h,
+                             hipStream_t st) {
+    const size_t lds = sampler_lds<CPL, LPC, JHP>(a.pot, jd);
+    if (lds > 120 * 1024 || rng_rounds(a.rng) != 10) return NFMC_EUNSUPPORTED;
+    return launch_mala_kernel<CPL, LPC, GaussFullPot, false, JHP>(a, jd, lds, tiles, grid, sqrt2h, st);
+}
+template <int CPL, int LPC, int JHP>
+int launch_hmc_fullrank_cfg(const NfmcHmcArgs& a, const JumpDev& jd, int64_t tiles, int grid, hipStream_t st) {
+    const size_t lds = sampler_lds<CPL, LPC, JHP>(a.pot, jd);
+    if (lds > 120 * 1024 || rng_rounds(a.rng) != 10) return NFMC_EUNSUPPORTED;
+    return launch_hmc_kernel<CPL, LPC, GaussFullPot, false, JHP>(a, jd, lds, tiles, grid, st);
+}
+
 // all sampler layouts (JHP == 0) / the layouts shared with flow_b (JHP > 0)
 #define NFMC_FOR_CFG(M)                                                                                             \
     M(4, 1) M(4, 2) M(4, 4) M(4, 8) M(4, 16) M(8, 8) M(16, 4) M(8, 16) M(16, 8) M(8, 32) M(16, 16) M(8, 64) M(16, 32) \
         M(16, 64)
 #define NFMC_FOR_BCFG(M) M(4, 1) M(4, 2) M(4, 4) M(4, 8) M(8, 8) M(8, 16) M(8, 32) M(8, 64)
+// the layouts choose_cfg picks by default (is_default_cfg) among NFMC_FOR_CFG
+#define NFMC_FOR_DEFAULT_CFG(M) M(4, 1) M(4, 2) M(4, 4) M(4, 8) M(8, 8) M(8, 16) M(8, 32) M(8, 64) M(16, 64)
 
 // defined in sampler_mala_j*.hip / sampler_hmc_j*.hip
 int launch_mala_j0(const NfmcMalaArgs&, const JumpDev&, Cfg, bool, int64_t, int, float, hipStream_t);
@@ -636,5 +678,8 @@ int launch_mala_j8(const NfmcMalaArgs&, const JumpDev&, Cfg, bool, int64_t, int,
 int launch_hmc_j0(const NfmcHmcArgs&, const JumpDev&, Cfg, bool, int64_t, int, hipStream_t);
 int launch_hmc_j4(const NfmcHmcArgs&, const JumpDev&, Cfg, bool, int64_t, int, hipStream_t);
 int launch_hmc_j8(const NfmcHmcArgs&, const JumpDev&, Cfg, bool, int64_t, int, hipStream_t);
+// defined in sampler_fullrank_mala.hip / sampler_fullrank_hmc.hip: kind 4 at layout c, jump-tail width jhp (0, 4, 8)
+int launch_mala_fullrank(const NfmcMalaArgs&, const JumpDev&, Cfg, int, int64_t, int, float, hipStream_t);
+int launch_hmc_fullrank(const NfmcHmcArgs&, const JumpDev&, Cfg, int, int64_t, int, hipStream_t);
 
 }  // namespace nfmc

@@ -1,6 +1,6 @@
 // K1/K2 (+K6, K7): C entry points of the fused Langevin / HMC samplers.  Kernels: sampler_impl.hpp; the
 // template instantiations live in sampler_{mala,hmc}_j{0,4,8}.hip (j = conditioner width of the optional
-// jump tail, 0 = none) so they compile in parallel.
+// jump tail, 0 = none) and, for the full-rank Gaussian, sampler_fullrank_{mala,hmc}.hip, so they compile in parallel.
 #include "sampler_impl.hpp"
 
 namespace nfmc {
@@ -44,10 +44,11 @@ static int check_common(const Args* a) {
     if (a->d > 1024) return NFMC_ESHAPE;
     if (!(a->step_size > 0.f)) return NFMC_EINVAL;
     if (a->pot.kind != NFMC_POT_QUADRATIC && a->pot.kind != NFMC_POT_FUNNEL && a->pot.kind != NFMC_POT_GAUSSIAN_MIXTURE &&
-        a->pot.kind != NFMC_POT_LOGISTIC_REGRESSION)
+        a->pot.kind != NFMC_POT_LOGISTIC_REGRESSION && a->pot.kind != NFMC_POT_GAUSSIAN_FULL)
         return NFMC_EUNSUPPORTED;
     if (int rc = check_mixture(a->pot)) return rc;
     if (int rc = check_logreg(a->pot)) return rc;
+    if (int rc = check_fullrank(a->pot, a->d)) return rc;
     if (((uintptr_t)a->x & 3u) != 0) return NFMC_EALIGN;
     if (!store_ok(a->samples)) return NFMC_EINVAL;
     if (!rng_rounds_ok(a->rng, true)) return NFMC_EINVAL;
@@ -258,6 +259,26 @@ static int check_tune(const Args& a) {
     return NFMC_OK;
 }
 
+// the potentials instantiated at the default layouts only (is_default_cfg)
+static bool default_cfg_only(const NfmcPotential& p) {
+    return p.kind == NFMC_POT_LOGISTIC_REGRESSION || p.kind == NFMC_POT_GAUSSIAN_FULL;
+}
+
+// one launch of the mala / hmc kernels at layout c with jump-tail width jhp: kind 4 has translation units of its own
+static int launch_mala(const NfmcMalaArgs& a, const JumpDev& jd, Cfg c, int jhp, bool fast, int64_t tiles, int grid,
+                       float sqrt2h, hipStream_t st) {
+    if (a.pot.kind == NFMC_POT_GAUSSIAN_FULL) return launch_mala_fullrank(a, jd, c, jhp, tiles, grid, sqrt2h, st);
+    return jhp == 0 ? launch_mala_j0(a, jd, c, fast, tiles, grid, sqrt2h, st)
+                    : (jhp == 4 ? launch_mala_j4(a, jd, c, fast, tiles, grid, sqrt2h, st)
+                                : launch_mala_j8(a, jd, c, fast, tiles, grid, sqrt2h, st));
+}
+static int launch_hmc(const NfmcHmcArgs& a, const JumpDev& jd, Cfg c, int jhp, bool fast, int64_t tiles, int grid,
+                      hipStream_t st) {
+    if (a.pot.kind == NFMC_POT_GAUSSIAN_FULL) return launch_hmc_fullrank(a, jd, c, jhp, tiles, grid, st);
+    return jhp == 0 ? launch_hmc_j0(a, jd, c, fast, tiles, grid, st)
+                    : (jhp == 4 ? launch_hmc_j4(a, jd, c, fast, tiles, grid, st) : launch_hmc_j8(a, jd, c, fast, tiles, grid, st));
+}
+
 static JumpDev jump_dev(const NfmcJumpTail* j) {
     JumpDev jd = {};
     if (j) {
@@ -291,7 +312,7 @@ extern "C" int nfmc_mala_steps_f32(const NfmcMalaArgs* args, nfmc_stream_t strea
     NfmcMalaArgs a = *args;
     hipStream_t st = (hipStream_t)stream;
     const int jhp = a.jump ? (a.jump->flow.n_hidden <= 4 ? 4 : 8) : 0;
-    const Cfg c = choose_cfg(a.d, jhp > 0, a.pot.kind == NFMC_POT_LOGISTIC_REGRESSION);
+    const Cfg c = choose_cfg(a.d, jhp > 0, default_cfg_only(a.pot));
     if (!c.cpl) return NFMC_ESHAPE;
     const bool fast = fast_path(&a, c);
     const int dp = c.cpl * c.lpc;
@@ -320,7 +341,7 @@ extern "C" int nfmc_mala_steps_f32(const NfmcMalaArgs* args, nfmc_stream_t strea
             if (a.rng.replay_uniforms) b.rng.replay_uniforms = a.rng.replay_uniforms + (int64_t)s0 * a.n;
             if (a.masks_out) b.masks_out = a.masks_out + (int64_t)s0 * a.n;
             if (a.log_ratio_out) b.log_ratio_out = a.log_ratio_out + (int64_t)s0 * a.n;
-            rc = launch_mala_j0(b, jd, c, fast, tiles, grid, sqrt2h, st);
+            rc = launch_mala(b, jd, c, 0, fast, tiles, grid, sqrt2h, st);
             if (rc) return rc;
             tune_update(a.stats, a.tune, grid, two_level, dp, a.d, (unsigned long long)a.n * (unsigned long long)k, st);
             NFMC_HIP_CHECK_LAUNCH();
@@ -328,9 +349,7 @@ extern "C" int nfmc_mala_steps_f32(const NfmcMalaArgs* args, nfmc_stream_t strea
         }
         return NFMC_OK;
     }
-    rc = jhp == 0 ? launch_mala_j0(a, jd, c, fast, tiles, grid, sqrt2h, st)
-                  : (jhp == 4 ? launch_mala_j4(a, jd, c, fast, tiles, grid, sqrt2h, st)
-                              : launch_mala_j8(a, jd, c, fast, tiles, grid, sqrt2h, st));
+    rc = launch_mala(a, jd, c, jhp, fast, tiles, grid, sqrt2h, st);
     if (rc) return rc;
     NFMC_HIP_CHECK_LAUNCH();
     if (a.stats.sum_x && !a.stats.defer) {
@@ -349,7 +368,7 @@ extern "C" int nfmc_hmc_steps_f32(const NfmcHmcArgs* args, nfmc_stream_t stream)
     NfmcHmcArgs a = *args;
     hipStream_t st = (hipStream_t)stream;
     const int jhp = a.jump ? (a.jump->flow.n_hidden <= 4 ? 4 : 8) : 0;
-    const Cfg c = choose_cfg(a.d, jhp > 0, a.pot.kind == NFMC_POT_LOGISTIC_REGRESSION);
+    const Cfg c = choose_cfg(a.d, jhp > 0, default_cfg_only(a.pot));
     if (!c.cpl) return NFMC_ESHAPE;
     const bool fast = fast_path(&a, c);
     const int dp = c.cpl * c.lpc;
@@ -376,7 +395,7 @@ extern "C" int nfmc_hmc_steps_f32(const NfmcHmcArgs* args, nfmc_stream_t stream)
             if (a.rng.replay_uniforms) b.rng.replay_uniforms = a.rng.replay_uniforms + (int64_t)s0 * a.n;
             if (a.masks_out) b.masks_out = a.masks_out + (int64_t)s0 * a.n;
             if (a.log_ratio_out) b.log_ratio_out = a.log_ratio_out + (int64_t)s0 * a.n;
-            rc = launch_hmc_j0(b, jd, c, fast, tiles, grid, st);
+            rc = launch_hmc(b, jd, c, 0, fast, tiles, grid, st);
             if (rc) return rc;
             tune_update(a.stats, a.tune, grid, two_level, dp, a.d, (unsigned long long)a.n * (unsigned long long)k, st);
             NFMC_HIP_CHECK_LAUNCH();
@@ -384,8 +403,7 @@ extern "C" int nfmc_hmc_steps_f32(const NfmcHmcArgs* args, nfmc_stream_t stream)
         }
         return NFMC_OK;
     }
-    rc = jhp == 0 ? launch_hmc_j0(a, jd, c, fast, tiles, grid, st)
-                  : (jhp == 4 ? launch_hmc_j4(a, jd, c, fast, tiles, grid, st) : launch_hmc_j8(a, jd, c, fast, tiles, grid, st));
+    rc = launch_hmc(a, jd, c, jhp, fast, tiles, grid, st);
     if (rc) return rc;
     NFMC_HIP_CHECK_LAUNCH();
     if (a.stats.sum_x && !a.stats.defer) {

@@ -295,6 +295,86 @@ class BayesianLogisticRegression(Potential):
         X, y = self._copy(device)
         return hip.NfmcPotential(hip.POT_LOGISTIC_REGRESSION, self.n_rows, hip.ptr(X), hip.ptr(y), self.inv_var, 0.0)
 
+
+class FullRankGaussian(Potential):
+    """Gaussian with a full (correlated) covariance:  U(x) = 1/2 (x - mu)^T Lambda (x - mu),  grad U = Lambda (x - mu),
+    Lambda the precision matrix (constants dropped).  Give exactly one of `covariance` / `precision`, a (d, d) symmetric
+    positive-definite matrix; `mu` has d entries; `event_shape` (default (d,)) has d elements and flattens row-major as
+    for the other potentials.  Validated in fp64 on the host: finite, symmetric to a relative 1e-6 of its largest entry
+    (then symmetrised), positive definite (the Cholesky factorisation succeeds), and Lambda finite in fp32 (the kernels
+    read an fp32 copy).  A covariance is inverted through its fp64 Cholesky factor.  The fused kernels evaluate it in the
+    mcmc, flow-MH and NeuTra launch families (NeuTra on its VALU kernels, conditioners of at most 32 units); every other
+    family runs on the split or composed path (`fused_in`).  It is never inferred from a plain callable: pass the object
+    as the target."""
+
+    SYMMETRY_RTOL = 1e-6
+
+    def __init__(self, mu, covariance=None, precision=None, event_shape=None):
+        if (covariance is None) == (precision is None):
+            raise ValueError('give exactly one of covariance / precision')
+        name = 'covariance' if covariance is not None else 'precision'
+        m = torch.as_tensor(covariance if covariance is not None else precision).detach().to('cpu', torch.float64)
+        if m.dim() != 2 or m.shape[0] != m.shape[1] or m.shape[0] < 1:
+            raise ValueError('%s must be a square (d, d) matrix with d >= 1, got shape %s' % (name, tuple(m.shape)))
+        d = int(m.shape[0])
+        if not bool(torch.isfinite(m).all()):
+            raise ValueError('%s must be finite' % name)
+        scale = float(m.abs().max())
+        if float((m - m.t()).abs().max()) > self.SYMMETRY_RTOL * scale:
+            raise ValueError('%s must be symmetric (to a relative %g of its largest entry)' % (name, self.SYMMETRY_RTOL))
+        m = 0.5 * (m + m.t())
+        chol, info = torch.linalg.cholesky_ex(m)
+        if int(info) != 0:
+            raise ValueError('%s must be positive definite (its Cholesky factorisation fails)' % name)
+        mu = torch.as_tensor(mu).detach().to('cpu', torch.float64).reshape(-1)
+        if mu.numel() != d:
+            raise ValueError('mu must have d = %d entries, got %d' % (d, mu.numel()))
+        if not bool(torch.isfinite(mu).all()):
+            raise ValueError('mu must be finite')
+        if event_shape is None:
+            event_shape = (d,)
+        elif isinstance(event_shape, int):
+            event_shape = (event_shape,)
+        self.event_shape = tuple(int(v) for v in event_shape)
+        if self.event_size != d:
+            raise ValueError('event_shape %s must have d = %d elements' % (self.event_shape, d))
+        if covariance is not None:
+            lam = torch.cholesky_inverse(chol)
+            lam = 0.5 * (lam + lam.t())
+        else:
+            lam = m
+        if not bool(torch.isfinite(lam).all()) or not bool(torch.isfinite(lam.float()).all()):
+            raise ValueError('the precision matrix must be finite in fp32 too (the kernels read an fp32 copy)')
+        self.dim = d
+        self.mean = mu.contiguous()          # fp64 masters; the kernels get fp32
+        self.precision = lam.contiguous()
+        self._dev = {}
+
+    def fused_in(self, family: str) -> bool:
+        return super().fused_in(family) and family in ('mcmc', 'flow_mh', 'neutra')
+
+    def _copy(self, device):
+        """The fp32 (Lambda, mu) of `device`, made once per device (every shard of a sharded run gets its own)."""
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = (self.precision.float().to(device).contiguous(), self.mean.float().to(device).contiguous())
+        return self._dev[key]
+
+    def __call__(self, x):
+        n = x.shape[0]
+        xf = x.reshape(n, -1)
+        if xf.dtype == torch.float32 and xf.is_cuda:
+            lam, mu = self._copy(xf.device)
+        else:
+            lam, mu = self.precision.to(xf), self.mean.to(xf)
+        r = xf - mu
+        return 0.5 * torch.sum((r @ lam) * r, dim=1)
+
+    def descriptor(self, device):
+        lam, mu = self._copy(device)
+        return hip.NfmcPotential(hip.POT_GAUSSIAN_FULL, self.dim, hip.ptr(lam), hip.ptr(mu), 0.0, 0.0)
+
+
 _log = logging.getLogger('nfmc_amd')
 _announced = set()
 
