@@ -64,7 +64,7 @@ enum {
        the tile's labels; a flow image that leaves no room for it gets NFMC_EUNSUPPORTED).  Served by nfmc_mala_steps_f32
        / nfmc_hmc_steps_f32 (general kernels, with or without a jump tail; not the Philox4x32-7 stream) and by the
        register-layout kernels of nfmc_flow_mh_steps_f32; every other entry point answers NFMC_EUNSUPPORTED. */
-    NFMC_POT_GAUSSIAN_FULL = 4
+    NFMC_POT_GAUSSIAN_FULL = 4,
     /* Full-rank Gaussian with precision Lambda (symmetric positive definite) and mean mu:
          U = 1/2 (x - mu)^T Lambda (x - mu),   dU/dx = Lambda (x - mu)   (constants dropped)
        a -> Lambda (d, d) fp32 row-major, device memory, 16-byte aligned;  b -> mu (d,) fp32, device memory;
@@ -75,12 +75,24 @@ enum {
        NeuTra kernels (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32 with conditioners of at most 32 units).
        NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the fit kernels, the Philox4x32-7 stream and the
        NeuTra matrix-core kernels (conditioners wider than 32). */
+    NFMC_POT_ROSENBROCK = 5
+    /* Blocked (hybrid) Rosenbrock over the flattened coordinates, split into consecutive blocks of B coordinates (the
+       last one may be shorter); coordinate c is a head when c % B == 0:
+         U = sum_{heads c} a (x_c - mu)^2 + sum_{non-heads c} b (x_c - x_{c-1}^2)^2   (constants dropped)
+         dU/dx_c = [c head] 2a (x_c - mu) + [c non-head] 2b (x_c - x_{c-1}^2) - [c+1 < d non-head] 4b x_c (x_{c+1} - x_c^2)
+       n_components = B (1 <= B <= d);  a_scalar = a > 0, b_scalar = b > 0 (finite);  a -> mu, ONE fp32 in device memory;
+       b unused.  A NULL a, B out of range, or a / b not positive and finite is NFMC_EINVAL.  Served by
+       nfmc_mala_steps_f32 / nfmc_hmc_steps_f32 (general kernels, with or without a jump tail, device warmup tuning
+       included), by the register-layout kernels of nfmc_flow_mh_steps_f32 and by the VALU NeuTra kernels
+       (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32 with conditioners of at most 32 units).
+       NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the fit kernels, the Philox4x32-7 stream and the
+       NeuTra matrix-core kernels (conditioners wider than 32). */
 };
 
 typedef struct {
     int32_t kind;
     int32_t n_components; /* NFMC_POT_GAUSSIAN_MIXTURE: K; NFMC_POT_LOGISTIC_REGRESSION: N; NFMC_POT_GAUSSIAN_FULL: d;
-                             0 for the other kinds (was `reserved`, same layout) */
+                             NFMC_POT_ROSENBROCK: block length; 0 for the other kinds (was `reserved`, same layout) */
     const float* a; /* (d,) or NULL -> a_scalar */
     const float* b; /* (d,) or NULL -> b_scalar */
     float a_scalar;

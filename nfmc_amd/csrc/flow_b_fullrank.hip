@@ -10,7 +10,7 @@ int flow_mh_b_fullrank(const NfmcFlowMhArgs& a, int cpl, int lpc, int hp, bool r
     int rc = NFMC_EUNSUPPORTED;
 #define M(CPL, LPC)                                                                                              \
     if (cpl == CPL && lpc == LPC)                                                                                \
-        rc = hp == 4 ? launch_b_fullrank<CPL, LPC, 4, 0>(a, tiles, grid, st, dry) : launch_b_fullrank<CPL, LPC, 8, 0>(a, tiles, grid, st, dry);
+        rc = hp == 4 ? launch_b_general<GaussFullPot, CPL, LPC, 4, 0>(a, tiles, grid, st, dry) : launch_b_general<GaussFullPot, CPL, LPC, 8, 0>(a, tiles, grid, st, dry);
     NFMC_FOR_BCFG(M)
 #undef M
     return rc;

@@ -8,8 +8,8 @@ int flow_mh_b_fullrank_rqs(const NfmcFlowMhArgs& a, int cpl, int lpc, int hp, in
     int rc = NFMC_EUNSUPPORTED;
 #define M(CPL, LPC)                                                                                              \
     if (cpl == CPL && lpc == LPC)                                                                                \
-        rc = hp == 4 ? launch_b_fullrank<CPL, LPC, 4, kRqsBins>(a, tiles, grid, st, dry)                         \
-                     : launch_b_fullrank<CPL, LPC, 8, kRqsBins>(a, tiles, grid, st, dry);
+        rc = hp == 4 ? launch_b_general<GaussFullPot, CPL, LPC, 4, kRqsBins>(a, tiles, grid, st, dry)                         \
+                     : launch_b_general<GaussFullPot, CPL, LPC, 8, kRqsBins>(a, tiles, grid, st, dry);
     NFMC_FOR_BCFG(M)
 #undef M
     return rc;

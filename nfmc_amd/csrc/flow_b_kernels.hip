@@ -277,6 +277,8 @@ int flow_mh_b_launch(const NfmcFlowMhArgs& a, hipStream_t st, int* grid_out, int
     int rc = NFMC_EUNSUPPORTED;
     if (a.pot.kind == NFMC_POT_GAUSSIAN_FULL) {   // never exact-fit or dual: Lambda and mu are tables
         rc = flow_mh_b_fullrank(a, c.cpl, c.lpc, hp, rqs, tiles, grid, st, dry);
+    } else if (a.pot.kind == NFMC_POT_ROSENBROCK) {   // never exact-fit or dual: mu is a device buffer
+        rc = flow_mh_b_rosenbrock(a, c.cpl, c.lpc, hp, rqs, tiles, grid, st, dry);
     } else {
 #define M(CPL, LPC)                                                                      \
     if (c.cpl == CPL && c.lpc == LPC)                                                    \

@@ -138,14 +138,21 @@ int flow_mh_b_fullrank(const NfmcFlowMhArgs& a, int cpl, int lpc, int hp, bool r
 int flow_mh_b_fullrank_rqs(const NfmcFlowMhArgs& a, int cpl, int lpc, int hp, int64_t tiles, int grid, hipStream_t st,
                            bool dry);
 
-template <int CPL, int LPC, int HP, int NB>
-int launch_b_fullrank(const NfmcFlowMhArgs& a, int64_t tiles, int grid, hipStream_t st, bool dry) {
+// kind 5 (RosenbrockPot), the same way: flow_b_rosenbrock.hip / flow_b_rosenbrock_rqs.hip.  No dual-chain kernel.
+int flow_mh_b_rosenbrock(const NfmcFlowMhArgs& a, int cpl, int lpc, int hp, bool rqs, int64_t tiles, int grid,
+                         hipStream_t st, bool dry);
+int flow_mh_b_rosenbrock_rqs(const NfmcFlowMhArgs& a, int cpl, int lpc, int hp, int64_t tiles, int grid, hipStream_t st,
+                             bool dry);
+
+// one launch of the general (diagnostics compiled in, default stream) register kernel of potential POT
+template <template <int, int, bool> class POT, int CPL, int LPC, int HP, int NB>
+int launch_b_general(const NfmcFlowMhArgs& a, int64_t tiles, int grid, hipStream_t st, bool dry) {
     const size_t img =
         (size_t)FlowImage<CPL, LPC, HP, false, NB>::total_floats(a.flow.n_hidden_layers, a.flow.n_coupling) * sizeof(float);
     const size_t lds = lds_with_potential(img, a.pot, CPL * LPC);
     if (lds > 120 * 1024 || rng_rounds(a.rng) != 10) return NFMC_EUNSUPPORTED;
     if (dry) return 0;
-    auto kern = flow_mh_b_kernel<CPL, LPC, HP, GaussFullPot, false, true, 10, NB>;
+    auto kern = flow_mh_b_kernel<CPL, LPC, HP, POT, false, true, 10, NB>;
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;

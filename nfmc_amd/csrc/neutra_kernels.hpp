@@ -187,6 +187,37 @@ __device__ __forceinline__ float fullrank_value_grad_row(const float* __restrict
     return 0.5f * u;
 }
 
+// Blocked Rosenbrock (NFMC_POT_ROSENBROCK) for the row of one chain, as potential_value_grad_row:
+//   U = sum_{heads c} a (x_c - mu)^2 + sum_{non-heads c} b (x_c - x_{c-1}^2)^2,   c a head when c % B == 0
+// One pass over the row: x_{c-1} and the residual of c (the successor term of c - 1) carry over in registers, so each
+// coordinate reads the row once and writes its gradient once.  Kept out of potential_value_grad_row, which the fit and
+// DLMC kernels share and which never see kind 5.
+__device__ __forceinline__ float rosenbrock_value_grad_row(const float* __restrict__ row, float* __restrict__ grow,
+                                                           const NfmcPotential& p, int d) {
+    const float ca = p.a_scalar, cb = p.b_scalar, mu = p.a[0];
+    const int blk = p.n_components;
+    float u = 0.f, xm = 0.f;
+    int k = 0;   // c % blk
+    for (int c = 0; c < d; ++c) {
+        const float xc = row[c];
+        float gr;
+        if (k == 0) {
+            const float r = xc - mu;
+            u = fmaf(ca * r, r, u);
+            gr = 2.f * ca * r;
+        } else {
+            const float r = fmaf(-xm, xm, xc);
+            u = fmaf(cb * r, r, u);
+            gr = 2.f * cb * r;
+            grow[c - 1] = fmaf(-4.f * cb * xm, r, grow[c - 1]);   // successor term of c - 1
+        }
+        grow[c] = gr;
+        xm = xc;
+        k = k + 1 == blk ? 0 : k + 1;
+    }
+    return u;
+}
+
 // U~(z) and grad U~(z) for this lane's chain.  zrow: latent (tile columns in latent order), read only;
 // wrow: scratch, ends holding z again (rebuilt); grow: gradient in the same column order as zrow.
 template <int HP>
@@ -196,7 +227,8 @@ __device__ __forceinline__ float adjusted_potential_grad_row(const float* __rest
     for (int c = 0; c < g.d; ++c) wrow[c] = zrow[c];
     const float ld = flow_inverse_row<HP>(wrow, f, g);          // w = x, ld = logdet_inverse (neutra.py:60)
     const float u = pot.kind == NFMC_POT_GAUSSIAN_FULL ? fullrank_value_grad_row(wrow, grow, pot, g.d)
-                                                       : potential_value_grad_row(wrow, grow, pot, g.d);  // U(x), dU/dx (neutra.py:62)
+                    : pot.kind == NFMC_POT_ROSENBROCK    ? rosenbrock_value_grad_row(wrow, grow, pot, g.d)
+                                                         : potential_value_grad_row(wrow, grow, pot, g.d);  // U(x), dU/dx (neutra.py:62)
     // reverse sweep, mirror image of flow_inverse_row
     for (int c = 0; c < g.d; ++c) {                               // EA0^-1
         const float s = fast_exp(-f.ea0_log_scale[c]);

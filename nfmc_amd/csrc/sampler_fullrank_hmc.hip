@@ -6,11 +6,11 @@ namespace nfmc {
 int launch_hmc_fullrank(const NfmcHmcArgs& a, const JumpDev& jd, Cfg c, int jhp, int64_t tiles, int grid, hipStream_t st) {
     int rc = NFMC_EUNSUPPORTED;
 #define M0(CPL, LPC) \
-    if (jhp == 0 && c.cpl == CPL && c.lpc == LPC) rc = launch_hmc_fullrank_cfg<CPL, LPC, 0>(a, jd, tiles, grid, st);
+    if (jhp == 0 && c.cpl == CPL && c.lpc == LPC) rc = launch_hmc_general_cfg<GaussFullPot, CPL, LPC, 0>(a, jd, tiles, grid, st);
 #define M4(CPL, LPC) \
-    if (jhp == 4 && c.cpl == CPL && c.lpc == LPC) rc = launch_hmc_fullrank_cfg<CPL, LPC, 4>(a, jd, tiles, grid, st);
+    if (jhp == 4 && c.cpl == CPL && c.lpc == LPC) rc = launch_hmc_general_cfg<GaussFullPot, CPL, LPC, 4>(a, jd, tiles, grid, st);
 #define M8(CPL, LPC) \
-    if (jhp == 8 && c.cpl == CPL && c.lpc == LPC) rc = launch_hmc_fullrank_cfg<CPL, LPC, 8>(a, jd, tiles, grid, st);
+    if (jhp == 8 && c.cpl == CPL && c.lpc == LPC) rc = launch_hmc_general_cfg<GaussFullPot, CPL, LPC, 8>(a, jd, tiles, grid, st);
     NFMC_FOR_DEFAULT_CFG(M0)
     NFMC_FOR_BCFG(M4)
     NFMC_FOR_BCFG(M8)

@@ -6,11 +6,11 @@ namespace nfmc {
 int launch_mala_fullrank(const NfmcMalaArgs& a, const JumpDev& jd, Cfg c, int jhp, int64_t tiles, int grid, float sqrt2h, hipStream_t st) {
     int rc = NFMC_EUNSUPPORTED;
 #define M0(CPL, LPC) \
-    if (jhp == 0 && c.cpl == CPL && c.lpc == LPC) rc = launch_mala_fullrank_cfg<CPL, LPC, 0>(a, jd, tiles, grid, sqrt2h, st);
+    if (jhp == 0 && c.cpl == CPL && c.lpc == LPC) rc = launch_mala_general_cfg<GaussFullPot, CPL, LPC, 0>(a, jd, tiles, grid, sqrt2h, st);
 #define M4(CPL, LPC) \
-    if (jhp == 4 && c.cpl == CPL && c.lpc == LPC) rc = launch_mala_fullrank_cfg<CPL, LPC, 4>(a, jd, tiles, grid, sqrt2h, st);
+    if (jhp == 4 && c.cpl == CPL && c.lpc == LPC) rc = launch_mala_general_cfg<GaussFullPot, CPL, LPC, 4>(a, jd, tiles, grid, sqrt2h, st);
 #define M8(CPL, LPC) \
-    if (jhp == 8 && c.cpl == CPL && c.lpc == LPC) rc = launch_mala_fullrank_cfg<CPL, LPC, 8>(a, jd, tiles, grid, sqrt2h, st);
+    if (jhp == 8 && c.cpl == CPL && c.lpc == LPC) rc = launch_mala_general_cfg<GaussFullPot, CPL, LPC, 8>(a, jd, tiles, grid, sqrt2h, st);
     NFMC_FOR_DEFAULT_CFG(M0)
     NFMC_FOR_BCFG(M4)
     NFMC_FOR_BCFG(M8)

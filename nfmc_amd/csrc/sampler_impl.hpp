@@ -521,8 +521,8 @@ struct Cfg {
 
 // The layouts choose_cfg picks without the NFMC_SAMPLER_CFG override: the smallest capacity CPL * LPC >= d, at equal
 // capacity the first in kCfgs.  (4, 16), (16, 4), (16, 8), (16, 16) and (16, 32) tie with an earlier layout and are
-// reachable only through the override; LogRegPot and GaussFullPot are not instantiated there (the override skips them
-// for kinds 3 and 4).
+// reachable only through the override; LogRegPot, GaussFullPot and RosenbrockPot are not instantiated there (the
+// override skips them for kinds 3, 4 and 5).
 constexpr bool is_default_cfg(int cpl, int lpc) {
     return !((cpl == 4 && lpc == 16) || (cpl == 16 && lpc != 64));
 }
@@ -591,8 +591,8 @@ int launch_mala_cfg(const NfmcMalaArgs& a, const JumpDev& jd, bool fast, int64_t
         } else {
             return NFMC_EUNSUPPORTED;   // not reached: choose_cfg never picks this layout for kind 3
         }
-    } else if (a.pot.kind == NFMC_POT_GAUSSIAN_FULL) {
-        return NFMC_EUNSUPPORTED;   // not reached: kind 4 launches from sampler_fullrank_*.hip
+    } else if (a.pot.kind == NFMC_POT_GAUSSIAN_FULL || a.pot.kind == NFMC_POT_ROSENBROCK) {
+        return NFMC_EUNSUPPORTED;   // not reached: kinds 4 and 5 launch from sampler_{fullrank,rosenbrock}_*.hip
     } else if (a.pot.kind == NFMC_POT_FUNNEL) {
         if (fast) NFMC_L(FunnelPot, true) else NFMC_L(FunnelPot, false)
     } else {
@@ -636,8 +636,8 @@ int launch_hmc_cfg(const NfmcHmcArgs& a, const JumpDev& jd, bool fast, int64_t t
         } else {
             return NFMC_EUNSUPPORTED;   // not reached: choose_cfg never picks this layout for kind 3
         }
-    } else if (a.pot.kind == NFMC_POT_GAUSSIAN_FULL) {
-        return NFMC_EUNSUPPORTED;   // not reached: kind 4 launches from sampler_fullrank_*.hip
+    } else if (a.pot.kind == NFMC_POT_GAUSSIAN_FULL || a.pot.kind == NFMC_POT_ROSENBROCK) {
+        return NFMC_EUNSUPPORTED;   // not reached: kinds 4 and 5 launch from sampler_{fullrank,rosenbrock}_*.hip
     } else if (a.pot.kind == NFMC_POT_FUNNEL) {
         if (fast) NFMC_L(FunnelPot, true) else NFMC_L(FunnelPot, false)
     } else {
@@ -647,20 +647,20 @@ int launch_hmc_cfg(const NfmcHmcArgs& a, const JumpDev& jd, bool fast, int64_t t
     return NFMC_OK;
 }
 
-// kind 4 (GaussFullPot): its own translation units (sampler_fullrank_*.hip), the layouts kind 3 gets, general kernels
-// on the default Philox4x32-10 stream only
-template <int CPL, int LPC, int JHP>
-int launch_mala_fullrank_cfg(const NfmcMalaArgs& a, const JumpDev& jd, int64_t tiles, int grid, float sqrt2h,
-                             hipStream_t st) {
+// kinds 4 (GaussFullPot) and 5 (RosenbrockPot): translation units of their own (sampler_fullrank_*.hip,
+// sampler_rosenbrock_*.hip), the layouts kind 3 gets, general kernels on the default Philox4x32-10 stream only
+template <template <int, int, bool> class POT, int CPL, int LPC, int JHP>
+int launch_mala_general_cfg(const NfmcMalaArgs& a, const JumpDev& jd, int64_t tiles, int grid, float sqrt2h,
+                            hipStream_t st) {
     const size_t lds = sampler_lds<CPL, LPC, JHP>(a.pot, jd);
     if (lds > 120 * 1024 || rng_rounds(a.rng) != 10) return NFMC_EUNSUPPORTED;
-    return launch_mala_kernel<CPL, LPC, GaussFullPot, false, JHP>(a, jd, lds, tiles, grid, sqrt2h, st);
+    return launch_mala_kernel<CPL, LPC, POT, false, JHP>(a, jd, lds, tiles, grid, sqrt2h, st);
 }
-template <int CPL, int LPC, int JHP>
-int launch_hmc_fullrank_cfg(const NfmcHmcArgs& a, const JumpDev& jd, int64_t tiles, int grid, hipStream_t st) {
+template <template <int, int, bool> class POT, int CPL, int LPC, int JHP>
+int launch_hmc_general_cfg(const NfmcHmcArgs& a, const JumpDev& jd, int64_t tiles, int grid, hipStream_t st) {
     const size_t lds = sampler_lds<CPL, LPC, JHP>(a.pot, jd);
     if (lds > 120 * 1024 || rng_rounds(a.rng) != 10) return NFMC_EUNSUPPORTED;
-    return launch_hmc_kernel<CPL, LPC, GaussFullPot, false, JHP>(a, jd, lds, tiles, grid, st);
+    return launch_hmc_kernel<CPL, LPC, POT, false, JHP>(a, jd, lds, tiles, grid, st);
 }
 
 // all sampler layouts (JHP == 0) / the layouts shared with flow_b (JHP > 0)
@@ -681,5 +681,8 @@ int launch_hmc_j8(const NfmcHmcArgs&, const JumpDev&, Cfg, bool, int64_t, int, h
 // defined in sampler_fullrank_mala.hip / sampler_fullrank_hmc.hip: kind 4 at layout c, jump-tail width jhp (0, 4, 8)
 int launch_mala_fullrank(const NfmcMalaArgs&, const JumpDev&, Cfg, int, int64_t, int, float, hipStream_t);
 int launch_hmc_fullrank(const NfmcHmcArgs&, const JumpDev&, Cfg, int, int64_t, int, hipStream_t);
+// defined in sampler_rosenbrock_mala.hip / sampler_rosenbrock_hmc.hip: kind 5, the same arguments
+int launch_mala_rosenbrock(const NfmcMalaArgs&, const JumpDev&, Cfg, int, int64_t, int, float, hipStream_t);
+int launch_hmc_rosenbrock(const NfmcHmcArgs&, const JumpDev&, Cfg, int, int64_t, int, hipStream_t);
 
 }  // namespace nfmc
