@@ -224,7 +224,11 @@ enum {
     NFMC_TUNE_GAMMA = 8,
     NFMC_TUNE_IMD_ADJUSTMENT = 9, /* beta */
     NFMC_TUNE_TICKET = 10,     /* internal: workgroup counter of the fold (zero between calls) */
-    NFMC_TUNE_WORDS = 12       /* followed by 2 * padded_d + 4 words of column totals: nfmc_tune_state_doubles(d) in all */
+    NFMC_TUNE_WORDS = 12       /* followed by 2 * padded_d + 4 words of column totals, then padded_d words of the
+                                  per-coordinate shift c: nfmc_tune_state_doubles(d) in all.  Tuning launches sum x - c and
+                                  (x - c)^2 (fp32 sums of x and x^2 cancel for chains far from the origin relative to
+                                  their spread); the controller un-shifts them in fp64 into NfmcStats and sets c to the
+                                  update's mean.  The caller initialises c (the column means of x0; zeros are valid) */
 };
 typedef struct {
     double* state;             /* NULL: no tuning (step_size / inv_mass_diag of the call are used as given) */

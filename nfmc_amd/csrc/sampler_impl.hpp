@@ -71,6 +71,31 @@ struct MassCoef {
     __device__ __forceinline__ float RS(int i) const { return FAST ? 1.f : rs[FAST ? 0 : i]; }
 };
 
+// Tuning launches (NfmcTune) accumulate the variance sums about a per-coordinate shift c -- x - c and (x - c)^2 -- that
+// the controller keeps near the chains' mean (tune_finish_kernel un-shifts in fp64): raw fp32 sums of x and x^2 cancel
+// for chains far from the origin relative to their spread.  ON only in the TUNE instantiations of the general kernels
+// (launch_*_kernel picks them for launches with a tuning state): every other instantiation carries no shift registers
+// and sums x itself, as before.
+template <int CPL, int LPC, bool ON>
+struct StatShift {
+    float c[ON ? CPL : 1];
+    // per tile: the rows past n hold x = 0 and must add 0, not -c (a few L2-resident loads per tile)
+    __device__ __forceinline__ void init(const NfmcTune& tn, int g, int d, bool active) {
+        if constexpr (ON) {
+            const double* __restrict__ src = tn.state + NFMC_TUNE_WORDS + 2 * CPL * LPC + kStatTail;
+#pragma unroll
+            for (int i = 0; i < CPL; ++i) {
+                const int k = coord_of<CPL, LPC>(g, i);
+                c[i] = (active && k < d) ? (float)src[k] : 0.f;
+            }
+        }
+    }
+    __device__ __forceinline__ float operator()(const float (&x)[CPL], int i) const {
+        if constexpr (ON) return x[i] - c[i];
+        else return x[i];
+    }
+};
+
 // noise for this lane's CPL coordinates of (chain, step): native Philox or (REPLAY) replay from HBM
 template <int CPL, int LPC, int R = 10, bool REPLAY = true>
 __device__ __forceinline__ void draw_normals(const NfmcRng& rng, uint32_t tag, uint32_t gchain, int64_t row, int64_t n,
@@ -202,9 +227,12 @@ __device__ __forceinline__ bool jump_once(float (&x)[CPL], const FlowT& fl, cons
 // ------------------------------------------------------------------------------------------------
 // LEAN: the launch has no per-step output and no replay (masks_out, log_ratio_out, samples.base, replay_normals and
 // replay_uniforms all null; launch_mala_cfg checks), so none of their pointers or branches is in the step loop.
-template <int CPL, int LPC, template <int, int, bool> class Pot, bool FAST, int JHP, int RR = 10, bool LEAN = false>
+// TUNE: a warmup launch (a.tune.state set): the variance sums are taken about the tuning state's shift (StatShift)
+template <int CPL, int LPC, template <int, int, bool> class Pot, bool FAST, int JHP, int RR = 10, bool LEAN = false,
+          bool TUNE = false>
 __global__ void __launch_bounds__(kBlock, NFMC_WPE) mala_kernel(NfmcMalaArgs a, float sqrt2h, int64_t tiles, JumpDev jd) {
     static_assert(!LEAN || JHP == 0, "the jump tail keeps its own outputs");
+    static_assert(!TUNE || (JHP == 0 && !FAST && !LEAN), "tuning launches run the general kernels without a jump tail");
     extern __shared__ __attribute__((aligned(16))) float flow_lds[];
     __shared__ float4 accept_slab[LPC > 1 ? kBlock : 1];
     constexpr int CPW = kWave / LPC;
@@ -237,6 +265,7 @@ __global__ void __launch_bounds__(kBlock, NFMC_WPE) mala_kernel(NfmcMalaArgs a, 
     float sx[CPL], sxx[CPL];
 #pragma unroll
     for (int i = 0; i < CPL; ++i) sx[i] = sxx[i] = 0.f;
+    StatShift<CPL, LPC, TUNE> shift;
     uint32_t n_acc = 0, n_bad = 0, j_acc = 0, j_bad = 0;
     const unsigned long long leaders = LPC == 64 ? 1ull : (LPC == 32 ? 0x0000000100000001ull
                                        : LPC == 16 ? 0x0001000100010001ull
@@ -250,6 +279,7 @@ __global__ void __launch_bounds__(kBlock, NFMC_WPE) mala_kernel(NfmcMalaArgs a, 
         const uint32_t gchain = (uint32_t)(a.rng.chain_offset + (uint64_t)row);
         float x[CPL];
         load_row<CPL, LPC, FAST>(a.x, row, d, g, active, x);
+        shift.init(a.tune, g, d, active);
         AcceptLnU<LPC, RR, !LEAN> au(accept_slab, g);
         StoreCursor keep(a.samples);
         const uint64_t live = __ballot(active);   // the wave's lanes with a chain
@@ -329,8 +359,9 @@ __global__ void __launch_bounds__(kBlock, NFMC_WPE) mala_kernel(NfmcMalaArgs a, 
 #pragma unroll
             for (int i = 0; i < CPL; ++i) {
                 x[i] = select_f32(am, xp[i], x[i]);  // mcmc/base.py:77
-                sx[i] += x[i];
-                sxx[i] = fmaf(x[i], x[i], sxx[i]);
+                const float xs = shift(x, i);
+                sx[i] += xs;
+                sxx[i] = fmaf(xs, xs, sxx[i]);
             }
             if constexpr (!LEAN) {
                 if (float* kept = keep.next(n * d)) store_row<CPL, LPC, FAST>(kept, row, d, g, active, x);
@@ -350,8 +381,9 @@ __global__ void __launch_bounds__(kBlock, NFMC_WPE) mala_kernel(NfmcMalaArgs a, 
             j_bad += (uint32_t)__popcll(__ballot(bad) & leaders);
 #pragma unroll
             for (int i = 0; i < CPL; ++i) {
-                sx[i] += x[i];
-                sxx[i] = fmaf(x[i], x[i], sxx[i]);
+                const float xs = shift(x, i);
+                sx[i] += xs;
+                sxx[i] = fmaf(xs, xs, sxx[i]);
             }
             if (float* kept = keep.next(n * d)) store_row<CPL, LPC, FAST>(kept, row, d, g, active, x);
             if (g == 0 && active) {
@@ -365,8 +397,9 @@ __global__ void __launch_bounds__(kBlock, NFMC_WPE) mala_kernel(NfmcMalaArgs a, 
 }
 
 // ------------------------------------------------------------------------------------------------
-template <int CPL, int LPC, template <int, int, bool> class Pot, bool FAST, int JHP, int RR = 10>
+template <int CPL, int LPC, template <int, int, bool> class Pot, bool FAST, int JHP, int RR = 10, bool TUNE = false>
 __global__ void __launch_bounds__(kBlock, NFMC_WPE) hmc_kernel(NfmcHmcArgs a, int64_t tiles, JumpDev jd) {
+    static_assert(!TUNE || (JHP == 0 && !FAST), "tuning launches run the general kernels without a jump tail");
     extern __shared__ __attribute__((aligned(16))) float flow_lds[];
     __shared__ float4 accept_slab[LPC > 1 ? kBlock : 1];
     constexpr int CPW = kWave / LPC;
@@ -393,6 +426,7 @@ __global__ void __launch_bounds__(kBlock, NFMC_WPE) hmc_kernel(NfmcHmcArgs a, in
     float sx[CPL], sxx[CPL];
 #pragma unroll
     for (int i = 0; i < CPL; ++i) sx[i] = sxx[i] = 0.f;
+    StatShift<CPL, LPC, TUNE> shift;
     uint32_t n_acc = 0, n_bad = 0, j_acc = 0, j_bad = 0;
     const unsigned long long leaders = LPC == 64 ? 1ull : (LPC == 32 ? 0x0000000100000001ull
                                        : LPC == 16 ? 0x0001000100010001ull
@@ -406,6 +440,7 @@ __global__ void __launch_bounds__(kBlock, NFMC_WPE) hmc_kernel(NfmcHmcArgs a, in
         const uint32_t gchain = (uint32_t)(a.rng.chain_offset + (uint64_t)row);
         float x[CPL];
         load_row<CPL, LPC, FAST>(a.x, row, d, g, active, x);
+        shift.init(a.tune, g, d, active);
         AcceptLnU<LPC, RR> au(accept_slab, g);
         StoreCursor keep(a.samples);
 
@@ -479,8 +514,9 @@ __global__ void __launch_bounds__(kBlock, NFMC_WPE) hmc_kernel(NfmcHmcArgs a, in
 #pragma unroll
             for (int i = 0; i < CPL; ++i) {
                 x[i] = select_f32(am, q[i], x[i]);
-                sx[i] += x[i];
-                sxx[i] = fmaf(x[i], x[i], sxx[i]);
+                const float xs = shift(x, i);
+                sx[i] += xs;
+                sxx[i] = fmaf(xs, xs, sxx[i]);
             }
             if (float* kept = keep.next(n * d)) store_row<CPL, LPC, FAST>(kept, row, d, g, active, x);
             if (g == 0 && active) {
@@ -498,8 +534,9 @@ __global__ void __launch_bounds__(kBlock, NFMC_WPE) hmc_kernel(NfmcHmcArgs a, in
             j_bad += (uint32_t)__popcll(__ballot(bad) & leaders);
 #pragma unroll
             for (int i = 0; i < CPL; ++i) {
-                sx[i] += x[i];
-                sxx[i] = fmaf(x[i], x[i], sxx[i]);
+                const float xs = shift(x, i);
+                sx[i] += xs;
+                sxx[i] = fmaf(xs, xs, sxx[i]);
             }
             if (float* kept = keep.next(n * d)) store_row<CPL, LPC, FAST>(kept, row, d, g, active, x);
             if (g == 0 && active) {
@@ -541,6 +578,9 @@ template <int CPL, int LPC, template <int, int, bool> class POT, bool F, int JHP
 int launch_mala_kernel(const NfmcMalaArgs& a, const JumpDev& jd, size_t lds, int64_t tiles, int grid, float sqrt2h,
                        hipStream_t st) {
     auto kern = mala_kernel<CPL, LPC, POT, F, JHP>;
+    if constexpr (JHP == 0 && !F) {
+        if (a.tune.state) kern = mala_kernel<CPL, LPC, POT, F, JHP, 10, false, true>;
+    }
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;
@@ -552,6 +592,9 @@ int launch_mala_kernel(const NfmcMalaArgs& a, const JumpDev& jd, size_t lds, int
 template <int CPL, int LPC, template <int, int, bool> class POT, bool F, int JHP>
 int launch_hmc_kernel(const NfmcHmcArgs& a, const JumpDev& jd, size_t lds, int64_t tiles, int grid, hipStream_t st) {
     auto kern = hmc_kernel<CPL, LPC, POT, F, JHP>;
+    if constexpr (JHP == 0 && !F) {
+        if (a.tune.state) kern = hmc_kernel<CPL, LPC, POT, F, JHP, 10, true>;
+    }
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;

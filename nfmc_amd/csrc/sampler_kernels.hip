@@ -139,12 +139,8 @@ __global__ void __launch_bounds__(kFinishBlock) tune_finish_kernel(double* __res
                 double s = 0.0;
 #pragma unroll
                 for (int k = 0; k < kFinishSlices; ++k) s += part[k][col];
-                totals[t] = s;
-                if (t < dp) {
-                    if (t < d) st.sum_x[t] += s;
-                } else if (t < 2 * dp) {
-                    if (t - dp < d) st.sum_x2[t - dp] += s;
-                } else if (t == 2 * dp) {
+                totals[t] = s;   // coordinate columns: sums of x - c and (x - c)^2, un-shifted below
+                if (t == 2 * dp) {
                     st.counters[NFMC_CNT_ACCEPTED] += (unsigned long long)(s + 0.5);
                     st.counters[NFMC_CNT_ATTEMPTED] += attempted;
                 } else if (t == 2 * dp + 1) {
@@ -155,17 +151,23 @@ __global__ void __launch_bounds__(kFinishBlock) tune_finish_kernel(double* __res
     }
     __syncthreads();   // totals[] written by this workgroup's own threads: workgroup scope is enough
     const double n_tot = (double)attempted;
-    if (tn.tune_inv_mass_diag && tn.inv_mass_diag && n_tot > 1.0) {   // mcmc/base.py:146-151
-        const double beta = tn.state[NFMC_TUNE_IMD_ADJUSTMENT];
-        for (int j = threadIdx.x; j < d; j += kFinishBlock) {
-            const double sx = totals[j], sxx = totals[dp + j];
-            // torch.var (unbiased) from one-pass sums: for chains far from the origin relative to their spread the
-            // subtraction cancels (fp32 per-lane partials of x^2), so the result is held at >= 0 -- the next launch takes
-            // 1 / inv_mass_diag^2 and its square root
-            double var = (sxx - sx * sx / n_tot) / (n_tot - 1.0);
+    // The kernels summed y = x - c about the shift c (StatShift): the run's sums of x and x^2 are un-shifted here in fp64,
+    // the variance comes from the shifted sums, which do not cancel while c stays near the mean, and c moves to this
+    // update's mean (an fp32 value: the kernels subtract it in fp32).
+    double* __restrict__ shift = tn.state + NFMC_TUNE_WORDS + 2 * dp + kStatTail;
+    const bool tune_imd = tn.tune_inv_mass_diag && tn.inv_mass_diag && n_tot > 1.0;   // mcmc/base.py:146-151
+    const double beta = tn.state[NFMC_TUNE_IMD_ADJUSTMENT];
+    for (int j = threadIdx.x; j < d; j += kFinishBlock) {
+        const double c = shift[j], s1 = totals[j], s2 = totals[dp + j];
+        st.sum_x[j] += s1 + n_tot * c;
+        st.sum_x2[j] += s2 + c * (2.0 * s1 + n_tot * c);
+        if (tune_imd) {
+            // torch.var (unbiased); held at >= 0 against rounding -- the next launch takes 1 / inv_mass_diag^2 and its root
+            double var = (s2 - s1 * s1 / n_tot) / (n_tot - 1.0);
             var = var > 0.0 ? var : 0.0;
             tn.inv_mass_diag[j] = (float)(beta * var + (1.0 - beta) * (double)tn.inv_mass_diag[j]);
         }
+        if (n_tot > 0.0) shift[j] = (double)(float)(c + s1 / n_tot);
     }
     if (threadIdx.x == 0 && tn.tune_step_size) {                                   // mcmc/base.py:153-161, tuning.py:22-38
         const double acc = totals[2 * dp];
@@ -255,10 +257,13 @@ static void tune_update(const NfmcStats& stats, const NfmcTune& tune, int grid, 
 }
 
 template <class Args>
-static int check_tune(const Args& a) {
+static int check_tune(const Args& a, int dp) {
     if (!a.tune.state) return NFMC_OK;
     if (!a.stats.sum_x || a.stats.defer || a.jump) return NFMC_EINVAL;   // the controller rides on the per-call fold
     if (a.tune.tune_inv_mass_diag && (!a.tune.inv_mass_diag || a.tune.inv_mass_diag != a.inv_mass_diag)) return NFMC_EINVAL;
+    // the state holds 2 * padded_d(d) + kStatTail column totals and padded_d(d) shift words (nfmc_tune_state_doubles):
+    // a layout override of a larger capacity would not fit them
+    if (dp != padded_d(a.d)) return NFMC_EINVAL;
     return NFMC_OK;
 }
 
@@ -309,7 +314,7 @@ extern "C" int64_t nfmc_stats_scratch_bytes(int32_t d) {
 
 extern "C" int64_t nfmc_tune_state_doubles(int32_t d) {
     if (d <= 0 || d > 1024) return 0;
-    return NFMC_TUNE_WORDS + 2 * padded_d(d) + kStatTail;
+    return NFMC_TUNE_WORDS + 3 * padded_d(d) + kStatTail;   // controller words, column totals, shift
 }
 
 extern "C" int nfmc_mala_steps_f32(const NfmcMalaArgs* args, nfmc_stream_t stream) {
@@ -320,7 +325,7 @@ extern "C" int nfmc_mala_steps_f32(const NfmcMalaArgs* args, nfmc_stream_t strea
     const int jhp = a.jump ? (a.jump->flow.n_hidden <= 4 ? 4 : 8) : 0;
     const Cfg c = choose_cfg(a.d, jhp > 0, default_cfg_only(a.pot));
     if (!c.cpl) return NFMC_ESHAPE;
-    const bool fast = fast_path(&a, c);
+    const bool fast = fast_path(&a, c) && !a.tune.state;   // tuning launches sum about a shift (StatShift): general kernels
     const int dp = c.cpl * c.lpc;
     const int cpw = kWave / c.lpc;
     const int64_t tiles = (a.n + (int64_t)kWavesPerBlock * cpw - 1) / ((int64_t)kWavesPerBlock * cpw);
@@ -329,7 +334,7 @@ extern "C" int nfmc_mala_steps_f32(const NfmcMalaArgs* args, nfmc_stream_t strea
     if (a.stats.sum_x && a.stats.scratch_bytes < (int64_t)grid * (2 * dp + kStatTail) * (int64_t)sizeof(double))
         return NFMC_ESCRATCH;
     if (check_defer(a.stats, dp, a.d)) return NFMC_EINVAL;
-    if ((rc = check_tune(a))) return rc;
+    if ((rc = check_tune(a, dp))) return rc;
     const float sqrt2h = (float)sqrt(2.0 * (double)a.step_size);  // math.sqrt(2*step_size), langevin.py:75
     const JumpDev jd = jump_dev(a.jump);
     unsigned long long* jc = a.jump ? a.jump->counters : nullptr;
@@ -376,7 +381,7 @@ extern "C" int nfmc_hmc_steps_f32(const NfmcHmcArgs* args, nfmc_stream_t stream)
     const int jhp = a.jump ? (a.jump->flow.n_hidden <= 4 ? 4 : 8) : 0;
     const Cfg c = choose_cfg(a.d, jhp > 0, default_cfg_only(a.pot));
     if (!c.cpl) return NFMC_ESHAPE;
-    const bool fast = fast_path(&a, c);
+    const bool fast = fast_path(&a, c) && !a.tune.state;   // tuning launches sum about a shift (StatShift): general kernels
     const int dp = c.cpl * c.lpc;
     const int cpw = kWave / c.lpc;
     const int64_t tiles = (a.n + (int64_t)kWavesPerBlock * cpw - 1) / ((int64_t)kWavesPerBlock * cpw);
@@ -385,7 +390,7 @@ extern "C" int nfmc_hmc_steps_f32(const NfmcHmcArgs* args, nfmc_stream_t stream)
     if (a.stats.sum_x && a.stats.scratch_bytes < (int64_t)grid * (2 * dp + kStatTail) * (int64_t)sizeof(double))
         return NFMC_ESCRATCH;
     if (check_defer(a.stats, dp, a.d)) return NFMC_EINVAL;
-    if ((rc = check_tune(a))) return rc;
+    if ((rc = check_tune(a, dp))) return rc;
     const JumpDev jd = jump_dev(a.jump);
     unsigned long long* jc = a.jump ? a.jump->counters : nullptr;
     a.jump = nullptr;

@@ -64,6 +64,26 @@ class NfmcTune(C.Structure):
 
 TUNE_STEP_SIZE, TUNE_LOG_SMOOTH, TUNE_ERROR_SUM, TUNE_ITERATION, TUNE_ANCHOR, TUNE_LOG_RAW = 0, 1, 2, 3, 4, 5
 TUNE_TARGET, TUNE_KAPPA, TUNE_GAMMA, TUNE_IMD_ADJUSTMENT, TUNE_TICKET, TUNE_WORDS = 6, 7, 8, 9, 10, 12
+STAT_TAIL = 4
+
+
+def padded_d(d):
+    """The column count of a statistics slab for event size d (csrc/common.hpp: padded_d)."""
+    p = 4
+    while p < d:
+        p <<= 1
+    return p
+
+
+def tune_shift_offset(d):
+    """First word of the per-coordinate shift c in the tuning state: tuning launches accumulate x - c and (x - c)^2, the
+    controller un-shifts in fp64 and moves c to the folded mean (include/nfmc_hip.h, NFMC_TUNE_WORDS)."""
+    return TUNE_WORDS + 2 * padded_d(d) + STAT_TAIL
+
+
+# Philox step of warmup transition 0: a warmup draws from its own half of the stream, so a sampling run that follows it
+# with the same seed (steps from 0) never reuses a warmup draw
+WARMUP_STEP0 = 1 << 31
 
 
 class NfmcMalaArgs(C.Structure):

@@ -54,7 +54,9 @@ class MetropolisParameters(MCMCParameters):
     imd_adjustment: float = 1e-3
     # warmup on the device: transitions per controller update.  1 = the reference's schedule (mcmc/base.py:92-96: the
     # kernel is updated after every transition); K > 1 updates once per K transitions with the acceptance rate and the
-    # per-coordinate variance pooled over them, K transitions per launch
+    # per-coordinate variance pooled over them (the n K states of the K transitions, unbiased variance), K transitions per
+    # launch.  A warmup of W transitions makes ceil(W / K) updates, the last one over the W mod K transitions left, however
+    # the warmup is cut into calls (progress bar, time limit).  At most 512 (hip.MAX_STEPS_PER_CALL): larger is a ValueError
     tune_every: int = 1
 
 
@@ -76,6 +78,9 @@ class DeviceTuning:
         st[hip.TUNE_KAPPA] = da.params.kappa
         st[hip.TUNE_GAMMA] = da.params.gamma
         st[hip.TUNE_IMD_ADJUSTMENT] = p.imd_adjustment
+        # shift of the variance sums: the column means of x0 (fp32 values), moved to the folded mean by every update
+        c0 = hip.tune_shift_offset(run.d)
+        st[c0:c0 + run.d] = run.x.double().mean(0).float().double()
         self.state = st.to(run.dev)
         self.imd = k.inv_mass_diag.detach().to(run.dev, torch.float32).contiguous().clone()
         self.tune_step = bool(p.tune_step_size and p.adjustment)            # mcmc/base.py:153
@@ -202,8 +207,13 @@ class MCMCSampler(Sampler):
 
     def sample(self, x0, show_progress: bool = True, time_limit_seconds=None) -> MCMCOutput:
         """mcmc/base.py:56-102 on the device."""
+        if self.params.tuning and int(getattr(self.params, 'tune_every', 1)) > hip.MAX_STEPS_PER_CALL:
+            raise ValueError('tune_every must be at most %d, got %d'
+                             % (hip.MAX_STEPS_PER_CALL, int(self.params.tune_every)))
         run = Run(self, x0)
-        step0 = 0
+        # a warmup draws from its own part of the Philox stream: with an explicit seed, the sampling run that follows
+        # it must not reuse the innovations that produced its starting state
+        step0 = hip.WARMUP_STEP0 if self.params.tuning else 0
         n = run.n
         event_shape = run.event_shape
         out = MCMCOutput(event_shape, kernel=self.kernel, store_samples=self.params.store_samples,
@@ -234,6 +244,8 @@ class MCMCSampler(Sampler):
             # one ABI call enqueues every (kernel, controller) pair of up to 512 transitions: no host work per update
             tune.every = max(1, int(getattr(self.params, 'tune_every', 1)))
             limit = hip.MAX_STEPS_PER_CALL if time_limit_seconds is None and not show_progress else max(32, tune.every)
+            # calls of whole pools: the controller updates once per `every` transitions whatever the call size
+            limit -= limit % tune.every
         while done < K:
             if run.time_is_up(t0, time_limit_seconds):
                 break

@@ -599,3 +599,124 @@ class DualAveraging:
     @property
     def value(self):
         return math.exp(self.log_step_averaged)
+
+
+# --------------------------------------------------------------------------- A.8 warmup controller in fp64
+@dataclass
+class ControllerParams:
+    """What `MetropolisSampler.update_kernel` (mcmc/base.py:142-161) reads: the initial step size and mass diagonal,
+    the EMA weight of the variance, which halves of the controller run, and the dual-averaging constants
+    (tuning.py:8-12).  `tune_step_size` is the reference's `tune_step_size and adjustment` (:153)."""
+    step_size: float
+    inv_mass_diag: torch.Tensor
+    imd_adjustment: float = 1e-3
+    tune_step_size: bool = True
+    tune_inv_mass_diag: bool = True
+    target_acceptance_rate: float = 0.651
+    kappa: float = 0.75
+    gamma: float = 0.05
+    t0: int = 10
+
+
+@dataclass
+class ControllerUpdate:
+    """The controller's state after one update."""
+    step_size: float
+    inv_mass_diag: torch.Tensor          # fp32, as the sampler stores it
+    error_sum: float
+    log_smooth: float
+    log_raw: float
+    iteration: int
+
+
+def pools(n_transitions, every):
+    """The transitions each controller update pools: consecutive blocks of `every`, the last one possibly shorter."""
+    every = max(1, int(every))
+    return [(s, min(every, n_transitions - s)) for s in range(0, n_transitions, every)]
+
+
+def controller_update(state, da, xs, accepted, n_samples, n_chains, p: ControllerParams):
+    """One `update_kernel` (mcmc/base.py:142-161) in fp64 over the pooled states xs (m, d): variance two-pass with
+    torch.var semantics (unbiased), the mass diagonal rounded to fp32 after the EMA, then one dual-averaging step
+    (tuning.py:22-38) on the pooled acceptance rate.  The mass diagonal is tuned only with more than one chain
+    (mcmc/base.py:146: `x.shape[0] > 1`), however many states a pool holds."""
+    imd = state['imd']
+    if p.tune_inv_mass_diag and n_chains > 1:
+        var = torch.var(xs.double(), dim=0)
+        imd = (p.imd_adjustment * var + (1 - p.imd_adjustment) * imd.double()).float()
+    h = state['h']
+    if p.tune_step_size:
+        da.step(p.target_acceptance_rate - float(accepted) / float(n_samples))
+        h = da.value
+    state['imd'], state['h'] = imd, h
+    return ControllerUpdate(h, imd.clone(), da.error_sum, da.log_step_averaged,
+                            da.log_step if hasattr(da, 'log_step') else math.nan, da.t)
+
+
+class _DA(DualAveraging):
+    def step(self, acceptance_rate_error):
+        self.log_step = self.mu - (self.error_sum + float(acceptance_rate_error)) / (math.sqrt(self.t) * self.gamma)
+        super().step(acceptance_rate_error)
+
+
+def _new_da(p: ControllerParams):
+    return _DA(p.step_size, p.target_acceptance_rate, p.kappa, p.gamma, p.t0)
+
+
+def replay_controller(states, accepted, every, params: ControllerParams):
+    """Every controller update of a warmup recomputed in fp64 from a kernel's own kept states `states` (T, n, d) (the
+    state after each transition) and its per-transition accept counts `accepted` (T,).  `every`: transitions per
+    update (`tune_every`; pooled definition of `MetropolisParameters`: the n * K states of the K transitions,
+    unbiased variance, accepted / (n K)).
+
+    Returns (updates, h_t, imd_t): the ControllerUpdate after each update, and the step size and mass diagonal each
+    transition ran with (what the next update's transitions see)."""
+    states = torch.as_tensor(states)
+    T, n = states.shape[0], states.shape[1]
+    x = states.reshape(T, n, -1).double()
+    acc = torch.as_tensor(accepted).reshape(T).double()
+    state = {'h': float(params.step_size), 'imd': torch.as_tensor(params.inv_mass_diag).float().reshape(-1).clone()}
+    da = _new_da(params)
+    updates, h_t, imd_t = [], [], []
+    for s0, k in pools(T, every):
+        h_t += [state['h']] * k
+        imd_t += [state['imd'].clone()] * k
+        xs = x[s0:s0 + k].reshape(k * n, -1)
+        updates.append(controller_update(state, da, xs, float(acc[s0:s0 + k].sum()), k * n, n, params))
+    return updates, h_t, imd_t
+
+
+def mcmc_warmup(x0, target, kind, n_iterations, params: ControllerParams, n_leapfrog=20, adjustment=True, every=1,
+                noise=None, step0=0):
+    """`MCMCSampler.warmup` (mcmc/base.py:39-54): `sample()` in tuning mode, the kernel updated by `update_kernel`
+    (:92-96, :142-161) after every transition (every = 1, the reference's schedule) or once per `every` transitions
+    with the statistics pooled over them.  kind in {'langevin', 'hmc', 'mh'}; runs in the dtype of x0.
+
+    Returns (trace, updates, h_t, imd_t): the mcmc_sample-style trace of the warmup, the ControllerUpdate after each
+    update and the step size / mass diagonal each transition ran with."""
+    noise = noise or TorchNoise()
+    n = x0.shape[0]
+    x = x0.detach().clone().reshape(n, -1)
+    state = {'h': float(params.step_size), 'imd': torch.as_tensor(params.inv_mass_diag).float().reshape(-1).clone()}
+    da = _new_da(params)
+    tr = Trace(moments=Moments.for_event((x.shape[1],)))
+    updates, h_t, imd_t = [], [], []
+    for s0, k in pools(n_iterations, every):
+        h, imd = state['h'], state['imd'].to(x.dtype)
+        t = mcmc_sample(x, target, kind, k, h, inv_mass_diag=imd, n_leapfrog=n_leapfrog, adjustment=adjustment,
+                        noise=noise, step0=step0 + s0)
+        h_t += [h] * k
+        imd_t += [state['imd'].clone()] * k
+        for name in ('n_accepted', 'n_attempted', 'n_target_calls', 'n_target_gradient_calls', 'n_divergences'):
+            setattr(tr, name, getattr(tr, name) + getattr(t, name))
+        for xi in t.samples:
+            tr.moments.update(xi)
+        tr.samples += t.samples
+        tr.masks += t.masks
+        tr.log_ratios += t.log_ratios
+        tr.uniforms += t.uniforms
+        x = t.last
+        tr.last = x.clone()
+        xs = torch.stack(t.samples).reshape(k * n, -1)
+        updates.append(controller_update(state, da, xs, t.n_accepted, k * n, n, params))
+    return tr, updates, h_t, imd_t

@@ -34,14 +34,18 @@ import torch
 
 from . import samplers as osamp
 
-KINDS = ('mala', 'hmc', 'neutra_hmc', 'jump_mala', 'jump_hmc', 'imh')
+KINDS = ('mala', 'hmc', 'neutra_hmc', 'jump_mala', 'jump_hmc', 'imh', 'ula', 'uhmc', 'mh')
+UNADJUSTED_MARGIN = 1e30     # margin of an unadjusted transition: every chain accepts, far from any tie
 
 
 @dataclass
 class Workload:
     """What the kernel ran.  `target`: an oracle potential (n, d) -> (n,) that works in fp32 and fp64 (oracle/potentials.py);
     `flow`: the oracle flow with the kernel's weights (the harness makes its own fp64 copy); jump runs number their
-    transitions i * (n_inner + 1) + k and jump at k = n_inner; run transition t draws at Philox step step0 + t."""
+    transitions i * (n_inner + 1) + k and jump at k = n_inner; run transition t draws at Philox step step0 + t.
+    `step_size` and `inv_mass_diag` may also be sequences indexed by run transition t (a warmup: what the controller had
+    set before t, oracle.samplers.replay_controller); `inv_mass_diag` is then a list of (d,) tensors or a (T, d) tensor.
+    `ula` / `uhmc` accept every proposal; `mh` is the random-walk proposal x + inv_mass_diag * eps (mh.py:44-73)."""
     kind: str
     target: Callable
     flow: Optional[object] = None
@@ -53,6 +57,18 @@ class Workload:
 
     def __post_init__(self):
         assert self.kind in KINDS, self.kind
+
+    def h_at(self, step):
+        h = self.step_size
+        return float(h[step - self.step0]) if isinstance(h, (list, tuple, torch.Tensor, np.ndarray)) else h
+
+    def imd_at(self, step, d, dtype):
+        m = self.inv_mass_diag
+        if m is None:
+            return torch.ones(d, dtype=dtype)
+        if isinstance(m, (list, tuple)) or (isinstance(m, torch.Tensor) and m.dim() == 2):
+            m = m[step - self.step0]
+        return torch.as_tensor(m).to(dtype).reshape(d)
 
     def is_jump(self, step):
         return self.kind == 'imh' or (self.kind.startswith('jump') and step % (self.n_inner + 1) == self.n_inner)
@@ -70,19 +86,30 @@ class Transition:
 def one_transition(wl: Workload, x, step, noise, flow, target):
     """Transition `step` of workload `wl` from the states x (n, d), in the dtype of x / flow / noise."""
     n, d = x.shape
-    imd = wl.inv_mass_diag.to(x.dtype) if wl.inv_mass_diag is not None else torch.ones(d, dtype=x.dtype)
+    imd = wl.imd_at(step, d, x.dtype)
+    h = wl.h_at(step)
     if wl.is_jump(step):
         js = osamp.jump_transition(x, target, flow, step, noise)
         scale = js.u_x.abs() + js.u_xp.abs() + js.f_x.abs() + js.f_xp.abs()
         return Transition(js.x, js.mask, js.log_alpha - js.log_u, scale)
     info = {}
-    if wl.kind in ('mala', 'jump_mala'):
-        xp, mask, lr, lu = osamp.langevin_propose(x, target, wl.step_size, imd, True, noise, step, info)
+    if wl.kind in ('ula', 'uhmc'):
+        if wl.kind == 'ula':
+            xp, mask, _lr, _lu = osamp.langevin_propose(x, target, h, imd, False, noise, step)
+        else:
+            xp, mask, _lr, _lu = osamp.hmc_propose(x, target, h, imd, wl.n_leapfrog, False, noise, step)
+        return Transition(xp.detach().clone(), mask, torch.full((n,), UNADJUSTED_MARGIN, dtype=torch.float64),
+                          torch.zeros(n, dtype=torch.float64))
+    if wl.kind == 'mh':
+        xp, mask, lr, lu = osamp.mh_propose(x, target, imd, True, noise, step)
+        scale = target(x).abs() + target(xp).abs()
+    elif wl.kind in ('mala', 'jump_mala'):
+        xp, mask, lr, lu = osamp.langevin_propose(x, target, h, imd, True, noise, step, info)
         scale = info['u0'].abs() + info['u1'].abs()
     else:
         if wl.kind == 'neutra_hmc':
             target = osamp.neutra_adjusted_target(flow, target, tuple(flow.event_shape))
-        xp, mask, lr, lu = osamp.hmc_propose(x, target, wl.step_size, imd, wl.n_leapfrog, True, noise, step, info)
+        xp, mask, lr, lu = osamp.hmc_propose(x, target, h, imd, wl.n_leapfrog, True, noise, step, info)
         scale = info['h0'].abs() + info['h1'].abs()
     xn = x.clone()
     xn[mask] = xp.detach()[mask]

@@ -359,6 +359,30 @@ def main():
          step_size0=np.float64(d ** (-1 / 3)), tuned_step_size=np.float64(s.kernel.step_size),
          tuned_inv_mass_diag=s.kernel.inv_mass_diag.numpy(), **out_arrays(wout))
 
+    # warmups on an offset diagonal Gaussian: the mass diagonal tracks a variance about a mean far from 0
+    mu_w = torch.tensor([3.0, -2.0, 0.5, 8.0, -5.0])
+    sig_w = torch.tensor([0.5, 1.0, 2.0, 0.25, 1.5])
+    offset = opot.quadratic(0.5 / sig_w ** 2, mu_w)
+    for name, kind, beta in [('warmup_mala_offset', 'mala', None), ('warmup_mala_offset_imd05', 'mala', 0.5),
+                             ('warmup_hmc_offset', 'hmc', None), ('warmup_hmc_offset_imd05', 'hmc', 0.5)]:
+        torch.manual_seed(21)
+        d, n, k = 5, 24, 8
+        x0 = mu_w + sig_w * torch.randn(n, d)
+        kw = {} if beta is None else {'imd_adjustment': beta}
+        if kind == 'mala':
+            kern = LangevinKernel(event_size=d, step_size=0.1)
+            s = MALA((d,), offset, kern, LangevinParameters(n_iterations=k, n_warmup_iterations=k, **kw))
+        else:
+            kern = HMCKernel(event_size=d, n_leapfrog_steps=3, step_size=0.2)
+            s = HMC((d,), offset, kern, HMCParameters(n_iterations=k, n_warmup_iterations=k, **kw))
+        h0 = float(kern.step_size)
+        with DrawRecorder() as rec:
+            wout = s.warmup(x0.clone(), show_progress=False)
+        save(name, rec, x0=x0.numpy(), mu=mu_w.numpy(), sigma=sig_w.numpy(), step_size0=np.float64(h0),
+             imd_adjustment=np.float64(s.params.imd_adjustment), tuned_step_size=np.float64(s.kernel.step_size),
+             tuned_inv_mass_diag=s.kernel.inv_mass_diag.numpy(), da_iteration=np.int64(s.kernel.da.t),
+             **out_arrays(wout))
+
     # ---------------------------------------------------------------- util (a3, a8)
     lr = metropolis_acceptance_log_ratio(torch.tensor([1.0, -2.0]), torch.tensor([0.5, 3.0]),
                                          torch.tensor([0.25, 0.0]), torch.tensor([-1.0, 4.0]))
