@@ -75,7 +75,7 @@ enum {
        NeuTra kernels (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32 with conditioners of at most 32 units).
        NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the fit kernels, the Philox4x32-7 stream and the
        NeuTra matrix-core kernels (conditioners wider than 32). */
-    NFMC_POT_ROSENBROCK = 5
+    NFMC_POT_ROSENBROCK = 5,
     /* Blocked (hybrid) Rosenbrock over the flattened coordinates, split into consecutive blocks of B coordinates (the
        last one may be shorter); coordinate c is a head when c % B == 0:
          U = sum_{heads c} a (x_c - mu)^2 + sum_{non-heads c} b (x_c - x_{c-1}^2)^2   (constants dropped)
@@ -87,12 +87,33 @@ enum {
        (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32 with conditioners of at most 32 units).
        NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the fit kernels, the Philox4x32-7 stream and the
        NeuTra matrix-core kernels (conditioners wider than 32). */
+    NFMC_POT_STOCHASTIC_VOLATILITY = 6
+    /* Stochastic-volatility model (Stan User's Guide) over d = T + 3 coordinates: x_0 = mu, x_1 = s = log sigma,
+       x_2 = r = atanh phi, x_{3+t} = h_t (t = 0 .. T-1); mu ~ Cauchy(0, c_mu), sigma ~ HalfCauchy(0, c_sigma),
+       (phi + 1)/2 ~ Beta(alpha, beta), h_0 ~ N(mu, sigma^2/(1 - phi^2)), h_t | h_{t-1} ~ N(mu + phi (h_{t-1} - mu), sigma^2),
+       y_t ~ N(0, e^{h_t}).  With w = e^{-2s}, phi = tanh r, q = 1 - phi^2, delta_0 = h_0 - mu, a_t = h_{t-1} - mu and
+       e_t = h_t - mu - phi a_t (t >= 1), the Jacobians of s and r included and constants dropped:
+         U = log1p((mu/c_mu)^2) + softplus(2(s - log c_sigma)) + (alpha + 1/2) softplus(-2r) + (beta + 1/2) softplus(2r)
+           + 1/2 q w delta_0^2 + sum_{t>=1} [1/2 w e_t^2 + s] + sum_{t>=0} 1/2 [h_t + y_t^2 e^{-h_t}]
+         dU/dmu  = 2 mu/(c_mu^2 + mu^2) - q w delta_0 - (1 - phi) w S1,   S1 = sum_{t>=1} e_t
+         dU/ds   = 2 sigmoid(2(s - log c_sigma)) - q w delta_0^2 - w S2 + (T - 1),   S2 = sum e_t^2
+         dU/dr   = 2(beta + 1/2) sigmoid(2r) - 2(alpha + 1/2) sigmoid(-2r) - phi q w delta_0^2 - q w S3,   S3 = sum e_t a_t
+         dU/dh_t = 1/2 - 1/2 y_t^2 e^{-h_t} + [t = 0] q w delta_0 + [t >= 1] w e_t - [t + 1 < T] phi w e_{t+1}
+       n_components = T (T >= 1 and T = d - 3);  a -> y (T,) fp32, device memory;  b -> (alpha, beta), two fp32 in device
+       memory;  a_scalar = c_mu > 0, b_scalar = c_sigma > 0 (finite).  A NULL a or b, T out of range, or a scale not
+       positive and finite is NFMC_EINVAL.  A proposal whose U or gradient overflows fp32 (w, e^{-h_t}) has a non-finite
+       log ratio: rejected and counted like every other kind's.  Served by nfmc_mala_steps_f32 / nfmc_hmc_steps_f32
+       (general kernels, with or without a jump tail, device warmup tuning included), by the register-layout kernels of
+       nfmc_flow_mh_steps_f32 and by the VALU NeuTra kernels (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32
+       with conditioners of at most 32 units).  NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the
+       fit kernels, the Philox4x32-7 stream and the NeuTra matrix-core kernels (conditioners wider than 32). */
 };
 
 typedef struct {
     int32_t kind;
     int32_t n_components; /* NFMC_POT_GAUSSIAN_MIXTURE: K; NFMC_POT_LOGISTIC_REGRESSION: N; NFMC_POT_GAUSSIAN_FULL: d;
-                             NFMC_POT_ROSENBROCK: block length; 0 for the other kinds (was `reserved`, same layout) */
+                             NFMC_POT_ROSENBROCK: block length; NFMC_POT_STOCHASTIC_VOLATILITY: T = d - 3;
+                             0 for the other kinds (was `reserved`, same layout) */
     const float* a; /* (d,) or NULL -> a_scalar */
     const float* b; /* (d,) or NULL -> b_scalar */
     float a_scalar;

@@ -218,6 +218,48 @@ __device__ __forceinline__ float rosenbrock_value_grad_row(const float* __restri
     return u;
 }
 
+// Stochastic volatility (NFMC_POT_STOCHASTIC_VOLATILITY) for the row of one chain, as potential_value_grad_row: U and
+// dU/dx of SVPot (common.hpp), x_0 = mu, x_1 = log sigma, x_2 = atanh phi, x_{3+t} = h_t.  One pass over h_0 .. h_{T-1}:
+// h_{t-1} carries over in a register, and e_t (the successor term of t - 1) is added to the gradient of h_{t-1} when t is
+// reached, so each coordinate reads the row once; the sums S1, S2, S3 accumulate on the way and the global gradients
+// follow the loop.  y is wave-uniform (scalar loads).  Kept out of potential_value_grad_row, which the fit and DLMC
+// kernels share and which never see kind 6.
+__device__ __forceinline__ float sv_value_grad_row(const float* __restrict__ row, float* __restrict__ grow,
+                                                   const NfmcPotential& p, int d) {
+    const float* __restrict__ y = p.a;
+    const float cmu = p.a_scalar, ca = p.b[0] + 0.5f, cb = p.b[1] + 0.5f, tm1 = (float)(d - 4);
+    const float mu = row[0], s = row[1], r = row[2];
+    float spp, sgp, spm, sgm, sps, sgs;   // softplus / sigmoid of 2r, -2r and 2(s - log c_sigma)
+    softplus_sigmoid(2.f * r, spp, sgp);
+    softplus_sigmoid(-2.f * r, spm, sgm);
+    softplus_sigmoid(2.f * (s - logf(p.b_scalar)), sps, sgs);
+    const float phi = sgp - sgm, w = fast_exp(-2.f * s), pw = phi * w;
+    float u = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f, hm = 0.f;
+    for (int c = 3; c < d; ++c) {
+        const float h = row[c], yv = y[c - 3];
+        const float ye = (yv * yv) * fast_exp(-h), dh = h - mu;
+        u += 0.5f * (h + ye);
+        float gr = fmaf(-0.5f, ye, 0.5f);
+        if (c > 3) {
+            const float a = hm - mu, e = fmaf(-phi, a, dh);
+            u = fmaf(0.5f * w * e, e, u);
+            gr = fmaf(w, e, gr);
+            grow[c - 1] = fmaf(-pw, e, grow[c - 1]);   // successor term of h_{t-1}
+            s1 += e;
+            s2 = fmaf(e, e, s2);
+            s3 = fmaf(e, a, s3);
+        }
+        grow[c] = gr;
+        hm = h;
+    }
+    const float d0 = row[3] - mu, qw = 4.f * sgp * sgm * w, qwd = qw * d0, m = mu / cmu;
+    grow[0] = 2.f * m / (cmu * fmaf(m, m, 1.f)) - qwd - 2.f * sgm * w * s1;
+    grow[1] = 2.f * sgs - qwd * d0 - w * s2 + tm1;
+    grow[2] = 2.f * cb * sgp - 2.f * ca * sgm - phi * qwd * d0 - qw * s3;
+    grow[3] += qwd;
+    return u + log1pf(m * m) + sps + tm1 * s + ca * spm + cb * spp + 0.5f * qwd * d0;
+}
+
 // U~(z) and grad U~(z) for this lane's chain.  zrow: latent (tile columns in latent order), read only;
 // wrow: scratch, ends holding z again (rebuilt); grow: gradient in the same column order as zrow.
 template <int HP>
@@ -228,6 +270,7 @@ __device__ __forceinline__ float adjusted_potential_grad_row(const float* __rest
     const float ld = flow_inverse_row<HP>(wrow, f, g);          // w = x, ld = logdet_inverse (neutra.py:60)
     const float u = pot.kind == NFMC_POT_GAUSSIAN_FULL ? fullrank_value_grad_row(wrow, grow, pot, g.d)
                     : pot.kind == NFMC_POT_ROSENBROCK    ? rosenbrock_value_grad_row(wrow, grow, pot, g.d)
+                    : pot.kind == NFMC_POT_STOCHASTIC_VOLATILITY ? sv_value_grad_row(wrow, grow, pot, g.d)
                                                          : potential_value_grad_row(wrow, grow, pot, g.d);  // U(x), dU/dx (neutra.py:62)
     // reverse sweep, mirror image of flow_inverse_row
     for (int c = 0; c < g.d; ++c) {                               // EA0^-1

@@ -558,8 +558,8 @@ struct Cfg {
 
 // The layouts choose_cfg picks without the NFMC_SAMPLER_CFG override: the smallest capacity CPL * LPC >= d, at equal
 // capacity the first in kCfgs.  (4, 16), (16, 4), (16, 8), (16, 16) and (16, 32) tie with an earlier layout and are
-// reachable only through the override; LogRegPot, GaussFullPot and RosenbrockPot are not instantiated there (the
-// override skips them for kinds 3, 4 and 5).
+// reachable only through the override; LogRegPot, GaussFullPot, RosenbrockPot and SVPot are not instantiated there
+// (the override skips them for kinds 3 to 6).
 constexpr bool is_default_cfg(int cpl, int lpc) {
     return !((cpl == 4 && lpc == 16) || (cpl == 16 && lpc != 64));
 }
@@ -634,8 +634,9 @@ int launch_mala_cfg(const NfmcMalaArgs& a, const JumpDev& jd, bool fast, int64_t
         } else {
             return NFMC_EUNSUPPORTED;   // not reached: choose_cfg never picks this layout for kind 3
         }
-    } else if (a.pot.kind == NFMC_POT_GAUSSIAN_FULL || a.pot.kind == NFMC_POT_ROSENBROCK) {
-        return NFMC_EUNSUPPORTED;   // not reached: kinds 4 and 5 launch from sampler_{fullrank,rosenbrock}_*.hip
+    } else if (a.pot.kind == NFMC_POT_GAUSSIAN_FULL || a.pot.kind == NFMC_POT_ROSENBROCK ||
+               a.pot.kind == NFMC_POT_STOCHASTIC_VOLATILITY) {
+        return NFMC_EUNSUPPORTED;   // not reached: kinds 4 to 6 launch from sampler_{fullrank,rosenbrock,sv}_*.hip
     } else if (a.pot.kind == NFMC_POT_FUNNEL) {
         if (fast) NFMC_L(FunnelPot, true) else NFMC_L(FunnelPot, false)
     } else {
@@ -679,8 +680,9 @@ int launch_hmc_cfg(const NfmcHmcArgs& a, const JumpDev& jd, bool fast, int64_t t
         } else {
             return NFMC_EUNSUPPORTED;   // not reached: choose_cfg never picks this layout for kind 3
         }
-    } else if (a.pot.kind == NFMC_POT_GAUSSIAN_FULL || a.pot.kind == NFMC_POT_ROSENBROCK) {
-        return NFMC_EUNSUPPORTED;   // not reached: kinds 4 and 5 launch from sampler_{fullrank,rosenbrock}_*.hip
+    } else if (a.pot.kind == NFMC_POT_GAUSSIAN_FULL || a.pot.kind == NFMC_POT_ROSENBROCK ||
+               a.pot.kind == NFMC_POT_STOCHASTIC_VOLATILITY) {
+        return NFMC_EUNSUPPORTED;   // not reached: kinds 4 to 6 launch from sampler_{fullrank,rosenbrock,sv}_*.hip
     } else if (a.pot.kind == NFMC_POT_FUNNEL) {
         if (fast) NFMC_L(FunnelPot, true) else NFMC_L(FunnelPot, false)
     } else {
@@ -690,8 +692,9 @@ int launch_hmc_cfg(const NfmcHmcArgs& a, const JumpDev& jd, bool fast, int64_t t
     return NFMC_OK;
 }
 
-// kinds 4 (GaussFullPot) and 5 (RosenbrockPot): translation units of their own (sampler_fullrank_*.hip,
-// sampler_rosenbrock_*.hip), the layouts kind 3 gets, general kernels on the default Philox4x32-10 stream only
+// kinds 4 (GaussFullPot), 5 (RosenbrockPot) and 6 (SVPot): translation units of their own (sampler_fullrank_*.hip,
+// sampler_rosenbrock_*.hip, sampler_sv_*.hip), the layouts kind 3 gets, general kernels on the default Philox4x32-10
+// stream only
 template <template <int, int, bool> class POT, int CPL, int LPC, int JHP>
 int launch_mala_general_cfg(const NfmcMalaArgs& a, const JumpDev& jd, int64_t tiles, int grid, float sqrt2h,
                             hipStream_t st) {
@@ -727,5 +730,8 @@ int launch_hmc_fullrank(const NfmcHmcArgs&, const JumpDev&, Cfg, int, int64_t, i
 // defined in sampler_rosenbrock_mala.hip / sampler_rosenbrock_hmc.hip: kind 5, the same arguments
 int launch_mala_rosenbrock(const NfmcMalaArgs&, const JumpDev&, Cfg, int, int64_t, int, float, hipStream_t);
 int launch_hmc_rosenbrock(const NfmcHmcArgs&, const JumpDev&, Cfg, int, int64_t, int, hipStream_t);
+// defined in sampler_sv_mala.hip / sampler_sv_hmc.hip: kind 6, the same arguments
+int launch_mala_sv(const NfmcMalaArgs&, const JumpDev&, Cfg, int, int64_t, int, float, hipStream_t);
+int launch_hmc_sv(const NfmcHmcArgs&, const JumpDev&, Cfg, int, int64_t, int, hipStream_t);
 
 }  // namespace nfmc
