@@ -87,7 +87,7 @@ enum {
        (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32 with conditioners of at most 32 units).
        NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the fit kernels, the Philox4x32-7 stream and the
        NeuTra matrix-core kernels (conditioners wider than 32). */
-    NFMC_POT_STOCHASTIC_VOLATILITY = 6
+    NFMC_POT_STOCHASTIC_VOLATILITY = 6,
     /* Stochastic-volatility model (Stan User's Guide) over d = T + 3 coordinates: x_0 = mu, x_1 = s = log sigma,
        x_2 = r = atanh phi, x_{3+t} = h_t (t = 0 .. T-1); mu ~ Cauchy(0, c_mu), sigma ~ HalfCauchy(0, c_sigma),
        (phi + 1)/2 ~ Beta(alpha, beta), h_0 ~ N(mu, sigma^2/(1 - phi^2)), h_t | h_{t-1} ~ N(mu + phi (h_{t-1} - mu), sigma^2),
@@ -107,12 +107,31 @@ enum {
        nfmc_flow_mh_steps_f32 and by the VALU NeuTra kernels (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32
        with conditioners of at most 32 units).  NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the
        fit kernels, the Philox4x32-7 stream and the NeuTra matrix-core kernels (conditioners wider than 32). */
+    NFMC_POT_SPARSE_LOGISTIC_REGRESSION = 7
+    /* Sparse logistic regression with a hierarchical shrinkage prior (the German-credit model of the Inference Gym) over
+       d = 2 D + 1 coordinates: x_{2j} = w_j, x_{2j+1} = l_j = log lambda_j (j = 0 .. D-1), x_{2D} = s = log tau;
+       tau ~ Gamma(a, b), lambda_j ~ Gamma(a, b) (shape a, rate b), w_j ~ N(0, 1), beta_j = tau lambda_j w_j,
+       y_i ~ Bernoulli(sigmoid(z_i)), z = X beta.  With r_i = sigmoid(z_i) - y_i and g = X^T r, the Jacobians of the two
+       logs included and constants dropped:
+         U = sum_i [softplus(z_i) - y_i z_i] + 1/2 sum_j w_j^2 + sum_j (b e^{l_j} - a l_j) + (b e^s - a s)
+         dU/dw_j = e^{s + l_j} g_j + w_j,   dU/dl_j = beta_j g_j + b e^{l_j} - a,   dU/ds = sum_j beta_j g_j + b e^s - a
+       a -> X (N, D) fp32 row-major, device memory, 16-byte aligned;  b -> y (N,) fp32, values 0 or 1, device memory;
+       n_components = N;  a_scalar = a > 0, b_scalar = b > 0 (finite).  An even d or d < 3, N < 1, a NULL or misaligned
+       pointer, or a scale not positive and finite is NFMC_EINVAL.  No cap on N (each evaluation streams X through an LDS
+       tile of 16 KB plus the tile's labels; a flow image that leaves no room for it gets NFMC_EUNSUPPORTED).  A proposal
+       whose U or gradient overflows fp32 (e^{s + l_j}, e^{l_j}, e^s, z) has a non-finite log ratio: rejected and counted
+       like every other kind's.  Served by nfmc_mala_steps_f32 / nfmc_hmc_steps_f32 (general kernels, with or without a
+       jump tail, device warmup tuning included), by the register-layout kernels of nfmc_flow_mh_steps_f32 and by the VALU
+       NeuTra kernels (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32 with conditioners of at most 32 units).
+       NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the fit kernels, the Philox4x32-7 stream and the
+       NeuTra matrix-core kernels (conditioners wider than 32). */
 };
 
 typedef struct {
     int32_t kind;
     int32_t n_components; /* NFMC_POT_GAUSSIAN_MIXTURE: K; NFMC_POT_LOGISTIC_REGRESSION: N; NFMC_POT_GAUSSIAN_FULL: d;
                              NFMC_POT_ROSENBROCK: block length; NFMC_POT_STOCHASTIC_VOLATILITY: T = d - 3;
+                             NFMC_POT_SPARSE_LOGISTIC_REGRESSION: N;
                              0 for the other kinds (was `reserved`, same layout) */
     const float* a; /* (d,) or NULL -> a_scalar */
     const float* b; /* (d,) or NULL -> b_scalar */

@@ -281,6 +281,8 @@ int flow_mh_b_launch(const NfmcFlowMhArgs& a, hipStream_t st, int* grid_out, int
         rc = flow_mh_b_rosenbrock(a, c.cpl, c.lpc, hp, rqs, tiles, grid, st, dry);
     } else if (a.pot.kind == NFMC_POT_STOCHASTIC_VOLATILITY) {   // never exact-fit or dual: y and (alpha, beta) are buffers
         rc = flow_mh_b_sv(a, c.cpl, c.lpc, hp, rqs, tiles, grid, st, dry);
+    } else if (a.pot.kind == NFMC_POT_SPARSE_LOGISTIC_REGRESSION) {   // never exact-fit or dual: X and y are tables
+        rc = flow_mh_b_slr(a, c.cpl, c.lpc, hp, rqs, tiles, grid, st, dry);
     } else {
 #define M(CPL, LPC)                                                                      \
     if (c.cpl == CPL && c.lpc == LPC)                                                    \

@@ -149,6 +149,11 @@ int flow_mh_b_sv(const NfmcFlowMhArgs& a, int cpl, int lpc, int hp, bool rqs, in
                  bool dry);
 int flow_mh_b_sv_rqs(const NfmcFlowMhArgs& a, int cpl, int lpc, int hp, int64_t tiles, int grid, hipStream_t st, bool dry);
 
+// kind 7 (SparseLogRegPot), the same way: flow_b_slr.hip / flow_b_slr_rqs.hip.  No dual-chain kernel.
+int flow_mh_b_slr(const NfmcFlowMhArgs& a, int cpl, int lpc, int hp, bool rqs, int64_t tiles, int grid, hipStream_t st,
+                  bool dry);
+int flow_mh_b_slr_rqs(const NfmcFlowMhArgs& a, int cpl, int lpc, int hp, int64_t tiles, int grid, hipStream_t st, bool dry);
+
 // one launch of the general (diagnostics compiled in, default stream) register kernel of potential POT
 template <template <int, int, bool> class POT, int CPL, int LPC, int HP, int NB>
 int launch_b_general(const NfmcFlowMhArgs& a, int64_t tiles, int grid, hipStream_t st, bool dry) {

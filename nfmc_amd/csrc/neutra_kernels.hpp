@@ -260,6 +260,48 @@ __device__ __forceinline__ float sv_value_grad_row(const float* __restrict__ row
     return u + log1pf(m * m) + sps + tm1 * s + ca * spm + cb * spp + 0.5f * qwd * d0;
 }
 
+// Sparse logistic regression (NFMC_POT_SPARSE_LOGISTIC_REGRESSION) for the row of one chain, as potential_value_grad_row:
+// U and dU/dx of SparseLogRegPot (common.hpp), x_{2j} = w_j, x_{2j+1} = log lambda_j, x_{2D} = log tau.  The gradient
+// row is the workspace: beta_j goes to grow[2j] and g_j accumulates in grow[2j + 1] over one pass through the rows of X
+// (z_i, then its residual into g), and the chain rule then overwrites both, pair by pair.  X and y are wave-uniform
+// (scalar loads); the data term is summed in fp64, as in SparseLogRegPot.  Kept out of potential_value_grad_row, which
+// the fit and DLMC kernels share and which never see kind 7.
+__device__ __forceinline__ float slr_value_grad_row(const float* __restrict__ row, float* __restrict__ grow,
+                                                    const NfmcPotential& p, int d) {
+    const float* __restrict__ X = p.a;
+    const float* __restrict__ y = p.b;
+    const int nd = (d - 1) >> 1, nr = p.n_components;
+    const float ca = p.a_scalar, cb = p.b_scalar, s = row[2 * nd];
+    for (int j = 0; j < nd; ++j) {
+        grow[2 * j] = fast_exp(s + row[2 * j + 1]) * row[2 * j];   // beta_j
+        grow[2 * j + 1] = 0.f;                                     // g_j
+    }
+    double ul = 0.0;
+    for (int i = 0; i < nr; ++i) {
+        const float* __restrict__ xi = X + (int64_t)i * nd;
+        float z = 0.f;
+        for (int j = 0; j < nd; ++j) z = fmaf(xi[j], grow[2 * j], z);
+        float sp, sg;
+        softplus_sigmoid(z, sp, sg);
+        const float yv = y[i];
+        ul += (double)(sp - yv * z);
+        const float r = sg - yv;
+        for (int j = 0; j < nd; ++j) grow[2 * j + 1] = fmaf(r, xi[j], grow[2 * j + 1]);
+    }
+    float u = 0.f, sbg = 0.f;
+    for (int j = 0; j < nd; ++j) {
+        const float w = row[2 * j], l = row[2 * j + 1], bt = grow[2 * j], gj = grow[2 * j + 1];
+        const float el = fast_exp(l), bg = bt * gj;
+        grow[2 * j] = fmaf(fast_exp(s + l), gj, w);
+        grow[2 * j + 1] = bg + fmaf(cb, el, -ca);
+        sbg += bg;
+        u += fmaf(0.5f * w, w, fmaf(cb, el, -ca * l));
+    }
+    const float es = fast_exp(s);
+    grow[2 * nd] = sbg + fmaf(cb, es, -ca);
+    return (float)(ul + (double)(u + fmaf(cb, es, -ca * s)));
+}
+
 // U~(z) and grad U~(z) for this lane's chain.  zrow: latent (tile columns in latent order), read only;
 // wrow: scratch, ends holding z again (rebuilt); grow: gradient in the same column order as zrow.
 template <int HP>
@@ -271,6 +313,7 @@ __device__ __forceinline__ float adjusted_potential_grad_row(const float* __rest
     const float u = pot.kind == NFMC_POT_GAUSSIAN_FULL ? fullrank_value_grad_row(wrow, grow, pot, g.d)
                     : pot.kind == NFMC_POT_ROSENBROCK    ? rosenbrock_value_grad_row(wrow, grow, pot, g.d)
                     : pot.kind == NFMC_POT_STOCHASTIC_VOLATILITY ? sv_value_grad_row(wrow, grow, pot, g.d)
+                    : pot.kind == NFMC_POT_SPARSE_LOGISTIC_REGRESSION ? slr_value_grad_row(wrow, grow, pot, g.d)
                                                          : potential_value_grad_row(wrow, grow, pot, g.d);  // U(x), dU/dx (neutra.py:62)
     // reverse sweep, mirror image of flow_inverse_row
     for (int c = 0; c < g.d; ++c) {                               // EA0^-1

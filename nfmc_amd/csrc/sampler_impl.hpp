@@ -558,8 +558,8 @@ struct Cfg {
 
 // The layouts choose_cfg picks without the NFMC_SAMPLER_CFG override: the smallest capacity CPL * LPC >= d, at equal
 // capacity the first in kCfgs.  (4, 16), (16, 4), (16, 8), (16, 16) and (16, 32) tie with an earlier layout and are
-// reachable only through the override; LogRegPot, GaussFullPot, RosenbrockPot and SVPot are not instantiated there
-// (the override skips them for kinds 3 to 6).
+// reachable only through the override; LogRegPot, GaussFullPot, RosenbrockPot, SVPot and SparseLogRegPot are not
+// instantiated there (the override skips them for kinds 3 to 7).
 constexpr bool is_default_cfg(int cpl, int lpc) {
     return !((cpl == 4 && lpc == 16) || (cpl == 16 && lpc != 64));
 }
@@ -635,8 +635,8 @@ int launch_mala_cfg(const NfmcMalaArgs& a, const JumpDev& jd, bool fast, int64_t
             return NFMC_EUNSUPPORTED;   // not reached: choose_cfg never picks this layout for kind 3
         }
     } else if (a.pot.kind == NFMC_POT_GAUSSIAN_FULL || a.pot.kind == NFMC_POT_ROSENBROCK ||
-               a.pot.kind == NFMC_POT_STOCHASTIC_VOLATILITY) {
-        return NFMC_EUNSUPPORTED;   // not reached: kinds 4 to 6 launch from sampler_{fullrank,rosenbrock,sv}_*.hip
+               a.pot.kind == NFMC_POT_STOCHASTIC_VOLATILITY || a.pot.kind == NFMC_POT_SPARSE_LOGISTIC_REGRESSION) {
+        return NFMC_EUNSUPPORTED;   // not reached: kinds 4 to 7 launch from sampler_{fullrank,rosenbrock,sv,slr}_*.hip
     } else if (a.pot.kind == NFMC_POT_FUNNEL) {
         if (fast) NFMC_L(FunnelPot, true) else NFMC_L(FunnelPot, false)
     } else {
@@ -681,8 +681,8 @@ int launch_hmc_cfg(const NfmcHmcArgs& a, const JumpDev& jd, bool fast, int64_t t
             return NFMC_EUNSUPPORTED;   // not reached: choose_cfg never picks this layout for kind 3
         }
     } else if (a.pot.kind == NFMC_POT_GAUSSIAN_FULL || a.pot.kind == NFMC_POT_ROSENBROCK ||
-               a.pot.kind == NFMC_POT_STOCHASTIC_VOLATILITY) {
-        return NFMC_EUNSUPPORTED;   // not reached: kinds 4 to 6 launch from sampler_{fullrank,rosenbrock,sv}_*.hip
+               a.pot.kind == NFMC_POT_STOCHASTIC_VOLATILITY || a.pot.kind == NFMC_POT_SPARSE_LOGISTIC_REGRESSION) {
+        return NFMC_EUNSUPPORTED;   // not reached: kinds 4 to 7 launch from sampler_{fullrank,rosenbrock,sv,slr}_*.hip
     } else if (a.pot.kind == NFMC_POT_FUNNEL) {
         if (fast) NFMC_L(FunnelPot, true) else NFMC_L(FunnelPot, false)
     } else {
@@ -692,9 +692,9 @@ int launch_hmc_cfg(const NfmcHmcArgs& a, const JumpDev& jd, bool fast, int64_t t
     return NFMC_OK;
 }
 
-// kinds 4 (GaussFullPot), 5 (RosenbrockPot) and 6 (SVPot): translation units of their own (sampler_fullrank_*.hip,
-// sampler_rosenbrock_*.hip, sampler_sv_*.hip), the layouts kind 3 gets, general kernels on the default Philox4x32-10
-// stream only
+// kinds 4 (GaussFullPot), 5 (RosenbrockPot), 6 (SVPot) and 7 (SparseLogRegPot): translation units of their own
+// (sampler_fullrank_*.hip, sampler_rosenbrock_*.hip, sampler_sv_*.hip, sampler_slr_*.hip), the layouts kind 3 gets,
+// general kernels on the default Philox4x32-10 stream only
 template <template <int, int, bool> class POT, int CPL, int LPC, int JHP>
 int launch_mala_general_cfg(const NfmcMalaArgs& a, const JumpDev& jd, int64_t tiles, int grid, float sqrt2h,
                             hipStream_t st) {
@@ -733,5 +733,8 @@ int launch_hmc_rosenbrock(const NfmcHmcArgs&, const JumpDev&, Cfg, int, int64_t,
 // defined in sampler_sv_mala.hip / sampler_sv_hmc.hip: kind 6, the same arguments
 int launch_mala_sv(const NfmcMalaArgs&, const JumpDev&, Cfg, int, int64_t, int, float, hipStream_t);
 int launch_hmc_sv(const NfmcHmcArgs&, const JumpDev&, Cfg, int, int64_t, int, hipStream_t);
+// defined in sampler_slr_mala.hip / sampler_slr_hmc.hip: kind 7, the same arguments
+int launch_mala_slr(const NfmcMalaArgs&, const JumpDev&, Cfg, int, int64_t, int, float, hipStream_t);
+int launch_hmc_slr(const NfmcHmcArgs&, const JumpDev&, Cfg, int, int64_t, int, hipStream_t);
 
 }  // namespace nfmc

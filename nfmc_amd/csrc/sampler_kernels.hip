@@ -46,13 +46,15 @@ static int check_common(const Args* a) {
     if (!(a->step_size > 0.f)) return NFMC_EINVAL;
     if (a->pot.kind != NFMC_POT_QUADRATIC && a->pot.kind != NFMC_POT_FUNNEL && a->pot.kind != NFMC_POT_GAUSSIAN_MIXTURE &&
         a->pot.kind != NFMC_POT_LOGISTIC_REGRESSION && a->pot.kind != NFMC_POT_GAUSSIAN_FULL &&
-        a->pot.kind != NFMC_POT_ROSENBROCK && a->pot.kind != NFMC_POT_STOCHASTIC_VOLATILITY)
+        a->pot.kind != NFMC_POT_ROSENBROCK && a->pot.kind != NFMC_POT_STOCHASTIC_VOLATILITY &&
+        a->pot.kind != NFMC_POT_SPARSE_LOGISTIC_REGRESSION)
         return NFMC_EUNSUPPORTED;
     if (int rc = check_mixture(a->pot)) return rc;
     if (int rc = check_logreg(a->pot)) return rc;
     if (int rc = check_fullrank(a->pot, a->d)) return rc;
     if (int rc = check_rosenbrock(a->pot, a->d)) return rc;
     if (int rc = check_sv(a->pot, a->d)) return rc;
+    if (int rc = check_slr(a->pot, a->d)) return rc;
     if (((uintptr_t)a->x & 3u) != 0) return NFMC_EALIGN;
     if (!store_ok(a->samples)) return NFMC_EINVAL;
     if (!rng_rounds_ok(a->rng, true)) return NFMC_EINVAL;
@@ -271,16 +273,17 @@ static int check_tune(const Args& a, int dp) {
 // the potentials instantiated at the default layouts only (is_default_cfg)
 static bool default_cfg_only(const NfmcPotential& p) {
     return p.kind == NFMC_POT_LOGISTIC_REGRESSION || p.kind == NFMC_POT_GAUSSIAN_FULL || p.kind == NFMC_POT_ROSENBROCK ||
-           p.kind == NFMC_POT_STOCHASTIC_VOLATILITY;
+           p.kind == NFMC_POT_STOCHASTIC_VOLATILITY || p.kind == NFMC_POT_SPARSE_LOGISTIC_REGRESSION;
 }
 
-// one launch of the mala / hmc kernels at layout c with jump-tail width jhp: kinds 4 and 5 have translation units of
+// one launch of the mala / hmc kernels at layout c with jump-tail width jhp: kinds 4 to 7 have translation units of
 // their own
 static int launch_mala(const NfmcMalaArgs& a, const JumpDev& jd, Cfg c, int jhp, bool fast, int64_t tiles, int grid,
                        float sqrt2h, hipStream_t st) {
     if (a.pot.kind == NFMC_POT_GAUSSIAN_FULL) return launch_mala_fullrank(a, jd, c, jhp, tiles, grid, sqrt2h, st);
     if (a.pot.kind == NFMC_POT_ROSENBROCK) return launch_mala_rosenbrock(a, jd, c, jhp, tiles, grid, sqrt2h, st);
     if (a.pot.kind == NFMC_POT_STOCHASTIC_VOLATILITY) return launch_mala_sv(a, jd, c, jhp, tiles, grid, sqrt2h, st);
+    if (a.pot.kind == NFMC_POT_SPARSE_LOGISTIC_REGRESSION) return launch_mala_slr(a, jd, c, jhp, tiles, grid, sqrt2h, st);
     return jhp == 0 ? launch_mala_j0(a, jd, c, fast, tiles, grid, sqrt2h, st)
                     : (jhp == 4 ? launch_mala_j4(a, jd, c, fast, tiles, grid, sqrt2h, st)
                                 : launch_mala_j8(a, jd, c, fast, tiles, grid, sqrt2h, st));
@@ -290,6 +293,7 @@ static int launch_hmc(const NfmcHmcArgs& a, const JumpDev& jd, Cfg c, int jhp, b
     if (a.pot.kind == NFMC_POT_GAUSSIAN_FULL) return launch_hmc_fullrank(a, jd, c, jhp, tiles, grid, st);
     if (a.pot.kind == NFMC_POT_ROSENBROCK) return launch_hmc_rosenbrock(a, jd, c, jhp, tiles, grid, st);
     if (a.pot.kind == NFMC_POT_STOCHASTIC_VOLATILITY) return launch_hmc_sv(a, jd, c, jhp, tiles, grid, st);
+    if (a.pot.kind == NFMC_POT_SPARSE_LOGISTIC_REGRESSION) return launch_hmc_slr(a, jd, c, jhp, tiles, grid, st);
     return jhp == 0 ? launch_hmc_j0(a, jd, c, fast, tiles, grid, st)
                     : (jhp == 4 ? launch_hmc_j4(a, jd, c, fast, tiles, grid, st) : launch_hmc_j8(a, jd, c, fast, tiles, grid, st));
 }
