@@ -20,6 +20,15 @@ constexpr int kMaxGrid = 2048;       // 256 CUs x 8 workgroups; larger problems 
 #endif
 constexpr int kStatTail = 4;         // per-workgroup scratch tail: accepted, nonfinite, jump accepted, jump nonfinite
 
+// Wave mask with the bit of the first lane of every group of LPC lanes (LPC a power of 2): one chain's lanes agree on
+// every per-chain predicate, so a ballot & leaders counts chains
+constexpr unsigned long long group_leaders(int lpc) {
+    unsigned long long m = 0;
+    for (int lane = 0; lane < kWave; lane += lpc) m |= 1ull << lane;
+    return m;
+}
+static_assert(group_leaders(1) == ~0ull && group_leaders(4) == 0x1111111111111111ull && group_leaders(64) == 1ull, "");
+
 // RNG stream tags (oracle/philox.py)
 constexpr uint32_t kTagNoise = 0, kTagAccept = 1, kTagLatent = 2, kTagJump = 3;
 
@@ -328,9 +337,8 @@ constexpr int kMixMaxK = 8;
 
 __host__ __device__ inline int mixture_floats(int k, int dp) { return 2 * k * dp; }
 
-// argument check of a kind-2 descriptor at the entry points that run it (0 for every other kind)
-inline int check_mixture(const NfmcPotential& p) {
-    if (p.kind != NFMC_POT_GAUSSIAN_MIXTURE) return NFMC_OK;
+// argument check of a kind-2 descriptor (the check of its row in kPotKinds, as the check_* below are of theirs)
+inline int check_mixture(const NfmcPotential& p, int) {
     if (!p.a || !p.b || p.n_components < 1) return NFMC_EINVAL;
     if ((((uintptr_t)p.a) & 15u) != 0 || (((uintptr_t)p.b) & 15u) != 0) return NFMC_EALIGN;
     if (p.n_components > kMixMaxK) return NFMC_EUNSUPPORTED;
@@ -355,35 +363,28 @@ constexpr int kLogRegTileFloats = 4096;   // the X part of a tile: 16 KB
 __host__ __device__ inline int logreg_tile_rows(int dp) { return kLogRegTileFloats / dp; }   // dp: a power of 2, 4 .. 1024
 __host__ __device__ inline int logreg_floats(int dp) { return logreg_tile_rows(dp) * (dp + 1); }
 
-// argument check of a kind-3 descriptor at the entry points that run it (0 for every other kind)
-inline int check_logreg(const NfmcPotential& p) {
-    if (p.kind != NFMC_POT_LOGISTIC_REGRESSION) return NFMC_OK;
+// argument check of a kind-3 descriptor
+inline int check_logreg(const NfmcPotential& p, int) {
     if (!p.a || !p.b || p.n_components < 1 || !(p.a_scalar > 0.f && p.a_scalar <= 3.0e38f)) return NFMC_EINVAL;
     if ((((uintptr_t)p.a) & 15u) != 0) return NFMC_EALIGN;
     return NFMC_OK;
 }
 
-// argument check of a kind-4 descriptor at the entry points that run it (0 for every other kind): Lambda (d, d) and mu
-// (d,) present, n_components = d, Lambda 16-byte aligned
+// argument check of a kind-4 descriptor: Lambda (d, d) and mu (d,) present, n_components = d, Lambda 16-byte aligned
 inline int check_fullrank(const NfmcPotential& p, int d) {
-    if (p.kind != NFMC_POT_GAUSSIAN_FULL) return NFMC_OK;
     if (!p.a || !p.b || p.n_components != d || (((uintptr_t)p.a) & 15u) != 0) return NFMC_EINVAL;
     return NFMC_OK;
 }
 
-// argument check of a kind-5 descriptor at the entry points that run it (0 for every other kind): mu present, block
-// 1 .. d, a and b positive and finite
+// argument check of a kind-5 descriptor: mu present, block 1 .. d, a and b positive and finite
 inline int check_rosenbrock(const NfmcPotential& p, int d) {
-    if (p.kind != NFMC_POT_ROSENBROCK) return NFMC_OK;
     if (!p.a || p.n_components < 1 || p.n_components > d) return NFMC_EINVAL;
     if (!(p.a_scalar > 0.f && p.a_scalar <= 3.0e38f) || !(p.b_scalar > 0.f && p.b_scalar <= 3.0e38f)) return NFMC_EINVAL;
     return NFMC_OK;
 }
 
-// argument check of a kind-6 descriptor at the entry points that run it (0 for every other kind): y and (alpha, beta)
-// present, T = d - 3 >= 1, c_mu and c_sigma positive and finite
+// argument check of a kind-6 descriptor: y and (alpha, beta) present, T = d - 3 >= 1, c_mu and c_sigma positive and finite
 inline int check_sv(const NfmcPotential& p, int d) {
-    if (p.kind != NFMC_POT_STOCHASTIC_VOLATILITY) return NFMC_OK;
     if (!p.a || !p.b || p.n_components < 1 || p.n_components != d - 3) return NFMC_EINVAL;
     if (!(p.a_scalar > 0.f && p.a_scalar <= 3.0e38f) || !(p.b_scalar > 0.f && p.b_scalar <= 3.0e38f)) return NFMC_EINVAL;
     return NFMC_OK;
@@ -394,24 +395,75 @@ inline int check_sv(const NfmcPotential& p, int d) {
 __host__ __device__ inline int slr_tile_rows(int dp) { return kLogRegTileFloats / (dp / 2); }   // dp: a power of 2, 4 .. 1024
 __host__ __device__ inline int slr_floats(int dp) { return slr_tile_rows(dp) * (dp / 2 + 1); }
 
-// argument check of a kind-7 descriptor at the entry points that run it (0 for every other kind): X and y present, d = 2 D
-// + 1 odd and >= 3, N >= 1, X 16-byte aligned, a and b positive and finite
+// argument check of a kind-7 descriptor: X and y present, d = 2 D + 1 odd and >= 3, N >= 1, X 16-byte aligned, a and b
+// positive and finite
 inline int check_slr(const NfmcPotential& p, int d) {
-    if (p.kind != NFMC_POT_SPARSE_LOGISTIC_REGRESSION) return NFMC_OK;
     if (!p.a || !p.b || p.n_components < 1 || d < 3 || (d & 1) == 0) return NFMC_EINVAL;
     if ((((uintptr_t)p.a) & 15u) != 0) return NFMC_EINVAL;
     if (!(p.a_scalar > 0.f && p.a_scalar <= 3.0e38f) || !(p.b_scalar > 0.f && p.b_scalar <= 3.0e38f)) return NFMC_EINVAL;
     return NFMC_OK;
 }
 
-// LDS bytes a register-layout kernel with DP padded coordinates stages for `p` beside its flow image (0 unless kind 2,
-// 3, 4 or 7)
+// LDS bytes a register-layout kernel with DP padded coordinates stages for `p` beside its flow image
+inline size_t mixture_bytes(const NfmcPotential& p, int dp) { return (size_t)mixture_floats(p.n_components, dp) * sizeof(float); }
+inline size_t logreg_bytes(const NfmcPotential&, int dp) { return (size_t)logreg_floats(dp) * sizeof(float); }
+inline size_t fullrank_bytes(const NfmcPotential&, int) { return (size_t)kLogRegTileFloats * sizeof(float); }
+inline size_t slr_bytes(const NfmcPotential&, int dp) { return (size_t)slr_floats(dp) * sizeof(float); }
+
+// ------------------------------------------------------------------------------------------------
+// The potential kinds, as the host sees them: one row per NFMC_POT_* value, indexed by it.  Every entry point that asks
+// "does this family of kernels run the kind, and is its descriptor well formed" goes through check_potential(); every
+// host decision that depends on the kind reads a column here.  Adding a potential kind:
+//   1. nfmc_hip.h: its NFMC_POT_* value and descriptor fields; here: its check_* function and its row.
+//   2. Its device class Pot<CPL, LPC, FAST> below (prepare / grad / term, and stage() with a *_bytes function if kStaged).
+//   3. own_units: a line in NFMC_FOR_OWN_UNIT_POT and four units that instantiate launch_{mala,hmc}_kind and
+//      launch_b_kind{,_rqs} for the class (sampler_slr_mala.hip and its three siblings are the pattern).
+//   4. neutra_valu: its *_value_grad_row and its arm of adjusted_potential_grad_row (neutra_kernels.hpp).
+//   5. Python: POT_* in nfmc_amd/hip.py, its class in nfmc_amd/potentials.py, an fp64 oracle tests/<kind>_fp64.py and
+//      tests/test_{host,gpu}_<kind>.py, which assert the codes of step 1's check.
+struct PotKind {
+    int kind;
+    int (*check)(const NfmcPotential&, int d);              // its own argument check (nullptr: nothing to check)
+    size_t (*staged_bytes)(const NfmcPotential&, int dp);   // the LDS block its class stages (nullptr: none)
+    bool own_units;          // samplers and flow-MH: general kernels only, in translation units of its own
+    bool default_cfg_only;   // samplers: instantiated at the default layouts only (is_default_cfg, sampler_impl.hpp)
+    bool register_only;      // flow-MH: the register-layout kernels only (no matrix-core or one-chain-per-lane kernel)
+    bool neutra_valu;        // evaluated by the VALU NeuTra kernels (neutra_kernels.hpp)
+};
+constexpr PotKind kPotKinds[] = {
+    {NFMC_POT_QUADRATIC, nullptr, nullptr, false, false, false, true},
+    {NFMC_POT_FUNNEL, nullptr, nullptr, false, false, false, true},
+    {NFMC_POT_GAUSSIAN_MIXTURE, check_mixture, mixture_bytes, false, false, true, false},
+    {NFMC_POT_LOGISTIC_REGRESSION, check_logreg, logreg_bytes, false, true, true, false},
+    {NFMC_POT_GAUSSIAN_FULL, check_fullrank, fullrank_bytes, true, true, true, true},
+    {NFMC_POT_ROSENBROCK, check_rosenbrock, nullptr, true, true, true, true},
+    {NFMC_POT_STOCHASTIC_VOLATILITY, check_sv, nullptr, true, true, true, true},
+    {NFMC_POT_SPARSE_LOGISTIC_REGRESSION, check_slr, slr_bytes, true, true, true, true},
+};
+constexpr int kNumPotKinds = (int)(sizeof(kPotKinds) / sizeof(PotKind));
+constexpr bool pot_kinds_indexed(int i = 0) { return i == kNumPotKinds || (kPotKinds[i].kind == i && pot_kinds_indexed(i + 1)); }
+static_assert(pot_kinds_indexed(), "row i of kPotKinds describes kind i");
+// the row of `kind`; nullptr for a value that is no kind
+constexpr const PotKind* pot_kind(int kind) { return kind >= 0 && kind < kNumPotKinds ? &kPotKinds[kind] : nullptr; }
+
+// The own_units kinds with their device classes: the explicit instantiations' extern declarations and the dispatch
+// switches (sampler_impl.hpp, flow_b_mh.hpp) expand this list, and each expansion asserts the row's flag.
+#define NFMC_FOR_OWN_UNIT_POT(M)                                            \
+    M(NFMC_POT_GAUSSIAN_FULL, GaussFullPot) M(NFMC_POT_ROSENBROCK, RosenbrockPot) \
+    M(NFMC_POT_STOCHASTIC_VOLATILITY, SVPot) M(NFMC_POT_SPARSE_LOGISTIC_REGRESSION, SparseLogRegPot)
+
+// The families of kernels that take a potential descriptor of any kind.  (The entry points that run kinds 0 and 1 only
+// say so themselves.)
+enum class PotFamily { kRegister, kNeutraValu };   // samplers and flow-MH / VALU NeuTra
+// NFMC_EUNSUPPORTED for a kind the family does not run, then the kind's own NFMC_EINVAL / NFMC_EALIGN / NFMC_EUNSUPPORTED
+inline int check_potential(const NfmcPotential& p, int d, PotFamily family) {
+    const PotKind* k = pot_kind(p.kind);
+    if (!k || (family == PotFamily::kNeutraValu && !k->neutra_valu)) return NFMC_EUNSUPPORTED;
+    return k->check ? k->check(p, d) : NFMC_OK;
+}
 inline size_t staged_potential_bytes(const NfmcPotential& p, int dp) {
-    if (p.kind == NFMC_POT_GAUSSIAN_MIXTURE) return (size_t)mixture_floats(p.n_components, dp) * sizeof(float);
-    if (p.kind == NFMC_POT_LOGISTIC_REGRESSION) return (size_t)logreg_floats(dp) * sizeof(float);
-    if (p.kind == NFMC_POT_GAUSSIAN_FULL) return (size_t)kLogRegTileFloats * sizeof(float);
-    if (p.kind == NFMC_POT_SPARSE_LOGISTIC_REGRESSION) return (size_t)slr_floats(dp) * sizeof(float);
-    return 0;
+    const PotKind* k = pot_kind(p.kind);
+    return k && k->staged_bytes ? k->staged_bytes(p, dp) : 0;
 }
 
 template <int CPL, int LPC, bool FAST>
@@ -1368,6 +1420,19 @@ inline int padded_d(int d) {
     int p = 4;
     while (p < d) p <<= 1;
     return p;
+}
+
+// Launch `kern` with `lds` bytes of dynamic LDS, raising the kernel's limit first where the launch needs more than the
+// 48 KB every kernel may have: the hipError_t of a failed attribute call, else NFMC_OK (a failed launch shows in
+// NFMC_HIP_CHECK_LAUNCH).  Per call: the attribute belongs to the (kernel, device) pair, and a process may drive several.
+template <class K, class... Args>
+int launch_lds(K kern, int grid, int block, size_t lds, hipStream_t st, const Args&... args) {
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, st, args...);
+    return NFMC_OK;
 }
 
 #define NFMC_HIP_CHECK_LAUNCH()                \

@@ -760,11 +760,10 @@ static int fit_call(const NfmcFlowFit* fit, const NfmcPotential* pot, const floa
         const size_t lds = fit_lds_bytes(f.d, hp, rpw);
 #define NFMC_FIT_LAUNCH3(HPV, RKLV, RPWV)                                                                                 \
     {                                                                                                                     \
-        auto kern = fit_grad_kernel<HPV, RKLV, RPWV>;                                                                     \
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);      \
-        if (e != hipSuccess) return (int)e;                                                                               \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kFitBlock), lds, st, f, p0, x, n_train, fit->x_val, nv, fit->partial,   \
-                           pstride, fit->ea_off, d4, fit->n_params, tiles, vtiles, state_in);                             \
+        const int rc_ = launch_lds(fit_grad_kernel<HPV, RKLV, RPWV>, grid, kFitBlock, lds, st, f, p0, x, n_train,         \
+                                   fit->x_val, nv, fit->partial, pstride, fit->ea_off, d4, fit->n_params, tiles, vtiles,  \
+                                   state_in);                                                                             \
+        if (rc_) return rc_;                                                                                              \
     }
 #define NFMC_FIT_LAUNCH2(HPV, RKLV)              \
     if (rpw == 16) NFMC_FIT_LAUNCH3(HPV, RKLV, 16) \

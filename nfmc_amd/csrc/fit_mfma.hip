@@ -478,19 +478,8 @@ __global__ void __launch_bounds__(kMfmaBlock, 2) fit_mfma_kernel(FitMfmaArgs a) 
 
 template <int TD, int TH, int NHL>
 static int fit_mfma_go(bool rkl, const FitMfmaArgs& a, int grid, hipStream_t st) {
-    hipError_t e;
-    if (rkl) {
-        auto kern = fit_mfma_kernel<TD, TH, NHL, true>;
-        e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMfmaLdsBytes);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kMfmaBlock), kMfmaLdsBytes, st, a);
-    } else {
-        auto kern = fit_mfma_kernel<TD, TH, NHL, false>;
-        e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMfmaLdsBytes);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kMfmaBlock), kMfmaLdsBytes, st, a);
-    }
-    return 0;
+    auto kern = rkl ? fit_mfma_kernel<TD, TH, NHL, true> : fit_mfma_kernel<TD, TH, NHL, false>;
+    return launch_lds(kern, grid, kMfmaBlock, kMfmaLdsBytes, st, a);
 }
 
 int64_t fit_mfma_ck_floats(int d, int hp, int n_hl, int n_coupling, int grid) {

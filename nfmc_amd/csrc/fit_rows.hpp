@@ -937,11 +937,7 @@ __global__ void __launch_bounds__(kFrThreads) fit_rows_kernel(FitRowsArgs a) {
     namespace nfmc {                                                                                                       \
     template <bool RKL, int CH, int S>                                                                                     \
     static int fit_rows_go(const FitRowsArgs& a, int grid, size_t lds, hipStream_t st) {                                   \
-        auto kern = fit_rows_kernel<HPV, RKL, CH, S>;                                                                      \
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);       \
-        if (e != hipSuccess) return (int)e;                                                                                \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kFrThreads), lds, st, a);                                                \
-        return 0;                                                                                                          \
+        return launch_lds(fit_rows_kernel<HPV, RKL, CH, S>, grid, kFrThreads, lds, st, a);                                 \
     }                                                                                                                      \
     int NAME(bool rkl, int ch, int s, const FitRowsArgs& a, int grid, size_t lds, hipStream_t st) {                        \
         if (rkl) {                                                                                                         \

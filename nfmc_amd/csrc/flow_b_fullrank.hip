@@ -1,19 +1,5 @@
-// Flow-MH register kernels for the full-rank Gaussian (kind 4, GaussFullPot), affine couplings, in a translation unit
-// of their own so that they compile in parallel with flow_b_kernels.hip: see flow_b_mh.hpp
+// flow-MH register kernels of kind 4 (GaussFullPot, the full-rank Gaussian), affine couplings, in a unit of their own,
+// compiled in parallel with flow_b_kernels.hip: launch_b_kind, flow_b_mh.hpp
 #include "flow_b_mh.hpp"
 
-namespace nfmc {
-
-int flow_mh_b_fullrank(const NfmcFlowMhArgs& a, int cpl, int lpc, int hp, bool rqs, int64_t tiles, int grid, hipStream_t st,
-                       bool dry) {
-    if (rqs) return flow_mh_b_fullrank_rqs(a, cpl, lpc, hp, tiles, grid, st, dry);
-    int rc = NFMC_EUNSUPPORTED;
-#define M(CPL, LPC)                                                                                              \
-    if (cpl == CPL && lpc == LPC)                                                                                \
-        rc = hp == 4 ? launch_b_general<GaussFullPot, CPL, LPC, 4, 0>(a, tiles, grid, st, dry) : launch_b_general<GaussFullPot, CPL, LPC, 8, 0>(a, tiles, grid, st, dry);
-    NFMC_FOR_BCFG(M)
-#undef M
-    return rc;
-}
-
-}  // namespace nfmc
+template int nfmc::launch_b_kind<nfmc::GaussFullPot, 0>(const NfmcFlowMhArgs&, nfmc::BCfg, int, int64_t, int, hipStream_t, bool);

@@ -31,8 +31,7 @@ __global__ void __launch_bounds__(kBlock, 1) flow_mh_b2_kernel(NfmcFlowMhArgs a,
 #pragma unroll
     for (int i = 0; i < CPL; ++i) sx[i] = sxx[i] = 0.f;
     uint32_t n_acc = 0, n_bad = 0;
-    const unsigned long long leaders = LPC == 64 ? 1ull : (LPC == 32 ? 0x0000000100000001ull
-                                       : LPC == 16 ? 0x0001000100010001ull : 0x0101010101010101ull);
+    constexpr unsigned long long leaders = group_leaders(LPC);
     static_assert(LPC >= 8, "two-chain layouts: 8 .. 64 lanes per chain");
 
     for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
@@ -139,13 +138,6 @@ __global__ void __launch_bounds__(kBlock, 1) flow_mh_b2_kernel(NfmcFlowMhArgs a,
     if (a.stats.sum_x) block_stats_flush<CPL, LPC>(sx, sxx, n_acc, n_bad, a.stats);
 }
 
-struct BCfg {
-    int cpl, lpc;
-};
-static const BCfg kBCfgs[] = {{4, 1}, {4, 2}, {4, 4}, {4, 8}, {8, 8}, {4, 16}, {8, 16}, {4, 32}, {8, 32}, {4, 64}, {8, 64}};
-
-// NFMC_FOR_BCFG (flow_b_mh.hpp) lists the same layouts
-
 // diagnostics (replayed noise, sample store, mask / log-ratio outputs) run on the DIAG instantiation
 static bool wants_diag(const NfmcFlowMhArgs& a) {
     return a.rng.replay_normals || a.rng.replay_uniforms || a.samples.base || a.masks_out || a.log_ratio_out;
@@ -158,12 +150,7 @@ static int launch_b2(const NfmcFlowMhArgs& a, int64_t tiles, int grid, hipStream
         if (lds > 120 * 1024) return NFMC_EUNSUPPORTED;
         if (dry) return 0;
         auto kern = rng_rounds(a.rng) == 7 ? flow_mh_b2_kernel<CPL, LPC, HP, 7> : flow_mh_b2_kernel<CPL, LPC, HP, 10>;
-        if (lds > 48 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return (int)e;
-        }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, a, tiles);
-        return 0;
+        return launch_lds(kern, grid, kBlock, lds, st, a, tiles);
     } else {
         return NFMC_EUNSUPPORTED;
     }
@@ -180,13 +167,7 @@ static int launch_b_rqs(const NfmcFlowMhArgs& a, bool fast, int64_t tiles, int g
         if (lds > 120 * 1024) return NFMC_EUNSUPPORTED;                                                           \
         if (rng_rounds(a.rng) == 7) return NFMC_EUNSUPPORTED;                                                     \
         if (dry) return 0;                                                                                        \
-        auto kern = flow_mh_b_kernel<CPL, LPC, HP, POT, F, true, 10, kRqsBins>;                                   \
-        if (lds > 48 * 1024) {                                                                                    \
-            hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,     \
-                                               (int)lds);                                                         \
-            if (e != hipSuccess) return (int)e;                                                                   \
-        }                                                                                                         \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, a, tiles);                                    \
+        return launch_lds(flow_mh_b_kernel<CPL, LPC, HP, POT, F, true, 10, kRqsBins>, grid, kBlock, lds, st, a, tiles); \
     }
     if (a.pot.kind == NFMC_POT_GAUSSIAN_MIXTURE) NFMC_LBR(MixturePot, false)
     else if (a.pot.kind == NFMC_POT_LOGISTIC_REGRESSION) NFMC_LBR(LogRegPot, false)
@@ -194,7 +175,6 @@ static int launch_b_rqs(const NfmcFlowMhArgs& a, bool fast, int64_t tiles, int g
     else if (fast) NFMC_LBR(QuadraticPot, true)
     else NFMC_LBR(QuadraticPot, false)
 #undef NFMC_LBR
-    return 0;
 }
 
 template <int CPL, int LPC, int HP>
@@ -213,12 +193,7 @@ static int launch_b(const NfmcFlowMhArgs& a, bool fast, int64_t tiles, int grid,
                                : flow_mh_b_kernel<CPL, LPC, HP, POT, F, (F ? false : true), (F ? 7 : 10)>)         \
                        : (diag ? flow_mh_b_kernel<CPL, LPC, HP, POT, F, true>                                      \
                                : flow_mh_b_kernel<CPL, LPC, HP, POT, F, (F ? false : true)>);                      \
-        if (lds > 48 * 1024) {                                                                                  \
-            hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                               (int)lds);                                                       \
-            if (e != hipSuccess) return (int)e;                                                                 \
-        }                                                                                                       \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, a, tiles);                                  \
+        return launch_lds(kern, grid, kBlock, lds, st, a, tiles);                                               \
     }
     if (a.pot.kind == NFMC_POT_GAUSSIAN_MIXTURE) NFMC_LB(MixturePot, false)
     else if (a.pot.kind == NFMC_POT_LOGISTIC_REGRESSION) NFMC_LB(LogRegPot, false)
@@ -226,7 +201,6 @@ static int launch_b(const NfmcFlowMhArgs& a, bool fast, int64_t tiles, int grid,
     else if (fast) NFMC_LB(QuadraticPot, true)
     else NFMC_LB(QuadraticPot, false)
 #undef NFMC_LB
-    return 0;
 }
 
 // Returns NFMC_EUNSUPPORTED when this path does not cover the request (caller falls back to flow_mh_kernel).
@@ -240,14 +214,14 @@ int flow_mh_b_launch(const NfmcFlowMhArgs& a, hipStream_t st, int* grid_out, int
     // few chains, where twice the lanes per chain win (n = 4096: 3.30 vs 3.40 ms)
     BCfg c = {0, 0};
     const int want_cpl = a.n <= 4096 ? 4 : 8;
-    for (const BCfg& k : kBCfgs) {
+    for (const BCfg& k : kFlowBCfgs) {
         if (k.cpl * k.lpc < d) continue;
         if (c.cpl == 0 || k.cpl * k.lpc < c.cpl * c.lpc || (k.cpl * k.lpc == c.cpl * c.lpc && k.cpl == want_cpl)) c = k;
     }
     if (const char* e = getenv("NFMC_FLOWB_CFG")) {  // "cpl,lpc" override (tuning)
         int cc = 0, ll = 0;
         if (sscanf(e, "%d,%d", &cc, &ll) == 2)
-            for (const BCfg& k : kBCfgs)
+            for (const BCfg& k : kFlowBCfgs)
                 if (k.cpl == cc && k.lpc == ll && cc * ll >= d) c = k;
     }
     if (!c.cpl) return NFMC_EUNSUPPORTED;
@@ -275,21 +249,20 @@ int flow_mh_b_launch(const NfmcFlowMhArgs& a, hipStream_t st, int* grid_out, int
         return NFMC_ESCRATCH;
     if (check_defer(a.stats, dp, d)) return NFMC_EINVAL;
     int rc = NFMC_EUNSUPPORTED;
-    if (a.pot.kind == NFMC_POT_GAUSSIAN_FULL) {   // never exact-fit or dual: Lambda and mu are tables
-        rc = flow_mh_b_fullrank(a, c.cpl, c.lpc, hp, rqs, tiles, grid, st, dry);
-    } else if (a.pot.kind == NFMC_POT_ROSENBROCK) {   // never exact-fit or dual: mu is a device buffer
-        rc = flow_mh_b_rosenbrock(a, c.cpl, c.lpc, hp, rqs, tiles, grid, st, dry);
-    } else if (a.pot.kind == NFMC_POT_STOCHASTIC_VOLATILITY) {   // never exact-fit or dual: y and (alpha, beta) are buffers
-        rc = flow_mh_b_sv(a, c.cpl, c.lpc, hp, rqs, tiles, grid, st, dry);
-    } else if (a.pot.kind == NFMC_POT_SPARSE_LOGISTIC_REGRESSION) {   // never exact-fit or dual: X and y are tables
-        rc = flow_mh_b_slr(a, c.cpl, c.lpc, hp, rqs, tiles, grid, st, dry);
-    } else {
+    switch (a.pot.kind) {
+#define NFMC_KIND_CASE(KIND, POT)                                                                    \
+    case KIND:                                                                                       \
+        rc = rqs ? launch_b_kind<POT, kRqsBins>(a, c, hp, tiles, grid, st, dry) : launch_b_kind<POT, 0>(a, c, hp, tiles, grid, st, dry); \
+        break;
+        NFMC_FOR_OWN_UNIT_POT(NFMC_KIND_CASE)
+#undef NFMC_KIND_CASE
+    default:
 #define M(CPL, LPC)                                                                      \
     if (c.cpl == CPL && c.lpc == LPC)                                                    \
         rc = rqs ? (hp == 4 ? launch_b_rqs<CPL, LPC, 4>(a, fast, tiles, grid, st, dry) : launch_b_rqs<CPL, LPC, 8>(a, fast, tiles, grid, st, dry)) \
            : dual ? (hp == 4 ? launch_b2<CPL, LPC, 4>(a, tiles, grid, st, dry) : launch_b2<CPL, LPC, 8>(a, tiles, grid, st, dry)) \
                   : (hp == 4 ? launch_b<CPL, LPC, 4>(a, fast, tiles, grid, st, dry) : launch_b<CPL, LPC, 8>(a, fast, tiles, grid, st, dry));
-        NFMC_FOR_BCFG(M)
+        NFMC_FOR_FLOWB_CFG(M)
 #undef M
     }
     *grid_out = grid;

@@ -1,5 +1,5 @@
 // flow_mh_b_kernel: the flow-proposal Metropolis transitions of flow_b_kernels.hip, in a header of its own so that the
-// full-rank Gaussian's instantiations (flow_b_fullrank.hip) compile in a translation unit of their own.
+// instantiations of the own_units kinds (kPotKinds, common.hpp) compile in translation units of their own.
 #pragma once
 
 #include "flow_b.hpp"
@@ -39,11 +39,7 @@ __global__ void __launch_bounds__(kBlock, NFMC_FLOWB_WPE) flow_mh_b_kernel(NfmcF
 #pragma unroll
     for (int i = 0; i < CPL; ++i) sx[i] = sxx[i] = 0.f;
     uint32_t n_acc = 0, n_bad = 0;
-    const unsigned long long leaders = LPC == 64 ? 1ull : (LPC == 32 ? 0x0000000100000001ull
-                                       : LPC == 16 ? 0x0001000100010001ull
-                                       : LPC == 8 ? 0x0101010101010101ull
-                                       : LPC == 4 ? 0x1111111111111111ull
-                                       : LPC == 2 ? 0x5555555555555555ull : ~0ull);
+    constexpr unsigned long long leaders = group_leaders(LPC);
 
     for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const int64_t row = (tile * kWavesPerBlock + wave) * CPW + cw;
@@ -127,48 +123,44 @@ __global__ void __launch_bounds__(kBlock, NFMC_FLOWB_WPE) flow_mh_b_kernel(NfmcF
     if (a.stats.sum_x) block_stats_flush<CPL, LPC>(sx, sxx, n_acc, n_bad, a.stats);
 }
 
-// the register layouts (CPL, LPC) of the flow-MH kernels (kBCfgs, flow_b_kernels.hip)
-#define NFMC_FOR_BCFG(M) M(4, 1) M(4, 2) M(4, 4) M(4, 8) M(8, 8) M(4, 16) M(8, 16) M(4, 32) M(8, 32) M(4, 64) M(8, 64)
+// the register layouts (CPL, LPC) of the flow-MH kernels, in flow_mh_b_launch's order of preference: kFlowBCfgs is
+// this list.  (Not the samplers' jump-tail layouts, NFMC_FOR_JUMP_CFG in sampler_impl.hpp.)
+struct BCfg {
+    int cpl, lpc;
+};
+#define NFMC_FOR_FLOWB_CFG(M) M(4, 1) M(4, 2) M(4, 4) M(4, 8) M(8, 8) M(4, 16) M(8, 16) M(4, 32) M(8, 32) M(4, 64) M(8, 64)
+#define NFMC_BCFG_ENTRY(CPL, LPC) {CPL, LPC},
+constexpr BCfg kFlowBCfgs[] = {NFMC_FOR_FLOWB_CFG(NFMC_BCFG_ENTRY)};
 
-// kind 4 (GaussFullPot) at layout (cpl, lpc), conditioner bucket hp (4 / 8), affine or spline (rqs) couplings; the
-// arguments and NFMC_EUNSUPPORTED / dry as in flow_mh_b_launch.  Defined in flow_b_fullrank.hip (the spline couplings in
-// flow_b_fullrank_rqs.hip): one instantiation per layout and width, diagnostics compiled in, default stream.
-int flow_mh_b_fullrank(const NfmcFlowMhArgs& a, int cpl, int lpc, int hp, bool rqs, int64_t tiles, int grid, hipStream_t st,
-                       bool dry);
-int flow_mh_b_fullrank_rqs(const NfmcFlowMhArgs& a, int cpl, int lpc, int hp, int64_t tiles, int grid, hipStream_t st,
-                           bool dry);
-
-// kind 5 (RosenbrockPot), the same way: flow_b_rosenbrock.hip / flow_b_rosenbrock_rqs.hip.  No dual-chain kernel.
-int flow_mh_b_rosenbrock(const NfmcFlowMhArgs& a, int cpl, int lpc, int hp, bool rqs, int64_t tiles, int grid,
-                         hipStream_t st, bool dry);
-int flow_mh_b_rosenbrock_rqs(const NfmcFlowMhArgs& a, int cpl, int lpc, int hp, int64_t tiles, int grid, hipStream_t st,
-                             bool dry);
-
-// kind 6 (SVPot), the same way: flow_b_sv.hip / flow_b_sv_rqs.hip.  No dual-chain kernel.
-int flow_mh_b_sv(const NfmcFlowMhArgs& a, int cpl, int lpc, int hp, bool rqs, int64_t tiles, int grid, hipStream_t st,
-                 bool dry);
-int flow_mh_b_sv_rqs(const NfmcFlowMhArgs& a, int cpl, int lpc, int hp, int64_t tiles, int grid, hipStream_t st, bool dry);
-
-// kind 7 (SparseLogRegPot), the same way: flow_b_slr.hip / flow_b_slr_rqs.hip.  No dual-chain kernel.
-int flow_mh_b_slr(const NfmcFlowMhArgs& a, int cpl, int lpc, int hp, bool rqs, int64_t tiles, int grid, hipStream_t st,
-                  bool dry);
-int flow_mh_b_slr_rqs(const NfmcFlowMhArgs& a, int cpl, int lpc, int hp, int64_t tiles, int grid, hipStream_t st, bool dry);
-
-// one launch of the general (diagnostics compiled in, default stream) register kernel of potential POT
-template <template <int, int, bool> class POT, int CPL, int LPC, int HP, int NB>
-int launch_b_general(const NfmcFlowMhArgs& a, int64_t tiles, int grid, hipStream_t st, bool dry) {
-    const size_t img =
-        (size_t)FlowImage<CPL, LPC, HP, false, NB>::total_floats(a.flow.n_hidden_layers, a.flow.n_coupling) * sizeof(float);
-    const size_t lds = lds_with_potential(img, a.pot, CPL * LPC);
-    if (lds > 120 * 1024 || rng_rounds(a.rng) != 10) return NFMC_EUNSUPPORTED;
-    if (dry) return 0;
-    auto kern = flow_mh_b_kernel<CPL, LPC, HP, POT, false, true, 10, NB>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
+// The own_units kinds (kPotKinds): class POT at layout c, conditioner bucket hp (4 / 8), affine (NB = 0) or spline
+// (NB = kRqsBins) couplings; one general kernel (diagnostics compiled in, default stream) per layout and width.  The
+// arguments and NFMC_EUNSUPPORTED / dry as in flow_mh_b_launch.  Never exact-fit or dual: their parameters are tables.
+// flow_b_{fullrank,rosenbrock,sv,slr}{,_rqs}.hip instantiate it explicitly.
+template <template <int, int, bool> class POT, int NB>
+int launch_b_kind(const NfmcFlowMhArgs& a, BCfg c, int hp, int64_t tiles, int grid, hipStream_t st, bool dry) {
+    if (rng_rounds(a.rng) != 10) return NFMC_EUNSUPPORTED;
+#define NFMC_AT(HP, CPL, LPC)                                                                                          \
+    if (hp == HP && c.cpl == CPL && c.lpc == LPC) {                                                                    \
+        const size_t img = (size_t)FlowImage<CPL, LPC, HP, false, NB>::total_floats(a.flow.n_hidden_layers, a.flow.n_coupling) * \
+                           sizeof(float);                                                                              \
+        const size_t lds = lds_with_potential(img, a.pot, CPL * LPC);                                                  \
+        if (lds > 120 * 1024) return NFMC_EUNSUPPORTED;                                                                \
+        return dry ? NFMC_OK : launch_lds(flow_mh_b_kernel<CPL, LPC, HP, POT, false, true, 10, NB>, grid, kBlock, lds, st, a, tiles); \
     }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, a, tiles);
-    return 0;
+#define M4(CPL, LPC) NFMC_AT(4, CPL, LPC)
+#define M8(CPL, LPC) NFMC_AT(8, CPL, LPC)
+    NFMC_FOR_FLOWB_CFG(M4) NFMC_FOR_FLOWB_CFG(M8)
+#undef NFMC_AT
+#undef M4
+#undef M8
+    return NFMC_EUNSUPPORTED;
 }
+// the dispatching unit (flow_b_kernels.hip) does not instantiate them, and so none of their kernels, itself
+#define NFMC_EXTERN_KIND(KIND, POT)                                                                                  \
+    static_assert(kPotKinds[KIND].own_units, #POT);                                                                  \
+    extern template int launch_b_kind<POT, 0>(const NfmcFlowMhArgs&, BCfg, int, int64_t, int, hipStream_t, bool);    \
+    extern template int launch_b_kind<POT, kRqsBins>(const NfmcFlowMhArgs&, BCfg, int, int64_t, int, hipStream_t, bool);
+NFMC_FOR_OWN_UNIT_POT(NFMC_EXTERN_KIND)
+#undef NFMC_EXTERN_KIND
 
 }  // namespace nfmc

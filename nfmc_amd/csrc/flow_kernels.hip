@@ -376,30 +376,16 @@ extern "C" int nfmc_realnvp_inverse_f32(const NfmcRealNVP* flow, const float* z,
     return NFMC_OK;
 }
 
-// potential kinds only the register-layout kernels (flow_b_kernels.hip, flow_b_fullrank*.hip, flow_b_rosenbrock*.hip,
-// flow_b_sv*.hip, flow_b_slr*.hip) evaluate
-static bool register_kernels_only(const NfmcPotential& p) {
-    return p.kind == NFMC_POT_GAUSSIAN_MIXTURE || p.kind == NFMC_POT_LOGISTIC_REGRESSION || p.kind == NFMC_POT_GAUSSIAN_FULL ||
-           p.kind == NFMC_POT_ROSENBROCK || p.kind == NFMC_POT_STOCHASTIC_VOLATILITY ||
-           p.kind == NFMC_POT_SPARSE_LOGISTIC_REGRESSION;
-}
+// the potential kinds only the register-layout kernels (flow_b_kernels.hip and the own_units kinds' flow_b_*.hip)
+// evaluate: register_only in kPotKinds (common.hpp).  After check_flow_mh, so the kind has a row.
+static bool register_kernels_only(const NfmcPotential& p) { return pot_kind(p.kind)->register_only; }
 
 static int check_flow_mh(const NfmcFlowMhArgs& a) {
     int rc = check_flow(&a.flow);
     if (rc) return rc;
     if (!a.x || !a.logq || a.n <= 0 || a.n_steps <= 0) return NFMC_EINVAL;
     if (a.n_steps > NFMC_MAX_STEPS_PER_CALL) return NFMC_ESHAPE;
-    if (a.pot.kind != NFMC_POT_QUADRATIC && a.pot.kind != NFMC_POT_FUNNEL && a.pot.kind != NFMC_POT_GAUSSIAN_MIXTURE &&
-        a.pot.kind != NFMC_POT_LOGISTIC_REGRESSION && a.pot.kind != NFMC_POT_GAUSSIAN_FULL &&
-        a.pot.kind != NFMC_POT_ROSENBROCK && a.pot.kind != NFMC_POT_STOCHASTIC_VOLATILITY &&
-        a.pot.kind != NFMC_POT_SPARSE_LOGISTIC_REGRESSION)
-        return NFMC_EUNSUPPORTED;
-    if (int rc = check_mixture(a.pot)) return rc;
-    if (int rc = check_logreg(a.pot)) return rc;
-    if (int rc = check_fullrank(a.pot, a.flow.d)) return rc;
-    if (int rc = check_rosenbrock(a.pot, a.flow.d)) return rc;
-    if (int rc = check_sv(a.pot, a.flow.d)) return rc;
-    if (int rc = check_slr(a.pot, a.flow.d)) return rc;
+    if ((rc = check_potential(a.pot, a.flow.d, PotFamily::kRegister))) return rc;
     if (a.stats.sum_x && (!a.stats.sum_x2 || !a.stats.counters || !a.stats.scratch)) return NFMC_EINVAL;
     if (a.adjusted && (a.rng.replay_normals != nullptr) != (a.rng.replay_uniforms != nullptr)) return NFMC_EINVAL;
     if (!store_ok(a.samples) || !rng_rounds_ok(a.rng, true)) return NFMC_EINVAL;
@@ -417,9 +403,7 @@ extern "C" int nfmc_flow_mh_supported_f32(const NfmcFlowMhArgs* args) {
     rc = getenv("NFMC_FLOW_TILE_PATH") ? NFMC_EUNSUPPORTED : flow_mh_b_launch(a, nullptr, &grid, &dp, true);
     if (rc != NFMC_EUNSUPPORTED) return rc;
     if (rng_rounds(a.rng) != 10) return NFMC_EUNSUPPORTED;   // the opt-in stream exists in the register kernels only
-    // the mixture, the logistic regression, the full-rank Gaussian, the Rosenbrock, the stochastic-volatility and the
-    // sparse logistic-regression targets exist in the register kernels only: the matrix-core and one-chain-per-lane kernels below evaluate quadratic and funnel targets and
-    // nothing else
+    // the matrix-core and one-chain-per-lane kernels below evaluate quadratic and funnel targets and nothing else
     if (register_kernels_only(a.pot)) return NFMC_EUNSUPPORTED;
     if (use_mfma_flow(&a.flow) && al16(a.x) && al16(a.samples.base)) return NFMC_OK;
     // wide conditioners at the streamed matrix-core shapes (mfma_wide.hip): the caller composes the step from the flow's

@@ -31,14 +31,7 @@ extern "C" int nfmc_neutra_potential_grad_f32(const NfmcRealNVP* flow, const Nfm
     int rc = check_flow_neutra(flow);
     if (rc) return rc;
     if (!pot || !z || n <= 0) return NFMC_EINVAL;
-    if (pot->kind != NFMC_POT_QUADRATIC && pot->kind != NFMC_POT_FUNNEL && pot->kind != NFMC_POT_GAUSSIAN_FULL &&
-        pot->kind != NFMC_POT_ROSENBROCK && pot->kind != NFMC_POT_STOCHASTIC_VOLATILITY &&
-        pot->kind != NFMC_POT_SPARSE_LOGISTIC_REGRESSION)
-        return NFMC_EUNSUPPORTED;
-    if ((rc = check_fullrank(*pot, flow->d))) return rc;
-    if ((rc = check_rosenbrock(*pot, flow->d))) return rc;
-    if ((rc = check_sv(*pot, flow->d))) return rc;
-    if ((rc = check_slr(*pot, flow->d))) return rc;
+    if ((rc = check_potential(*pot, flow->d, PotFamily::kNeutraValu))) return rc;
     const int rpw = neutra_rows_per_wave(flow->d, 3);
     if (!rpw) return NFMC_ESHAPE;
     const int64_t tiles = (n + rpw - 1) / rpw;
@@ -60,7 +53,7 @@ extern "C" int nfmc_neutra_hmc_steps_f32(const NfmcNeutraHmcArgs* args, nfmc_str
     if (a.flow.n_hidden > 32 && a.flow.n_bins == 0) {
         if (!a.z || a.n <= 0 || a.n_steps <= 0 || a.n_leapfrog <= 0 || !(a.step_size > 0.f)) return NFMC_EINVAL;
         if (a.n_steps > NFMC_MAX_STEPS_PER_CALL) return NFMC_ESHAPE;
-        // the matrix-core kernels evaluate quadratic and funnel targets only (kinds 4 to 7: conditioners of at most 32)
+        // the matrix-core kernels evaluate quadratic and funnel targets only (the other neutra_valu kinds: conditioners of at most 32)
         if (a.pot.kind != NFMC_POT_QUADRATIC && a.pot.kind != NFMC_POT_FUNNEL) return NFMC_EUNSUPPORTED;
         if (a.stats.sum_x && (!a.stats.sum_x2 || !a.stats.counters || !a.stats.scratch)) return NFMC_EINVAL;
         if (a.adjust && (a.rng.replay_normals != nullptr) != (a.rng.replay_uniforms != nullptr)) return NFMC_EINVAL;
@@ -71,14 +64,7 @@ extern "C" int nfmc_neutra_hmc_steps_f32(const NfmcNeutraHmcArgs* args, nfmc_str
     if (rc) return rc;
     if (!a.z || a.n <= 0 || a.n_steps <= 0 || a.n_leapfrog <= 0 || !(a.step_size > 0.f)) return NFMC_EINVAL;
     if (a.n_steps > NFMC_MAX_STEPS_PER_CALL) return NFMC_ESHAPE;
-    if (a.pot.kind != NFMC_POT_QUADRATIC && a.pot.kind != NFMC_POT_FUNNEL && a.pot.kind != NFMC_POT_GAUSSIAN_FULL &&
-        a.pot.kind != NFMC_POT_ROSENBROCK && a.pot.kind != NFMC_POT_STOCHASTIC_VOLATILITY &&
-        a.pot.kind != NFMC_POT_SPARSE_LOGISTIC_REGRESSION)
-        return NFMC_EUNSUPPORTED;
-    if ((rc = check_fullrank(a.pot, a.flow.d))) return rc;
-    if ((rc = check_rosenbrock(a.pot, a.flow.d))) return rc;
-    if ((rc = check_sv(a.pot, a.flow.d))) return rc;
-    if ((rc = check_slr(a.pot, a.flow.d))) return rc;
+    if ((rc = check_potential(a.pot, a.flow.d, PotFamily::kNeutraValu))) return rc;
     if (a.stats.sum_x && (!a.stats.sum_x2 || !a.stats.counters || !a.stats.scratch)) return NFMC_EINVAL;
     if (a.adjust && (a.rng.replay_normals != nullptr) != (a.rng.replay_uniforms != nullptr)) return NFMC_EINVAL;
     if (!store_ok(a.samples)) return NFMC_EINVAL;

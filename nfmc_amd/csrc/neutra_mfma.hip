@@ -502,11 +502,7 @@ static int launch_grad(const NfmcRealNVP& f, const NfmcPotential& pot, const flo
                        hipStream_t st) {
     const int64_t tiles = (n + kMfmaChains - 1) / kMfmaChains;
     const int grid = (int)(tiles < kMaxGrid ? tiles : kMaxGrid);
-    auto kern = neutra_grad_mfma_kernel<TD, TH, NHL>;
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMfmaLdsBytes);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kMfmaBlock), kMfmaLdsBytes, st, f, pot, z, n, u, g, tiles);
-    return 0;
+    return launch_lds(neutra_grad_mfma_kernel<TD, TH, NHL>, grid, kMfmaBlock, kMfmaLdsBytes, st, f, pot, z, n, u, g, tiles);
 }
 
 template <int TD, int TH, int NHL>

@@ -6,7 +6,7 @@ int launch_hmc_j8(const NfmcHmcArgs& a, const JumpDev& jd, Cfg c, bool fast, int
     int rc = NFMC_EUNSUPPORTED;
 #define M(CPL, LPC) \
     if (c.cpl == CPL && c.lpc == LPC) rc = launch_hmc_cfg<CPL, LPC, 8>(a, jd, fast, tiles, grid, st);
-    NFMC_FOR_BCFG(M)
+    NFMC_FOR_JUMP_CFG(M)
 #undef M
     return rc;
 }

@@ -267,11 +267,7 @@ __global__ void __launch_bounds__(kBlock, NFMC_WPE) mala_kernel(NfmcMalaArgs a, 
     for (int i = 0; i < CPL; ++i) sx[i] = sxx[i] = 0.f;
     StatShift<CPL, LPC, TUNE> shift;
     uint32_t n_acc = 0, n_bad = 0, j_acc = 0, j_bad = 0;
-    const unsigned long long leaders = LPC == 64 ? 1ull : (LPC == 32 ? 0x0000000100000001ull
-                                       : LPC == 16 ? 0x0001000100010001ull
-                                       : LPC == 8 ? 0x0101010101010101ull
-                                       : LPC == 4 ? 0x1111111111111111ull
-                                       : LPC == 2 ? 0x5555555555555555ull : ~0ull);
+    constexpr unsigned long long leaders = group_leaders(LPC);
 
     for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const int64_t row = (tile * kWavesPerBlock + wave) * CPW + cw;
@@ -428,11 +424,7 @@ __global__ void __launch_bounds__(kBlock, NFMC_WPE) hmc_kernel(NfmcHmcArgs a, in
     for (int i = 0; i < CPL; ++i) sx[i] = sxx[i] = 0.f;
     StatShift<CPL, LPC, TUNE> shift;
     uint32_t n_acc = 0, n_bad = 0, j_acc = 0, j_bad = 0;
-    const unsigned long long leaders = LPC == 64 ? 1ull : (LPC == 32 ? 0x0000000100000001ull
-                                       : LPC == 16 ? 0x0001000100010001ull
-                                       : LPC == 8 ? 0x0101010101010101ull
-                                       : LPC == 4 ? 0x1111111111111111ull
-                                       : LPC == 2 ? 0x5555555555555555ull : ~0ull);
+    constexpr unsigned long long leaders = group_leaders(LPC);
 
     for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const int64_t row = (tile * kWavesPerBlock + wave) * CPW + cw;
@@ -558,10 +550,15 @@ struct Cfg {
 
 // The layouts choose_cfg picks without the NFMC_SAMPLER_CFG override: the smallest capacity CPL * LPC >= d, at equal
 // capacity the first in kCfgs.  (4, 16), (16, 4), (16, 8), (16, 16) and (16, 32) tie with an earlier layout and are
-// reachable only through the override; LogRegPot, GaussFullPot, RosenbrockPot, SVPot and SparseLogRegPot are not
-// instantiated there (the override skips them for kinds 3 to 7).
+// reachable only through the override, which skips them for the kinds whose row in kPotKinds says default_cfg_only:
+// their classes are not instantiated there.
 constexpr bool is_default_cfg(int cpl, int lpc) {
     return !((cpl == 4 && lpc == 16) || (cpl == 16 && lpc != 64));
+}
+// whether sampler_{mala,hmc}_j*.hip hold kernels of `kind` at this layout and jump-tail width
+template <int CPL, int LPC, int JHP>
+constexpr bool cfg_instantiated(int kind) {
+    return !pot_kind(kind)->own_units && (JHP > 0 || is_default_cfg(CPL, LPC) || !pot_kind(kind)->default_cfg_only);
 }
 
 // dynamic LDS of a launch: the jump tail's flow image, then the potential's block (the mixture's parameters / the tile
@@ -581,12 +578,7 @@ int launch_mala_kernel(const NfmcMalaArgs& a, const JumpDev& jd, size_t lds, int
     if constexpr (JHP == 0 && !F) {
         if (a.tune.state) kern = mala_kernel<CPL, LPC, POT, F, JHP, 10, false, true>;
     }
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, a, sqrt2h, tiles, jd);
-    return NFMC_OK;
+    return launch_lds(kern, grid, kBlock, lds, st, a, sqrt2h, tiles, jd);
 }
 
 template <int CPL, int LPC, template <int, int, bool> class POT, bool F, int JHP>
@@ -595,26 +587,18 @@ int launch_hmc_kernel(const NfmcHmcArgs& a, const JumpDev& jd, size_t lds, int64
     if constexpr (JHP == 0 && !F) {
         if (a.tune.state) kern = hmc_kernel<CPL, LPC, POT, F, JHP, 10, true>;
     }
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, a, tiles, jd);
-    return NFMC_OK;
+    return launch_lds(kern, grid, kBlock, lds, st, a, tiles, jd);
 }
 
+// kinds 0 to 3 at one layout and jump-tail width (launch_{mala,hmc}_j*): the class, and FAST where it has such kernels
 template <int CPL, int LPC, int JHP>
 int launch_mala_cfg(const NfmcMalaArgs& a, const JumpDev& jd, bool fast, int64_t tiles, int grid, float sqrt2h,
                     hipStream_t st) {
     const size_t lds = sampler_lds<CPL, LPC, JHP>(a.pot, jd);
-    if (lds > 120 * 1024) return NFMC_EUNSUPPORTED;
+    if (lds > 120 * 1024 || !cfg_instantiated<CPL, LPC, JHP>(a.pot.kind)) return NFMC_EUNSUPPORTED;
     // no per-step output and no replay: the FAST quadratic kernels without a jump tail have a LEAN instantiation
     const bool lean = !a.masks_out && !a.log_ratio_out && !a.samples.base && !a.rng.replay_normals && !a.rng.replay_uniforms;
-#define NFMC_L(POT, F)                                                                                            \
-    {                                                                                                             \
-        const int rc_ = launch_mala_kernel<CPL, LPC, POT, F, JHP>(a, jd, lds, tiles, grid, sqrt2h, st);           \
-        if (rc_) return rc_;                                                                                      \
-    }
+#define NFMC_L(POT, F) return launch_mala_kernel<CPL, LPC, POT, F, JHP>(a, jd, lds, tiles, grid, sqrt2h, st);
     if (rng_rounds(a.rng) == 7) {   // opt-in Philox4x32-7 stream: the exact-fit quadratic kernel without a jump tail
         if constexpr (JHP == 0) {
             if (fast && a.pot.kind == NFMC_POT_QUADRATIC) {
@@ -629,14 +613,7 @@ int launch_mala_cfg(const NfmcMalaArgs& a, const JumpDev& jd, bool fast, int64_t
     if (a.pot.kind == NFMC_POT_GAUSSIAN_MIXTURE) {   // never exact-fit: a and b are tables
         NFMC_L(MixturePot, false)
     } else if (a.pot.kind == NFMC_POT_LOGISTIC_REGRESSION) {
-        if constexpr (JHP > 0 || is_default_cfg(CPL, LPC)) {
-            NFMC_L(LogRegPot, false)
-        } else {
-            return NFMC_EUNSUPPORTED;   // not reached: choose_cfg never picks this layout for kind 3
-        }
-    } else if (a.pot.kind == NFMC_POT_GAUSSIAN_FULL || a.pot.kind == NFMC_POT_ROSENBROCK ||
-               a.pot.kind == NFMC_POT_STOCHASTIC_VOLATILITY || a.pot.kind == NFMC_POT_SPARSE_LOGISTIC_REGRESSION) {
-        return NFMC_EUNSUPPORTED;   // not reached: kinds 4 to 7 launch from sampler_{fullrank,rosenbrock,sv,slr}_*.hip
+        if constexpr (cfg_instantiated<CPL, LPC, JHP>(NFMC_POT_LOGISTIC_REGRESSION)) NFMC_L(LogRegPot, false)
     } else if (a.pot.kind == NFMC_POT_FUNNEL) {
         if (fast) NFMC_L(FunnelPot, true) else NFMC_L(FunnelPot, false)
     } else {
@@ -650,18 +627,14 @@ int launch_mala_cfg(const NfmcMalaArgs& a, const JumpDev& jd, bool fast, int64_t
         if (fast) NFMC_L(QuadraticPot, true) else NFMC_L(QuadraticPot, false)
     }
 #undef NFMC_L
-    return NFMC_OK;
+    return NFMC_EUNSUPPORTED;
 }
 
 template <int CPL, int LPC, int JHP>
 int launch_hmc_cfg(const NfmcHmcArgs& a, const JumpDev& jd, bool fast, int64_t tiles, int grid, hipStream_t st) {
     const size_t lds = sampler_lds<CPL, LPC, JHP>(a.pot, jd);
-    if (lds > 120 * 1024) return NFMC_EUNSUPPORTED;
-#define NFMC_L(POT, F)                                                                                            \
-    {                                                                                                             \
-        const int rc_ = launch_hmc_kernel<CPL, LPC, POT, F, JHP>(a, jd, lds, tiles, grid, st);                    \
-        if (rc_) return rc_;                                                                                      \
-    }
+    if (lds > 120 * 1024 || !cfg_instantiated<CPL, LPC, JHP>(a.pot.kind)) return NFMC_EUNSUPPORTED;
+#define NFMC_L(POT, F) return launch_hmc_kernel<CPL, LPC, POT, F, JHP>(a, jd, lds, tiles, grid, st);
     if (rng_rounds(a.rng) == 7) {
         if constexpr (JHP == 0) {
             if (fast && a.pot.kind == NFMC_POT_QUADRATIC) {
@@ -675,66 +648,77 @@ int launch_hmc_cfg(const NfmcHmcArgs& a, const JumpDev& jd, bool fast, int64_t t
     if (a.pot.kind == NFMC_POT_GAUSSIAN_MIXTURE) {   // never exact-fit: a and b are tables
         NFMC_L(MixturePot, false)
     } else if (a.pot.kind == NFMC_POT_LOGISTIC_REGRESSION) {
-        if constexpr (JHP > 0 || is_default_cfg(CPL, LPC)) {
-            NFMC_L(LogRegPot, false)
-        } else {
-            return NFMC_EUNSUPPORTED;   // not reached: choose_cfg never picks this layout for kind 3
-        }
-    } else if (a.pot.kind == NFMC_POT_GAUSSIAN_FULL || a.pot.kind == NFMC_POT_ROSENBROCK ||
-               a.pot.kind == NFMC_POT_STOCHASTIC_VOLATILITY || a.pot.kind == NFMC_POT_SPARSE_LOGISTIC_REGRESSION) {
-        return NFMC_EUNSUPPORTED;   // not reached: kinds 4 to 7 launch from sampler_{fullrank,rosenbrock,sv,slr}_*.hip
+        if constexpr (cfg_instantiated<CPL, LPC, JHP>(NFMC_POT_LOGISTIC_REGRESSION)) NFMC_L(LogRegPot, false)
     } else if (a.pot.kind == NFMC_POT_FUNNEL) {
         if (fast) NFMC_L(FunnelPot, true) else NFMC_L(FunnelPot, false)
     } else {
         if (fast) NFMC_L(QuadraticPot, true) else NFMC_L(QuadraticPot, false)
     }
 #undef NFMC_L
-    return NFMC_OK;
+    return NFMC_EUNSUPPORTED;
 }
 
-// kinds 4 (GaussFullPot), 5 (RosenbrockPot), 6 (SVPot) and 7 (SparseLogRegPot): translation units of their own
-// (sampler_fullrank_*.hip, sampler_rosenbrock_*.hip, sampler_sv_*.hip, sampler_slr_*.hip), the layouts kind 3 gets,
-// general kernels on the default Philox4x32-10 stream only
-template <template <int, int, bool> class POT, int CPL, int LPC, int JHP>
-int launch_mala_general_cfg(const NfmcMalaArgs& a, const JumpDev& jd, int64_t tiles, int grid, float sqrt2h,
-                            hipStream_t st) {
-    const size_t lds = sampler_lds<CPL, LPC, JHP>(a.pot, jd);
-    if (lds > 120 * 1024 || rng_rounds(a.rng) != 10) return NFMC_EUNSUPPORTED;
-    return launch_mala_kernel<CPL, LPC, POT, false, JHP>(a, jd, lds, tiles, grid, sqrt2h, st);
-}
-template <template <int, int, bool> class POT, int CPL, int LPC, int JHP>
-int launch_hmc_general_cfg(const NfmcHmcArgs& a, const JumpDev& jd, int64_t tiles, int grid, hipStream_t st) {
-    const size_t lds = sampler_lds<CPL, LPC, JHP>(a.pot, jd);
-    if (lds > 120 * 1024 || rng_rounds(a.rng) != 10) return NFMC_EUNSUPPORTED;
-    return launch_hmc_kernel<CPL, LPC, POT, false, JHP>(a, jd, lds, tiles, grid, st);
-}
-
-// all sampler layouts (JHP == 0) / the layouts shared with flow_b (JHP > 0)
+// all sampler layouts (kCfgs, sampler_kernels.hip)
 #define NFMC_FOR_CFG(M)                                                                                             \
     M(4, 1) M(4, 2) M(4, 4) M(4, 8) M(4, 16) M(8, 8) M(16, 4) M(8, 16) M(16, 8) M(8, 32) M(16, 16) M(8, 64) M(16, 32) \
         M(16, 64)
-#define NFMC_FOR_BCFG(M) M(4, 1) M(4, 2) M(4, 4) M(4, 8) M(8, 8) M(8, 16) M(8, 32) M(8, 64)
 // the layouts choose_cfg picks by default (is_default_cfg) among NFMC_FOR_CFG
 #define NFMC_FOR_DEFAULT_CFG(M) M(4, 1) M(4, 2) M(4, 4) M(4, 8) M(8, 8) M(8, 16) M(8, 32) M(8, 64) M(16, 64)
+// the samplers' jump-tail layouts (JHP > 0), in choose_cfg's order of preference: kJumpCfgs is this list
+#define NFMC_FOR_JUMP_CFG(M) M(4, 1) M(4, 2) M(4, 4) M(4, 8) M(8, 8) M(8, 16) M(8, 32) M(8, 64)
+#define NFMC_CFG_ENTRY(CPL, LPC) {CPL, LPC},
+constexpr Cfg kJumpCfgs[] = {NFMC_FOR_JUMP_CFG(NFMC_CFG_ENTRY)};
 
-// defined in sampler_mala_j*.hip / sampler_hmc_j*.hip
+// The own_units kinds (kPotKinds): every layout and jump-tail width of one class in a translation unit of its own
+// (sampler_{fullrank,rosenbrock,sv,slr}_{mala,hmc}.hip instantiate these explicitly), the layouts kind 3 gets, general
+// kernels on the default Philox4x32-10 stream only
+template <template <int, int, bool> class POT>
+int launch_mala_kind(const NfmcMalaArgs& a, const JumpDev& jd, Cfg c, int jhp, int64_t tiles, int grid, float sqrt2h,
+                     hipStream_t st) {
+    if (rng_rounds(a.rng) != 10) return NFMC_EUNSUPPORTED;
+#define NFMC_AT(JHP, CPL, LPC)                                                       \
+    if (jhp == JHP && c.cpl == CPL && c.lpc == LPC) {                                \
+        const size_t lds = sampler_lds<CPL, LPC, JHP>(a.pot, jd);                    \
+        if (lds > 120 * 1024) return NFMC_EUNSUPPORTED;                              \
+        return launch_mala_kernel<CPL, LPC, POT, false, JHP>(a, jd, lds, tiles, grid, sqrt2h, st); \
+    }
+#define M0(CPL, LPC) NFMC_AT(0, CPL, LPC)
+#define M4(CPL, LPC) NFMC_AT(4, CPL, LPC)
+#define M8(CPL, LPC) NFMC_AT(8, CPL, LPC)
+    NFMC_FOR_DEFAULT_CFG(M0) NFMC_FOR_JUMP_CFG(M4) NFMC_FOR_JUMP_CFG(M8)
+#undef NFMC_AT
+    return NFMC_EUNSUPPORTED;
+}
+template <template <int, int, bool> class POT>
+int launch_hmc_kind(const NfmcHmcArgs& a, const JumpDev& jd, Cfg c, int jhp, int64_t tiles, int grid, hipStream_t st) {
+    if (rng_rounds(a.rng) != 10) return NFMC_EUNSUPPORTED;
+#define NFMC_AT(JHP, CPL, LPC)                                                       \
+    if (jhp == JHP && c.cpl == CPL && c.lpc == LPC) {                                \
+        const size_t lds = sampler_lds<CPL, LPC, JHP>(a.pot, jd);                    \
+        if (lds > 120 * 1024) return NFMC_EUNSUPPORTED;                              \
+        return launch_hmc_kernel<CPL, LPC, POT, false, JHP>(a, jd, lds, tiles, grid, st); \
+    }
+    NFMC_FOR_DEFAULT_CFG(M0) NFMC_FOR_JUMP_CFG(M4) NFMC_FOR_JUMP_CFG(M8)
+#undef NFMC_AT
+#undef M0
+#undef M4
+#undef M8
+    return NFMC_EUNSUPPORTED;
+}
+// the dispatching unit (sampler_kernels.hip) does not instantiate them, and so none of their kernels, itself
+#define NFMC_EXTERN_KIND(KIND, POT)                                                                                       \
+    static_assert(kPotKinds[KIND].own_units, #POT);                                                                       \
+    extern template int launch_mala_kind<POT>(const NfmcMalaArgs&, const JumpDev&, Cfg, int, int64_t, int, float, hipStream_t); \
+    extern template int launch_hmc_kind<POT>(const NfmcHmcArgs&, const JumpDev&, Cfg, int, int64_t, int, hipStream_t);
+NFMC_FOR_OWN_UNIT_POT(NFMC_EXTERN_KIND)
+#undef NFMC_EXTERN_KIND
+
+// defined in sampler_mala_j*.hip / sampler_hmc_j*.hip: kinds 0 to 3
 int launch_mala_j0(const NfmcMalaArgs&, const JumpDev&, Cfg, bool, int64_t, int, float, hipStream_t);
 int launch_mala_j4(const NfmcMalaArgs&, const JumpDev&, Cfg, bool, int64_t, int, float, hipStream_t);
 int launch_mala_j8(const NfmcMalaArgs&, const JumpDev&, Cfg, bool, int64_t, int, float, hipStream_t);
 int launch_hmc_j0(const NfmcHmcArgs&, const JumpDev&, Cfg, bool, int64_t, int, hipStream_t);
 int launch_hmc_j4(const NfmcHmcArgs&, const JumpDev&, Cfg, bool, int64_t, int, hipStream_t);
 int launch_hmc_j8(const NfmcHmcArgs&, const JumpDev&, Cfg, bool, int64_t, int, hipStream_t);
-// defined in sampler_fullrank_mala.hip / sampler_fullrank_hmc.hip: kind 4 at layout c, jump-tail width jhp (0, 4, 8)
-int launch_mala_fullrank(const NfmcMalaArgs&, const JumpDev&, Cfg, int, int64_t, int, float, hipStream_t);
-int launch_hmc_fullrank(const NfmcHmcArgs&, const JumpDev&, Cfg, int, int64_t, int, hipStream_t);
-// defined in sampler_rosenbrock_mala.hip / sampler_rosenbrock_hmc.hip: kind 5, the same arguments
-int launch_mala_rosenbrock(const NfmcMalaArgs&, const JumpDev&, Cfg, int, int64_t, int, float, hipStream_t);
-int launch_hmc_rosenbrock(const NfmcHmcArgs&, const JumpDev&, Cfg, int, int64_t, int, hipStream_t);
-// defined in sampler_sv_mala.hip / sampler_sv_hmc.hip: kind 6, the same arguments
-int launch_mala_sv(const NfmcMalaArgs&, const JumpDev&, Cfg, int, int64_t, int, float, hipStream_t);
-int launch_hmc_sv(const NfmcHmcArgs&, const JumpDev&, Cfg, int, int64_t, int, hipStream_t);
-// defined in sampler_slr_mala.hip / sampler_slr_hmc.hip: kind 7, the same arguments
-int launch_mala_slr(const NfmcMalaArgs&, const JumpDev&, Cfg, int, int64_t, int, float, hipStream_t);
-int launch_hmc_slr(const NfmcHmcArgs&, const JumpDev&, Cfg, int, int64_t, int, hipStream_t);
 
 }  // namespace nfmc

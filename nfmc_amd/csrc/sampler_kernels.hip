@@ -1,7 +1,7 @@
 // K1/K2 (+K6, K7): C entry points of the fused Langevin / HMC samplers.  Kernels: sampler_impl.hpp; the
 // template instantiations live in sampler_{mala,hmc}_j{0,4,8}.hip (j = conditioner width of the optional
-// jump tail, 0 = none) and, for the full-rank Gaussian, the Rosenbrock and the stochastic-volatility targets,
-// sampler_{fullrank,rosenbrock,sv}_{mala,hmc}.hip, so they compile in parallel.
+// jump tail, 0 = none) and, for the kinds whose row in kPotKinds (common.hpp) says own_units, in a mala and an hmc
+// unit per kind, so they compile in parallel.
 #include "sampler_impl.hpp"
 
 namespace nfmc {
@@ -9,28 +9,21 @@ namespace nfmc {
 // (CPL, LPC) layouts, ordered by capacity CPL*LPC; equal capacities in order of measured preference
 // (CPL = 8 keeps 4 waves/SIMD resident).
 static const Cfg kCfgs[] = {{4, 1}, {4, 2}, {4, 4}, {4, 8}, {8, 8}, {4, 16}, {16, 4}, {8, 16}, {16, 8}, {8, 32}, {16, 16}, {8, 64}, {16, 32}, {16, 64}};
-static const Cfg kBCfgs[] = {{4, 1}, {4, 2}, {4, 4}, {4, 8}, {8, 8}, {8, 16}, {8, 32}, {8, 64}};  // jump-tail variants
 
-// default_only: the override may name only layouts the default choice picks (the potentials with no instantiation at
-// the other layouts, is_default_cfg)
-static Cfg choose_cfg(int d, bool with_jump, bool default_only = false) {
-    if (const char* e = getenv("NFMC_SAMPLER_CFG")) {  // "cpl,lpc" override (tuning)
-        int c = 0, l = 0;
-        if (sscanf(e, "%d,%d", &c, &l) == 2) {
-            const Cfg* list = with_jump ? kBCfgs : kCfgs;
-            const int len = with_jump ? (int)(sizeof(kBCfgs) / sizeof(Cfg)) : (int)(sizeof(kCfgs) / sizeof(Cfg));
-            for (int i = 0; i < len; ++i)
-                if (list[i].cpl == c && list[i].lpc == l && c * l >= d && (!default_only || is_default_cfg(c, l)))
-                    return list[i];
-        }
-    }
+// with_jump: among the jump-tail layouts (kJumpCfgs, sampler_impl.hpp).  default_only: the override may name only
+// layouts the default choice picks (the kinds with no instantiation at the other layouts: default_cfg_only in kPotKinds)
+static Cfg choose_cfg(int d, bool with_jump, bool default_only) {
+    const Cfg* list = with_jump ? kJumpCfgs : kCfgs;
+    const int len = with_jump ? (int)(sizeof(kJumpCfgs) / sizeof(Cfg)) : (int)(sizeof(kCfgs) / sizeof(Cfg));
+    int c = 0, l = 0;
+    const char* e = getenv("NFMC_SAMPLER_CFG");   // "cpl,lpc" override (tuning)
+    const bool named = e && sscanf(e, "%d,%d", &c, &l) == 2 && (!default_only || is_default_cfg(c, l));
     Cfg best = {0, 0};
-    if (with_jump) {
-        for (const Cfg& k : kBCfgs)
-            if (k.cpl * k.lpc >= d && (best.cpl == 0 || k.cpl * k.lpc < best.cpl * best.lpc)) best = k;
-    } else {
-        for (const Cfg& k : kCfgs)
-            if (k.cpl * k.lpc >= d && (best.cpl == 0 || k.cpl * k.lpc < best.cpl * best.lpc)) best = k;
+    for (int i = 0; i < len; ++i) {
+        const Cfg& k = list[i];
+        if (k.cpl * k.lpc < d) continue;
+        if (named && k.cpl == c && k.lpc == l) return k;
+        if (best.cpl == 0 || k.cpl * k.lpc < best.cpl * best.lpc) best = k;
     }
     return best;
 }
@@ -44,17 +37,7 @@ static int check_common(const Args* a) {
     if (a->n_steps > NFMC_MAX_STEPS_PER_CALL) return NFMC_ESHAPE;
     if (a->d > 1024) return NFMC_ESHAPE;
     if (!(a->step_size > 0.f)) return NFMC_EINVAL;
-    if (a->pot.kind != NFMC_POT_QUADRATIC && a->pot.kind != NFMC_POT_FUNNEL && a->pot.kind != NFMC_POT_GAUSSIAN_MIXTURE &&
-        a->pot.kind != NFMC_POT_LOGISTIC_REGRESSION && a->pot.kind != NFMC_POT_GAUSSIAN_FULL &&
-        a->pot.kind != NFMC_POT_ROSENBROCK && a->pot.kind != NFMC_POT_STOCHASTIC_VOLATILITY &&
-        a->pot.kind != NFMC_POT_SPARSE_LOGISTIC_REGRESSION)
-        return NFMC_EUNSUPPORTED;
-    if (int rc = check_mixture(a->pot)) return rc;
-    if (int rc = check_logreg(a->pot)) return rc;
-    if (int rc = check_fullrank(a->pot, a->d)) return rc;
-    if (int rc = check_rosenbrock(a->pot, a->d)) return rc;
-    if (int rc = check_sv(a->pot, a->d)) return rc;
-    if (int rc = check_slr(a->pot, a->d)) return rc;
+    if (int rc = check_potential(a->pot, a->d, PotFamily::kRegister)) return rc;
     if (((uintptr_t)a->x & 3u) != 0) return NFMC_EALIGN;
     if (!store_ok(a->samples)) return NFMC_EINVAL;
     if (!rng_rounds_ok(a->rng, true)) return NFMC_EINVAL;
@@ -270,33 +253,27 @@ static int check_tune(const Args& a, int dp) {
     return NFMC_OK;
 }
 
-// the potentials instantiated at the default layouts only (is_default_cfg)
-static bool default_cfg_only(const NfmcPotential& p) {
-    return p.kind == NFMC_POT_LOGISTIC_REGRESSION || p.kind == NFMC_POT_GAUSSIAN_FULL || p.kind == NFMC_POT_ROSENBROCK ||
-           p.kind == NFMC_POT_STOCHASTIC_VOLATILITY || p.kind == NFMC_POT_SPARSE_LOGISTIC_REGRESSION;
-}
-
-// one launch of the mala / hmc kernels at layout c with jump-tail width jhp: kinds 4 to 7 have translation units of
-// their own
+// one launch of the mala / hmc kernels at layout c with jump-tail width jhp: the own_units kinds (kPotKinds) from their
+// units, kinds 0 to 3 from the unit of the width
+#define NFMC_KIND_CASE(KIND, POT) \
+    case KIND: return launch_mala_kind<POT>(a, jd, c, jhp, tiles, grid, sqrt2h, st);
 static int launch_mala(const NfmcMalaArgs& a, const JumpDev& jd, Cfg c, int jhp, bool fast, int64_t tiles, int grid,
                        float sqrt2h, hipStream_t st) {
-    if (a.pot.kind == NFMC_POT_GAUSSIAN_FULL) return launch_mala_fullrank(a, jd, c, jhp, tiles, grid, sqrt2h, st);
-    if (a.pot.kind == NFMC_POT_ROSENBROCK) return launch_mala_rosenbrock(a, jd, c, jhp, tiles, grid, sqrt2h, st);
-    if (a.pot.kind == NFMC_POT_STOCHASTIC_VOLATILITY) return launch_mala_sv(a, jd, c, jhp, tiles, grid, sqrt2h, st);
-    if (a.pot.kind == NFMC_POT_SPARSE_LOGISTIC_REGRESSION) return launch_mala_slr(a, jd, c, jhp, tiles, grid, sqrt2h, st);
+    switch (a.pot.kind) { NFMC_FOR_OWN_UNIT_POT(NFMC_KIND_CASE) }
     return jhp == 0 ? launch_mala_j0(a, jd, c, fast, tiles, grid, sqrt2h, st)
                     : (jhp == 4 ? launch_mala_j4(a, jd, c, fast, tiles, grid, sqrt2h, st)
                                 : launch_mala_j8(a, jd, c, fast, tiles, grid, sqrt2h, st));
 }
+#undef NFMC_KIND_CASE
+#define NFMC_KIND_CASE(KIND, POT) \
+    case KIND: return launch_hmc_kind<POT>(a, jd, c, jhp, tiles, grid, st);
 static int launch_hmc(const NfmcHmcArgs& a, const JumpDev& jd, Cfg c, int jhp, bool fast, int64_t tiles, int grid,
                       hipStream_t st) {
-    if (a.pot.kind == NFMC_POT_GAUSSIAN_FULL) return launch_hmc_fullrank(a, jd, c, jhp, tiles, grid, st);
-    if (a.pot.kind == NFMC_POT_ROSENBROCK) return launch_hmc_rosenbrock(a, jd, c, jhp, tiles, grid, st);
-    if (a.pot.kind == NFMC_POT_STOCHASTIC_VOLATILITY) return launch_hmc_sv(a, jd, c, jhp, tiles, grid, st);
-    if (a.pot.kind == NFMC_POT_SPARSE_LOGISTIC_REGRESSION) return launch_hmc_slr(a, jd, c, jhp, tiles, grid, st);
+    switch (a.pot.kind) { NFMC_FOR_OWN_UNIT_POT(NFMC_KIND_CASE) }
     return jhp == 0 ? launch_hmc_j0(a, jd, c, fast, tiles, grid, st)
                     : (jhp == 4 ? launch_hmc_j4(a, jd, c, fast, tiles, grid, st) : launch_hmc_j8(a, jd, c, fast, tiles, grid, st));
 }
+#undef NFMC_KIND_CASE
 
 static JumpDev jump_dev(const NfmcJumpTail* j) {
     JumpDev jd = {};
@@ -325,13 +302,14 @@ extern "C" int64_t nfmc_tune_state_doubles(int32_t d) {
     return NFMC_TUNE_WORDS + 3 * padded_d(d) + kStatTail;   // controller words, column totals, shift
 }
 
-extern "C" int nfmc_mala_steps_f32(const NfmcMalaArgs* args, nfmc_stream_t stream) {
-    int rc = check_common(args);
-    if (rc) return rc;
-    NfmcMalaArgs a = *args;
-    hipStream_t st = (hipStream_t)stream;
+// The part the two sampler entry points share, behind their own argument checks: layout, tile and grid arithmetic, the
+// scratch / defer / tune checks, then either the warmup loop (one launch + controller update per `every` transitions, all
+// of the call enqueued here) or one launch and the statistics finish.  launch(args, jd, c, jhp, fast, tiles, grid).
+template <class Args, class Launch>
+static int sampler_steps(const Args* args, hipStream_t st, Launch launch) {
+    Args a = *args;
     const int jhp = a.jump ? (a.jump->flow.n_hidden <= 4 ? 4 : 8) : 0;
-    const Cfg c = choose_cfg(a.d, jhp > 0, default_cfg_only(a.pot));
+    const Cfg c = choose_cfg(a.d, jhp > 0, pot_kind(a.pot.kind)->default_cfg_only);
     if (!c.cpl) return NFMC_ESHAPE;
     const bool fast = fast_path(&a, c) && !a.tune.state;   // tuning launches sum about a shift (StatShift): general kernels
     const int dp = c.cpl * c.lpc;
@@ -342,34 +320,30 @@ extern "C" int nfmc_mala_steps_f32(const NfmcMalaArgs* args, nfmc_stream_t strea
     if (a.stats.sum_x && a.stats.scratch_bytes < (int64_t)grid * (2 * dp + kStatTail) * (int64_t)sizeof(double))
         return NFMC_ESCRATCH;
     if (check_defer(a.stats, dp, a.d)) return NFMC_EINVAL;
-    if ((rc = check_tune(a, dp))) return rc;
-    const float sqrt2h = (float)sqrt(2.0 * (double)a.step_size);  // math.sqrt(2*step_size), langevin.py:75
+    if (int rc = check_tune(a, dp)) return rc;
     const JumpDev jd = jump_dev(a.jump);
     unsigned long long* jc = a.jump ? a.jump->counters : nullptr;
     a.jump = nullptr;  // host pointer: never dereferenced on the device
     if (a.tune.state) {
-        // warmup: `every` transitions per controller update, all pairs of the call enqueued here
         const int every = (a.tune.every > 0 && a.tune.every < a.n_steps) ? a.tune.every : a.n_steps;
         const int total = a.n_steps;
         for (int s0 = 0; s0 < total; s0 += every) {
             const int k = total - s0 < every ? total - s0 : every;
-            NfmcMalaArgs b = a;
+            Args b = a;
             b.n_steps = k;
             b.rng.step0 = a.rng.step0 + (uint32_t)s0;
             if (a.rng.replay_normals) b.rng.replay_normals = a.rng.replay_normals + (int64_t)s0 * a.n * a.d;
             if (a.rng.replay_uniforms) b.rng.replay_uniforms = a.rng.replay_uniforms + (int64_t)s0 * a.n;
             if (a.masks_out) b.masks_out = a.masks_out + (int64_t)s0 * a.n;
             if (a.log_ratio_out) b.log_ratio_out = a.log_ratio_out + (int64_t)s0 * a.n;
-            rc = launch_mala(b, jd, c, 0, fast, tiles, grid, sqrt2h, st);
-            if (rc) return rc;
+            if (int rc = launch(b, jd, c, 0, fast, tiles, grid)) return rc;
             tune_update(a.stats, a.tune, grid, two_level, dp, a.d, (unsigned long long)a.n * (unsigned long long)k, st);
             NFMC_HIP_CHECK_LAUNCH();
             store_advance(a.samples, k);
         }
         return NFMC_OK;
     }
-    rc = launch_mala(a, jd, c, jhp, fast, tiles, grid, sqrt2h, st);
-    if (rc) return rc;
+    if (int rc = launch(a, jd, c, jhp, fast, tiles, grid)) return rc;
     NFMC_HIP_CHECK_LAUNCH();
     if (a.stats.sum_x && !a.stats.defer) {
         hipLaunchKernelGGL(stats_finish_kernel<true>, dim3(stats_finish_grid(dp)), dim3(kFinishBlock), 0, st, a.stats.scratch,
@@ -380,56 +354,20 @@ extern "C" int nfmc_mala_steps_f32(const NfmcMalaArgs* args, nfmc_stream_t strea
     return NFMC_OK;
 }
 
-extern "C" int nfmc_hmc_steps_f32(const NfmcHmcArgs* args, nfmc_stream_t stream) {
-    int rc = check_common(args);
-    if (rc) return rc;
-    if (args->n_leapfrog <= 0) return NFMC_EINVAL;
-    NfmcHmcArgs a = *args;
+extern "C" int nfmc_mala_steps_f32(const NfmcMalaArgs* args, nfmc_stream_t stream) {
+    if (int rc = check_common(args)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const int jhp = a.jump ? (a.jump->flow.n_hidden <= 4 ? 4 : 8) : 0;
-    const Cfg c = choose_cfg(a.d, jhp > 0, default_cfg_only(a.pot));
-    if (!c.cpl) return NFMC_ESHAPE;
-    const bool fast = fast_path(&a, c) && !a.tune.state;   // tuning launches sum about a shift (StatShift): general kernels
-    const int dp = c.cpl * c.lpc;
-    const int cpw = kWave / c.lpc;
-    const int64_t tiles = (a.n + (int64_t)kWavesPerBlock * cpw - 1) / ((int64_t)kWavesPerBlock * cpw);
-    bool two_level = false;
-    const int grid = a.tune.state ? tune_grid(tiles, dp, a.stats.scratch_bytes, &two_level) : (int)(tiles < kMaxGrid ? tiles : kMaxGrid);
-    if (a.stats.sum_x && a.stats.scratch_bytes < (int64_t)grid * (2 * dp + kStatTail) * (int64_t)sizeof(double))
-        return NFMC_ESCRATCH;
-    if (check_defer(a.stats, dp, a.d)) return NFMC_EINVAL;
-    if ((rc = check_tune(a, dp))) return rc;
-    const JumpDev jd = jump_dev(a.jump);
-    unsigned long long* jc = a.jump ? a.jump->counters : nullptr;
-    a.jump = nullptr;
-    if (a.tune.state) {
-        const int every = (a.tune.every > 0 && a.tune.every < a.n_steps) ? a.tune.every : a.n_steps;
-        const int total = a.n_steps;
-        for (int s0 = 0; s0 < total; s0 += every) {
-            const int k = total - s0 < every ? total - s0 : every;
-            NfmcHmcArgs b = a;
-            b.n_steps = k;
-            b.rng.step0 = a.rng.step0 + (uint32_t)s0;
-            if (a.rng.replay_normals) b.rng.replay_normals = a.rng.replay_normals + (int64_t)s0 * a.n * a.d;
-            if (a.rng.replay_uniforms) b.rng.replay_uniforms = a.rng.replay_uniforms + (int64_t)s0 * a.n;
-            if (a.masks_out) b.masks_out = a.masks_out + (int64_t)s0 * a.n;
-            if (a.log_ratio_out) b.log_ratio_out = a.log_ratio_out + (int64_t)s0 * a.n;
-            rc = launch_hmc(b, jd, c, 0, fast, tiles, grid, st);
-            if (rc) return rc;
-            tune_update(a.stats, a.tune, grid, two_level, dp, a.d, (unsigned long long)a.n * (unsigned long long)k, st);
-            NFMC_HIP_CHECK_LAUNCH();
-            store_advance(a.samples, k);
-        }
-        return NFMC_OK;
-    }
-    rc = launch_hmc(a, jd, c, jhp, fast, tiles, grid, st);
-    if (rc) return rc;
-    NFMC_HIP_CHECK_LAUNCH();
-    if (a.stats.sum_x && !a.stats.defer) {
-        hipLaunchKernelGGL(stats_finish_kernel<true>, dim3(stats_finish_grid(dp)), dim3(kFinishBlock), 0, st, a.stats.scratch,
-                           grid, dp, a.d, a.stats, (unsigned long long)a.n * (unsigned long long)a.n_steps, jc,
-                           (unsigned long long)a.n);
-        NFMC_HIP_CHECK_LAUNCH();
-    }
-    return NFMC_OK;
+    const float sqrt2h = (float)sqrt(2.0 * (double)args->step_size);  // math.sqrt(2*step_size), langevin.py:75
+    return sampler_steps(args, st, [=](const NfmcMalaArgs& a, const JumpDev& jd, Cfg c, int jhp, bool fast, int64_t tiles, int grid) {
+        return launch_mala(a, jd, c, jhp, fast, tiles, grid, sqrt2h, st);
+    });
+}
+
+extern "C" int nfmc_hmc_steps_f32(const NfmcHmcArgs* args, nfmc_stream_t stream) {
+    if (int rc = check_common(args)) return rc;
+    if (args->n_leapfrog <= 0) return NFMC_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    return sampler_steps(args, st, [=](const NfmcHmcArgs& a, const JumpDev& jd, Cfg c, int jhp, bool fast, int64_t tiles, int grid) {
+        return launch_hmc(a, jd, c, jhp, fast, tiles, grid, st);
+    });
 }

@@ -6,7 +6,7 @@ int launch_mala_j8(const NfmcMalaArgs& a, const JumpDev& jd, Cfg c, bool fast, i
     int rc = NFMC_EUNSUPPORTED;
 #define M(CPL, LPC) \
     if (c.cpl == CPL && c.lpc == LPC) rc = launch_mala_cfg<CPL, LPC, 8>(a, jd, fast, tiles, grid, sqrt2h, st);
-    NFMC_FOR_BCFG(M)
+    NFMC_FOR_JUMP_CFG(M)
 #undef M
     return rc;
 }
