@@ -107,7 +107,7 @@ enum {
        nfmc_flow_mh_steps_f32 and by the VALU NeuTra kernels (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32
        with conditioners of at most 32 units).  NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the
        fit kernels, the Philox4x32-7 stream and the NeuTra matrix-core kernels (conditioners wider than 32). */
-    NFMC_POT_SPARSE_LOGISTIC_REGRESSION = 7
+    NFMC_POT_SPARSE_LOGISTIC_REGRESSION = 7,
     /* Sparse logistic regression with a hierarchical shrinkage prior (the German-credit model of the Inference Gym) over
        d = 2 D + 1 coordinates: x_{2j} = w_j, x_{2j+1} = l_j = log lambda_j (j = 0 .. D-1), x_{2D} = s = log tau;
        tau ~ Gamma(a, b), lambda_j ~ Gamma(a, b) (shape a, rate b), w_j ~ N(0, 1), beta_j = tau lambda_j w_j,
@@ -125,13 +125,30 @@ enum {
        NeuTra kernels (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32 with conditioners of at most 32 units).
        NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the fit kernels, the Philox4x32-7 stream and the
        NeuTra matrix-core kernels (conditioners wider than 32). */
+    NFMC_POT_LATTICE_PHI4 = 8
+    /* phi^4 scalar field on a lattice of H rows of W sites, flattened row-major (d = H W; H = 1 is the 1-D lattice,
+       which has no second axis).  Every site c has two neighbours c' per axis; a periodic axis wraps round (so an axis
+       of length 2 counts its bond twice), and with the zero boundary the field is 0 past the ends of an axis:
+         U = sum_c [1/2 m2 x_c^2 + 1/4 lam x_c^4] + 1/2 kappa sum_bonds (x_c' - x_c)^2   (constants dropped)
+         dU/dx_c = m2 x_c + lam x_c^3 + kappa sum_{c'} (x_c - x_c')
+       n_components = W;  a -> (m2, lam, kappa, boundary), four fp32 in device memory, boundary 0 = periodic, 1 = zero
+       (any other value reads as zero);  b, a_scalar and b_scalar unused.  One row with the zero boundary on BOTH axes
+       (a 2-D lattice of shape (1, W)) is the 1-D lattice with m2 + 2 kappa in place of m2: the caller folds it.  A NULL
+       a, W < 1 or d % W != 0 is NFMC_EINVAL; W % 4 != 0 is NFMC_EUNSUPPORTED (the kernels need every lattice row to start
+       on a 16-byte register quad).  The kernels exchange neighbours through a wave-private LDS block of 16 + 1024 CPL
+       bytes (CPL = 4, 8 or 16 coordinates per lane; a flow image that leaves no room for it gets NFMC_EUNSUPPORTED).
+       Served by nfmc_mala_steps_f32 / nfmc_hmc_steps_f32 (general kernels, with or without a jump tail, device warmup
+       tuning included), by the register-layout kernels of nfmc_flow_mh_steps_f32 and by the VALU NeuTra kernels
+       (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32 with conditioners of at most 32 units).
+       NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the fit kernels, the Philox4x32-7 stream and the
+       NeuTra matrix-core kernels (conditioners wider than 32). */
 };
 
 typedef struct {
     int32_t kind;
     int32_t n_components; /* NFMC_POT_GAUSSIAN_MIXTURE: K; NFMC_POT_LOGISTIC_REGRESSION: N; NFMC_POT_GAUSSIAN_FULL: d;
                              NFMC_POT_ROSENBROCK: block length; NFMC_POT_STOCHASTIC_VOLATILITY: T = d - 3;
-                             NFMC_POT_SPARSE_LOGISTIC_REGRESSION: N;
+                             NFMC_POT_SPARSE_LOGISTIC_REGRESSION: N; NFMC_POT_LATTICE_PHI4: W (sites per lattice row);
                              0 for the other kinds (was `reserved`, same layout) */
     const float* a; /* (d,) or NULL -> a_scalar */
     const float* b; /* (d,) or NULL -> b_scalar */

@@ -404,27 +404,51 @@ inline int check_slr(const NfmcPotential& p, int d) {
     return NFMC_OK;
 }
 
-// LDS bytes a register-layout kernel with DP padded coordinates stages for `p` beside its flow image
-inline size_t mixture_bytes(const NfmcPotential& p, int dp) { return (size_t)mixture_floats(p.n_components, dp) * sizeof(float); }
-inline size_t logreg_bytes(const NfmcPotential&, int dp) { return (size_t)logreg_floats(dp) * sizeof(float); }
-inline size_t fullrank_bytes(const NfmcPotential&, int) { return (size_t)kLogRegTileFloats * sizeof(float); }
-inline size_t slr_bytes(const NfmcPotential&, int dp) { return (size_t)slr_floats(dp) * sizeof(float); }
+// phi^4 lattice field (kind 8): the exchange block of a workgroup is one zeroed register quad and, behind it, one row of
+// DP = CPL * LPC floats for each of its kBlock / LPC chains (Phi4Pot)
+__host__ __device__ inline int phi4_floats(int cpl) { return 4 + kBlock * cpl; }
+
+// argument check of a kind-8 descriptor: (m2, lam, kappa, boundary) present, rows of W = n_components sites that tile d;
+// the register kernels need every row to start on a register quad, so W % 4 != 0 is a valid request they do not run
+inline int check_phi4(const NfmcPotential& p, int d) {
+    if (!p.a || p.n_components < 1 || d % p.n_components != 0) return NFMC_EINVAL;
+    if (p.n_components % 4 != 0) return NFMC_EUNSUPPORTED;
+    return NFMC_OK;
+}
+
+// LDS bytes a register-layout kernel with DP = CPL * LPC padded coordinates stages for `p` beside its flow image
+inline size_t mixture_bytes(const NfmcPotential& p, int dp, int) { return (size_t)mixture_floats(p.n_components, dp) * sizeof(float); }
+inline size_t logreg_bytes(const NfmcPotential&, int dp, int) { return (size_t)logreg_floats(dp) * sizeof(float); }
+inline size_t fullrank_bytes(const NfmcPotential&, int, int) { return (size_t)kLogRegTileFloats * sizeof(float); }
+inline size_t slr_bytes(const NfmcPotential&, int dp, int) { return (size_t)slr_floats(dp) * sizeof(float); }
+inline size_t phi4_bytes(const NfmcPotential&, int, int cpl) { return (size_t)phi4_floats(cpl) * sizeof(float); }
 
 // ------------------------------------------------------------------------------------------------
 // The potential kinds, as the host sees them: one row per NFMC_POT_* value, indexed by it.  Every entry point that asks
 // "does this family of kernels run the kind, and is its descriptor well formed" goes through check_potential(); every
 // host decision that depends on the kind reads a column here.  Adding a potential kind:
-//   1. nfmc_hip.h: its NFMC_POT_* value and descriptor fields; here: its check_* function and its row.
+//   1. nfmc_hip.h: its NFMC_POT_* value and descriptor fields; here: its check_* function and its row.  The check
+//      answers NFMC_EINVAL / NFMC_EALIGN for a malformed descriptor and NFMC_EUNSUPPORTED for a well-formed one no
+//      kernel runs (check_phi4: a row length that is no multiple of 4); it sees host values only, never what a or b
+//      point to.
 //   2. Its device class Pot<CPL, LPC, FAST> below (prepare / grad / term, and stage() with a *_bytes function if kStaged).
+//      The *_bytes function gets the layout as (DP, CPL): a read-only table is sized by DP, a block with a slot per
+//      chain by CPL (phi4_bytes).  A block the lanes write (Phi4Pot) must not rely on workgroup barriers inside
+//      prepare() unless every thread of the workgroup calls it equally often (LogRegPot's rule).
 //   3. own_units: a line in NFMC_FOR_OWN_UNIT_POT and four units that instantiate launch_{mala,hmc}_kind and
-//      launch_b_kind{,_rqs} for the class (sampler_slr_mala.hip and its three siblings are the pattern).
-//   4. neutra_valu: its *_value_grad_row and its arm of adjusted_potential_grad_row (neutra_kernels.hpp).
+//      launch_b_kind{,_rqs} for the class (sampler_slr_mala.hip and its three siblings are the pattern).  The build
+//      picks up every .hip file of this directory; a unit that takes a minute or more also goes into SLOW_FIRST
+//      (nfmc_amd/build.py).
+//   4. neutra_valu: its *_value_grad_row and its arm of adjusted_potential_grad_row (neutra_kernels.hpp), and its class
+//      in the tuple of NeuTra._min_hidden (nfmc_amd/samplers/neutra.py) that keeps it off the matrix-core kernels.
 //   5. Python: POT_* in nfmc_amd/hip.py, its class in nfmc_amd/potentials.py, an fp64 oracle tests/<kind>_fp64.py and
 //      tests/test_{host,gpu}_<kind>.py, which assert the codes of step 1's check.
+//   6. Words: the kind's comment in nfmc_hip.h, its line in INTEGRATION.md, its paragraph in README.md and its
+//      subsection of DESIGN.md 3.3 with the measured cost (a tools/probe_<kind>.py).
 struct PotKind {
     int kind;
     int (*check)(const NfmcPotential&, int d);              // its own argument check (nullptr: nothing to check)
-    size_t (*staged_bytes)(const NfmcPotential&, int dp);   // the LDS block its class stages (nullptr: none)
+    size_t (*staged_bytes)(const NfmcPotential&, int dp, int cpl);   // the LDS block its class stages (nullptr: none)
     bool own_units;          // samplers and flow-MH: general kernels only, in translation units of its own
     bool default_cfg_only;   // samplers: instantiated at the default layouts only (is_default_cfg, sampler_impl.hpp)
     bool register_only;      // flow-MH: the register-layout kernels only (no matrix-core or one-chain-per-lane kernel)
@@ -439,6 +463,7 @@ constexpr PotKind kPotKinds[] = {
     {NFMC_POT_ROSENBROCK, check_rosenbrock, nullptr, true, true, true, true},
     {NFMC_POT_STOCHASTIC_VOLATILITY, check_sv, nullptr, true, true, true, true},
     {NFMC_POT_SPARSE_LOGISTIC_REGRESSION, check_slr, slr_bytes, true, true, true, true},
+    {NFMC_POT_LATTICE_PHI4, check_phi4, phi4_bytes, true, true, true, true},
 };
 constexpr int kNumPotKinds = (int)(sizeof(kPotKinds) / sizeof(PotKind));
 constexpr bool pot_kinds_indexed(int i = 0) { return i == kNumPotKinds || (kPotKinds[i].kind == i && pot_kinds_indexed(i + 1)); }
@@ -450,7 +475,8 @@ constexpr const PotKind* pot_kind(int kind) { return kind >= 0 && kind < kNumPot
 // switches (sampler_impl.hpp, flow_b_mh.hpp) expand this list, and each expansion asserts the row's flag.
 #define NFMC_FOR_OWN_UNIT_POT(M)                                            \
     M(NFMC_POT_GAUSSIAN_FULL, GaussFullPot) M(NFMC_POT_ROSENBROCK, RosenbrockPot) \
-    M(NFMC_POT_STOCHASTIC_VOLATILITY, SVPot) M(NFMC_POT_SPARSE_LOGISTIC_REGRESSION, SparseLogRegPot)
+    M(NFMC_POT_STOCHASTIC_VOLATILITY, SVPot) M(NFMC_POT_SPARSE_LOGISTIC_REGRESSION, SparseLogRegPot) \
+    M(NFMC_POT_LATTICE_PHI4, Phi4Pot)
 
 // The families of kernels that take a potential descriptor of any kind.  (The entry points that run kinds 0 and 1 only
 // say so themselves.)
@@ -461,9 +487,9 @@ inline int check_potential(const NfmcPotential& p, int d, PotFamily family) {
     if (!k || (family == PotFamily::kNeutraValu && !k->neutra_valu)) return NFMC_EUNSUPPORTED;
     return k->check ? k->check(p, d) : NFMC_OK;
 }
-inline size_t staged_potential_bytes(const NfmcPotential& p, int dp) {
+inline size_t staged_potential_bytes(const NfmcPotential& p, int dp, int cpl) {
     const PotKind* k = pot_kind(p.kind);
-    return k && k->staged_bytes ? k->staged_bytes(p, dp) : 0;
+    return k && k->staged_bytes ? k->staged_bytes(p, dp, cpl) : 0;
 }
 
 template <int CPL, int LPC, bool FAST>
@@ -1181,9 +1207,120 @@ struct SparseLogRegPot {
     __device__ __forceinline__ float term(const Ctx& cx, int i, float) const { return i == 0 ? cx.u : 0.f; }
 };
 
+// phi^4 scalar field on a lattice (NFMC_POT_LATTICE_PHI4; rows of W = p.n_components sites, H = d / W of them, row-major;
+// (m2, lam, kappa, boundary) = p.a[0 .. 3], boundary 0 periodic / 1 zero field outside).  With L_c = sum over the
+// neighbours c' of c of (x_c - x_c') -- two per axis; a periodic axis wraps, a zero-boundary axis reads 0 past its ends:
+//   dU/dx_c = m2 x_c + lam x_c^3 + kappa L_c
+//   U = sum_c x_c [1/2 m2 x_c + 1/4 lam x_c^3 + 1/2 kappa L_c]
+// (sum_c x_c L_c counts (x_c' - x_c)^2 once per bond, a boundary bond of the zero boundary included: each bond's
+// a^2 + b^2 - 2ab is a (a - b) at one end plus b (b - a) at the other).  H = 1 is the 1-D lattice: no second axis.
+// W % 4 == 0 (check_phi4), so every lattice row starts on a register quad and d % 4 == 0: inside a quad the left and
+// right neighbours are the lane's own registers, the upper and lower neighbours of a quad are ONE aligned quad W floats
+// before / behind it in the chain's row, and only register 0's left and register 3's right neighbour lie in other quads.
+// In the interleaved layout those quads sit in other lanes at a register index that depends on the lane, so the lanes
+// exchange through LDS, not through ds_bpermute (one permute per source register and a select chain per target quad):
+// the workgroup's block is one zeroed quad and one row of DP floats per chain (phi4_floats); prepare() stores the
+// lane's quads into its chain's row (ds_write_b128) and reads, per quad, the upper and the lower quad (ds_read_b128) and
+// the two single neighbours (ds_read_b32): 5 Q LDS operations per evaluation.  The four addresses of a quad are set once
+// in init().  A periodic wrap is another address in the row; a neighbour the zero boundary leaves out is the zeroed
+// quad; with H = 1 "up" and "down" are the quad itself, whose differences are exactly zero; a padding quad (c >= d)
+// reads the zeroed quad and has no bit in `ok`, so its term and gradient are exactly zero.  No branch on the boundary
+// in prepare().  A chain's row is written and read by the lanes of ONE wave, whose LDS operations complete in order, so
+// no workgroup barrier is needed (and none is possible: the waves do not call prepare() in step); wavefront-scope fences
+// and wave barriers keep the compiler from moving the reads over the stores of this or the next evaluation.  term() puts
+// the lane's share of U on its register 0.
+template <int CPL, int LPC, bool FAST>
+struct Phi4Pot {
+    static constexpr bool kQuadratic = false;
+    static constexpr bool kStaged = true;
+    static constexpr int DP = CPL * LPC;
+    static constexpr int Q = CPL / 4;   // register quads
+    float* blk;                          // LDS: zero quad | rows (kBlock / LPC, DP)
+    float m2, lam, kap;
+    int own;                             // float index of this lane's quad 0 in its chain's row (quad q: + 4 q LPC)
+    int up[Q], dn[Q], lf[Q], rt[Q];      // float indices of the quad above / below and of the single neighbours
+    uint32_t ok;                         // bit q: quad q holds lattice sites (c < d)
+    struct Ctx {
+        float u;                         // this lane's share of U
+        float gr[CPL];                   // dU/dx of this lane's coordinates
+    };
+
+    __device__ __forceinline__ static void order() {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+    // all threads of the workgroup; the caller synchronises before the first prepare()
+    __device__ __forceinline__ static void stage(float* __restrict__ lds, const NfmcPotential&, int) {
+        if (threadIdx.x < 4) lds[threadIdx.x] = 0.f;
+    }
+    __device__ __forceinline__ void init(const NfmcPotential& p, int g, int d, float* lds) {
+        blk = lds;
+        m2 = p.a[0];
+        lam = p.a[1];
+        kap = p.a[2];
+        const bool zero = p.a[3] != 0.f;
+        const int W = p.n_components, H = d / W;
+        const int row = 4 + (int)(threadIdx.x / LPC) * DP;   // this chain's row, behind the zero quad
+        own = row + 4 * g;
+        ok = 0u;
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            const int c0 = 4 * (q * LPC + g);   // the quad's first site (coord_of)
+            up[q] = dn[q] = lf[q] = rt[q] = 0;  // the zero quad
+            if (c0 < d) {
+                ok |= 1u << q;
+                const int r = c0 / W, k = c0 - r * W, at = row + c0;
+                if (k > 0) lf[q] = at - 1;
+                else if (!zero) lf[q] = at + W - 1;
+                if (k + 4 < W) rt[q] = at + 4;
+                else if (!zero) rt[q] = at + 4 - W;
+                if (H == 1) {
+                    up[q] = dn[q] = at;
+                } else {
+                    if (r > 0) up[q] = at - W;
+                    else if (!zero) up[q] = at + (H - 1) * W;
+                    if (r + 1 < H) dn[q] = at + W;
+                    else if (!zero) dn[q] = at - (H - 1) * W;
+                }
+            }
+        }
+    }
+    __device__ __forceinline__ Ctx prepare(const float (&x)[CPL], int, int) const {
+        order();   // behind the reads of the previous evaluation
+#pragma unroll
+        for (int q = 0; q < Q; ++q)
+            *reinterpret_cast<float4*>(blk + own + 4 * q * LPC) = make_float4(x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]);
+        order();   // the wave's stores precede its reads
+        Ctx cx;
+        float u = 0.f;
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            const float4 a = *reinterpret_cast<const float4*>(blk + up[q]), b = *reinterpret_cast<const float4*>(blk + dn[q]);
+            const float va[4] = {a.x, a.y, a.z, a.w}, vb[4] = {b.x, b.y, b.z, b.w};
+            const float row[6] = {blk[lf[q]], x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3], blk[rt[q]]};
+            const bool site = (ok >> q) & 1u;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float xc = row[k + 1];
+                const float L = ((xc - row[k]) + (xc - row[k + 2])) + ((xc - va[k]) + (xc - vb[k]));
+                const float x2 = xc * xc;
+                const float gr = fmaf(kap, L, xc * fmaf(lam, x2, m2));
+                const float t = xc * fmaf(0.5f * kap, L, xc * fmaf(0.25f * lam, x2, 0.5f * m2));
+                cx.gr[4 * q + k] = site ? gr : 0.f;
+                u += site ? t : 0.f;
+            }
+        }
+        order();   // the next evaluation's stores stay behind these reads
+        cx.u = u;
+        return cx;
+    }
+    __device__ __forceinline__ float grad(const Ctx& cx, int i, float) const { return cx.gr[i]; }
+    __device__ __forceinline__ float term(const Ctx& cx, int i, float) const { return i == 0 ? cx.u : 0.f; }
+};
+
 // Potentials with an LDS block (kStaged) stage it behind the `img_floats` floats of flow image a kernel keeps at the
 // start of its dynamic LDS (16-byte aligned), synchronise the workgroup and bind to it.  lds_with_potential() is the
-// host side: the kernel's dynamic LDS bytes for an image of `img_bytes`.
+// host side: the kernel's dynamic LDS bytes for an image of `img_bytes` at layout (cpl, lpc).
 template <class P>
 __device__ __forceinline__ void init_staged(P& pot, const NfmcPotential& p, int g, int d, float* lds, int img_floats) {
     float* blk = lds + ((img_floats + 3) & ~3);
@@ -1191,8 +1328,8 @@ __device__ __forceinline__ void init_staged(P& pot, const NfmcPotential& p, int 
     __syncthreads();
     pot.init(p, g, d, blk);
 }
-inline size_t lds_with_potential(size_t img_bytes, const NfmcPotential& p, int dp) {
-    const size_t blk = staged_potential_bytes(p, dp);
+inline size_t lds_with_potential(size_t img_bytes, const NfmcPotential& p, int cpl, int lpc) {
+    const size_t blk = staged_potential_bytes(p, cpl * lpc, cpl);
     return blk ? ((img_bytes + 15) & ~(size_t)15) + blk : img_bytes;
 }
 

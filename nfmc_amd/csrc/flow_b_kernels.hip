@@ -163,7 +163,7 @@ static int launch_b_rqs(const NfmcFlowMhArgs& a, bool fast, int64_t tiles, int g
     {                                                                                                             \
         const size_t img = (size_t)FlowImage<CPL, LPC, HP, (F && CPL >= 8), kRqsBins>::total_floats(a.flow.n_hidden_layers, \
                                                                                                  a.flow.n_coupling) * sizeof(float); \
-        const size_t lds = lds_with_potential(img, a.pot, CPL * LPC);                                             \
+        const size_t lds = lds_with_potential(img, a.pot, CPL, LPC);                                             \
         if (lds > 120 * 1024) return NFMC_EUNSUPPORTED;                                                           \
         if (rng_rounds(a.rng) == 7) return NFMC_EUNSUPPORTED;                                                     \
         if (dry) return 0;                                                                                        \
@@ -183,7 +183,7 @@ static int launch_b(const NfmcFlowMhArgs& a, bool fast, int64_t tiles, int grid,
     {                                                                                                           \
         const size_t img = (size_t)FlowImage<CPL, LPC, HP, (F && CPL >= 8)>::total_floats(a.flow.n_hidden_layers, \
                                                                                        a.flow.n_coupling) * sizeof(float); \
-        const size_t lds = lds_with_potential(img, a.pot, CPL * LPC);                                           \
+        const size_t lds = lds_with_potential(img, a.pot, CPL, LPC);                                           \
         if (lds > 120 * 1024) return NFMC_EUNSUPPORTED;                                                         \
         if (dry) return 0;                                                                                      \
         const bool diag = !F || wants_diag(a);                                                                  \

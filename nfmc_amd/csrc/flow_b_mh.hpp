@@ -135,7 +135,7 @@ constexpr BCfg kFlowBCfgs[] = {NFMC_FOR_FLOWB_CFG(NFMC_BCFG_ENTRY)};
 // The own_units kinds (kPotKinds): class POT at layout c, conditioner bucket hp (4 / 8), affine (NB = 0) or spline
 // (NB = kRqsBins) couplings; one general kernel (diagnostics compiled in, default stream) per layout and width.  The
 // arguments and NFMC_EUNSUPPORTED / dry as in flow_mh_b_launch.  Never exact-fit or dual: their parameters are tables.
-// flow_b_{fullrank,rosenbrock,sv,slr}{,_rqs}.hip instantiate it explicitly.
+// flow_b_{fullrank,rosenbrock,sv,slr,phi4}{,_rqs}.hip instantiate it explicitly.
 template <template <int, int, bool> class POT, int NB>
 int launch_b_kind(const NfmcFlowMhArgs& a, BCfg c, int hp, int64_t tiles, int grid, hipStream_t st, bool dry) {
     if (rng_rounds(a.rng) != 10) return NFMC_EUNSUPPORTED;
@@ -143,7 +143,7 @@ int launch_b_kind(const NfmcFlowMhArgs& a, BCfg c, int hp, int64_t tiles, int gr
     if (hp == HP && c.cpl == CPL && c.lpc == LPC) {                                                                    \
         const size_t img = (size_t)FlowImage<CPL, LPC, HP, false, NB>::total_floats(a.flow.n_hidden_layers, a.flow.n_coupling) * \
                            sizeof(float);                                                                              \
-        const size_t lds = lds_with_potential(img, a.pot, CPL * LPC);                                                  \
+        const size_t lds = lds_with_potential(img, a.pot, CPL, LPC);                                                  \
         if (lds > 120 * 1024) return NFMC_EUNSUPPORTED;                                                                \
         return dry ? NFMC_OK : launch_lds(flow_mh_b_kernel<CPL, LPC, HP, POT, false, true, 10, NB>, grid, kBlock, lds, st, a, tiles); \
     }

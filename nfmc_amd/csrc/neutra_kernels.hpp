@@ -302,6 +302,37 @@ __device__ __forceinline__ float slr_value_grad_row(const float* __restrict__ ro
     return (float)(ul + (double)(u + fmaf(cb, es, -ca * s)));
 }
 
+// phi^4 lattice field (NFMC_POT_LATTICE_PHI4) for the row of one chain, as potential_value_grad_row: U and dU/dx of
+// Phi4Pot (common.hpp), H = d / W rows of W = n_components sites.  A plain loop over the sites with index arithmetic for
+// the four neighbours (two with H = 1): a periodic axis wraps, the zero boundary reads 0 past its ends.  The constants
+// are wave-uniform (scalar loads).  Kept out of potential_value_grad_row, which the fit and DLMC kernels share and which
+// never see kind 8.
+__device__ __forceinline__ float phi4_value_grad_row(const float* __restrict__ row, float* __restrict__ grow,
+                                                     const NfmcPotential& p, int d) {
+    const float m2 = p.a[0], lam = p.a[1], kap = p.a[2];
+    const bool zero = p.a[3] != 0.f;
+    const int W = p.n_components, H = d / W, wrap = (H - 1) * W;
+    float u = 0.f;
+    int c = 0;
+    for (int r = 0; r < H; ++r) {
+        for (int k = 0; k < W; ++k, ++c) {
+            const float xc = row[c];
+            const float xl = k > 0 ? row[c - 1] : (zero ? 0.f : row[c + W - 1]);
+            const float xr = k + 1 < W ? row[c + 1] : (zero ? 0.f : row[c + 1 - W]);
+            float L = (xc - xl) + (xc - xr);
+            if (H > 1) {
+                const float xu = r > 0 ? row[c - W] : (zero ? 0.f : row[c + wrap]);
+                const float xd = r + 1 < H ? row[c + W] : (zero ? 0.f : row[c - wrap]);
+                L += (xc - xu) + (xc - xd);
+            }
+            const float x2 = xc * xc;
+            grow[c] = fmaf(kap, L, xc * fmaf(lam, x2, m2));
+            u = fmaf(xc, fmaf(0.5f * kap, L, xc * fmaf(0.25f * lam, x2, 0.5f * m2)), u);
+        }
+    }
+    return u;
+}
+
 // U~(z) and grad U~(z) for this lane's chain.  zrow: latent (tile columns in latent order), read only;
 // wrow: scratch, ends holding z again (rebuilt); grow: gradient in the same column order as zrow.
 template <int HP>
@@ -314,6 +345,7 @@ __device__ __forceinline__ float adjusted_potential_grad_row(const float* __rest
                     : pot.kind == NFMC_POT_ROSENBROCK    ? rosenbrock_value_grad_row(wrow, grow, pot, g.d)
                     : pot.kind == NFMC_POT_STOCHASTIC_VOLATILITY ? sv_value_grad_row(wrow, grow, pot, g.d)
                     : pot.kind == NFMC_POT_SPARSE_LOGISTIC_REGRESSION ? slr_value_grad_row(wrow, grow, pot, g.d)
+                    : pot.kind == NFMC_POT_LATTICE_PHI4 ? phi4_value_grad_row(wrow, grow, pot, g.d)
                                                          : potential_value_grad_row(wrow, grow, pot, g.d);  // U(x), dU/dx (neutra.py:62)
     // reverse sweep, mirror image of flow_inverse_row
     for (int c = 0; c < g.d; ++c) {                               // EA0^-1

@@ -568,7 +568,7 @@ size_t sampler_lds(const NfmcPotential& p, const JumpDev& jd) {
     size_t lds = 0;
     if constexpr (JHP > 0)
         lds = (size_t)FlowImage<CPL, LPC, JHP>::total_floats(jd.flow.n_hidden_layers, jd.flow.n_coupling) * sizeof(float);
-    return lds_with_potential(lds, p, CPL * LPC);
+    return lds_with_potential(lds, p, CPL, LPC);
 }
 
 template <int CPL, int LPC, template <int, int, bool> class POT, bool F, int JHP>
@@ -670,7 +670,7 @@ int launch_hmc_cfg(const NfmcHmcArgs& a, const JumpDev& jd, bool fast, int64_t t
 constexpr Cfg kJumpCfgs[] = {NFMC_FOR_JUMP_CFG(NFMC_CFG_ENTRY)};
 
 // The own_units kinds (kPotKinds): every layout and jump-tail width of one class in a translation unit of its own
-// (sampler_{fullrank,rosenbrock,sv,slr}_{mala,hmc}.hip instantiate these explicitly), the layouts kind 3 gets, general
+// (sampler_{fullrank,rosenbrock,sv,slr,phi4}_{mala,hmc}.hip instantiate these explicitly), the layouts kind 3 gets, general
 // kernels on the default Philox4x32-10 stream only
 template <template <int, int, bool> class POT>
 int launch_mala_kind(const NfmcMalaArgs& a, const JumpDev& jd, Cfg c, int jhp, int64_t tiles, int grid, float sqrt2h,

@@ -17,6 +17,7 @@ OK, EINVAL, ESHAPE, EALIGN, EUNSUPPORTED, ESCRATCH = 0, -1, -2, -3, -4, -5
 POT_QUADRATIC, POT_FUNNEL, POT_GAUSSIAN_MIXTURE, POT_LOGISTIC_REGRESSION, POT_GAUSSIAN_FULL, POT_ROSENBROCK = 0, 1, 2, 3, 4, 5
 POT_STOCHASTIC_VOLATILITY = 6
 POT_SPARSE_LOGISTIC_REGRESSION = 7
+POT_LATTICE_PHI4 = 8
 MIXTURE_MAX_COMPONENTS = 8   # kMixMaxK (csrc/common.hpp)
 TAG_NOISE, TAG_ACCEPT, TAG_LATENT, TAG_JUMP = 0, 1, 2, 3
 CNT_ACCEPTED, CNT_ATTEMPTED, CNT_NONFINITE, CNT_WORDS = 0, 1, 2, 4
