@@ -402,6 +402,40 @@ int nfmc_flow_mh_steps_f32(const NfmcFlowMhArgs* args, nfmc_stream_t stream);
  * nfmc_mh_accept_select_f32 (the split path every foreign flow object takes; jump.py:205-231). */
 int nfmc_flow_mh_supported_f32(const NfmcFlowMhArgs* args);
 
+/* ---- A whole run of `JumpNFMC.sample` (jump.py:156-246) in one call: for each of n_outer outer iterations, the n_inner
+ * inner transitions -- nfmc_mala_steps_f32 / nfmc_hmc_steps_f32 launches of at most NFMC_MAX_STEPS_PER_CALL steps -- and
+ * then ONE flow-MH step (nfmc_flow_mh_steps_f32, n_steps = 1, logq_cached = 0): the launches a host loop over the two entry
+ * points enqueues, in its order.  With s = inner->rng.step0 the inner launch that starts `off` transitions into iteration i
+ * runs from transition s + i (n_inner + 1) + off, the jump of iteration i is transition s + i (n_inner + 1) + n_inner
+ * (n_steps, rng.step0 of the structs are otherwise not read).
+ *
+ * n_parts > 1 splits the chains into that many ranges -- part p = chains [p m, min(n, (p + 1) m)), m = n / n_parts rounded
+ * up to whole workgroup tiles of both kernels; a part without chains launches nothing -- and enqueues part 0 on `stream`
+ * and every other part on a stream the library keeps for it (created on first use, per device, never destroyed), so that
+ * the jump of one part runs beside the inner kernel of another and their launch boundaries fall inside kernels.  The side
+ * streams start behind everything enqueued on `stream` before the call, and `stream` continues behind them: to the caller
+ * the call is ordered on `stream` like every other entry point, also when it returns an error.  Each chain sees the
+ * arguments, the global chain id and the transitions of the unsplit run: states and logq are bitwise those of n_parts = 1,
+ * the counters exact; the moments are the same per-workgroup partials folded from other slabs (fp64 rounding).  Part p
+ * writes the statistics slabs from p * ceil(2048 / n_parts) on.
+ *
+ * Both structs describe the same chains (x, n, d, rng.seed / chain_offset / rounds, stats) and are otherwise filled as for
+ * their own entry points, with statistics either off or deferred (stats.defer = 1), and without what a host would have to
+ * advance between the launches: no jump tail, no tuning, no sample store, no mask / log-ratio outputs, no replayed noise
+ * (NFMC_EINVAL).  Where the jump does not run on the register-layout kernels (n_hidden > 8, d > 512) the run is one part. */
+enum { NFMC_INNER_MALA = 0, NFMC_INNER_HMC = 1 };
+#define NFMC_JUMP_RUN_MAX_PARTS 4
+typedef struct {
+    int32_t inner_kind;          /* NFMC_INNER_MALA: inner -> NfmcMalaArgs; NFMC_INNER_HMC: inner -> NfmcHmcArgs */
+    int32_t n_parts;             /* 1 .. NFMC_JUMP_RUN_MAX_PARTS; 1 = everything on `stream`, no event, no side stream */
+    const void* inner;
+    const NfmcFlowMhArgs* jump;
+    int32_t n_outer;             /* T >= 1 */
+    int32_t n_inner;             /* K >= 1 */
+} NfmcJumpRun;
+
+int nfmc_jump_run_f32(const NfmcJumpRun* run, nfmc_stream_t stream);
+
 /* The same run of n_steps independent-MH transitions (FixedIMH.sample, imh.py:200-255) as a data-parallel problem:
  * the proposals of an independence sampler do not depend on the state, so all n * n_steps of them are evaluated at
  * once, a per-chain scan (one lane per chain) applies the Metropolis tests, and proposals are replayed for the moments /

@@ -3,6 +3,7 @@
 // LPC lanes per chain, state and proposal in VGPRs, flow weights in one LDS image per workgroup
 // (flow_b.hpp).  Same skeleton and statistics path as mala_kernel.
 #include "flow_b_mh.hpp"
+#include "run_parts.hpp"
 
 namespace nfmc {
 
@@ -204,8 +205,11 @@ static int launch_b(const NfmcFlowMhArgs& a, bool fast, int64_t tiles, int grid,
 }
 
 // Returns NFMC_EUNSUPPORTED when this path does not cover the request (caller falls back to flow_mh_kernel).
-// dry: decide only, launch nothing (nfmc_flow_mh_supported_f32).
-int flow_mh_b_launch(const NfmcFlowMhArgs& a, hipStream_t st, int* grid_out, int* dp_out, bool dry) {
+// dry: decide only, launch nothing (nfmc_flow_mh_supported_f32).  part: `args` are one part of a split run (run_parts.hpp).
+// tile_chains_out (optional): chains per workgroup tile of the chosen kernel.
+int flow_mh_b_launch(const NfmcFlowMhArgs& args, hipStream_t st, int* grid_out, int* dp_out, bool dry, const LaunchPart* part,
+                     int64_t* tile_chains_out) {
+    NfmcFlowMhArgs a = args;
     const int d = a.flow.d;
     const int hp = a.flow.n_hidden <= 4 ? 4 : 8;
     if (a.flow.n_hidden > 8 || d > 512) return NFMC_EUNSUPPORTED;
@@ -213,7 +217,7 @@ int flow_mh_b_launch(const NfmcFlowMhArgs& a, hipStream_t st, int* grid_out, int
     // IMH d = 64, 1000 transitions: 3.23 vs 3.64 ms at n = 8192, 4.2 vs 6.5 ms at n = 16384) except for very
     // few chains, where twice the lanes per chain win (n = 4096: 3.30 vs 3.40 ms)
     BCfg c = {0, 0};
-    const int want_cpl = a.n <= 4096 ? 4 : 8;
+    const int want_cpl = (part ? part->layout_n : a.n) <= 4096 ? 4 : 8;
     for (const BCfg& k : kFlowBCfgs) {
         if (k.cpl * k.lpc < d) continue;
         if (c.cpl == 0 || k.cpl * k.lpc < c.cpl * c.lpc || (k.cpl * k.lpc == c.cpl * c.lpc && k.cpl == want_cpl)) c = k;
@@ -244,10 +248,13 @@ int flow_mh_b_launch(const NfmcFlowMhArgs& a, hipStream_t st, int* grid_out, int
     // at 512 / 1024 / 2048 workgroups; C5 jump (32768 x 256, image 35 KB) 61.6 / 65.6 / 73.9 us.
     int gcap = dp <= 128 ? 1024 : 512;
     if (const char* e = getenv("NFMC_FLOWB_GRID")) gcap = atoi(e) > 0 ? atoi(e) : gcap;
+    if (part && part->grid_cap < gcap) gcap = part->grid_cap;
     const int grid = (int)(tiles < gcap ? tiles : gcap);
+    if (tile_chains_out) *tile_chains_out = (int64_t)kWavesPerBlock * cpw;
     if (a.stats.sum_x && a.stats.scratch_bytes < (int64_t)grid * (2 * dp + kStatTail) * (int64_t)sizeof(double))
         return NFMC_ESCRATCH;
     if (check_defer(a.stats, dp, d)) return NFMC_EINVAL;
+    if (part && a.stats.sum_x) a.stats.scratch += (size_t)part->slab0 * (2 * dp + kStatTail);   // checked as the caller gave it
     int rc = NFMC_EUNSUPPORTED;
     switch (a.pot.kind) {
 #define NFMC_KIND_CASE(KIND, POT)                                                                    \

@@ -9,13 +9,15 @@
 //
 // One wave per workgroup, one chain per lane, the (64, d) tiles of the wave in LDS (flow_device.hpp).
 #include "mfma_device.hpp"
+#include "run_parts.hpp"
 
 namespace nfmc {
 
 constexpr int kFlowBlock = 64;
 
 // flow_b_kernels.hip: register-layout path for narrow conditioners
-int flow_mh_b_launch(const NfmcFlowMhArgs& a, hipStream_t st, int* grid_out, int* dp_out, bool dry);
+int flow_mh_b_launch(const NfmcFlowMhArgs& a, hipStream_t st, int* grid_out, int* dp_out, bool dry, const LaunchPart* part = nullptr,
+                     int64_t* tile_chains_out = nullptr);
 constexpr int kMaxSlots = 8;  // d <= 512 -> at most 8 coordinates per lane in the column-sum pass
 
 template <int HP>
@@ -418,16 +420,23 @@ extern "C" int nfmc_flow_mh_supported_f32(const NfmcFlowMhArgs* args) {
     return flow_mh_tile_lds(a.flow) <= kMaxLdsBytes ? NFMC_OK : NFMC_EUNSUPPORTED;
 }
 
-extern "C" int nfmc_flow_mh_steps_f32(const NfmcFlowMhArgs* args, nfmc_stream_t stream) {
-    if (!args) return NFMC_EINVAL;
-    NfmcFlowMhArgs a = *args;
+int64_t nfmc::flow_mh_tile_chains(const NfmcFlowMhArgs& a) {
+    int grid = 0, dp = 0;
+    int64_t tile = 0;
+    if (getenv("NFMC_FLOW_TILE_PATH") || check_flow_mh(a) || flow_mh_b_launch(a, nullptr, &grid, &dp, true, nullptr, &tile)) return 0;
+    return tile;
+}
+
+int nfmc::flow_mh_steps(const NfmcFlowMhArgs& args, hipStream_t st, const LaunchPart* part) {
+    NfmcFlowMhArgs a = args;
     int rc = check_flow_mh(a);
     if (rc) return rc;
     const int d = a.flow.d;
     int dp = padded_d(d);
-    hipStream_t st = (hipStream_t)stream;
+    nfmc_stream_t stream = (nfmc_stream_t)st;
     int grid = 0;
-    rc = getenv("NFMC_FLOW_TILE_PATH") ? NFMC_EUNSUPPORTED : flow_mh_b_launch(a, st, &grid, &dp, false);
+    rc = getenv("NFMC_FLOW_TILE_PATH") ? NFMC_EUNSUPPORTED : flow_mh_b_launch(a, st, &grid, &dp, false, part);
+    if (rc == NFMC_EUNSUPPORTED && part) return rc;   // the kernels below lay their slabs out from the start of the scratch
     if (rc == NFMC_EUNSUPPORTED && rng_rounds(a.rng) != 10) return NFMC_EUNSUPPORTED;
     if (rc == NFMC_EUNSUPPORTED && register_kernels_only(a.pot)) return NFMC_EUNSUPPORTED;
     if (rc == NFMC_EUNSUPPORTED && use_mfma_flow(&a.flow) && al16(a.x) && al16(a.samples.base)) {
@@ -460,4 +469,9 @@ extern "C" int nfmc_flow_mh_steps_f32(const NfmcFlowMhArgs* args, nfmc_stream_t 
         NFMC_HIP_CHECK_LAUNCH();
     }
     return NFMC_OK;
+}
+
+extern "C" int nfmc_flow_mh_steps_f32(const NfmcFlowMhArgs* args, nfmc_stream_t stream) {
+    if (!args) return NFMC_EINVAL;
+    return flow_mh_steps(*args, (hipStream_t)stream, nullptr);
 }

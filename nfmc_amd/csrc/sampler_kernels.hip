@@ -2,6 +2,9 @@
 // template instantiations live in sampler_{mala,hmc}_j{0,4,8}.hip (j = conditioner width of the optional
 // jump tail, 0 = none) and, for the kinds whose row in kPotKinds (common.hpp) says own_units, in a mala and an hmc
 // unit per kind, so they compile in parallel.
+#include <mutex>
+
+#include "run_parts.hpp"
 #include "sampler_impl.hpp"
 
 namespace nfmc {
@@ -305,8 +308,9 @@ extern "C" int64_t nfmc_tune_state_doubles(int32_t d) {
 // The part the two sampler entry points share, behind their own argument checks: layout, tile and grid arithmetic, the
 // scratch / defer / tune checks, then either the warmup loop (one launch + controller update per `every` transitions, all
 // of the call enqueued here) or one launch and the statistics finish.  launch(args, jd, c, jhp, fast, tiles, grid).
+// part: the call is one part of a split run (run_parts.hpp).
 template <class Args, class Launch>
-static int sampler_steps(const Args* args, hipStream_t st, Launch launch) {
+static int sampler_steps(const Args* args, hipStream_t st, Launch launch, const LaunchPart* part = nullptr) {
     Args a = *args;
     const int jhp = a.jump ? (a.jump->flow.n_hidden <= 4 ? 4 : 8) : 0;
     const Cfg c = choose_cfg(a.d, jhp > 0, pot_kind(a.pot.kind)->default_cfg_only);
@@ -316,11 +320,13 @@ static int sampler_steps(const Args* args, hipStream_t st, Launch launch) {
     const int cpw = kWave / c.lpc;
     const int64_t tiles = (a.n + (int64_t)kWavesPerBlock * cpw - 1) / ((int64_t)kWavesPerBlock * cpw);
     bool two_level = false;
-    const int grid = a.tune.state ? tune_grid(tiles, dp, a.stats.scratch_bytes, &two_level) : (int)(tiles < kMaxGrid ? tiles : kMaxGrid);
+    const int gcap = part ? part->grid_cap : kMaxGrid;
+    const int grid = a.tune.state ? tune_grid(tiles, dp, a.stats.scratch_bytes, &two_level) : (int)(tiles < gcap ? tiles : gcap);
     if (a.stats.sum_x && a.stats.scratch_bytes < (int64_t)grid * (2 * dp + kStatTail) * (int64_t)sizeof(double))
         return NFMC_ESCRATCH;
     if (check_defer(a.stats, dp, a.d)) return NFMC_EINVAL;
     if (int rc = check_tune(a, dp)) return rc;
+    if (part && a.stats.sum_x) a.stats.scratch += (size_t)part->slab0 * (2 * dp + kStatTail);   // checked as the caller gave it
     const JumpDev jd = jump_dev(a.jump);
     unsigned long long* jc = a.jump ? a.jump->counters : nullptr;
     a.jump = nullptr;  // host pointer: never dereferenced on the device
@@ -354,20 +360,168 @@ static int sampler_steps(const Args* args, hipStream_t st, Launch launch) {
     return NFMC_OK;
 }
 
-extern "C" int nfmc_mala_steps_f32(const NfmcMalaArgs* args, nfmc_stream_t stream) {
+static int mala_steps(const NfmcMalaArgs* args, hipStream_t st, const LaunchPart* part) {
     if (int rc = check_common(args)) return rc;
-    hipStream_t st = (hipStream_t)stream;
     const float sqrt2h = (float)sqrt(2.0 * (double)args->step_size);  // math.sqrt(2*step_size), langevin.py:75
     return sampler_steps(args, st, [=](const NfmcMalaArgs& a, const JumpDev& jd, Cfg c, int jhp, bool fast, int64_t tiles, int grid) {
         return launch_mala(a, jd, c, jhp, fast, tiles, grid, sqrt2h, st);
-    });
+    }, part);
+}
+
+static int hmc_steps(const NfmcHmcArgs* args, hipStream_t st, const LaunchPart* part) {
+    if (int rc = check_common(args)) return rc;
+    if (args->n_leapfrog <= 0) return NFMC_EINVAL;
+    return sampler_steps(args, st, [=](const NfmcHmcArgs& a, const JumpDev& jd, Cfg c, int jhp, bool fast, int64_t tiles, int grid) {
+        return launch_hmc(a, jd, c, jhp, fast, tiles, grid, st);
+    }, part);
+}
+
+extern "C" int nfmc_mala_steps_f32(const NfmcMalaArgs* args, nfmc_stream_t stream) {
+    return mala_steps(args, (hipStream_t)stream, nullptr);
 }
 
 extern "C" int nfmc_hmc_steps_f32(const NfmcHmcArgs* args, nfmc_stream_t stream) {
-    if (int rc = check_common(args)) return rc;
-    if (args->n_leapfrog <= 0) return NFMC_EINVAL;
+    return hmc_steps(args, (hipStream_t)stream, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------------
+// nfmc_jump_run_f32: the launches of a whole JumpNFMC.sample run, split into parts of chains on streams of their own.
+//
+// Nothing couples one chain to another in these kernels (the Philox streams are keyed by the global chain id, the
+// statistics are per-workgroup slabs), so jump i of a part depends on inner launch i of the same part only: with two parts
+// on two streams the jump of one -- a short kernel of one round of waves that stages a weight image and flushes statistics,
+// well short of the vector pipes' rate -- runs while the inner kernel of the other fills the SIMDs, and the launch
+// boundaries of one part fall inside kernels of the other.
+
+// The side streams of the current device: non-blocking, created on first use, kept for the life of the process.
+static int side_streams(int count, hipStream_t* out) {
+    constexpr int kMaxDevices = 64;
+    static std::mutex mu;
+    static hipStream_t streams[kMaxDevices][NFMC_JUMP_RUN_MAX_PARTS - 1] = {};
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev)) return (int)e;
+    if (dev < 0 || dev >= kMaxDevices) return NFMC_EUNSUPPORTED;
+    std::lock_guard<std::mutex> lock(mu);
+    for (int i = 0; i < count; ++i) {
+        if (!streams[dev][i])
+            if (hipError_t e = hipStreamCreateWithFlags(&streams[dev][i], hipStreamNonBlocking)) return (int)e;
+        out[i] = streams[dev][i];
+    }
+    return NFMC_OK;
+}
+
+// chains per workgroup tile of the sampler kernels at event size d (sampler_steps: jump-tail-free layout)
+static int64_t sampler_tile_chains(int d, int pot_kind_id) {
+    const PotKind* pk = pot_kind(pot_kind_id);
+    const Cfg c = choose_cfg(d, false, pk && pk->default_cfg_only);
+    return c.cpl ? (int64_t)kWavesPerBlock * (kWave / c.lpc) : 0;
+}
+
+template <class Args, class Steps>
+static int jump_run(const NfmcJumpRun& r, const Args& inner, hipStream_t st, Steps steps) {
+    const NfmcFlowMhArgs& jump = *r.jump;
+    const int64_t n = inner.n;
+    const int d = inner.d, K = r.n_inner, T = r.n_outer;
+    if (T <= 0 || K <= 0 || r.n_parts < 1 || r.n_parts > NFMC_JUMP_RUN_MAX_PARTS) return NFMC_EINVAL;
+    if (!inner.x || n <= 0 || d <= 0 || jump.x != inner.x || jump.n != n || jump.flow.d != d || !jump.logq) return NFMC_EINVAL;
+    if (jump.rng.seed != inner.rng.seed || jump.rng.chain_offset != inner.rng.chain_offset || jump.rng.rounds != inner.rng.rounds)
+        return NFMC_EINVAL;
+    // nothing a host would advance between the launches
+    if (inner.jump || inner.tune.state || inner.samples.base || jump.samples.base || inner.masks_out || jump.masks_out ||
+        inner.log_ratio_out || jump.log_ratio_out || inner.rng.replay_normals || inner.rng.replay_uniforms ||
+        jump.rng.replay_normals || jump.rng.replay_uniforms)
+        return NFMC_EINVAL;
+    if ((inner.stats.sum_x != nullptr) != (jump.stats.sum_x != nullptr)) return NFMC_EINVAL;
+    if (inner.stats.sum_x && (!inner.stats.defer || !jump.stats.defer || inner.stats.scratch != jump.stats.scratch)) return NFMC_EINVAL;
+
+    // parts: whole tiles of both kernels, so that every chain keeps its place in its tile (and its wave's partial sums)
+    int parts = r.n_parts;
+    int64_t m = n;
+    if (parts > 1) {
+        const int64_t ti = sampler_tile_chains(d, inner.pot.kind), tj = flow_mh_tile_chains(jump);
+        if (ti <= 0 || tj <= 0) {
+            parts = 1;   // the jump runs on kernels that take no part; the checks of the unsplit launches speak for the rest
+        } else {
+            const int64_t tile = ti > tj ? ti : tj, per = (n + parts - 1) / parts;
+            m = (per + tile - 1) / tile * tile;
+        }
+    }
+    const int share = (kMaxGrid + parts - 1) / parts;
+    int used = 0;   // parts with chains
+    while (used < parts && (int64_t)used * m < n) ++used;
+
+    // events[p], p < used - 1: the fork of part p + 1, recorded on part p's stream; events[used - 2 + p], p >= 1: the join of part p
+    hipStream_t streams[NFMC_JUMP_RUN_MAX_PARTS] = {st};
+    hipEvent_t events[2 * NFMC_JUMP_RUN_MAX_PARTS] = {};
+    const int n_events = used > 1 ? 2 * (used - 1) : 0;
+    if (used > 1) {
+        if (int rc = side_streams(used - 1, streams + 1)) return rc;
+        for (int p = 0; p < n_events; ++p)
+            if (hipError_t e = hipEventCreateWithFlags(&events[p], hipEventDisableTiming)) {
+                for (int q = 0; q < p; ++q) (void)hipEventDestroy(events[q]);
+                return (int)e;
+            }
+    }
+    // Fork.  Parts that start together stay in step -- their inner kernels run side by side, then their jumps do, and
+    // nothing is won -- so part p + 1 starts behind the first inner block of part p: the parts run a fraction of an
+    // iteration apart from then on, and the jump of one falls into the inner kernel of the others.  (NFMC_JUMP_STAGGER=0,
+    // for measurements: every part starts behind what the caller's stream held on entry.)
+    const char* stagger_env = getenv("NFMC_JUMP_STAGGER");
+    const bool stagger = !(stagger_env && atoi(stagger_env) == 0);
+
+    int rc = NFMC_OK;
+    for (int i = 0; i < T && !rc; ++i) {
+        const uint32_t base = inner.rng.step0 + (uint32_t)i * (uint32_t)(K + 1);
+        for (int p = 0; p < used && !rc; ++p) {
+            const int64_t lo = (int64_t)p * m, np = (n - lo < m ? n - lo : m);
+            const LaunchPart lp = {p * share, share < kMaxGrid - p * share ? share : kMaxGrid - p * share, n};
+            const LaunchPart* part = parts > 1 ? &lp : nullptr;
+            if (i == 0 && p > 0) {   // behind the fork event of the part before (a side stream has no other work: every call joins it)
+                if (hipError_t e = hipStreamWaitEvent(streams[p], events[p - 1], 0)) rc = (int)e;
+            }
+            if (i == 0 && p + 1 < used && !stagger && !rc)
+                if (hipError_t e = hipEventRecord(events[p], streams[p])) rc = (int)e;
+            for (int off = 0; off < K && !rc; off += NFMC_MAX_STEPS_PER_CALL) {
+                Args b = inner;
+                b.x = inner.x + lo * d;
+                b.n = np;
+                b.n_steps = K - off < NFMC_MAX_STEPS_PER_CALL ? K - off : NFMC_MAX_STEPS_PER_CALL;
+                b.rng.chain_offset = inner.rng.chain_offset + (uint64_t)lo;
+                b.rng.step0 = base + (uint32_t)off;
+                rc = steps(&b, streams[p], part);
+            }
+            // recorded also behind a failed enqueue: the next part's wait must find a recorded event
+            if (i == 0 && p + 1 < used && (stagger || rc)) {
+                hipError_t e = hipEventRecord(events[p], streams[p]);
+                if (e != hipSuccess && !rc) rc = (int)e;
+            }
+            if (rc) break;
+            NfmcFlowMhArgs j = jump;
+            j.x = jump.x + lo * d;
+            j.logq = jump.logq + lo;
+            j.n = np;
+            j.n_steps = 1;
+            j.logq_cached = 0;
+            j.rng.chain_offset = jump.rng.chain_offset + (uint64_t)lo;
+            j.rng.step0 = base + (uint32_t)K;
+            rc = flow_mh_steps(j, streams[p], part);
+        }
+    }
+
+    // join, also behind a failed enqueue: no side stream runs past the call
+    for (int p = 1; p < used; ++p) {
+        hipError_t e = hipEventRecord(events[used - 1 + p - 1], streams[p]);
+        if (e == hipSuccess) e = hipStreamWaitEvent(st, events[used - 1 + p - 1], 0);
+        if (e != hipSuccess && !rc) rc = (int)e;
+    }
+    for (int p = 0; p < n_events; ++p) (void)hipEventDestroy(events[p]);
+    return rc;
+}
+
+extern "C" int nfmc_jump_run_f32(const NfmcJumpRun* run, nfmc_stream_t stream) {
+    if (!run || !run->inner || !run->jump) return NFMC_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    return sampler_steps(args, st, [=](const NfmcHmcArgs& a, const JumpDev& jd, Cfg c, int jhp, bool fast, int64_t tiles, int grid) {
-        return launch_hmc(a, jd, c, jhp, fast, tiles, grid, st);
-    });
+    if (run->inner_kind == NFMC_INNER_MALA) return jump_run(*run, *(const NfmcMalaArgs*)run->inner, st, mala_steps);
+    if (run->inner_kind == NFMC_INNER_HMC) return jump_run(*run, *(const NfmcHmcArgs*)run->inner, st, hmc_steps);
+    return NFMC_EINVAL;
 }

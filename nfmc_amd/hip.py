@@ -112,6 +112,15 @@ class NfmcFlowMhArgs(C.Structure):
                 ('log_ratio_out', c_fp)]
 
 
+INNER_MALA, INNER_HMC = 0, 1
+JUMP_RUN_MAX_PARTS = 4
+
+
+class NfmcJumpRun(C.Structure):
+    _fields_ = [('inner_kind', C.c_int32), ('n_parts', C.c_int32), ('inner', c_fp), ('jump', C.POINTER(NfmcFlowMhArgs)),
+                ('n_outer', C.c_int32), ('n_inner', C.c_int32)]
+
+
 class NfmcNeutraHmcArgs(C.Structure):
     _fields_ = [('z', c_fp), ('n', C.c_int64), ('n_steps', C.c_int32), ('n_leapfrog', C.c_int32),
                 ('step_size', C.c_float), ('adjust', C.c_int32), ('inv_mass_diag', c_fp),
@@ -183,6 +192,7 @@ SYMBOLS = [
                                            C.POINTER(NfmcRng), c_fp]),
     ('nfmc_flow_mh_steps_f32', C.c_int, [C.POINTER(NfmcFlowMhArgs), c_fp]),
     ('nfmc_flow_mh_supported_f32', C.c_int, [C.POINTER(NfmcFlowMhArgs)]),
+    ('nfmc_jump_run_f32', C.c_int, [C.POINTER(NfmcJumpRun), c_fp]),
     ('nfmc_imh_parallel_supported_f32', C.c_int, [C.POINTER(NfmcFlowMhArgs)]),
     ('nfmc_imh_parallel_work_bytes', C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     ('nfmc_imh_parallel_f32', C.c_int, [C.POINTER(NfmcFlowMhArgs), c_fp, C.c_int64, c_fp]),

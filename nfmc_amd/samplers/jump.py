@@ -21,7 +21,7 @@ from ..flows import Flow, RealNVP
 from ..tuning import train_val_split
 from ..util import metropolis_acceptance_log_ratio
 from .common import Run, chunks, progress, resolve_target
-from .mcmc import HMC, MALA, MH, UHMC, ULA, TargetFailure, _guarded
+from .mcmc import HMC, MALA, MH, UHMC, ULA, Langevin, TargetFailure, _guarded
 
 
 @dataclass
@@ -101,8 +101,9 @@ def flow_mh_supported(run: Run, flow, pot, logq, adjusted=True) -> bool:
     return hip.supported(int(hip.lib().nfmc_flow_mh_supported_f32(C.byref(a))), 'nfmc_flow_mh_supported_f32')
 
 
-def launch_flow_mh(run: Run, flow, pot, logq, k, step0, cached, adjusted, stats_struct, samples=None,
-                   masks_out=None, log_ratio_out=None):
+def flow_mh_args(run: Run, flow, pot, logq, k, step0, cached, adjusted, stats_struct, samples=None, masks_out=None,
+                 log_ratio_out=None):
+    """NfmcFlowMhArgs of k flow-proposal transitions from transition `step0` (+ keep-alive references)."""
     a = hip.NfmcFlowMhArgs()
     st, _keep = flow.bijection.packed(run.dev)
     a.x, a.logq, a.n, a.n_steps = hip.ptr(run.x), hip.ptr(logq), run.n, k
@@ -115,8 +116,40 @@ def launch_flow_mh(run: Run, flow, pot, logq, k, step0, cached, adjusted, stats_
     a.samples = hip.store_struct(samples, k)
     a.masks_out = hip.ptr(masks_out, torch.uint8) if masks_out is not None else None
     a.log_ratio_out = hip.ptr(log_ratio_out) if log_ratio_out is not None else None
+    a._keep = _keep
+    return a
+
+
+def launch_flow_mh(run: Run, flow, pot, logq, k, step0, cached, adjusted, stats_struct, samples=None,
+                   masks_out=None, log_ratio_out=None):
+    a = flow_mh_args(run, flow, pot, logq, k, step0, cached, adjusted, stats_struct, samples, masks_out, log_ratio_out)
     with run.timed('flow_mh_steps'):
         hip.check(hip.lib().nfmc_flow_mh_steps_f32(C.byref(a), hip.stream()), 'nfmc_flow_mh_steps_f32')
+
+
+# Parts of a whole-run call (nfmc_jump_run_f32) by inner kind: (parts, fewest chains at which the run is split).  Measured
+# on the benchmark's C3 / C5 shapes and at 4096 chains; `JumpNFMC.jump_parts` or NFMC_JUMP_PARTS
+# override them.
+JUMP_PARTS = {hip.INNER_MALA: (2, 16384), hip.INNER_HMC: (2, 16384)}
+# outer iterations per whole-run call under a time limit: the clock is read between calls
+JUMP_RUN_SLICE = 16
+
+
+def launch_jump_run(run: Run, inner, flow, pot, logq, step0, n_outer, n_inner, n_parts, adjusted):
+    """`n_outer` outer iterations (n_inner inner transitions, then the jump) from transition `step0` in ONE call of the
+    library, which enqueues the launches of the loop in `JumpNFMC.sample` -- split into `n_parts` ranges of chains on
+    streams of their own, so that the jump of one range runs beside the inner kernel of another."""
+    n = run.n
+    k = min(n_inner, hip.MAX_STEPS_PER_CALL)
+    ia = inner._args(run, pot, k, step0, None, attempted=n * n_inner * n_outer)
+    ja = flow_mh_args(run, flow, pot, logq, 1, step0 + n_inner, False, adjusted,
+                      run.stats.struct(defer=True, attempted=n * n_outer, jump=True))
+    r = hip.NfmcJumpRun()
+    r.inner_kind = hip.INNER_HMC if isinstance(ia, hip.NfmcHmcArgs) else hip.INNER_MALA
+    r.inner = C.cast(C.pointer(ia), C.c_void_p)
+    r.jump = C.pointer(ja)
+    r.n_outer, r.n_inner, r.n_parts = n_outer, n_inner, n_parts
+    hip.check(hip.lib().nfmc_jump_run_f32(C.byref(r), hip.stream()), 'nfmc_jump_run_f32')
 
 
 def _flow_mh_probe_args(run: Run, flow, pot, logq, adjusted):
@@ -240,6 +273,9 @@ class JumpNFMC(Sampler):
     # launch does (measured 0.474 vs 0.45 ms per outer iteration at C3).
     fuse_jump_tail = False
 
+    # Parts of the whole-run call (launch_jump_run): None = NFMC_JUMP_PARTS, else the measured default (JUMP_PARTS)
+    jump_parts = None
+
     def __init__(self, event_shape, target, inner_sampler: Sampler, kernel: NFMCKernel = None,
                  params: JumpNFMCParameters = None):
         if kernel is None:
@@ -263,6 +299,18 @@ class JumpNFMC(Sampler):
             return flow.fit(x_train=x_train, x_val=x_val, **{'defer_check': True, **self.params.flow_fit_kwargs})
         flow.fit(x_train=x_train, x_val=x_val, **self.params.flow_fit_kwargs)
         return None
+
+    def _jump_parts(self, inner, n):
+        parts = self.jump_parts
+        if parts is None and os.environ.get('NFMC_JUMP_PARTS'):
+            parts = os.environ['NFMC_JUMP_PARTS']
+        if parts is None:
+            parts, n_min = JUMP_PARTS[hip.INNER_HMC if isinstance(inner, HMC) else hip.INNER_MALA]
+            return parts if n >= n_min else 1
+        parts = int(parts)
+        if not 1 <= parts <= hip.JUMP_RUN_MAX_PARTS:
+            raise ValueError('jump_parts must be 1 .. %d' % hip.JUMP_RUN_MAX_PARTS)
+        return parts
 
     def warmup(self, x0, show_progress: bool = True, time_limit_seconds=None) -> MCMCOutput:
         """jump.py:104-154: tune the inner sampler, then MLE-fit the flow on its samples (rollback on ValueError)."""
@@ -323,13 +371,28 @@ class JumpNFMC(Sampler):
 
         if tail_ok:
             probe()
+        # The rest of the run in one call of the library (launch_jump_run) once iteration 0 has gone through the loop
+        # below (its inner launch keeps the GPU busy while the host packs the flow): fused target and flow, nothing that
+        # needs the host between launches (refits, kept states, replayed noise, per-launch events, a progress bar)
+        whole_run = (pot is not None and not tail_ok and not self.params.fit_nf and store is None and run.replay is None
+                     and run.kernel_events is None and not show_progress and isinstance(inner, (Langevin, HMC))
+                     and os.environ.get('NFMC_STATS_DEFER', '1') != '0')
 
         t0 = time.time()
         done = 0
         bar = progress(show_progress, range(T), desc='Jump MCMC')
         for i in bar:
+            if i < done:   # covered by a whole-run call
+                continue
             if run.time_is_up(t0, time_limit_seconds):
                 break
+            if i > 0 and whole_run and fused:
+                ts = T - i if time_limit_seconds is None else min(JUMP_RUN_SLICE, T - i)
+                launch_jump_run(run, inner, flow, pot, logq, i * (K + 1), ts, K, self._jump_parts(inner, n),
+                                self.params.adjusted_jumps)
+                jump_target_calls += 2 * n * ts if self.params.adjusted_jumps else 0
+                done = i + ts
+                continue
             base = i * (K + 1)
             dense = fit_buf is not None   # inner states into the refit block (offered to the store afterwards), else straight into the store
             # ---- K inner transitions (jump.py:178); when the flow is narrow the jump rides at the end of

@@ -360,7 +360,10 @@ class Langevin(MetropolisSampler):
         per = 2 * n if self.params.adjustment else n  # langevin.py:116-120
         return per * k, per * k
 
-    def _launch(self, run, pot, k, step0, samples, masks_out=None, log_ratio_out=None, jump=None, rng=None, tune=None):
+    def _args(self, run, pot, k, step0, samples, masks_out=None, log_ratio_out=None, jump=None, rng=None, tune=None,
+              attempted=None):
+        """NfmcMalaArgs of a launch of k transitions (`attempted`: chain-transitions to book with deferred statistics when
+        the struct stands for more launches than one, samplers/jump.py: launch_jump_run)."""
         a = hip.NfmcMalaArgs()
         a.x, a.n, a.d, a.n_steps = hip.ptr(run.x), run.n, run.d, k
         a.step_size = float(self.kernel.step_size)
@@ -374,11 +377,17 @@ class Langevin(MetropolisSampler):
             a.stats = run.stats.struct()
             a.tune = tune.struct(getattr(tune, 'every', 0), k)
         else:
-            a.stats = run.stats.struct(defer=True, attempted=run.n * k, jump_attempted=run.n if jump is not None else 0)
+            a.stats = run.stats.struct(defer=True, attempted=run.n * k if attempted is None else attempted,
+                                       jump_attempted=run.n if jump is not None else 0)
         a.samples = hip.store_struct(samples, k + (1 if jump is not None else 0))
         a.masks_out = hip.ptr(masks_out, torch.uint8) if masks_out is not None else None
         a.log_ratio_out = hip.ptr(log_ratio_out) if log_ratio_out is not None else None
         a.jump = C.pointer(jump) if jump is not None else None
+        a._keep = imd   # the struct borrows its memory
+        return a
+
+    def _launch(self, run, pot, k, step0, samples, **kw):
+        a = self._args(run, pot, k, step0, samples, **kw)
         with run.timed('mala_steps'):
             hip.check(hip.lib().nfmc_mala_steps_f32(C.byref(a), hip.stream()), 'nfmc_mala_steps_f32')
 
@@ -553,7 +562,9 @@ class HMC(MetropolisSampler):
         calls = grads + (2 * n if self.params.adjustment else 0)
         return calls * k, grads * k
 
-    def _launch(self, run, pot, k, step0, samples, masks_out=None, log_ratio_out=None, jump=None, rng=None, tune=None):
+    def _args(self, run, pot, k, step0, samples, masks_out=None, log_ratio_out=None, jump=None, rng=None, tune=None,
+              attempted=None):
+        """NfmcHmcArgs of a launch of k trajectories (`attempted` as in Langevin._args)."""
         a = hip.NfmcHmcArgs()
         a.x, a.n, a.d, a.n_steps = hip.ptr(run.x), run.n, run.d, k
         a.step_size = float(self.kernel.step_size)
@@ -568,11 +579,17 @@ class HMC(MetropolisSampler):
             a.stats = run.stats.struct()
             a.tune = tune.struct(getattr(tune, 'every', 0), k)
         else:
-            a.stats = run.stats.struct(defer=True, attempted=run.n * k, jump_attempted=run.n if jump is not None else 0)
+            a.stats = run.stats.struct(defer=True, attempted=run.n * k if attempted is None else attempted,
+                                       jump_attempted=run.n if jump is not None else 0)
         a.samples = hip.store_struct(samples, k + (1 if jump is not None else 0))
         a.masks_out = hip.ptr(masks_out, torch.uint8) if masks_out is not None else None
         a.log_ratio_out = hip.ptr(log_ratio_out) if log_ratio_out is not None else None
         a.jump = C.pointer(jump) if jump is not None else None
+        a._keep = imd   # the struct borrows its memory
+        return a
+
+    def _launch(self, run, pot, k, step0, samples, **kw):
+        a = self._args(run, pot, k, step0, samples, **kw)
         with run.timed('hmc_steps'):
             hip.check(hip.lib().nfmc_hmc_steps_f32(C.byref(a), hip.stream()), 'nfmc_hmc_steps_f32')
 
