@@ -40,6 +40,9 @@ constexpr uint32_t kTagNoise = 0, kTagAccept = 1, kTagLatent = 2, kTagJump = 3;
 // UC1: the caller guarantees c1 is wave-uniform (the step of a sampler transition).  Round 0's c1 ^ k0 is then one s_xor
 // on the SALU and the word one VOP2 v_xor_b32 with that SGPR: v_bitop3_b32 is VOP3, which reads one SGPR at most on gfx9,
 // so with c1 and k0 both in SGPRs it needs a v_mov first.  Same bits either way.
+// Measured and not kept: the round keys as per-lane copies in VGPRs.  Alone, v_bitop3_b32 issues 12 % faster without an
+// SGPR operand (tools/ubench.hip), but in mala_kernel's step loop the 19 extra VGPRs (74 -> 92) bought nothing: 224-226 us
+// per launch with them against 221 us without, at the C3 shape.
 template <int R, bool UC1 = false>
 __device__ __forceinline__ uint4 philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
 #pragma unroll
@@ -133,18 +136,63 @@ __device__ __forceinline__ float dpp_add(float v) {
 // Per-lane select with the condition in an SGPR pair (mask = __ballot(cond)).  Measured on gfx950
 // (tools/ubench.hip, profiles/): the VOP2 form the compiler shrinks `c ? a : b` to, v_cndmask_b32_e32 with the
 // implicit vcc, issues at 6.6x a v_fma (~22 cycles per wave instruction); the VOP3 form is 1.3x.  Hot loops
-// that select a whole register row on one condition (the Metropolis update) use this.
+// that select a whole register row on one condition (the Metropolis update) use this; the exact-fit Gaussian MALA loop,
+// which only ever replaces a row by the proposal, uses plain moves under the mask instead (assign_where below).
 __device__ __forceinline__ float select_f32(uint64_t mask, float if_true, float if_false) {
     float r;
     asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(if_false), "v"(if_true), "s"(mask));
     return r;
 }
 
-template <int LPC>
+// x <- xp and sq <- sqp in the lanes of `mask`, as plain moves with exec narrowed to the mask: a v_mov_b32 issues in about
+// half the time of the VOP3 select (tools/ubench.hip).  exec is saved, narrowed and restored inside ONE asm statement (the
+// compiler never sees it changed), and narrowed by AND, so lanes that were off stay off.  The same values land in the same
+// lanes as with select_f32.  One statement holds every move where the operand limit of an asm allows it (CPL = 8: the
+// benchmark's layout); otherwise one statement per four registers.
+#define NFMC_MOV4(I) \
+    "v_mov_b32 %[x" #I "0], %[p" #I "0]\n v_mov_b32 %[x" #I "1], %[p" #I "1]\n v_mov_b32 %[x" #I "2], %[p" #I "2]\n v_mov_b32 %[x" #I "3], %[p" #I "3]\n"
+template <int CPL>
+__device__ __forceinline__ void assign_where(uint64_t mask, float (&x)[CPL], const float (&xp)[CPL], float& sq, float sqp) {
+    static_assert(CPL % 4 == 0, "whole register quads");
+    uint64_t saved;
+    if constexpr (CPL == 8) {
+        asm("s_and_saveexec_b64 %[sv], %[m]\n" NFMC_MOV4(a) NFMC_MOV4(b) "v_mov_b32 %[sq], %[sp]\n"
+            "s_mov_b64 exec, %[sv]"
+            : [xa0] "+v"(x[0]), [xa1] "+v"(x[1]), [xa2] "+v"(x[2]), [xa3] "+v"(x[3]), [xb0] "+v"(x[4]), [xb1] "+v"(x[5]),
+              [xb2] "+v"(x[6]), [xb3] "+v"(x[7]), [sq] "+v"(sq), [sv] "=&s"(saved)
+            : [pa0] "v"(xp[0]), [pa1] "v"(xp[1]), [pa2] "v"(xp[2]), [pa3] "v"(xp[3]), [pb0] "v"(xp[4]), [pb1] "v"(xp[5]),
+              [pb2] "v"(xp[6]), [pb3] "v"(xp[7]), [sp] "v"(sqp), [m] "s"(mask)
+            : "scc");
+    } else {
+#pragma unroll
+        for (int i = 0; i < CPL; i += 4)
+            asm("s_and_saveexec_b64 %[sv], %[m]\n" NFMC_MOV4(a) "s_mov_b64 exec, %[sv]"
+                : [xa0] "+v"(x[i]), [xa1] "+v"(x[i + 1]), [xa2] "+v"(x[i + 2]), [xa3] "+v"(x[i + 3]), [sv] "=&s"(saved)
+                : [pa0] "v"(xp[i]), [pa1] "v"(xp[i + 1]), [pa2] "v"(xp[i + 2]), [pa3] "v"(xp[i + 3]), [m] "s"(mask)
+                : "scc");
+        asm("s_and_saveexec_b64 %[sv], %[m]\n v_mov_b32 %[sq], %[sp]\n s_mov_b64 exec, %[sv]"
+            : [sq] "+v"(sq), [sv] "=&s"(saved)
+            : [sp] "v"(sqp), [m] "s"(mask)
+            : "scc");
+    }
+}
+#undef NFMC_MOV4
+
+// v + (v of lane i ^ 7 within each 8 lanes), the row_half_mirror stage of group_allreduce, as ONE v_add_f32_dpp like
+// the two quad_perm stages: the compiler's own lowering of dpp_add<0x141> is v_mov 0 + v_mov_dpp + v_add.  The same add
+// of the same two values.  The s_nop covers the two wait states between a VALU write of v and a DPP read of it.
+__device__ __forceinline__ float dpp_add_half_mirror(float v) {
+    float r;
+    asm("s_nop 1\n v_add_f32_dpp %0, %1, %1 row_half_mirror row_mask:0xf bank_mask:0xf" : "=v"(r) : "v"(v));
+    return r;
+}
+
+// HM_ASM: the 8-lane stage through dpp_add_half_mirror (off by default: every other caller compiles as before)
+template <int LPC, bool HM_ASM = false>
 __device__ __forceinline__ float group_allreduce(float v) {
     if constexpr (LPC >= 2) v = dpp_add<0xB1>(v);   // quad_perm [1,0,3,2]  : lane ^ 1
     if constexpr (LPC >= 4) v = dpp_add<0x4E>(v);   // quad_perm [2,3,0,1]  : lane ^ 2
-    if constexpr (LPC >= 8) v = dpp_add<0x141>(v);  // row_half_mirror      : i <-> 7 - i
+    if constexpr (LPC >= 8) v = HM_ASM ? dpp_add_half_mirror(v) : dpp_add<0x141>(v);  // row_half_mirror : i <-> 7 - i
     if constexpr (LPC >= 16) v = dpp_add<0x140>(v); // row_mirror           : i <-> 15 - i
     if constexpr (LPC >= 32) v += __shfl_xor(v, 16, kWave);
     if constexpr (LPC >= 64) v += __shfl_xor(v, 32, kWave);

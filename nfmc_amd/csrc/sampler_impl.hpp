@@ -345,16 +345,18 @@ __global__ void __launch_bounds__(kBlock, NFMC_WPE) mala_kernel(NfmcMalaArgs a, 
             // combined bool went through a VGPR 0/1 and a compare back)
             uint64_t am = live;
             if (adjust) {
-                lr = group_allreduce<LPC>(lr);
+                // exact-fit path: the 8-lane stage as one DPP add (dpp_add_half_mirror), the same sum
+                lr = group_allreduce<LPC, Pot<CPL, LPC, FAST>::kQuadratic && FAST>(lr);
                 const float ln_u = au.draw(a.rng, gchain, row, n, g, s);
                 am &= __ballot(ln_u < lr);  // NaN -> reject (langevin.py:106, mh.py:59)
                 n_bad += (uint32_t)__popcll(__ballot(!(fabsf(lr) <= 3.0e38f)) & live & leaders);
             }
             n_acc += (uint32_t)__popcll(am & leaders);
-            if constexpr (Pot<CPL, LPC, FAST>::kQuadratic && FAST) sq = select_f32(am, sq_prop, sq);
+            // mcmc/base.py:77.  Exact-fit path: x and the carried |x|^2 as moves under the accept mask (assign_where)
+            if constexpr (Pot<CPL, LPC, FAST>::kQuadratic && FAST) assign_where<CPL>(am, x, xp, sq, sq_prop);
 #pragma unroll
             for (int i = 0; i < CPL; ++i) {
-                x[i] = select_f32(am, xp[i], x[i]);  // mcmc/base.py:77
+                if constexpr (!(Pot<CPL, LPC, FAST>::kQuadratic && FAST)) x[i] = select_f32(am, xp[i], x[i]);
                 const float xs = shift(x, i);
                 sx[i] += xs;
                 sxx[i] = fmaf(xs, xs, sxx[i]);

@@ -69,7 +69,17 @@ BENCH_KERNEL(k_bitop3, asm volatile("v_bitop3_b32 %0, %0, %1, %2 bitop3:0x96\n v
 BENCH_KERNEL(k_bitop3_s, asm volatile("v_bitop3_b32 %0, %0, %1, %4 bitop3:0x96\n v_bitop3_b32 %1, %1, %2, %4 bitop3:0x96\n v_bitop3_b32 %2, %2, %3, %4 bitop3:0x96\n v_bitop3_b32 %3, %3, %0, %4 bitop3:0x96" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "s"((uint32_t)sm));)
 BENCH_KERNEL(k_xor_pair, asm volatile("v_xor_b32 %0, %0, %1\n v_xor_b32 %0, %4, %0\n v_xor_b32 %2, %2, %3\n v_xor_b32 %2, %4, %2" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "s"((uint32_t)sm));)
 
-struct Ent { const char* name; void (*fn)(uint32_t*, int); };
+// forms of the MALA step loop's update on acceptance and of its 8-lane reduction: a register pair moved by one
+// v_pk_mov_b32; plain moves under an exec mask that one asm statement sets and restores (4 moves, and the 9 of the (8, 8)
+// layout's x and |x|^2, per pair of exec writes: ns per MOVE, the two SALU writes included); the row_half_mirror add
+BENCH_KERNEL(k_pk_mov, asm volatile("v_pk_mov_b32 %0, %1, %1 op_sel:[0,1]\n v_pk_mov_b32 %1, %2, %2 op_sel:[0,1]\n v_pk_mov_b32 %2, %3, %3 op_sel:[0,1]\n v_pk_mov_b32 %3, %0, %0 op_sel:[0,1]" : "+v"(pa), "+v"(pb), "+v"(pc), "+v"(pd));)
+BENCH_KERNEL(k_mov_exec4, uint64_t sv; asm volatile("s_and_saveexec_b64 %4, %5\n v_mov_b32 %0, %1\n v_mov_b32 %1, %2\n v_mov_b32 %2, %3\n v_mov_b32 %3, %0\n s_mov_b64 exec, %4" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "=&s"(sv) : "s"(sm) : "scc");)
+BENCH_KERNEL(k_mov_exec9, uint64_t sv; asm volatile("s_and_saveexec_b64 %8, %9\n v_mov_b32 %0, %1\n v_mov_b32 %1, %2\n v_mov_b32 %2, %3\n v_mov_b32 %3, %0\n v_mov_b32 %4, %5\n v_mov_b32 %5, %6\n v_mov_b32 %6, %7\n v_mov_b32 %7, %4\n v_mov_b32 %0, %4\n s_mov_b64 exec, %8" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h), "=&s"(sv) : "s"(sm) : "scc");)
+BENCH_KERNEL(k_pk_mov_exec5, uint64_t sv; asm volatile("s_and_saveexec_b64 %5, %6\n v_pk_mov_b32 %0, %1, %1 op_sel:[0,1]\n v_pk_mov_b32 %1, %2, %2 op_sel:[0,1]\n v_pk_mov_b32 %2, %3, %3 op_sel:[0,1]\n v_pk_mov_b32 %3, %0, %0 op_sel:[0,1]\n v_mov_b32 %4, %4\n s_mov_b64 exec, %5" : "+v"(pa), "+v"(pb), "+v"(pc), "+v"(pd), "+v"(a), "=&s"(sv) : "s"(sm) : "scc");)
+BENCH_KERNEL(k_dpp_rhm, asm volatile("v_add_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n v_add_f32_dpp %1, %1, %1 row_half_mirror row_mask:0xf bank_mask:0xf\n v_add_f32_dpp %2, %2, %2 row_half_mirror row_mask:0xf bank_mask:0xf\n v_add_f32_dpp %3, %3, %3 row_half_mirror row_mask:0xf bank_mask:0xf" : "+v"(fa), "+v"(fb), "+v"(fc), "+v"(fd));)
+
+// instructions a body issues where that is not 4 (the rate is per REP / 4 bodies of 4: scaled in main)
+struct Ent { const char* name; void (*fn)(uint32_t*, int); int per_body = 4; };
 
 int main() {
     uint32_t* out;
@@ -85,7 +95,11 @@ int main() {
                   {"v_pk_add_f32", k_pk_add}, {"v_and_or_b32", k_and_or}, {"v_mul_f32", k_mul_f32}, {"v_cos_f32", k_cos},
                   {"v_fmac_f32(e32)", k_fmac_e32}, {"cndmask e64 vcc", k_cndmask_e64vcc}, {"cndmask e32 indep", k_cndmask_ind}, {"cndmask e32 vcc set", k_cndmask_setvcc},
                   {"v_bitop3_b32", k_bitop3}, {"v_bitop3_b32(sgpr)", k_bitop3_s}, {"v_xor x2 (dependent pair, sgpr)", k_xor_pair},
-                  {"v_add_f32", k_add_f32}, {"v_mov_b32", k_mov}, {"v_fma_f32 (4 distinct regs)", k_fma4}};
+                  {"v_add_f32", k_add_f32}, {"v_mov_b32", k_mov}, {"v_fma_f32 (4 distinct regs)", k_fma4},
+                  {"v_pk_mov_b32", k_pk_mov}, {"v_mov_b32 x4 under saved exec", k_mov_exec4},
+                  {"v_mov_b32 x9 under saved exec", k_mov_exec9, 9},
+                  {"v_pk_mov_b32 x4 + v_mov under saved exec", k_pk_mov_exec5, 5},
+                  {"v_add_f32_dpp row_half_mirror", k_dpp_rhm}};
     hipEvent_t e0, e1;
     hipEventCreate(&e0);
     hipEventCreate(&e1);
@@ -104,7 +118,7 @@ int main() {
             if (ms < best) best = ms;
         }
         // wave-instructions per SIMD: grid*4 waves / 1024 SIMDs * iters * REP
-        const double winstr = (double)grid * 4 / 1024.0 * iters * REP;
+        const double winstr = (double)grid * 4 / 1024.0 * iters * (REP / 4) * e.per_body;
         const double ns_per = best * 1e6 / winstr;
         if (base == 0) base = ns_per;
         printf("%-18s %8.3f ms  %6.3f ns/wave-instr/SIMD  = %5.2f x v_fma\n", e.name, best, ns_per, ns_per / base);
