@@ -570,7 +570,10 @@ int nfmc_philox_uniforms_f32(const NfmcRng* rng, int32_t tag, int64_t n, float* 
  * (ea0 log-scale, ea0 shift, ea1 log-scale, ea1 shift; d4 = d rounded up to 4 floats each) -- and `flow`'s pointers must be
  * views of it (weights = params, ea0_log_scale = params + ea_off, ...), so the sampling kernels see every step at once.
  * Shapes: affine / additive couplings (n_bins = 0), one or two hidden layers; n_hidden <= 8 at d <= 512, n_hidden 9..32 at
- * d <= 256, n_hidden 33..128 at d = 64 / 128 (nfmc_flow_fit_supported_f32); other flows are trained by the host package's torch path.
+ * d <= 256, n_hidden 33..128 at d = 64 / 128; rational-quadratic spline couplings (n_bins = 8, `spline_bound` > 0: W3 holds
+ * 23 d_b rows, target-major, and b3 as many entries; layer_stride >= nfmc_coupling_layer_floats(d, n_hidden, n_hidden_layers, 8)
+ * and a multiple of 4, `params` 16-byte aligned) with n_hidden <= 8 at d <= 256, both losses, on the (row, target)-pair kernel
+ * of csrc/fit_rqs.hip (nfmc_flow_fit_supported_f32); other flows are trained by the host package's torch path.
  * Conditioners of width <= 8 (every default flow) run on the row-per-wave kernel (csrc/fit_rows.hpp: up to 1024 waves per
  * launch); it needs `params` 16-byte aligned and layer_stride, ea_off multiples of 4 floats (NFMC_EALIGN otherwise). */
 typedef struct {
@@ -634,7 +637,8 @@ int nfmc_flow_fit_supported_f32(const NfmcRealNVP* flow);
 int64_t nfmc_flow_fit_partial_floats(int64_t n, int64_t n_params);
 /* Workspace of a fit of `flow` on n batch rows (+ n_val validation rows) with a trainable vector of n_params floats:
  * returns the bytes of NfmcFlowFit.scratch (0 for conditioners of width <= 32) and stores the floats `partial` must hold
- * (one slab of n_params + 4 floats per workgroup of the gradient launch).  Conditioners of width 33..128 are trained at
+ * (one slab of n_params + 4 floats per workgroup of the gradient launch; for spline couplings the launch is capped so that
+ * the slabs never exceed 64 MiB).  Conditioners of width 33..128 are trained at
  * d = 64 / 128 (the shapes of the register-resident matrix-core kernels) with the trainable vector in the matrix-core blob
  * layout (csrc/mfma_device.hpp: every matrix in both orientations; the gradient kernel writes both slots, AdamW keeps them
  * equal), layer_stride >= nfmc_realnvp_layer_floats(d, n_hidden, n_hidden_layers) and a multiple of 4. */

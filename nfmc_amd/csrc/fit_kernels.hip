@@ -23,8 +23,11 @@
 // up to 1024 waves per launch); the row-per-lane kernel below stays for widths 16 / 32.  The epoch loop's bookkeeping (best
 // validation loss, best weights, early stopping, divergence) moved into the fold kernel, so a run of epochs is enqueued
 // without a host round trip per epoch (nfmc_flow_fit_epochs_f32).
+// Spline couplings ('c-rqnsf', conditioner width <= 8, d <= 256) take the (row, target)-pair gradient kernel of fit_rqs.hip;
+// the fold kernel below is shared.
 #include "fit_rows.hpp"
 #include "fit_mfma.hpp"
+#include "fit_rqs.hpp"
 
 namespace nfmc {
 
@@ -623,15 +626,21 @@ static bool fit_rows_shape(const NfmcRealNVP* f, int64_t n_params, int* hp_out, 
 
 // trainable floats of a flow in the fit's layout with the tightest packing (what nfmc_flow_fit_supported_f32 assumes)
 static int64_t fit_min_params(const NfmcRealNVP* f) {
-    const int64_t stride = (nfmc_coupling_layer_floats(f->d, f->n_hidden, f->n_hidden_layers, 0) + 3) / 4 * 4;
+    const int64_t stride = (nfmc_coupling_layer_floats(f->d, f->n_hidden, f->n_hidden_layers, f->n_bins) + 3) / 4 * 4;
     const int64_t d4 = (f->d + 3) / 4 * 4;
     return (int64_t)(f->n_coupling > 0 ? f->n_coupling : 1) * stride + 4 * d4;
 }
 
 static bool fit_wide(const NfmcRealNVP* f);
 static int64_t mfma_layer_floats_of(const NfmcRealNVP& f) { return nfmc_realnvp_layer_floats(f.d, f.n_hidden, f.n_hidden_layers); }
+// spline couplings ('c-rqnsf'): the (row, target)-pair kernel of fit_rqs.hip, conditioner width <= 8 (every default), d <= 256
+static bool fit_spline(const NfmcRealNVP* f) {
+    return f && f->n_bins == kRqsBins && f->d > 0 && f->d <= 256 && f->n_coupling >= 0 && f->n_hidden > 0 && f->n_hidden <= 8 &&
+           f->n_hidden_layers >= 1 && f->n_hidden_layers <= 2;
+}
+
 static bool fit_supported(const NfmcRealNVP* f) {
-    if (fit_wide(f)) return true;
+    if (fit_wide(f) || fit_spline(f)) return true;
     if (!f || f->n_bins != 0 || f->d <= 0 || f->d > 512 || f->n_coupling < 0) return false;
     if (f->n_hidden <= 0 || f->n_hidden > 32 || f->n_hidden_layers < 1 || f->n_hidden_layers > 2) return false;
     const int hp = nfmc_realnvp_padded_hidden(f->n_hidden);
@@ -663,6 +672,10 @@ extern "C" int64_t nfmc_flow_fit_workspace(const NfmcRealNVP* flow, int64_t n, i
                                            int64_t* partial_floats) {
     if (partial_floats) *partial_floats = 0;
     if (!flow || n <= 0 || n_val < 0 || n_params <= 0 || !fit_supported(flow)) return 0;
+    if (fit_spline(flow)) {
+        if (partial_floats) *partial_floats = (int64_t)fit_rqs_grid(n, n_val, n_params) * (n_params + kFitTail);
+        return 0;
+    }
     if (!fit_wide(flow)) {
         if (partial_floats) *partial_floats = nfmc_flow_fit_partial_floats(n, n_params);
         return 0;
@@ -718,6 +731,29 @@ static int fit_call(const NfmcFlowFit* fit, const NfmcPotential* pot, const floa
         a.ck = fit->scratch;
         a.run_state = state_in;
         const int rc = fit_mfma_launch(pot != nullptr, a, grid, st);
+        if (rc != 0) return rc;
+    } else if (fit_spline(&f)) {
+        if ((f.layer_stride & 3) != 0 || (reinterpret_cast<uintptr_t>(fit->params) & 15) != 0) return NFMC_EALIGN;   // 16-byte W3 loads
+        const int64_t tiles = (n_train + kRqRows - 1) / kRqRows, vtiles = (nv + kRqRows - 1) / kRqRows;
+        grid = fit_rqs_grid(n_train, nv, fit->n_params);
+        grad_slabs = (int)(tiles < grid ? tiles : grid);   // workgroups beyond the batch tiles never write gradient entries
+        if (fit->partial_floats < (int64_t)grid * pstride) return NFMC_ESCRATCH;
+        FitRqsArgs a;
+        a.f = f;
+        a.pot = p0;
+        a.x = x;
+        a.n = n_train;
+        a.xv = fit->x_val;
+        a.nv = nv;
+        a.partial = fit->partial;
+        a.pstride = pstride;
+        a.ea_off = fit->ea_off;
+        a.d4 = d4;
+        a.n_params = fit->n_params;
+        a.tiles = tiles;
+        a.vtiles = vtiles;
+        a.run_state = state_in;
+        const int rc = fit_rqs_launch(pot != nullptr, hp, a, grid, st);
         if (rc != 0) return rc;
     } else if (fit_rows_shape(&f, fit->n_params, &rhp, &rch)) {
         if ((f.layer_stride & 3) != 0 || (fit->ea_off & 3) != 0 || (reinterpret_cast<uintptr_t>(fit->params) & 15) != 0)
@@ -811,6 +847,8 @@ static int fit_check(const NfmcFlowFit* fit, const NfmcPotential* pot, const flo
     if (!fit->params || !fit->adam_m || !fit->adam_v || !fit->partial || !fit->status) return NFMC_EINVAL;
     if (!fit_supported(&f)) return NFMC_EUNSUPPORTED;
     if (fit_wide(&f) && f.layer_stride < mfma_layer_floats_of(f)) return NFMC_EINVAL;
+    if (fit_spline(&f) && (f.layer_stride < nfmc_coupling_layer_floats(f.d, f.n_hidden, f.n_hidden_layers, f.n_bins) || !(f.spline_bound > 0.f)))
+        return NFMC_EINVAL;
     if (pot && pot->kind != NFMC_POT_QUADRATIC && pot->kind != NFMC_POT_FUNNEL) return NFMC_EUNSUPPORTED;
     const int d4 = (f.d + 3) / 4 * 4;
     if (fit->ea_off < (int64_t)f.n_coupling * f.layer_stride || fit->n_params < fit->ea_off + 4 * d4) return NFMC_EINVAL;

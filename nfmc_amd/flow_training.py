@@ -8,8 +8,10 @@ surface nfmc passes (`early_stopping`, `early_stopping_threshold`, `keep_best_we
 `fit` of a RealNVP / NICE flow with a narrow conditioner (n_hidden <= 32, d <= 256: every default flow) runs on the device:
 `DeviceFit` drives `nfmc_flow_fit_step_f32` (csrc/fit_kernels.hip: hand-written reverse sweep with weight gradients +
 fused AdamW), two launches per epoch; so does `variational_fit` when the caller knows the target as a closed-form potential
-(`potential=`, which the samplers pass).  Everything else -- spline couplings, wide conditioners, mini-batches, arbitrary
-Python targets -- evaluates the same spec with differentiable torch ops (on the GPU when there is one).
+(`potential=`, which the samplers pass).  Spline couplings ('c-rqnsf') with n_hidden <= 8 at d <= 256 (every default spline
+flow in that range) take the same path through the (row, target)-pair kernel of csrc/fit_rqs.hip.  Everything else -- wider
+spline conditioners, splines beyond d = 256, mini-batches, arbitrary Python targets -- evaluates the same spec with
+differentiable torch ops (on the GPU when there is one).
 None of it is on the sampling path: `sample()` never calls into it unless `warmup=True` / `fit_nf=True`.
 """
 import math
@@ -200,7 +202,8 @@ class DeviceFit:
         self.H, self.nhl = max(bijection.n_hidden, self.min_hidden), bijection.n_hidden_layers
         self.hp = int(lib.nfmc_realnvp_padded_hidden(self.H))
         # layer stride rounded to 16 bytes: the row-per-wave kernel reads the staged blob with 16-byte LDS loads
-        self.layer_stride = (int(lib.nfmc_coupling_layer_floats(d, self.H, self.nhl, 0)) + 3) // 4 * 4
+        self.n_bins = int(bijection.n_bins)
+        self.layer_stride = (int(lib.nfmc_coupling_layer_floats(d, self.H, self.nhl, self.n_bins)) + 3) // 4 * 4
         self.d4 = (d + 3) // 4 * 4
         self.ea_off = (max(1, bijection.n_coupling * self.layer_stride) + 3) // 4 * 4
         self.n_params = self.ea_off + 4 * self.d4
@@ -250,6 +253,7 @@ class DeviceFit:
         fitter = bijection.__dict__.get('_device_fit')
         if (fitter is None or fitter.dev != device or fitter.bij is not bijection or fitter.H_true != bijection.n_hidden
                 or fitter.min_hidden != int(bijection.default_min_hidden()) or fitter.nhl != bijection.n_hidden_layers or fitter.d != bijection.d
+                or fitter.n_bins != int(bijection.n_bins)
                 or fitter.ea_off < bijection.n_coupling * fitter.layer_stride):
             fitter = cls(bijection, device, n_rows, lr)
             bijection.__dict__['_device_fit'] = fitter
@@ -272,15 +276,16 @@ class DeviceFit:
     def _struct(self, vec):
         hip, o, d4, bij = self.hip, self.ea_off, self.d4, self.bij
         view = lambda k: hip.ptr(vec[o + k * d4:o + k * d4 + self.d])
-        return hip.NfmcRealNVP(self.d, bij.n_coupling, self.H, self.nhl, float(bij.min_scale), 0, view(0), view(1), view(2),
-                               view(3), hip.ptr(vec), self.layer_stride, float(bij.spline_bound), 0)
+        return hip.NfmcRealNVP(self.d, bij.n_coupling, self.H, self.nhl, float(bij.min_scale), self.n_bins, view(0), view(1),
+                               view(2), view(3), hip.ptr(vec), self.layer_stride, float(bij.spline_bound), 0)
 
     def _layout(self, bijection):
         """[(parameter tensor, offset in the vector, rows, cols, vector stride of a row, of a column)] in the VALU blob
         layout (include/nfmc_hip.h: W1T (d_a, HP) | b1 | [WhT (HP, HP) | bh] | W3 (2 d_b, HP) | b3 per coupling layer, then
-        the four ElementwiseAffine vectors at ea_off)."""
+        the four ElementwiseAffine vectors at ea_off).  Spline couplings: W3 has (3K - 1) d_b rows, target-major, b3 as many."""
         H, hp, d = self.H_true, self.hp, self.d
         d_a, d_b = d // 2, d - d // 2
+        out_rows = (3 * self.n_bins - 1) * d_b if self.n_bins else 2 * d_b
         out = []
         if self.wide:
             # W1 (HP, d_a) | W1T (d_a, HP) | b1 | [Wh (HP, HP) | WhT | bh] | W3 (2 d_b, HP) | W3T (HP, 2 d_b) | b3: every Linear
@@ -309,9 +314,9 @@ class DeviceFit:
                 cur += hp * hp
                 out.append((l.bias, cur, 1, H, 0, 1))
                 cur += hp
-            out.append((lin[-1].weight, cur, 2 * d_b, H, hp, 1))        # W3 keeps (out, in)
-            cur += 2 * d_b * hp
-            out.append((lin[-1].bias, cur, 1, 2 * d_b, 0, 1))
+            out.append((lin[-1].weight, cur, out_rows, H, hp, 1))       # W3 keeps (out, in)
+            cur += out_rows * hp
+            out.append((lin[-1].bias, cur, 1, out_rows, 0, 1))
         ea0, ea1 = bijection.layers[0], bijection.layers[-1]
         for k, t in enumerate((ea0.log_scale, ea0.shift, ea1.log_scale, ea1.shift)):
             out.append((t, self.ea_off + k * self.d4, 1, d, 0, 1))
@@ -356,12 +361,13 @@ class DeviceFit:
         from . import hip
         from .flows import RealNVP
         import ctypes as C
-        if not isinstance(bijection, RealNVP) or bijection.n_bins != 0 or device.type != 'cuda':
+        if not isinstance(bijection, RealNVP) or device.type != 'cuda':
             return False
         if bijection.n_coupling < 1 or any(p.device != device for p in bijection.parameters()):
             return False
         st = hip.NfmcRealNVP(bijection.d, bijection.n_coupling, bijection.n_hidden, bijection.n_hidden_layers,
-                             float(bijection.min_scale), 0, None, None, None, None, None, 0, 0.0, 0)   # dimensions only
+                             float(bijection.min_scale), int(bijection.n_bins), None, None, None, None, None, 0,
+                             float(bijection.spline_bound), 0)   # dimensions only
         return bool(hip.lib().nfmc_flow_fit_supported_f32(C.byref(st)))
 
     def set_validation(self, xv):

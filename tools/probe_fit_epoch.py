@@ -1,6 +1,12 @@
 """One epoch of the device fit at the refit shapes (profiles/r04_refit.txt): d, rows, validation rows -> microseconds per
 epoch (gradient launch + fold launch, 200 epochs enqueued back to back, HIP events), the shuffled split of the refit buffer,
-and a whole `Flow.fit(n_epochs=2)` call as the refit of jump.py:193-201 issues it."""
+and a whole `Flow.fit(n_epochs=2)` call as the refit of jump.py:193-201 issues it.
+
+    python tools/probe_fit_epoch.py spline {rkl24|ml64|ml256}
+
+times one shape of the spline ('c-rqnsf') fit instead, in one process: the median epoch of the device path (gradient + fold
+launch, HIP events around every epoch) and of the eager torch loop it replaces (flow_training._loop's epoch, wall clock with
+the loop's own read of the loss), 60 epochs each after 5 warm ones (profiles/r08_spline_fit.txt)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -23,7 +29,76 @@ def ev_ms(fn, reps=5):
     return best
 
 
+SPLINE_CASES = {  # d, batch rows, validation rows, reverse KL to SumOfSquares
+    'rkl24': (24, 1000, 0, True),      # the IMH warmup's shape
+    'ml64': (64, 1024, 1024, False),
+    'ml256': (256, 4096, 4096, False),   # the C5 refit shape
+}
+
+
+def spline(case, warm=5, epochs=60):
+    import statistics
+    from nfmc_amd.flow_training import _base_log_prob, forward_torch, inverse_torch
+    from nfmc_amd.potentials import SumOfSquares
+    from nfmc_amd.util import create_flow_object
+    d, n, nv, rkl = SPLINE_CASES[case]
+    dev = torch.device('cuda', 0)
+    g = torch.Generator().manual_seed(0)
+    x = (torch.randn(n, d, generator=g) * 0.7071).to(dev)
+    xv = (torch.randn(nv, d, generator=g) * 0.7071).to(dev) if nv else None
+    pot = SumOfSquares((d,))
+    # ---- device path
+    torch.manual_seed(1)
+    f = create_flow_object('c-rqnsf', (d,)).to(dev)
+    assert DeviceFit.supported(f.bijection, dev)
+    fit = DeviceFit.of(f.bijection, dev, n + nv, 0.01)
+    if nv:
+        fit.set_validation(xv)
+    ctl = fit.control(1 << 20, False, 50, True)
+    desc = pot.descriptor(dev) if rkl else None
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(warm + epochs + 1)]
+    torch.cuda.synchronize()
+    marks[0].record()
+    for e in range(warm + epochs):
+        rows = torch.randn(n, d, device=dev) if rkl else x
+        fit.run_calls(ctl, rows, e, 1, pot_struct=desc)
+        marks[e + 1].record()
+    torch.cuda.synchronize()
+    t_dev = statistics.median(marks[e].elapsed_time(marks[e + 1]) for e in range(warm, warm + epochs)) * 1e3
+    st = fit.state_after(warm + epochs)
+    # ---- the eager torch loop (flow_training._loop, one epoch at a time)
+    torch.manual_seed(1)
+    f = create_flow_object('c-rqnsf', (d,)).to(dev)
+    opt = torch.optim.AdamW(f.parameters(), lr=0.01)
+
+    def loss_fn(rows):
+        if rkl:
+            xs, ld = inverse_torch(f.bijection, rows)
+            return (_base_log_prob(rows) - ld + pot(xs)).mean()
+        z, ld = forward_torch(f.bijection, rows)
+        return -(_base_log_prob(z) + ld).mean()
+    times = []
+    for e in range(warm + epochs):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        opt.zero_grad()
+        loss = loss_fn(torch.randn(n, d, device=dev) if rkl else x)
+        assert torch.isfinite(loss)
+        loss.backward()
+        opt.step()
+        with torch.no_grad():
+            float(loss_fn(xv)) if nv else float(loss)
+        torch.cuda.synchronize()
+        times.append((time.perf_counter() - t0) * 1e6)
+    t_torch = statistics.median(times[warm:])
+    print('c-rqnsf %s d=%d H=%d rows=%d val=%d %s: device %.1f us per epoch, torch loop %.1f us, ratio %.1f (n_params %d, best loss %.4f)'
+          % (case, d, f.bijection.n_hidden, n, nv, 'reverse KL' if rkl else 'max likelihood', t_dev, t_torch, t_torch / t_dev,
+             fit.n_params, st[0]), flush=True)
+
+
 def main():
+    if len(sys.argv) > 2 and sys.argv[1] == 'spline':
+        return spline(sys.argv[2])
     dev = torch.device('cuda', 0)
     g = torch.Generator().manual_seed(0)
     for d, n, nv, H in ((256, 4096, 4096, None), (256, 2867, 1229, None), (64, 4096, 1024, None), (64, 1024, 0, None), (128, 4096, 4096, 16),
