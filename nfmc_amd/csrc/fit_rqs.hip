@@ -11,14 +11,18 @@
 //   * hidden stack: one thread per (row, hidden unit), activations to LDS;
 //   * forward / inverse sweep: threads stride over the tile's (row, target) pairs, rows fastest, so the 16 lanes of a
 //     target read the same W3 rows (16-byte loads from L1 / L2: at d = 256 the trainable vector is 220 KB and is not staged);
-//   * reverse sweep, 16 targets at a time: thread (row, target) rebuilds the layer input, evaluates the spline adjoint
+//   * reverse sweep, 16 targets at a time: thread (row, target) takes the layer input, evaluates the spline adjoint
 //     (rqs_forward_backward / rqs_inverse_backward, flow_device.hpp), stages its 23 output deltas and its HP-vector of
 //     dL/dh in LDS; then thread (target, output) walks the 16 rows in order and accumulates its W3 row (HP registers) and
 //     bias, while thread (row, unit) adds the targets' dL/dh in target order.  No atomics, every sum in a fixed order;
 //   * W1 / Wh / bias gradients and the ElementwiseAffine layers: transposed phases as in fit_grad_kernel.
-// No activation is stored: going backward a layer's input is rebuilt from its output (maximum likelihood: x_b = F^-1(z_b),
-// reverse KL: v = F(y), both closed form) and the conditioner re-evaluated from the unchanged half, so any number of
-// coupling layers fits.  Slabs, tails, validation tiles, `first`-tile stores and run_state follow fit_grad_kernel.
+// No activation is stored, so any number of coupling layers fits.  Reverse KL: going backward a layer's input is rebuilt from
+// its output with the forward map, v = F(y), closed form and well conditioned wherever the inverse pass was.  Maximum
+// likelihood: the input of layer l is recomputed from the tile's rows by running layers 0 .. l - 1 forward again, L (L - 1) / 2
+// extra layer evaluations per tile of an L-layer flow (one for the default two layers), each a fraction of a layer's reverse
+// step.  x_b = F^-1(z_b) would be closed form too, but fp32 cannot carry x through a forward pass of derivative 1e-3 and
+// back.  The conditioner is re-evaluated from the unchanged half.  Slabs, tails, validation tiles, `first`-tile stores and
+// run_state follow fit_grad_kernel.
 #include "fit_rqs.hpp"
 
 namespace nfmc {
@@ -104,8 +108,9 @@ __global__ void __launch_bounds__(kRqThreads) fit_rqs_kernel(FitRqsArgs a) {
         const int64_t nsrc = val ? a.nv : a.n, r0 = (val ? tile - a.tiles : tile) * R;
         const int nrow = (int)(nsrc - r0 < R ? nsrc - r0 : R);
         float lacc = 0.f;
-        __syncthreads();
-        {
+        // the tile's rows into xt (all threads must be done with the tile's previous contents)
+        auto load_rows = [&]() {
+            __syncthreads();
             const int total = nrow * d;
             const float* s = src + r0 * d;
             const bool rev = RKL && rev_last;
@@ -113,18 +118,19 @@ __global__ void __launch_bounds__(kRqThreads) fit_rqs_kernel(FitRqsArgs a) {
                 const int r = i / d, c = i - r * d;
                 xt[r * stride + (rev ? d - 1 - c : c)] = i < total ? s[i] : 0.f;   // rows beyond the batch: zeros
             }
-        }
-        __syncthreads();
-        if constexpr (!RKL) {
-            // ---- forward sweep: z = f(x) in place
+            __syncthreads();
+        };
+        // maximum likelihood: the first ElementwiseAffine and coupling layers [0, n_layers) applied to xt in place; with
+        // `count` their log-derivatives go to the loss.  The reverse sweep runs it again, without, to get a layer's input.
+        auto forward_layers = [&](int n_layers, bool count) {
             for (int i = tid; i < R * d; i += NT) {
                 const int r = i / d, c = i - r * d;
                 const float ls = f.ea0_log_scale[c];
                 xt[r * stride + c] = fmaf(fast_exp(ls), xt[r * stride + c], f.ea0_shift[c]);
-                if (r < nrow) lacc -= ls;
+                if (count && r < nrow) lacc -= ls;
             }
             __syncthreads();
-            for (int l = 0; l < g.n_coupling; ++l) {
+            for (int l = 0; l < n_layers; ++l) {
                 const bool rev = (l & 1) == 0;
                 const float* __restrict__ W = f.weights + l * g.layer_stride;
                 hidden(W, rev);
@@ -135,10 +141,15 @@ __global__ void __launch_bounds__(kRqThreads) fit_rqs_kernel(FitRqsArgs a) {
                     const int p = phys(g.d_a + t, d, rev);
                     float ld = 0.f;
                     xt[r * stride + p] = rqs_coordinate<false>(xt[r * stride + p], raw, g.bound, ld);
-                    if (r < nrow) lacc -= ld;
+                    if (count && r < nrow) lacc -= ld;
                 }
                 __syncthreads();
             }
+        };
+        load_rows();
+        if constexpr (!RKL) {
+            // ---- forward sweep: z = f(x) in place
+            forward_layers(g.n_coupling, true);
             for (int i = tid; i < R * d; i += NT) {
                 const int r = i / d, c = i - r * d, p = phys(c, d, rev_last);
                 const float ls = f.ea1_log_scale[c];
@@ -202,14 +213,13 @@ __global__ void __launch_bounds__(kRqThreads) fit_rqs_kernel(FitRqsArgs a) {
             for (int c = tid; c < d; c += NT) {   // z_p = e^s y_p + t
                 const int p = phys(c, d, rev_last);
                 const float s = f.ea1_log_scale[c], t = f.ea1_shift[c];
-                const float es = fast_exp(s), eis = fast_exp(-s);
+                const float es = fast_exp(s);
                 float as = 0.f, at = 0.f;
                 for (int r = 0; r < R; ++r) {
                     const float gz = gt[r * stride + p], zc = xt[r * stride + p] - t;
                     as = fmaf(gz, zc, as);
                     at += gz;
                     gt[r * stride + p] = gz * es;
-                    xt[r * stride + p] = zc * eis;
                 }
                 emit(ea_off + 2 * d4 + c, as - (float)nrow);   // d(-logdet)/ds = -1 per row
                 emit(ea_off + 3 * d4 + c, at);
@@ -237,6 +247,13 @@ __global__ void __launch_bounds__(kRqThreads) fit_rqs_kernel(FitRqsArgs a) {
             const bool rev = (l & 1) == 0;
             const float* __restrict__ W = f.weights + l * g.layer_stride;
             const int64_t L0 = (int64_t)l * g.layer_stride;
+            if constexpr (!RKL) {
+                // The layer's INPUT, by running the rows forward again through the layers before it.  Inverting the layer's
+                // output instead loses it: through a knot of derivative 1e-3 (fitted splines have them) one ulp of z spans
+                // 5e-4 of x, and every gradient of this and the earlier layers inherits that error.
+                load_rows();
+                forward_layers(l, false);
+            }
             hidden(W, rev);
             float ghacc = 0.f;   // dL/dh_last of (row hr, unit hk)
             for (int c0 = 0; c0 < g.d_b; c0 += TC) {
@@ -248,17 +265,15 @@ __global__ void __launch_bounds__(kRqThreads) fit_rqs_kernel(FitRqsArgs a) {
                     float raw[P], draw[P];
                     rqs_raw_outputs<HP>(W3t, W + o_b3 + t * P, hl + pr * HP, raw);
                     const bool ok = pr < nrow;
-                    const float so = xt[pr * stride + p], go = gt[pr * stride + p];   // the layer's output side
-                    float si, gi;                                                    // its input side
+                    const float so = xt[pr * stride + p], go = gt[pr * stride + p];   // reverse KL: the layer's output side
+                    float gi;
                     if constexpr (!RKL) {
-                        float unused = 0.f;
-                        si = rqs_coordinate<true>(so, raw, g.bound, unused);      // x_b = F^-1(z_b)
-                        if (so >= -g.bound && so <= g.bound) si = fminf(fmaxf(si, -g.bound), g.bound);
-                        rqs_forward_backward(si, go, raw, g.bound, draw, gi);
+                        rqs_forward_backward(so, go, raw, g.bound, draw, gi);     // xt holds the layer's input already
                     } else {
+                        float si;                                                 // v = F(y), rebuilt with the forward map
                         rqs_inverse_backward(so, go, raw, g.bound, draw, si, gi);
+                        xt[pr * stride + p] = si;
                     }
-                    xt[pr * stride + p] = si;
                     gt[pr * stride + p] = ok ? gi : 0.f;
                     float gh[HP];
 #pragma unroll

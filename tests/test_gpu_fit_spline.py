@@ -9,13 +9,17 @@ reference's own fp32 floor; the margin covers hardware exp / rcp / sqrt / log an
 
 The knot filter: a point within rounding of a knot may land in the neighbouring bin on the other side; the value is
 continuous there, the gradient of the log-derivative term is not.  Rows with such a point (in any coupling layer, +-B
-included) are removed before either side runs, by an fp64 walk of the restatement's layers."""
+included) are removed before either side runs, by an fp64 walk of the restatement's layers (tests/spline_fixtures.py, which
+also holds the gradient check; tests/test_gpu_spline_trained.py uses both on trained splines)."""
 import copy
 import math
 
 import numpy as np
 import pytest
 import torch
+
+from spline_fixtures import (check_gradient as _check_gradient, device_potential as _potential, filtered as _filtered,
+                             knot_free as _knot_free)
 
 pytestmark = pytest.mark.gpu
 
@@ -43,78 +47,55 @@ def _rows(n, d, seed):
     return x
 
 
-def _knot_free(of, rows, inverse, tol=1e-4):
-    """(rows kept, rows with a tail coordinate): fp64 walk of the restatement's layers in the direction of the sweep; a row
-    goes when any spline input lies within `tol` of a knot of that direction (width knots forward, height knots inverse)."""
-    from oracle import flow as oflow
-    bij = copy.deepcopy(of.bijection).double()
-    h = rows.double()
-    keep = torch.ones(rows.shape[0], dtype=torch.bool)
-    tail = torch.zeros(rows.shape[0], dtype=torch.bool)
-    layers = list(bij.layers)
-    with torch.no_grad():
-        for layer in (reversed(layers) if inverse else layers):
-            if isinstance(layer, oflow.RQSCoupling):
-                v = h[:, layer.d_a:]
-                cw, ch, _ = oflow.rqs_params(layer._raw(h[:, :layer.d_a]), layer.n_bins)
-                knots = ch if inverse else cw
-                keep &= ~((v[..., None] - knots).abs() < tol).any(-1).any(-1)
-                tail |= (v.abs() > oflow.RQS_BOUND).any(-1)
-            h, _ = layer.inverse(h) if inverse else layer.forward(h)
-    return keep, tail
-
-
-def _filtered(of, rows, inverse):
-    keep, tail = _knot_free(of, rows, inverse)
-    assert float((~keep).float().mean()) <= 0.10, 'the knot filter removed more than 10 % of the rows'
-    assert int((keep & tail).sum()) >= 2, 'fewer than two rows with a tail coordinate remain'
-    return rows[keep].contiguous()
-
-
-def _potential(kind, d):
-    from nfmc_amd.potentials import DiagonalGaussian, Funnel, SumOfSquares
-    if kind == 'sum':
-        return SumOfSquares((d,))
-    if kind == 'diag':
-        return DiagonalGaussian((d,), torch.linspace(-0.5, 0.5, d), torch.linspace(0.6, 1.7, d))
-    return Funnel((d,), 3.0)
-
-
-def _check_gradient(fit, f, of, loss, dev, padded=True):
-    """fit.m (beta1 = 0: the gradient) and the reported loss against `loss` of the restatement and its autograd."""
-    loss.backward()
-    loss_gpu, applied, _val = (float(v) for v in fit.status.cpu())
-    assert applied == 1.0
-    print('loss device %.8g oracle %.8g' % (loss_gpu, float(loss.detach())))
-    g = copy.deepcopy(f)
-    fit.write_back(fit.m, bijection=g.bijection)                        # the gradient, laid out as parameters
-    want = dict(of.named_parameters())
-    worst = []
-    for name, p in g.named_parameters():
-        w = want[name].grad
-        if w is None or w.numel() == 0:      # d = 1: the source half is empty, W1 has no entries
-            continue
-        scale = max(float(w.abs().max()), 1e-3)
-        worst.append((float((p.detach().cpu() - w).abs().max()) / scale, name))
-    print('worst gradient error / scale: %.3g (%s)' % max(worst))
-    np.testing.assert_allclose(loss_gpu, float(loss.detach()), rtol=3e-5, atol=3e-5)
-    for err, name in worst:
-        assert err <= 3e-4, (name, err)
-    if padded:
-        # the padded entries of the blob (hidden units beyond n_hidden, alignment gaps) carry no gradient
-        used = torch.zeros_like(fit.m, dtype=torch.bool)
-        for _p, off, r, c, rs, cs in fit._layout(f.bijection):
-            idx = off + torch.arange(r, device=dev)[:, None] * rs + torch.arange(c, device=dev)[None, :] * cs
-            used[idx.reshape(-1)] = True
-        assert int(used.sum()) > 0
-        assert float(fit.m[~used].abs().max() if (~used).any() else 0.0) == 0.0
-
-
 SHAPES = [  # d, n_hidden, hidden layers, coupling layers, rows, potential of the reverse-KL case
     (6, 4, 2, 2, 50, 'sum'), (7, 3, 1, 3, 64, 'diag'), (25, 4, 2, 2, 200, 'funnel'), (64, 8, 2, 2, 130, 'sum'),
     (100, 7, 2, 3, 129, 'diag'), (128, 5, 2, 2, 70, 'funnel'), (256, 7, 2, 2, 300, 'sum'), (1, 4, 2, 2, 30, 'diag'),
     (33, 8, 1, 2, 65, 'funnel'), (16, 4, 2, 2, 4300, 'sum'),
+    # one and four coupling layers; conditioner widths 1 and 2
+    (6, 4, 2, 1, 50, 'diag'), (10, 4, 2, 4, 50, 'funnel'), (6, 1, 1, 2, 40, 'sum'), (9, 2, 2, 2, 40, 'diag'),
+    # a lone row, an exactly full 16-row tile, a one-row second tile
+    (12, 4, 2, 2, 1, 'funnel'), (12, 4, 2, 2, 16, 'sum'), (12, 4, 2, 2, 17, 'diag'),
+    # so many parameters that 64 MiB of partial-gradient slabs hold fewer than 256: the grid is capped below the tile count
+    (256, 8, 2, 3, 4200, 'sum'),
 ]
+CAPPED = (256, 8, 2, 3, 4200)
+ROW_SEED = {(6, 1): 61}      # (d, coupling layers): with d's own seed neither far-out row reaches the one coupling's tails
+
+
+def _case_rows(of, d, n, inverse, nl=2):
+    """The rows of a SHAPES case after the knot filter.  n = 1: a hand-made row with one coordinate in the identity tails
+    (the filter's two-tail-rows assert cannot hold for it; that it is kept and has its tail coordinate is asserted here)."""
+    if n == 1:
+        rows = torch.linspace(-2.0, 2.0, d).reshape(1, d).clone()
+        rows[0, 3] = 7.5
+        keep, tail = _knot_free(of, rows, inverse)
+        assert bool(keep.all()) and bool(tail.all())
+        return _filtered(of, rows, inverse, need_tail=False)
+    if n <= 17:     # a row count that stands for a tile edge: spare rows, so that exactly n come through the filter
+        rows = _filtered(of, _rows(n + 8, d, d), inverse=inverse)[:n].contiguous()
+        assert rows.shape[0] == n and int(_knot_free(of, rows, inverse)[1].sum()) >= 2
+        return rows
+    return _filtered(of, _rows(n, d, ROW_SEED.get((d, nl), d)), inverse=inverse)
+
+
+def _assert_grid(fit, shape, n_rows):
+    """The workgroups of the spline gradient launch on `n_rows` rows, from the workspace the library sizes for them (one
+    slab of n_params + 4 floats each); for the CAPPED shape the 64 MiB cap falls below 256 and below the tile count, so
+    workgroups stride over several tiles."""
+    import ctypes as C
+    from nfmc_amd import hip
+    slabs = []
+    for rows in (n_rows, 1 << 20):
+        nfl = C.c_int64(0)
+        hip.lib().nfmc_flow_fit_workspace(C.byref(fit.flow_struct), rows, 0, fit.n_params, C.byref(nfl))
+        assert nfl.value % (fit.n_params + 4) == 0
+        slabs.append(nfl.value // (fit.n_params + 4))
+    grid, cap = slabs
+    tiles = (n_rows + 15) // 16
+    print('tiles %d, workgroups %d, cap %d' % (tiles, grid, cap))
+    assert grid == min(tiles, cap) and cap <= 256
+    if shape == CAPPED:
+        assert cap < 256 and cap < tiles
 
 
 @pytest.mark.parametrize('d,H,nhl,nl,n,_kind', SHAPES)
@@ -124,10 +105,11 @@ def test_spline_nll_gradient_matches_autograd(dev, d, H, nhl, nl, n, _kind):
     the blob's padding exactly zero."""
     from nfmc_amd.flow_training import DeviceFit
     of, f = _flow(d, H, nhl, nl, 3 + d)
-    x = _filtered(of, _rows(n, d, d), inverse=False)
+    x = _case_rows(of, d, n, False, nl)
     f.to(dev)
     assert DeviceFit.supported(f.bijection, dev)
     fit = DeviceFit(f.bijection, dev, x.shape[0], lr=0.0)
+    _assert_grid(fit, (d, H, nhl, nl, n), x.shape[0])
     fit.opt.beta1, fit.opt.weight_decay = 0.0, 0.0
     before = fit.params.clone()
     fit.step(x.to(dev), 0)
@@ -142,10 +124,11 @@ def test_spline_reverse_kl_gradient_matches_autograd(dev, d, H, nhl, nl, n, kind
     parameter against autograd through the CPU restatement's inverse pass and the potential's torch form."""
     from nfmc_amd.flow_training import DeviceFit
     of, f = _flow(d, H, nhl, nl, 3 + d)
-    z = _filtered(of, _rows(n, d, d), inverse=True)
+    z = _case_rows(of, d, n, True, nl)
     pot = _potential(kind, d)
     f.to(dev)
     fit = DeviceFit(f.bijection, dev, z.shape[0], lr=0.0)
+    _assert_grid(fit, (d, H, nhl, nl, n), z.shape[0])
     fit.opt.beta1, fit.opt.weight_decay = 0.0, 0.0
     fit.step_variational(z.to(dev), pot.descriptor(dev), 0)
     torch.cuda.synchronize()
@@ -283,6 +266,78 @@ def test_spline_device_steps_follow_torch_adamw(dev):
     assert la[-1] < la[0] and lb[-1] < lb[0]                              # the loss falls
     np.testing.assert_allclose(la[:8], lb[:8], rtol=1e-3)
     np.testing.assert_allclose(la, lb, rtol=2e-2, atol=5e-2)
+
+
+@pytest.mark.parametrize('bad', [1e30, float('nan')])
+@pytest.mark.parametrize('loss_kind', ['nll', 'reverse_kl'])
+def test_spline_run_skips_or_ends_on_a_nonfinite_epoch(dev, loss_kind, bad):
+    """The spline twin of test_gpu_fit.py's test_variational_run_skips_or_ends_on_a_nonfinite_epoch, for both losses: the
+    third of four batches has one row holding 1e30 (a coordinate in the identity tails whose square overflows) or NaN, so
+    its loss is not finite.  The run skips that epoch (weights, AdamW moments and step count untouched) or ends as diverged,
+    decided on the device; a following run on finite rows with the same fitter steps normally."""
+    from nfmc_amd import hip
+    from nfmc_amd.flow_training import DeviceFit
+    from nfmc_amd.potentials import SumOfSquares
+    d, n = 16, 128
+    _of, f = _flow(d, 4, 2, 2, 5)
+    f.to(dev)
+    pot = SumOfSquares((d,)).descriptor(dev) if loss_kind == 'reverse_kl' else None
+    g0 = torch.Generator().manual_seed(4)
+    rows = [(torch.randn(n, d, generator=g0)).to(dev) for _ in range(4)]
+    rows[2][5, 3] = bad
+    for skip in (True, False):
+        fit = DeviceFit(f.bijection, dev, n, lr=0.02)
+        start = fit.params.clone()
+        ctl = fit.control(4, False, 50, True, skip_nonfinite=skip)
+        w, moments = [], []
+        for c in range(4):
+            fit.run_calls(ctl, rows[c], c, 1, pot_struct=pot)
+            w.append(fit.params.clone())
+            moments.append((fit.m.clone(), fit.v.clone()))
+        st = fit.state_after(4)
+        assert bool(torch.isfinite(torch.stack(w)).all())
+        assert not torch.equal(start, w[0]) and not torch.equal(w[0], w[1])
+        assert torch.equal(w[1], w[2])                                    # the non-finite epoch moved nothing
+        assert torch.equal(moments[1][0], moments[2][0]) and torch.equal(moments[1][1], moments[2][1])
+        if skip:
+            assert st[hip.FIT_DIVERGED] == 0.0 and st[hip.FIT_APPLIED] == 3.0 and not torch.equal(w[2], w[3])
+        else:
+            assert st[hip.FIT_DIVERGED] == 1.0 and st[hip.FIT_APPLIED] == 2.0 and torch.equal(w[2], w[3])
+        assert math.isfinite(st[hip.FIT_BEST_LOSS])
+        # a fresh run on finite rows
+        ctl = fit.control(2, False, 50, True, skip_nonfinite=skip)
+        fit.run_calls(ctl, rows[3], 0, 1, pot_struct=pot)
+        after = fit.params.clone()
+        st = fit.state_after(1)
+        assert st[hip.FIT_DIVERGED] == 0.0 and st[hip.FIT_APPLIED] == 1.0 and math.isfinite(st[hip.FIT_LAST_LOSS])
+        assert not torch.equal(after, w[3]) and bool(torch.isfinite(after).all())
+        assert float((after - w[3]).abs().max()) <= 0.021                 # one AdamW step at lr = 0.02 (+ weight decay)
+
+
+@pytest.mark.parametrize('bad', [1e30, float('nan')])
+def test_spline_fit_raises_on_a_nonfinite_batch_and_keeps_the_weights(dev, bad, monkeypatch):
+    """The divergence part of test_device_fit_early_stopping_best_weights_and_divergence for a spline flow: a non-finite
+    loss raises ValueError (the only error the samplers catch) and leaves the weights the flow came in with; the next fit
+    on finite rows runs.  Both fits are counted on the device path."""
+    d = 16
+    calls = _count_calls(monkeypatch)
+    _of, f = _flow(d, 4, 2, 2, 2)
+    f.to(dev)
+    x = (torch.randn(256, d, generator=torch.Generator().manual_seed(1)) * 0.5).to(dev)
+    before = copy.deepcopy(f.state_dict())
+    broken = x.clone()
+    broken[3, 2] = bad
+    with pytest.raises(ValueError):
+        f.fit(broken, n_epochs=5, show_progress=False)
+    assert 1 <= len(calls) <= 5                                         # the device run, ended by the non-finite epoch
+    for k, v in f.state_dict().items():
+        assert torch.equal(v, before[k]), k
+    n0 = float(-f.log_prob(x).mean())
+    del calls[:]
+    f.fit(x, n_epochs=5, lr=0.02, show_progress=False)
+    assert len(calls) == 5
+    n1 = float(-f.log_prob(x).mean())
+    assert math.isfinite(n1) and n1 < n0
 
 
 # ------------------------------------------------------------------------------------------------ the public paths
