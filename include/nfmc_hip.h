@@ -125,7 +125,7 @@ enum {
        NeuTra kernels (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32 with conditioners of at most 32 units).
        NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the fit kernels, the Philox4x32-7 stream and the
        NeuTra matrix-core kernels (conditioners wider than 32). */
-    NFMC_POT_LATTICE_PHI4 = 8
+    NFMC_POT_LATTICE_PHI4 = 8,
     /* phi^4 scalar field on a lattice of H rows of W sites, flattened row-major (d = H W; H = 1 is the 1-D lattice,
        which has no second axis).  Every site c has two neighbours c' per axis; a periodic axis wraps round (so an axis
        of length 2 counts its bond twice), and with the zero boundary the field is 0 past the ends of an axis:
@@ -142,6 +142,27 @@ enum {
        (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32 with conditioners of at most 32 units).
        NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the fit kernels, the Philox4x32-7 stream and the
        NeuTra matrix-core kernels (conditioners wider than 32). */
+    NFMC_POT_ITEM_RESPONSE = 9
+    /* One-parameter item-response theory (the synthetic IRT model of the Inference Gym): S students answer Q questions,
+       d = S + Q + 1 coordinates x = [alpha_0 .. alpha_{S-1} | beta_0 .. beta_{Q-1} | mu] (abilities, difficulties, mean
+       ability);  mu ~ N(m0, 1/p_mu), alpha_s ~ N(0, 1/p_a), beta_q ~ N(0, 1/p_b), y_sq ~ Bernoulli(sigmoid(l_sq)) for
+       every observed pair, l_sq = mu + alpha_s - beta_q.  With r_sq = sigmoid(l_sq) - y_sq (0 where unobserved):
+         U = 1/2 p_mu (mu - m0)^2 + 1/2 p_a sum_s alpha_s^2 + 1/2 p_b sum_q beta_q^2
+             + sum_{observed} [softplus(l_sq) - y_sq l_sq]                                   (constants dropped)
+         dU/dalpha_s = p_a alpha_s + sum_q r_sq,  dU/dbeta_q = p_b beta_q - sum_s r_sq,  dU/dmu = p_mu (mu - m0) + sum r_sq
+       n_components = S (Q = d - 1 - S);  b -> (m0, p_mu, p_a, p_b), four fp32 in device memory;  a -> the responses in
+       device memory, 16-byte aligned: ONE block of Q rows of SA = 4 ceil(S / 4) fp32, question-major,
+       a[q * SA + s] = 1 or 0 for the observed answer of student s to question q and any negative value (-1) for a
+       missing one and for the padding s >= S.  (The kernels evaluate each pair once, in a pass over the questions, so
+       there is no second, student-major block.)  a_scalar and b_scalar unused.  A NULL a or b, S < 1 or S > d - 2 is
+       NFMC_EINVAL; a misaligned a is NFMC_EALIGN.  No cap on S Q; d <= 1024.  The kernels keep one LDS row of d padded
+       to DP = CPL LPC floats, plus 4, per chain of a workgroup: (256 / LPC) (DP + 4) fp32 (a flow image that leaves no room
+       for it gets NFMC_EUNSUPPORTED).
+       Served by nfmc_mala_steps_f32 / nfmc_hmc_steps_f32 (general kernels, with or without a jump tail, device warmup
+       tuning included), by the register-layout kernels of nfmc_flow_mh_steps_f32 and by the VALU NeuTra kernels
+       (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32 with conditioners of at most 32 units).
+       NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the fit kernels, the Philox4x32-7 stream and the
+       NeuTra matrix-core kernels (conditioners wider than 32). */
 };
 
 typedef struct {
@@ -149,6 +170,7 @@ typedef struct {
     int32_t n_components; /* NFMC_POT_GAUSSIAN_MIXTURE: K; NFMC_POT_LOGISTIC_REGRESSION: N; NFMC_POT_GAUSSIAN_FULL: d;
                              NFMC_POT_ROSENBROCK: block length; NFMC_POT_STOCHASTIC_VOLATILITY: T = d - 3;
                              NFMC_POT_SPARSE_LOGISTIC_REGRESSION: N; NFMC_POT_LATTICE_PHI4: W (sites per lattice row);
+                             NFMC_POT_ITEM_RESPONSE: S (students);
                              0 for the other kinds (was `reserved`, same layout) */
     const float* a; /* (d,) or NULL -> a_scalar */
     const float* b; /* (d,) or NULL -> b_scalar */
@@ -299,6 +321,12 @@ typedef struct {
     int32_t reserved;
 } NfmcTune;
 int64_t nfmc_tune_state_doubles(int32_t d);
+
+/* The register layout nfmc_mala_steps_f32 / nfmc_hmc_steps_f32 run a call without a jump tail on, for event size d and
+ * potential kind `pot_kind`: *cpl coordinates per lane, *lpc lanes per chain (a workgroup holds 256 / lpc chains).  Host
+ * arithmetic only, no device call.  NFMC_EINVAL for a NULL pointer or d <= 0, NFMC_ESHAPE for d > 1024,
+ * NFMC_EUNSUPPORTED for an unknown kind. */
+int nfmc_sampler_layout(int32_t d, int32_t pot_kind, int32_t* cpl, int32_t* lpc);
 
 /* Optional tail of a sampler call: after the n_steps inner transitions, ONE flow-proposal Metropolis jump
  * (jump.py:205-243: flow.sample, flow.log_prob, 2 target calls, log u < log alpha, masked update) on the

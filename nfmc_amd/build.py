@@ -39,7 +39,8 @@ UNIT_FLAGS = {'neutra_mfma.hip': ['-mllvm', '-amdgpu-promote-alloca-to-vector-li
 # units that take a minute or more to compile go first, so that the pool finishes with the short ones
 # (NFMC_BUILD_TIMES=1 prints the time of each)
 SLOW_FIRST = ['flow_b_kernels.hip', 'neutra_kernels_r64.hip', 'neutra_kernels_r32.hip', 'neutra_kernels_r16.hip',
-              'imh_parallel_rqs.hip', 'imh_parallel.hip', 'fit_kernels.hip', 'neutra_mfma.hip', 'fit_mfma.hip']
+              'imh_parallel_rqs.hip', 'imh_parallel.hip', 'fit_kernels.hip', 'neutra_mfma.hip', 'fit_mfma.hip',
+              'sampler_irt_hmc.hip', 'sampler_irt_mala.hip']
 
 
 def sources():

@@ -333,6 +333,52 @@ __device__ __forceinline__ float phi4_value_grad_row(const float* __restrict__ r
     return u;
 }
 
+// Item-response theory (NFMC_POT_ITEM_RESPONSE) for the row of one chain, as potential_value_grad_row: U and dU/dx of
+// IrtPot (common.hpp), x = [alpha (S) | beta (Q) | mu].  One pass over the questions: the students' entries of the
+// gradient row accumulate r_sq = sigmoid(l_sq) - y_sq, question q's entry gets -sum_s r_sq when its row is done, and the
+// sum of those is mu's.  The responses are wave-uniform (scalar loads); a negative entry is a missing answer.  The data
+// term is summed in fp64, as in IrtPot.  grow[s] += r is a read and a write of the lane's own LDS row per pair, beside
+// the exp, log and reciprocal of softplus_sigmoid: the price of evaluating every pair once with the responses read in
+// storage order (a second pass for the students' sums would evaluate every pair twice, student-major blocks would
+// read each 64-byte line of the responses in four far-apart visits).  Kept out of potential_value_grad_row, which the fit and DLMC kernels share and
+// which never see kind 9.
+__device__ __forceinline__ float irt_value_grad_row(const float* __restrict__ row, float* __restrict__ grow,
+                                                    const NfmcPotential& p, int d) {
+    const int ns = p.n_components, nq = d - 1 - ns, sa = (ns + 3) & ~3;
+    const float m0 = p.b[0], pmu = p.b[1], pa = p.b[2], pb = p.b[3], mu = row[d - 1];
+    float u = 0.f;
+    for (int s = 0; s < ns; ++s) {
+        const float a = row[s];
+        grow[s] = pa * a;
+        u = fmaf(0.5f * pa * a, a, u);
+    }
+    double ul = 0.0;
+    float sr = 0.f;
+    for (int q = 0; q < nq; ++q) {
+        const float* __restrict__ aq = p.a + (int64_t)q * sa;
+        const float beta = row[ns + q];
+        float rs = 0.f;
+        for (int s = 0; s < ns; ++s) {
+            const float v = aq[s];
+            if (v >= 0.f) {   // wave-uniform
+                const float l = (mu + row[s]) - beta;
+                float sp, sg;
+                softplus_sigmoid(l, sp, sg);
+                const float r = sg - v;
+                grow[s] += r;
+                rs += r;
+                ul += (double)(sp - v * l);
+            }
+        }
+        grow[ns + q] = fmaf(pb, beta, -rs);
+        u = fmaf(0.5f * pb * beta, beta, u);
+        sr += rs;
+    }
+    const float dm = mu - m0;
+    grow[d - 1] = fmaf(pmu, dm, sr);
+    return (float)(ul + (double)fmaf(0.5f * pmu * dm, dm, u));
+}
+
 // U~(z) and grad U~(z) for this lane's chain.  zrow: latent (tile columns in latent order), read only;
 // wrow: scratch, ends holding z again (rebuilt); grow: gradient in the same column order as zrow.
 template <int HP>
@@ -346,6 +392,7 @@ __device__ __forceinline__ float adjusted_potential_grad_row(const float* __rest
                     : pot.kind == NFMC_POT_STOCHASTIC_VOLATILITY ? sv_value_grad_row(wrow, grow, pot, g.d)
                     : pot.kind == NFMC_POT_SPARSE_LOGISTIC_REGRESSION ? slr_value_grad_row(wrow, grow, pot, g.d)
                     : pot.kind == NFMC_POT_LATTICE_PHI4 ? phi4_value_grad_row(wrow, grow, pot, g.d)
+                    : pot.kind == NFMC_POT_ITEM_RESPONSE ? irt_value_grad_row(wrow, grow, pot, g.d)
                                                          : potential_value_grad_row(wrow, grow, pot, g.d);  // U(x), dU/dx (neutra.py:62)
     // reverse sweep, mirror image of flow_inverse_row
     for (int c = 0; c < g.d; ++c) {                               // EA0^-1

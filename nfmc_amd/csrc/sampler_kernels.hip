@@ -305,6 +305,18 @@ extern "C" int64_t nfmc_tune_state_doubles(int32_t d) {
     return NFMC_TUNE_WORDS + 3 * padded_d(d) + kStatTail;   // controller words, column totals, shift
 }
 
+extern "C" int nfmc_sampler_layout(int32_t d, int32_t pot_kind_id, int32_t* cpl, int32_t* lpc) {
+    if (!cpl || !lpc || d <= 0) return NFMC_EINVAL;
+    if (d > 1024) return NFMC_ESHAPE;
+    const PotKind* pk = pot_kind(pot_kind_id);
+    if (!pk) return NFMC_EUNSUPPORTED;
+    const Cfg c = choose_cfg(d, false, pk->default_cfg_only);   // as sampler_steps, no jump tail
+    if (!c.cpl) return NFMC_ESHAPE;
+    *cpl = c.cpl;
+    *lpc = c.lpc;
+    return NFMC_OK;
+}
+
 // The part the two sampler entry points share, behind their own argument checks: layout, tile and grid arithmetic, the
 // scratch / defer / tune checks, then either the warmup loop (one launch + controller update per `every` transitions, all
 // of the call enqueued here) or one launch and the statistics finish.  launch(args, jd, c, jhp, fast, tiles, grid).

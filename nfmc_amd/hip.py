@@ -18,6 +18,7 @@ POT_QUADRATIC, POT_FUNNEL, POT_GAUSSIAN_MIXTURE, POT_LOGISTIC_REGRESSION, POT_GA
 POT_STOCHASTIC_VOLATILITY = 6
 POT_SPARSE_LOGISTIC_REGRESSION = 7
 POT_LATTICE_PHI4 = 8
+POT_ITEM_RESPONSE = 9
 MIXTURE_MAX_COMPONENTS = 8   # kMixMaxK (csrc/common.hpp)
 TAG_NOISE, TAG_ACCEPT, TAG_LATENT, TAG_JUMP = 0, 1, 2, 3
 CNT_ACCEPTED, CNT_ATTEMPTED, CNT_NONFINITE, CNT_WORDS = 0, 1, 2, 4
@@ -181,6 +182,7 @@ class NfmcLimits(C.Structure):
 SYMBOLS = [
     ('nfmc_stats_scratch_bytes', C.c_int64, [C.c_int32]),
     ('nfmc_tune_state_doubles', C.c_int64, [C.c_int32]),
+    ('nfmc_sampler_layout', C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ('nfmc_mala_steps_f32', C.c_int, [C.POINTER(NfmcMalaArgs), c_fp]),
     ('nfmc_hmc_steps_f32', C.c_int, [C.POINTER(NfmcHmcArgs), c_fp]),
     ('nfmc_realnvp_padded_hidden', C.c_int32, [C.c_int32]),
