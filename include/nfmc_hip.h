@@ -142,7 +142,7 @@ enum {
        (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32 with conditioners of at most 32 units).
        NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the fit kernels, the Philox4x32-7 stream and the
        NeuTra matrix-core kernels (conditioners wider than 32). */
-    NFMC_POT_ITEM_RESPONSE = 9
+    NFMC_POT_ITEM_RESPONSE = 9,
     /* One-parameter item-response theory (the synthetic IRT model of the Inference Gym): S students answer Q questions,
        d = S + Q + 1 coordinates x = [alpha_0 .. alpha_{S-1} | beta_0 .. beta_{Q-1} | mu] (abilities, difficulties, mean
        ability);  mu ~ N(m0, 1/p_mu), alpha_s ~ N(0, 1/p_a), beta_q ~ N(0, 1/p_b), y_sq ~ Bernoulli(sigmoid(l_sq)) for
@@ -163,6 +163,44 @@ enum {
        (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32 with conditioners of at most 32 units).
        NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the fit kernels, the Philox4x32-7 stream and the
        NeuTra matrix-core kernels (conditioners wider than 32). */
+    NFMC_POT_VARYING_EFFECTS = 10
+    /* Gaussian regression with group-level (varying) effects: the radon models and eight schools.  Observation i has a
+       response y_i, an optional covariate x_i and a group g_i in 0 .. C-1:  y_i ~ N(a[g_i] + b[g_i] x_i, sigma_i^2).
+       Intercept side: varying (a_c ~ N(mu_a, sigma_a^2), mu_a ~ N(0, m^2), sigma_a ~ HalfNormal(h)) or shared (one
+       a ~ N(0, m^2)); slope side: varying, shared or none (b = 0); at least one side varies.  Noise: unknown
+       (sigma_i = sigma_y ~ HalfNormal(h)) or known per observation.  Scales are sampled as logs s = log sigma (Jacobian
+       included).  Centered: the group coordinates are a_c, b_c; non-centered: t_c ~ N(0, 1) with a_c = mu_a + e^{s_a} t_c.
+       Coordinates: the group block, [a_0, b_0, a_1, b_1, ...] (2 C, interleaved) when both sides vary and [v_0 .. v_{C-1}]
+       when one does, then the globals that exist, in this order: (mu_a, s_a) or a; (mu_b, s_b) or b or nothing; s_y if the
+       noise is unknown.  d = 2 C + 5 at most.
+       The likelihood enters through six sufficient statistics per group, weights omega_i = 1 / sigma_i^2 (1 when the
+       noise is unknown): n_c = sum omega, the weighted means xbar_c, ybar_c and the CENTRED weighted sums Sxx_c, Sxy_c,
+       Syy_c.  With P = 1 / m^2, Hh = 1 / h^2, w_y = e^{-2 s_y} (1 when known), e_c = ybar_c - a_c - b_c xbar_c:
+         Q_c  = n_c e_c^2 + Syy_c - 2 b_c Sxy_c + b_c^2 Sxx_c
+         gA_c = -w_y n_c e_c,   gB_c = w_y (-n_c e_c xbar_c - Sxy_c + b_c Sxx_c)
+         U = 1/2 w_y sum_c Q_c  [+ N s_y + 1/2 Hh e^{2 s_y} - s_y  when the noise is unknown]
+             + per varying side (mu, s), r_c = v_c - mu, w = e^{-2 s}:
+                 centered      C s + 1/2 w sum r_c^2 + 1/2 P mu^2 + 1/2 Hh e^{2 s} - s
+                 non-centered  1/2 sum t_c^2 + 1/2 P mu^2 + 1/2 Hh e^{2 s} - s
+             + per shared side 1/2 P v^2                                                     (constants dropped)
+         dU/ds_y = N - w_y sum Q_c + Hh e^{2 s_y} - 1
+         centered:      dU/dv_c = gV_c + w r_c,      dU/dmu = P mu - w sum r_c,  dU/ds = C - w sum r_c^2 + Hh e^{2 s} - 1
+         non-centered:  dU/dt_c = e^{s} gV_c + t_c,  dU/dmu = P mu + sum gV_c,   dU/ds = e^{s} sum gV_c t_c + Hh e^{2 s} - 1
+         shared:        dU/dv = P v + sum gV_c
+       n_components = C;  a -> the group table in device memory, 16-byte aligned, C rows of 8 fp32
+       (n, xbar, ybar, Sxx, Sxy, Syy, 0, 0);  b -> (P, Hh), two fp32 in device memory;  a_scalar = the layout code, an
+       integer-valued float mode_a + 4 mode_b + 16 known_noise + 32 non_centered with mode 0 = none, 1 = shared,
+       2 = varying (mode_a is 1 or 2, mode_b 0, 1 or 2, one of them 2);  b_scalar = N, the number of observations, when
+       the noise is unknown (unused otherwise).  A NULL a or b, C < 1, a code that is none of the 16 valid ones, d other
+       than group block + globals of the code, or N not positive and finite with unknown noise is NFMC_EINVAL; a
+       misaligned a is NFMC_EALIGN.  d <= 1024.  No LDS block: every lane reads the table rows of its own groups (two
+       16-byte loads per group and evaluation).  e^{-2 s}, e^{2 s} and e^{s} overflow fp32 far in the tails: U is then inf
+       or NaN and the samplers reject the state and count its log ratio as non-finite.
+       Served by nfmc_mala_steps_f32 / nfmc_hmc_steps_f32 (general kernels, with or without a jump tail, device warmup
+       tuning included), by the register-layout kernels of nfmc_flow_mh_steps_f32 and by the VALU NeuTra kernels
+       (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32 with conditioners of at most 32 units).
+       NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the fit kernels, the Philox4x32-7 stream and the
+       NeuTra matrix-core kernels (conditioners wider than 32). */
 };
 
 typedef struct {
@@ -170,7 +208,7 @@ typedef struct {
     int32_t n_components; /* NFMC_POT_GAUSSIAN_MIXTURE: K; NFMC_POT_LOGISTIC_REGRESSION: N; NFMC_POT_GAUSSIAN_FULL: d;
                              NFMC_POT_ROSENBROCK: block length; NFMC_POT_STOCHASTIC_VOLATILITY: T = d - 3;
                              NFMC_POT_SPARSE_LOGISTIC_REGRESSION: N; NFMC_POT_LATTICE_PHI4: W (sites per lattice row);
-                             NFMC_POT_ITEM_RESPONSE: S (students);
+                             NFMC_POT_ITEM_RESPONSE: S (students); NFMC_POT_VARYING_EFFECTS: C (groups);
                              0 for the other kinds (was `reserved`, same layout) */
     const float* a; /* (d,) or NULL -> a_scalar */
     const float* b; /* (d,) or NULL -> b_scalar */

@@ -379,6 +379,57 @@ __device__ __forceinline__ float irt_value_grad_row(const float* __restrict__ ro
     return (float)(ul + (double)fmaf(0.5f * pmu * dm, dm, u));
 }
 
+// Varying-effects regression (NFMC_POT_VARYING_EFFECTS) for the row of one chain, as potential_value_grad_row: U and
+// dU/dx of VaryEffPot (common.hpp), the group block first and the globals behind it.  One pass over the groups: the
+// table row of a group (two 16-byte loads), the layout and (P, Hh) are wave-uniform; the group's one or two coordinates
+// are read from and its gradient written to the lane's own LDS row; the five sums run in registers and the globals'
+// gradients follow the pass.  O(d), no pass over the observations.  Kept out of potential_value_grad_row, which the fit
+// and DLMC kernels share and which never see kind 10.
+__device__ __forceinline__ float vfx_value_grad_row(const float* __restrict__ row, float* __restrict__ grow,
+                                                    const NfmcPotential& p, int) {
+    VfxLayout L;
+    vfx_layout(p.a_scalar, p.n_components, L);   // valid: check_vfx
+    const int nc = p.n_components;
+    const bool va = L.ma == 2, vb = L.mb == 2, both = va && vb, ncp = L.ncp;
+    const float P = p.b[0], Hh = p.b[1], fc = (float)nc;
+    const float* __restrict__ gl = row + L.gb;
+    float* __restrict__ gg = grow + L.gb;
+    const float mua = gl[0], sa = va ? gl[1] : 0.f, mub = L.mb ? gl[L.ib] : 0.f, sb = vb ? gl[L.ib + 1] : 0.f;
+    const float sy = L.known ? 0.f : gl[L.iy];
+    const float wy = L.known ? 1.f : fast_exp(-2.f * sy);
+    const float wa = fast_exp(-2.f * sa), esa = fast_exp(sa), wb = fast_exp(-2.f * sb), esb = fast_exp(sb);
+    const float4* __restrict__ tab = reinterpret_cast<const float4*>(p.a);
+    float u = 0.f, sq = 0.f, a1 = 0.f, a2 = 0.f, b1 = 0.f, b2 = 0.f;
+    for (int c = 0; c < nc; ++c) {
+        const float4 s0 = tab[2 * c], s1 = tab[2 * c + 1];
+        const int ia = both ? 2 * c : c, ib = both ? 2 * c + 1 : c;
+        const float xa = va ? row[ia] : 0.f, xb = vb ? row[ib] : 0.f;
+        const float a = va ? (ncp ? fmaf(esa, xa, mua) : xa) : mua, b = vb ? (ncp ? fmaf(esb, xb, mub) : xb) : mub;
+        float qc, ga, gb;
+        vfx_group(s0, s1, a, b, wy, qc, ga, gb);
+        sq += qc;
+        if (va) grow[ia] = vfx_vary(ncp, xa, mua, wa, esa, ga, a1, a2, u);
+        else a1 += ga;
+        if (vb) grow[ib] = vfx_vary(ncp, xb, mub, wb, esb, gb, b1, b2, u);
+        else b1 += gb;
+    }
+    if (!ncp) u = fmaf(0.5f * wa, va ? a2 : 0.f, fmaf(0.5f * wb, vb ? b2 : 0.f, u));
+    u = fmaf(0.5f * wy, sq, u);
+    float g0, g1;
+    u += vfx_side_globals(L.ma, ncp, mua, sa, wa, esa, a1, a2, fc, P, Hh, g0, g1);
+    gg[0] = g0;
+    if (va) gg[1] = g1;
+    u += vfx_side_globals(L.mb, ncp, mub, sb, wb, esb, b1, b2, fc, P, Hh, g0, g1);
+    if (L.mb) gg[L.ib] = g0;
+    if (vb) gg[L.ib + 1] = g1;
+    if (!L.known) {
+        const float he = Hh * fast_exp(2.f * sy);
+        gg[L.iy] = fmaf(-wy, sq, p.b_scalar) + he - 1.f;
+        u += fmaf(p.b_scalar, sy, fmaf(0.5f, he, -sy));
+    }
+    return u;
+}
+
 // U~(z) and grad U~(z) for this lane's chain.  zrow: latent (tile columns in latent order), read only;
 // wrow: scratch, ends holding z again (rebuilt); grow: gradient in the same column order as zrow.
 template <int HP>
@@ -393,6 +444,7 @@ __device__ __forceinline__ float adjusted_potential_grad_row(const float* __rest
                     : pot.kind == NFMC_POT_SPARSE_LOGISTIC_REGRESSION ? slr_value_grad_row(wrow, grow, pot, g.d)
                     : pot.kind == NFMC_POT_LATTICE_PHI4 ? phi4_value_grad_row(wrow, grow, pot, g.d)
                     : pot.kind == NFMC_POT_ITEM_RESPONSE ? irt_value_grad_row(wrow, grow, pot, g.d)
+                    : pot.kind == NFMC_POT_VARYING_EFFECTS ? vfx_value_grad_row(wrow, grow, pot, g.d)
                                                          : potential_value_grad_row(wrow, grow, pot, g.d);  // U(x), dU/dx (neutra.py:62)
     // reverse sweep, mirror image of flow_inverse_row
     for (int c = 0; c < g.d; ++c) {                               // EA0^-1
