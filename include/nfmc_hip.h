@@ -163,7 +163,7 @@ enum {
        (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32 with conditioners of at most 32 units).
        NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the fit kernels, the Philox4x32-7 stream and the
        NeuTra matrix-core kernels (conditioners wider than 32). */
-    NFMC_POT_VARYING_EFFECTS = 10
+    NFMC_POT_VARYING_EFFECTS = 10,
     /* Gaussian regression with group-level (varying) effects: the radon models and eight schools.  Observation i has a
        response y_i, an optional covariate x_i and a group g_i in 0 .. C-1:  y_i ~ N(a[g_i] + b[g_i] x_i, sigma_i^2).
        Intercept side: varying (a_c ~ N(mu_a, sigma_a^2), mu_a ~ N(0, m^2), sigma_a ~ HalfNormal(h)) or shared (one
@@ -201,6 +201,28 @@ enum {
        (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32 with conditioners of at most 32 units).
        NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the fit kernels, the Philox4x32-7 stream and the
        NeuTra matrix-core kernels (conditioners wider than 32). */
+    NFMC_POT_PARTICLES = 11
+    /* Interacting particles in a harmonic trap (many-particle Boltzmann density): P particles in D = 1, 2 or 3
+       dimensions, coordinates particle-major x = [r_0 | r_1 | .. | r_{P-1}], d = P D.  With r_ij = |r_i - r_j|:
+         U = beta [ k/2 sum_i |r_i|^2 + sum_{i<j} phi(r_ij) ]                                  (constants dropped)
+         dU/dr_i = beta [ k r_i + sum_{j != i} (phi'(r_ij) / r_ij) (r_i - r_j) ]
+       pair code 0, Lennard-Jones:  phi(r) = eps [ (r_m / r)^12 - 2 (r_m / r)^6 ], minimum -eps at r_m, evaluated from
+       s = r^2 alone (no square root);  pair code 1, double well:  phi(r) = a (r - r0) + b (r - r0)^2 + c (r - r0)^4.
+       n_components = P;  a -> one 16-byte aligned block of 8 fp32 in device memory:
+         (pair code, D, beta k, q0, q1, q2, q3, 0)  with  (q0 .. q3) = (beta eps, r_m^2, 0, 0)  for Lennard-Jones and
+         (beta a, beta b, beta c, r0)  for the double well;  b, a_scalar, b_scalar unused.  beta = 1 / temperature is
+       folded in by the caller (ParticleSystem does it in fp64).  The check sees host values only: D is d / P, and the
+       block's D is not read.  A NULL a, P < 2, or d that is not P D with D in 1 .. 3 is NFMC_EINVAL; a misaligned a is
+       NFMC_EALIGN; d > 1024 is NFMC_EUNSUPPORTED.  Two coincident particles (s = 0): Lennard-Jones gives U = inf and a
+       NaN force, the samplers reject the state and count its log ratio as non-finite; the double well contributes
+       phi(0) and zero force.  k > 0 is the caller's business: the pair terms are translation invariant, so without
+       the trap the density is improper.  Cost: P (P - 1) pair evaluations per chain and gradient (every unordered
+       pair twice, once per owner: no atomics, bitwise repeatable).  LDS: one row of DP + 4 floats per chain.
+       Served by nfmc_mala_steps_f32 / nfmc_hmc_steps_f32 (general kernels, with or without a jump tail, device warmup
+       tuning included), by the register-layout kernels of nfmc_flow_mh_steps_f32 and by the VALU NeuTra kernels
+       (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32 with conditioners of at most 32 units).
+       NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the fit kernels, the Philox4x32-7 stream and the
+       NeuTra matrix-core kernels (conditioners wider than 32). */
 };
 
 typedef struct {
@@ -209,6 +231,7 @@ typedef struct {
                              NFMC_POT_ROSENBROCK: block length; NFMC_POT_STOCHASTIC_VOLATILITY: T = d - 3;
                              NFMC_POT_SPARSE_LOGISTIC_REGRESSION: N; NFMC_POT_LATTICE_PHI4: W (sites per lattice row);
                              NFMC_POT_ITEM_RESPONSE: S (students); NFMC_POT_VARYING_EFFECTS: C (groups);
+                             NFMC_POT_PARTICLES: P (particles);
                              0 for the other kinds (was `reserved`, same layout) */
     const float* a; /* (d,) or NULL -> a_scalar */
     const float* b; /* (d,) or NULL -> b_scalar */

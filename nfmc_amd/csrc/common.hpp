@@ -515,6 +515,20 @@ inline int check_vfx(const NfmcPotential& p, int d) {
     return NFMC_OK;
 }
 
+// Interacting particles (kind 11): the exchange block of a workgroup is one row of DP + 4 floats for each of its
+// kBlock / LPC chains, the block of kind 9 (ParticlePot)
+__host__ __device__ inline int particles_floats(int dp, int cpl) { return irt_floats(dp, cpl); }
+
+// argument check of a kind-11 descriptor: the parameter block present, P = n_components >= 2 particles of D = d / P in
+// 1 .. 3 dimensions with d = P D (the check sees host values only, so D is recovered from d), the block 16-byte aligned;
+// d > 1024 is a valid request no kernel runs
+inline int check_particles(const NfmcPotential& p, int d) {
+    if (!p.a || p.n_components < 2 || d < p.n_components || d % p.n_components != 0 || d / p.n_components > 3) return NFMC_EINVAL;
+    if ((((uintptr_t)p.a) & 15u) != 0) return NFMC_EALIGN;
+    if (d > 1024) return NFMC_EUNSUPPORTED;
+    return NFMC_OK;
+}
+
 // LDS bytes a register-layout kernel with DP = CPL * LPC padded coordinates stages for `p` beside its flow image
 inline size_t mixture_bytes(const NfmcPotential& p, int dp, int) { return (size_t)mixture_floats(p.n_components, dp) * sizeof(float); }
 inline size_t logreg_bytes(const NfmcPotential&, int dp, int) { return (size_t)logreg_floats(dp) * sizeof(float); }
@@ -522,6 +536,7 @@ inline size_t fullrank_bytes(const NfmcPotential&, int, int) { return (size_t)kL
 inline size_t slr_bytes(const NfmcPotential&, int dp, int) { return (size_t)slr_floats(dp) * sizeof(float); }
 inline size_t phi4_bytes(const NfmcPotential&, int, int cpl) { return (size_t)phi4_floats(cpl) * sizeof(float); }
 inline size_t irt_bytes(const NfmcPotential&, int dp, int cpl) { return (size_t)irt_floats(dp, cpl) * sizeof(float); }
+inline size_t particles_bytes(const NfmcPotential&, int dp, int cpl) { return (size_t)particles_floats(dp, cpl) * sizeof(float); }
 
 // ------------------------------------------------------------------------------------------------
 // The potential kinds, as the host sees them: one row per NFMC_POT_* value, indexed by it.  Every entry point that asks
@@ -537,6 +552,10 @@ inline size_t irt_bytes(const NfmcPotential&, int dp, int cpl) { return (size_t)
 //      must not rely on workgroup barriers inside prepare() unless every thread of the workgroup calls it equally often
 //      (LogRegPot's rule).  A class that reads its data straight from global memory (VaryEffPot) has kStaged = false,
 //      the three-argument init(p, g, d) and nullptr for the *_bytes function in its row.
+//      A class in which every coordinate meets every other (ParticlePot) exchanges the chain's state through a
+//      wave-private LDS row like Phi4Pot and IrtPot; its number of registers depends on how many objects a lane owns,
+//      which depends on a run-time shape (D): dispatch on that shape ONCE per prepare(), outside the loops, to bodies
+//      with compile-time bounds, or a register array indexed by it goes to scratch memory.
 //   3. own_units: a line in NFMC_FOR_OWN_UNIT_POT and four units that instantiate launch_{mala,hmc}_kind and
 //      launch_b_kind{,_rqs} for the class (sampler_slr_mala.hip and its three siblings are the pattern).  The build
 //      picks up every .hip file of this directory; a unit that takes a minute or more also goes into SLOW_FIRST
@@ -568,6 +587,7 @@ constexpr PotKind kPotKinds[] = {
     {NFMC_POT_LATTICE_PHI4, check_phi4, phi4_bytes, true, true, true, true},
     {NFMC_POT_ITEM_RESPONSE, check_irt, irt_bytes, true, true, true, true},
     {NFMC_POT_VARYING_EFFECTS, check_vfx, nullptr, true, true, true, true},
+    {NFMC_POT_PARTICLES, check_particles, particles_bytes, true, true, true, true},
 };
 constexpr int kNumPotKinds = (int)(sizeof(kPotKinds) / sizeof(PotKind));
 constexpr bool pot_kinds_indexed(int i = 0) { return i == kNumPotKinds || (kPotKinds[i].kind == i && pot_kinds_indexed(i + 1)); }
@@ -581,7 +601,7 @@ constexpr const PotKind* pot_kind(int kind) { return kind >= 0 && kind < kNumPot
     M(NFMC_POT_GAUSSIAN_FULL, GaussFullPot) M(NFMC_POT_ROSENBROCK, RosenbrockPot) \
     M(NFMC_POT_STOCHASTIC_VOLATILITY, SVPot) M(NFMC_POT_SPARSE_LOGISTIC_REGRESSION, SparseLogRegPot) \
     M(NFMC_POT_LATTICE_PHI4, Phi4Pot) M(NFMC_POT_ITEM_RESPONSE, IrtPot) \
-    M(NFMC_POT_VARYING_EFFECTS, VaryEffPot)
+    M(NFMC_POT_VARYING_EFFECTS, VaryEffPot) M(NFMC_POT_PARTICLES, ParticlePot)
 
 // The families of kernels that take a potential descriptor of any kind.  (The entry points that run kinds 0 and 1 only
 // say so themselves.)
@@ -1769,6 +1789,156 @@ struct VaryEffPot {
         }
         cx.u = first ? u + ug : u;
         return cx;
+    }
+    __device__ __forceinline__ float grad(const Ctx& cx, int i, float) const { return cx.gr[i]; }
+    __device__ __forceinline__ float term(const Ctx& cx, int i, float) const { return i == 0 ? cx.u : 0.f; }
+};
+
+// One pair of particles at squared distance s: e = beta phi(r) and w = beta phi'(r) / r, the factor of (r_i - r_j) in
+// the force.  Lennard-Jones (p0 = beta eps, p1 = r_m^2) from s alone, t = r_m^2 / s:  e = p0 t^3 (t^3 - 2),
+// w = -12 p0 t^3 (t^3 - 1) / s; at s = 0 e = inf and w (r_i - r_j) = NaN: the samplers reject the state.  Double well
+// (p0 .. p2 = beta (a, b, c), p3 = r0) with u = sqrt(s) - r0:  e = u (p0 + u (p1 + p2 u^2)), w = (p0 + u (2 p1 + 4 p2
+// u^2)) / sqrt(s), and w = 0 at s = 0.  Shared by ParticlePot and particles_value_grad_row (neutra_kernels.hpp).
+template <bool LJ>
+__device__ __forceinline__ void particle_pair(float s, float p0, float p1, float p2, float p3, float& e, float& w) {
+    if constexpr (LJ) {
+        const float is = __builtin_amdgcn_rcpf(s), t = p1 * is, t3 = t * t * t;
+        const float pt = p0 * t3;
+        e = pt * (t3 - 2.f);
+        w = -12.f * pt * (t3 - 1.f) * is;
+    } else {
+        const float u = __builtin_amdgcn_sqrtf(s) - p3, u2 = u * u;
+        e = u * fmaf(u, fmaf(p2, u2, p1), p0);
+        w = s > 0.f ? fmaf(u, fmaf(4.f * p2, u2, 2.f * p1), p0) * __builtin_amdgcn_rsqf(s) : 0.f;
+    }
+}
+
+// Interacting particles (NFMC_POT_PARTICLES; P = p.n_components particles in D = d / P dimensions, particle-major
+// x = [r_0 | .. | r_{P-1}]; p.a = (pair code 0 Lennard-Jones / 1 double well, D, beta k, four pair parameters, 0)):
+//   U = 1/2 beta k sum_i |r_i|^2 + sum_{i<j} beta phi(r_ij),   dU/dr_i = beta k r_i + sum_{j != i} w(r_ij) (r_i - r_j)
+// (particle_pair).  Every coordinate meets every other, and a particle's D coordinates straddle register quads and
+// lanes, so the chain's state goes through a wave-private LDS row as in IrtPot (one row of DP + 4 floats per chain,
+// particles_floats; the pitch for IrtPot's bank reason: the reads below are the same broadcasts).  prepare() stores the
+// lane's quads into the row (ds_write_b128).  Particle p belongs to lane p % LPC of its chain: lane g owns particles g,
+// g + LPC, .., at most NP = ceil(CPL / D) of them (P D <= CPL LPC), keeps their positions and forces in registers and
+// loops j = 0 .. P-1 -- a uniform trip count; r_j is read from the row at an address all lanes of the chain share, a
+// broadcast -- adding w (r_p - r_j) to the force of each owned p and 1/2 beta phi to its share of U.  An unordered pair
+// is evaluated twice, once per owner: no atomics and a fixed summation order, so runs are bitwise repeatable.  j = p
+// and owned slots p >= P are taken out by a select on w and e, not by a branch; slot m is skipped when no lane of the
+// wave owns a particle in it (m LPC >= P, uniform).  D and the pair form are wave-uniform and chosen ONCE, outside the
+// loops (pairs<D, LJ>): NP and the register arrays have compile-time bounds.  After the loop the owners write their
+// forces over their particles' slots in the row -- every read of a position is behind them: one wave, LDS operations
+// complete in order, a fence between -- and each lane reads back the quads it holds as the pair part of dU/dx and adds
+// the trap term from its own registers.  Padding coordinates (c >= d) get a zero gradient and add zero to U.  No
+// workgroup barrier (LogRegPot's rule); wavefront fences as in Phi4Pot.  term() puts the lane's share of U on register 0.
+template <int CPL, int LPC, bool FAST>
+struct ParticlePot {
+    static constexpr bool kQuadratic = false;
+    static constexpr bool kStaged = true;
+    static constexpr int DP = CPL * LPC;
+    static constexpr int Q = CPL / 4;    // register quads
+    static constexpr int PITCH = DP + 4;
+    float* row;                          // LDS: this chain's row
+    int np, nd, dd;                      // P, D, d
+    bool lj;
+    float bk, p0, p1, p2, p3;            // beta k and the pair parameters
+    struct Ctx {
+        float u;                         // this lane's share of U
+        float gr[CPL];                   // dU/dx of this lane's coordinates
+    };
+
+    __device__ __forceinline__ static void order() {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+    __device__ __forceinline__ static void stage(float*, const NfmcPotential&, int) {}   // the rows are the lanes' own
+    __device__ __forceinline__ void init(const NfmcPotential& p, int, int d, float* lds) {
+        row = lds + (int)(threadIdx.x / LPC) * PITCH;
+        np = p.n_components;
+        dd = d;
+        nd = d / np;
+        lj = p.a[0] == 0.f;
+        bk = p.a[2];
+        p0 = p.a[3];
+        p1 = p.a[4];
+        p2 = p.a[5];
+        p3 = p.a[6];
+    }
+    template <int D, bool LJ>
+    __device__ __forceinline__ Ctx pairs(const float (&x)[CPL], int g) const {
+        constexpr int NP = (CPL + D - 1) / D;   // owned particles per lane, at most
+        order();   // behind the reads of the previous evaluation
+#pragma unroll
+        for (int k = 0; k < Q; ++k)
+            *reinterpret_cast<float4*>(row + 4 * (k * LPC + g)) = make_float4(x[4 * k], x[4 * k + 1], x[4 * k + 2], x[4 * k + 3]);
+        order();   // the wave's stores precede its reads
+        float rp[NP][D], f[NP][D], e = 0.f;
+#pragma unroll
+        for (int m = 0; m < NP; ++m) {
+            const int own = min(m * LPC + g, np - 1);   // a slot past P reads particle P - 1 and is selected away
+#pragma unroll
+            for (int c = 0; c < D; ++c) {
+                rp[m][c] = row[own * D + c];
+                f[m][c] = 0.f;
+            }
+        }
+#pragma unroll 1
+        for (int j = 0; j < np; ++j) {
+            float rj[D];
+#pragma unroll
+            for (int c = 0; c < D; ++c) rj[c] = row[j * D + c];
+#pragma unroll
+            for (int m = 0; m < NP; ++m) {
+                if (m * LPC < np) {   // uniform
+                    float dx[D], s = 0.f;
+#pragma unroll
+                    for (int c = 0; c < D; ++c) {
+                        dx[c] = rp[m][c] - rj[c];
+                        s = fmaf(dx[c], dx[c], s);
+                    }
+                    float ep, w;
+                    particle_pair<LJ>(s, p0, p1, p2, p3, ep, w);
+                    const int own = m * LPC + g;
+                    const bool on = own != j && own < np;
+                    e += on ? ep : 0.f;
+                    w = on ? w : 0.f;
+#pragma unroll
+                    for (int c = 0; c < D; ++c) f[m][c] = fmaf(w, dx[c], f[m][c]);
+                }
+            }
+        }
+        order();   // every read of a position precedes the owners' stores
+#pragma unroll
+        for (int m = 0; m < NP; ++m) {
+            const int own = m * LPC + g;
+            if (own < np) {
+#pragma unroll
+                for (int c = 0; c < D; ++c) row[own * D + c] = f[m][c];
+            }
+        }
+        order();   // the owners' stores precede the reads below
+        Ctx cx;
+        float u = 0.5f * e;
+#pragma unroll
+        for (int k = 0; k < Q; ++k) {
+            const float4 t4 = *reinterpret_cast<const float4*>(row + 4 * (k * LPC + g));
+            const float t[4] = {t4.x, t4.y, t4.z, t4.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int i = 4 * k + j;
+                const bool in = 4 * (k * LPC + g) + j < dd;
+                const float xv = x[i], kx = bk * xv;
+                cx.gr[i] = in ? kx + t[j] : 0.f;
+                u += in ? 0.5f * kx * xv : 0.f;
+            }
+        }
+        order();   // the next evaluation's stores stay behind these reads
+        cx.u = u;
+        return cx;
+    }
+    __device__ __forceinline__ Ctx prepare(const float (&x)[CPL], int g, int) const {
+        if (lj) return nd == 3 ? pairs<3, true>(x, g) : (nd == 2 ? pairs<2, true>(x, g) : pairs<1, true>(x, g));
+        return nd == 3 ? pairs<3, false>(x, g) : (nd == 2 ? pairs<2, false>(x, g) : pairs<1, false>(x, g));
     }
     __device__ __forceinline__ float grad(const Ctx& cx, int i, float) const { return cx.gr[i]; }
     __device__ __forceinline__ float term(const Ctx& cx, int i, float) const { return i == 0 ? cx.u : 0.f; }

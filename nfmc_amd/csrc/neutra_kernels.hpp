@@ -430,6 +430,54 @@ __device__ __forceinline__ float vfx_value_grad_row(const float* __restrict__ ro
     return u;
 }
 
+// Interacting particles (NFMC_POT_PARTICLES) for the row of one chain, as potential_value_grad_row: U and dU/dx of
+// ParticlePot (common.hpp), P = n_components particles of D = d / P coordinates each, particle-major.  A double loop:
+// the position and the force of particle i stay in registers over j (three components; those past D are zero and add
+// nothing to s), r_j is read from the lane's own LDS row, the pair j = i is taken out by a select, every unordered
+// pair is evaluated twice and 1/2 phi added each time.  D, the pair form and the parameters are wave-uniform; the pair
+// form is chosen outside the j loop.  Kept out of potential_value_grad_row, which the fit and DLMC kernels share and
+// which never see kind 11.
+template <bool LJ>
+__device__ __forceinline__ float particles_force_row(const float* __restrict__ row, int np, int D, int i, float a0, float a1,
+                                                     float a2, float p0, float p1, float p2, float p3, float& f0, float& f1,
+                                                     float& f2) {
+    float e = 0.f;
+    f0 = f1 = f2 = 0.f;
+    for (int j = 0; j < np; ++j) {
+        const float* __restrict__ rj = row + j * D;
+        const float d0 = a0 - rj[0], d1 = D > 1 ? a1 - rj[1] : 0.f, d2 = D > 2 ? a2 - rj[2] : 0.f;
+        const float s = fmaf(d2, d2, fmaf(d1, d1, d0 * d0));
+        float ep, w;
+        particle_pair<LJ>(s, p0, p1, p2, p3, ep, w);
+        e += j != i ? ep : 0.f;
+        w = j != i ? w : 0.f;
+        f0 = fmaf(w, d0, f0);
+        f1 = fmaf(w, d1, f1);
+        f2 = fmaf(w, d2, f2);
+    }
+    return e;
+}
+__device__ __forceinline__ float particles_value_grad_row(const float* __restrict__ row, float* __restrict__ grow,
+                                                          const NfmcPotential& p, int d) {
+    const int np = p.n_components, D = d / np;
+    const bool lj = p.a[0] == 0.f;
+    const float bk = p.a[2], p0 = p.a[3], p1 = p.a[4], p2 = p.a[5], p3 = p.a[6];
+    float u = 0.f, e = 0.f;
+    for (int i = 0; i < np; ++i) {
+        const float* __restrict__ ri = row + i * D;
+        const float a0 = ri[0], a1 = D > 1 ? ri[1] : 0.f, a2 = D > 2 ? ri[2] : 0.f;
+        float f0, f1, f2;
+        e += lj ? particles_force_row<true>(row, np, D, i, a0, a1, a2, p0, p1, p2, p3, f0, f1, f2)
+                : particles_force_row<false>(row, np, D, i, a0, a1, a2, p0, p1, p2, p3, f0, f1, f2);
+        float* __restrict__ gi = grow + i * D;
+        gi[0] = fmaf(bk, a0, f0);
+        if (D > 1) gi[1] = fmaf(bk, a1, f1);
+        if (D > 2) gi[2] = fmaf(bk, a2, f2);
+        u = fmaf(0.5f * bk, fmaf(a2, a2, fmaf(a1, a1, a0 * a0)), u);
+    }
+    return fmaf(0.5f, e, u);
+}
+
 // U~(z) and grad U~(z) for this lane's chain.  zrow: latent (tile columns in latent order), read only;
 // wrow: scratch, ends holding z again (rebuilt); grow: gradient in the same column order as zrow.
 template <int HP>
@@ -445,6 +493,7 @@ __device__ __forceinline__ float adjusted_potential_grad_row(const float* __rest
                     : pot.kind == NFMC_POT_LATTICE_PHI4 ? phi4_value_grad_row(wrow, grow, pot, g.d)
                     : pot.kind == NFMC_POT_ITEM_RESPONSE ? irt_value_grad_row(wrow, grow, pot, g.d)
                     : pot.kind == NFMC_POT_VARYING_EFFECTS ? vfx_value_grad_row(wrow, grow, pot, g.d)
+                    : pot.kind == NFMC_POT_PARTICLES ? particles_value_grad_row(wrow, grow, pot, g.d)
                                                          : potential_value_grad_row(wrow, grow, pot, g.d);  // U(x), dU/dx (neutra.py:62)
     // reverse sweep, mirror image of flow_inverse_row
     for (int c = 0; c < g.d; ++c) {                               // EA0^-1

@@ -346,7 +346,7 @@ class JumpNFMC(Sampler):
                              'never' if (self.fuse in off or getattr(inner, 'fuse', 'auto') in off) else 'auto', run.x,
                              family='mcmc')
         fused = pot is not None and flow_is_native(flow) and pot.fused_in('flow_mh')
-        tail_ok = (self.fuse_jump_tail and fused and flow_fits_jump_tail(flow) and not self.params.fit_nf
+        tail_ok = (self.fuse_jump_tail and fused and pot.jump_tail_ok() and flow_fits_jump_tail(flow) and not self.params.fit_nf
                    and isinstance(inner, (MALA, ULA, HMC, UHMC)))
         inner._cur_run = run
         inner._n_divergences = 0
