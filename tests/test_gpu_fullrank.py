@@ -15,14 +15,15 @@ d in {1, 3, 8, 25, 64, 130, 256, 512} covers every (CPL, LPC) layout choose_cfg 
 d = 512 in the jump-tail-free kernels: (8, 64)) and tiles of 1024 rows (d <= 4) down to 8 rows (d = 512), so that
 Lambda streams through up to 64 tiles per evaluation.
 """
-import ctypes as C
+import functools
 import math
 
-import numpy as np
 import pytest
 import torch
 
+import target_harness as H
 from fullrank_fp64 import FullRankU64, draw, spd
+from target_harness import Spy as _Spy, flow_pair as _flow_pair
 
 pytestmark = pytest.mark.gpu
 
@@ -56,45 +57,19 @@ def _lmax(ref):
     return float(torch.linalg.eigvalsh(ref.lam).max())
 
 
-def _compare(got, tr, what):
-    want = tr.stacked().float()
-    n = want.shape[1]
-    keep = torch.ones(n, dtype=torch.bool)
-    if tr.log_ratios:
-        lr = torch.stack([v.reshape(-1).double() for v in tr.log_ratios])
-        lu = torch.stack([v.reshape(-1).double() for v in tr.uniforms])
-        keep = ((lu - lr).abs() >= MARGIN).all(0)
-    excluded = 1.0 - float(keep.float().mean())
-    print('%s: %.1f %% of the chains excluded as near-ties' % (what, 100 * excluded))
-    assert excluded < 0.10, (what, excluded)
-    assert torch.isfinite(got).all()
-    np.testing.assert_allclose(got[:, keep].numpy(), want[:, keep].numpy(), atol=ATOL, rtol=RTOL, err_msg=what)
+def _record(d, seed, n, x0_seed, cond=None):
+    """the problem as the harness takes it: the restatement is the oracle's target"""
+    pot, ref = _problem(d, seed, cond)
+    return H.Problem(pot, ref, ref, _x0(ref, n, x0_seed), d, 'd=%d' % d)
 
 
-def _sampler(kind, d, pot, T, h, L=5, imd=None):
-    from nfmc_amd.samplers import mcmc
-    if kind in ('mala', 'ula'):
-        cls = mcmc.MALA if kind == 'mala' else mcmc.ULA
-        s = cls((d,), pot, mcmc.LangevinKernel(event_size=d, step_size=h), mcmc.LangevinParameters(n_iterations=T))
-    elif kind == 'mh':
-        s = mcmc.MH((d,), pot, None, mcmc.MHParameters(n_iterations=T))
-        s.kernel.inv_mass_diag = imd.float()
-    else:
-        cls = mcmc.HMC if kind == 'hmc' else mcmc.UHMC
-        s = cls((d,), pot, mcmc.HMCKernel(event_size=d, n_leapfrog_steps=L, step_size=h),
-                mcmc.HMCParameters(n_iterations=T))
-    return s
+_compare = functools.partial(H.compare_states, margin=MARGIN, atol=ATOL, rtol=RTOL)
+_sampler = functools.partial(H.mcmc_sampler, imd_kinds=('mh',))      # Langevin and HMC keep the unit mass diagonal
+_oracle = functools.partial(H.oracle_trace, imd_kinds=('mh',))
 
 
 def _mh_scale(d, ref):
     return torch.full((d,), 0.5 / math.sqrt(d * _lmax(ref)), dtype=torch.float64)
-
-
-def _oracle(kind, x0, target, T, h, noise, L=5, imd=None):
-    from oracle import samplers as osamp
-    okind = {'mala': 'langevin', 'ula': 'langevin', 'mh': 'mh', 'hmc': 'hmc', 'uhmc': 'hmc'}[kind]
-    return osamp.mcmc_sample(x0.double(), target, okind, T, h, n_leapfrog=L, adjustment=kind not in ('ula', 'uhmc'),
-                             noise=noise, inv_mass_diag=imd if kind == 'mh' else None)
 
 
 def _step(kind, d, ref):
@@ -106,122 +81,32 @@ def _step(kind, d, ref):
     return {'mala': 0.5, 'ula': 0.1, 'mh': 0.0}[kind] * d ** (-1 / 3) / lm
 
 
-class _Record:
-    """Hands every fused mcmc launch of `sampler` mask and log-ratio buffers and keeps them (T, n)."""
-
-    def __init__(self, monkeypatch, sampler):
-        self.masks, self.log_ratios = [], []
-        cls = type(sampler)
-        orig = cls._launch
-
-        def launch(s, run, pot, k, step0, samples, masks_out=None, log_ratio_out=None, **kw):
-            if masks_out is None:
-                masks_out = torch.zeros(k, run.n, dtype=torch.uint8, device=run.dev)
-            if log_ratio_out is None:
-                log_ratio_out = torch.zeros(k, run.n, dtype=torch.float32, device=run.dev)
-            self.masks.append(masks_out)
-            self.log_ratios.append(log_ratio_out)
-            return orig(s, run, pot, k, step0, samples, masks_out=masks_out, log_ratio_out=log_ratio_out, **kw)
-        monkeypatch.setattr(cls, '_launch', launch)
-
-    def stacked(self):
-        return torch.cat(self.masks).cpu().bool(), torch.cat(self.log_ratios).cpu()
-
-
-def _compare_decisions(rec, tr, kind, x0, ref, what):
-    """Accept masks and log ratios against the oracle's on the rows before a chain's first disagreeing decision.  Log
-    ratios to 2e-4 max(1, d / 64) + 1e-4 |log r| + 8 ulp(fp32) |U(x)|: the kernel's U(x) and U(x') are fp32 sums of d^2
-    products, so their difference cannot be closer than a few of their ulps."""
-    got_m, got_lr = rec.stacked()
-    if kind in ('ula', 'uhmc'):
-        assert bool(got_m.all()), what
-        return
-    want_m = torch.stack([m.reshape(-1).bool() for m in tr.masks])
-    want_lr = torch.stack([v.reshape(-1).double() for v in tr.log_ratios])
-    assert got_m.shape == want_m.shape, (got_m.shape, want_m.shape)
-    same = got_m == want_m
-    agree = torch.cumprod(torch.cat([torch.ones(1, same.shape[1], dtype=torch.bool), same[:-1]]).int(), 0).bool()
-    assert float(agree.float().mean()) > 0.9, what
-    assert float(same[agree].float().mean()) > 0.97, what
-    d = x0.shape[1]
-    states = tr.stacked()
-    prev = torch.cat([x0.double()[None], states[:-1].double()])
-    u_prev = ref(prev.reshape(-1, d)).reshape(prev.shape[:2])
-    err = (got_lr.double() - want_lr).abs()
-    tol = 2e-4 * max(1.0, d / 64) + 1e-4 * want_lr.abs() + 8 * 2.0 ** -24 * u_prev.abs()
-    print('%s: worst log-ratio error %.2e' % (what, float(err[agree].max())))
-    assert bool((err[agree] <= tol[agree]).all()), (what, float(err[agree].max()))
-
-
-class _Spy:
-    """Counts the split-path transitions of the mcmc samplers (none on the fused route)."""
-
-    def __init__(self, monkeypatch):
-        from nfmc_amd.samplers import mcmc
-        self.calls = []
-        orig = mcmc.MCMCSampler._split_step
-        monkeypatch.setattr(mcmc.MCMCSampler, '_split_step',
-                            lambda s, *a, **k: self.calls.append(1) or orig(s, *a, **k))
-
-
 KINDS = ['mala', 'ula', 'mh', 'hmc', 'uhmc']
 DIMS = [1, 3, 8, 25, 64, 130, 256, 512]
+
+
+def _against_oracle(check, monkeypatch, kind, p, T, **kw):
+    """Log ratios: the kernel's U(x) and U(x') are fp32 sums of d^2 products, so their difference cannot be closer than a
+    few of their ulps (H.compare_decisions)."""
+    d = p.d
+    h, imd = _step(kind, d, p.ref), _mh_scale(d, p.ref)
+    check(monkeypatch, p, kind, T, _sampler(kind, d, p.pot, T, h, imd=imd),
+          lambda noise: _oracle(kind, p.x0, p.target, T, h, noise, imd=imd), compare=_compare, decisions=H.compare_decisions, **kw)
 
 
 # ------------------------------------------------------------------------- 1. fused kernels vs fp64 oracle, replayed noise
 @pytest.mark.parametrize('kind', KINDS)
 @pytest.mark.parametrize('d', DIMS)
 def test_mcmc_replay_matches_oracle(dev, monkeypatch, kind, d):
-    from oracle import samplers as osamp
-    from nfmc_amd.samplers import mcmc
-    n, T = 96, 4
-    pot, ref = _problem(d, 10 * d + 1)
-    x0 = _x0(ref, n, d + 2)
-    h = _step(kind, d, ref)
-    imd = _mh_scale(d, ref)
-    s = _sampler(kind, d, pot, T, h, imd=imd)
-    rec = osamp.RecordingNoise(osamp.TorchNoise())
-    torch.manual_seed(d)
-    tr = _oracle(kind, x0, ref, T, h, rec, imd=imd)
-    s.replay = (torch.stack([v.float() for v in rec.normals]),
-                torch.stack([v.float() for v in rec.uniforms]) if rec.uniforms else None)
-    assert mcmc.resolve_target(pot, (d,), family='mcmc') is pot
-    spy = _Spy(monkeypatch)
-    rec_k = _Record(monkeypatch, s)
-    out = s.sample(x0, show_progress=False)
-    assert not spy.calls                                       # every transition on the fused kernel
-    _compare(out.samples.reshape(T, n, d), tr, '%s d=%d' % (kind, d))
-    _compare_decisions(rec_k, tr, kind, x0, ref, '%s d=%d' % (kind, d))
+    _against_oracle(H.replay_matches_oracle, monkeypatch, kind, _record(d, 10 * d + 1, 96, d + 2), 4, torch_seed=d,
+                    what='%s d=%d' % (kind, d))
 
 
 # ------------------------------------------------------------------------- 2. native Philox streams
 @pytest.mark.parametrize('kind,d', [('mala', 25), ('ula', 8), ('mh', 130), ('hmc', 64), ('uhmc', 3), ('hmc', 512)])
 def test_mcmc_native_stream_matches_oracle(dev, monkeypatch, kind, d):
-    from oracle import samplers as osamp
-    n, T, seed = 160, 5, 777 + d
-    pot, ref = _problem(d, 7 * d + 3)
-    x0 = _x0(ref, n, d)
-    h = _step(kind, d, ref)
-    imd = _mh_scale(d, ref)
-    s = _sampler(kind, d, pot, T, h, imd=imd)
-    s.seed = seed
-    spy = _Spy(monkeypatch)
-    rec_k = _Record(monkeypatch, s)
-    out = s.sample(x0, show_progress=False)
-    assert not spy.calls
-    tr = _oracle(kind, x0, ref, T, h, osamp.PhiloxNoise(seed, dtype=torch.float64), imd=imd)
-    _compare(out.samples.reshape(T, n, d), tr, 'native %s d=%d' % (kind, d))
-    _compare_decisions(rec_k, tr, kind, x0, ref, 'native %s d=%d' % (kind, d))
-
-
-def _flow_pair(d, seed=5, n_hidden=None):
-    from nfmc_amd.flows import Flow, RealNVP
-    from oracle import flow as oflow
-    ck = {} if n_hidden is None else {'conditioner_kwargs': {'n_hidden': n_hidden}}
-    of = oflow.perturb_(oflow.Flow(oflow.RealNVP((d,), **ck)), seed, 0.2, 0.7071)
-    f = Flow(RealNVP((d,), **ck))
-    f.load_state_dict(of.state_dict())
-    return f, of.double()
+    _against_oracle(H.native_matches_oracle, monkeypatch, kind, _record(d, 7 * d + 3, 160, d), 5, seed=777 + d,
+                    what='native %s d=%d' % (kind, d))
 
 
 @pytest.mark.parametrize('fuse_tail', [False, True])
@@ -229,299 +114,78 @@ def _flow_pair(d, seed=5, n_hidden=None):
 def test_jump_mala_native_stream_matches_oracle(dev, monkeypatch, fuse_tail, d):
     """A mildly correlated target (cond 4): the jump proposals of a perturbed identity-like flow must be accepted often
     enough for the comparison to cover the flow-MH step."""
-    from nfmc_amd.containers import NFMCKernel
-    from nfmc_amd.samplers import jump, mcmc
-    from oracle import samplers as osamp
-    n, T, Kin, seed = 192, 3, 4, 31337
-    pot, ref = _problem(d, 3 * d + 5, cond=4.0)
-    x0 = _x0(ref, n, 3)
-    f, of = _flow_pair(d)
-    h = 0.3 * d ** (-1 / 3) / _lmax(ref)
-    split, flow_mh = [], []
-    orig, orig_fm = jump.split_flow_mh, jump.launch_flow_mh
-    monkeypatch.setattr(jump, 'split_flow_mh', lambda *a, **k: split.append(1) or orig(*a, **k))
-    monkeypatch.setattr(jump, 'launch_flow_mh', lambda *a, **k: flow_mh.append(1) or orig_fm(*a, **k))
-    spy = _Spy(monkeypatch)
-    s = jump.JumpMALA((d,), pot, NFMCKernel((d,), flow=f), jump.JumpNFMCParameters(n_iterations=T), None,
-                      mcmc.LangevinParameters(n_iterations=Kin))
-    s.inner_sampler.kernel.step_size = h
-    s.seed, s.fuse_jump_tail = seed, fuse_tail
-    out = s.sample(x0, show_progress=False)
-    assert not spy.calls and not split                        # inner loop and jump fused
-    if not fuse_tail:
-        assert len(flow_mh) == T                              # each jump on the flow-MH kernel
-    tr = osamp.jump_sample(x0.double(), ref, of, 'langevin', T, Kin, h, noise=osamp.PhiloxNoise(seed, dtype=torch.float64))
-    got, want = out.samples.reshape(T * (Kin + 1), n, d), tr.stacked().float()
-    same = (got - want).abs().amax(dim=(0, 2)) < ATOL + RTOL * want.abs().amax(dim=(0, 2))
-    assert same.float().mean() > 0.95, float(same.float().mean())
-    assert out.statistics.n_attempted_jumps == n * T
-    assert abs(out.statistics.n_accepted_jumps - tr.n_accepted_jumps) <= max(2, int(0.03 * n * T))
+    n, T = 192, 3
+    p = _record(d, 3 * d + 5, n, 3, cond=4.0)
+    H.jump_mala_matches_oracle(monkeypatch, p, T=T, Kin=4, seed=31337, h=0.3 * d ** (-1 / 3) / _lmax(p.ref), imd=None,
+                               fuse_tail=fuse_tail, spline=False, atol=ATOL, rtol=RTOL, share=0.95,
+                               jump_slack=max(2, int(0.03 * n * T)))
 
 
 @pytest.mark.parametrize('d', [2, 25, 64, 256])
 def test_imh_runs_on_the_sequential_flow_mh_kernel(dev, monkeypatch, d):
-    from nfmc_amd.samplers import imh
-    from oracle import samplers as osamp
-    n, T, seed = 256, 6, 4711 + d
-    pot, ref = _problem(d, 5 * d + 7, cond=4.0)
-    x0 = _x0(ref, n, 9)
-    f, of = _flow_pair(d, 9)
-    s = imh.FixedIMH((d,), pot, imh.IMHKernel((d,), flow=f), imh.IMHParameters(n_iterations=T))
-    s.seed = seed
-    calls = {'launch_imh_parallel': 0, 'launch_flow_mh': 0, 'split_flow_mh': 0}
-
-    def spy(name):
-        fn = getattr(imh, name)
-
-        def wrapped(*a, **k):
-            calls[name] += 1
-            return fn(*a, **k)
-        monkeypatch.setattr(imh, name, wrapped)
-    for name in list(calls):
-        spy(name)
-    out = s.sample(x0, show_progress=False)
-    assert calls['launch_flow_mh'] >= 1 and calls['launch_imh_parallel'] == 0 and calls['split_flow_mh'] == 0, calls
-    assert out.statistics.n_attempted_trajectories == n * T
-    tr = osamp.imh_sample(x0.double(), ref, of, T, noise=osamp.PhiloxNoise(seed, dtype=torch.float64))
-    _compare(out.samples.reshape(T, n, d), tr, 'imh d=%d' % d)
+    H.imh_matches_oracle(monkeypatch, _record(d, 5 * d + 7, 256, 9, cond=4.0), T=6, seed=4711 + d, flow_seed=9, spline=False,
+                         compare=_compare, what='imh d=%d' % d)
 
 
 # ------------------------------------------------------------------------- 3. fused equals split
 @pytest.mark.parametrize('kind,d', [('mala', 25), ('hmc', 9), ('mh', 64)])
 def test_fused_equals_split(dev, monkeypatch, kind, d):
-    n, T = 200, 6
-    pot, ref = _problem(d, 17 * d)
-    x0 = _x0(ref, n, 17)
-    outs, counts = [], []
-    for target, fuse in ((pot, 'auto'), (lambda x: pot(x), 'never')):
-        spy = _Spy(monkeypatch)
-        s = _sampler(kind, d, target, T, _step(kind, d, ref), imd=_mh_scale(d, ref))
-        s.seed, s.fuse = 2024, fuse
-        outs.append(s.sample(x0, show_progress=False))
-        counts.append(len(spy.calls))
-    assert counts == [0, T]
-    a, b = (o.samples.reshape(T, n, d) for o in outs)
-    same = (a - b).abs().amax(dim=(0, 2)) < ATOL
-    assert same.float().mean() > 0.95, float(same.float().mean())
-    np.testing.assert_allclose(a[:, same].numpy(), b[:, same].numpy(), atol=ATOL, rtol=RTOL)
+    T = 6
+    p = _record(d, 17 * d, 200, 17)
+    H.fused_equals_split(monkeypatch, p,
+                         lambda target: _sampler(kind, d, target, T, _step(kind, d, p.ref), imd=_mh_scale(d, p.ref)), T, seed=2024, atol=ATOL, rtol=RTOL, share=0.95)
 
 
 # ------------------------------------------------------------------------- 4. NeuTra (VALU kernels)
-def _neutra_grad(dev, f, pot, z):
-    from nfmc_amd import hip
-    n, d = z.shape
-    st, _keep = f.bijection.packed(dev, 0)          # the flow's own width, as NeuTra presents it for this target
-    pd = pot.descriptor(dev)
-    zd = z.to(dev, torch.float32).contiguous()
-    u = torch.empty(n, device=dev)
-    g = torch.empty(n, d, device=dev)
-    rc = int(hip.lib().nfmc_neutra_potential_grad_f32(C.byref(st), C.byref(pd), hip.ptr(zd), n, hip.ptr(u), hip.ptr(g),
-                                                        hip.stream()))
-    torch.cuda.synchronize()
-    return rc, u.cpu(), g.cpu()
-
-
 @pytest.mark.parametrize('d,nh', [(2, 4), (3, 8), (8, 16), (25, 32), (64, 8), (64, 32), (128, 16), (130, 8), (256, 4)])
 def test_neutra_gradient_matches_fp64_autograd(dev, d, nh):
-    """U~(z) = U(f^-1(z)) - log|det J_{f^-1}(z)| and its gradient from the VALU NeuTra kernel against fp64 autograd
-    through oracle/flow.py, on a perturbed RealNVP (couplings need d >= 2).  d = 64 / 128 are the shapes the matrix-core
-    kernels would take for the other kinds.  Tolerance: relative 2e-4 of (1 + max |.|) per row, fp32 arithmetic through the coupling stack and a
-    d-term dot product per gradient coordinate."""
-    from nfmc_amd import hip
-    from oracle import samplers as osamp
+    """On a perturbed RealNVP (couplings need d >= 2).  d = 64 / 128 are the shapes the matrix-core kernels would take
+    for the other kinds.  Tolerance: relative 2e-4 of (1 + max |.|) per row, fp32 arithmetic through the coupling stack
+    and a d-term dot product per gradient coordinate."""
     pot, ref = _problem(d, 11 * d + nh, cond=100.0)
-    f, of = _flow_pair(d, 3, n_hidden=nh)
-    n = 130
-    z = draw(ref.lam, torch.zeros(d), n, d).requires_grad_(True)
-    u_ref = osamp.neutra_adjusted_target(of, ref, (d,))(z)
-    g_ref, = torch.autograd.grad(u_ref.sum(), z)
-    rc, u, g = _neutra_grad(dev, f, pot, z.detach())
-    assert rc == hip.OK
-    ur = u_ref.detach()
-    np.testing.assert_allclose(u.numpy(), ur.numpy(), atol=2e-4 * (1 + float(ur.abs().max())), rtol=0)
-    err = (g.double() - g_ref).abs().amax(dim=1) / (1 + g_ref.abs().amax(dim=1))
-    print('d=%d H=%d: worst relative gradient error %.2e' % (d, nh, float(err.max())))
-    assert float(err.max()) < 2e-4
+    H.neutra_gradient_matches_autograd(dev, pot, ref, draw(ref.lam, torch.zeros(d), 130, d), nh, 'd=%d H=%d' % (d, nh),
+                                       flow_seed=3, bound=2e-4)
 
 
 @pytest.mark.parametrize('d,nh', [(8, 8), (64, 16), (128, 8)])
 def test_neutra_hmc_fused_matches_oracle(dev, monkeypatch, d, nh):
-    """Fused NeuTra HMC (nfmc_neutra_hmc_steps_f32, VALU kernel, never the split path) against neutra_hmc_sample on the
-    native stream."""
-    from nfmc_amd.samplers import mcmc, neutra
-    from oracle import samplers as osamp
-    n, T, L = 96, 3, 4
-    pot, ref = _problem(d, 13 * d, cond=10.0)
-    h = 0.2 / math.sqrt(_lmax(ref))
-    f, of = _flow_pair(d, 9, n_hidden=nh)
-    z0 = _x0(ref, n, 61)
-    s = neutra.NeuTraHMC((d,), pot, mcmc.HMCKernel(event_size=d, n_leapfrog_steps=L, step_size=h),
-                         mcmc.HMCParameters(), neutra.NeuTraKernel((d,), flow=f), neutra.NeuTraParameters(n_iterations=T))
-    assert s._closed_form() is pot and s._min_hidden() == 0
-    split = []
-    monkeypatch.setattr(s.inner_sampler, 'sample', lambda *a, **k: split.append(1))
-    s.seed = 12
-    out = s.sample(z0, show_progress=False)
-    assert not split
-    tr = osamp.neutra_hmc_sample(z0.double(), ref, of, T, h, None, L, noise=osamp.PhiloxNoise(12, dtype=torch.float64))
-    got, want = out.samples.reshape(T, n, d), tr.stacked().float()
-    same = (got - want).abs().amax(dim=(0, 2)) < 1e-3
-    assert same.float().mean() > 0.93, float(same.float().mean())
-    assert abs(out.statistics.n_accepted_trajectories - tr.n_accepted) <= 6
+    p = _record(d, 13 * d, 96, 61, cond=10.0)
+    H.neutra_hmc_fused_matches_oracle(monkeypatch, p, _flow_pair(d, 9, n_hidden=nh), T=3, L=4, h=0.2 / math.sqrt(_lmax(p.ref)),
+                                      seed=12, atol=1e-3, share=0.93, accept_slack=6)
 
 
 def test_neutra_wide_conditioner_takes_the_split_path_and_matches_the_oracle(dev):
-    """A conditioner of 64 units at d = 64 would run on the matrix cores, which evaluate kinds 0 and 1 only: the run takes
-    the inner sampler's split path (autograd through the flow) and still follows the oracle."""
-    from nfmc_amd import hip
-    from nfmc_amd.samplers import mcmc, neutra
-    from oracle import samplers as osamp
-    d, n, T, L = 64, 96, 3, 4
-    pot, ref = _problem(d, 29, cond=10.0)
-    h = 0.2 / math.sqrt(_lmax(ref))
-    f, of = _flow_pair(d, 9, n_hidden=64)
-    z0 = _x0(ref, n, 62)
-    rc, _u, _g = _neutra_grad(dev, f, pot, z0)
-    assert rc == hip.EUNSUPPORTED
-    s = neutra.NeuTraHMC((d,), pot, mcmc.HMCKernel(event_size=d, n_leapfrog_steps=L, step_size=h),
-                         mcmc.HMCParameters(), neutra.NeuTraKernel((d,), flow=f), neutra.NeuTraParameters(n_iterations=T))
-    split = []
-    orig = s.inner_sampler.sample
-    s.inner_sampler.sample = lambda *a, **k: split.append(1) or orig(*a, **k)
-    s.seed = 12
-    out = s.sample(z0, show_progress=False)
-    assert split == [1]
-    tr = osamp.neutra_hmc_sample(z0.double(), ref, of, T, h, None, L, noise=osamp.PhiloxNoise(12, dtype=torch.float64))
-    got, want = out.samples.reshape(T, n, d), tr.stacked().float()
-    same = (got - want).abs().amax(dim=(0, 2)) < 1e-3
-    assert same.float().mean() > 0.93, float(same.float().mean())
+    d = 64
+    p = _record(d, 29, 96, 62, cond=10.0)
+    H.neutra_wide_takes_the_split_path(dev, p, _flow_pair(d, 9, n_hidden=64), T=3, L=4, h=0.2 / math.sqrt(_lmax(p.ref)), seed=12,
+                                       atol=1e-3, share=0.93)
 
 
 # ------------------------------------------------------------------------- 5. refused entry points, bad descriptors
 def test_refusing_entry_points_answer_unsupported(dev):
     from nfmc_amd import hip
-    from nfmc_amd.samplers import dlmc, imh
-    from nfmc_amd.samplers.common import Run
-    from nfmc_amd.samplers.jump import _flow_mh_probe_args
-    d, n = 64, 256
+    d = 64
     pot, ref = _problem(d, 4)
-    x = _x0(ref, n, 4).to(dev)
-    f, _ = _flow_pair(d)
-    f.to(dev)
     pd = pot.descriptor(dev)
     assert pd.kind == hip.POT_GAUSSIAN_FULL and pd.reserved == d
-    a, _keep = dlmc.step_args(f, x, 0.05, pot=pot)
-    assert int(hip.lib().nfmc_dlmc_step_supported_f32(C.byref(a))) == hip.EUNSUPPORTED
-    s = imh.FixedIMH((d,), pot, imh.IMHKernel((d,), flow=f), imh.IMHParameters(n_iterations=1))
-    run = Run(s, x.cpu())
-    logq = torch.empty(n, device=dev)
-    pa, _k3 = _flow_mh_probe_args(run, f, pot, logq, True)
-    assert int(hip.lib().nfmc_imh_parallel_supported_f32(C.byref(pa))) == hip.EUNSUPPORTED
-    assert int(hip.lib().nfmc_flow_mh_supported_f32(C.byref(pa))) == hip.OK        # the register kernels take it
-    pa.rng.rounds = 7                                                               # the opt-in stream: not for kind 4
-    before = run.x.clone()
-    assert int(hip.lib().nfmc_flow_mh_steps_f32(C.byref(pa), hip.stream())) == hip.EUNSUPPORTED
-    torch.cuda.synchronize()
-    assert torch.equal(run.x, before)
-    # a wide conditioner (one-chain-per-lane / matrix-core flow-MH kernels): refused, never evaluated as a quadratic
-    fw, _ = _flow_pair(d, 5, n_hidden=48)
-    fw.to(dev)
-    pw, _k4 = _flow_mh_probe_args(run, fw, pot, logq, True)
-    assert int(hip.lib().nfmc_flow_mh_supported_f32(C.byref(pw))) == hip.EUNSUPPORTED
-    pw.x, pw.logq, pw.n_steps = hip.ptr(x), hip.ptr(logq), 1
-    before = x.clone()
-    assert int(hip.lib().nfmc_flow_mh_steps_f32(C.byref(pw), hip.stream())) == hip.EUNSUPPORTED
-    # NeuTra on the matrix cores (d = 64, 48 units): the gradient and the trajectory entry points
-    u = torch.full((n,), 123.0, device=dev)
-    gr = torch.full_like(x, 123.0)
-    stw, _k5 = fw.bijection.packed(dev)
-    rc = int(hip.lib().nfmc_neutra_potential_grad_f32(C.byref(stw), C.byref(pd), hip.ptr(x), n, hip.ptr(u), hip.ptr(gr),
-                                                        hip.stream()))
-    assert rc == hip.EUNSUPPORTED
-    na = hip.NfmcNeutraHmcArgs()
-    na.z, na.n, na.n_steps, na.n_leapfrog, na.step_size, na.adjust = hip.ptr(x), n, 1, 2, 0.01, 1
-    na.flow, na.pot = stw, pd
-    na.rng.seed = 3
-    assert int(hip.lib().nfmc_neutra_hmc_steps_f32(C.byref(na), hip.stream())) == hip.EUNSUPPORTED
-    torch.cuda.synchronize()
-    assert torch.equal(x, before) and bool((u == 123.0).all()) and bool((gr == 123.0).all())
-    assert not pot.fused_in('fit') and not pot.fused_in('imh_parallel') and not pot.fused_in('dlmc_step')
+    H.refusing_entry_points(dev, pot, _x0(ref, 256, 4), functools.partial(_flow_pair, d))
 
 
 def test_philox7_and_bad_descriptors_are_refused(dev):
-    """The opt-in Philox4x32-7 stream has no kind-4 kernel; a NULL Lambda or mu, a misaligned Lambda and
-    n_components != d are argument errors, at the mcmc, flow-MH and NeuTra entry points alike.  Nothing is written."""
+    """A NULL Lambda or mu, a misaligned Lambda and n_components != d are argument errors."""
     from nfmc_amd import hip
-    from nfmc_amd.samplers import imh
-    from nfmc_amd.samplers.common import Run
-    from nfmc_amd.samplers.jump import _flow_mh_probe_args
-    d, n = 25, 128
+    d = 25
     pot, ref = _problem(d, 8)
-    x = _x0(ref, n, 8).to(dev)
-    before = x.clone()
-    lam32, mu32 = pot._copy(dev)
-    bad = []
-    for field, value in (('a', 0), ('b', 0), ('a', lam32.data_ptr() + 4), ('reserved', d - 1), ('reserved', d + 1)):
-        p = pot.descriptor(dev)
-        setattr(p, field, value)
-        bad.append(p)
-    a = hip.NfmcMalaArgs()
-    a.x, a.n, a.d, a.n_steps, a.step_size, a.adjust = hip.ptr(x), n, d, 2, 0.01, 1
-    a.pot = pot.descriptor(dev)
-    a.rng.seed, a.rng.rounds = 3, 7
-    assert int(hip.lib().nfmc_mala_steps_f32(C.byref(a), hip.stream())) == hip.EUNSUPPORTED
-    a.rng.rounds = 10
-    for p in bad:
-        a.pot = p
-        assert int(hip.lib().nfmc_mala_steps_f32(C.byref(a), hip.stream())) == hip.EINVAL
-    hm = hip.NfmcHmcArgs()
-    hm.x, hm.n, hm.d, hm.n_steps, hm.step_size, hm.adjust, hm.n_leapfrog = hip.ptr(x), n, d, 2, 0.01, 1, 3
-    hm.rng.seed = 3
-    for p in bad:
-        hm.pot = p
-        assert int(hip.lib().nfmc_hmc_steps_f32(C.byref(hm), hip.stream())) == hip.EINVAL
-    f, _ = _flow_pair(d)
-    f.to(dev)
-    s = imh.FixedIMH((d,), pot, imh.IMHKernel((d,), flow=f), imh.IMHParameters(n_iterations=1))
-    run = Run(s, x.cpu())
-    logq = torch.empty(n, device=dev)
-    pa, _k = _flow_mh_probe_args(run, f, pot, logq, True)
-    st, _k2 = f.bijection.packed(dev)
-    u = torch.empty(n, device=dev)
-    g = torch.empty_like(x)
-    for p in bad:
-        pa.pot = p
-        assert int(hip.lib().nfmc_flow_mh_supported_f32(C.byref(pa))) == hip.EINVAL
-        assert int(hip.lib().nfmc_neutra_potential_grad_f32(C.byref(st), C.byref(p), hip.ptr(x), n, hip.ptr(u), hip.ptr(g),
-                                                              hip.stream())) == hip.EINVAL
-    torch.cuda.synchronize()
-    assert torch.equal(x, before)
+    bad = [('a', 0), ('b', 0), ('a', 'misaligned'), ('reserved', d - 1), ('reserved', d + 1)]
+    H.bad_descriptors_are_refused(dev, pot, _x0(ref, 128, 8), _flow_pair(d)[0], [(f, v, hip.EINVAL) for f, v in bad])
 
 
 # ------------------------------------------------------------------------- 6. determinism and sharding
 @pytest.mark.parametrize('kind', ['mala', 'hmc'])
 def test_determinism_and_sharding(dev, kind):
-    from nfmc_amd.dist import Shard
-    d, n, T = 20, 300, 8
-    pot, ref = _problem(d, 44)
-    x0 = _x0(ref, n, 44)
-    h = _step(kind, d, ref)
-    runs = []
-    for _ in range(2):
-        s = _sampler(kind, d, pot, T, h)
-        s.seed = 7
-        runs.append(s.sample(x0, show_progress=False))
-    assert torch.equal(runs[0].samples, runs[1].samples)
-    assert runs[0].statistics.n_accepted_trajectories == runs[1].statistics.n_accepted_trajectories
-    dense = runs[0].samples.reshape(T, n, d)
-    parts = []
-    for r in range(2):
-        sh = Shard(rank=r, world=2)
-        sh.merge_statistics = lambda s_: s_
-        s = _sampler(kind, d, pot, T, h)
-        s.seed, s.shard = 7, sh
-        parts.append(s.sample(x0, show_progress=False).samples.reshape(T, -1, d))
-    assert torch.equal(torch.cat(parts, 1), dense)
+    d, T = 20, 8
+    p = _record(d, 44, 300, 44)
+    H.determinism_and_sharding(lambda: _sampler(kind, d, p.pot, T, _step(kind, d, p.ref)), p.x0, T, d, seed=7, world=2)
 
 
 def test_sample_api_with_a_two_dimensional_event(dev):

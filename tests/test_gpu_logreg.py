@@ -11,13 +11,15 @@ The (d, N) grid covers every (CPL, LPC) layout the sampler kernels pick (d = 1 .
 N = 1, 63, 64, 65 and 1000, and N past the LDS tile of its layout (4096 / (CPL LPC) rows: 1024 at d <= 4, 8 at d = 512).
 """
 import ctypes as C
+import functools
 import math
 
-import numpy as np
 import pytest
 import torch
 
+import target_harness as H
 from logreg_fp64 import LogRegU64, synthetic
+from target_harness import Spy as _Spy, flow_pair as _flow_pair
 
 pytestmark = pytest.mark.gpu
 
@@ -42,106 +44,29 @@ def _x0(n, d, seed):
     return 0.7 * torch.randn(n, d, generator=torch.Generator().manual_seed(seed))
 
 
-def _compare(got, tr, what):
-    want = tr.stacked().float()
-    n = want.shape[1]
-    keep = torch.ones(n, dtype=torch.bool)
-    if tr.log_ratios:
-        lr = torch.stack([v.reshape(-1).double() for v in tr.log_ratios])
-        lu = torch.stack([v.reshape(-1).double() for v in tr.uniforms])
-        keep = ((lu - lr).abs() >= MARGIN).all(0)
-    excluded = 1.0 - float(keep.float().mean())
-    print('%s: %.1f %% of the chains excluded as near-ties' % (what, 100 * excluded))
-    assert excluded < 0.10, (what, excluded)
-    assert torch.isfinite(got).all()
-    np.testing.assert_allclose(got[:, keep].numpy(), want[:, keep].numpy(), atol=ATOL, rtol=RTOL, err_msg=what)
+def _record(N, d, seed, n, x0_seed):
+    """the problem as the harness takes it: the restatement is the oracle's target"""
+    pot, ref = _problem(N, d, seed)
+    return H.Problem(pot, ref, ref, _x0(n, d, x0_seed), d, 'd=%d N=%d' % (d, N))
+
+
+_compare = functools.partial(H.compare_states, margin=MARGIN, atol=ATOL, rtol=RTOL)
+
+
+def _mh_scale(d):
+    return torch.full((d,), 0.3 / math.sqrt(d), dtype=torch.float64)
 
 
 def _sampler(kind, d, pot, T, h, L=5):
-    from nfmc_amd.samplers import mcmc
-    if kind in ('mala', 'ula'):
-        cls = mcmc.MALA if kind == 'mala' else mcmc.ULA
-        s = cls((d,), pot, mcmc.LangevinKernel(event_size=d, step_size=h), mcmc.LangevinParameters(n_iterations=T))
-    elif kind == 'mh':
-        s = mcmc.MH((d,), pot, None, mcmc.MHParameters(n_iterations=T))
-        s.kernel.inv_mass_diag = torch.full((d,), 0.3 / math.sqrt(d))
-    else:
-        cls = mcmc.HMC if kind == 'hmc' else mcmc.UHMC
-        s = cls((d,), pot, mcmc.HMCKernel(event_size=d, n_leapfrog_steps=L, step_size=h),
-                mcmc.HMCParameters(n_iterations=T))
-    return s
+    return H.mcmc_sampler(kind, d, pot, T, h, L, _mh_scale(d), imd_kinds=('mh',))
 
 
 def _oracle(kind, x0, target, T, h, noise, L=5):
-    from oracle import samplers as osamp
-    okind = {'mala': 'langevin', 'ula': 'langevin', 'mh': 'mh', 'hmc': 'hmc', 'uhmc': 'hmc'}[kind]
-    imd = torch.full((x0.shape[1],), 0.3 / math.sqrt(x0.shape[1]), dtype=torch.float64) if kind == 'mh' else None
-    return osamp.mcmc_sample(x0.double(), target, okind, T, h, n_leapfrog=L, adjustment=kind not in ('ula', 'uhmc'),
-                             noise=noise, inv_mass_diag=imd)
+    return H.oracle_trace(kind, x0, target, T, h, noise, L, _mh_scale(x0.shape[1]), imd_kinds=('mh',))
 
 
 def _step(kind, d):
     return {'mala': 0.3, 'ula': 0.05, 'mh': 0.0, 'hmc': 0.1, 'uhmc': 0.05}[kind] * d ** (-1 / 3)
-
-
-class _Record:
-    """Hands every fused mcmc launch of `sampler` mask and log-ratio buffers and keeps them: the kernel's accept
-    decisions and log ratios, stacked over the launches as (T, n)."""
-
-    def __init__(self, monkeypatch, sampler):
-        self.masks, self.log_ratios = [], []
-        cls = type(sampler)
-        orig = cls._launch
-
-        def launch(s, run, pot, k, step0, samples, masks_out=None, log_ratio_out=None, **kw):
-            if masks_out is None:
-                masks_out = torch.zeros(k, run.n, dtype=torch.uint8, device=run.dev)
-            if log_ratio_out is None:
-                log_ratio_out = torch.zeros(k, run.n, dtype=torch.float32, device=run.dev)
-            self.masks.append(masks_out)
-            self.log_ratios.append(log_ratio_out)
-            return orig(s, run, pot, k, step0, samples, masks_out=masks_out, log_ratio_out=log_ratio_out, **kw)
-        monkeypatch.setattr(cls, '_launch', launch)
-
-    def stacked(self):
-        return torch.cat(self.masks).cpu().bool(), torch.cat(self.log_ratios).cpu()
-
-
-def _compare_decisions(rec, tr, kind, x0, ref, what):
-    """The kernel's accept masks and log ratios against the oracle's, transition by transition, on the rows before a
-    chain's first disagreeing decision (a near-tie flips it; the states test bounds how many).  Log ratios to
-    2e-4 max(1, d / 64) + 1e-4 |log r| + 8 ulp(fp32) |U(x)|: the kernel's U(x) and U(x') are fp32 numbers of that
-    magnitude (a sum of N terms), so their difference cannot be closer than a few of their ulps."""
-    got_m, got_lr = rec.stacked()
-    if kind in ('ula', 'uhmc'):
-        assert bool(got_m.all()), what                        # unadjusted: every proposal kept
-        return
-    want_m = torch.stack([m.reshape(-1).bool() for m in tr.masks])
-    want_lr = torch.stack([v.reshape(-1).double() for v in tr.log_ratios])
-    assert got_m.shape == want_m.shape, (got_m.shape, want_m.shape)
-    same = got_m == want_m
-    agree = torch.cumprod(torch.cat([torch.ones(1, same.shape[1], dtype=torch.bool), same[:-1]]).int(), 0).bool()
-    assert float(agree.float().mean()) > 0.9, what
-    assert float(same[agree].float().mean()) > 0.97, what
-    d = x0.shape[1]
-    states = tr.stacked()
-    prev = torch.cat([x0.double()[None], states[:-1].double()])         # the state each transition starts from
-    u_prev = ref(prev.reshape(-1, d)).reshape(prev.shape[:2])
-    err = (got_lr.double() - want_lr).abs()
-    tol = 2e-4 * max(1.0, d / 64) + 1e-4 * want_lr.abs() + 8 * 2.0 ** -24 * u_prev.abs()
-    print('%s: worst log-ratio error %.2e' % (what, float(err[agree].max())))
-    assert bool((err[agree] <= tol[agree]).all()), (what, float(err[agree].max()))
-
-
-class _Spy:
-    """Counts the split-path transitions of the mcmc samplers (none on the fused route)."""
-
-    def __init__(self, monkeypatch):
-        from nfmc_amd.samplers import mcmc
-        self.calls = []
-        orig = mcmc.MCMCSampler._split_step
-        monkeypatch.setattr(mcmc.MCMCSampler, '_split_step',
-                            lambda s, *a, **k: self.calls.append(1) or orig(s, *a, **k))
 
 
 KINDS = ['mala', 'ula', 'mh', 'hmc', 'uhmc']
@@ -149,140 +74,51 @@ GRID = [(1, 1), (1, 2500), (3, 64), (7, 63), (16, 65), (25, 1000), (32, 200), (6
         (512, 1), (512, 1000), (700, 40)]
 
 
+def _against_oracle(check, monkeypatch, kind, p, T, **kw):
+    """Log ratios: the kernel's U(x) and U(x') are fp32 numbers of the magnitude of U (a sum of N terms), so their
+    difference cannot be closer than a few of their ulps (H.compare_decisions)."""
+    h = _step(kind, p.d)
+    check(monkeypatch, p, kind, T, _sampler(kind, p.d, p.pot, T, h), lambda noise: _oracle(kind, p.x0, p.target, T, h, noise),
+          compare=_compare, decisions=H.compare_decisions, **kw)
+
+
 # ------------------------------------------------------------------------- 1. fused kernels vs fp64 oracle, replayed noise
 @pytest.mark.parametrize('kind', KINDS)
 @pytest.mark.parametrize('d,N', GRID)
 def test_mcmc_replay_matches_oracle(dev, monkeypatch, kind, d, N):
-    from oracle import samplers as osamp
-    from nfmc_amd.samplers import mcmc
-    n, T = 96, 4
-    pot, ref = _problem(N, d, 10 * d + N)
-    x0 = _x0(n, d, d + N)
-    h = _step(kind, d)
-    s = _sampler(kind, d, pot, T, h)
-    rec = osamp.RecordingNoise(osamp.TorchNoise())
-    torch.manual_seed(d + N)
-    tr = _oracle(kind, x0, ref, T, h, rec)
-    s.replay = (torch.stack([v.float() for v in rec.normals]),
-                torch.stack([v.float() for v in rec.uniforms]) if rec.uniforms else None)
-    assert mcmc.resolve_target(pot, (d,), family='mcmc') is pot
-    spy = _Spy(monkeypatch)
-    rec_k = _Record(monkeypatch, s)
-    out = s.sample(x0, show_progress=False)
-    assert not spy.calls                                       # every transition on the fused kernel
-    _compare(out.samples.reshape(T, n, d), tr, '%s d=%d N=%d' % (kind, d, N))
-    _compare_decisions(rec_k, tr, kind, x0, ref, '%s d=%d N=%d' % (kind, d, N))
+    _against_oracle(H.replay_matches_oracle, monkeypatch, kind, _record(N, d, 10 * d + N, 96, d + N), 4, torch_seed=d + N,
+                    what='%s d=%d N=%d' % (kind, d, N))
 
 
 # ------------------------------------------------------------------------- 2. native Philox streams
 @pytest.mark.parametrize('kind,d,N', [('mala', 25, 1000), ('ula', 7, 65), ('mh', 33, 300), ('hmc', 64, 129),
                                       ('uhmc', 16, 1100)])
 def test_mcmc_native_stream_matches_oracle(dev, monkeypatch, kind, d, N):
-    from oracle import samplers as osamp
-    n, T, seed = 160, 5, 777 + d
-    pot, ref = _problem(N, d, 7 * d + N)
-    x0 = _x0(n, d, N)
-    h = _step(kind, d)
-    s = _sampler(kind, d, pot, T, h)
-    s.seed = seed
-    spy = _Spy(monkeypatch)
-    rec_k = _Record(monkeypatch, s)
-    out = s.sample(x0, show_progress=False)
-    assert not spy.calls
-    tr = _oracle(kind, x0, ref, T, h, osamp.PhiloxNoise(seed, dtype=torch.float64))
-    _compare(out.samples.reshape(T, n, d), tr, 'native %s' % kind)
-    _compare_decisions(rec_k, tr, kind, x0, ref, 'native %s' % kind)
-
-
-def _flow_pair(d, seed=5, n_hidden=None):
-    from nfmc_amd.flows import Flow, RealNVP
-    from oracle import flow as oflow
-    ck = {} if n_hidden is None else {'conditioner_kwargs': {'n_hidden': n_hidden}}
-    of = oflow.perturb_(oflow.Flow(oflow.RealNVP((d,), **ck)), seed, 0.2, 0.7071)
-    f = Flow(RealNVP((d,), **ck))
-    f.load_state_dict(of.state_dict())
-    return f, of.double()
+    _against_oracle(H.native_matches_oracle, monkeypatch, kind, _record(N, d, 7 * d + N, 160, N), 5, seed=777 + d,
+                    what='native %s' % kind)
 
 
 @pytest.mark.parametrize('fuse_tail', [False, True])
 @pytest.mark.parametrize('d,N', [(5, 300), (25, 1000)])
 def test_jump_mala_native_stream_matches_oracle(dev, monkeypatch, fuse_tail, d, N):
-    from nfmc_amd.containers import NFMCKernel
-    from nfmc_amd.samplers import jump, mcmc
-    from oracle import samplers as osamp
-    n, T, Kin, seed = 192, 3, 4, 31337
-    pot, ref = _problem(N, d, 3 * d + N)
-    x0 = _x0(n, d, 3)
-    f, of = _flow_pair(d)
-    h = 0.3 * d ** (-1 / 3)
-    split, flow_mh = [], []
-    orig, orig_fm = jump.split_flow_mh, jump.launch_flow_mh
-    monkeypatch.setattr(jump, 'split_flow_mh', lambda *a, **k: split.append(1) or orig(*a, **k))
-    monkeypatch.setattr(jump, 'launch_flow_mh', lambda *a, **k: flow_mh.append(1) or orig_fm(*a, **k))
-    spy = _Spy(monkeypatch)
-    s = jump.JumpMALA((d,), pot, NFMCKernel((d,), flow=f), jump.JumpNFMCParameters(n_iterations=T), None,
-                      mcmc.LangevinParameters(n_iterations=Kin))
-    s.inner_sampler.kernel.step_size = h
-    s.seed, s.fuse_jump_tail = seed, fuse_tail
-    out = s.sample(x0, show_progress=False)
-    assert not spy.calls and not split                        # inner loop and jump fused
-    if not fuse_tail:
-        assert len(flow_mh) == T                              # each jump on the flow-MH kernel
-    tr = osamp.jump_sample(x0.double(), ref, of, 'langevin', T, Kin, h, noise=osamp.PhiloxNoise(seed, dtype=torch.float64))
-    got, want = out.samples.reshape(T * (Kin + 1), n, d), tr.stacked().float()
-    same = (got - want).abs().amax(dim=(0, 2)) < ATOL + RTOL * want.abs().amax(dim=(0, 2))
-    assert same.float().mean() > 0.95, float(same.float().mean())
-    assert out.statistics.n_attempted_jumps == n * T
-    assert abs(out.statistics.n_accepted_jumps - tr.n_accepted_jumps) <= max(2, int(0.03 * n * T))
+    n, T = 192, 3
+    H.jump_mala_matches_oracle(monkeypatch, _record(N, d, 3 * d + N, n, 3), T=T, Kin=4, seed=31337, h=0.3 * d ** (-1 / 3),
+                               imd=None, fuse_tail=fuse_tail, spline=False, atol=ATOL, rtol=RTOL, share=0.95,
+                               jump_slack=max(2, int(0.03 * n * T)))
 
 
 @pytest.mark.parametrize('d,N', [(2, 64), (25, 1000), (64, 65), (256, 100)])
 def test_imh_runs_on_the_sequential_flow_mh_kernel(dev, monkeypatch, d, N):
-    from nfmc_amd.samplers import imh
-    from oracle import samplers as osamp
-    n, T, seed = 256, 6, 4711 + d
-    pot, ref = _problem(N, d, 5 * d + N)
-    x0 = _x0(n, d, 9)
-    f, of = _flow_pair(d, 9)
-    s = imh.FixedIMH((d,), pot, imh.IMHKernel((d,), flow=f), imh.IMHParameters(n_iterations=T))
-    s.seed = seed
-    calls = {'launch_imh_parallel': 0, 'launch_flow_mh': 0, 'split_flow_mh': 0}
-
-    def spy(name):   # the names imh.py calls (bound there by its `from .jump import ...`)
-        fn = getattr(imh, name)
-
-        def wrapped(*a, **k):
-            calls[name] += 1
-            return fn(*a, **k)
-        monkeypatch.setattr(imh, name, wrapped)
-    for name in list(calls):
-        spy(name)
-    out = s.sample(x0, show_progress=False)
-    # the sequential flow-MH kernel ran every transition: neither nfmc_imh_parallel_f32 nor the composed step
-    assert calls['launch_flow_mh'] >= 1 and calls['launch_imh_parallel'] == 0 and calls['split_flow_mh'] == 0, calls
-    assert out.statistics.n_attempted_trajectories == n * T
-    tr = osamp.imh_sample(x0.double(), ref, of, T, noise=osamp.PhiloxNoise(seed, dtype=torch.float64))
-    _compare(out.samples.reshape(T, n, d), tr, 'imh d=%d N=%d' % (d, N))
+    H.imh_matches_oracle(monkeypatch, _record(N, d, 5 * d + N, 256, 9), T=6, seed=4711 + d, flow_seed=9, spline=False,
+                         compare=_compare, what='imh d=%d N=%d' % (d, N))
 
 
 # ------------------------------------------------------------------------- 3. fused equals split
 @pytest.mark.parametrize('kind,d,N', [('mala', 25, 1000), ('hmc', 9, 200), ('mh', 7, 63)])
 def test_fused_equals_split(dev, monkeypatch, kind, d, N):
-    n, T = 200, 6
-    pot, _ = _problem(N, d, 17 * d + N)
-    x0 = _x0(n, d, 17)
-    outs, counts = [], []
-    for target, fuse in ((pot, 'auto'), (lambda x: pot(x), 'never')):
-        spy = _Spy(monkeypatch)
-        s = _sampler(kind, d, target, T, _step(kind, d))
-        s.seed, s.fuse = 2024, fuse
-        outs.append(s.sample(x0, show_progress=False))
-        counts.append(len(spy.calls))
-    assert counts == [0, T]
-    a, b = (o.samples.reshape(T, n, d) for o in outs)
-    same = (a - b).abs().amax(dim=(0, 2)) < ATOL
-    assert same.float().mean() > 0.95, float(same.float().mean())
-    np.testing.assert_allclose(a[:, same].numpy(), b[:, same].numpy(), atol=ATOL, rtol=RTOL)
+    T = 6
+    H.fused_equals_split(monkeypatch, _record(N, d, 17 * d + N, 200, 17),
+                         lambda target: _sampler(kind, d, target, T, _step(kind, d)), T, seed=2024, atol=ATOL, rtol=RTOL, share=0.95)
 
 
 # ------------------------------------------------------------------------- 4. refused families
@@ -339,48 +175,12 @@ def test_dlmc_borrows_the_gradient_step_and_matches_the_oracle(dev, monkeypatch)
 
 def test_refusing_entry_points_answer_unsupported(dev):
     from nfmc_amd import hip
-    from nfmc_amd.samplers import dlmc, imh
-    from nfmc_amd.samplers.common import Run
-    from nfmc_amd.samplers.jump import _flow_mh_probe_args
-    d, n, N = 64, 256, 1000
+    d, N = 64, 1000
     pot, _ = _problem(N, d, 4)
-    x = _x0(n, d, 4).to(dev)
-    f, _ = _flow_pair(d)
-    f.to(dev)
     pd = pot.descriptor(dev)
     assert pd.kind == hip.POT_LOGISTIC_REGRESSION and pd.reserved == N
-    a, _keep = dlmc.step_args(f, x, 0.05, pot=pot)
-    assert int(hip.lib().nfmc_dlmc_step_supported_f32(C.byref(a))) == hip.EUNSUPPORTED
-    st, _k2 = f.bijection.packed(dev)
-    u = torch.full((n,), 123.0, device=dev)
-    gr = torch.full_like(x, 123.0)
-    rc = int(hip.lib().nfmc_neutra_potential_grad_f32(C.byref(st), C.byref(pd), hip.ptr(x), n, hip.ptr(u), hip.ptr(gr),
-                                                        hip.stream()))
-    torch.cuda.synchronize()
-    assert rc == hip.EUNSUPPORTED and bool((u == 123.0).all()) and bool((gr == 123.0).all())
-    s = imh.FixedIMH((d,), pot, imh.IMHKernel((d,), flow=f), imh.IMHParameters(n_iterations=1))
-    run = Run(s, x.cpu())
-    logq = torch.empty(n, device=dev)
-    pa, _k3 = _flow_mh_probe_args(run, f, pot, logq, True)
-    assert int(hip.lib().nfmc_imh_parallel_supported_f32(C.byref(pa))) == hip.EUNSUPPORTED
-    assert int(hip.lib().nfmc_flow_mh_supported_f32(C.byref(pa))) == hip.OK        # the register kernels take it
-    pa.rng.rounds = 7                                                               # the opt-in stream: not for kind 3
-    before = run.x.clone()                                                          # the probe arguments' state
-    assert int(hip.lib().nfmc_flow_mh_steps_f32(C.byref(pa), hip.stream())) == hip.EUNSUPPORTED
-    torch.cuda.synchronize()
-    assert torch.equal(run.x, before)
-    # a wide conditioner (one-chain-per-lane / matrix-core flow-MH kernels): refused, never evaluated as a quadratic
-    fw, _ = _flow_pair(d, 5, n_hidden=48)
-    fw.to(dev)
-    pw, _k4 = _flow_mh_probe_args(run, fw, pot, logq, True)
-    assert int(hip.lib().nfmc_flow_mh_supported_f32(C.byref(pw))) == hip.EUNSUPPORTED
-    pw.x, pw.logq, pw.n_steps = hip.ptr(x), hip.ptr(logq), 1
-    before = x.clone()
-    assert int(hip.lib().nfmc_flow_mh_steps_f32(C.byref(pw), hip.stream())) == hip.EUNSUPPORTED
-    torch.cuda.synchronize()
-    assert torch.equal(x, before)
-    # the device variational fit is never handed the descriptor
-    assert not pot.fused_in('fit') and not pot.fused_in('neutra') and not pot.fused_in('dlmc_step')
+    # no NeuTra kernels for kind 3 either
+    H.refusing_entry_points(dev, pot, _x0(256, d, 4), functools.partial(_flow_pair, d), neutra_fused=False)
 
 
 def test_mala_philox7_and_bad_descriptors_are_refused(dev):
@@ -432,26 +232,9 @@ def test_separable_data_stay_finite(dev, kind):
 # ------------------------------------------------------------------------- 6. determinism and sharding
 @pytest.mark.parametrize('kind', ['mala', 'hmc'])
 def test_determinism_and_sharding(dev, kind):
-    from nfmc_amd.dist import Shard
-    d, n, T, N = 20, 300, 8, 700
-    pot, _ = _problem(N, d, 44)
-    x0 = _x0(n, d, 44)
-    runs = []
-    for _ in range(2):
-        s = _sampler(kind, d, pot, T, _step(kind, d))
-        s.seed = 7
-        runs.append(s.sample(x0, show_progress=False))
-    assert torch.equal(runs[0].samples, runs[1].samples)
-    assert runs[0].statistics.n_accepted_trajectories == runs[1].statistics.n_accepted_trajectories
-    dense = runs[0].samples.reshape(T, n, d)
-    parts = []
-    for r in range(2):
-        sh = Shard(rank=r, world=2)
-        sh.merge_statistics = lambda s_: s_
-        s = _sampler(kind, d, pot, T, _step(kind, d))
-        s.seed, s.shard = 7, sh
-        parts.append(s.sample(x0, show_progress=False).samples.reshape(T, -1, d))
-    assert torch.equal(torch.cat(parts, 1), dense)
+    d, T = 20, 8
+    pot, _ = _problem(700, d, 44)
+    H.determinism_and_sharding(lambda: _sampler(kind, d, pot, T, _step(kind, d)), _x0(300, d, 44), T, d, seed=7, world=2)
 
 
 def test_every_device_gets_its_own_copy(dev):

@@ -9,11 +9,15 @@ Tolerances (fp32 kernels, fp64 oracle on the same noise):
                 excluded share is reported and must stay under 10 %; all other chains must match.
 """
 import ctypes as C
+import functools
 import math
 
 import numpy as np
 import pytest
 import torch
+
+import target_harness as H
+from target_harness import flow_pair as _flow_pair
 
 pytestmark = pytest.mark.gpu
 
@@ -41,123 +45,57 @@ def _x0(pot, n, g):
     return (pot.means[k] + 0.7 * torch.randn(n, pot.event_size, generator=g, dtype=torch.float64)).float()
 
 
-def _compare(got, tr, what):
-    """got (T, n, d) fp32 from the kernels, tr an oracle Trace on the same noise; returns the excluded share."""
-    want = tr.stacked().float()
-    n = want.shape[1]
-    keep = torch.ones(n, dtype=torch.bool)
-    if tr.log_ratios:
-        lr = torch.stack([v.reshape(-1).double() for v in tr.log_ratios])
-        lu = torch.stack([v.reshape(-1).double() for v in tr.uniforms])
-        keep = ((lu - lr).abs() >= MARGIN).all(0)
-    excluded = 1.0 - float(keep.float().mean())
-    print('%s: %.1f %% of the chains excluded as near-ties' % (what, 100 * excluded))
-    assert excluded < 0.10, (what, excluded)
-    assert torch.isfinite(got).all()
-    np.testing.assert_allclose(got[:, keep].numpy(), want[:, keep].numpy(), atol=ATOL, rtol=RTOL, err_msg=what)
-    return excluded
+def _record(K, d, seed, n, spread=2.0):
+    """the problem as the harness takes it: the class itself, called in fp64, is the oracle's target"""
+    pot, g = _mixture(K, d, seed, spread)
+    return H.Problem(pot, pot, pot, _x0(pot, n, g), d, 'K=%d d=%d' % (K, d))
 
 
-def _sampler(kind, d, pot, T, h, L=5):
-    from nfmc_amd.samplers import mcmc
-    if kind in ('mala', 'ula'):
-        cls = mcmc.MALA if kind == 'mala' else mcmc.ULA
-        return cls((d,), pot, mcmc.LangevinKernel(event_size=d, step_size=h), mcmc.LangevinParameters(n_iterations=T))
-    if kind == 'mh':
-        return mcmc.MH((d,), pot, None, mcmc.MHParameters(n_iterations=T))
-    cls = mcmc.HMC if kind == 'hmc' else mcmc.UHMC
-    return cls((d,), pot, mcmc.HMCKernel(event_size=d, n_leapfrog_steps=L, step_size=h), mcmc.HMCParameters(n_iterations=T))
+_compare = functools.partial(H.compare_states, margin=MARGIN, atol=ATOL, rtol=RTOL)
+_sampler = functools.partial(H.mcmc_sampler, imd_kinds=('mh',))      # Langevin and HMC keep the unit mass diagonal
+_oracle = functools.partial(H.oracle_trace, imd_kinds=('mh',))
 
 
-def _oracle(kind, x0, pot, T, h, noise, L=5, inv_mass_diag=None):
-    from oracle import samplers as osamp
-    okind = {'mala': 'langevin', 'ula': 'langevin', 'mh': 'mh', 'hmc': 'hmc', 'uhmc': 'hmc'}[kind]
-    return osamp.mcmc_sample(x0.double(), pot, okind, T, h, n_leapfrog=L, adjustment=kind not in ('ula', 'uhmc'),
-                             noise=noise, inv_mass_diag=inv_mass_diag)
+def _mh_scale(d):
+    return torch.full((d,), 0.3 / math.sqrt(d))
 
 
 def _step(kind, d):
     return {'mala': 0.3, 'ula': 0.05, 'mh': 0.0, 'hmc': 0.1, 'uhmc': 0.05}[kind] * d ** (-1 / 3) if kind != 'mh' else 0.0
 
 
+def _against_oracle(check, monkeypatch, kind, p, T, **kw):
+    """states alone: the kernel's masks and log ratios are not recorded for this kind"""
+    h, imd = _step(kind, p.d), _mh_scale(p.d)
+    check(monkeypatch, p, kind, T, _sampler(kind, p.d, p.pot, T, h, imd=imd),
+          lambda noise: _oracle(kind, p.x0, p.target, T, h, noise, imd=imd.double()), compare=_compare, decisions=None, **kw)
+
+
 # ------------------------------------------------------------------------- 1. fused kernels vs fp64 oracle, replayed noise
 @pytest.mark.parametrize('kind', ['mala', 'ula', 'mh', 'hmc', 'uhmc'])
 @pytest.mark.parametrize('K', [1, 2, 5, 8])
 @pytest.mark.parametrize('d', [2, 7, 64, 256, 512])
-def test_mcmc_replay_matches_oracle(dev, kind, K, d):
-    from oracle import samplers as osamp
-    from nfmc_amd.samplers import mcmc
-    n, T = 96, 4
-    pot, g = _mixture(K, d, 1000 * K + d)
-    x0 = _x0(pot, n, g)
-    h = _step(kind, d)
-    s = _sampler(kind, d, pot, T, h)
-    imd = None
-    if kind == 'mh':
-        s.kernel.inv_mass_diag = torch.full((d,), 0.3 / math.sqrt(d))
-        imd = s.kernel.inv_mass_diag.double()
-    rec = osamp.RecordingNoise(osamp.TorchNoise())
-    torch.manual_seed(d + K)
-    tr = _oracle(kind, x0, pot, T, h, rec, inv_mass_diag=imd)
-    s.replay = (torch.stack([v.float() for v in rec.normals]),
-                torch.stack([v.float() for v in rec.uniforms]) if rec.uniforms else None)
-    assert mcmc.resolve_target(pot, (d,), family='mcmc') is pot     # the fused route
-    out = s.sample(x0, show_progress=False)
-    _compare(out.samples.reshape(T, n, d), tr, '%s K=%d d=%d' % (kind, K, d))
+def test_mcmc_replay_matches_oracle(dev, monkeypatch, kind, K, d):
+    _against_oracle(H.replay_matches_oracle, monkeypatch, kind, _record(K, d, 1000 * K + d, 96), 4, torch_seed=d + K,
+                    what='%s K=%d d=%d' % (kind, K, d))
 
 
 # ------------------------------------------------------------------------- 2. native Philox streams
-def _flow_pair(d, seed=5):
-    from nfmc_amd.flows import Flow, RealNVP
-    from oracle import flow as oflow
-    of = oflow.perturb_(oflow.Flow(oflow.RealNVP((d,))), seed, 0.2, 0.7071)
-    f = Flow(RealNVP((d,)))
-    f.load_state_dict(of.state_dict())
-    return f, of.double()
-
-
 @pytest.mark.parametrize('kind,K,d', [('mala', 3, 64), ('ula', 2, 7), ('mh', 5, 33), ('hmc', 8, 256), ('uhmc', 4, 16)])
-def test_mcmc_native_stream_matches_oracle(dev, kind, K, d):
-    from oracle import samplers as osamp
-    n, T, seed = 160, 5, 777 + d
-    pot, g = _mixture(K, d, 7 * K + d)
-    x0 = _x0(pot, n, g)
-    h = _step(kind, d)
-    s = _sampler(kind, d, pot, T, h)
-    imd = None
-    if kind == 'mh':
-        s.kernel.inv_mass_diag = torch.full((d,), 0.3 / math.sqrt(d))
-        imd = s.kernel.inv_mass_diag.double()
-    s.seed = seed
-    out = s.sample(x0, show_progress=False)
-    tr = _oracle(kind, x0, pot, T, h, osamp.PhiloxNoise(seed, dtype=torch.float64), inv_mass_diag=imd)
-    _compare(out.samples.reshape(T, n, d), tr, 'native %s' % kind)
+def test_mcmc_native_stream_matches_oracle(dev, monkeypatch, kind, K, d):
+    _against_oracle(H.native_matches_oracle, monkeypatch, kind, _record(K, d, 7 * K + d, 160), 5, seed=777 + d,
+                    what='native %s' % kind)
 
 
 @pytest.mark.parametrize('fuse_tail', [False, True])
 @pytest.mark.parametrize('K,d', [(2, 16), (5, 64)])
-def test_jump_mala_native_stream_matches_oracle(dev, fuse_tail, K, d):
+def test_jump_mala_native_stream_matches_oracle(dev, monkeypatch, fuse_tail, K, d):
     """jump_mala on a fixed perturbed flow: inner MALA fused, the jump on the register flow-MH kernel (or as the tail of
     the last inner launch)."""
-    from nfmc_amd.containers import NFMCKernel
-    from nfmc_amd.samplers import jump, mcmc
-    from oracle import samplers as osamp
-    n, T, Kin, seed = 192, 3, 4, 31337
-    pot, g = _mixture(K, d, 3 * K + d, spread=1.0)
-    x0 = _x0(pot, n, g)
-    f, of = _flow_pair(d)
-    h = 0.3 * d ** (-1 / 3)
-    s = jump.JumpMALA((d,), pot, NFMCKernel((d,), flow=f), jump.JumpNFMCParameters(n_iterations=T), None,
-                      mcmc.LangevinParameters(n_iterations=Kin))
-    s.inner_sampler.kernel.step_size = h
-    s.seed, s.fuse_jump_tail = seed, fuse_tail
-    out = s.sample(x0, show_progress=False)
-    tr = osamp.jump_sample(x0.double(), pot, of, 'langevin', T, Kin, h, noise=osamp.PhiloxNoise(seed, dtype=torch.float64))
-    got, want = out.samples.reshape(T * (Kin + 1), n, d), tr.stacked().float()
-    same = (got - want).abs().amax(dim=(0, 2)) < ATOL + RTOL * want.abs().amax(dim=(0, 2))
-    assert same.float().mean() > 0.95, float(same.float().mean())
-    assert out.statistics.n_attempted_jumps == n * T
-    assert abs(out.statistics.n_accepted_jumps - tr.n_accepted_jumps) <= max(2, int(0.03 * n * T))
+    n, T = 192, 3
+    H.jump_mala_matches_oracle(monkeypatch, _record(K, d, 3 * K + d, n, spread=1.0), T=T, Kin=4, seed=31337, h=0.3 * d ** (-1 / 3),
+                               imd=None, fuse_tail=fuse_tail, spline=False, atol=ATOL, rtol=RTOL, share=0.95,
+                               jump_slack=max(2, int(0.03 * n * T)))
 
 
 @pytest.mark.parametrize('K,d', [(1, 7), (4, 64), (8, 256)])
@@ -211,21 +149,11 @@ def test_one_component_equals_diagonal_gaussian(dev, kind):
 
 # ------------------------------------------------------------------------- 4. fused equals split
 @pytest.mark.parametrize('kind,K,d', [('mala', 3, 64), ('hmc', 5, 20), ('mh', 2, 7)])
-def test_fused_equals_split(dev, kind, K, d):
-    n, T = 200, 6
-    pot, g = _mixture(K, d, 17 * K + d)
-    x0 = _x0(pot, n, g)
-    outs = []
-    for target, fuse in ((pot, 'auto'), (lambda x: pot(x), 'never')):
-        s = _sampler(kind, d, target, T, _step(kind, d))
-        if kind == 'mh':
-            s.kernel.inv_mass_diag = torch.full((d,), 0.3 / math.sqrt(d))
-        s.seed, s.fuse = 2024, fuse
-        outs.append(s.sample(x0, show_progress=False))
-    a, b = (o.samples.reshape(T, n, d) for o in outs)
-    same = (a - b).abs().amax(dim=(0, 2)) < ATOL
-    assert same.float().mean() > 0.95, float(same.float().mean())
-    np.testing.assert_allclose(a[:, same].numpy(), b[:, same].numpy(), atol=ATOL, rtol=RTOL)
+def test_fused_equals_split(dev, monkeypatch, kind, K, d):
+    T = 6
+    H.fused_equals_split(monkeypatch, _record(K, d, 17 * K + d, 200),
+                         lambda target: _sampler(kind, d, target, T, _step(kind, d), imd=_mh_scale(d)), T,
+                         seed=2024, atol=ATOL, rtol=RTOL, share=0.95)
 
 
 # ------------------------------------------------------------------------- 5. refused families take the split / composed path
@@ -321,87 +249,28 @@ def test_jump_mala_wide_conditioner_composes_the_jump(dev):
 # ------------------------------------------------------------------------- 6. kind 2 on the refusing entry points
 def test_refusing_entry_points_answer_unsupported(dev):
     from nfmc_amd import hip
-    from nfmc_amd.samplers import dlmc
-    from nfmc_amd.samplers.common import Run
-    from nfmc_amd.samplers.jump import _flow_mh_probe_args
-    d, n = 64, 256
+    d = 64
     pot, g = _mixture(3, d, 4)
-    x = _x0(pot, n, g).to(dev)
-    f, _ = _flow_pair(d)
-    f.to(dev)
-    pd = pot.descriptor(dev)
-    # dlmc's fused gradient step
-    a, _keep = dlmc.step_args(f, x, 0.05, pot=pot)
-    assert a.pot.kind == hip.POT_GAUSSIAN_MIXTURE
-    assert int(hip.lib().nfmc_dlmc_step_supported_f32(C.byref(a))) == hip.EUNSUPPORTED
-    # NeuTra gradient kernel: nothing written
-    st, _k2 = f.bijection.packed(dev)
-    u = torch.full((n,), 123.0, device=dev)
-    gr = torch.full_like(x, 123.0)
-    rc = int(hip.lib().nfmc_neutra_potential_grad_f32(C.byref(st), C.byref(pd), hip.ptr(x), n, hip.ptr(u), hip.ptr(gr),
-                                                        hip.stream()))
-    torch.cuda.synchronize()
-    assert rc == hip.EUNSUPPORTED and bool((u == 123.0).all()) and bool((gr == 123.0).all())
-    # imh_parallel and the flow-MH tile path (one chain per lane) through the same probe arguments as the samplers
-    from nfmc_amd.samplers import imh
-    s = imh.FixedIMH((d,), pot, imh.IMHKernel((d,), flow=f), imh.IMHParameters(n_iterations=1))
-    run = Run(s, x.cpu())
-    logq = torch.empty(n, device=dev)
-    pa, _k3 = _flow_mh_probe_args(run, f, pot, logq, True)
-    assert int(hip.lib().nfmc_imh_parallel_supported_f32(C.byref(pa))) == hip.EUNSUPPORTED
-    assert int(hip.lib().nfmc_flow_mh_supported_f32(C.byref(pa))) == hip.OK        # the register kernels take it
+    assert pot.descriptor(dev).kind == hip.POT_GAUSSIAN_MIXTURE
+    # no NeuTra kernels for kind 2 either
+    pa, _keep = H.refusing_entry_points(dev, pot, _x0(pot, 256, g), functools.partial(_flow_pair, d),
+                                        neutra_fused=False)
     pa.pot.reserved = 9                                                             # K over the cap
     assert int(hip.lib().nfmc_flow_mh_supported_f32(C.byref(pa))) == hip.EUNSUPPORTED
-    # a wide conditioner (one-chain-per-lane / matrix-core flow-MH kernels): refused, never evaluated as a quadratic
-    fw, _ = _flow_pair_wide(d)
-    fw.to(dev)
-    pw, _k4 = _flow_mh_probe_args(run, fw, pot, logq, True)
-    assert int(hip.lib().nfmc_flow_mh_supported_f32(C.byref(pw))) == hip.EUNSUPPORTED
-    pw.x, pw.logq, pw.n_steps = hip.ptr(x), hip.ptr(logq), 1
-    before = x.clone()
-    assert int(hip.lib().nfmc_flow_mh_steps_f32(C.byref(pw), hip.stream())) == hip.EUNSUPPORTED
-    torch.cuda.synchronize()
-    assert torch.equal(x, before)
-    # variational fit kernel
     assert hip.EUNSUPPORTED < 0 and pot.fused_in('fit') is False
-
-
-def _flow_pair_wide(d):
-    from nfmc_amd.flows import Flow, RealNVP
-    from oracle import flow as oflow
-    of = oflow.perturb_(oflow.Flow(oflow.RealNVP((d,), conditioner_kwargs={'n_hidden': 48})), 5, 0.2, 0.7071)
-    f = Flow(RealNVP((d,), conditioner_kwargs={'n_hidden': 48}))
-    f.load_state_dict(of.state_dict())
-    return f, of
 
 
 # ------------------------------------------------------------------------- 7. determinism, sharding, store
 def test_determinism_sharding_and_store(dev):
-    from nfmc_amd.dist import Shard
     d, n, T = 20, 300, 12
-    pot, g = _mixture(4, d, 44)
-    x0 = _x0(pot, n, g)
-    runs = []
-    for _ in range(2):
-        s = _sampler('mala', d, pot, T, _step('mala', d))
-        s.seed = 7
-        runs.append(s.sample(x0, show_progress=False))
-    assert torch.equal(runs[0].samples, runs[1].samples)
-    assert runs[0].statistics.n_accepted_trajectories == runs[1].statistics.n_accepted_trajectories
-    dense = runs[0].samples.reshape(T, n, d)
-    parts = []
-    for r in range(2):
-        sh = Shard(rank=r, world=2)
-        sh.merge_statistics = lambda s_: s_
-        s = _sampler('mala', d, pot, T, _step('mala', d))
-        s.seed, s.shard = 7, sh
-        parts.append(s.sample(x0, show_progress=False).samples.reshape(T, -1, d))
-    assert torch.equal(torch.cat(parts, 1), dense)
+    p = _record(4, d, 44, n)
+    make = lambda: _sampler('mala', d, p.pot, T, _step('mala', d))   # noqa: E731
+    dense = H.determinism_and_sharding(make, p.x0, T, d, seed=7, world=2)
     # thinning / max_samples keep states of the dense run, in order
-    s = _sampler('mala', d, pot, T, _step('mala', d))
+    s = make()
     s.seed = 7
     s.params.thinning, s.params.max_samples = 3, 3
-    kept = s.sample(x0, show_progress=False).samples.reshape(-1, n, d)
+    kept = s.sample(p.x0, show_progress=False).samples.reshape(-1, n, d)
     assert kept.shape[0] == 3
     idx = [next(t for t in range(T) if torch.equal(kept[i], dense[t])) for i in range(3)]
     assert idx == sorted(idx) and len(set(idx)) == 3

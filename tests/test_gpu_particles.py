@@ -53,15 +53,15 @@ Shapes (P, D): (2, 1), (2, 2) layout (4, 1); (4, 2) DW4 itself, (4, 2); (3, 3) a
 (341, 3) (16, 64); (16, 2) fills (4, 8) and (8, 1) fills (4, 2) exactly (tests/test_host_particles.py asks the library).
 Both pair forms up to d = 129, Lennard-Jones alone above.  64 chains, 16 at d >= 513."""
 import copy
-import ctypes as C
 import functools
 import math
 
-import numpy as np
 import pytest
 import torch
 
+import target_harness as H
 from particles_fp64 import Particles64, lattice_sites, min_pair_distance, start_states
+from target_harness import Spy as _Spy, imh_run as _imh_run, neutra_grad as _neutra_grad
 
 pytestmark = pytest.mark.gpu
 
@@ -132,65 +132,18 @@ def _problem(P, D, pair, n=None):
     return _Problem(P, D, pair, n)
 
 
-def _compare(got, tr, what):
-    want = tr.stacked().float()
-    n = want.shape[1]
-    keep = torch.ones(n, dtype=torch.bool)
-    if tr.log_ratios:
-        lr = torch.stack([v.reshape(-1).double() for v in tr.log_ratios])
-        lu = torch.stack([v.reshape(-1).double() for v in tr.uniforms])
-        keep = ((lu - lr).abs() >= MARGIN).all(0)
-    excluded = 1.0 - float(keep.float().mean())
-    print('%s: %.1f %% of the chains excluded as near-ties' % (what, 100 * excluded))
-    assert excluded < 0.10, (what, excluded)
-    assert torch.isfinite(got).all()
-    np.testing.assert_allclose(got[:, keep].numpy(), want[:, keep].numpy(), atol=ATOL, rtol=RTOL, err_msg=what)
-    return keep
+_compare = functools.partial(H.compare_states, margin=MARGIN, atol=ATOL, rtol=RTOL)
 
 
 def _sampler(kind, p, T, L=None, target=None, h=None, imd=None):
-    from nfmc_amd.samplers import mcmc
-    d = p.d
-    L = p.leapfrog() if L is None else L
-    target = p.pot if target is None else target
-    h = p.step(kind) if h is None else h
-    imd = (p.imd(kind) if imd is None else imd).float()
-    if kind in ('mala', 'ula'):
-        cls = mcmc.MALA if kind == 'mala' else mcmc.ULA
-        s = cls((d,), target, mcmc.LangevinKernel(event_size=d, step_size=h, inv_mass_diag=imd),
-                mcmc.LangevinParameters(n_iterations=T))
-    elif kind == 'mh':
-        s = mcmc.MH((d,), target, mcmc.MHKernel(event_size=d, inv_mass_diag=imd), mcmc.MHParameters(n_iterations=T))
-    else:
-        cls = mcmc.HMC if kind == 'hmc' else mcmc.UHMC
-        s = cls((d,), target, mcmc.HMCKernel(event_size=d, n_leapfrog_steps=L, step_size=h, inv_mass_diag=imd),
-                mcmc.HMCParameters(n_iterations=T))
-    return s
+    """every kind with the problem's mass diagonal of that kind"""
+    return H.mcmc_sampler(kind, p.d, p.pot if target is None else target, T, p.step(kind) if h is None else h,
+                          p.leapfrog() if L is None else L, p.imd(kind) if imd is None else imd, imd_kinds=H.KINDS)
 
 
 def _oracle(kind, p, T, noise, L=None):
-    from oracle import samplers as osamp
-    okind = {'mala': 'langevin', 'ula': 'langevin', 'mh': 'mh', 'hmc': 'hmc', 'uhmc': 'hmc'}[kind]
-    tr = osamp.mcmc_sample(p.x0.double(), p.target, okind, T, p.step(kind), n_leapfrog=p.leapfrog() if L is None else L,
-                           adjustment=kind not in ('ula', 'uhmc'), noise=noise, inv_mass_diag=p.imd(kind).float().double())
-    if kind in ('mala', 'mh', 'hmc'):
-        print('%s %s: oracle acceptance %.3f' % (kind, p.name, tr.n_accepted / (p.x0.shape[0] * T)))
-    return tr
-
-
-class _Spy:
-    """Counts the split-path transitions of the mcmc samplers (none on the fused route)."""
-
-    def __init__(self, monkeypatch):
-        from nfmc_amd.samplers import mcmc
-        self.calls = []
-        for cls in (mcmc.MCMCSampler, mcmc.MALA, mcmc.ULA, mcmc.MH, mcmc.HMC, mcmc.UHMC):
-            if cls is mcmc.MCMCSampler or '_split_step' in vars(cls):
-                orig = vars(cls)['_split_step']
-                monkeypatch.setattr(cls, '_split_step', self._wrap(orig))
-
-    def _wrap(self, orig):
-        return lambda s, *a, **k: self.calls.append(1) or orig(s, *a, **k)
+    return H.oracle_trace(kind, p.x0, p.target, T, p.step(kind), noise, p.leapfrog() if L is None else L,
+                          p.imd(kind).float().double(), imd_kinds=H.KINDS, label='%s %s' % (kind, p.name))
 
 
 SMALL = [(2, 1), (2, 2), (4, 2), (3, 3), (5, 3), (11, 3), (13, 3), (22, 3), (43, 3), (16, 2), (8, 1)]
@@ -200,19 +153,10 @@ IDS = ['%s-%dx%d' % (pair, P, D) for P, D, pair in GRID]
 
 
 def _run_against_oracle(monkeypatch, kind, P, D, pair, T):
-    from oracle import samplers as osamp
-    from nfmc_amd.samplers import mcmc
+    """the native stream, states alone: the kernel's masks and log ratios are not recorded for this kind"""
     p = _problem(P, D, pair)
-    d, n = p.d, p.x0.shape[0]
-    seed = 777 + d
-    s = _sampler(kind, p, T)
-    s.seed = seed
-    assert mcmc.resolve_target(p.pot, (d,), family='mcmc') is p.pot
-    spy = _Spy(monkeypatch)
-    out = s.sample(p.x0, show_progress=False)
-    assert not spy.calls                                       # every transition on the fused kernel
-    tr = _oracle(kind, p, T, osamp.PhiloxNoise(seed, dtype=torch.float64))
-    _compare(out.samples.reshape(T, n, d), tr, '%s %s' % (kind, p.name))
+    H.native_matches_oracle(monkeypatch, p, kind, T, _sampler(kind, p, T), lambda noise: _oracle(kind, p, T, noise),
+                            seed=777 + p.d, what='%s %s' % (kind, p.name), compare=_compare, decisions=None)
 
 
 # ------------------------------------------------------------------------- 1. mala, mh, hmc against the fp64 oracle
@@ -329,27 +273,6 @@ def test_jump_mala_matches_oracle(dev, monkeypatch, fuse_tail, P, D, pair):
     assert abs(out.statistics.n_accepted_jumps - tr.n_accepted_jumps) <= T * int((~keep).sum())   # the excluded chains' jumps
 
 
-def _imh_run(monkeypatch, pot, d, f, x0, T, seed):
-    from nfmc_amd.samplers import imh
-    s = imh.FixedIMH((d,), pot, imh.IMHKernel((d,), flow=f), imh.IMHParameters(n_iterations=T))
-    s.seed = seed
-    calls = {'launch_imh_parallel': 0, 'launch_flow_mh': 0, 'split_flow_mh': 0}
-
-    def spy(name):
-        fn = getattr(imh, name)
-
-        def wrapped(*a, **k):
-            calls[name] += 1
-            return fn(*a, **k)
-        monkeypatch.setattr(imh, name, wrapped)
-    for name in list(calls):
-        spy(name)
-    out = s.sample(x0, show_progress=False)
-    assert calls['launch_flow_mh'] >= 1 and calls['launch_imh_parallel'] == 0 and calls['split_flow_mh'] == 0, calls
-    assert out.statistics.n_attempted_trajectories == x0.shape[0] * T
-    return out
-
-
 @pytest.mark.parametrize('spline', [False, True])
 @pytest.mark.parametrize('P,D,pair', D8_9_39)
 def test_imh_runs_on_the_register_flow_mh_kernel(dev, monkeypatch, P, D, pair, spline):
@@ -368,20 +291,6 @@ def test_imh_runs_on_the_register_flow_mh_kernel(dev, monkeypatch, P, D, pair, s
 
 
 # ------------------------------------------------------------------------- 4. NeuTra gradient and trajectory (VALU kernels)
-def _neutra_grad(dev, f, pot, z):
-    from nfmc_amd import hip
-    n, d = z.shape
-    st, _keep = f.bijection.packed(dev, 0)          # the flow's own width, as NeuTra presents it for this target
-    pd = pot.descriptor(dev)
-    zd = z.to(dev, torch.float32).contiguous()
-    u = torch.empty(n, device=dev)
-    g = torch.empty(n, d, device=dev)
-    rc = int(hip.lib().nfmc_neutra_potential_grad_f32(C.byref(st), C.byref(pd), hip.ptr(zd), n, hip.ptr(u), hip.ptr(g),
-                                                        hip.stream()))
-    torch.cuda.synchronize()
-    return rc, u.cpu(), g.cpu()
-
-
 def neutra_reference(of, ref, z, d):
     """(U~, grad U~) in fp64 and the restatement's own fp32 error in each: (u64, g64, floor_u, floor_g), the floors in the
     normalisation of the check -- U~ absolute, the gradient per row relative to 1 + the row's largest entry."""
@@ -426,60 +335,22 @@ def test_neutra_gradient_matches_fp64_autograd(dev, P, D, pair, nh):
 
 @pytest.mark.parametrize('P,D,pair,nh', [(3, 3, 'lj', 8), (13, 3, 'lj', 16), (43, 3, 'dw', 16)])
 def test_neutra_hmc_fused_matches_oracle(dev, monkeypatch, P, D, pair, nh):
-    from nfmc_amd.samplers import mcmc, neutra
-    from oracle import samplers as osamp
-    n, T, L = 64, 1, 4
     p = _problem(P, D, pair)
-    d = p.d
     h = 0.2 / (SIGMA[pair] * math.sqrt(float(p.H.max())))      # a latent step: the flow scales it by SIGMA
-    f, of = _flow_pair(p, 9, n_hidden=nh)
-    s = neutra.NeuTraHMC((d,), p.pot, mcmc.HMCKernel(event_size=d, n_leapfrog_steps=L, step_size=h),
-                         mcmc.HMCParameters(), neutra.NeuTraKernel((d,), flow=f), neutra.NeuTraParameters(n_iterations=T))
-    assert s._closed_form() is p.pot and s._min_hidden() == 0
-    split = []
-    monkeypatch.setattr(s.inner_sampler, 'sample', lambda *a, **k: split.append(1))
-    s.seed = 12
-    out = s.sample(p.x0, show_progress=False)
-    assert not split
-    tr = osamp.neutra_hmc_sample(p.x0.double(), p.target, of, T, h, None, L, noise=osamp.PhiloxNoise(12, dtype=torch.float64))
-    got, want = out.samples.reshape(T, n, d), tr.stacked().float()
-    same = (got - want).abs().amax(dim=(0, 2)) < 1e-3
-    assert same.float().mean() > 0.93, float(same.float().mean())
-    assert abs(out.statistics.n_accepted_trajectories - tr.n_accepted) <= 4
+    H.neutra_hmc_fused_matches_oracle(monkeypatch, p, _flow_pair(p, 9, n_hidden=nh), T=1, L=4, h=h, seed=12, atol=1e-3,
+                                      share=0.93, accept_slack=4)
 
 
 # ------------------------------------------------------------------------- 5. device warmup against the fp64 controller
 @pytest.mark.parametrize('kind,every', [('mala', 1), ('hmc', 2)])
 def test_warmup_controller_transitions_and_handoff(dev, monkeypatch, kind, every):
-    """LJ13 (d = 39).  As tests/test_gpu_warmup.py does for the other kinds: the controller state after the device warmup
-    against oracle.samplers.replay_controller over the kernel's kept states and accept counts, every warmup transition
-    and the sampling run after it shadowed in fp64."""
-    from test_gpu_warmup import _Record as _Accepts, _check_controller, _controller_params, _sampler as _wsampler, _shadow
-    from nfmc_amd import hip
-    from oracle import samplers as osamp
-    n, W, T, L = 70, 8, 4, 4
+    """LJ13 (d = 39).  As tests/test_gpu_warmup.py does for the other kinds."""
+    n = 70
     p = _problem(13, 3, 'lj', n)
-    d = p.d
-    lm = float(p.H.max())
+    d, lm = p.d, float(p.H.max())
     h0 = 0.3 * (0.5 * d ** (-1 / 4) / math.sqrt(lm) if kind == 'hmc' else 0.5 * d ** (-1 / 3) / lm)
-    imd0 = torch.ones(d)
-    seed = 4242 + d
-    s = _wsampler(kind, d, p.pot, W, T, h0, L=L, every=every)
-    h0 = float(s.kernel.step_size)
-    s.seed = seed
-    rec = _Accepts(monkeypatch, s)
-    wout = s.warmup(p.x0, show_progress=False)
-    what = 'particles %s %s n=%d every=%d' % (kind, p.name, n, every)
-    states = wout.samples.reshape(W, n, d)
-    ups, h_t, imd_t = osamp.replay_controller(states, rec.accepted(), every, _controller_params(s, h0, imd0))
-    assert len(ups) == math.ceil(W / every)
-    _check_controller(s, ups, what)
-    _shadow(torch.cat([p.x0[None], states]), kind, p.target, h_t, imd_t, seed, hip.WARMUP_STEP0, L, what + ' warmup', 0.05)
-    x1 = wout.running_samples.last_sample.cpu()
-    out = s.sample(x1, show_progress=False)
-    assert torch.isfinite(out.samples).all()
-    _shadow(torch.cat([x1[None], out.samples.reshape(T, n, d)]), kind, p.target, s.kernel.step_size,
-            s.kernel.inv_mass_diag.clone(), seed, 0, L, what + ' sampling', 0.05)
+    H.warmup_matches_controller(monkeypatch, p, kind, W=8, T=4, L=4, every=every, h0=h0, imd0=torch.ones(d), seed=4242 + d,
+                                what='particles %s %s n=%d every=%d' % (kind, p.name, n, every), ties=0.05)
 
 
 # ------------------------------------------------------------------------- 6. coincident Lennard-Jones particles
@@ -566,150 +437,32 @@ def test_sample_keeps_the_states_of_the_dense_run(dev):
 # ------------------------------------------------------------------------- 8. refused entry points, bad descriptors
 def test_refusing_entry_points_answer_unsupported(dev):
     from nfmc_amd import hip
-    from nfmc_amd.samplers import dlmc, imh
-    from nfmc_amd.samplers.common import Run
-    from nfmc_amd.samplers.jump import _flow_mh_probe_args
-    n = 64
     p = _problem(13, 3, 'lj')
-    d, pot = p.d, p.pot
-    x = p.x0.to(dev)
-    f, _ = _flow_pair(p)
-    f.to(dev)
+    pot = p.pot
     pd = pot.descriptor(dev)
     assert pd.kind == hip.POT_PARTICLES == 11 and pd.reserved == 13 and not pd.b
     assert pd.a % 16 == 0 and pot.descriptor(dev).a == pd.a                           # cached per device
-    a, _keep = dlmc.step_args(f, x, 0.05, pot=pot)
-    assert int(hip.lib().nfmc_dlmc_step_supported_f32(C.byref(a))) == hip.EUNSUPPORTED
-    before = x.clone()
-    assert int(hip.lib().nfmc_dlmc_step_f32(C.byref(a), hip.stream())) == hip.EUNSUPPORTED
-    torch.cuda.synchronize()
-    assert torch.equal(x, before)
-    s = imh.FixedIMH((d,), pot, imh.IMHKernel((d,), flow=f), imh.IMHParameters(n_iterations=1))
-    run = Run(s, x.cpu())
-    logq = torch.empty(n, device=dev)
-    pa, _k3 = _flow_mh_probe_args(run, f, pot, logq, True)
-    assert int(hip.lib().nfmc_imh_parallel_supported_f32(C.byref(pa))) == hip.EUNSUPPORTED
-    work = torch.zeros(64, device=dev)                                               # refused before the work area is sized
-    assert int(hip.lib().nfmc_imh_parallel_f32(C.byref(pa), hip.ptr(work), work.numel() * 4, hip.stream())) == hip.EUNSUPPORTED
-    assert int(hip.lib().nfmc_flow_mh_supported_f32(C.byref(pa))) == hip.OK        # the register kernels take it
-    pa.rng.rounds = 7                                                               # the opt-in stream: not for kind 11
-    before = run.x.clone()
-    assert int(hip.lib().nfmc_flow_mh_steps_f32(C.byref(pa), hip.stream())) == hip.EUNSUPPORTED
-    torch.cuda.synchronize()
-    assert torch.equal(run.x, before)
-    # a wide conditioner (one-chain-per-lane / matrix-core flow-MH kernels): refused, never evaluated as a quadratic
-    fw, _ = _flow_pair(p, 5, n_hidden=48)
-    fw.to(dev)
-    pw, _k4 = _flow_mh_probe_args(run, fw, pot, logq, True)
-    assert int(hip.lib().nfmc_flow_mh_supported_f32(C.byref(pw))) == hip.EUNSUPPORTED
-    # NeuTra on the matrix cores (48 units): the gradient and the trajectory entry points
-    u = torch.full((n,), 123.0, device=dev)
-    gr = torch.full_like(x, 123.0)
-    before = x.clone()
-    stw, _k5 = fw.bijection.packed(dev)
-    rc = int(hip.lib().nfmc_neutra_potential_grad_f32(C.byref(stw), C.byref(pd), hip.ptr(x), n, hip.ptr(u), hip.ptr(gr),
-                                                        hip.stream()))
-    assert rc == hip.EUNSUPPORTED
-    na = hip.NfmcNeutraHmcArgs()
-    na.z, na.n, na.n_steps, na.n_leapfrog, na.step_size, na.adjust = hip.ptr(x), n, 1, 2, 0.01, 1
-    na.flow, na.pot = stw, pd
-    na.rng.seed = 3
-    assert int(hip.lib().nfmc_neutra_hmc_steps_f32(C.byref(na), hip.stream())) == hip.EUNSUPPORTED
-    torch.cuda.synchronize()
-    assert torch.equal(x, before) and bool((u == 123.0).all()) and bool((gr == 123.0).all())
-    assert not pot.fused_in('fit') and not pot.fused_in('imh_parallel') and not pot.fused_in('dlmc_step')
+    H.refusing_entry_points(dev, pot, p.x0, functools.partial(_flow_pair, p))
 
 
 def test_the_fit_step_refuses_kind_11(dev):
-    """The device variational fit evaluates kinds 0 and 1 only: the sampler warmups are not offered the potential
-    (fused_in('fit') is False) and nfmc_flow_variational_fit_step_f32 answers EUNSUPPORTED without touching the weights."""
-    from nfmc_amd import hip
-    from nfmc_amd.flow_training import DeviceFit
-    from nfmc_amd.samplers.common import resolve_target
     p = _problem(4, 2, 'dw')
-    n = p.x0.shape[0]
-    assert resolve_target(p.pot, (p.d,), family='fit') is None
-    f, _ = _flow_pair(p)
-    f.to(dev)
-    fit = DeviceFit(f.bijection, dev, n, lr=1e-3)
-    before = fit.params.clone()
-    pd = p.pot.descriptor(dev)
-    z = p.x0.to(dev)
-    fit.opt.step = 1
-    rc = int(hip.lib().nfmc_flow_variational_fit_step_f32(C.byref(fit.fit), C.byref(pd), hip.ptr(z), n, C.byref(fit.opt),
-                                                            hip.stream()))
-    torch.cuda.synchronize()
-    assert rc == hip.EUNSUPPORTED and torch.equal(fit.params, before)
+    H.fit_step_refuses(dev, p.pot, p.x0, _flow_pair(p)[0])
 
 
 def test_philox7_and_bad_descriptors_are_refused(dev):
-    """The opt-in Philox4x32-7 stream has no kind-11 kernel (and sample(..., rng_rounds=7) raises ValueError);
-    check_particles' codes at the mcmc, flow-MH and NeuTra entry points alike: a NULL a, P < 2 and a P that does not give
-    d = P D with D in 1 .. 3 are EINVAL; a misaligned a is EALIGN.  Nothing is written."""
-    from nfmc_amd import hip, sample
-    from nfmc_amd.samplers import imh
-    from nfmc_amd.samplers.common import Run
-    from nfmc_amd.samplers.jump import _flow_mh_probe_args
-    n = 64
+    """check_particles' codes: a NULL a, P < 2 and a P that does not give d = P D with D in 1 .. 3 are EINVAL; a misaligned
+    a is EALIGN."""
+    from nfmc_amd import hip
     p = _problem(4, 3, 'lj')
-    d, pot = p.d, p.pot
-    assert d == 12
-    x = p.x0.to(dev)
-    before = x.clone()
-    bad = []
-    for field, value, code in (('a', 0, hip.EINVAL), ('reserved', 0, hip.EINVAL), ('reserved', 1, hip.EINVAL),
-                               ('reserved', -4, hip.EINVAL), ('reserved', 5, hip.EINVAL),     # 12 % 5 != 0
-                               ('reserved', 3, hip.EINVAL), ('reserved', 2, hip.EINVAL),      # D = 4, D = 6
-                               ('reserved', 24, hip.EINVAL), ('reserved', 2 ** 30, hip.EINVAL),
-                               ('a', 'misaligned', hip.EALIGN)):
-        q = pot.descriptor(dev)
-        setattr(q, field, q.a + 4 if value == 'misaligned' else value)
-        bad.append((q, code))
-    ok = [pot.descriptor(dev) for _ in range(2)]
-    ok[0].reserved, ok[1].reserved = 6, 12                                           # the same d as D = 2 and D = 1: well formed
-    a = hip.NfmcMalaArgs()
-    a.x, a.n, a.d, a.n_steps, a.step_size, a.adjust = hip.ptr(x), n, d, 2, 0.01, 1
-    a.pot = pot.descriptor(dev)
-    a.rng.seed, a.rng.rounds = 3, 7
-    assert int(hip.lib().nfmc_mala_steps_f32(C.byref(a), hip.stream())) == hip.EUNSUPPORTED
-    a.rng.rounds = 10
-    for q, code in bad:
-        a.pot = q
-        assert int(hip.lib().nfmc_mala_steps_f32(C.byref(a), hip.stream())) == code, q.reserved
-    hm = hip.NfmcHmcArgs()
-    hm.x, hm.n, hm.d, hm.n_steps, hm.step_size, hm.adjust, hm.n_leapfrog = hip.ptr(x), n, d, 2, 0.01, 1, 3
-    hm.rng.seed = 3
-    for q, code in bad:
-        hm.pot = q
-        assert int(hip.lib().nfmc_hmc_steps_f32(C.byref(hm), hip.stream())) == code
-    f, _ = _flow_pair(p)
-    f.to(dev)
-    s = imh.FixedIMH((d,), pot, imh.IMHKernel((d,), flow=f), imh.IMHParameters(n_iterations=1))
-    run = Run(s, x.cpu())
-    logq = torch.empty(n, device=dev)
-    pa, _k = _flow_mh_probe_args(run, f, pot, logq, True)
-    st, _k2 = f.bijection.packed(dev)
-    u = torch.empty(n, device=dev)
-    g = torch.empty_like(x)
-    for q, code in bad:
-        pa.pot = q
-        assert int(hip.lib().nfmc_flow_mh_supported_f32(C.byref(pa))) == code
-        assert int(hip.lib().nfmc_neutra_potential_grad_f32(C.byref(st), C.byref(q), hip.ptr(x), n, hip.ptr(u), hip.ptr(g),
-                                                              hip.stream())) == code
-    for q in ok:
-        pa.pot = q
-        assert int(hip.lib().nfmc_flow_mh_supported_f32(C.byref(pa))) == hip.OK
-    torch.cuda.synchronize()
-    assert torch.equal(x, before)
-    with pytest.raises(ValueError):
-        sample(pot, flow=None, strategy='mala', n_iterations=2, n_chains=32, show_progress=False, seed=1,
-               x0=x[:32].cpu(), rng_rounds=7)
+    assert p.d == 12
+    bad = [('a', 0, hip.EINVAL), ('reserved', 0, hip.EINVAL), ('reserved', 1, hip.EINVAL), ('reserved', -4, hip.EINVAL),
+           ('reserved', 5, hip.EINVAL),                                               # 12 % 5 != 0
+           ('reserved', 3, hip.EINVAL), ('reserved', 2, hip.EINVAL),                  # D = 4, D = 6
+           ('reserved', 24, hip.EINVAL), ('reserved', 2 ** 30, hip.EINVAL), ('a', 'misaligned', hip.EALIGN)]
+    H.bad_descriptors_are_refused(dev, p.pot, p.x0, _flow_pair(p)[0], bad,
+                                  ok=[('reserved', 6), ('reserved', 12)])            # the same d as D = 2 and D = 1: well formed
 
 
 def test_limits_are_unchanged(dev):
-    """Kind 11 adds no shape limit of its own: nfmc_limits answers what it did for ABI version 4."""
-    from nfmc_amd import hip
-    lim = hip.NfmcLimits()
-    assert int(hip.lib().nfmc_limits(C.byref(lim))) == hip.OK
-    assert ((lim.abi_version, lim.max_d_sampler, lim.max_d_flow, lim.max_hidden_valu, lim.max_hidden, lim.max_steps_per_call)
-            == (4, 1024, 512, 32, 128, hip.MAX_STEPS_PER_CALL))
+    H.limits_are_unchanged()

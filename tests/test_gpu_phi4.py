@@ -14,14 +14,15 @@ Tolerances are the Rosenbrock tests' (tests/test_gpu_rosenbrock.py):
 The shapes cover every (CPL, LPC) layout choose_cfg picks (d = 4 ... 1024), ragged d (100, 60, 144), an odd number of
 rows, one and two rows, and lattices whose rows wrap through every lane of a chain.
 """
-import ctypes as C
+import functools
 import math
 
-import numpy as np
 import pytest
 import torch
 
+import target_harness as H
 from phi4_fp64 import Phi4U64
+from target_harness import Spy as _Spy, flow_pair as _flow_pair
 
 pytestmark = pytest.mark.gpu
 
@@ -56,47 +57,19 @@ def _x0(ref, n, seed):
     return x.float()
 
 
-def _compare(got, tr, what):
-    want = tr.stacked().float()
-    n = want.shape[1]
-    keep = torch.ones(n, dtype=torch.bool)
-    if tr.log_ratios:
-        lr = torch.stack([v.reshape(-1).double() for v in tr.log_ratios])
-        lu = torch.stack([v.reshape(-1).double() for v in tr.uniforms])
-        keep = ((lu - lr).abs() >= MARGIN).all(0)
-    excluded = 1.0 - float(keep.float().mean())
-    print('%s: %.1f %% of the chains excluded as near-ties' % (what, 100 * excluded))
-    assert excluded < 0.10, (what, excluded)
-    assert torch.isfinite(got).all()
-    np.testing.assert_allclose(got[:, keep].numpy(), want[:, keep].numpy(), atol=ATOL, rtol=RTOL, err_msg=what)
+def _record(shape, boundary, n, seed):
+    """the problem as the harness takes it (flat states; the restatement is the oracle's target), and its curvature bound"""
+    pot, ref = _problem(shape, boundary)
+    return H.Problem(pot, ref, ref, _x0(ref, n, seed), ref.d, '%s %s' % (shape, boundary)), _lmax(ref)
 
 
-def _sampler(kind, shape, pot, T, h, L=5, imd=None):
-    from nfmc_amd.samplers import mcmc
-    shape = tuple(shape)
-    d = int(math.prod(shape))
-    if kind in ('mala', 'ula'):
-        cls = mcmc.MALA if kind == 'mala' else mcmc.ULA
-        s = cls(shape, pot, mcmc.LangevinKernel(event_size=d, step_size=h), mcmc.LangevinParameters(n_iterations=T))
-    elif kind == 'mh':
-        s = mcmc.MH(shape, pot, None, mcmc.MHParameters(n_iterations=T))
-        s.kernel.inv_mass_diag = imd.float()
-    else:
-        cls = mcmc.HMC if kind == 'hmc' else mcmc.UHMC
-        s = cls(shape, pot, mcmc.HMCKernel(event_size=d, n_leapfrog_steps=L, step_size=h),
-                mcmc.HMCParameters(n_iterations=T))
-    return s
+_compare = functools.partial(H.compare_states, margin=MARGIN, atol=ATOL, rtol=RTOL)
+_sampler = functools.partial(H.mcmc_sampler, imd_kinds=('mh',))      # Langevin and HMC keep the unit mass diagonal
+_oracle = functools.partial(H.oracle_trace, imd_kinds=('mh',))
 
 
 def _mh_scale(d, lm):
     return torch.full((d,), 0.5 / math.sqrt(d * lm), dtype=torch.float64)
-
-
-def _oracle(kind, x0, target, T, h, noise, L=5, imd=None):
-    from oracle import samplers as osamp
-    okind = {'mala': 'langevin', 'ula': 'langevin', 'mh': 'mh', 'hmc': 'hmc', 'uhmc': 'hmc'}[kind]
-    return osamp.mcmc_sample(x0.double(), target, okind, T, h, n_leapfrog=L, adjustment=kind not in ('ula', 'uhmc'),
-                             noise=noise, inv_mass_diag=imd if kind == 'mh' else None)
 
 
 def _step(kind, d, lm):
@@ -106,97 +79,16 @@ def _step(kind, d, lm):
     return {'mala': 0.5, 'ula': 0.1, 'mh': 0.0}[kind] * d ** (-1 / 3) / lm
 
 
-class _Record:
-    """Hands every fused mcmc launch of `sampler` mask and log-ratio buffers and keeps them (T, n)."""
-
-    def __init__(self, monkeypatch, sampler):
-        self.masks, self.log_ratios = [], []
-        cls = type(sampler)
-        orig = cls._launch
-
-        def launch(s, run, pot, k, step0, samples, masks_out=None, log_ratio_out=None, **kw):
-            if masks_out is None:
-                masks_out = torch.zeros(k, run.n, dtype=torch.uint8, device=run.dev)
-            if log_ratio_out is None:
-                log_ratio_out = torch.zeros(k, run.n, dtype=torch.float32, device=run.dev)
-            self.masks.append(masks_out)
-            self.log_ratios.append(log_ratio_out)
-            return orig(s, run, pot, k, step0, samples, masks_out=masks_out, log_ratio_out=log_ratio_out, **kw)
-        monkeypatch.setattr(cls, '_launch', launch)
-
-    def stacked(self):
-        return torch.cat(self.masks).cpu().bool(), torch.cat(self.log_ratios).cpu()
-
-    def accepted(self):
-        return torch.cat(self.masks).cpu().long().sum(1)
-
-
-def _compare_decisions(rec, tr, kind, x0, ref, what):
-    """Accept masks and log ratios against the oracle's on the rows before a chain's first disagreeing decision.  Log
-    ratios to 2e-4 max(1, d / 64) + 1e-4 |log r| + 8 ulp(fp32) |U(x)|."""
-    got_m, got_lr = rec.stacked()
-    if kind in ('ula', 'uhmc'):
-        assert bool(got_m.all()), what
-        return
-    want_m = torch.stack([m.reshape(-1).bool() for m in tr.masks])
-    want_lr = torch.stack([v.reshape(-1).double() for v in tr.log_ratios])
-    assert got_m.shape == want_m.shape, (got_m.shape, want_m.shape)
-    same = got_m == want_m
-    agree = torch.cumprod(torch.cat([torch.ones(1, same.shape[1], dtype=torch.bool), same[:-1]]).int(), 0).bool()
-    assert float(agree.float().mean()) > 0.9, what
-    assert float(same[agree].float().mean()) > 0.97, what
-    d = x0.shape[1]
-    states = tr.stacked()
-    prev = torch.cat([x0.double()[None], states[:-1].double()])
-    u_prev = ref(prev.reshape(-1, d)).reshape(prev.shape[:2])
-    err = (got_lr.double() - want_lr).abs()
-    tol = 2e-4 * max(1.0, d / 64) + 1e-4 * want_lr.abs() + 8 * 2.0 ** -24 * u_prev.abs()
-    print('%s: worst log-ratio error %.2e' % (what, float(err[agree].max())))
-    assert bool((err[agree] <= tol[agree]).all()), (what, float(err[agree].max()))
-
-
-class _Spy:
-    """Counts the split-path transitions of the mcmc samplers (none on the fused route).  A sampler class that holds
-    `_split_step` in its own namespace (an earlier test may have left the inherited function there) is patched too, so
-    that every class's lookup reaches a counting wrapper."""
-
-    def __init__(self, monkeypatch):
-        from nfmc_amd.samplers import mcmc
-        self.calls = []
-        for cls in (mcmc.MCMCSampler, mcmc.MALA, mcmc.ULA, mcmc.MH, mcmc.HMC, mcmc.UHMC):
-            if cls is mcmc.MCMCSampler or '_split_step' in vars(cls):
-                orig = vars(cls)['_split_step']
-                monkeypatch.setattr(cls, '_split_step', self._wrap(orig))
-
-    def _wrap(self, orig):
-        return lambda s, *a, **k: self.calls.append(1) or orig(s, *a, **k)
-
-
 KINDS = ['mala', 'ula', 'mh', 'hmc', 'uhmc']
 SHAPES = [(4,), (8,), (100,), (1, 8), (2, 8), (4, 4), (8, 4), (3, 20), (8, 8), (12, 12), (16, 16), (8, 32), (64, 4),
           (16, 32), (32, 32)]
 UNFUSED = [(7,), (5, 5), (6, 6)]
 
 
-def _replay_case(monkeypatch, kind, shape, boundary, n=96, T=4):
-    """one replayed-noise run of the package sampler and the oracle: (sampler output, oracle trace, kernel record, spy)"""
-    from oracle import samplers as osamp
-    pot, ref = _problem(shape, boundary)
-    d = ref.d
-    x0 = _x0(ref, n, d + 7 * len(shape))
-    lm = _lmax(ref)
-    h = _step(kind, d, lm)
-    imd = _mh_scale(d, lm)
-    s = _sampler(kind, shape, pot, T, h, imd=imd)
-    rec = osamp.RecordingNoise(osamp.TorchNoise())
-    torch.manual_seed(d + len(shape))
-    tr = _oracle(kind, x0, ref, T, h, rec, imd=imd)
-    s.replay = (torch.stack([v.float() for v in rec.normals]),
-                torch.stack([v.float() for v in rec.uniforms]) if rec.uniforms else None)
-    spy = _Spy(monkeypatch)
-    rec_k = _Record(monkeypatch, s)
-    out = s.sample(x0.reshape((n,) + tuple(shape)), show_progress=False)
-    return pot, ref, x0, out, tr, rec_k, spy
+def _pair(kind, shape, p, lm, T):
+    """(package sampler on the lattice shape, oracle(noise) -> Trace) for T transitions of `kind` from p.x0"""
+    h, imd = _step(kind, p.d, lm), _mh_scale(p.d, lm)
+    return _sampler(kind, shape, p.pot, T, h, imd=imd), lambda noise: _oracle(kind, p.x0, p.target, T, h, noise, imd=imd)
 
 
 # ------------------------------------------------------------------------- 1. fused kernels vs fp64 oracle, replayed noise
@@ -204,14 +96,11 @@ def _replay_case(monkeypatch, kind, shape, boundary, n=96, T=4):
 @pytest.mark.parametrize('boundary', BOUNDARIES)
 @pytest.mark.parametrize('shape', SHAPES, ids=str)
 def test_mcmc_replay_matches_oracle(dev, monkeypatch, kind, shape, boundary):
-    from nfmc_amd.samplers import mcmc
-    n, T = 96, 4
-    pot, ref, x0, out, tr, rec_k, spy = _replay_case(monkeypatch, kind, shape, boundary, n, T)
-    assert mcmc.resolve_target(pot, shape, family='mcmc') is pot
-    assert not spy.calls                                       # every transition on the fused kernel
-    what = '%s %s %s' % (kind, shape, boundary)
-    _compare(out.samples.reshape(T, n, ref.d), tr, what)
-    _compare_decisions(rec_k, tr, kind, x0, ref, what)
+    T, d = 4, math.prod(shape)
+    p, lm = _record(shape, boundary, 96, d + 7 * len(shape))
+    H.replay_matches_oracle(monkeypatch, p, kind, T, *_pair(kind, shape, p, lm, T), torch_seed=d + len(shape),
+                            what='%s %s %s' % (kind, shape, boundary), compare=_compare, decisions=H.compare_decisions,
+                            event_shape=shape)
 
 
 # ------------------------------------------------------------------------- 2. native Philox streams
@@ -220,24 +109,11 @@ def test_mcmc_replay_matches_oracle(dev, monkeypatch, kind, shape, boundary):
                                                  ('hmc', (32, 32), 'zero'), ('mala', (16, 16), 'periodic'),
                                                  ('mala', (64, 4), 'zero')], ids=str)
 def test_mcmc_native_stream_matches_oracle(dev, monkeypatch, kind, shape, boundary):
-    from oracle import samplers as osamp
-    pot, ref = _problem(shape, boundary)
-    d = ref.d
-    n, T, seed = 160, 5, 777 + d
-    x0 = _x0(ref, n, d)
-    lm = _lmax(ref)
-    h = _step(kind, d, lm)
-    imd = _mh_scale(d, lm)
-    s = _sampler(kind, shape, pot, T, h, imd=imd)
-    s.seed = seed
-    spy = _Spy(monkeypatch)
-    rec_k = _Record(monkeypatch, s)
-    out = s.sample(x0.reshape((n,) + tuple(shape)), show_progress=False)
-    assert not spy.calls
-    tr = _oracle(kind, x0, ref, T, h, osamp.PhiloxNoise(seed, dtype=torch.float64), imd=imd)
-    what = 'native %s %s %s' % (kind, shape, boundary)
-    _compare(out.samples.reshape(T, n, d), tr, what)
-    _compare_decisions(rec_k, tr, kind, x0, ref, what)
+    T, d = 5, math.prod(shape)
+    p, lm = _record(shape, boundary, 160, d)
+    H.native_matches_oracle(monkeypatch, p, kind, T, *_pair(kind, shape, p, lm, T), seed=777 + d,
+                            what='native %s %s %s' % (kind, shape, boundary), compare=_compare, decisions=H.compare_decisions,
+                            event_shape=shape)
 
 
 # ------------------------------------------------------------------------- 3. lattices the kernels do not take
@@ -248,221 +124,62 @@ def test_unfused_lattices_run_on_the_split_path(dev, monkeypatch, kind, shape, b
     """A last axis that is no multiple of 4: `fused_in` is False, every transition is a split-path one, and the states
     match the oracle to the same tolerances (no kernel masks to compare: the split path returns none)."""
     from nfmc_amd.samplers import mcmc
-    n, T = 96, 4
-    pot, ref, x0, out, tr, rec_k, spy = _replay_case(monkeypatch, kind, shape, boundary, n, T)
-    assert mcmc.resolve_target(pot, shape, family='mcmc') is None
+    n, T, d = 96, 4, math.prod(shape)
+    p, lm = _record(shape, boundary, n, d + 7 * len(shape))
+    s, oracle = _pair(kind, shape, p, lm, T)
+    out, tr, _rec, spy = H.replay_run(monkeypatch, s, oracle, p.x0.reshape((n,) + tuple(shape)), d + len(shape), True)
+    assert mcmc.resolve_target(p.pot, shape, family='mcmc') is None
     assert len(spy.calls) > 0
-    _compare(out.samples.reshape(T, n, ref.d), tr, 'split %s %s %s' % (kind, shape, boundary))
+    _compare(out.samples.reshape(T, n, d), tr, 'split %s %s %s' % (kind, shape, boundary))
 
 
 # ------------------------------------------------------------------------- 4. jump_mala, 5. imh
-def _flow_pair(d, seed=5, n_hidden=None, spline=False):
-    from nfmc_amd.flows import Flow, RealNVP
-    from nfmc_amd.util import create_flow_object
-    from oracle import flow as oflow
-    ck = {} if n_hidden is None else {'conditioner_kwargs': {'n_hidden': n_hidden}}
-    if spline:
-        of = oflow.perturb_(oflow.Flow(oflow.CRQNSF((d,))), seed, 0.3, 0.75)
-        f = create_flow_object('c-rqnsf', (d,))
-    else:
-        of = oflow.perturb_(oflow.Flow(oflow.RealNVP((d,), **ck)), seed, 0.2, 0.7071)
-        f = Flow(RealNVP((d,), **ck))
-    f.load_state_dict(of.state_dict())
-    return f, of.double()
-
-
 @pytest.mark.parametrize('spline', [False, True])
 @pytest.mark.parametrize('fuse_tail', [False, True])
 @pytest.mark.parametrize('shape,boundary', [((8,), 'zero'), ((3, 8), 'periodic'), ((8, 8), 'zero')], ids=str)
 def test_jump_mala_native_stream_matches_oracle(dev, monkeypatch, fuse_tail, spline, shape, boundary):
-    from nfmc_amd.containers import NFMCKernel
-    from nfmc_amd.samplers import jump, mcmc
-    from oracle import samplers as osamp
-    n, T, Kin, seed = 192, 3, 4, 31337
-    pot, ref = _problem(shape, boundary)
-    d = ref.d
-    x0 = _x0(ref, n, 3)
-    f, of = _flow_pair(d, spline=spline)
-    h = 0.3 * d ** (-1 / 3) / _lmax(ref)
-    split, flow_mh = [], []
-    orig, orig_fm = jump.split_flow_mh, jump.launch_flow_mh
-    monkeypatch.setattr(jump, 'split_flow_mh', lambda *a, **k: split.append(1) or orig(*a, **k))
-    monkeypatch.setattr(jump, 'launch_flow_mh', lambda *a, **k: flow_mh.append(1) or orig_fm(*a, **k))
-    spy = _Spy(monkeypatch)
-    s = jump.JumpMALA((d,), pot, NFMCKernel((d,), flow=f), jump.JumpNFMCParameters(n_iterations=T), None,
-                      mcmc.LangevinParameters(n_iterations=Kin))
-    s.inner_sampler.kernel.step_size = h
-    s.seed, s.fuse_jump_tail = seed, fuse_tail
-    out = s.sample(x0, show_progress=False)
-    assert not spy.calls and not split                        # inner loop and jump fused
-    if not fuse_tail or spline:
-        assert len(flow_mh) == T                              # each jump on the flow-MH kernel (the tail is affine only)
-    tr = osamp.jump_sample(x0.double(), ref, of, 'langevin', T, Kin, h, noise=osamp.PhiloxNoise(seed, dtype=torch.float64))
-    got, want = out.samples.reshape(T * (Kin + 1), n, d), tr.stacked().float()
-    same = (got - want).abs().amax(dim=(0, 2)) < ATOL + RTOL * want.abs().amax(dim=(0, 2))
-    assert same.float().mean() > 0.95, float(same.float().mean())
-    assert out.statistics.n_attempted_jumps == n * T
-    assert abs(out.statistics.n_accepted_jumps - tr.n_accepted_jumps) <= max(2, int(0.03 * n * T))
-
-
-def _imh_run(monkeypatch, pot, d, f, x0, T, seed):
-    from nfmc_amd.samplers import imh
-    s = imh.FixedIMH((d,), pot, imh.IMHKernel((d,), flow=f), imh.IMHParameters(n_iterations=T))
-    s.seed = seed
-    calls = {'launch_imh_parallel': 0, 'launch_flow_mh': 0, 'split_flow_mh': 0}
-
-    def spy(name):
-        fn = getattr(imh, name)
-
-        def wrapped(*a, **k):
-            calls[name] += 1
-            return fn(*a, **k)
-        monkeypatch.setattr(imh, name, wrapped)
-    for name in list(calls):
-        spy(name)
-    out = s.sample(x0, show_progress=False)
-    assert calls['launch_flow_mh'] >= 1 and calls['launch_imh_parallel'] == 0 and calls['split_flow_mh'] == 0, calls
-    assert out.statistics.n_attempted_trajectories == x0.shape[0] * T
-    return out
+    n, T = 192, 3
+    p, lm = _record(shape, boundary, n, 3)
+    H.jump_mala_matches_oracle(monkeypatch, p, T=T, Kin=4, seed=31337, h=0.3 * p.d ** (-1 / 3) / lm, imd=None, fuse_tail=fuse_tail,
+                               spline=spline, atol=ATOL, rtol=RTOL, share=0.95, jump_slack=max(2, int(0.03 * n * T)))
 
 
 @pytest.mark.parametrize('shape,boundary,spline', [((4,), 'periodic', False), ((3, 8), 'zero', False),
                                                    ((8, 8), 'periodic', False), ((16, 16), 'zero', False),
                                                    ((8,), 'periodic', True), ((4, 8), 'zero', True)], ids=str)
 def test_imh_runs_on_the_sequential_flow_mh_kernel(dev, monkeypatch, shape, boundary, spline):
-    from oracle import samplers as osamp
-    pot, ref = _problem(shape, boundary)
-    d = ref.d
-    n, T, seed = 256, 6, 4711 + d
-    x0 = _x0(ref, n, 9)
-    f, of = _flow_pair(d, 9 if not spline else 3, spline=spline)
-    out = _imh_run(monkeypatch, pot, d, f, x0, T, seed)
-    tr = osamp.imh_sample(x0.double(), ref, of, T, noise=osamp.PhiloxNoise(seed, dtype=torch.float64))
-    _compare(out.samples.reshape(T, n, d), tr, 'imh %s %s spline=%s' % (shape, boundary, spline))
+    p, _lm = _record(shape, boundary, 256, 9)
+    H.imh_matches_oracle(monkeypatch, p, T=6, seed=4711 + p.d, flow_seed=3 if spline else 9, spline=spline, compare=_compare,
+                         what='imh %s %s spline=%s' % (shape, boundary, spline))
 
 
 # ------------------------------------------------------------------------- 6. NeuTra (VALU kernels)
-def _neutra_grad(dev, f, pot, z):
-    from nfmc_amd import hip
-    n, d = z.shape
-    st, _keep = f.bijection.packed(dev, 0)          # the flow's own width, as NeuTra presents it for this target
-    pd = pot.descriptor(dev)
-    zd = z.to(dev, torch.float32).contiguous()
-    u = torch.empty(n, device=dev)
-    g = torch.empty(n, d, device=dev)
-    rc = int(hip.lib().nfmc_neutra_potential_grad_f32(C.byref(st), C.byref(pd), hip.ptr(zd), n, hip.ptr(u), hip.ptr(g),
-                                                        hip.stream()))
-    torch.cuda.synchronize()
-    return rc, u.cpu(), g.cpu()
-
-
 @pytest.mark.parametrize('boundary', BOUNDARIES)
 @pytest.mark.parametrize('shape,nh', [((4,), 4), ((1, 8), 8), ((2, 8), 16), ((3, 20), 32), ((8, 8), 8), ((100,), 8),
                                       ((8, 16), 16), ((16, 16), 4)], ids=str)
 def test_neutra_gradient_matches_fp64_autograd(dev, shape, nh, boundary):
-    """U~(z) = U(f^-1(z)) - log|det J_{f^-1}(z)| and its gradient from the VALU NeuTra kernel against fp64 autograd
-    through oracle/flow.py.  Tolerance: relative 2e-4 of (1 + max |.|) per row."""
-    from nfmc_amd import hip
-    from oracle import samplers as osamp
-    pot, ref = _problem(shape, boundary)
-    d = ref.d
-    f, of = _flow_pair(d, 3, n_hidden=nh)
-    n = 130
-    z = _x0(ref, n, d).double().requires_grad_(True)
-    u_ref = osamp.neutra_adjusted_target(of, ref, (d,))(z)
-    g_ref, = torch.autograd.grad(u_ref.sum(), z)
-    rc, u, g = _neutra_grad(dev, f, pot, z.detach())
-    assert rc == hip.OK
-    ur = u_ref.detach()
-    np.testing.assert_allclose(u.numpy(), ur.numpy(), atol=2e-4 * (1 + float(ur.abs().max())), rtol=0)
-    err = (g.double() - g_ref).abs().amax(dim=1) / (1 + g_ref.abs().amax(dim=1))
-    print('%s H=%d %s: worst relative gradient error %.2e' % (shape, nh, boundary, float(err.max())))
-    assert float(err.max()) < 2e-4
+    """Against fp64 autograd through oracle/flow.py, at the starts.  Tolerance: relative 2e-4 of (1 + max |.|) per row."""
+    p, _lm = _record(shape, boundary, 130, math.prod(shape))
+    H.neutra_gradient_matches_autograd(dev, p.pot, p.ref, p.x0, nh, '%s H=%d %s' % (shape, nh, boundary), flow_seed=3, bound=2e-4)
 
 
 @pytest.mark.parametrize('shape,nh,boundary', [((8,), 8, 'zero'), ((8, 8), 16, 'periodic'), ((8, 16), 8, 'zero')], ids=str)
 def test_neutra_hmc_fused_matches_oracle(dev, monkeypatch, shape, nh, boundary):
-    from nfmc_amd.samplers import mcmc, neutra
-    from oracle import samplers as osamp
-    n, T, L = 96, 3, 4
-    pot, ref = _problem(shape, boundary)
-    d = ref.d
-    z0 = _x0(ref, n, 61)
-    h = 0.2 / math.sqrt(_lmax(ref))
-    f, of = _flow_pair(d, 9, n_hidden=nh)
-    s = neutra.NeuTraHMC((d,), pot, mcmc.HMCKernel(event_size=d, n_leapfrog_steps=L, step_size=h),
-                         mcmc.HMCParameters(), neutra.NeuTraKernel((d,), flow=f), neutra.NeuTraParameters(n_iterations=T))
-    assert s._closed_form() is pot and s._min_hidden() == 0
-    split = []
-    monkeypatch.setattr(s.inner_sampler, 'sample', lambda *a, **k: split.append(1))
-    s.seed = 12
-    out = s.sample(z0, show_progress=False)
-    assert not split
-    tr = osamp.neutra_hmc_sample(z0.double(), ref, of, T, h, None, L, noise=osamp.PhiloxNoise(12, dtype=torch.float64))
-    got, want = out.samples.reshape(T, n, d), tr.stacked().float()
-    same = (got - want).abs().amax(dim=(0, 2)) < 1e-3
-    assert same.float().mean() > 0.93, float(same.float().mean())
-    assert abs(out.statistics.n_accepted_trajectories - tr.n_accepted) <= 6
+    p, lm = _record(shape, boundary, 96, 61)
+    H.neutra_hmc_fused_matches_oracle(monkeypatch, p, _flow_pair(p.d, 9, n_hidden=nh), T=3, L=4, h=0.2 / math.sqrt(lm), seed=12,
+                                      atol=1e-3, share=0.93, accept_slack=6)
 
 
 def test_neutra_wide_conditioner_stays_off_the_matrix_core_kernels(dev):
     """d = 64 with a conditioner of 64 units is the matrix-core NeuTra shape: kind 8 is refused there, NeuTraHMC keeps
     the flow's own width and runs the composed path, and the states match the oracle."""
-    from nfmc_amd import hip
-    from nfmc_amd.samplers import mcmc, neutra
-    from oracle import samplers as osamp
-    shape, n, T, L = (8, 8), 96, 3, 4
-    pot, ref = _problem(shape, 'periodic')
-    d = ref.d
-    z0 = _x0(ref, n, 62)
-    h = 0.2 / math.sqrt(_lmax(ref))
-    f, of = _flow_pair(d, 9, n_hidden=64)
-    rc, _u, _g = _neutra_grad(dev, f, pot, z0)
-    assert rc == hip.EUNSUPPORTED
-    s = neutra.NeuTraHMC((d,), pot, mcmc.HMCKernel(event_size=d, n_leapfrog_steps=L, step_size=h),
-                         mcmc.HMCParameters(), neutra.NeuTraKernel((d,), flow=f), neutra.NeuTraParameters(n_iterations=T))
+    p, lm = _record((8, 8), 'periodic', 96, 62)
+    s = H.neutra_wide_takes_the_split_path(dev, p, _flow_pair(p.d, 9, n_hidden=64), T=3, L=4, h=0.2 / math.sqrt(lm), seed=12,
+                                           atol=1e-3, share=0.93)
     assert s._min_hidden() == 0
-    split = []
-    orig = s.inner_sampler.sample
-    s.inner_sampler.sample = lambda *a, **k: split.append(1) or orig(*a, **k)
-    s.seed = 12
-    out = s.sample(z0, show_progress=False)
-    assert split == [1]
-    tr = osamp.neutra_hmc_sample(z0.double(), ref, of, T, h, None, L, noise=osamp.PhiloxNoise(12, dtype=torch.float64))
-    got, want = out.samples.reshape(T, n, d), tr.stacked().float()
-    same = (got - want).abs().amax(dim=(0, 2)) < 1e-3
-    assert same.float().mean() > 0.93, float(same.float().mean())
 
 
 # ------------------------------------------------------------------------- 7. device warmup against the fp64 controller
-def _controller_params(s, h0, imd0):
-    from oracle import samplers as osamp
-    p = s.params
-    return osamp.ControllerParams(step_size=h0, inv_mass_diag=imd0.clone(), imd_adjustment=p.imd_adjustment,
-                                  tune_step_size=bool(p.tune_step_size and p.adjustment),
-                                  tune_inv_mass_diag=bool(p.tune_inv_mass_diag))
-
-
-def _check_controller(s, ups, what):
-    last = ups[-1]
-    np.testing.assert_allclose(s.kernel.step_size, last.step_size, rtol=1e-10, err_msg=what)
-    if s.params.tune_step_size and s.params.adjustment:
-        np.testing.assert_allclose(s.kernel.da.error_sum, last.error_sum, rtol=1e-10, atol=1e-10, err_msg=what)
-        np.testing.assert_allclose(s.kernel.da.log_smooth, last.log_smooth, rtol=1e-10, atol=1e-12, err_msg=what)
-        assert s.kernel.da.iteration == last.iteration, what
-    got, want = s.kernel.inv_mass_diag.double(), last.inv_mass_diag.double()
-    assert torch.isfinite(got).all() and (got > 0).all(), what
-    np.testing.assert_allclose(got.numpy(), want.numpy(), rtol=4e-6 * len(ups) ** 0.5, atol=0, err_msg=what)
-
-
-def _shadow(states, kind, target, h, imd, seed, step0, L, what, max_tie_share=0.01):
-    from oracle import shadow
-    wl = shadow.Workload(kind, target, step_size=h, n_leapfrog=L, inv_mass_diag=imd, step0=step0)
-    rep = shadow.shadow(states, wl, seed)
-    fails = rep.failures(8.0, max_tie_share)
-    assert not fails, (what, fails, rep.summary())
-
-
 def _largest_growth(updates):
     """the factor by which `updates` dual-averaging updates raise the step size when every transition is accepted"""
     from oracle import samplers as osamp
@@ -477,154 +194,42 @@ def _largest_growth(updates):
                                                            ('mala', (8, 16), 'periodic', 70, 8, 1),
                                                            ('hmc', (3, 20), 'zero', 100, 8, 4)], ids=str)
 def test_warmup_controller_transitions_and_handoff(dev, monkeypatch, kind, shape, boundary, n, W, every):
-    """tests/test_gpu_warmup.py's check of the device warmup for kind 8: the controller against its fp64 replay over the
-    kernel's own kept states and accept counts, every warmup transition shadowed in fp64 with the step size and mass
-    diagonal the replay says it ran with, and the sampling run that follows shadowed with the tuned kernel."""
-    from nfmc_amd import hip
-    from nfmc_amd.samplers import mcmc
-    from oracle import samplers as osamp
-    pot, ref = _problem(shape, boundary)
-    d = ref.d
-    x0 = _x0(ref, n, d)
-    h0 = 0.3 * _step(kind, d, _lmax(ref))
+    """tests/test_gpu_warmup.py's check of the device warmup for kind 8, on the fused kernels throughout.  The launches
+    are handed log-ratio buffers too, as in the tests above."""
+    d = math.prod(shape)
+    p, lm = _record(shape, boundary, n, d)
+    h0 = 0.3 * _step(kind, d, lm)
     if kind == 'hmc':
         # the leapfrog of this force is stable below h = 2 / sqrt(lm): the start is such that the largest step the
         # controller can reach in this warmup (every transition of every update accepted) is 0.3 x that bound
-        h0 = min(h0, 0.3 * (2.0 / math.sqrt(_lmax(ref))) / _largest_growth(math.ceil(W / every)))
-    imd0 = torch.ones(d)
-    T, L, seed = 6, 4, 4242 + d
-    kw = dict(n_iterations=T, n_warmup_iterations=W, imd_adjustment=1e-3, tune_every=every)
-    if kind == 'mala':
-        s = mcmc.MALA((d,), pot, mcmc.LangevinKernel(event_size=d, step_size=h0), mcmc.LangevinParameters(**kw))
-    else:
-        s = mcmc.HMC((d,), pot, mcmc.HMCKernel(event_size=d, n_leapfrog_steps=L, step_size=h0), mcmc.HMCParameters(**kw))
-    s.seed = seed
+        h0 = min(h0, 0.3 * (2.0 / math.sqrt(lm)) / _largest_growth(math.ceil(W / every)))
     spy = _Spy(monkeypatch)
-    rec = _Record(monkeypatch, s)
-    wout = s.warmup(x0, show_progress=False)
-    assert not spy.calls
-    what = '%s %s %s n=%d every=%d' % (kind, shape, boundary, n, every)
-    states = wout.samples.reshape(W, n, d)
-    ups, h_t, imd_t = osamp.replay_controller(states, rec.accepted(), every, _controller_params(s, h0, imd0))
-    assert len(ups) == math.ceil(W / every)
-    _check_controller(s, ups, what)
     # fp32 rounding of Hamiltonians that are large next to their differences widens the tie windows, as for kind 5
-    _shadow(torch.cat([x0[None], states]), kind, ref, h_t, imd_t, seed, hip.WARMUP_STEP0, L, what + ' warmup', 0.05)
-    x1 = wout.running_samples.last_sample.cpu()
-    out = s.sample(x1, show_progress=False)
-    assert torch.isfinite(out.samples).all()
-    _shadow(torch.cat([x1[None], out.samples.reshape(T, n, d)]), kind, ref, s.kernel.step_size,
-            s.kernel.inv_mass_diag.clone(), seed, 0, L, what + ' sampling', 0.05)
+    H.warmup_matches_controller(monkeypatch, p, kind, W=W, T=6, L=4, every=every, h0=h0, imd0=torch.ones(d), seed=4242 + d,
+                                what='%s %s %s n=%d every=%d' % (kind, shape, boundary, n, every), ties=0.05,
+                                record_log_ratios=True)
+    assert not spy.calls
 
 
 # ------------------------------------------------------------------------- 8. refused entry points, bad descriptors
 def test_refusing_entry_points_answer_unsupported(dev):
     from nfmc_amd import hip
-    from nfmc_amd.samplers import dlmc, imh
-    from nfmc_amd.samplers.common import Run
-    from nfmc_amd.samplers.jump import _flow_mh_probe_args
-    shape, n = (8, 8), 256
-    pot, ref = _problem(shape, 'periodic')
-    d = ref.d
-    x = _x0(ref, n, 4).to(dev)
-    f, _ = _flow_pair(d)
-    f.to(dev)
+    pot, ref = _problem((8, 8), 'periodic')
     pd = pot.descriptor(dev)
     assert pd.kind == hip.POT_LATTICE_PHI4 and pd.reserved == 8
-    a, _keep = dlmc.step_args(f, x, 0.05, pot=pot)
-    assert int(hip.lib().nfmc_dlmc_step_supported_f32(C.byref(a))) == hip.EUNSUPPORTED
-    s = imh.FixedIMH((d,), pot, imh.IMHKernel((d,), flow=f), imh.IMHParameters(n_iterations=1))
-    run = Run(s, x.cpu())
-    logq = torch.empty(n, device=dev)
-    pa, _k3 = _flow_mh_probe_args(run, f, pot, logq, True)
-    assert int(hip.lib().nfmc_imh_parallel_supported_f32(C.byref(pa))) == hip.EUNSUPPORTED
-    assert int(hip.lib().nfmc_flow_mh_supported_f32(C.byref(pa))) == hip.OK        # the register kernels take it
-    pa.rng.rounds = 7                                                               # the opt-in stream: not for kind 8
-    before = run.x.clone()
-    assert int(hip.lib().nfmc_flow_mh_steps_f32(C.byref(pa), hip.stream())) == hip.EUNSUPPORTED
-    torch.cuda.synchronize()
-    assert torch.equal(run.x, before)
-    # a wide conditioner (one-chain-per-lane / matrix-core flow-MH kernels): refused, never evaluated as a quadratic
-    fw, _ = _flow_pair(d, 5, n_hidden=48)
-    fw.to(dev)
-    pw, _k4 = _flow_mh_probe_args(run, fw, pot, logq, True)
-    assert int(hip.lib().nfmc_flow_mh_supported_f32(C.byref(pw))) == hip.EUNSUPPORTED
-    pw.x, pw.logq, pw.n_steps = hip.ptr(x), hip.ptr(logq), 1
-    before = x.clone()
-    assert int(hip.lib().nfmc_flow_mh_steps_f32(C.byref(pw), hip.stream())) == hip.EUNSUPPORTED
-    # NeuTra on the matrix cores (d = 64, 48 units): the gradient and the trajectory entry points
-    u = torch.full((n,), 123.0, device=dev)
-    gr = torch.full_like(x, 123.0)
-    stw, _k5 = fw.bijection.packed(dev)
-    rc = int(hip.lib().nfmc_neutra_potential_grad_f32(C.byref(stw), C.byref(pd), hip.ptr(x), n, hip.ptr(u), hip.ptr(gr),
-                                                        hip.stream()))
-    assert rc == hip.EUNSUPPORTED
-    na = hip.NfmcNeutraHmcArgs()
-    na.z, na.n, na.n_steps, na.n_leapfrog, na.step_size, na.adjust = hip.ptr(x), n, 1, 2, 0.01, 1
-    na.flow, na.pot = stw, pd
-    na.rng.seed = 3
-    assert int(hip.lib().nfmc_neutra_hmc_steps_f32(C.byref(na), hip.stream())) == hip.EUNSUPPORTED
-    torch.cuda.synchronize()
-    assert torch.equal(x, before) and bool((u == 123.0).all()) and bool((gr == 123.0).all())
-    assert not pot.fused_in('fit') and not pot.fused_in('imh_parallel') and not pot.fused_in('dlmc_step')
+    H.refusing_entry_points(dev, pot, _x0(ref, 256, 4), functools.partial(_flow_pair, ref.d))
 
 
 def test_philox7_and_bad_descriptors_are_refused(dev):
-    """The opt-in Philox4x32-7 stream has no kind-8 kernel (and sample(..., rng_rounds=7) raises ValueError).  check_phi4:
-    a NULL a, W < 1 and a W that does not divide d are argument errors; a W that is no multiple of 4 is a valid lattice
-    the kernels do not run, NFMC_EUNSUPPORTED -- at the mcmc, flow-MH and NeuTra entry points alike.  Nothing is
-    written."""
-    from nfmc_amd import hip, sample
-    from nfmc_amd.samplers import imh
-    from nfmc_amd.samplers.common import Run
-    from nfmc_amd.samplers.jump import _flow_mh_probe_args
-    shape, n = (3, 8), 128
+    """check_phi4: a NULL a, W < 1 and a W that does not divide d are argument errors; a W that is no multiple of 4 is a
+    valid lattice the kernels do not run, NFMC_EUNSUPPORTED."""
+    from nfmc_amd import hip
+    shape = (3, 8)
     pot, ref = _problem(shape, 'zero')
-    d = ref.d
-    x = _x0(ref, n, 8).to(dev)
-    before = x.clone()
-    bad = []
-    for field, value, code in (('a', 0, hip.EINVAL), ('reserved', 0, hip.EINVAL), ('reserved', -4, hip.EINVAL),
-                               ('reserved', 16, hip.EINVAL), ('reserved', 5, hip.EINVAL), ('reserved', 48, hip.EINVAL),
-                               ('reserved', 6, hip.EUNSUPPORTED), ('reserved', 2, hip.EUNSUPPORTED),
-                               ('reserved', 3, hip.EUNSUPPORTED), ('reserved', 1, hip.EUNSUPPORTED)):
-        p = pot.descriptor(dev)
-        setattr(p, field, value)
-        bad.append((p, code))
-    a = hip.NfmcMalaArgs()
-    a.x, a.n, a.d, a.n_steps, a.step_size, a.adjust = hip.ptr(x), n, d, 2, 0.01, 1
-    a.pot = pot.descriptor(dev)
-    a.rng.seed, a.rng.rounds = 3, 7
-    assert int(hip.lib().nfmc_mala_steps_f32(C.byref(a), hip.stream())) == hip.EUNSUPPORTED
-    a.rng.rounds = 10
-    for p, code in bad:
-        a.pot = p
-        assert int(hip.lib().nfmc_mala_steps_f32(C.byref(a), hip.stream())) == code
-    hm = hip.NfmcHmcArgs()
-    hm.x, hm.n, hm.d, hm.n_steps, hm.step_size, hm.adjust, hm.n_leapfrog = hip.ptr(x), n, d, 2, 0.01, 1, 3
-    hm.rng.seed = 3
-    for p, code in bad:
-        hm.pot = p
-        assert int(hip.lib().nfmc_hmc_steps_f32(C.byref(hm), hip.stream())) == code
-    f, _ = _flow_pair(d)
-    f.to(dev)
-    s = imh.FixedIMH((d,), pot, imh.IMHKernel((d,), flow=f), imh.IMHParameters(n_iterations=1))
-    run = Run(s, x.cpu())
-    logq = torch.empty(n, device=dev)
-    pa, _k = _flow_mh_probe_args(run, f, pot, logq, True)
-    st, _k2 = f.bijection.packed(dev)
-    u = torch.empty(n, device=dev)
-    g = torch.empty_like(x)
-    for p, code in bad:
-        pa.pot = p
-        assert int(hip.lib().nfmc_flow_mh_supported_f32(C.byref(pa))) == code
-        assert int(hip.lib().nfmc_neutra_potential_grad_f32(C.byref(st), C.byref(p), hip.ptr(x), n, hip.ptr(u), hip.ptr(g),
-                                                              hip.stream())) == code
-    torch.cuda.synchronize()
-    assert torch.equal(x, before)
-    with pytest.raises(ValueError):
-        sample(pot, flow=None, strategy='mala', n_iterations=2, n_chains=32, show_progress=False, seed=1,
-               x0=x[:32].cpu().reshape(32, 3, 8), rng_rounds=7)
+    bad = [('a', 0, hip.EINVAL), ('reserved', 0, hip.EINVAL), ('reserved', -4, hip.EINVAL), ('reserved', 16, hip.EINVAL),
+           ('reserved', 5, hip.EINVAL), ('reserved', 48, hip.EINVAL), ('reserved', 6, hip.EUNSUPPORTED),
+           ('reserved', 2, hip.EUNSUPPORTED), ('reserved', 3, hip.EUNSUPPORTED), ('reserved', 1, hip.EUNSUPPORTED)]
+    H.bad_descriptors_are_refused(dev, pot, _x0(ref, 128, 8), _flow_pair(ref.d)[0], bad, event_shape=shape)
 
 
 # ------------------------------------------------------------------------- 9. sharding, 10. run to run
@@ -632,31 +237,10 @@ def test_philox7_and_bad_descriptors_are_refused(dev):
 def test_determinism_and_sharding(dev, monkeypatch, kind):
     """Two identical runs on the fused kernel agree bitwise, and rank r of a 4-way split equals its slice of the
     single-process run."""
-    from nfmc_amd.dist import Shard
     spy = _Spy(monkeypatch)
-    shape, n, T = (5, 8), 300, 8
-    pot, ref = _problem(shape, 'periodic')
-    d = ref.d
-    x0 = _x0(ref, n, 44)
-    h = _step(kind, d, _lmax(ref))
-    runs = []
-    for _ in range(2):
-        s = _sampler(kind, (d,), pot, T, h)
-        s.seed = 7
-        runs.append(s.sample(x0, show_progress=False))
-    assert torch.equal(runs[0].samples, runs[1].samples)
-    assert runs[0].statistics.n_accepted_trajectories == runs[1].statistics.n_accepted_trajectories
-    dense = runs[0].samples.reshape(T, n, d)
-    at = 0
-    for r in range(4):
-        sh = Shard(rank=r, world=4)
-        sh.merge_statistics = lambda s_: s_
-        s = _sampler(kind, (d,), pot, T, h)
-        s.seed, s.shard = 7, sh
-        part = s.sample(x0, show_progress=False).samples.reshape(T, -1, d)
-        assert torch.equal(part, dense[:, at:at + part.shape[1]]), r
-        at += part.shape[1]
-    assert at == n
+    T = 8
+    p, lm = _record((5, 8), 'periodic', 300, 44)
+    H.determinism_and_sharding(lambda: _sampler(kind, (p.d,), p.pot, T, _step(kind, p.d, lm)), p.x0, T, p.d, seed=7, world=4)
     assert not spy.calls                                       # all six runs on the fused kernel
 
 

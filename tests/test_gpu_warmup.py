@@ -9,40 +9,26 @@ sampling run's.
                    separates them), inv_mass_diag to a few fp32 ulps (fp32 partial sums of the shifted states), iteration exact
   transitions      oracle/shadow.py at kappa 8 (tests/test_gpu_benchmarked_workloads.py)
 """
+import functools
 import math
 
 import numpy as np
 import pytest
 import torch
 
+import target_harness as H
+from target_harness import (check_controller as _check_controller, controller_params as _controller_params,
+                            warmup_sampler as _sampler)
+
 pytestmark = pytest.mark.gpu
 
-KAPPA = 8.0
+_Record = functools.partial(H.Record, log_ratios=False)     # accept counts alone: the launches get no log-ratio buffer
 
 
 @pytest.fixture(scope='module')
 def dev():
     assert torch.cuda.is_available(), 'GPU tests need a ROCm device'
     return torch.device('cuda', 0)
-
-
-class _Record:
-    """Hands every fused mcmc launch of `sampler` a mask buffer and keeps them (T, n)."""
-
-    def __init__(self, monkeypatch, sampler):
-        self.masks = []
-        cls = type(sampler)
-        orig = cls._launch
-
-        def launch(s, run, pot, k, step0, samples, masks_out=None, **kw):
-            if masks_out is None:
-                masks_out = torch.zeros(k, run.n, dtype=torch.uint8, device=run.dev)
-            self.masks.append(masks_out)
-            return orig(s, run, pot, k, step0, samples, masks_out=masks_out, **kw)
-        monkeypatch.setattr(cls, '_launch', launch)
-
-    def accepted(self):
-        return torch.cat(self.masks).cpu().long().sum(1)
 
 
 def _tile(d):
@@ -92,48 +78,6 @@ def _target(name, d, seed=0):
     raise ValueError(name)
 
 
-def _sampler(kind, d, pot, W, T, h, L=4, beta=1e-3, every=1, imd=None):
-    from nfmc_amd.samplers import mcmc
-    kw = dict(n_iterations=T, n_warmup_iterations=W, imd_adjustment=beta, tune_every=every)
-    if kind in ('mala', 'ula'):
-        cls = mcmc.MALA if kind == 'mala' else mcmc.ULA
-        s = cls((d,), pot, mcmc.LangevinKernel(event_size=d, step_size=h), mcmc.LangevinParameters(**kw))
-    elif kind == 'mh':
-        s = mcmc.MH((d,), pot, mcmc.MHKernel(event_size=d, inv_mass_diag=imd), mcmc.MHParameters(**kw))
-    else:
-        cls = mcmc.HMC if kind == 'hmc' else mcmc.UHMC
-        s = cls((d,), pot, mcmc.HMCKernel(event_size=d, n_leapfrog_steps=L, step_size=h), mcmc.HMCParameters(**kw))
-    return s
-
-
-def _controller_params(s, h0, imd0):
-    from oracle import samplers as osamp
-    p = s.params
-    return osamp.ControllerParams(step_size=h0, inv_mass_diag=imd0.clone(), imd_adjustment=p.imd_adjustment,
-                                  tune_step_size=bool(p.tune_step_size and p.adjustment),
-                                  tune_inv_mass_diag=bool(p.tune_inv_mass_diag))
-
-
-def _check_controller(s, ups, what):
-    last = ups[-1]
-    np.testing.assert_allclose(s.kernel.step_size, last.step_size, rtol=1e-10, err_msg=what)
-    if s.params.tune_step_size and s.params.adjustment:
-        np.testing.assert_allclose(s.kernel.da.error_sum, last.error_sum, rtol=1e-10, atol=1e-10, err_msg=what)
-        np.testing.assert_allclose(s.kernel.da.log_smooth, last.log_smooth, rtol=1e-10, atol=1e-12, err_msg=what)
-        assert s.kernel.da.iteration == last.iteration, what
-    got, want = s.kernel.inv_mass_diag.double(), last.inv_mass_diag.double()
-    assert torch.isfinite(got).all() and (got > 0).all(), what
-    np.testing.assert_allclose(got.numpy(), want.numpy(), rtol=4e-6 * len(ups) ** 0.5, atol=0, err_msg=what)
-
-
-def _shadow(states, kind, target, h, imd, seed, step0, L, what, max_tie_share=0.01):
-    from oracle import shadow
-    wl = shadow.Workload(kind, target, step_size=h, n_leapfrog=L, inv_mass_diag=imd, step0=step0)
-    rep = shadow.shadow(states, wl, seed)
-    fails = rep.failures(KAPPA, max_tie_share)
-    assert not fails, (what, fails, rep.summary())
-
-
 # ------------------------------------------------------------------- 1-3. controller, transitions, handoff
 # (kind, target, d, n, W, every): every closed-form target, every kind, every default lane layout, chain counts off the
 # tile sizes, tune_every > 1 on the staged-LDS targets
@@ -155,35 +99,17 @@ CASES = [
 
 @pytest.mark.parametrize('kind,tname,d,n,W,every', CASES)
 def test_warmup_controller_transitions_and_handoff(dev, monkeypatch, kind, tname, d, n, W, every):
-    from nfmc_amd import hip
-    from oracle import samplers as osamp
     pot, target, draw = _target(tname, d, seed=d)
     x0 = draw(n).float()
     h0 = {'mala': 0.3, 'ula': 0.05, 'hmc': 0.1, 'uhmc': 0.05, 'mh': 0.3}[kind] * d ** (-1 / 3)
     if tname in ('funnel', 'rosenbrock', 'logreg'):
         h0 *= 0.3
     imd0 = torch.full((d,), 0.3 * d ** -0.5) if kind == 'mh' else torch.ones(d)
-    T, L, seed = 6, 4, 4242 + d
-    s = _sampler(kind, d, pot, W, T, h0, L=L, every=every, imd=imd0.clone() if kind == 'mh' else None)
-    h0 = float(s.kernel.step_size)      # MH keeps its kernel's own (untuned, unused) step size
-    s.seed = seed
     # Rosenbrock's Hamiltonians are large next to their differences: fp32 rounding of the margin widens more tie windows
     ties = 0.05 if tname == 'rosenbrock' else 0.01
-    rec = _Record(monkeypatch, s)
-    wout = s.warmup(x0, show_progress=False)
-    what = '%s %s d=%d n=%d every=%d' % (kind, tname, d, n, every)
-    states = wout.samples.reshape(W, n, d)
-    ups, h_t, imd_t = osamp.replay_controller(states, rec.accepted(), every, _controller_params(s, h0, imd0))
-    assert len(ups) == math.ceil(W / every)
-    _check_controller(s, ups, what)
-    # 2. every warmup transition with the (h_t, imd_t) the replay says it ran with (warmup stream: hip.WARMUP_STEP0)
-    _shadow(torch.cat([x0[None], states]), kind, target, h_t, imd_t, seed, hip.WARMUP_STEP0, L, what + ' warmup', ties)
-    # 3. the sampling run that follows, with the tuned (non-unit) mass diagonal
-    x1 = wout.running_samples.last_sample.cpu()
-    out = s.sample(x1, show_progress=False)
-    assert torch.isfinite(out.samples).all()
-    _shadow(torch.cat([x1[None], out.samples.reshape(T, n, d)]), kind, target, s.kernel.step_size,
-            s.kernel.inv_mass_diag.clone(), seed, 0, L, what + ' sampling', ties)
+    H.warmup_matches_controller(monkeypatch, H.Problem(pot, target, target, x0, d, tname), kind, W=W, T=6, L=4, every=every,
+                                h0=h0, imd0=imd0, seed=4242 + d, what='%s %s d=%d n=%d every=%d' % (kind, tname, d, n, every),
+                                ties=ties)
 
 
 # ------------------------------------------------------------------------------------------- 4. fold levels
