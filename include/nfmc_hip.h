@@ -201,7 +201,7 @@ enum {
        (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32 with conditioners of at most 32 units).
        NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the fit kernels, the Philox4x32-7 stream and the
        NeuTra matrix-core kernels (conditioners wider than 32). */
-    NFMC_POT_PARTICLES = 11
+    NFMC_POT_PARTICLES = 11,
     /* Interacting particles in a harmonic trap (many-particle Boltzmann density): P particles in D = 1, 2 or 3
        dimensions, coordinates particle-major x = [r_0 | r_1 | .. | r_{P-1}], d = P D.  With r_ij = |r_i - r_j|:
          U = beta [ k/2 sum_i |r_i|^2 + sum_{i<j} phi(r_ij) ]                                  (constants dropped)
@@ -223,6 +223,33 @@ enum {
        (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32 with conditioners of at most 32 units).
        NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the fit kernels, the Philox4x32-7 stream and the
        NeuTra matrix-core kernels (conditioners wider than 32). */
+    NFMC_POT_LATENT_GAUSSIAN = 12
+    /* Latent Gaussian model: a Gaussian (process) prior f ~ N(m, K) on a latent vector of d coordinates, K = L L^T
+       (L the lower-triangular Cholesky factor), Lambda = K^-1, and a non-Gaussian likelihood on each coordinate with
+       an observation y_j and a weight w_j >= 0 (w_j = 0: not observed, the coordinate adds exactly 0 to U and grad U).
+       The log-Gaussian Cox process, GP classification and robust GP regression.  Negative log-likelihood l_j(f),
+       constants dropped, by likelihood code:
+         0 Poisson, log link      l = w e^f - y f                               l' = w e^f - y            (w: exposure)
+         1 binomial, logit link   l = w softplus(f) - y f                       l' = w sigmoid(f) - y     (w: trials)
+         2 Student-t noise        l = w (nu+1)/2 log1p((y-f)^2 / (nu s^2))      l' = -w (nu+1)(y-f) / (nu s^2 + (y-f)^2)
+       Two parameterisations of the same posterior:
+         centred   x = f:             U = 1/2 (x-m)^T Lambda (x-m) + sum_j l_j(x_j),   dU/dx = Lambda (x-m) + l'(x)
+         whitened  x = z, f = m + L z:  U = 1/2 |z|^2 + sum_j l_j(f_j),                  dU/dz = z + L^T l'(f)
+       n_components = d;  a_scalar = likelihood code + 4 [whitened], an integer-valued float in {0, 1, 2, 4, 5, 6};
+       b_scalar unused.  a -> the matrix block, fp32 row-major in device memory, 16-byte aligned: Lambda (d, d) when
+       centred; when whitened L^T (d, d) and behind it L (d, d), 2 d^2 floats, the upper triangle of L (lower of L^T)
+       exact zeros (the NeuTra kernels do not read it).  b -> the table, fp32 in device memory, 16-byte aligned, with
+       d4 = 4 ceil(d / 4):  8 floats ((nu+1)/2, 1/(nu s^2), nu s^2, nu+1, 0, 0, 0, 0), zeros for codes 0 and 1, then the
+       rows m, y, w of d4 floats each, zero past d.  A NULL a or b, n_components != d or an invalid code is NFMC_EINVAL;
+       a misaligned a or b is NFMC_EALIGN; d > 1024 is NFMC_EUNSUPPORTED.  Nothing is clamped: a Poisson rate that
+       overflows fp32 gives U = inf or a NaN log ratio, the samplers reject the proposal and count it as non-finite, and
+       the chain's state stays finite.  Cost: d^2 FMAs per chain and evaluation when centred, 2 d^2 when whitened (two
+       matrix-vector products streamed through one LDS tile of 16 KB), no atomics, bitwise repeatable.
+       Served by nfmc_mala_steps_f32 / nfmc_hmc_steps_f32 (general kernels, with or without a jump tail, device warmup
+       tuning included), by the register-layout kernels of nfmc_flow_mh_steps_f32 and by the VALU NeuTra kernels
+       (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32 with conditioners of at most 32 units).
+       NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the fit kernels, the Philox4x32-7 stream and the
+       NeuTra matrix-core kernels (conditioners wider than 32). */
 };
 
 typedef struct {
@@ -231,7 +258,7 @@ typedef struct {
                              NFMC_POT_ROSENBROCK: block length; NFMC_POT_STOCHASTIC_VOLATILITY: T = d - 3;
                              NFMC_POT_SPARSE_LOGISTIC_REGRESSION: N; NFMC_POT_LATTICE_PHI4: W (sites per lattice row);
                              NFMC_POT_ITEM_RESPONSE: S (students); NFMC_POT_VARYING_EFFECTS: C (groups);
-                             NFMC_POT_PARTICLES: P (particles);
+                             NFMC_POT_PARTICLES: P (particles); NFMC_POT_LATENT_GAUSSIAN: d;
                              0 for the other kinds (was `reserved`, same layout) */
     const float* a; /* (d,) or NULL -> a_scalar */
     const float* b; /* (d,) or NULL -> b_scalar */

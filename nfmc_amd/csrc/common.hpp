@@ -529,6 +529,30 @@ inline int check_particles(const NfmcPotential& p, int d) {
     return NFMC_OK;
 }
 
+// Latent Gaussian model (kind 12): what the code in a_scalar says (likelihood + 4 whitened).  false for a value that is
+// none of 0, 1, 2, 4, 5, 6.
+__host__ __device__ __forceinline__ bool latent_code(float code, int& lik, bool& white) {
+    if (!(code >= 0.f && code < 8.f)) return false;
+    const int ic = (int)code;
+    if ((float)ic != code) return false;
+    lik = ic & 3;
+    white = (ic >> 2) & 1;
+    return lik < 3;
+}
+// floats of a kind-12 table row: rows m, y, w start 8 + k latent_row(d) floats into b
+__host__ __device__ inline int latent_row(int d) { return 4 * ((d + 3) / 4); }
+
+// argument check of a kind-12 descriptor: the matrix block and the table present, n_components = d, a valid code, both
+// blocks 16-byte aligned; d > 1024 is a valid request no kernel runs
+inline int check_latent(const NfmcPotential& p, int d) {
+    int lik;
+    bool white;
+    if (!p.a || !p.b || p.n_components != d || !latent_code(p.a_scalar, lik, white)) return NFMC_EINVAL;
+    if ((((uintptr_t)p.a) & 15u) != 0 || (((uintptr_t)p.b) & 15u) != 0) return NFMC_EALIGN;
+    if (d > 1024) return NFMC_EUNSUPPORTED;
+    return NFMC_OK;
+}
+
 // LDS bytes a register-layout kernel with DP = CPL * LPC padded coordinates stages for `p` beside its flow image
 inline size_t mixture_bytes(const NfmcPotential& p, int dp, int) { return (size_t)mixture_floats(p.n_components, dp) * sizeof(float); }
 inline size_t logreg_bytes(const NfmcPotential&, int dp, int) { return (size_t)logreg_floats(dp) * sizeof(float); }
@@ -588,6 +612,7 @@ constexpr PotKind kPotKinds[] = {
     {NFMC_POT_ITEM_RESPONSE, check_irt, irt_bytes, true, true, true, true},
     {NFMC_POT_VARYING_EFFECTS, check_vfx, nullptr, true, true, true, true},
     {NFMC_POT_PARTICLES, check_particles, particles_bytes, true, true, true, true},
+    {NFMC_POT_LATENT_GAUSSIAN, check_latent, fullrank_bytes, true, true, true, true},
 };
 constexpr int kNumPotKinds = (int)(sizeof(kPotKinds) / sizeof(PotKind));
 constexpr bool pot_kinds_indexed(int i = 0) { return i == kNumPotKinds || (kPotKinds[i].kind == i && pot_kinds_indexed(i + 1)); }
@@ -601,7 +626,8 @@ constexpr const PotKind* pot_kind(int kind) { return kind >= 0 && kind < kNumPot
     M(NFMC_POT_GAUSSIAN_FULL, GaussFullPot) M(NFMC_POT_ROSENBROCK, RosenbrockPot) \
     M(NFMC_POT_STOCHASTIC_VOLATILITY, SVPot) M(NFMC_POT_SPARSE_LOGISTIC_REGRESSION, SparseLogRegPot) \
     M(NFMC_POT_LATTICE_PHI4, Phi4Pot) M(NFMC_POT_ITEM_RESPONSE, IrtPot) \
-    M(NFMC_POT_VARYING_EFFECTS, VaryEffPot) M(NFMC_POT_PARTICLES, ParticlePot)
+    M(NFMC_POT_VARYING_EFFECTS, VaryEffPot) M(NFMC_POT_PARTICLES, ParticlePot) \
+    M(NFMC_POT_LATENT_GAUSSIAN, LatentGaussPot)
 
 // The families of kernels that take a potential descriptor of any kind.  (The entry points that run kinds 0 and 1 only
 // say so themselves.)
@@ -945,6 +971,204 @@ struct GaussFullPot {
 #pragma unroll
         for (int i = 0; i < CPL; ++i) s = fmaf(r[i], cx.gr[i], s);
         cx.u = 0.5f * group_allreduce<LPC>(s);
+        return cx;
+    }
+    __device__ __forceinline__ float grad(const Ctx& cx, int i, float) const { return cx.gr[i]; }
+    __device__ __forceinline__ float term(const Ctx& cx, int i, float) const { return (lead && i == 0) ? cx.u : 0.f; }
+};
+
+// Latent Gaussian model (NFMC_POT_LATENT_GAUSSIAN, nfmc_hip.h): a Gaussian prior N(m, K) on f with a likelihood term
+// l_j(f_j) per coordinate.  latent_lik<LIK> is that term and its derivative for one coordinate (LIK 0 Poisson, 1 binomial,
+// 2 Student-t; c0 = (nu+1)/2, c1 = 1/(nu s^2), c2 = nu s^2 of the table's header); an unobserved coordinate (w = 0, the
+// padding included) gets exactly 0 for both, by a select, so that an overflowing e^f cannot turn 0 * inf into NaN.
+// Shared with latent_value_grad_row (neutra_kernels.hpp).  log1p as in softplus_sigmoid.
+template <int LIK>
+__device__ __forceinline__ void latent_lik(float f, float y, float w, float c0, float c1, float c2, float& l, float& lp) {
+    if constexpr (LIK == 0) {
+        const float e = w * fast_exp(f);
+        l = fmaf(-y, f, e);
+        lp = e - y;
+    } else if constexpr (LIK == 1) {
+        float sp, sg;
+        softplus_sigmoid(f, sp, sg);
+        l = fmaf(w, sp, -y * f);
+        lp = fmaf(w, sg, -y);
+    } else {
+        const float t = y - f, q = t * t, e = q * c1;
+        const float l1p = e < 0x1p-8f ? e * fmaf(e, fmaf(e, 1.f / 3.f, -0.5f), 1.f) : fast_ln(1.f + e);
+        l = w * c0 * l1p;
+        lp = -2.f * w * c0 * t * __builtin_amdgcn_rcpf(c2 + q);
+    }
+    const bool on = w > 0.f;
+    l = on ? l : 0.f;
+    lp = on ? lp : 0.f;
+}
+
+// The device class.  centred (x = f):  U = 1/2 r^T Lambda r + sum_j l_j(x_j),  dU/dx = Lambda r + l'(x),  r = x - m;
+// whitened (x = z, f = m + L z):  U = 1/2 |z|^2 + sum_j l_j(f_j),  dU/dz = z + L^T l'(f).
+// matvec() is GaussFullPot's loop: the (d, d) row-major matrix M streams through the LDS tile and every lane adds
+// v_i M_ij to its own coordinates j, v_i broadcast from its owner, one ds_read_b128 per register quad and row, no
+// reduction per row: out += M^T v.  The centred form is one pass (M = Lambda = Lambda^T, v = r).  The whitened form is
+// two passes through the same tile: M = L^T with v = z leaves L z in the lane's registers, the lane evaluates l and l'
+// of its own coordinates, and M = L with v = l'(f) gives L^T l'.  The known-zero triangle of L is streamed like the
+// rest.  The rows m, y, w are read from the table (global memory, one 16-byte load per register quad) where they are
+// used, not held in registers across the sampler's loop.  U: lane-local sums, then ONE group_allreduce.  The tile rule
+// of LogRegPot holds: every thread of the workgroup calls prepare() equally often; the parameterisation is
+// workgroup-uniform, so every thread runs the same number of passes.  Likelihood and parameterisation are dispatched
+// once per prepare(), outside the loops.  Padding coordinates have v = 0, zero rows / columns and w = 0.
+template <int CPL, int LPC, bool FAST>
+struct LatentGaussPot {
+    static constexpr bool kQuadratic = false;
+    static constexpr bool kStaged = true;
+    static constexpr int DP = CPL * LPC;
+    static constexpr int T = kLogRegTileFloats / DP;   // matrix rows per tile
+    static_assert(T % 4 == 0, "whole register quads per tile");
+    float* tile;          // LDS: matrix rows (T, DP)
+    const float* mat;     // Lambda | L^T then L
+    const float* tab;     // rows m, y, w of d4 floats (behind the 8 floats of the header)
+    int dd, d4;
+    int grp;              // byte address of the chain's first lane for ds_bpermute
+    int lik;
+    bool white;
+    bool lead;            // this lane holds coordinate 0 in register 0
+    float c0, c1, c2;     // Student-t constants
+    struct Ctx {
+        float u;          // U of the chain (every lane of the group)
+        float gr[CPL];    // dU/dx of this lane's coordinates
+    };
+
+    __device__ __forceinline__ static void stage(float*, const NfmcPotential&, int) {}   // prepare() streams the tiles
+    __device__ __forceinline__ void init(const NfmcPotential& p, int g, int d, float* lds) {
+        tile = lds;
+        mat = p.a;
+        tab = p.b + 8;
+        dd = d;
+        d4 = latent_row(d);
+        grp = 4 * ((int)(threadIdx.x & 63) - g);
+        lead = (g == 0);
+        lik = 0;
+        white = false;
+        latent_code(p.a_scalar, lik, white);
+        c0 = p.b[0];
+        c1 = p.b[1];
+        c2 = p.b[2];
+    }
+    // value v of lane `src` (uniform) of this lane's chain group
+    __device__ __forceinline__ float from_lane(float v, int src) const {
+        if constexpr (LPC == 1) return v;
+        else if constexpr (LPC == 64) return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
+        else return __int_as_float(__builtin_amdgcn_ds_bpermute(grp + 4 * src, __float_as_int(v)));
+    }
+    // register quad q of table row k (0 m, 1 y, 2 w) for this lane; zeros past the row
+    __device__ __forceinline__ float4 tab4(int k, int q, int g) const {
+        const int c = 4 * (q * LPC + g);
+        return c < d4 ? *reinterpret_cast<const float4*>(tab + k * d4 + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    // all threads of the workgroup: out += M^T v, M (dd, dd) row-major in global memory, v = 0 on padding coordinates
+    __device__ __forceinline__ void matvec(const float* __restrict__ M, const float (&v)[CPL], float (&out)[CPL], int g) const {
+        for (int t0 = 0; t0 < dd; t0 += T) {
+            const int rows = dd - t0 < T ? dd - t0 : T;
+            load_tile_rows<DP>(tile, M, dd, t0, rows);
+            __syncthreads();
+            const int b1 = (t0 + rows + 3) >> 2;   // register quads (4 rows each) of this tile: t0 / 4 .. b1 - 1
+            for (int b = t0 >> 2; b < b1;) {
+                const int q = b / LPC;             // the quad's register index, constant over LPC consecutive quads
+                float vq[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int k = 0; k < CPL / 4; ++k)
+                    if (k == q) {
+                        vq[0] = v[4 * k];
+                        vq[1] = v[4 * k + 1];
+                        vq[2] = v[4 * k + 2];
+                        vq[3] = v[4 * k + 3];
+                    }
+                const int bq = b1 < (q + 1) * LPC ? b1 : (q + 1) * LPC;
+                for (; b < bq; ++b) {
+                    const int src = b - q * LPC;   // the lane that holds coordinates 4 b .. 4 b + 3
+                    const float vi[4] = {from_lane(vq[0], src), from_lane(vq[1], src), from_lane(vq[2], src),
+                                         from_lane(vq[3], src)};
+                    const float* rows4 = tile + (4 * b - t0) * DP + 4 * g;
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+#pragma unroll
+                        for (int k = 0; k < CPL / 4; ++k) {
+                            const float4 w = *reinterpret_cast<const float4*>(rows4 + c * DP + 4 * k * LPC);
+                            out[4 * k] = fmaf(vi[c], w.x, out[4 * k]);
+                            out[4 * k + 1] = fmaf(vi[c], w.y, out[4 * k + 1]);
+                            out[4 * k + 2] = fmaf(vi[c], w.z, out[4 * k + 2]);
+                            out[4 * k + 3] = fmaf(vi[c], w.w, out[4 * k + 3]);
+                        }
+                    }
+                }
+            }
+        }
+    }
+    // l'(f) of this lane's coordinates into lp, their share of sum_j l_j(f_j) returned
+    template <int LIK>
+    __device__ __forceinline__ float likelihood(const float (&f)[CPL], float (&lp)[CPL], int g) const {
+        float s = 0.f;
+#pragma unroll
+        for (int q = 0; q < CPL / 4; ++q) {
+            const float4 y = tab4(1, q, g), w = tab4(2, q, g);
+            const float yy[4] = {y.x, y.y, y.z, y.w}, ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float l;
+                latent_lik<LIK>(f[4 * q + k], yy[k], ww[k], c0, c1, c2, l, lp[4 * q + k]);
+                s += l;
+            }
+        }
+        return s;
+    }
+    __device__ __forceinline__ float likelihood_of(const float (&f)[CPL], float (&lp)[CPL], int g) const {
+        return lik == 0 ? likelihood<0>(f, lp, g) : lik == 1 ? likelihood<1>(f, lp, g) : likelihood<2>(f, lp, g);
+    }
+    __device__ __forceinline__ Ctx prepare(const float (&x)[CPL], int g, int) const {
+        Ctx cx;
+        float v[CPL], mv[CPL];   // x on the real coordinates, 0 on the padding / the prior mean
+#pragma unroll
+        for (int q = 0; q < CPL / 4; ++q) {
+            const float4 m = tab4(0, q, g);
+            mv[4 * q] = m.x;
+            mv[4 * q + 1] = m.y;
+            mv[4 * q + 2] = m.z;
+            mv[4 * q + 3] = m.w;
+        }
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) v[i] = coord_of<CPL, LPC>(g, i) < dd ? x[i] : 0.f;
+        float s = 0.f;
+        if (white) {
+            float f[CPL];
+#pragma unroll
+            for (int i = 0; i < CPL; ++i) f[i] = 0.f;
+            matvec(mat, v, f, g);                                   // L z
+#pragma unroll
+            for (int i = 0; i < CPL; ++i) f[i] += mv[i];
+            float lp[CPL];
+            s = likelihood_of(f, lp, g);
+#pragma unroll
+            for (int i = 0; i < CPL; ++i) {
+                cx.gr[i] = v[i];
+                s = fmaf(0.5f * v[i], v[i], s);
+            }
+            matvec(mat + (int64_t)dd * dd, lp, cx.gr, g);           // z + L^T l'(f)
+        } else {
+            float r[CPL];
+#pragma unroll
+            for (int i = 0; i < CPL; ++i) {
+                r[i] = coord_of<CPL, LPC>(g, i) < dd ? x[i] - mv[i] : 0.f;
+                cx.gr[i] = 0.f;
+            }
+            matvec(mat, r, cx.gr, g);                               // Lambda r
+            float lp[CPL];
+            s = likelihood_of(v, lp, g);
+#pragma unroll
+            for (int i = 0; i < CPL; ++i) {
+                s = fmaf(0.5f * r[i], cx.gr[i], s);
+                cx.gr[i] += lp[i];
+            }
+        }
+        cx.u = group_allreduce<LPC>(s);
         return cx;
     }
     __device__ __forceinline__ float grad(const Ctx& cx, int i, float) const { return cx.gr[i]; }

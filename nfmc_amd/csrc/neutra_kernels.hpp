@@ -478,6 +478,109 @@ __device__ __forceinline__ float particles_value_grad_row(const float* __restric
     return fmaf(0.5f, e, u);
 }
 
+// Latent Gaussian model (NFMC_POT_LATENT_GAUSSIAN) for the row of one chain, as potential_value_grad_row: U and dU/dx
+// of LatentGaussPot (common.hpp).  The matrices and the table are wave-uniform (scalar loads); blocks of kFullRankJB
+// outputs stay in registers over i as in fullrank_value_grad_row.  latent_row_lik is the elementwise part: l'(f_j)
+// into grow[j], sum_j l_j(f_j) returned, the likelihood chosen outside the loop.
+//   centred:   grow = Lambda (x - m), one sweep; then l'(x) is added.
+//   whitened:  a first sweep over the row forms f_j = m_j + sum_{i <= j} L_ji z_i from the rows of L^T and leaves
+//              l'(f_j) in grow[j]; a second sweep over grow, held in LDS, forms z_j + sum_{i >= j} L_ij l'_i from the
+//              rows of L and overwrites grow block by block in ascending j: block j0 reads entries i >= j0 only, none of
+//              them overwritten yet.  Both sweeps skip the triangle of L that is zero by construction.
+// Kept out of potential_value_grad_row, which the fit and DLMC kernels share and which never see kind 12.
+template <int LIK>
+__device__ __forceinline__ float latent_row_lik(const float* __restrict__ f, float* __restrict__ grow, const float* __restrict__ y,
+                                                const float* __restrict__ w, float c0, float c1, float c2, int j0, int nj) {
+    float s = 0.f;
+    for (int k = 0; k < nj; ++k) {
+        float l, lp;
+        latent_lik<LIK>(f[k], y[j0 + k], w[j0 + k], c0, c1, c2, l, lp);
+        grow[j0 + k] = lp;
+        s += l;
+    }
+    return s;
+}
+__device__ __forceinline__ float latent_row_lik_of(int lik, const float* __restrict__ f, float* __restrict__ grow,
+                                                   const float* __restrict__ y, const float* __restrict__ w, float c0, float c1,
+                                                   float c2, int j0, int nj) {
+    return lik == 0 ? latent_row_lik<0>(f, grow, y, w, c0, c1, c2, j0, nj)
+         : lik == 1 ? latent_row_lik<1>(f, grow, y, w, c0, c1, c2, j0, nj)
+                    : latent_row_lik<2>(f, grow, y, w, c0, c1, c2, j0, nj);
+}
+__device__ __forceinline__ float latent_value_grad_row(const float* __restrict__ row, float* __restrict__ grow,
+                                                       const NfmcPotential& p, int d) {
+    constexpr int JB = kFullRankJB;
+    int lik = 0;
+    bool white = false;
+    latent_code(p.a_scalar, lik, white);
+    const int d4 = latent_row(d);
+    const float c0 = p.b[0], c1 = p.b[1], c2 = p.b[2];
+    const float* __restrict__ m = p.b + 8;
+    const float* __restrict__ y = m + d4;
+    const float* __restrict__ w = y + d4;
+    float u = 0.f;
+    if (!white) {
+        const float* __restrict__ lam = p.a;
+        for (int j0 = 0; j0 < d; j0 += JB) {
+            const int nj = d - j0 < JB ? d - j0 : JB;
+            float acc[JB], f[JB];
+#pragma unroll
+            for (int k = 0; k < JB; ++k) acc[k] = 0.f;
+            for (int i = 0; i < d; ++i) {
+                const float ri = row[i] - m[i];
+                const float* __restrict__ li = lam + (int64_t)i * d + j0;
+#pragma unroll
+                for (int k = 0; k < JB; ++k) acc[k] = fmaf(k < nj ? li[k] : 0.f, ri, acc[k]);
+            }
+#pragma unroll
+            for (int k = 0; k < JB; ++k) f[k] = k < nj ? row[j0 + k] : 0.f;
+            u += latent_row_lik_of(lik, f, grow, y, w, c0, c1, c2, j0, nj);
+#pragma unroll
+            for (int k = 0; k < JB; ++k)
+                if (k < nj) {
+                    u = fmaf(0.5f * (f[k] - m[j0 + k]), acc[k], u);
+                    grow[j0 + k] += acc[k];
+                }
+        }
+        return u;
+    }
+    const float* __restrict__ lt = p.a;                       // rows of L^T
+    const float* __restrict__ lo = p.a + (int64_t)d * d;      // rows of L
+    for (int j0 = 0; j0 < d; j0 += JB) {
+        const int nj = d - j0 < JB ? d - j0 : JB;
+        float f[JB];
+#pragma unroll
+        for (int k = 0; k < JB; ++k) f[k] = k < nj ? m[j0 + k] : 0.f;
+        for (int i = 0; i < j0 + nj; ++i) {                   // L^T_ij = 0 for i > j
+            const float zi = row[i];
+            const float* __restrict__ li = lt + (int64_t)i * d + j0;
+#pragma unroll
+            for (int k = 0; k < JB; ++k) f[k] = fmaf(k < nj ? li[k] : 0.f, zi, f[k]);
+        }
+        u += latent_row_lik_of(lik, f, grow, y, w, c0, c1, c2, j0, nj);
+    }
+    for (int j0 = 0; j0 < d; j0 += JB) {
+        const int nj = d - j0 < JB ? d - j0 : JB;
+        float acc[JB];
+#pragma unroll
+        for (int k = 0; k < JB; ++k) acc[k] = 0.f;
+        for (int i = j0; i < d; ++i) {                        // L_ij = 0 for i < j
+            const float gi = grow[i];
+            const float* __restrict__ li = lo + (int64_t)i * d + j0;
+#pragma unroll
+            for (int k = 0; k < JB; ++k) acc[k] = fmaf(k < nj ? li[k] : 0.f, gi, acc[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < JB; ++k)
+            if (k < nj) {
+                const float z = row[j0 + k];
+                grow[j0 + k] = z + acc[k];
+                u = fmaf(0.5f * z, z, u);
+            }
+    }
+    return u;
+}
+
 // U~(z) and grad U~(z) for this lane's chain.  zrow: latent (tile columns in latent order), read only;
 // wrow: scratch, ends holding z again (rebuilt); grow: gradient in the same column order as zrow.
 template <int HP>
@@ -494,6 +597,7 @@ __device__ __forceinline__ float adjusted_potential_grad_row(const float* __rest
                     : pot.kind == NFMC_POT_ITEM_RESPONSE ? irt_value_grad_row(wrow, grow, pot, g.d)
                     : pot.kind == NFMC_POT_VARYING_EFFECTS ? vfx_value_grad_row(wrow, grow, pot, g.d)
                     : pot.kind == NFMC_POT_PARTICLES ? particles_value_grad_row(wrow, grow, pot, g.d)
+                    : pot.kind == NFMC_POT_LATENT_GAUSSIAN ? latent_value_grad_row(wrow, grow, pot, g.d)
                                                          : potential_value_grad_row(wrow, grow, pot, g.d);  // U(x), dU/dx (neutra.py:62)
     // reverse sweep, mirror image of flow_inverse_row
     for (int c = 0; c < g.d; ++c) {                               // EA0^-1

@@ -21,6 +21,7 @@ POT_LATTICE_PHI4 = 8
 POT_ITEM_RESPONSE = 9
 POT_VARYING_EFFECTS = 10
 POT_PARTICLES = 11
+POT_LATENT_GAUSSIAN = 12
 MIXTURE_MAX_COMPONENTS = 8   # kMixMaxK (csrc/common.hpp)
 TAG_NOISE, TAG_ACCEPT, TAG_LATENT, TAG_JUMP = 0, 1, 2, 3
 CNT_ACCEPTED, CNT_ATTEMPTED, CNT_NONFINITE, CNT_WORDS = 0, 1, 2, 4
