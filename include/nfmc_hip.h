@@ -223,7 +223,7 @@ enum {
        (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32 with conditioners of at most 32 units).
        NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the fit kernels, the Philox4x32-7 stream and the
        NeuTra matrix-core kernels (conditioners wider than 32). */
-    NFMC_POT_LATENT_GAUSSIAN = 12
+    NFMC_POT_LATENT_GAUSSIAN = 12,
     /* Latent Gaussian model: a Gaussian (process) prior f ~ N(m, K) on a latent vector of d coordinates, K = L L^T
        (L the lower-triangular Cholesky factor), Lambda = K^-1, and a non-Gaussian likelihood on each coordinate with
        an observation y_j and a weight w_j >= 0 (w_j = 0: not observed, the coordinate adds exactly 0 to U and grad U).
@@ -250,6 +250,38 @@ enum {
        (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32 with conditioners of at most 32 units).
        NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the fit kernels, the Philox4x32-7 stream and the
        NeuTra matrix-core kernels (conditioners wider than 32). */
+    NFMC_POT_LATENT_GMRF = 13
+    /* Latent Gaussian Markov random field: n sites with a sparse, symmetric, positive semi-definite structure matrix R
+       of rank rho (random-walk smoothers, ICAR / Besag models on an adjacency graph, the SPDE-Matern field on a grid),
+       prior x | tau ~ tau^(rho/2) exp(-tau/2 r^T R r), r = x - m, and on every site one of the likelihoods of
+       NFMC_POT_LATENT_GAUSSIAN (same codes, same l and l', observation y_j, weight w_j >= 0, w_j = 0: not observed).
+       Three modes; q = v^T R v for the vector v named with the mode:
+         fixed tau  (d = n, v = r; the caller folds tau into the values of R)
+                    U = 1/2 q + sum_j l_j(x_j),                                  dU/dx = R r + l'(x)
+         centred    (d = n + 1, v = r; coordinate n is s = log tau, tau ~ Gamma(a, b) (shape, rate), Jacobian included)
+                    U = 1/2 e^s q - (rho/2) s + sum_j l_j(x_j) + b e^s - a s,    dU/dx_j = e^s (R r)_j + l'_j,
+                    dU/ds = 1/2 e^s q - rho/2 + b e^s - a
+         scaled     (d = n + 1, v = u; the coordinates are u with f = m + e^(-s/2) u, and s)
+                    U = 1/2 q + sum_j l_j(f_j) + b e^s - a s + ((n - rho)/2) s,  dU/du_j = (R u)_j + e^(-s/2) l'_j(f_j),
+                    dU/ds = -1/2 e^(-s/2) sum_j u_j l'_j(f_j) + b e^s - a + (n - rho)/2
+       n_components = W, the ELL width (the largest number of stored entries in a row of R), 1 <= W <= 32;
+       a_scalar = likelihood code + 4 [tau unknown] + 8 [scaled], an integer-valued float in {0, 1, 2, 4, 5, 6, 12, 13, 14};
+       b_scalar unused.  With n4 = 4 ceil(n / 4):  a -> the ELL block, fp32 in device memory, 16-byte aligned, slot-major:
+       W rows of n4 values, a[k n4 + j] = the k-th stored entry of row j of R, then W rows of n4 column indices as
+       integer-valued floats; a padding slot (and every slot of a row past n) has value 0 and its own row as index.
+       b -> the table, fp32 in device memory, 16-byte aligned: 8 floats ((nu+1)/2, 1/(nu s^2), nu s^2, nu+1, a, b, rho/2,
+       (n - rho)/2), then the rows m, y, w of n4 floats each, zero past n.  A NULL a or b, W < 1, an invalid code, d < 1
+       (d < 2 with tau unknown) is NFMC_EINVAL; a misaligned a or b is NFMC_EALIGN; W > 32 or d > 1024 is
+       NFMC_EUNSUPPORTED.  The check sees host values only; every kernel clamps every gathered column index into the
+       sites 0 .. n - 1 of the chain, so a bad table gives wrong numbers and never a read outside them.  Nothing else is clamped:
+       an overflowing e^s or Poisson rate gives a non-finite U or log ratio, the samplers reject the proposal and count
+       it as non-finite, and the chain's state stays finite.  Cost: W n FMAs and gathers per chain and evaluation, no
+       matrix stream, no atomics, bitwise repeatable.
+       Served by nfmc_mala_steps_f32 / nfmc_hmc_steps_f32 (general kernels, with or without a jump tail, device warmup
+       tuning included), by the register-layout kernels of nfmc_flow_mh_steps_f32 and by the VALU NeuTra kernels
+       (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32 with conditioners of at most 32 units).
+       NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the fit kernels, the Philox4x32-7 stream and the
+       NeuTra matrix-core kernels (conditioners wider than 32). */
 };
 
 typedef struct {
@@ -259,6 +291,7 @@ typedef struct {
                              NFMC_POT_SPARSE_LOGISTIC_REGRESSION: N; NFMC_POT_LATTICE_PHI4: W (sites per lattice row);
                              NFMC_POT_ITEM_RESPONSE: S (students); NFMC_POT_VARYING_EFFECTS: C (groups);
                              NFMC_POT_PARTICLES: P (particles); NFMC_POT_LATENT_GAUSSIAN: d;
+                             NFMC_POT_LATENT_GMRF: W (ELL width);
                              0 for the other kinds (was `reserved`, same layout) */
     const float* a; /* (d,) or NULL -> a_scalar */
     const float* b; /* (d,) or NULL -> b_scalar */

@@ -553,6 +553,31 @@ inline int check_latent(const NfmcPotential& p, int d) {
     return NFMC_OK;
 }
 
+// Latent Gaussian Markov random field (kind 13): what the code in a_scalar says (likelihood + 4 [tau unknown] +
+// 8 [scaled]).  false for a value that is none of 0, 1, 2, 4, 5, 6, 12, 13, 14 (scaled needs tau unknown).
+__host__ __device__ __forceinline__ bool gmrf_code(float code, int& lik, bool& tau, bool& scaled) {
+    if (!(code >= 0.f && code < 16.f)) return false;
+    const int ic = (int)code;
+    if ((float)ic != code) return false;
+    lik = ic & 3;
+    tau = (ic >> 2) & 1;
+    scaled = (ic >> 3) & 1;
+    return lik < 3 && (tau || !scaled);
+}
+
+// argument check of a kind-13 descriptor: the ELL block and the table present, 1 <= W = n_components, a valid code,
+// d >= 1 (d >= 2 with tau unknown: d = n + 1), both blocks 16-byte aligned; W > 32 or d > 1024 is a valid request no
+// kernel runs.  The column indices are device data the check never sees: the kernels clamp them.
+inline int check_gmrf(const NfmcPotential& p, int d) {
+    int lik;
+    bool tau, scaled;
+    if (!p.a || !p.b || p.n_components < 1 || !gmrf_code(p.a_scalar, lik, tau, scaled)) return NFMC_EINVAL;
+    if (d < (tau ? 2 : 1)) return NFMC_EINVAL;
+    if ((((uintptr_t)p.a) & 15u) != 0 || (((uintptr_t)p.b) & 15u) != 0) return NFMC_EALIGN;
+    if (p.n_components > 32 || d > 1024) return NFMC_EUNSUPPORTED;
+    return NFMC_OK;
+}
+
 // LDS bytes a register-layout kernel with DP = CPL * LPC padded coordinates stages for `p` beside its flow image
 inline size_t mixture_bytes(const NfmcPotential& p, int dp, int) { return (size_t)mixture_floats(p.n_components, dp) * sizeof(float); }
 inline size_t logreg_bytes(const NfmcPotential&, int dp, int) { return (size_t)logreg_floats(dp) * sizeof(float); }
@@ -613,6 +638,7 @@ constexpr PotKind kPotKinds[] = {
     {NFMC_POT_VARYING_EFFECTS, check_vfx, nullptr, true, true, true, true},
     {NFMC_POT_PARTICLES, check_particles, particles_bytes, true, true, true, true},
     {NFMC_POT_LATENT_GAUSSIAN, check_latent, fullrank_bytes, true, true, true, true},
+    {NFMC_POT_LATENT_GMRF, check_gmrf, irt_bytes, true, true, true, true},
 };
 constexpr int kNumPotKinds = (int)(sizeof(kPotKinds) / sizeof(PotKind));
 constexpr bool pot_kinds_indexed(int i = 0) { return i == kNumPotKinds || (kPotKinds[i].kind == i && pot_kinds_indexed(i + 1)); }
@@ -627,7 +653,7 @@ constexpr const PotKind* pot_kind(int kind) { return kind >= 0 && kind < kNumPot
     M(NFMC_POT_STOCHASTIC_VOLATILITY, SVPot) M(NFMC_POT_SPARSE_LOGISTIC_REGRESSION, SparseLogRegPot) \
     M(NFMC_POT_LATTICE_PHI4, Phi4Pot) M(NFMC_POT_ITEM_RESPONSE, IrtPot) \
     M(NFMC_POT_VARYING_EFFECTS, VaryEffPot) M(NFMC_POT_PARTICLES, ParticlePot) \
-    M(NFMC_POT_LATENT_GAUSSIAN, LatentGaussPot)
+    M(NFMC_POT_LATENT_GAUSSIAN, LatentGaussPot) M(NFMC_POT_LATENT_GMRF, GmrfPot)
 
 // The families of kernels that take a potential descriptor of any kind.  (The entry points that run kinds 0 and 1 only
 // say so themselves.)
@@ -1169,6 +1195,193 @@ struct LatentGaussPot {
             }
         }
         cx.u = group_allreduce<LPC>(s);
+        return cx;
+    }
+    __device__ __forceinline__ float grad(const Ctx& cx, int i, float) const { return cx.gr[i]; }
+    __device__ __forceinline__ float term(const Ctx& cx, int i, float) const { return (lead && i == 0) ? cx.u : 0.f; }
+};
+
+// Latent Gaussian Markov random field (NFMC_POT_LATENT_GMRF, nfmc_hip.h): n sites with the sparse structure matrix R in
+// slot-major ELL form (W = p.n_components slots; p.a = W rows of n4 = 4 ceil(n / 4) values, then W rows of n4 column
+// indices as integer-valued floats; a padding slot has value 0 and its own row as index), kind 12's likelihoods on the
+// sites (latent_lik, table p.b = 8 header floats, then the rows m, y, w of n4 floats) and optionally s = log tau as
+// coordinate n.  With v the vector of the mode, q = v^T R v, (a, b, rho/2, (n - rho)/2) = p.b[4 .. 7]:
+//   fixed tau  (d = n, v = x - m):      U = 1/2 q + sum l_j(x_j),                               dU/dx = R v + l'(x)
+//   centred    (d = n + 1, v = x - m):  U = 1/2 e^s q - (rho/2 + a) s + sum l_j(x_j) + b e^s,   dU/dx_j = e^s (R v)_j + l'_j,
+//                                       dU/ds = 1/2 e^s q - rho/2 + b e^s - a
+//   scaled     (d = n + 1, v = u, f = m + e^(-s/2) u):
+//                                       U = 1/2 q + sum l_j(f_j) + b e^s - a s + (n - rho)/2 s,
+//                                       dU/du_j = (R u)_j + e^(-s/2) l'_j(f_j),
+//                                       dU/ds = -1/2 e^(-s/2) sum u_j l'_j(f_j) + b e^s - a + (n - rho)/2
+// The access pattern is a gather: coordinate j needs v at the W columns of its row, anywhere in the chain.  The
+// workgroup's block is IrtPot's: one wave-private row of DP + 4 floats per chain (irt_floats).  prepare() stores the
+// lane's quads of v into the row (zeros on the padding; s itself at position n, which every lane then reads back: one
+// address per chain, a broadcast), and forms (R v)_j of its own coordinates slot by slot: per register quad and slot ONE
+// 16-byte load of values and ONE of indices from global memory (consecutive lanes consecutive 16 bytes, every chain the
+// same ones: the block of at most 2 x 32 x 1024 floats stays in L2) and four ds_read_b32 gathers.  ds_bpermute cannot
+// serve: it moves one register of one other lane, and the column a lane needs sits in a register whose index depends
+// on the column.  Every gathered index is clamped into the sites 0 .. n - 1 (gmrf_row in neutra_kernels.hpp clamps
+// alike), so a bad table reads a wrong site of the chain's own row: never s, another chain's row or memory outside
+// the block.  Row pitch DP + 4 as in IrtPot: the gathers of one
+// chain spread over the banks like the columns of R do; chains of one 32-lane half that gather the same column (the
+// same stencil offset) would meet in one bank at a pitch of DP >= 32 and sit 4 banks apart here.  The row is written
+// and read by ONE wave: wavefront fences (Phi4Pot), no workgroup barrier.  1/2 v^T R v, the data term and sum u l' are
+// lane-local sums; what crosses lanes goes through group_allreduce: U alone when tau is fixed, q and the data term
+// when centred, U's site part and sum u l' when scaled.  No atomics: bitwise repeatable.  The likelihood is dispatched
+// once per prepare() outside the loops (LatentGaussPot), the mode is a wave-uniform branch behind them.  Nothing is
+// clamped: an overflowing e^s or e^f gives a non-finite U, which the samplers reject and count.
+template <int CPL, int LPC, bool FAST>
+struct GmrfPot {
+    static constexpr bool kQuadratic = false;
+    static constexpr bool kStaged = true;
+    static constexpr int DP = CPL * LPC;
+    static constexpr int Q = CPL / 4;    // register quads
+    static constexpr int PITCH = DP + 4;
+    float* row;                          // LDS: this chain's row
+    const float* ell;                    // this lane's quad 0 of slot 0: values; the indices wn4 floats behind
+    const float* tab;                    // rows m, y, w of n4 floats (behind the 8 floats of the header)
+    int nn, n4, nw, wn4;                 // n, 4 ceil(n / 4), W, W n4
+    int lik;
+    bool tau, scaled;
+    bool lead;                           // this lane holds coordinate 0 in register 0
+    float c0, c1, c2;                    // Student-t constants
+    float pa, pb, hr, hn;                // Gamma(a, b) prior of tau, rho / 2, (n - rho) / 2
+    struct Ctx {
+        float u;                         // U of the chain (every lane of the group)
+        float gr[CPL];                   // dU/dx of this lane's coordinates
+    };
+
+    __device__ __forceinline__ static void order() {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+    __device__ __forceinline__ static void stage(float*, const NfmcPotential&, int) {}   // the rows are the lanes' own
+    __device__ __forceinline__ void init(const NfmcPotential& p, int g, int d, float* lds) {
+        row = lds + (int)(threadIdx.x / LPC) * PITCH;
+        lik = 0;
+        tau = scaled = false;
+        gmrf_code(p.a_scalar, lik, tau, scaled);
+        nn = tau ? d - 1 : d;
+        n4 = latent_row(nn);
+        nw = p.n_components;
+        wn4 = nw * n4;
+        ell = p.a + 4 * g;
+        tab = p.b + 8;
+        lead = (g == 0);
+        c0 = p.b[0];
+        c1 = p.b[1];
+        c2 = p.b[2];
+        pa = p.b[4];
+        pb = p.b[5];
+        hr = p.b[6];
+        hn = p.b[7];
+    }
+    // register quad q of table row k (0 m, 1 y, 2 w) for this lane; zeros past the row
+    __device__ __forceinline__ float4 tab4(int k, int q, int g) const {
+        const int c = 4 * (q * LPC + g);
+        return c < n4 ? *reinterpret_cast<const float4*>(tab + k * n4 + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    // value of the chain's row at the column a table entry names, clamped into the sites 0 .. n - 1
+    __device__ __forceinline__ float gather(float col) const {
+        const int j = (int)col;
+        return row[j < 0 ? 0 : (j > nn - 1 ? nn - 1 : j)];
+    }
+    // l'(f) of this lane's coordinates into lp, their share of sum_j l_j(f_j) returned
+    template <int LIK>
+    __device__ __forceinline__ float likelihood(const float (&f)[CPL], float (&lp)[CPL], int g) const {
+        float s = 0.f;
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            const float4 y = tab4(1, q, g), w = tab4(2, q, g);
+            const float yy[4] = {y.x, y.y, y.z, y.w}, ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float l;
+                latent_lik<LIK>(f[4 * q + k], yy[k], ww[k], c0, c1, c2, l, lp[4 * q + k]);
+                s += l;
+            }
+        }
+        return s;
+    }
+    __device__ __forceinline__ float likelihood_of(const float (&f)[CPL], float (&lp)[CPL], int g) const {
+        return lik == 0 ? likelihood<0>(f, lp, g) : lik == 1 ? likelihood<1>(f, lp, g) : likelihood<2>(f, lp, g);
+    }
+    __device__ __forceinline__ Ctx prepare(const float (&x)[CPL], int g, int) const {
+        float v[CPL], mv[CPL];           // r or u on the sites, 0 elsewhere / the prior mean
+        order();   // behind the reads of the previous evaluation
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            const float4 m = tab4(0, q, g);
+            mv[4 * q] = m.x;
+            mv[4 * q + 1] = m.y;
+            mv[4 * q + 2] = m.z;
+            mv[4 * q + 3] = m.w;
+            float st[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int i = 4 * q + k, c = coord_of<CPL, LPC>(g, i);
+                v[i] = c < nn ? (scaled ? x[i] : x[i] - mv[i]) : 0.f;
+                st[k] = (tau && c == nn) ? x[i] : v[i];
+            }
+            *reinterpret_cast<float4*>(row + 4 * (q * LPC + g)) = make_float4(st[0], st[1], st[2], st[3]);
+        }
+        order();   // the wave's stores precede its reads
+        const float s = tau ? row[nn] : 0.f;
+        const float es = tau ? fast_exp(s) : 1.f, eh = scaled ? fast_exp(-0.5f * s) : 1.f;
+        float rv[CPL];                   // (R v)_j of this lane's coordinates
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) rv[i] = 0.f;
+        const float* slot = ell;
+        for (int k = 0; k < nw; ++k, slot += n4) {
+#pragma unroll
+            for (int q = 0; q < Q; ++q) {
+                if (4 * (q * LPC + g) < n4) {
+                    const float4 a = *reinterpret_cast<const float4*>(slot + 4 * q * LPC);
+                    const float4 j = *reinterpret_cast<const float4*>(slot + wn4 + 4 * q * LPC);
+                    rv[4 * q] = fmaf(a.x, gather(j.x), rv[4 * q]);
+                    rv[4 * q + 1] = fmaf(a.y, gather(j.y), rv[4 * q + 1]);
+                    rv[4 * q + 2] = fmaf(a.z, gather(j.z), rv[4 * q + 2]);
+                    rv[4 * q + 3] = fmaf(a.w, gather(j.w), rv[4 * q + 3]);
+                }
+            }
+        }
+        order();   // the next evaluation's stores stay behind these reads
+        float f[CPL], lp[CPL];
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) f[i] = scaled ? fmaf(eh, v[i], mv[i]) : x[i];
+        const float ls = likelihood_of(f, lp, g);
+        float qf = 0.f;                  // this lane's share of v^T R v
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) qf = fmaf(v[i], rv[i], qf);
+        Ctx cx;
+        float gs = 0.f;                  // dU/ds
+        if (!tau) {
+            cx.u = group_allreduce<LPC>(fmaf(0.5f, qf, ls));
+#pragma unroll
+            for (int i = 0; i < CPL; ++i) cx.gr[i] = rv[i] + lp[i];
+        } else if (!scaled) {
+            const float qq = group_allreduce<LPC>(qf), lt = group_allreduce<LPC>(ls);
+            const float hq = 0.5f * es * qq, be = pb * es;
+            cx.u = (hq + lt) + (be - (hr + pa) * s);
+            gs = (hq - hr) + (be - pa);
+#pragma unroll
+            for (int i = 0; i < CPL; ++i) cx.gr[i] = fmaf(es, rv[i], lp[i]);
+        } else {
+            float ul = 0.f;              // this lane's share of sum u l'
+#pragma unroll
+            for (int i = 0; i < CPL; ++i) ul = fmaf(v[i], lp[i], ul);
+            const float us = group_allreduce<LPC>(fmaf(0.5f, qf, ls)), ut = group_allreduce<LPC>(ul);
+            const float be = pb * es;
+            cx.u = us + (be + (hn - pa) * s);
+            gs = fmaf(-0.5f * eh, ut, be) + (hn - pa);
+#pragma unroll
+            for (int i = 0; i < CPL; ++i) cx.gr[i] = fmaf(eh, lp[i], rv[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) {
+            const int c = coord_of<CPL, LPC>(g, i);
+            cx.gr[i] = c < nn ? cx.gr[i] : ((tau && c == nn) ? gs : 0.f);
+        }
         return cx;
     }
     __device__ __forceinline__ float grad(const Ctx& cx, int i, float) const { return cx.gr[i]; }

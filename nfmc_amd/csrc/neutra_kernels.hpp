@@ -581,6 +581,62 @@ __device__ __forceinline__ float latent_value_grad_row(const float* __restrict__
     return u;
 }
 
+// Latent Gaussian Markov random field (NFMC_POT_LATENT_GMRF) for the row of one chain, as potential_value_grad_row: U and
+// dU/dx of GmrfPot (common.hpp), the sites first and s = log tau behind them when tau is unknown.  The row is
+// addressable here, so the gather is direct: (R v)_j = sum_k val[k][j] v[idx[k][j]] with v = row - m (fixed tau,
+// centred) or row (scaled), the ELL block and the table wave-uniform (scalar loads), every index clamped into the
+// sites 0 .. n - 1.  One pass over the sites: O(W n), the three sums of GmrfPot run in registers, the s entry follows
+// the pass.  The likelihood is chosen outside the loop.  Kept out of potential_value_grad_row, which the fit and DLMC
+// kernels share and which never see kind 13.
+template <int LIK>
+__device__ __forceinline__ float gmrf_row(const float* __restrict__ row, float* __restrict__ grow, const NfmcPotential& p, int d,
+                                          bool tau, bool scaled) {
+    const int n = tau ? d - 1 : d, n4 = latent_row(n), nw = p.n_components;
+    const float c0 = p.b[0], c1 = p.b[1], c2 = p.b[2], pa = p.b[4], pb = p.b[5], hr = p.b[6], hn = p.b[7];
+    const float* __restrict__ m = p.b + 8;
+    const float* __restrict__ y = m + n4;
+    const float* __restrict__ w = y + n4;
+    const float* __restrict__ val = p.a;
+    const float* __restrict__ idx = p.a + (int64_t)nw * n4;
+    const float s = tau ? row[n] : 0.f;
+    const float es = tau ? fast_exp(s) : 1.f, eh = scaled ? fast_exp(-0.5f * s) : 1.f;
+    float us = 0.f, qq = 0.f, ls = 0.f, ut = 0.f;   // sum 1/2 v Rv + l | v^T R v | sum l | sum u l'
+    for (int j = 0; j < n; ++j) {
+        float t = 0.f;
+        for (int k = 0; k < nw; ++k) {
+            int i = (int)idx[k * n4 + j];
+            i = i < 0 ? 0 : (i > n - 1 ? n - 1 : i);
+            t = fmaf(val[k * n4 + j], scaled ? row[i] : row[i] - m[i], t);
+        }
+        const float xj = row[j], v = scaled ? xj : xj - m[j];
+        float l, lp;
+        latent_lik<LIK>(scaled ? fmaf(eh, v, m[j]) : xj, y[j], w[j], c0, c1, c2, l, lp);
+        qq = fmaf(v, t, qq);
+        ls += l;
+        us += fmaf(0.5f * v, t, l);
+        ut = fmaf(v, lp, ut);
+        grow[j] = !tau ? t + lp : (scaled ? fmaf(eh, lp, t) : fmaf(es, t, lp));
+    }
+    if (!tau) return us;
+    const float be = pb * es;
+    if (!scaled) {
+        const float hq = 0.5f * es * qq;
+        grow[n] = (hq - hr) + (be - pa);
+        return (hq + ls) + (be - (hr + pa) * s);
+    }
+    grow[n] = fmaf(-0.5f * eh, ut, be) + (hn - pa);
+    return us + (be + (hn - pa) * s);
+}
+__device__ __forceinline__ float gmrf_value_grad_row(const float* __restrict__ row, float* __restrict__ grow,
+                                                     const NfmcPotential& p, int d) {
+    int lik = 0;
+    bool tau = false, scaled = false;
+    gmrf_code(p.a_scalar, lik, tau, scaled);
+    return lik == 0 ? gmrf_row<0>(row, grow, p, d, tau, scaled)
+         : lik == 1 ? gmrf_row<1>(row, grow, p, d, tau, scaled)
+                    : gmrf_row<2>(row, grow, p, d, tau, scaled);
+}
+
 // U~(z) and grad U~(z) for this lane's chain.  zrow: latent (tile columns in latent order), read only;
 // wrow: scratch, ends holding z again (rebuilt); grow: gradient in the same column order as zrow.
 template <int HP>
@@ -598,6 +654,7 @@ __device__ __forceinline__ float adjusted_potential_grad_row(const float* __rest
                     : pot.kind == NFMC_POT_VARYING_EFFECTS ? vfx_value_grad_row(wrow, grow, pot, g.d)
                     : pot.kind == NFMC_POT_PARTICLES ? particles_value_grad_row(wrow, grow, pot, g.d)
                     : pot.kind == NFMC_POT_LATENT_GAUSSIAN ? latent_value_grad_row(wrow, grow, pot, g.d)
+                    : pot.kind == NFMC_POT_LATENT_GMRF ? gmrf_value_grad_row(wrow, grow, pot, g.d)
                                                          : potential_value_grad_row(wrow, grow, pot, g.d);  // U(x), dU/dx (neutra.py:62)
     // reverse sweep, mirror image of flow_inverse_row
     for (int c = 0; c < g.d; ++c) {                               // EA0^-1

@@ -18,8 +18,9 @@ from tqdm import tqdm
 
 from .. import hip
 from ..containers import MCMCOutput, NFMCKernel, NFMCParameters, Sampler
-from ..potentials import (FullRankGaussian, ItemResponseTheory, LatentGaussianModel, LatticePhi4, ParticleSystem,
-                          Rosenbrock, SparseLogisticRegression, StochasticVolatility, VaryingEffectsRegression)
+from ..potentials import (FullRankGaussian, ItemResponseTheory, LatentGaussianModel, LatentGMRF, LatticePhi4,
+                          ParticleSystem, Rosenbrock, SparseLogisticRegression, StochasticVolatility,
+                          VaryingEffectsRegression)
 from .common import Run, chunks, imd_tensor, progress, resolve_target
 from .mcmc import (HMC, MH, HMCKernel, HMCParameters, MHKernel, MHParameters, MetropolisKernel, MetropolisParameters,
                    MetropolisSampler)
@@ -98,11 +99,12 @@ class NeuTra(Sampler):
         """Conditioner width to present to the kernels: d = 64 / 128 with one or two hidden layers runs on the
         matrix cores (csrc/neutra_mfma.hip) also when the flow's own conditioner is narrow (zero-padded).  The matrix-core
         kernels evaluate quadratic and funnel targets only: a FullRankGaussian, a Rosenbrock, a StochasticVolatility, a
-        SparseLogisticRegression, a LatticePhi4, an ItemResponseTheory, a VaryingEffectsRegression, a ParticleSystem or a
-        LatentGaussianModel keeps the flow's own width (VALU kernels).  The sparse regression has an odd d = 2 D + 1, so
-        it never reaches the d = 64 / 128 test below; it is listed all the same."""
+        SparseLogisticRegression, a LatticePhi4, an ItemResponseTheory, a VaryingEffectsRegression, a ParticleSystem, a
+        LatentGaussianModel or a LatentGMRF keeps the flow's own width (VALU kernels).  The sparse regression has an odd
+        d = 2 D + 1, so it never reaches the d = 64 / 128 test below; it is listed all the same."""
         if isinstance(self.target, (FullRankGaussian, Rosenbrock, StochasticVolatility, SparseLogisticRegression, LatticePhi4,
-                                    ItemResponseTheory, VaryingEffectsRegression, ParticleSystem, LatentGaussianModel)):
+                                    ItemResponseTheory, VaryingEffectsRegression, ParticleSystem, LatentGaussianModel,
+                                    LatentGMRF)):
             return 0
         bij = self.kernel.flow.bijection
         ok = (getattr(bij, 'd', 0) in (64, 128) and getattr(bij, 'n_hidden_layers', 0) in (1, 2)
