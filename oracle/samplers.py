@@ -141,6 +141,7 @@ class Trace:
     n_divergences: int = 0
     moments: Optional[Moments] = None
     last: Optional[torch.Tensor] = None
+    flow_steps: List['JumpStep'] = field(default_factory=list)   # one per flow-proposal transition (imh_sample, jump_sample)
 
     def stacked(self):
         return torch.stack(self.samples, dim=0)
@@ -317,6 +318,7 @@ def jump_sample(x0, target, flow, inner_kind, n_outer, n_inner, step_size, inv_m
         jstep = base + n_inner
         x = inner.last                                                            # :209
         js = jump_transition(x, target, flow, jstep, noise, adjusted_jumps, event)
+        tr.flow_steps.append(js)
         tr.n_target_calls += js.n_target_calls
         if js.log_alpha is not None:
             tr.log_ratios.append(js.log_alpha)
@@ -379,9 +381,10 @@ def jump_transition(x, target, flow, jstep, noise, adjusted=True, event=None):
 
 
 # --------------------------------------------------------------------------- A.4 FixedIMH
-def imh_sample(x0, target, flow, n_iterations, noise=None, store=True, step0=0):
+def imh_sample(x0, target, flow, n_iterations, noise=None, store=True, step0=0, adjusted=True):
     """`FixedIMH.sample` (nfmc/algorithms/sampling/nfmc/imh.py:200-255).  Iteration `it` draws at transition step0 + it;
-    log q of the current states is computed from x0 and then carried (imh.py:214,233)."""
+    log q of the current states is computed from x0 and then carried (imh.py:214,233).  Every transition is kept as a JumpStep in `flow_steps` (u_x, u_xp, f_x, f_xp:
+    the four numbers of the log ratio).  adjusted=False keeps every proposal; the log ratios are still formed."""
     noise = noise or TorchNoise()
     n = x0.shape[0]
     event = x0.shape[1:]
@@ -395,11 +398,16 @@ def imh_sample(x0, target, flow, n_iterations, noise=None, store=True, step0=0):
             x_prime, ld_inv = flow.bijection.inverse(z)                           # :221
             f_xp = flow.base_log_prob(z) - ld_inv
             x_prime = x_prime.reshape(n, -1)
-            log_alpha = (-target(x_prime)) - (-target(x)) + f_x - f_xp           # :223-228
+            u_x, u_xp = target(x), target(x_prime)
+            log_alpha = (-u_xp) - (-u_x) + f_x - f_xp                             # :223-228
             log_u = noise.uniform(n, step, philox.TAG_JUMP).log()                 # :229
-            mask = torch.less(log_u, log_alpha)                                   # :230
+            mask = torch.less(log_u, log_alpha) if adjusted else torch.ones(n, dtype=torch.bool)   # :230
             x[mask] = x_prime[mask]                                               # :232
+            f_before = f_x.clone()
             f_x[mask] = f_xp[mask]                                                # :233
+            tr.flow_steps.append(JumpStep(x=x.clone(), x_prime=x_prime.clone(), mask=mask.clone(), log_alpha=log_alpha.clone(),
+                                          log_u=log_u, u_x=u_x.detach().clone(), u_xp=u_xp.detach().clone(), f_x=f_before,
+                                          f_xp=f_xp.clone(), n_target_calls=2 * n))
             tr.moments.update(x)                                                  # :242
             tr.n_target_calls += 2 * n
             tr.n_accepted += int(mask.sum())

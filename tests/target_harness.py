@@ -8,10 +8,18 @@ are arguments without a default: each test file states its own.  Where the files
 an argument whose default is the stricter behaviour.  tests/test_host_target_harness.py checks on the CPU that the
 comparisons here do fail when they should.
 
+The flow-proposal Metropolis step (flow_mh_b_kernel, and the jump tail of mala_kernel / hmc_kernel) is compared row by
+row: FlowRecord hands every launch a mask and a log-ratio buffer, compare_flow_mh holds them against the oracle's
+JumpSteps, centred_flow_pair and centred give inputs under which proposals are accepted, and flow_cases is the matrix of
+layouts, widths and couplings that a per-target file runs through run_flow_case.  Every figure about those inputs comes
+from the fp64 (or fp32) oracle on the CPU: oracle_only and probe_flow_inputs run the cases' inputs without a GPU.
+
 A problem is a `Problem`: the package potential, its fp64 restatement `ref` (U alone, for magnitudes and NeuTra), the
 fp64 target the oracle samplers run on, the fp32 starts x0 (n, d), d and a name for messages.  The `_Problem` classes of
 the newer files have the same attributes and are passed as they are."""
 import collections
+import contextlib
+import copy
 import ctypes as C
 import math
 
@@ -80,6 +88,140 @@ def compare_decisions(rec, tr, kind, x0, ref, what, *, mag=None, skip_below_minu
     assert bool((err[agree] <= tol[agree]).all()), (what, float(err[agree].max()))
 
 
+def affine_c(d):
+    """the unexplained part of a flow-MH log ratio's tolerance for affine couplings (tests/test_gpu_parity.py)"""
+    return 2e-4 * max(1.0, d / 64)
+
+
+SPLINE_C_FACTOR = 4.0      # see spline_c
+# worst fp32-against-fp64 difference of log q over the spline cases of each file's matrix, from the CPU alone: 4 x the
+# figure exceeds affine_c (2e-4 up to d = 64) only for particles, by a quarter
+SPLINE_FIGURES = {'fullrank': 2.4e-5, 'gmrf': 2.8e-5, 'latent_gaussian': 2.3e-5, 'logreg': 2.4e-5, 'mixture': 2.2e-5,
+                  'phi4': 2.1e-5, 'irt': 2.4e-5, 'varying_effects': 3.1e-5, 'rosenbrock': 4.2e-5, 'sv': 4.4e-5,
+                  'sparse_logreg': 2.5e-5, 'particles': 6.4e-5}
+
+
+def spline_c(d, of, steps):
+    """The same for spline couplings, measured against the reference and not against the kernels: the oracle flow cast
+    to fp32 on the CPU against itself in fp64 at the case's own proposals (the inverse pass and log q at the oracle's
+    latents, re-derived from x' through the fp64 forward pass; the forward pass and log q at x'), SPLINE_C_FACTOR = 4
+    times the worst difference of log q over the case, and never less than affine_c(d).  The flow alone: what the fp32
+    proposal's rounding does to U(x') is no part of it, as it is none of affine_c.
+
+    Measured on the CPU at the spline cases of the per-target files' matrices (d = 3 .. 101, widths 4 and 8), worst
+    fp32-against-fp64 difference per file: SPLINE_FIGURES.  Returns (c, the worst difference)."""
+    f32 = copy.deepcopy(of).float()
+    worst = 0.0
+    with torch.no_grad():
+        for js in steps:
+            xp = js.x_prime.reshape(js.x_prime.shape[0], *of.event_shape)
+            z, _ = of.bijection.forward(xp)                                   # the latents the proposals came from
+            _x32, ld32 = f32.bijection.inverse(z.float())
+            lq_inv = (f32.base_log_prob(z.float()) - ld32).double()
+            worst = max(worst, float((lq_inv - js.f_xp).abs().max()),
+                        float((f32.log_prob(xp.float()).double() - of.log_prob(xp)).abs().max()))
+    return max(affine_c(d), SPLINE_C_FACTOR * worst), worst
+
+
+def flow_mh_tolerance(steps, c):
+    """(T, n): c + 2e-5 |log r| + 8 ulp(fp32) (|U(x)| + |U(x')| + |log q(x)| + |log q(x')|), the four fp32 numbers the
+    kernel subtracts (csrc/flow_b_mh.hpp: lr = -u_xp + u_x + f_x - f_xp)"""
+    lr = torch.stack([js.log_alpha.reshape(-1).double() for js in steps])
+    size = torch.stack([(js.u_x.abs() + js.u_xp.abs() + js.f_x.abs() + js.f_xp.abs()).reshape(-1).double() for js in steps])
+    size = torch.where(torch.isfinite(size), size, torch.zeros_like(size))
+    return c + 2e-5 * torch.where(torch.isfinite(lr), lr.abs(), torch.zeros_like(lr)) + 8 * 2.0 ** -24 * size
+
+
+def u_sensitivity_of(steps, target, ulps=4):
+    """(T, n): ulps ulp(fp32) sum_i |dU/dx_i (x')| |x'_i| in fp64 autograd: the kernel's proposal is an fp32 flow image
+    whose every coordinate carries a few roundings (the elementwise layers and the coupling: 4), and a potential of r^-12
+    terms turns those into a change of U(x') that the magnitudes of flow_mh_tolerance do not see"""
+    out = []
+    for js in steps:
+        x = js.x_prime.detach().clone().requires_grad_(True)
+        u = target(x)
+        u = torch.where(torch.isfinite(u), u, torch.zeros_like(u))
+        g, = torch.autograd.grad(u.sum(), x)
+        out.append(ulps * 2.0 ** -24 * (g.abs() * x.detach().abs()).sum(1))
+    return torch.stack(out)
+
+
+def oracle_inputs_ok(steps, what, *, margin, floor=None, cap=0.10, skip_below_minus_50=False):
+    """What a flow-MH case asks of its inputs, from the fp64 oracle alone: at least `floor` of the proposals accepted
+    (None: no floor), under `cap` of the chains within `margin` of a tie, every log ratio finite and above -50 unless
+    skip_below_minus_50.  Returns (acceptance, tie share, least log ratio)."""
+    lr = torch.stack([js.log_alpha.reshape(-1).double() for js in steps])
+    lu = torch.stack([js.log_u.reshape(-1).double() for js in steps])
+    acc = float(torch.stack([js.mask.reshape(-1) for js in steps]).float().mean())
+    ties = float(((lu - lr).abs() < margin).any(0).float().mean())
+    print('%s: oracle accepts %.3f of the proposals, %.1f %% of the chains near a tie, log ratios %.1f .. %.1f'
+          % (what, acc, 100 * ties, float(lr.min()), float(lr.max())))
+    if floor is not None:
+        assert acc >= floor, (what, 'acceptance', acc, floor)
+    assert ties < cap, (what, 'near-ties', ties)
+    if not skip_below_minus_50:
+        assert bool(torch.isfinite(lr).all()) and float(lr.min()) > -50, (what, 'log ratio', float(lr.min()))
+    return acc, ties, float(lr.min())
+
+
+def compare_flow_mh(got_m, got_lr, steps, what, *, c, margin, comparable=None, floor=None, cap=0.10,
+                    skip_below_minus_50=False, adjusted=True, min_share=0.97, u_sensitivity=None):
+    """The kernel's decisions got_m (T, n) bool and log ratios got_lr (T, n) of T flow-proposal Metropolis transitions
+    against the oracle's JumpSteps, row by row.  A row (transition, chain) is comparable while the chain has followed
+    the oracle: before its first disagreeing decision, or, with `comparable` (T, n) given (the jump samplers: inner
+    transitions lie between the jumps), where that says so.  In order:
+      the inputs (oracle_inputs_ok: floor, tie cap, finite log ratios);
+      more than min_share of the rows comparable;
+      decisions: equal on every comparable row whose fp64 |log u - log r| exceeds margin + the row's tolerance (there
+        neither the kernel's log ratio nor its log u can turn the test), and on more than min_share of all comparable rows;
+      log ratios to flow_mh_tolerance(steps, c) on every comparable row (with skip_below_minus_50: on those whose fp64
+        log ratio is finite and above -50; the others must be rejected).
+    Unadjusted (every proposal kept): all decisions 1, the log ratios compared on every row.
+    u_sensitivity (T, n), for a target as steep as a pair potential alone: what the fp32 rounding of the proposal's
+    coordinates does to U(x'), u_sensitivity_of(steps, target), added to the tolerance under its own name.
+    Returns (mask (n,) of the chains that followed through every transition, worst log-ratio error over tolerance)."""
+    got_m, got_lr = got_m.bool(), got_lr.double()
+    want_m = torch.stack([js.mask.reshape(-1).bool() for js in steps])
+    want_lr = torch.stack([js.log_alpha.reshape(-1).double() for js in steps])
+    lu = torch.stack([js.log_u.reshape(-1).double() for js in steps])
+    assert got_m.shape == want_m.shape == got_lr.shape, (got_m.shape, want_m.shape, got_lr.shape)
+    tol = flow_mh_tolerance(steps, c)
+    if u_sensitivity is not None:
+        tol = tol + torch.where(torch.isfinite(u_sensitivity), u_sensitivity, torch.zeros_like(u_sensitivity))
+    if not adjusted:
+        assert bool(got_m.all()) and bool(want_m.all()), what
+        rows = torch.ones_like(want_m)
+    else:
+        oracle_inputs_ok(steps, what, margin=margin, floor=floor, cap=cap, skip_below_minus_50=skip_below_minus_50)
+        same = got_m == want_m
+        if comparable is None:
+            first = torch.ones(1, same.shape[1], dtype=torch.bool)
+            comparable = torch.cumprod(torch.cat([first, same[:-1]]).int(), 0).bool()
+        share = float(comparable.float().mean())
+        assert share > min_share, (what, 'comparable rows', share)
+        clear = comparable & ((lu - want_lr).abs() > margin + tol)
+        wrong = clear & ~same
+        assert not bool(wrong.any()), (what, 'decisions differ on %d rows clear of a tie' % int(wrong.sum()),
+                                       want_lr[wrong][:4].tolist(), got_lr[wrong][:4].tolist())
+        assert float(same[comparable].float().mean()) > min_share, what
+        rows = comparable
+        if skip_below_minus_50:
+            hopeless = ~torch.isfinite(want_lr) | (want_lr <= -50)
+            assert not bool(got_m[comparable & hopeless].any()), what
+            rows = comparable & ~hopeless
+    assert bool(rows.any()), (what, 'no log ratio to compare')
+    err = (got_lr - want_lr).abs()
+    err = torch.where(torch.isnan(err), torch.full_like(err, math.inf), err)
+    worst = int(torch.argmax(torch.where(rows, err / tol, torch.zeros_like(err))))
+    t_w, c_w = divmod(worst, err.shape[1])
+    ratio = float((err / tol)[t_w, c_w])
+    print('%s: worst log-ratio error %.2e at tolerance %.2e (log r %.3f), accepted %d of %d'
+          % (what, float(err[t_w, c_w]), float(tol[t_w, c_w]), float(want_lr[t_w, c_w]), int(got_m.sum()), got_m.numel()))
+    assert bool((err[rows] <= tol[rows]).all()), (what, float(err[t_w, c_w]), float(tol[t_w, c_w]))
+    follows = (comparable & same).all(0) if adjusted else torch.ones(got_m.shape[1], dtype=torch.bool)
+    return follows, ratio
+
+
 # ------------------------------------------------------------------------------------- spies and recorders
 class Spy:
     """Counts the split-path transitions of the mcmc samplers (none on the fused route).  A sampler class that holds
@@ -126,21 +268,183 @@ class Record:
         return torch.cat(self.masks).cpu().long().sum(1)
 
 
+class FlowRecord:
+    """As Record for the flow-proposal Metropolis step: every launch_flow_mh (the name as nfmc_amd.samplers.jump and
+    .imh bind it) is handed a mask buffer and a log-ratio buffer, and every jump tail (make_jump_tail) a mask_out and a
+    log_ratio_out of its own; stacked() is (T, n) in the order of the transitions.  `tails` counts the jumps that rode
+    behind an inner launch, `launches` those on the flow-MH kernel."""
+
+    def __init__(self, monkeypatch):
+        from nfmc_amd import hip
+        from nfmc_amd.samplers import imh, jump
+        self.masks, self.log_ratios, self.tails, self.launches = [], [], 0, 0
+        orig, orig_tail = jump.launch_flow_mh, jump.make_jump_tail
+
+        def launch(run, flow, pot, logq, k, step0, cached, adjusted, stats_struct, samples=None, masks_out=None,
+                   log_ratio_out=None):
+            if masks_out is None:
+                masks_out = torch.zeros(k, run.n, dtype=torch.uint8, device=run.dev)
+            if log_ratio_out is None:
+                log_ratio_out = torch.zeros(k, run.n, dtype=torch.float32, device=run.dev)
+            self.masks.append(masks_out)
+            self.log_ratios.append(log_ratio_out)
+            self.launches += 1
+            return orig(run, flow, pot, logq, k, step0, cached, adjusted, stats_struct, samples, masks_out, log_ratio_out)
+
+        def tail(run, flow, adjusted):
+            t = orig_tail(run, flow, adjusted)
+            m = torch.zeros(1, run.n, dtype=torch.uint8, device=run.dev)
+            lr = torch.zeros(1, run.n, dtype=torch.float32, device=run.dev)
+            t.mask_out, t.log_ratio_out = hip.ptr(m, torch.uint8), hip.ptr(lr)
+            t._keep += [m, lr]
+            self.masks.append(m)
+            self.log_ratios.append(lr)
+            self.tails += 1
+            return t
+        for mod in (jump, imh):
+            monkeypatch.setattr(mod, 'launch_flow_mh', launch)
+        monkeypatch.setattr(jump, 'make_jump_tail', tail)
+
+    def stacked(self):
+        return torch.cat(self.masks).cpu().bool(), torch.cat(self.log_ratios).cpu()
+
+
 # --------------------------------------------------------------------------------------------- builders
-def flow_pair(d, seed=5, n_hidden=None, spline=False):
-    """(package flow, fp64 oracle flow) with the same perturbed weights (oracle.flow.perturb_, every parameter touched)"""
+def _flow_objects(d, n_hidden, spline, n_layers):
+    """(package flow, oracle flow) of one architecture, weights untouched"""
     from nfmc_amd.flows import Flow, RealNVP
     from nfmc_amd.util import create_flow_object
     from oracle import flow as oflow
-    ck = {} if n_hidden is None else {'conditioner_kwargs': {'n_hidden': n_hidden}}
+    kw = {} if n_hidden is None else {'conditioner_kwargs': {'n_hidden': n_hidden}}
+    if n_layers is not None:
+        kw['n_layers'] = n_layers
     if spline:
-        of = oflow.perturb_(oflow.Flow(oflow.CRQNSF((d,))), seed, 0.3, 0.75)
-        f = create_flow_object('c-rqnsf', (d,))
+        return create_flow_object('c-rqnsf', (d,), **kw), oflow.Flow(oflow.CRQNSF((d,), **kw))
+    return Flow(RealNVP((d,), **kw)), oflow.Flow(oflow.RealNVP((d,), **kw))
+
+
+def flow_pair(d, seed=5, n_hidden=None, spline=False, n_layers=None, init_seed=None):
+    """(package flow, fp64 oracle flow) with the same perturbed weights (oracle.flow.perturb_, every parameter touched);
+    n_hidden and n_layers (coupling layers) for either coupling, None: the architecture's defaults.  The weights that are
+    perturbed are torch's default initialisation, drawn from the global generator as it stands; with init_seed they are
+    drawn from that seed instead (the global generator is left as it was), which a case whose inputs must satisfy a
+    condition needs."""
+    from oracle import flow as oflow
+    if init_seed is None:
+        f, of = _flow_objects(d, n_hidden, spline, n_layers)
     else:
-        of = oflow.perturb_(oflow.Flow(oflow.RealNVP((d,), **ck)), seed, 0.2, 0.7071)
-        f = Flow(RealNVP((d,), **ck))
+        with torch.random.fork_rng(devices=[]):
+            torch.manual_seed(init_seed)
+            f, of = _flow_objects(d, n_hidden, spline, n_layers)
+    of = oflow.perturb_(of, seed, 0.3, 0.75) if spline else oflow.perturb_(of, seed, 0.2, 0.7071)
     f.load_state_dict(of.state_dict())
     return f, of.double()
+
+
+_LAPLACE = {}
+
+
+def laplace_fit(p):
+    """(mode c, marginal standard deviations s) of a Laplace fit of p.target in fp64 on the CPU: LBFGS from the mean of
+    the starts, then the autograd Hessian H at the mode; s = sqrt(diag(H^-1)), the eigenvalues of H clamped from below at
+    1e-8 of the largest (a flat or negative direction gets a wide, finite scale).  One fit per problem object."""
+    hit = _LAPLACE.get(id(p.target))
+    if hit is not None and hit[0] is p.target:
+        return hit[1], hit[2]
+    d = p.d
+    c = p.x0.double().reshape(-1, d).mean(0).clone().requires_grad_(True)
+    opt = torch.optim.LBFGS([c], lr=1.0, max_iter=500, tolerance_grad=1e-10, tolerance_change=1e-14, line_search_fn='strong_wolfe')
+
+    def closure():
+        opt.zero_grad()
+        u = p.target(c[None]).sum()
+        u.backward()
+        return u
+    opt.step(closure)
+    c = c.detach()
+    hess = torch.autograd.functional.hessian(lambda x: p.target(x[None]).sum(), c, vectorize=True)
+    lam, vec = torch.linalg.eigh(0.5 * (hess + hess.t()))
+    lam = lam.clamp_min(1e-8 * float(lam.max()))
+    s = ((vec ** 2) / lam[None]).sum(1).sqrt()
+    assert torch.isfinite(c).all() and torch.isfinite(s).all() and bool((s > 0).all()), p.name
+    _LAPLACE[id(p.target)] = (p.target, c, s)
+    return c, s
+
+
+def local_fit(p, shrink, at='starts'):
+    """(point c, scales s) for a proposal that sits INSIDE the target where laplace_fit has no use: c the mean of the
+    file's starts (at='starts'; a point of ordinary energy where the mode is degenerate, as in a funnel's neck) or the
+    LBFGS mode (at='mode'), s = shrink / sqrt(|d^2 U / dx_i^2|) at c, the conditional standard deviations times shrink
+    (a curvature under 1e-8 of the largest counts as that).  With chains started at c + s eps (centred) the target
+    varies little across such a proposal when shrink is small, so the fp64 oracle accepts; U(x'), log q(x') and the
+    carry are exercised as with any other accepting input."""
+    key = (id(p.target), shrink, at)
+    hit = _LAPLACE.get(key)
+    if hit is not None and hit[0] is p.target:
+        return hit[1], hit[2]
+    c = laplace_fit(p)[0] if at == 'mode' else p.x0.double().reshape(-1, p.d).mean(0)
+    hess = torch.autograd.functional.hessian(lambda x: p.target(x[None]).sum(), c, vectorize=True)
+    curv = torch.diagonal(hess).abs()
+    s = shrink / curv.clamp_min(1e-8 * float(curv.max())).sqrt()
+    assert torch.isfinite(c).all() and torch.isfinite(s).all() and bool((s > 0).all()), p.name
+    _LAPLACE[key] = (p.target, c, s)
+    return c, s
+
+
+def centred_flow_pair(p, seed=5, n_hidden=None, spline=False, n_layers=None, *, scale, centre=None):
+    """flow_pair's architecture as the identity map (every weight 0; a spline's interior knot derivatives 1), every
+    parameter perturbed by `scale` (oracle.flow.perturb_), and the data-side ElementwiseAffine set so that the flow's
+    forward pass starts z = (x - c) / s, (c, s) = laplace_fit(p) or the `centre` given (local_fit), the perturbation on
+    top: a proposal that sits on the target closely enough for the Metropolis test to accept.  Nothing is drawn from
+    torch's global generator."""
+    from oracle import flow as oflow
+    c, s = laplace_fit(p) if centre is None else centre
+    f, of = _flow_objects(p.d, n_hidden, spline, n_layers)
+    of = of.double()
+    with torch.no_grad():
+        for prm in of.parameters():
+            prm.zero_()
+        for layer in of.bijection.layers:
+            if isinstance(layer, oflow.RQSCoupling):             # d_k = MIN_DERIV + softplus(raw) = 1: the identity
+                k, raw = layer.n_bins, math.log(math.expm1(1.0 - oflow.RQS_MIN_DERIV))
+                layer.conditioner[-1].bias.reshape(layer.d_b, 3 * k - 1)[:, 2 * k:] = raw
+    of = oflow.perturb_(of, seed, scale)
+    with torch.no_grad():
+        first = of.bijection.layers[0]                      # forward: exp(log_scale) x + shift
+        first.log_scale.sub_(s.log())
+        first.shift.sub_(torch.exp(first.log_scale) * c)
+    f.load_state_dict({k: v.float() for k, v in of.state_dict().items()})
+    of.load_state_dict({k: v.double() for k, v in f.state_dict().items()})   # the oracle holds the fp32 weights exactly
+    return f, of
+
+
+def flow_inputs(p, d, n, flow_seed=5, spline=False, from_d=25, centre=None):
+    """The inputs of the files' IMH and jump cases from before the matrix: (problem, flows).  From d = 25 up the
+    fp64 oracle alone accepts no proposal of a flow about the origin, so those cases run on a centred flow
+    (centred_flow_pair about laplace_fit or the `centre` given; RealNVP perturbation 0.2, 0.05 from d = 200, splines half
+    of that) from centred starts; below,
+    flow_pair's flow about the origin (its initial weights drawn from flow_seed) and the file's own starts."""
+    if d < from_d:
+        return p, flow_pair(d, flow_seed, spline=spline, init_seed=flow_seed)
+    scale = (0.2 if d < 200 else 0.05) * (0.5 if spline else 1.0)
+    return centred(p, n, 3, centre), centred_flow_pair(p, flow_seed, spline=spline, scale=scale, centre=centre)
+
+
+def with_starts(p, x0):
+    """the problem p with other starts (p itself is shared and stays as it is)"""
+    if hasattr(p, '_replace'):
+        return p._replace(x0=x0)
+    q = copy.copy(p)
+    q.x0 = x0
+    return q
+
+
+def centred(p, n, seed, centre=None):
+    """p started at c + s eps rounded to fp32, (c, s) = laplace_fit(p) or the `centre` given: n chains, eps ~ N(0, I) of
+    `seed`"""
+    c, s = laplace_fit(p) if centre is None else centre
+    eps = torch.randn(n, p.d, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
+    return with_starts(p, (c + s * eps).float())
 
 
 def mcmc_sampler(kind, event_shape, target, T, h, L=5, imd=None, *, imd_kinds):
@@ -177,9 +481,9 @@ def neutra_hmc_sampler(d, pot, f, T, L, h):
                             mcmc.HMCParameters(), neutra.NeuTraKernel((d,), flow=f), neutra.NeuTraParameters(n_iterations=T))
 
 
-def imh_run(monkeypatch, pot, d, f, x0, T, seed):
+def imh_run(monkeypatch, pot, d, f, x0, T, seed, composed=False):
     """T FixedIMH transitions, every one on the sequential flow-MH kernel: neither nfmc_imh_parallel_f32 nor the
-    composed step"""
+    composed step; with `composed`, every one on the composed step (split_flow_mh) and none on either kernel"""
     from nfmc_amd.samplers import imh
     s = imh.FixedIMH((d,), pot, imh.IMHKernel((d,), flow=f), imh.IMHParameters(n_iterations=T))
     s.seed = seed
@@ -195,7 +499,10 @@ def imh_run(monkeypatch, pot, d, f, x0, T, seed):
     for name in list(calls):
         spy(name)
     out = s.sample(x0, show_progress=False)
-    assert calls['launch_flow_mh'] >= 1 and calls['launch_imh_parallel'] == 0 and calls['split_flow_mh'] == 0, calls
+    if composed:
+        assert calls == {'launch_imh_parallel': 0, 'launch_flow_mh': 0, 'split_flow_mh': T}, calls
+    else:
+        assert calls['launch_flow_mh'] >= 1 and calls['launch_imh_parallel'] == 0 and calls['split_flow_mh'] == 0, calls
     assert out.statistics.n_attempted_trajectories == x0.shape[0] * T
     return out
 
@@ -335,49 +642,340 @@ def native_matches_oracle(monkeypatch, p, kind, T, s, oracle, *, seed, what, com
         decisions(rec_k, tr, kind, p.x0, p.ref, what)
 
 
-def jump_mala_matches_oracle(monkeypatch, p, *, T, Kin, seed, h, imd, fuse_tail, spline, atol, rtol, share, jump_slack):
-    """jump_mala on a fixed perturbed flow, native stream: inner MALA fused, the jump on the register flow-MH kernel or,
-    with fuse_tail, as the tail of the last inner launch (affine flows only).  imd None: the inner kernel is the
-    sampler's default one with its step size set to h; else LangevinKernel(step_size=h, inv_mass_diag=imd).  A share of
-    the chains must follow the oracle through all T (Kin + 1) transitions, and the accepted jumps agree to jump_slack."""
+_ORACLE_ONLY = [False]
+
+
+@contextlib.contextmanager
+def oracle_only():
+    """Inside, the flow-MH bodies below stop after the conditions on their inputs (oracle_inputs_ok), which need the fp64
+    oracle alone: the host tests run every GPU case's inputs through them on the CPU."""
+    _ORACLE_ONLY[0] = True
+    try:
+        yield
+    finally:
+        _ORACLE_ONLY[0] = False
+
+
+def _param_sets(fn):
+    """the keyword sets of a test function's pytest.mark.parametrize marks"""
+    sets = [{}]
+    for m in getattr(fn, 'pytestmark', []):
+        if m.name != 'parametrize':
+            continue
+        names = [v.strip() for v in m.args[0].split(',')] if isinstance(m.args[0], str) else list(m.args[0])
+        rows = [getattr(v, 'values', v) for v in m.args[1]]
+        sets = [dict(s, **dict(zip(names, row if len(names) > 1 else (row,)))) for s in sets for row in rows]
+    return sets
+
+
+def probe_flow_inputs(module, monkeypatch):
+    """Every case of the tests a GPU test file names in FLOW_TESTS, on the CPU and up to the conditions on its inputs
+    (oracle_only): the acceptance floor, the tie cap and the finite log ratios hold for the fp64 oracle alone.  Returns
+    the number of cases."""
+    count = 0
+    with oracle_only():
+        for name in module.FLOW_TESTS:
+            fn = getattr(module, name)
+            for kw in _param_sets(fn):
+                fn(None, monkeypatch, **kw)
+                count += 1
+    return count
+
+
+def flow_layout(d, n, cfg=None):
+    """(CPL, LPC) csrc/flow_b_kernels.hip: flow_mh_b_launch picks: the smallest capacity CPL LPC >= d, at equal capacity
+    CPL = 4 up to 4096 chains and 8 above; cfg = (cpl, lpc): the NFMC_FLOWB_CFG override, taken when it holds d"""
+    cfgs = ((4, 1), (4, 2), (4, 4), (4, 8), (8, 8), (4, 16), (8, 16), (4, 32), (8, 32), (4, 64), (8, 64))
+    if cfg is not None and tuple(cfg) in cfgs and cfg[0] * cfg[1] >= d:
+        return tuple(cfg)
+    want, best = (4 if n <= 4096 else 8), None
+    for k in cfgs:
+        if k[0] * k[1] < d:
+            continue
+        if best is None or k[0] * k[1] < best[0] * best[1] or (k[0] * k[1] == best[0] * best[1] and k[0] == want):
+            best = k
+    return best
+
+
+def jump_comparable(got, want, n_inner, atol, rtol):
+    """(T, n): the chain's kept states of every transition before jump i agree with the oracle's, so that jump i starts
+    from the oracle's state; got, want (T (n_inner + 1), n, d)"""
+    ok = ((got - want).abs() <= atol + rtol * want.abs()).all(2)                    # (transitions, n)
+    before = torch.cumprod(torch.cat([torch.ones(1, ok.shape[1], dtype=torch.bool), ok[:-1]]).int(), 0).bool()
+    return before[n_inner::n_inner + 1]
+
+
+def jump_matches_oracle(monkeypatch, p, inner_kind, *, T, Kin, seed, h, imd, fuse_tail, spline, atol, rtol, share, jump_slack,
+                        margin, skip_below_minus_50, L=3, flows=None, floor=None, tail_expected=None, refused=False):
+    """jump_mala / jump_hmc (inner_kind 'mala' / 'hmc', L leapfrog steps) on a fixed flow, native stream: the inner
+    transitions fused, the jump on the register flow-MH kernel or, with fuse_tail, as the tail of the last inner launch
+    (affine flows only).  flows None: flow_pair's perturbed flow about the origin, else (package flow, oracle flow).
+    imd None: the inner kernel is the sampler's default one with its step size set to h; else the kernel of
+    (step_size=h, inv_mass_diag=imd).  The jumps' decisions and log ratios by compare_flow_mh on the chains that reach
+    each jump in the oracle's state; a share of the chains must follow the oracle through all T (Kin + 1) transitions, and
+    the accepted jumps agree to jump_slack and equal the kernel's own masks.  refused: the flow-MH probe refuses the shape
+    (the 120 KB LDS bound), every jump is composed (split_flow_mh) and the states and counters alone are compared.  tail_expected: whether every jump must have
+    ridden behind the inner launch (None: fuse_tail and not spline, as production decides for most kinds)."""
     from nfmc_amd.containers import NFMCKernel
     from nfmc_amd.samplers import jump, mcmc
     from oracle import samplers as osamp
     n, d = p.x0.shape[0], p.d
-    f, of = flow_pair(d, spline=spline)
+    f, of = flow_pair(d, spline=spline) if flows is None else flows
+    what = 'jump_%s %s%s' % (inner_kind, p.name, ' tail' if fuse_tail else '')
+    tr = osamp.jump_sample(p.x0.double(), p.target, of, 'langevin' if inner_kind == 'mala' else 'hmc', T, Kin, h,
+                           inv_mass_diag=None if imd is None else imd.double(), n_leapfrog=L,
+                           noise=osamp.PhiloxNoise(seed, dtype=torch.float64))
+    oracle_inputs_ok(tr.flow_steps, what, margin=margin, floor=floor, skip_below_minus_50=skip_below_minus_50)
+    if _ORACLE_ONLY[0]:
+        return
+    rec = FlowRecord(monkeypatch)
     split, flow_mh = [], []
     orig, orig_fm = jump.split_flow_mh, jump.launch_flow_mh
     monkeypatch.setattr(jump, 'split_flow_mh', lambda *a, **k: split.append(1) or orig(*a, **k))
     monkeypatch.setattr(jump, 'launch_flow_mh', lambda *a, **k: flow_mh.append(1) or orig_fm(*a, **k))
     spy = Spy(monkeypatch)
-    inner = None if imd is None else mcmc.LangevinKernel(event_size=d, step_size=h, inv_mass_diag=imd)
-    s = jump.JumpMALA((d,), p.pot, NFMCKernel((d,), flow=f), jump.JumpNFMCParameters(n_iterations=T), inner,
-                      mcmc.LangevinParameters(n_iterations=Kin))
+    if inner_kind == 'mala':
+        inner = None if imd is None else mcmc.LangevinKernel(event_size=d, step_size=h, inv_mass_diag=imd)
+        s = jump.JumpMALA((d,), p.pot, NFMCKernel((d,), flow=f), jump.JumpNFMCParameters(n_iterations=T), inner,
+                          mcmc.LangevinParameters(n_iterations=Kin))
+    else:
+        kw = {} if imd is None else {'inv_mass_diag': imd}
+        s = jump.JumpHMC((d,), p.pot, NFMCKernel((d,), flow=f), jump.JumpNFMCParameters(n_iterations=T),
+                         mcmc.HMCKernel(event_size=d, n_leapfrog_steps=L, step_size=h, **kw), mcmc.HMCParameters(n_iterations=Kin))
     if imd is None:
         s.inner_sampler.kernel.step_size = h
     s.seed, s.fuse_jump_tail = seed, fuse_tail
     out = s.sample(p.x0, show_progress=False)
+    got, want = out.samples.reshape(T * (Kin + 1), n, d), tr.stacked().float()
+    if refused:                                               # no flow-MH kernel for the shape: every jump composed
+        assert flow_mh_refuses(torch.device('cuda', torch.cuda.current_device()), p, f), what   # NFMC_EUNSUPPORTED
+        assert not spy.calls and len(split) == T and (rec.tails, rec.launches) == (0, 0), (len(split), rec.tails, rec.launches)
+        same = (got - want).abs().amax(dim=(0, 2)) < atol + rtol * want.abs().amax(dim=(0, 2))
+        assert same.float().mean() > share, float(same.float().mean())
+        assert out.statistics.n_attempted_jumps == n * T
+        assert abs(out.statistics.n_accepted_jumps - tr.n_accepted_jumps) <= jump_slack
+        return
     assert not spy.calls and not split                        # inner loop and jump fused
     if not fuse_tail or spline:
         assert len(flow_mh) == T                              # each jump on the flow-MH kernel (the tail is affine only)
-    tr = osamp.jump_sample(p.x0.double(), p.target, of, 'langevin', T, Kin, h,
-                           inv_mass_diag=None if imd is None else imd.double(),
-                           noise=osamp.PhiloxNoise(seed, dtype=torch.float64))
-    got, want = out.samples.reshape(T * (Kin + 1), n, d), tr.stacked().float()
+    if tail_expected is None:
+        tail_expected = fuse_tail and not spline and p.pot.jump_tail_ok()
+    assert (rec.tails, rec.launches) == ((T, 0) if tail_expected else (0, T)), (rec.tails, rec.launches)
+    got_m, got_lr = rec.stacked()
+    c = spline_c(d, of, tr.flow_steps)[0] if spline else affine_c(d)
+    compare_flow_mh(got_m, got_lr, tr.flow_steps, what, c=c, margin=margin, skip_below_minus_50=skip_below_minus_50,
+                    comparable=jump_comparable(got, want, Kin, atol, rtol), min_share=share)
     same = (got - want).abs().amax(dim=(0, 2)) < atol + rtol * want.abs().amax(dim=(0, 2))
     assert same.float().mean() > share, float(same.float().mean())
     assert out.statistics.n_attempted_jumps == n * T
+    assert out.statistics.n_accepted_jumps == int(got_m.sum())
     assert abs(out.statistics.n_accepted_jumps - tr.n_accepted_jumps) <= jump_slack
 
 
-def imh_matches_oracle(monkeypatch, p, *, T, seed, flow_seed, spline, what, compare):
-    """FixedIMH on the register flow-MH kernel (affine, or the 'c-rqnsf' spline instantiation) against imh_sample"""
+def jump_mala_matches_oracle(monkeypatch, p, **kw):
+    """jump_matches_oracle with inner MALA"""
+    jump_matches_oracle(monkeypatch, p, 'mala', **kw)
+
+
+def jump_hmc_matches_oracle(monkeypatch, p, **kw):
+    """jump_matches_oracle with inner HMC: oracle.samplers.jump_sample(..., 'hmc', ...)"""
+    jump_matches_oracle(monkeypatch, p, 'hmc', **kw)
+
+
+def flow_mh_refuses(dev, p, f):
+    """nfmc_flow_mh_supported_f32's answer for FixedIMH on flow f from p's starts is NFMC_EUNSUPPORTED"""
+    from nfmc_amd import hip
+    from nfmc_amd.samplers import imh
+    from nfmc_amd.samplers.common import Run
+    from nfmc_amd.samplers.jump import _flow_mh_probe_args
+    s = imh.FixedIMH((p.d,), p.pot, imh.IMHKernel((p.d,), flow=f), imh.IMHParameters(n_iterations=1))
+    run = Run(s, p.x0)
+    logq = torch.empty(p.x0.shape[0], device=dev)
+    pa, _keep = _flow_mh_probe_args(run, f, p.pot, logq, True)
+    return _rc(hip.lib().nfmc_flow_mh_supported_f32, C.byref(pa)) == hip.EUNSUPPORTED
+
+
+def flow_mh_matches_oracle(monkeypatch, p, flows, *, T, seed, spline, what, compare, margin, skip_below_minus_50, floor=None,
+                           cfg=None, refused=False, dev=None):
+    """FixedIMH from p.x0 on the register flow-MH kernel (flow_mh_b_kernel; affine, or the 'c-rqnsf' spline
+    instantiation) against imh_sample on the same Philox streams; flows = (package flow, fp64 oracle flow).  Every launch
+    is handed a mask and a log-ratio buffer (FlowRecord): the rows by compare_flow_mh (floor: the least share of
+    proposals the oracle alone must accept), then the kept states by `compare` as before, then the counters: attempted
+    n T, accepted the sum of the kernel's own masks.  cfg = (cpl, lpc): NFMC_FLOWB_CFG for the run, the sibling layout
+    of the same capacity that a run of more than 4096 chains takes.
+    refused (needs dev): the shape is one the kernel's LDS bound refuses: the probe answers NFMC_EUNSUPPORTED, every
+    transition takes the composed path (split_flow_mh) and the kept states still follow the oracle."""
     from oracle import samplers as osamp
     n, d = p.x0.shape[0], p.d
-    f, of = flow_pair(d, flow_seed, spline=spline)
-    out = imh_run(monkeypatch, p.pot, d, f, p.x0, T, seed)
+    f, of = flows
     tr = osamp.imh_sample(p.x0.double(), p.target, of, T, noise=osamp.PhiloxNoise(seed, dtype=torch.float64))
+    oracle_inputs_ok(tr.flow_steps, what, margin=margin, floor=floor, skip_below_minus_50=skip_below_minus_50)
+    if _ORACLE_ONLY[0]:
+        return
+    if cfg is not None:
+        monkeypatch.setenv('NFMC_FLOWB_CFG', '%d,%d' % tuple(cfg))
+    if refused:
+        assert flow_mh_refuses(dev, p, f), what
+        out = imh_run(monkeypatch, p.pot, d, f, p.x0, T, seed, composed=True)
+        compare(out.samples.reshape(T, n, d), tr, what)
+        return
+    rec = FlowRecord(monkeypatch)
+    out = imh_run(monkeypatch, p.pot, d, f, p.x0, T, seed)
+    got_m, got_lr = rec.stacked()
+    c = spline_c(d, of, tr.flow_steps)[0] if spline else affine_c(d)
+    compare_flow_mh(got_m, got_lr, tr.flow_steps, what, c=c, margin=margin, skip_below_minus_50=skip_below_minus_50)
     compare(out.samples.reshape(T, n, d), tr, what)
+    assert out.statistics.n_accepted_trajectories == int(got_m.sum()), what
+
+
+def imh_matches_oracle(monkeypatch, p, *, T, seed, flow_seed, spline, what, compare, margin, skip_below_minus_50, flows=None,
+                       floor=None):
+    """flow_mh_matches_oracle on flow_pair's perturbed flow about the origin (flows None) or on the pair given"""
+    flows = flow_pair(p.d, flow_seed, spline=spline) if flows is None else flows
+    flow_mh_matches_oracle(monkeypatch, p, flows, T=T, seed=seed, spline=spline, what=what, compare=compare, margin=margin,
+                           skip_below_minus_50=skip_below_minus_50, floor=floor)
+
+
+def _direct_flow_mh(dev, p, f, T, seed, adjusted):
+    """T transitions of one nfmc_flow_mh_steps_f32 launch from p.x0: (kept states (T, n, d), masks, log ratios), CPU"""
+    from nfmc_amd.samplers import imh, jump
+    from nfmc_amd.samplers.common import Run
+    n, d = p.x0.shape[0], p.d
+    s = imh.FixedIMH((d,), p.pot, imh.IMHKernel((d,), flow=f), imh.IMHParameters(n_iterations=T))
+    s.seed = seed
+    run = Run(s, p.x0)
+    logq = torch.empty(n, dtype=torch.float32, device=dev)
+    masks = torch.zeros(T, n, dtype=torch.uint8, device=dev)
+    lr = torch.zeros(T, n, dtype=torch.float32, device=dev)
+    samples = torch.zeros(T, n, d, dtype=torch.float32, device=dev)
+    assert jump.flow_mh_supported(run, f, p.pot, logq, adjusted)
+    jump.launch_flow_mh(run, f, p.pot, logq, T, 0, False, adjusted, run.stats.struct(), samples, masks, lr)
+    torch.cuda.synchronize()
+    return samples.cpu(), masks.cpu().bool(), lr.cpu()
+
+
+def flow_mh_unadjusted_matches_oracle(dev, monkeypatch, p, flows, *, T, seed, spline, what, atol, rtol, cfg=None):
+    """launch_flow_mh(..., adjusted=False): every proposal is kept, so x <- x', U(x) <- U(x') and log q(x) <- log q(x')
+    run at every transition of every chain.  The kept states are the fp64 flow's samples at the same Philox latents (to
+    atol + rtol |x'|), and the log ratio the kernel still writes at transition s + 1, which uses the U and log q carried
+    from transition s, follows the oracle's on every row (flow_mh_tolerance)."""
+    from oracle import samplers as osamp
+    f, of = flows
+    tr = osamp.imh_sample(p.x0.double(), p.target, of, T, noise=osamp.PhiloxNoise(seed, dtype=torch.float64), adjusted=False)
+    lr = torch.stack([js.log_alpha for js in tr.flow_steps])
+    print('%s: unadjusted, log ratios %.1f .. %.1f' % (what, float(lr.min()), float(lr.max())))
+    assert bool(torch.isfinite(lr).all()), what
+    if _ORACLE_ONLY[0]:
+        return
+    if cfg is not None:
+        monkeypatch.setenv('NFMC_FLOWB_CFG', '%d,%d' % tuple(cfg))
+    got, got_m, got_lr = _direct_flow_mh(dev, p, f, T, seed, False)
+    c = spline_c(p.d, of, tr.flow_steps)[0] if spline else affine_c(p.d)
+    compare_flow_mh(got_m, got_lr, tr.flow_steps, what, c=c, margin=0.0, adjusted=False)
+    want = torch.stack([js.x_prime for js in tr.flow_steps]).float()
+    np.testing.assert_allclose(got.numpy(), want.numpy(), atol=atol, rtol=rtol, err_msg=what)
+
+
+def flowb_override_equals_production(dev, monkeypatch, p, f, *, lpc, T, seed):
+    """More than 4096 chains take the CPL = 8 sibling by themselves; the same run under NFMC_FLOWB_CFG = '8,<lpc>' must
+    be that kernel again: states, masks and log ratios bit for bit.  That the override is read and does switch the
+    instantiation is observed through the library, which has no entry point that names the layout: under
+    '4,<2 lpc>' the log ratios (fp32 sums over another lane tree) differ from production's in some bit while agreeing
+    to 1e-3 + 1e-5 |log r|, and under '8,64' a width-8 flow of two coupling layers (132 KB of LDS at capacity 512) is
+    refused by nfmc_flow_mh_supported_f32 where it is taken without.  (No oracle: the 96-chain cases compare the
+    CPL = 8 kernels with it through the override.)"""
+    assert p.x0.shape[0] > 4096 and flow_layout(p.d, p.x0.shape[0]) == (8, lpc), (p.d, lpc)
+    assert f.bijection.n_hidden > 4
+    monkeypatch.delenv('NFMC_FLOWB_CFG', raising=False)
+    assert not flow_mh_refuses(dev, p, f)
+    a = _direct_flow_mh(dev, p, f, T, seed, True)
+    monkeypatch.setenv('NFMC_FLOWB_CFG', '8,%d' % lpc)
+    b = _direct_flow_mh(dev, p, f, T, seed, True)
+    for u, v, name in zip(a, b, ('states', 'masks', 'log ratios')):
+        assert torch.equal(u, v), name
+    assert bool(torch.isfinite(a[0]).all())
+    monkeypatch.setenv('NFMC_FLOWB_CFG', '4,%d' % (2 * lpc))
+    c = _direct_flow_mh(dev, p, f, T, seed, True)
+    fin = torch.isfinite(a[2]) & torch.isfinite(c[2])
+    assert not torch.equal(a[2], c[2]), 'the CPL = 4 sibling gave the same bits: is the override read?'
+    assert bool(((a[2] - c[2]).abs()[fin] <= 1e-3 + 1e-5 * a[2].abs()[fin]).all())
+    monkeypatch.setenv('NFMC_FLOWB_CFG', '8,64')
+    assert flow_mh_refuses(dev, p, f)
+
+
+# ---- the flow-MH matrix of the per-target files
+FLOW_DIMS = {4: 3, 8: 7, 16: 13, 32: 25, 64: 50, 128: 100, 256: 200, 512: 300}     # capacity CPL LPC -> a ragged d in it
+FlowCase = collections.namedtuple('FlowCase', 'family cap d n_hidden cfg spline n_layers')
+
+
+def flow_case_id(c):
+    return '%s-cap%d-d%d-h%d%s%s%s' % (c.family, c.cap, c.d, c.n_hidden, '' if c.cfg is None else '-cpl%d' % c.cfg[0],
+                                       '-spline' if c.spline else '', '' if c.n_layers is None else '-%dlayer' % c.n_layers)
+
+
+def flow_cases(dims=None, *, jump_tail=True):
+    """The cases every per-target file runs (n = 96 chains, T = 4), dims: capacity -> d (FLOW_DIMS where a kind takes any d).
+    flow-MH, affine: one ragged d in each capacity; at 64, 128 and 256 both siblings (CPL = 4 by default, CPL = 8
+      through NFMC_FLOWB_CFG) at both conditioner widths (n_hidden 4 -> HP = 4, 8 -> HP = 8), both widths at 512 (width 8 also with a
+      single coupling layer: two are refused by the 120 KB LDS bound, so that one launches (8, 64) at HP = 8), the width
+      rotating below 64.
+    flow-MH, spline: two coupling layers at the six layouts up to capacity 64 at either width, and capacity 128 with a
+      single coupling layer (width 4).
+    unadjusted: capacities 256 and 512.
+    jump tail (unless a kind is never offered it): jump_mala at capacities 128, 256, 512 and both tail widths (at 512 width 8 also with a single coupling layer);
+      jump_hmc
+      (L = 3) at one d per capacity from 8 to 512, the width rotating."""
+    dims = FLOW_DIMS if dims is None else dims
+    rot = {4: 3, 8: 6, 16: 4, 32: 8, 64: 4, 128: 8, 256: 4, 512: 4}
+    out = [FlowCase('mh', cap, dims[cap], rot[cap], None, False, None) for cap in (4, 8, 16, 32)]
+    for cap, lpc in ((64, 8), (128, 16), (256, 32)):
+        out += [FlowCase('mh', cap, dims[cap], nh, cfg, False, None) for nh in (4, 8) for cfg in (None, (8, lpc))]
+    out += [FlowCase('mh', 512, dims[512], nh, None, False, None) for nh in (4, 8)]
+    out.append(FlowCase('mh', 512, dims[512], 8, None, False, 1))       # two width-8 layers are refused there (132 KB of LDS)
+    for nh in (4, 8):
+        out += [FlowCase('mh', cap, dims[cap], nh, None, True, None) for cap in (4, 8, 16, 32, 64)]
+        out.append(FlowCase('mh', 64, dims[64], nh, (8, 8), True, None))
+    out.append(FlowCase('mh', 128, dims[128], 4, None, True, 1))
+    out += [FlowCase('unadjusted', 256, dims[256], 8, None, False, None), FlowCase('unadjusted', 512, dims[512], 4, None, False, None)]
+    if jump_tail:
+        out += [FlowCase('jump_mala', cap, dims[cap], nh, None, False, None) for cap in (128, 256, 512) for nh in (4, 8)]
+        out.append(FlowCase('jump_mala', 512, dims[512], 8, None, False, 1))       # the (8, 64) tail at width 8
+        out += [FlowCase('jump_hmc', cap, dims[cap], rot[cap], None, False, None) for cap in (8, 16, 32, 64, 128, 256, 512)]
+    return out
+
+
+def flow_case_scale(c):
+    """the perturbation of a case's centred flow, affine or spline: 0.1 below d = 200 and 0.05 from there (at a fixed
+    scale the acceptance falls with d).  The fp64 oracle alone then accepts 0.19 to 0.73 of the proposals of the
+    full-rank and GMRF files' cases, splines included; with 0.2 it accepts 0.03 of the spline proposals at d = 50."""
+    return 0.1 if c.d < 200 else 0.05
+
+
+def run_flow_case(dev, monkeypatch, p, c, *, margin, compare, atol, rtol, h_mala, h_hmc, imd=None, refused=False, seed=2718,
+                  tail_expected=None, skip_caps=(), centre=None):
+    """One FlowCase on the problem p (the file's own, d = c.d): centred flow and starts (96 chains), T = 4 (unadjusted
+    3; the jumps T = 2 outer iterations of 2 inner transitions).  The fp64 oracle alone must accept at least 5 % of the
+    proposals at capacities up to 128, and everywhere hold the tie cap and keep every log ratio finite and above -50,
+    but at the capacities of skip_caps, where the file's problem has hopeless proposals and skip_below_minus_50 is set.
+    refused: the case is one the 120 KB LDS bound refuses (flow_mh_matches_oracle; the jumps then take the composed
+    path too).  centre: (c, s) of local_fit where laplace_fit has no use.  imd: the inner kernels' mass diagonal, or a function of the inner kind ('mala' / 'hmc') that gives it."""
+    assert p.d == c.d, (p.d, c)
+    what = '%s %s' % (p.name, flow_case_id(c))
+    flows = centred_flow_pair(p, 5, c.n_hidden, c.spline, c.n_layers, scale=flow_case_scale(c), centre=centre)
+    q = centred(p, 96, 40 + c.cap, centre)
+    floor = 0.05 if c.cap <= 128 else None
+    assert c.cfg is None or flow_layout(c.d, 96, c.cfg) == tuple(c.cfg), c
+    if c.family == 'mh':
+        flow_mh_matches_oracle(monkeypatch, q, flows, T=4, seed=seed + c.d, spline=c.spline, what=what, compare=compare,
+                               margin=margin, skip_below_minus_50=c.cap in skip_caps, floor=floor, cfg=c.cfg, refused=refused, dev=dev)
+    elif c.family == 'unadjusted':
+        flow_mh_unadjusted_matches_oracle(dev, monkeypatch, q, flows, T=3, seed=seed + c.d, spline=c.spline, what=what,
+                                          atol=atol, rtol=rtol, cfg=c.cfg)
+    else:
+        jump_matches_oracle(monkeypatch, q, c.family[5:], T=2, Kin=2, seed=seed + c.d, h=h_mala if c.family == 'jump_mala' else h_hmc,
+                            imd=imd(c.family[5:]) if callable(imd) else imd, fuse_tail=True, spline=False, atol=atol, rtol=rtol,
+                            share=0.95, jump_slack=2, margin=margin,
+                            skip_below_minus_50=c.cap in skip_caps, L=3, flows=flows, floor=floor, tail_expected=tail_expected, refused=refused)
 
 
 def fused_equals_split(monkeypatch, p, make, T, *, seed, atol, rtol, share):

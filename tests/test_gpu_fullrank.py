@@ -14,6 +14,13 @@ Tolerances are the logistic-regression tests' (tests/test_gpu_logreg.py):
 d in {1, 3, 8, 25, 64, 130, 256, 512} covers every (CPL, LPC) layout choose_cfg picks (LPC 1 ... 64, CPL 4 / 8 / 16 at
 d = 512 in the jump-tail-free kernels: (8, 64)) and tiles of 1024 rows (d <= 4) down to 8 rows (d = 512), so that
 Lambda streams through up to 64 tiles per evaluation.
+
+Flow-proposal cases (section 2 and 2b).  On a flow about the origin the fp64 oracle alone accepted 4 of 1536 IMH
+proposals at d = 25 and none at d = 64 and 256, so from d = 25 they run on a flow centred by a Laplace fit
+(H.flow_inputs).  With the present inputs the oracle alone accepts 865, 406, 285 and 436 of 1536 IMH proposals at d = 2,
+25, 64 and 256 (0.186 to 0.563) and 0.064 to 0.361 of the jumps of section 2, and in the matrix 0.156 to 0.729 up to
+capacity 128 and 0.229 to 0.401 above; at most 1.2 % of the chains of a case are within MARGIN of a tie, and every log
+ratio is above -31.
 """
 import functools
 import math
@@ -109,22 +116,51 @@ def test_mcmc_native_stream_matches_oracle(dev, monkeypatch, kind, d):
                     what='native %s d=%d' % (kind, d))
 
 
+@functools.lru_cache(maxsize=None)
+def _mild(d, seed, n, x0_seed):
+    """a mildly correlated target (cond 4), one object per distinct problem (the Laplace fit is kept per object)"""
+    return _record(d, seed, n, x0_seed, cond=4.0)
+
+
 @pytest.mark.parametrize('fuse_tail', [False, True])
 @pytest.mark.parametrize('d', [5, 25, 64])
 def test_jump_mala_native_stream_matches_oracle(dev, monkeypatch, fuse_tail, d):
-    """A mildly correlated target (cond 4): the jump proposals of a perturbed identity-like flow must be accepted often
-    enough for the comparison to cover the flow-MH step."""
+    """A mildly correlated target (cond 4).  At d = 5 the jump proposals of a perturbed identity-like flow are accepted
+    often enough (97 of 576 in the fp64 oracle alone); from d = 25 the flow is centred on the target (H.flow_inputs)."""
     n, T = 192, 3
-    p = _record(d, 3 * d + 5, n, 3, cond=4.0)
-    H.jump_mala_matches_oracle(monkeypatch, p, T=T, Kin=4, seed=31337, h=0.3 * d ** (-1 / 3) / _lmax(p.ref), imd=None,
+    p = _mild(d, 3 * d + 5, n, 3)
+    q, flows = H.flow_inputs(p, d, n)
+    H.jump_mala_matches_oracle(monkeypatch, q, T=T, Kin=4, seed=31337, h=0.3 * d ** (-1 / 3) / _lmax(p.ref), imd=None,
                                fuse_tail=fuse_tail, spline=False, atol=ATOL, rtol=RTOL, share=0.95,
-                               jump_slack=max(2, int(0.03 * n * T)))
+                               jump_slack=max(2, int(0.03 * n * T)), margin=MARGIN, skip_below_minus_50=False, flows=flows)
 
 
 @pytest.mark.parametrize('d', [2, 25, 64, 256])
 def test_imh_runs_on_the_sequential_flow_mh_kernel(dev, monkeypatch, d):
-    H.imh_matches_oracle(monkeypatch, _record(d, 5 * d + 7, 256, 9, cond=4.0), T=6, seed=4711 + d, flow_seed=9, spline=False,
-                         compare=_compare, what='imh d=%d' % d)
+    p = _mild(d, 5 * d + 7, 256, 9)
+    q, flows = H.flow_inputs(p, d, 256, 9)
+    H.imh_matches_oracle(monkeypatch, q, T=6, seed=4711 + d, flow_seed=9, spline=False, compare=_compare, what='imh d=%d' % d,
+                         margin=MARGIN, skip_below_minus_50=False, flows=flows)
+
+
+# ------------------------------------------------------------------------- 2b. the flow-MH matrix
+FLOW_CASES = H.flow_cases()
+FLOW_TESTS = ('test_jump_mala_native_stream_matches_oracle', 'test_imh_runs_on_the_sequential_flow_mh_kernel',
+              'test_flow_mh_matrix')
+# the 120 KB LDS bound with this kind's 16 KB tile of Lambda behind the image: two affine coupling layers of width 8 at
+# the ragged capacity 512 are 132 KB by themselves, two spline layers of width 8 at capacity 64 are 111 KB
+FLOW_REFUSED = {'mh-cap512-d300-h8', 'jump_mala-cap512-d300-h8', 'mh-cap64-d50-h8-spline', 'mh-cap64-d50-h8-cpl8-spline'}
+
+
+@pytest.mark.parametrize('case', FLOW_CASES, ids=H.flow_case_id)
+def test_flow_mh_matrix(dev, monkeypatch, case):
+    """H.flow_cases: every flow-MH layout, sibling, width and coupling, the unadjusted carry path and the jump tails, with
+    decisions and log ratios compared row by row (H.compare_flow_mh); the mildly correlated target (cond 4)"""
+    d = case.d
+    p = _mild(d, 5 * d + 7, 96, 9)
+    H.run_flow_case(dev, monkeypatch, p, case, margin=MARGIN, compare=_compare, atol=ATOL, rtol=RTOL,
+                    h_mala=0.3 * d ** (-1 / 3) / _lmax(p.ref), h_hmc=0.5 * d ** (-1 / 4) / math.sqrt(_lmax(p.ref)),
+                    refused=H.flow_case_id(case) in FLOW_REFUSED)
 
 
 # ------------------------------------------------------------------------- 3. fused equals split

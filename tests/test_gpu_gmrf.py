@@ -21,6 +21,13 @@ run within 2e-3 of a tie, accepts 0.62 to 1.0 of the proposals and keeps every l
 probed with the same rule: at most 3.1 % near-ties, acceptance 0.91 to 1.0.
 
 The grid covers every default (CPL, LPC) layout: (16, 64) by the 32 x 32 lattice (tests/test_host_gmrf.py).
+
+Flow-proposal cases (section 3 and 3b).  On a flow about the origin the fp64 oracle alone accepted none of 1536 IMH
+proposals at d = 25, 64 and 256, so from d = 25 they run on a flow centred by a Laplace fit (H.flow_inputs).  With the
+present inputs the oracle alone accepts 163, 422, 345 and 372 of 1536 IMH proposals at d = 2, 25, 64 and 256 (0.106 to
+0.275) and 0.076 to 0.142 of the jumps of section 3, and in the matrix 0.214 to 0.701 up to capacity 128 and 0.135 to
+0.333 above; at most 1.0 % of the chains of a case are within MARGIN of a tie.  With tau unknown some proposals are
+hopeless (fp64 log ratios down to -1870): those cases set skip_below_minus_50; the others keep every log ratio above -50.
 """
 import functools
 import math
@@ -169,16 +176,58 @@ def test_mcmc_native_stream_matches_oracle(dev, monkeypatch, kind, d, lik, mode)
 def test_jump_mala_native_stream_matches_oracle(dev, monkeypatch, fuse_tail, d):
     n, T = 192, 3
     p = _Problem(d, 'binomial', 'fixed' if d == 25 else 'scaled', 3 * d + 5, n, 3)
-    H.jump_mala_matches_oracle(monkeypatch, p, T=T, Kin=4, seed=31337, h=0.3 * d ** (-1 / 3) / p.lam, imd=None,
+    q, flows = H.flow_inputs(p, d, n)
+    H.jump_mala_matches_oracle(monkeypatch, q, T=T, Kin=4, seed=31337, h=0.3 * d ** (-1 / 3) / p.lam, imd=None,
                                fuse_tail=fuse_tail, spline=False, atol=ATOL, rtol=RTOL, share=0.95,
-                               jump_slack=max(2, int(0.03 * n * T)))
+                               jump_slack=max(2, int(0.03 * n * T)), margin=MARGIN, skip_below_minus_50=d != 25, flows=flows)   # unknown tau: FLOW_SKIP_CAPS
 
 
 @pytest.mark.parametrize('d', [2, 25, 64, 256])
 def test_imh_runs_on_the_sequential_flow_mh_kernel(dev, monkeypatch, d):
     mode = {2: 'scaled', 25: 'fixed', 64: 'centered', 256: 'scaled'}[d]
-    H.imh_matches_oracle(monkeypatch, _Problem(d, 'binomial', mode, 5 * d + 7, 256, 9), T=6, seed=4711 + d, flow_seed=9,
-                         spline=False, compare=_compare, what='imh %s d=%d' % (mode, d))
+    p = _Problem(d, 'binomial', mode, 5 * d + 7, 256, 9)
+    q, flows = H.flow_inputs(p, d, 256, 9)
+    H.imh_matches_oracle(monkeypatch, q, T=6, seed=4711 + d, flow_seed=9, spline=False, compare=_compare,
+                         what='imh %s d=%d' % (mode, d), margin=MARGIN, skip_below_minus_50=mode != 'fixed', flows=flows)
+
+
+# ------------------------------------------------------------------------- 3b. the flow-MH matrix
+FLOW_CASES = H.flow_cases()
+FLOW_TESTS = ('test_jump_mala_native_stream_matches_oracle', 'test_imh_runs_on_the_sequential_flow_mh_kernel',
+              'test_flow_mh_matrix')
+# the 120 KB LDS bound: two affine coupling layers of width 8 at the ragged capacity 512 are 132 KB by themselves
+FLOW_REFUSED = {'mh-cap512-d300-h8', 'jump_mala-cap512-d300-h8'}
+
+
+# unknown tau at these capacities: a proposal's log precision can be far off, with fp64 log ratios down to -390
+FLOW_SKIP_CAPS = (64, 256, 512)
+
+
+def _flow_problem(c):
+    """(likelihood, mode) rotating with the capacity; never the Poisson / scaled pair (e^f of a proposal overflows).
+    _Problem keeps one object per distinct problem (lru_cache), and H.laplace_fit one fit per object."""
+    lik, mode = [('binomial', 'scaled'), ('student_t', 'fixed'), ('poisson', 'centered'), ('binomial', 'centered'),
+                 ('student_t', 'scaled'), ('poisson', 'fixed')][int(math.log2(c.cap)) % 6]
+    return _Problem(c.d, lik, mode, 5 * c.d + 7, 96, 9)
+
+
+@pytest.mark.parametrize('case', FLOW_CASES, ids=H.flow_case_id)
+def test_flow_mh_matrix(dev, monkeypatch, case):
+    """H.flow_cases: every flow-MH layout, sibling, width and coupling, the unadjusted carry path and the jump tails, with
+    decisions and log ratios compared row by row (H.compare_flow_mh)"""
+    p = _flow_problem(case)
+    H.run_flow_case(dev, monkeypatch, p, case, margin=MARGIN, compare=_compare, atol=ATOL, rtol=RTOL,
+                    h_mala=0.3 * case.d ** (-1 / 3) / p.lam, h_hmc=0.5 * _hmc_factor(p) * case.d ** (-1 / 4) / math.sqrt(p.lam),
+                    refused=H.flow_case_id(case) in FLOW_REFUSED, skip_caps=FLOW_SKIP_CAPS)
+
+
+@pytest.mark.parametrize('cap', [64, 128, 256])
+def test_flowb_override_launches_what_more_than_4096_chains_get(dev, monkeypatch, cap):
+    """a staged kind (its ELL block sits behind the flow image)"""
+    d = H.FLOW_DIMS[cap]
+    p = _Problem(d, 'binomial', 'centered', 5 * d + 7, 96, 9)
+    f, _of = H.centred_flow_pair(p, 5, 8, scale=0.2 if d < 200 else 0.05)
+    H.flowb_override_equals_production(dev, monkeypatch, H.centred(p, 4160, 6), f, lpc=cap // 8, T=3, seed=99)
 
 
 # ------------------------------------------------------------------------- 4. fused equals split

@@ -17,6 +17,13 @@ Tolerances are the sparse-logistic-regression tests' (tests/test_gpu_sparse_logr
 51 -> (8, 8), 101 -> (8, 16), 255 -> (8, 32), 401 -> (8, 64), 1023 -> (16, 64); (5, 3) has a register quad that holds a
 student, the questions and mu; (23, 1) and (1, 23) are the one-question and the one-student edge.  The responses are read
 by plain global loads (no tile), so there is no tile edge to cover.
+
+Flow-proposal cases (sections 3, 4 and 4b): from d = 25 on a flow centred by a Laplace fit (H.flow_inputs).  The fp64
+oracle alone accepts 0.024 to 0.222 of the jumps and 0.001 to 0.308 of the IMH proposals of sections 3 and 4 (the low ends
+are the shapes under d = 25, on a flow about the origin), and in the matrix 0.073 to 0.828 up to capacity 128 and 0.026 to
+0.359 above; at most 3.1 % of the chains of a case are within MARGIN of a tie.  The cases under d = 25 and from d = 50
+(the matrix from capacity 128) have fp64 log ratios down to -190 and set skip_below_minus_50; the others keep every log
+ratio above -50.
 """
 import functools
 import math
@@ -160,9 +167,10 @@ def test_mcmc_native_stream_matches_oracle(dev, monkeypatch, kind, S, Q):
 def test_jump_mala_native_stream_matches_oracle(dev, monkeypatch, fuse_tail, S, Q):
     n, T = 192, 3
     p = _problem(S, Q, n)
-    H.jump_mala_matches_oracle(monkeypatch, p, T=T, Kin=4, seed=31337, h=p.step('mala'), imd=p.imd('mala').float(),
+    q, flows = H.flow_inputs(p, p.d, n)
+    H.jump_mala_matches_oracle(monkeypatch, q, T=T, Kin=4, seed=31337, h=p.step('mala'), imd=p.imd('mala').float(),
                                fuse_tail=fuse_tail, spline=False, atol=ATOL, rtol=RTOL, share=0.95,
-                               jump_slack=max(2, int(0.03 * n * T)))
+                               jump_slack=max(2, int(0.03 * n * T)), margin=MARGIN, skip_below_minus_50=not 25 <= p.d < 50, flows=flows)
 
 
 # ------------------------------------------------------------------------- 4. imh on the sequential flow-MH kernel
@@ -170,8 +178,29 @@ def test_jump_mala_native_stream_matches_oracle(dev, monkeypatch, fuse_tail, S, 
 def test_imh_runs_on_the_sequential_flow_mh_kernel(dev, monkeypatch, S, Q, spline):
     """Affine and spline ('c-rqnsf') instantiations of the register flow-MH kernel for kind 9."""
     p = _problem(S, Q, 192)
-    H.imh_matches_oracle(monkeypatch, p, T=5, seed=4711 + p.d, flow_seed=3 if spline else 9, spline=spline, compare=_compare,
-                         what='%s imh S=%d Q=%d' % ('c-rqnsf' if spline else 'realnvp', S, Q))
+    q, flows = H.flow_inputs(p, p.d, 192, 3 if spline else 9, spline=spline)
+    H.imh_matches_oracle(monkeypatch, q, T=5, seed=4711 + p.d, flow_seed=3 if spline else 9, spline=spline, compare=_compare,
+                         what='%s imh S=%d Q=%d' % ('c-rqnsf' if spline else 'realnvp', S, Q), margin=MARGIN,
+                         skip_below_minus_50=not 25 <= p.d < 50, flows=flows)
+
+
+# ------------------------------------------------------------------------- 4b. the flow-MH matrix
+FLOW_SQ = {4: (1, 1), 8: (3, 3), 16: (8, 4), 32: (16, 8), 64: (30, 19), 128: (60, 39), 256: (150, 49), 512: (200, 99)}   # d = S + Q + 1
+FLOW_CASES = H.flow_cases({cap: S + Q + 1 for cap, (S, Q) in FLOW_SQ.items()})
+FLOW_TESTS = ('test_jump_mala_native_stream_matches_oracle', 'test_imh_runs_on_the_sequential_flow_mh_kernel',
+              'test_flow_mh_matrix')
+# the 120 KB LDS bound: two affine coupling layers of width 8 at the ragged capacity 512 are 132 KB by themselves
+FLOW_REFUSED = {'mh-cap512-d300-h8', 'jump_mala-cap512-d300-h8'}
+
+
+@pytest.mark.parametrize('case', FLOW_CASES, ids=H.flow_case_id)
+def test_flow_mh_matrix(dev, monkeypatch, case):
+    """H.flow_cases: every flow-MH layout, sibling, width and coupling, the unadjusted carry path and the jump tails, with
+    decisions and log ratios compared row by row (H.compare_flow_mh); the inner kernels with the problem's mass diagonals"""
+    p = _problem(*FLOW_SQ[case.cap], 96)
+    H.run_flow_case(dev, monkeypatch, p, case, margin=MARGIN, compare=_compare, atol=ATOL, rtol=RTOL, h_mala=p.step('mala'),
+                    h_hmc=p.step('hmc'), imd=lambda kind: p.imd(kind).float(), refused=H.flow_case_id(case) in FLOW_REFUSED,
+                    skip_caps=(128, 256, 512))    # from d = 100: fp64 log ratios down to -190
 
 
 # ------------------------------------------------------------------------- 5. fused equals split

@@ -17,6 +17,12 @@ puts at most 2.1 % of the chains of a mala, hmc or mh run within 2e-3 of a tie, 
 
 DIMS covers every default (CPL, LPC) layout below (16, 64) and tiles of 1024 rows (d <= 4) down to 8 rows (d = 512), so
 each matrix streams through up to 64 tiles per pass, and the whitened form makes two passes.
+
+Flow-proposal cases (section 2 and 2b): from d = 25 on a flow centred by a Laplace fit (H.flow_inputs).  The fp64 oracle
+alone accepts 0.092 to 0.236 of the jumps and 0.176 to 0.495 of the IMH proposals of section 2, and in the matrix 0.161 to
+0.826 up to capacity 128 and 0.042 to 0.411 above; at most 2.1 % of the chains of a case are within MARGIN of a tie.  At
+capacities 128 and 256 some proposals are hopeless (fp64 log ratios down to -547): those cases set skip_below_minus_50;
+the others keep every log ratio above -50.
 """
 import functools
 import math
@@ -123,20 +129,54 @@ def test_mcmc_native_stream_matches_oracle(dev, monkeypatch, kind, d):
                     seed=777 + d, what='native %s d=%d' % (kind, d))
 
 
+@functools.lru_cache(maxsize=None)
+def _flow_built(d, lik, par, seed, n, x0_seed):
+    """one object per distinct problem of the flow tests: the Laplace fit (H.laplace_fit) is kept per object"""
+    return _Problem(d, lik, par, seed, n, x0_seed)
+
+
 @pytest.mark.parametrize('fuse_tail', [False, True])
 @pytest.mark.parametrize('d', [5, 25, 64])
 def test_jump_mala_native_stream_matches_oracle(dev, monkeypatch, fuse_tail, d):
     n, T = 192, 3
-    p = _Problem(d, 'binomial', 'whitened', 3 * d + 5, n, 3)
-    H.jump_mala_matches_oracle(monkeypatch, p, T=T, Kin=4, seed=31337, h=0.3 * d ** (-1 / 3) / p.lam, imd=None,
+    p = _flow_built(d, 'binomial', 'whitened', 3 * d + 5, n, 3)
+    q, flows = H.flow_inputs(p, d, n)
+    H.jump_mala_matches_oracle(monkeypatch, q, T=T, Kin=4, seed=31337, h=0.3 * d ** (-1 / 3) / p.lam, imd=None,
                                fuse_tail=fuse_tail, spline=False, atol=ATOL, rtol=RTOL, share=0.95,
-                               jump_slack=max(2, int(0.03 * n * T)))
+                               jump_slack=max(2, int(0.03 * n * T)), margin=MARGIN, skip_below_minus_50=False, flows=flows)
 
 
 @pytest.mark.parametrize('d', [2, 25, 64, 256])
 def test_imh_runs_on_the_sequential_flow_mh_kernel(dev, monkeypatch, d):
-    H.imh_matches_oracle(monkeypatch, _Problem(d, 'binomial', 'whitened', 5 * d + 7, 256, 9), T=6, seed=4711 + d, flow_seed=9,
-                         spline=False, compare=_compare, what='imh d=%d' % d)
+    p = _flow_built(d, 'binomial', 'whitened', 5 * d + 7, 256, 9)
+    q, flows = H.flow_inputs(p, d, 256, 9)
+    H.imh_matches_oracle(monkeypatch, q, T=6, seed=4711 + d, flow_seed=9, spline=False, compare=_compare, what='imh d=%d' % d,
+                         margin=MARGIN, skip_below_minus_50=False, flows=flows)
+
+
+# ------------------------------------------------------------------------- 2b. the flow-MH matrix
+FLOW_CASES = H.flow_cases()
+FLOW_TESTS = ('test_jump_mala_native_stream_matches_oracle', 'test_imh_runs_on_the_sequential_flow_mh_kernel',
+              'test_flow_mh_matrix')
+# the 120 KB LDS bound with this kind's 16 KB tile of the matrix behind the image: two affine coupling layers of width 8
+# at the ragged capacity 512 are 132 KB by themselves, two spline layers of width 8 at capacity 64 are 111 KB
+FLOW_REFUSED = {'mh-cap512-d300-h8', 'jump_mala-cap512-d300-h8', 'mh-cap64-d50-h8-spline', 'mh-cap64-d50-h8-cpl8-spline'}
+# a diagonal proposal against the prior's correlations: Poisson / whitened at d = 100 and binomial / centred at d = 200
+# have fp64 log ratios down to -547 and -158
+FLOW_SKIP_CAPS = (128, 256)
+
+
+@pytest.mark.parametrize('case', FLOW_CASES, ids=H.flow_case_id)
+def test_flow_mh_matrix(dev, monkeypatch, case):
+    """H.flow_cases: every flow-MH layout, sibling, width and coupling, the unadjusted carry path and the jump tails, with
+    decisions and log ratios compared row by row (H.compare_flow_mh); the (likelihood, parameterisation) pair rotates
+    with the capacity"""
+    d = case.d
+    lik, par = PAIRS[int(math.log2(case.cap)) % len(PAIRS)]
+    p = _flow_built(d, lik, par, 5 * d + 7, 96, 9)
+    H.run_flow_case(dev, monkeypatch, p, case, margin=MARGIN, compare=_compare, atol=ATOL, rtol=RTOL,
+                    h_mala=0.3 * d ** (-1 / 3) / p.lam, h_hmc=0.5 * d ** (-1 / 4) / math.sqrt(p.lam),
+                    refused=H.flow_case_id(case) in FLOW_REFUSED, skip_caps=FLOW_SKIP_CAPS)
 
 
 # ------------------------------------------------------------------------- 3. fused equals split

@@ -9,6 +9,12 @@ Tolerances are the mixture tests' (tests/test_gpu_mixture.py):
 
 The (d, N) grid covers every (CPL, LPC) layout the sampler kernels pick (d = 1 ... 700: LPC 1 ... 64, CPL 4 / 8 / 16),
 N = 1, 63, 64, 65 and 1000, and N past the LDS tile of its layout (4096 / (CPL LPC) rows: 1024 at d <= 4, 8 at d = 512).
+
+Flow-proposal cases (section 2 and 2b): from d = 25 on a flow centred by a Laplace fit (H.flow_inputs).  The fp64 oracle
+alone accepts 0.160 to 0.267 of the jumps and 0.191 to 0.436 of the IMH proposals of section 2, and in the matrix 0.104 to
+0.833 up to capacity 128 and 0.115 to 0.422 above; at most 1.0 % of the chains of a case are within MARGIN of a tie.  IMH
+at d = 256 and the matrix at capacity 256 have fp64 log ratios down to -76 and set skip_below_minus_50, as does the jump
+at d = 5; the others keep every log ratio above -50.
 """
 import ctypes as C
 import functools
@@ -98,19 +104,51 @@ def test_mcmc_native_stream_matches_oracle(dev, monkeypatch, kind, d, N):
                     what='native %s' % kind)
 
 
+@functools.lru_cache(maxsize=None)
+def _flow_built(N, d, seed, n, x0_seed):
+    """one object per distinct problem of the flow tests: the Laplace fit (H.laplace_fit) is kept per object"""
+    return _record(N, d, seed, n, x0_seed)
+
+
 @pytest.mark.parametrize('fuse_tail', [False, True])
 @pytest.mark.parametrize('d,N', [(5, 300), (25, 1000)])
 def test_jump_mala_native_stream_matches_oracle(dev, monkeypatch, fuse_tail, d, N):
     n, T = 192, 3
-    H.jump_mala_matches_oracle(monkeypatch, _record(N, d, 3 * d + N, n, 3), T=T, Kin=4, seed=31337, h=0.3 * d ** (-1 / 3),
+    p = _flow_built(N, d, 3 * d + N, n, 3)
+    q, flows = H.flow_inputs(p, d, n)
+    H.jump_mala_matches_oracle(monkeypatch, q, T=T, Kin=4, seed=31337, h=0.3 * d ** (-1 / 3),
                                imd=None, fuse_tail=fuse_tail, spline=False, atol=ATOL, rtol=RTOL, share=0.95,
-                               jump_slack=max(2, int(0.03 * n * T)))
+                               jump_slack=max(2, int(0.03 * n * T)), margin=MARGIN, skip_below_minus_50=d < 25, flows=flows)
 
 
 @pytest.mark.parametrize('d,N', [(2, 64), (25, 1000), (64, 65), (256, 100)])
 def test_imh_runs_on_the_sequential_flow_mh_kernel(dev, monkeypatch, d, N):
-    H.imh_matches_oracle(monkeypatch, _record(N, d, 5 * d + N, 256, 9), T=6, seed=4711 + d, flow_seed=9, spline=False,
-                         compare=_compare, what='imh d=%d N=%d' % (d, N))
+    p = _flow_built(N, d, 5 * d + N, 256, 9)
+    q, flows = H.flow_inputs(p, d, 256, 9)
+    H.imh_matches_oracle(monkeypatch, q, T=6, seed=4711 + d, flow_seed=9, spline=False,
+                         compare=_compare, what='imh d=%d N=%d' % (d, N), margin=MARGIN, skip_below_minus_50=d >= 200, flows=flows)
+
+
+# ------------------------------------------------------------------------- 2b. the flow-MH matrix
+FLOW_CASES = H.flow_cases()
+FLOW_TESTS = ('test_jump_mala_native_stream_matches_oracle', 'test_imh_runs_on_the_sequential_flow_mh_kernel',
+              'test_flow_mh_matrix')
+# the 120 KB LDS bound with this kind's 16 KB tile of X behind the image: two affine coupling layers of width 8 at the
+# ragged capacity 512 are 132 KB by themselves, two spline layers of width 8 at capacity 64 are 111 KB
+FLOW_REFUSED = {'mh-cap512-d300-h8', 'jump_mala-cap512-d300-h8', 'mh-cap64-d50-h8-spline', 'mh-cap64-d50-h8-cpl8-spline'}
+
+
+@pytest.mark.parametrize('case', FLOW_CASES, ids=H.flow_case_id)
+def test_flow_mh_matrix(dev, monkeypatch, case):
+    """H.flow_cases: every flow-MH layout, sibling, width and coupling (the LogRegPot arms of launch_b and launch_b_rqs),
+    the unadjusted carry path and the jump tails, with decisions and log ratios compared row by row (H.compare_flow_mh);
+    N rotates with the capacity over row counts around the 16 KB tile"""
+    d = case.d
+    N = (65, 300, 1000, 63)[int(math.log2(case.cap)) % 4]
+    p = _flow_built(N, d, 5 * d + N, 96, 9)
+    H.run_flow_case(dev, monkeypatch, p, case, margin=MARGIN, compare=_compare, atol=ATOL, rtol=RTOL,
+                    h_mala=0.3 * d ** (-1 / 3), h_hmc=_step('hmc', d), refused=H.flow_case_id(case) in FLOW_REFUSED,
+                    skip_caps=(256,))    # d = 200 on N = 65 rows: fp64 log ratios down to -60
 
 
 # ------------------------------------------------------------------------- 3. fused equals split

@@ -7,6 +7,11 @@ Tolerances (fp32 kernels, fp64 oracle on the same noise):
   decisions     tie-aware: a chain whose fp64 |log u - log ratio| falls under MARGIN at any of its transitions is
                 excluded (its decision is ill-conditioned in fp32 and a flip changes the rest of its trajectory).  The
                 excluded share is reported and must stay under 10 %; all other chains must match.
+
+Flow-proposal cases (section 2 and 2b): from d = 25 on a flow centred by a Laplace fit (H.flow_inputs).  The fp64 oracle
+alone accepts up to 0.085 of the jumps (none at d = 16, a flow about the origin: skip_below_minus_50, log ratios down to
+-141) and 0.168 to 0.421 of the IMH proposals of section 2, and in the matrix 0.227 to 0.836 up to capacity 128 and 0.292
+to 0.510 above; at most 2.1 % of the chains of a case are within MARGIN of a tie, and every other log ratio is above -18.
 """
 import ctypes as C
 import functools
@@ -87,38 +92,51 @@ def test_mcmc_native_stream_matches_oracle(dev, monkeypatch, kind, K, d):
                     what='native %s' % kind)
 
 
+@functools.lru_cache(maxsize=None)
+def _flow_built(K, d, seed, n, spread):
+    """one object per distinct problem of the flow tests: the Laplace fit (H.laplace_fit) is kept per object"""
+    return _record(K, d, seed, n, spread=spread)
+
+
 @pytest.mark.parametrize('fuse_tail', [False, True])
 @pytest.mark.parametrize('K,d', [(2, 16), (5, 64)])
 def test_jump_mala_native_stream_matches_oracle(dev, monkeypatch, fuse_tail, K, d):
     """jump_mala on a fixed perturbed flow: inner MALA fused, the jump on the register flow-MH kernel (or as the tail of
     the last inner launch)."""
     n, T = 192, 3
-    H.jump_mala_matches_oracle(monkeypatch, _record(K, d, 3 * K + d, n, spread=1.0), T=T, Kin=4, seed=31337, h=0.3 * d ** (-1 / 3),
+    p = _flow_built(K, d, 3 * K + d, n, 1.0)
+    q, flows = H.flow_inputs(p, d, n)
+    H.jump_mala_matches_oracle(monkeypatch, q, T=T, Kin=4, seed=31337, h=0.3 * d ** (-1 / 3),
                                imd=None, fuse_tail=fuse_tail, spline=False, atol=ATOL, rtol=RTOL, share=0.95,
-                               jump_slack=max(2, int(0.03 * n * T)))
+                               jump_slack=max(2, int(0.03 * n * T)), margin=MARGIN, skip_below_minus_50=d < 25, flows=flows)
+
+
+# ------------------------------------------------------------------------- 2b. the flow-MH matrix
+FLOW_CASES = H.flow_cases()
+FLOW_TESTS = ('test_jump_mala_native_stream_matches_oracle', 'test_imh_native_stream_matches_oracle', 'test_flow_mh_matrix')
+# the 120 KB LDS bound: two affine coupling layers of width 8 at the ragged capacity 512 are 132 KB by themselves
+FLOW_REFUSED = {'mh-cap512-d300-h8', 'jump_mala-cap512-d300-h8'}
+
+
+@pytest.mark.parametrize('case', FLOW_CASES, ids=H.flow_case_id)
+def test_flow_mh_matrix(dev, monkeypatch, case):
+    """H.flow_cases: every flow-MH layout, sibling, width and coupling (the MixturePot arms of launch_b and launch_b_rqs),
+    the unadjusted carry path and the jump tails, with decisions and log ratios compared row by row (H.compare_flow_mh);
+    K rotates with the capacity, the components overlap (spread 0.5) so that one Gaussian proposal covers them"""
+    d = case.d
+    K = (2, 5, 1, 8)[int(math.log2(case.cap)) % 4]
+    p = _flow_built(K, d, 5 * K + d, 96, 0.5)
+    H.run_flow_case(dev, monkeypatch, p, case, margin=MARGIN, compare=_compare, atol=ATOL, rtol=RTOL,
+                    h_mala=0.3 * d ** (-1 / 3), h_hmc=_step('hmc', d), refused=H.flow_case_id(case) in FLOW_REFUSED)
 
 
 @pytest.mark.parametrize('K,d', [(1, 7), (4, 64), (8, 256)])
-def test_imh_native_stream_matches_oracle(dev, K, d):
-    from nfmc_amd.samplers import imh
-    from nfmc_amd.samplers import jump as jmod
-    from oracle import samplers as osamp
-    n, T, seed = 256, 6, 4711 + d
-    pot, g = _mixture(K, d, 5 * K + d, spread=0.5)
-    x0 = _x0(pot, n, g)
-    f, of = _flow_pair(d, 9)
-    s = imh.FixedIMH((d,), pot, imh.IMHKernel((d,), flow=f), imh.IMHParameters(n_iterations=T))
-    s.seed = seed
-    calls = []
-    orig = jmod.launch_imh_parallel
-    jmod.launch_imh_parallel = lambda *a, **k: calls.append(1) or orig(*a, **k)
-    try:
-        out = s.sample(x0, show_progress=False)
-    finally:
-        jmod.launch_imh_parallel = orig
-    assert not calls   # nfmc_imh_parallel_supported_f32 answers no for kind 2: the sequential flow-MH kernel ran
-    tr = osamp.imh_sample(x0.double(), pot, of, T, noise=osamp.PhiloxNoise(seed, dtype=torch.float64))
-    _compare(out.samples.reshape(T, n, d), tr, 'imh K=%d d=%d' % (K, d))
+def test_imh_native_stream_matches_oracle(dev, monkeypatch, K, d):
+    """nfmc_imh_parallel_supported_f32 answers no for kind 2: the sequential flow-MH kernel runs (H.imh_run asserts it)"""
+    p = _flow_built(K, d, 5 * K + d, 256, 0.5)
+    q, flows = H.flow_inputs(p, d, 256, 9)
+    H.imh_matches_oracle(monkeypatch, q, T=6, seed=4711 + d, flow_seed=9, spline=False, compare=_compare,
+                         what='imh K=%d d=%d' % (K, d), margin=MARGIN, skip_below_minus_50=False, flows=flows)
 
 
 # ------------------------------------------------------------------------- 3. K = 1 is a diagonal Gaussian

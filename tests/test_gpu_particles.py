@@ -51,7 +51,14 @@ other.
 Shapes (P, D): (2, 1), (2, 2) layout (4, 1); (4, 2) DW4 itself, (4, 2); (3, 3) a particle straddling a quad and a lane and
 (5, 3), (4, 4); (11, 3) and (13, 3) = LJ13, (8, 8); (22, 3) (8, 16); (43, 3) (8, 32); (86, 3) (8, 64); (171, 3) and
 (341, 3) (16, 64); (16, 2) fills (4, 8) and (8, 1) fills (4, 2) exactly (tests/test_host_particles.py asks the library).
-Both pair forms up to d = 129, Lennard-Jones alone above.  64 chains, 16 at d >= 513."""
+Both pair forms up to d = 129, Lennard-Jones alone above.  64 chains, 16 at d >= 513.
+
+The jump and IMH cases of section 3 also compare the kernel's decisions and log ratios row by row (H.compare_flow_mh,
+skip_below_minus_50: overlapping particles give U = inf).  The matrix of section 3b proposes about the start lattice
+with 0.3 of the conditional standard deviations there (_flow_centre): the fp64 oracle alone accepts 0.083 to 0.536 of
+the proposals up to capacity 128 and 0.052 to 0.401 above, at most 1.0 % of the chains of a case are within MARGIN of a
+tie, and some proposals are hopeless (fp64 log ratios down to -588): every case sets skip_below_minus_50.
+"""
 import copy
 import functools
 import math
@@ -249,6 +256,7 @@ def test_jump_mala_matches_oracle(dev, monkeypatch, fuse_tail, P, D, pair):
     p = _problem(P, D, pair)
     d, h, imd = p.d, p.step('mala'), p.imd('mala').float()
     f, of = _flow_pair(p)
+    rec = H.FlowRecord(monkeypatch)                           # the jumps' decisions and log ratios, tail or flow-MH kernel
     split, flow_mh = [], []
     orig, orig_fm = jump.split_flow_mh, jump.launch_flow_mh
     monkeypatch.setattr(jump, 'split_flow_mh', lambda *a, **k: split.append(1) or orig(*a, **k))
@@ -268,8 +276,14 @@ def test_jump_mala_matches_oracle(dev, monkeypatch, fuse_tail, P, D, pair):
     ref = osamp.jump_sample(xs.double(), p.target, of, 'langevin', T, Kin, h, inv_mass_diag=imd.double(),
                             noise=osamp.PhiloxNoise(seed, dtype=torch.float64))
     assert torch.equal(tr.stacked(), ref.stacked()) and tr.n_accepted_jumps == ref.n_accepted_jumps
-    keep = _compare(out.samples.reshape(T * (Kin + 1), n, d), tr, 'jump_mala %s tail=%s' % (p.name, fuse_tail))
+    got, what = out.samples.reshape(T * (Kin + 1), n, d), 'jump_mala %s tail=%s' % (p.name, fuse_tail)
+    assert (rec.tails, rec.launches) == ((T, 0) if fuse_tail else (0, T))
+    got_m, got_lr = rec.stacked()
+    H.compare_flow_mh(got_m, got_lr, ref.flow_steps, what, c=H.affine_c(d), margin=MARGIN, skip_below_minus_50=True, min_share=0.9,
+                      comparable=H.jump_comparable(got, ref.stacked().float(), Kin, ATOL, RTOL))
+    keep = _compare(got, tr, what)
     assert out.statistics.n_attempted_jumps == n * T
+    assert out.statistics.n_accepted_jumps == int(got_m.sum())
     assert abs(out.statistics.n_accepted_jumps - tr.n_accepted_jumps) <= T * int((~keep).sum())   # the excluded chains' jumps
 
 
@@ -285,9 +299,48 @@ def test_imh_runs_on_the_register_flow_mh_kernel(dev, monkeypatch, P, D, pair, s
     d, seed = p.d, 4711 + p.d
     f, of = _flow_pair(p, 3 if spline else 9, spline=spline)
     xs = _flow_starts(p, of, 23)
+    rec = H.FlowRecord(monkeypatch)
     out = _imh_run(monkeypatch, p.pot, d, f, xs, T, seed)
     tr = osamp.imh_sample(xs.double(), p.target, of, T, noise=osamp.PhiloxNoise(seed, dtype=torch.float64))
-    _compare(out.samples.reshape(T, n, d), tr, '%s imh %s' % ('c-rqnsf' if spline else 'realnvp', p.name))
+    what = '%s imh %s' % ('c-rqnsf' if spline else 'realnvp', p.name)
+    got_m, got_lr = rec.stacked()
+    c = H.spline_c(d, of, tr.flow_steps)[0] if spline else H.affine_c(d)
+    # proposals with U = inf or a log ratio below -50 must be rejected; the others' log ratios are compared
+    H.compare_flow_mh(got_m, got_lr, tr.flow_steps, what, c=c, margin=MARGIN, skip_below_minus_50=True, min_share=0.9,
+                      u_sensitivity=H.u_sensitivity_of(tr.flow_steps, p.target))     # Lennard-Jones: U(x') is steep in x'
+    _compare(out.samples.reshape(T, n, d), tr, what)
+    assert out.statistics.n_accepted_trajectories == int(got_m.sum())
+
+# ------------------------------------------------------------------------- 3b. the flow-MH matrix
+# capacity -> (P, D, pair), d = P D ragged in it.  jump_tail_ok stays as the class has it: from d = 33 the jumps of the
+# jump cases run on the flow-MH kernel, not behind the inner launch
+FLOW_SHAPES = {4: (3, 1, 'dw'), 8: (2, 3, 'lj'), 16: (4, 3, 'dw'), 32: (8, 3, 'lj'), 64: (16, 3, 'lj'), 128: (33, 3, 'lj'),
+               256: (66, 3, 'lj'), 512: (100, 3, 'lj')}
+FLOW_SKIP_CAPS = (4, 8, 16, 32, 64, 128, 256, 512)    # some proposals are hopeless at every capacity: see the docstring
+FLOW_CASES = H.flow_cases({cap: P * D for cap, (P, D, _pair) in FLOW_SHAPES.items()})
+FLOW_TESTS = ('test_flow_mh_matrix',)
+# the 120 KB LDS bound: two affine coupling layers of width 8 at the ragged capacity 512 are 132 KB by themselves
+FLOW_REFUSED = {'mh-cap512-d300-h8', 'jump_mala-cap512-d300-h8'}
+FLOW_SHRINK = 0.3
+
+
+def _flow_centre(p):
+    """Proposals about the start lattice (the mean of the file's starts), FLOW_SHRINK of the conditional standard deviations there:
+    configurations of finite energy, as _flow_pair's"""
+    return H.local_fit(p, FLOW_SHRINK, at='starts')
+
+
+@pytest.mark.parametrize('case', FLOW_CASES, ids=H.flow_case_id)
+def test_flow_mh_matrix(dev, monkeypatch, case):
+    """H.flow_cases: every flow-MH layout, sibling, width and coupling, the unadjusted carry path and the jump tails, with
+    decisions and log ratios compared row by row (H.compare_flow_mh).  The inner steps of the jump cases shrink with the
+    proposal (FLOW_SHRINK^2 for MALA, a tenth of FLOW_SHRINK for HMC, whose mass diagonal is the lattice's and not the
+    proposal's), so that a chain is still inside it when the jump comes."""
+    P, D, pair = FLOW_SHAPES[case.cap]
+    p = _problem(P, D, pair, 96)
+    H.run_flow_case(dev, monkeypatch, p, case, margin=MARGIN, compare=_compare, atol=ATOL, rtol=RTOL, h_mala=FLOW_SHRINK ** 2 * p.step('mala'),
+                    h_hmc=0.1 * FLOW_SHRINK * p.step('hmc'), imd=lambda kind: p.imd(kind).float(),
+                    refused=H.flow_case_id(case) in FLOW_REFUSED, centre=_flow_centre(p), skip_caps=FLOW_SKIP_CAPS)
 
 
 # ------------------------------------------------------------------------- 4. NeuTra gradient and trajectory (VALU kernels)

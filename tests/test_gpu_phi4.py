@@ -13,6 +13,13 @@ Tolerances are the Rosenbrock tests' (tests/test_gpu_rosenbrock.py):
 
 The shapes cover every (CPL, LPC) layout choose_cfg picks (d = 4 ... 1024), ragged d (100, 60, 144), an odd number of
 rows, one and two rows, and lattices whose rows wrap through every lane of a chain.
+
+Flow-proposal cases (sections 4, 5 and 5b): from d = 24 on a flow centred by a Laplace fit (H.flow_inputs).  The fp64
+oracle alone accepts up to 0.245 of the jumps and 0.001 to 0.280 of the IMH proposals of sections 4 and 5 (the low ends
+are the lattices under d = 24, on a flow about the origin), and in the matrix 0.214 to 0.625 up to capacity 128 and 0.125
+to 0.310 above; under 1 % of the chains of a case are within MARGIN of a tie.  The cases under d = 24, the (8, 8) jump and
+the matrix at capacity 512 have fp64 log ratios down to -140 and set skip_below_minus_50; the others keep every log
+ratio above -50.
 """
 import functools
 import math
@@ -134,23 +141,55 @@ def test_unfused_lattices_run_on_the_split_path(dev, monkeypatch, kind, shape, b
 
 
 # ------------------------------------------------------------------------- 4. jump_mala, 5. imh
+@functools.lru_cache(maxsize=None)
+def _flow_built(shape, boundary, n, seed):
+    """one object per distinct problem of the flow tests: the Laplace fit (H.laplace_fit) is kept per object.  The fit
+    starts between the two wells and ends in one of them: the centred flows propose within that well."""
+    return _record(shape, boundary, n, seed)
+
+
 @pytest.mark.parametrize('spline', [False, True])
 @pytest.mark.parametrize('fuse_tail', [False, True])
 @pytest.mark.parametrize('shape,boundary', [((8,), 'zero'), ((3, 8), 'periodic'), ((8, 8), 'zero')], ids=str)
 def test_jump_mala_native_stream_matches_oracle(dev, monkeypatch, fuse_tail, spline, shape, boundary):
     n, T = 192, 3
-    p, lm = _record(shape, boundary, n, 3)
-    H.jump_mala_matches_oracle(monkeypatch, p, T=T, Kin=4, seed=31337, h=0.3 * p.d ** (-1 / 3) / lm, imd=None, fuse_tail=fuse_tail,
-                               spline=spline, atol=ATOL, rtol=RTOL, share=0.95, jump_slack=max(2, int(0.03 * n * T)))
+    p, lm = _flow_built(shape, boundary, n, 3)
+    q, flows = H.flow_inputs(p, p.d, n, spline=spline, from_d=24)
+    H.jump_mala_matches_oracle(monkeypatch, q, T=T, Kin=4, seed=31337, h=0.3 * p.d ** (-1 / 3) / lm, imd=None, fuse_tail=fuse_tail,
+                               spline=spline, atol=ATOL, rtol=RTOL, share=0.95, jump_slack=max(2, int(0.03 * n * T)), margin=MARGIN,
+                               skip_below_minus_50=p.d != 24, flows=flows)    # (8, 8): fp64 log ratios down to -76
 
 
 @pytest.mark.parametrize('shape,boundary,spline', [((4,), 'periodic', False), ((3, 8), 'zero', False),
                                                    ((8, 8), 'periodic', False), ((16, 16), 'zero', False),
                                                    ((8,), 'periodic', True), ((4, 8), 'zero', True)], ids=str)
 def test_imh_runs_on_the_sequential_flow_mh_kernel(dev, monkeypatch, shape, boundary, spline):
-    p, _lm = _record(shape, boundary, 256, 9)
-    H.imh_matches_oracle(monkeypatch, p, T=6, seed=4711 + p.d, flow_seed=3 if spline else 9, spline=spline, compare=_compare,
-                         what='imh %s %s spline=%s' % (shape, boundary, spline))
+    p, _lm = _flow_built(shape, boundary, 256, 9)
+    q, flows = H.flow_inputs(p, p.d, 256, 3 if spline else 9, spline=spline, from_d=24)
+    H.imh_matches_oracle(monkeypatch, q, T=6, seed=4711 + p.d, flow_seed=3 if spline else 9, spline=spline, compare=_compare,
+                         what='imh %s %s spline=%s' % (shape, boundary, spline), margin=MARGIN, skip_below_minus_50=p.d < 24,
+                         flows=flows)
+
+
+# ------------------------------------------------------------------------- 5b. the flow-MH matrix
+# capacity -> lattice: rows of W = 4 or 8 sites (the register kernels need W % 4 == 0), so d is a multiple of 4 and the
+# capacities 4 and 8 are exact fits; from 16 up d is ragged
+FLOW_SHAPES = {4: (4,), 8: (8,), 16: (3, 4), 32: (3, 8), 64: (6, 8), 128: (12, 8), 256: (24, 8), 512: (36, 8)}
+FLOW_CASES = H.flow_cases({cap: math.prod(shape) for cap, shape in FLOW_SHAPES.items()})
+FLOW_TESTS = ('test_jump_mala_native_stream_matches_oracle', 'test_imh_runs_on_the_sequential_flow_mh_kernel',
+              'test_flow_mh_matrix')
+# the 120 KB LDS bound: two affine coupling layers of width 8 at the ragged capacity 512 are 132 KB by themselves
+FLOW_REFUSED = {'mh-cap512-d288-h8', 'jump_mala-cap512-d288-h8'}
+
+
+@pytest.mark.parametrize('case', FLOW_CASES, ids=H.flow_case_id)
+def test_flow_mh_matrix(dev, monkeypatch, case):
+    """H.flow_cases: every flow-MH layout, sibling, width and coupling, the unadjusted carry path and the jump tails, with
+    decisions and log ratios compared row by row (H.compare_flow_mh); the boundary alternates with the capacity"""
+    p, lm = _flow_built(FLOW_SHAPES[case.cap], BOUNDARIES[int(math.log2(case.cap)) % 2], 96, 9)
+    H.run_flow_case(dev, monkeypatch, p, case, margin=MARGIN, compare=_compare, atol=ATOL, rtol=RTOL,
+                    h_mala=0.3 * p.d ** (-1 / 3) / lm, h_hmc=_step('hmc', p.d, lm), refused=H.flow_case_id(case) in FLOW_REFUSED,
+                    skip_caps=(512,))    # d = 288: fp64 log ratios down to -53
 
 
 # ------------------------------------------------------------------------- 6. NeuTra (VALU kernels)

@@ -13,6 +13,13 @@ Tolerances are the full-rank Gaussian tests' (tests/test_gpu_fullrank.py):
                 excluded; the excluded share must stay under 10 %, all other chains must match.
 
 d in {1, 3, 8, 25, 64, 130, 256, 512} covers every (CPL, LPC) layout choose_cfg picks (LPC 1 ... 64, CPL 4 / 8 / 16).
+
+Flow-proposal cases (section 2 and 2b).  Section 2 runs from d = 25 on a flow centred by a Laplace fit (H.flow_inputs):
+the fp64 oracle alone accepts 0.031 to 0.123 of the jumps, 0.192 to 0.277 of the IMH proposals and 0.001 to 0.266 of the
+spline ones.  A Gaussian with the mode's marginal scales does not cover the ridge, so the matrix proposes inside it
+(_flow_centre: the mode, 0.3 of the conditional standard deviations): the oracle alone accepts 0.234 to 0.573 up to
+capacity 128 and 0.336 to 0.411 above.  Under 1 % of the chains of a case are within MARGIN of a tie.  A proposal off
+the ridge is hopeless (fp64 log ratios down to -4375, in the matrix -63): every case sets skip_below_minus_50.
 """
 import functools
 import math
@@ -28,6 +35,7 @@ pytestmark = pytest.mark.gpu
 
 MARGIN = 2e-3
 ATOL, RTOL = 1e-3, 1e-4
+SKIP = True     # skip_below_minus_50 of the flow-MH cases: a proposal off the ridge is hopeless: see the docstring
 
 
 @pytest.fixture(scope='module')
@@ -124,23 +132,62 @@ def test_mcmc_native_stream_matches_oracle(dev, monkeypatch, kind, d, blk):
 def test_jump_mala_native_stream_matches_oracle(dev, monkeypatch, fuse_tail, d, blk):
     n, T = 192, 3
     p, lm = _record(d, blk, n, 3)
-    H.jump_mala_matches_oracle(monkeypatch, p, T=T, Kin=4, seed=31337, h=0.3 * d ** (-1 / 3) / lm, imd=None, fuse_tail=fuse_tail,
-                               spline=False, atol=ATOL, rtol=RTOL, share=0.95, jump_slack=max(2, int(0.03 * n * T)))
+    q, flows = H.flow_inputs(p, d, n)
+    H.jump_mala_matches_oracle(monkeypatch, q, T=T, Kin=4, seed=31337, h=0.3 * d ** (-1 / 3) / lm, imd=None, fuse_tail=fuse_tail,
+                               spline=False, atol=ATOL, rtol=RTOL, share=0.95, jump_slack=max(2, int(0.03 * n * T)), margin=MARGIN,
+                               skip_below_minus_50=SKIP, flows=flows)
 
 
 @pytest.mark.parametrize('d,blk', [(2, 2), (25, 5), (64, 64), (256, 3)])
 def test_imh_runs_on_the_sequential_flow_mh_kernel(dev, monkeypatch, d, blk):
     p, _lm = _record(d, blk, 256, 9)
-    H.imh_matches_oracle(monkeypatch, p, T=6, seed=4711 + d, flow_seed=9, spline=False, compare=_compare,
-                         what='imh d=%d block=%d' % (d, blk))
+    q, flows = H.flow_inputs(p, d, 256, 9)
+    H.imh_matches_oracle(monkeypatch, q, T=6, seed=4711 + d, flow_seed=9, spline=False, compare=_compare,
+                         what='imh d=%d block=%d' % (d, blk), margin=MARGIN, skip_below_minus_50=SKIP, flows=flows)
 
 
 @pytest.mark.parametrize('d,blk', [(6, 2), (33, 3)])
 def test_spline_flow_imh_matches_oracle(dev, monkeypatch, d, blk):
     """A 'c-rqnsf' flow: the spline instantiations of the register flow-MH kernel for kind 5."""
     p, _lm = _record(d, blk, 256, 11)
-    H.imh_matches_oracle(monkeypatch, p, T=5, seed=99 + d, flow_seed=3, spline=True, compare=_compare,
-                         what='c-rqnsf imh d=%d block=%d' % (d, blk))
+    q, flows = H.flow_inputs(p, d, 256, 3, spline=True)
+    H.imh_matches_oracle(monkeypatch, q, T=5, seed=99 + d, flow_seed=3, spline=True, compare=_compare,
+                         what='c-rqnsf imh d=%d block=%d' % (d, blk), margin=MARGIN, skip_below_minus_50=SKIP, flows=flows)
+
+
+# ------------------------------------------------------------------------- 2b. the flow-MH matrix
+FLOW_SKIP_CAPS = (4, 8, 16, 32, 64, 128, 256, 512)    # some proposals are hopeless at every capacity: see the docstring
+FLOW_CASES = H.flow_cases()
+FLOW_TESTS = ('test_jump_mala_native_stream_matches_oracle', 'test_imh_runs_on_the_sequential_flow_mh_kernel',
+              'test_spline_flow_imh_matches_oracle', 'test_flow_mh_matrix')
+# the 120 KB LDS bound: two affine coupling layers of width 8 at the ragged capacity 512 are 132 KB by themselves
+FLOW_REFUSED = {'mh-cap512-d300-h8', 'jump_mala-cap512-d300-h8'}
+FLOW_SHRINK = 0.3
+
+
+@functools.lru_cache(maxsize=None)
+def _flow_problem(d):
+    """one object per distinct problem of the flow tests: the fit of the proposal's centre is kept per object"""
+    return _record(d, 2 + d % 2, 96, 9)
+
+
+def _flow_centre(p):
+    """A Gaussian with the mode's marginal scales does not cover the ridge (the fp64 oracle alone accepts under 5 % from d = 50); the
+    proposals sit inside the ridge instead: the mode, FLOW_SHRINK of the conditional standard deviations"""
+    return H.local_fit(p, FLOW_SHRINK, at='mode')
+
+
+@pytest.mark.parametrize('case', FLOW_CASES, ids=H.flow_case_id)
+def test_flow_mh_matrix(dev, monkeypatch, case):
+    """H.flow_cases: every flow-MH layout, sibling, width and coupling, the unadjusted carry path and the jump tails, with
+    decisions and log ratios compared row by row (H.compare_flow_mh).  The inner steps of the jump cases shrink with the
+    proposal (FLOW_SHRINK^2 for MALA, FLOW_SHRINK for HMC), so that a chain is still inside it when the jump comes."""
+    d = case.d
+    p, lm = _flow_problem(d)
+    H.run_flow_case(dev, monkeypatch, p, case, margin=MARGIN, compare=_compare, atol=ATOL, rtol=RTOL,
+                    h_mala=FLOW_SHRINK ** 2 * 0.3 * d ** (-1 / 3) / lm, h_hmc=FLOW_SHRINK * _step('hmc', d, lm),
+                    refused=H.flow_case_id(case) in FLOW_REFUSED, centre=_flow_centre(p), skip_caps=FLOW_SKIP_CAPS)
+
 
 
 def test_dual_chain_override_does_not_apply(dev, monkeypatch):

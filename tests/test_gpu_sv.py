@@ -14,6 +14,14 @@ Tolerances are the Rosenbrock tests' (tests/test_gpu_rosenbrock.py):
 
 d in {4, 5, 8, 25, 64, 130, 256, 512, 1024} covers every default (CPL, LPC) layout choose_cfg picks (LPC 1 ... 64, CPL
 4 / 8 / 16) and the lane wrap of the neighbour exchange.
+
+Flow-proposal cases (section 2 and 2b).  The posterior's mode in log sigma is degenerate (a Laplace fit leaves it with a
+gradient of 1e8), so from d = 25 the proposals sit about the mean of the file's starts with 0.3 of the conditional
+standard deviations there (_flow_centre), and the inner steps of the jumps shrink with them.  The fp64 oracle alone
+accepts 0.036 to 0.155 of the jumps and up to 0.325 of the IMH proposals of section 2 (none at the spline d = 6, a flow
+about the origin), and in the matrix 0.115 to 0.495 up to capacity 128 and 0.307 to 0.406 above; under 1 % of the chains
+of a case are within MARGIN of a tie.  Some proposals are hopeless (fp64 log ratios down to -8602, in the matrix -234):
+every case sets skip_below_minus_50.
 """
 import functools
 import math
@@ -29,6 +37,7 @@ pytestmark = pytest.mark.gpu
 
 MARGIN = 2e-3
 ATOL, RTOL = 1e-3, 1e-4
+SKIP = True     # skip_below_minus_50 of the flow-MH cases: a proposal's log sigma can be far off: see the docstring
 MU, SIGMA, PHI = -1.0, 0.25, 0.95
 
 
@@ -108,8 +117,11 @@ def test_mcmc_native_stream_matches_oracle(dev, monkeypatch, kind, d):
 def test_jump_mala_native_stream_matches_oracle(dev, monkeypatch, fuse_tail, d):
     n, T = 192, 3
     p, lm = _record(d, n, 3 + d)
-    H.jump_mala_matches_oracle(monkeypatch, p, T=T, Kin=4, seed=31337, h=0.3 * d ** (-1 / 3) / lm, imd=None, fuse_tail=fuse_tail,
-                               spline=False, atol=ATOL, rtol=RTOL, share=0.95, jump_slack=max(2, int(0.03 * n * T)))
+    q, flows = H.flow_inputs(p, d, n, centre=_flow_centre(p))
+    shrink = FLOW_SHRINK ** 2 if d >= 25 else 1.0          # the inner steps shrink with the proposal: test_flow_mh_matrix
+    H.jump_mala_matches_oracle(monkeypatch, q, T=T, Kin=4, seed=31337, h=shrink * 0.3 * d ** (-1 / 3) / lm, imd=None, fuse_tail=fuse_tail,
+                               spline=False, atol=ATOL, rtol=RTOL, share=0.95, jump_slack=max(2, int(0.03 * n * T)), margin=MARGIN,
+                               skip_below_minus_50=SKIP, flows=flows)
 
 
 @pytest.mark.parametrize('d,spline', [(4, False), (25, False), (130, False), (256, False), (6, True), (33, True)])
@@ -117,8 +129,45 @@ def test_imh_runs_on_the_sequential_flow_mh_kernel(dev, monkeypatch, d, spline):
     """Affine and spline ('c-rqnsf') instantiations of the register flow-MH kernel for kind 6.  The flows are near the
     identity, so starts with a wide spread give a useful share of accepted proposals."""
     p, _lm = _record(d, 256, 9 + d, spread=0.3)
-    H.imh_matches_oracle(monkeypatch, p, T=6, seed=4711 + d, flow_seed=3 if spline else 9, spline=spline, compare=_compare,
-                         what='%s imh d=%d' % ('c-rqnsf' if spline else 'realnvp', d))
+    q, flows = H.flow_inputs(p, d, 256, 3 if spline else 9, spline=spline, centre=_flow_centre(p))
+    H.imh_matches_oracle(monkeypatch, q, T=6, seed=4711 + d, flow_seed=3 if spline else 9, spline=spline, compare=_compare,
+                         what='%s imh d=%d' % ('c-rqnsf' if spline else 'realnvp', d), margin=MARGIN, skip_below_minus_50=SKIP,
+                         flows=flows)
+
+# ------------------------------------------------------------------------- 2b. the flow-MH matrix
+FLOW_DIMS = dict(H.FLOW_DIMS)
+FLOW_DIMS[4] = 4                       # d = T + 3 >= 4: capacity 4 is an exact fit
+FLOW_SKIP_CAPS = (4, 8, 16, 32, 64, 128, 256, 512)    # some proposals are hopeless at every capacity: see the docstring
+FLOW_CASES = H.flow_cases(FLOW_DIMS)
+FLOW_TESTS = ('test_jump_mala_native_stream_matches_oracle', 'test_imh_runs_on_the_sequential_flow_mh_kernel',
+              'test_flow_mh_matrix')
+# the 120 KB LDS bound: two affine coupling layers of width 8 at the ragged capacity 512 are 132 KB by themselves
+FLOW_REFUSED = {'mh-cap512-d300-h8', 'jump_mala-cap512-d300-h8'}
+FLOW_SHRINK = 0.3
+
+
+@functools.lru_cache(maxsize=None)
+def _flow_problem(d):
+    """one object per distinct problem of the flow tests: the fit of the proposal's centre is kept per object"""
+    return _record(d, 96, 9 + d)
+
+
+def _flow_centre(p):
+    """The posterior's mode in log sigma is degenerate (a Laplace fit leaves with a gradient of 1e8): the proposals sit about the
+    mean of the file's starts, FLOW_SHRINK of the conditional standard deviations there"""
+    return H.local_fit(p, FLOW_SHRINK, at='starts')
+
+
+@pytest.mark.parametrize('case', FLOW_CASES, ids=H.flow_case_id)
+def test_flow_mh_matrix(dev, monkeypatch, case):
+    """H.flow_cases: every flow-MH layout, sibling, width and coupling, the unadjusted carry path and the jump tails, with
+    decisions and log ratios compared row by row (H.compare_flow_mh).  The inner steps of the jump cases shrink with the
+    proposal (FLOW_SHRINK^2 for MALA, FLOW_SHRINK for HMC), so that a chain is still inside it when the jump comes."""
+    d = case.d
+    p, lm = _flow_problem(d)
+    H.run_flow_case(dev, monkeypatch, p, case, margin=MARGIN, compare=_compare, atol=ATOL, rtol=RTOL,
+                    h_mala=FLOW_SHRINK ** 2 * 0.3 * d ** (-1 / 3) / lm, h_hmc=FLOW_SHRINK * _step('hmc', d, lm),
+                    refused=H.flow_case_id(case) in FLOW_REFUSED, centre=_flow_centre(p), skip_caps=FLOW_SKIP_CAPS)
 
 
 # ------------------------------------------------------------------------- 3. fused equals split

@@ -27,7 +27,15 @@ Shapes: 'both' at C = 1, 2, 5, 6, 14, 30, 62, 126, 254, 509 is d = 7, 9, 15, 17,
 layouts (4, 2), (4, 4), (4, 4), (4, 8), (8, 8), (8, 16), (8, 32), (8, 64), (16, 64), (16, 64)
 (tests/test_host_varying_effects.py asks the library); 2 C mod 4 is 2 for odd and 0 for even C, so the five globals start
 mid-quad and on a quad boundary; with known noise d = 2 C + 4 = 16 and 32 fill their layouts with no padding.  'int' and
-'slo' at C = 1, 2, 3, 4, 13, 61 put the four globals at every residue of C mod 4; 'es' at C = 1, 2 is layout (4, 1)."""
+'slo' at C = 1, 2, 3, 4, 13, 61 put the four globals at every residue of C mod 4; 'es' at C = 1, 2 is layout (4, 1).
+
+Flow-proposal cases (sections 3, 4 and 4b): from d = 25 on a flow centred by a Laplace fit (H.flow_inputs); the matrix
+uses the non-centred parameterisation, because the Laplace fit of the centred one ends in the funnel's neck, where the
+fp64 oracle alone accepts nothing.  The oracle alone accepts up to 0.326 of the jumps and up to 0.253 of the IMH proposals
+of sections 3 and 4 (none at the small centred shapes, on a flow about the origin), and in the matrix 0.089 to 0.419 up to
+capacity 128 and 0.281 to 0.391 above; under 1 % of the chains of a case are within MARGIN of a tie.  A proposal's log
+scales can be far off (fp64 log ratios down to -73300, in the matrix -8090): every case sets skip_below_minus_50.
+"""
 import functools
 import math
 
@@ -154,14 +162,20 @@ def test_mcmc_native_stream_matches_oracle(dev, monkeypatch, kind, model, Cn, kn
 
 
 # ------------------------------------------------------------------------- 3. jump_mala
+SKIP = True     # skip_below_minus_50 of the flow-MH cases: a proposal's log scales can be far off: see the docstring
+
+
 @pytest.mark.parametrize('fuse_tail', [False, True])
 @pytest.mark.parametrize('model,Cn,centered', [('both', 5, True), ('int', 13, False), ('both', 14, True)])
 def test_jump_mala_native_stream_matches_oracle(dev, monkeypatch, fuse_tail, model, Cn, centered):
     n, T = 192, 3
     p = _problem(model, Cn, n, None, centered)
-    H.jump_mala_matches_oracle(monkeypatch, p, T=T, Kin=4, seed=31337, h=p.step('mala'), imd=p.imd('mala').float(),
+    q, flows = H.flow_inputs(p, p.d, n, from_d=0, centre=H.local_fit(p, 0.3))     # see the docstring
+    # under d = 25 the inner steps shrink with the proposal (0.3^2): the fp64 oracle alone otherwise has every jump below -59
+    H.jump_mala_matches_oracle(monkeypatch, q, T=T, Kin=4, seed=31337, h=(0.09 if p.d < 25 else 1.0) * p.step('mala'),
+                               imd=p.imd('mala').float(),
                                fuse_tail=fuse_tail, spline=False, atol=ATOL, rtol=RTOL, share=0.95,
-                               jump_slack=max(2, int(0.03 * n * T)))
+                               jump_slack=max(2, int(0.03 * n * T)), margin=MARGIN, skip_below_minus_50=SKIP, flows=flows)
 
 
 # ------------------------------------------------------------------------- 4. imh on the sequential flow-MH kernel
@@ -171,8 +185,41 @@ def test_jump_mala_native_stream_matches_oracle(dev, monkeypatch, fuse_tail, mod
 def test_imh_runs_on_the_sequential_flow_mh_kernel(dev, monkeypatch, model, Cn, centered, spline):
     """Affine and spline ('c-rqnsf') instantiations of the register flow-MH kernel for kind 10."""
     p = _problem(model, Cn, 192, None, centered)
-    H.imh_matches_oracle(monkeypatch, p, T=5, seed=4711 + p.d, flow_seed=3 if spline else 9, spline=spline, compare=_compare,
-                         what='%s imh %s' % ('c-rqnsf' if spline else 'realnvp', p.name))
+    q, flows = H.flow_inputs(p, p.d, 192, 3 if spline else 9, spline=spline, from_d=0, centre=H.local_fit(p, 0.3))
+    H.imh_matches_oracle(monkeypatch, q, T=5, seed=4711 + p.d, flow_seed=3 if spline else 9, spline=spline, compare=_compare,
+                         what='%s imh %s' % ('c-rqnsf' if spline else 'realnvp', p.name), margin=MARGIN, skip_below_minus_50=SKIP,
+                         flows=flows)
+
+
+# ------------------------------------------------------------------------- 4b. the flow-MH matrix
+# capacity -> (model, groups): d = C + 2 ('es'), C + 4 ('int'), 2 C + 5 ('both').  The non-centred parameterisation: the
+# Laplace fit of the centred one ends in the funnel's neck, where the fp64 oracle alone accepts nothing
+FLOW_MODELS = {4: ('es', 1), 8: ('es', 5), 16: ('both', 4), 32: ('both', 10), 64: ('int', 46), 128: ('both', 48),
+               256: ('int', 196), 512: ('both', 148)}
+FLOW_DIMS = {4: 3, 8: 7, 16: 13, 32: 25, 64: 50, 128: 101, 256: 200, 512: 301}
+FLOW_CASES = H.flow_cases(FLOW_DIMS)
+FLOW_TESTS = ('test_jump_mala_native_stream_matches_oracle', 'test_imh_runs_on_the_sequential_flow_mh_kernel',
+              'test_flow_mh_matrix')
+# the 120 KB LDS bound: two affine coupling layers of width 8 at the ragged capacity 512 are 132 KB by themselves
+FLOW_REFUSED = {'mh-cap512-d301-h8', 'jump_mala-cap512-d301-h8'}
+
+
+@pytest.mark.parametrize('case', FLOW_CASES, ids=H.flow_case_id)
+def test_flow_mh_matrix(dev, monkeypatch, case):
+    """H.flow_cases: every flow-MH layout, sibling, width and coupling, the unadjusted carry path and the jump tails, with
+    decisions and log ratios compared row by row (H.compare_flow_mh); the inner kernels with the problem's mass diagonals"""
+    p = _problem(*FLOW_MODELS[case.cap], 96, None, False)
+    H.run_flow_case(dev, monkeypatch, p, case, margin=MARGIN, compare=_compare, atol=ATOL, rtol=RTOL, h_mala=p.step('mala'),
+                    h_hmc=p.step('hmc'), imd=lambda kind: p.imd(kind).float(), refused=H.flow_case_id(case) in FLOW_REFUSED,
+                    skip_caps=tuple(FLOW_DIMS))
+
+
+@pytest.mark.parametrize('cap', [64, 128, 256])
+def test_flowb_override_launches_what_more_than_4096_chains_get(dev, monkeypatch, cap):
+    """an unstaged kind (its data is read from global memory; nothing sits behind the flow image)"""
+    p = _problem(*FLOW_MODELS[cap], 96, None, False)
+    f, _of = H.centred_flow_pair(p, 5, 8, scale=0.1 if p.d < 200 else 0.05)
+    H.flowb_override_equals_production(dev, monkeypatch, H.centred(p, 4160, 6), f, lpc=cap // 8, T=3, seed=99)
 
 
 # ------------------------------------------------------------------------- 5. fused equals split

@@ -1,7 +1,8 @@
 """CPU: tests/target_harness.py's own comparisons.  Ten GPU test files trust compare_states, compare_decisions and Spy: a
 bug there silences all of them, so each is shown here to pass on the oracle's own output and to fail on every kind of
 error it exists to catch.  The trace is a real one: oracle.samplers.mcmc_sample, MALA on a standard normal (d = 4, 64
-chains, 3 transitions) with PhiloxNoise."""
+chains, 3 transitions) with PhiloxNoise; the flow-proposal comparison (compare_flow_mh) has imh_sample traces of its own
+below, and the last test runs the inputs of every flow-MH case of the GPU files through the fp64 oracle alone."""
 import copy
 import functools
 
@@ -145,3 +146,182 @@ def test_spy_counts_a_call_through_a_subclass_with_its_own_split_step(monkeypatc
     spy = H.Spy(monkeypatch)
     assert mcmc.MALA._split_step(object()) == 'ran'
     assert spy.calls == [1]
+
+
+# ------------------------------------------------------------------------- the flow-proposal Metropolis comparison
+FD, FN, FT = 6, 96, 4
+
+
+class _Normal:
+    """the harness's Problem, standard normal scaled per coordinate: U = sum (x / sd)^2 / 2"""
+
+    def __init__(self, d):
+        self.d, self.name, self.pot = d, 'normal d=%d' % d, None
+        self.sd = torch.linspace(0.5, 2.0, d, dtype=torch.float64)
+        self.mean = torch.linspace(-3.0, 3.0, d, dtype=torch.float64)
+        self.target = self.ref = lambda x: 0.5 * (((x - self.mean) / self.sd) ** 2).sum(-1)
+        self.x0 = torch.randn(FN, d, generator=torch.Generator().manual_seed(2))
+
+
+@functools.lru_cache(maxsize=None)
+def _flow_case(centred=True, spline=False):
+    """(problem, oracle flow, imh_sample Trace) on the CPU; centred: a centred flow and starts, else flow_pair's about the
+    origin, whose proposals this target (means up to 3, scales down to 0.5) hardly ever takes from its own draws"""
+    from oracle import samplers as osamp
+    p = _Normal(FD)
+    if centred:
+        _f, of = H.centred_flow_pair(p, 3, spline=spline, scale=0.2)
+        p = H.centred(p, FN, 5)
+    else:
+        _f, of = H.flow_pair(FD, 3, spline=spline)
+        p = H.with_starts(p, (p.mean + p.sd * p.x0.double()).float())     # draws of the target: nothing to gain by moving
+    tr = osamp.imh_sample(p.x0.double(), p.target, of, FT, noise=osamp.PhiloxNoise(11, dtype=torch.float64))
+    return p, of, tr
+
+
+def _flow_rec(tr):
+    return (torch.stack([js.mask.reshape(-1) for js in tr.flow_steps]),
+            torch.stack([js.log_alpha.reshape(-1).float() for js in tr.flow_steps]))
+
+
+def _flow_cmp(m, lr, tr, **kw):
+    kw.setdefault('floor', 0.05)
+    return H.compare_flow_mh(m, lr, tr.flow_steps, 'host', c=H.affine_c(FD), margin=MARGIN, skip_below_minus_50=False, **kw)
+
+
+def test_laplace_fit_finds_the_mode_and_the_marginal_scales():
+    p = _Normal(FD)
+    c, s = H.laplace_fit(p)
+    torch.testing.assert_close(c, p.mean, atol=1e-5, rtol=0)          # LBFGS stops at a gradient of 1e-10 or a step of 1e-14
+    torch.testing.assert_close(s, p.sd, atol=1e-8, rtol=0)
+
+
+def test_centred_flow_maps_the_mode_to_its_perturbation_alone():
+    """z = (x - c) / s plus the perturbation: the first layer sends c to its perturbed shift, at most scale in size, and
+    the package flow and the oracle flow hold the same fp32 numbers"""
+    p = _Normal(FD)
+    f, of = H.centred_flow_pair(p, 3, scale=0.2)
+    first = of.bijection.layers[0]
+    z0, _ = first.forward(p.mean[None])
+    assert float(z0.detach().abs().max()) <= 0.2 and float((first.log_scale.detach() + p.sd.log()).abs().max()) <= 0.2
+    for k, v in f.state_dict().items():
+        assert v.dtype == torch.float32 and torch.equal(v.double(), of.state_dict()[k]), k
+    q = H.centred(p, FN, 5)
+    assert q.x0.dtype == torch.float32 and q.x0.shape == (FN, FD) and p.x0 is not q.x0
+
+
+def test_flow_mh_passes_on_the_oracles_own_and_centring_makes_it_accept():
+    _p, _of, tr = _flow_case()
+    m, lr = _flow_rec(tr)
+    follows, ratio = _flow_cmp(m, lr, tr)
+    assert bool(follows.all()) and ratio < 1e-2            # fp32 rounding of the oracle's own log ratios
+    assert tr.n_accepted >= 0.3 * FN * FT
+    assert _flow_case(centred=False)[2].n_accepted <= 0.02 * FN * FT
+
+
+def test_flow_mh_fails_on_a_log_ratio_off_by_one_coordinates_term():
+    """the kernel's log q(x') without the last coordinate's -z^2 / 2: what a dropped lane or tile row gives"""
+    _p, of, tr = _flow_case()
+    m, lr = _flow_rec(tr)
+    js = tr.flow_steps[1]
+    with torch.no_grad():
+        z, _ = of.bijection.forward(js.x_prime)
+    lr = lr.clone()
+    lr[1] -= (0.5 * z[:, -1] ** 2).float()                 # -log q(x') loses +z^2 / 2
+    with pytest.raises(AssertionError):
+        _flow_cmp(m, lr, tr)
+    lr2 = _flow_rec(tr)[1]
+    lr2[1, 7] -= float(0.5 * z[7, -1] ** 2) + 1e-2         # one row alone
+    with pytest.raises(AssertionError):
+        _flow_cmp(m, lr2, tr)
+
+
+def test_flow_mh_fails_on_one_rejection_the_oracle_accepts_by_a_wide_margin():
+    _p, _of, tr = _flow_case()
+    m, lr = _flow_rec(tr)
+    js = tr.flow_steps[0]
+    chain = int(torch.argmax(torch.where(js.mask, js.log_alpha - js.log_u, torch.full_like(js.log_u, -1.0))))
+    assert float(js.log_alpha[chain] - js.log_u[chain]) > 0.5
+    m = m.clone()
+    m[0, chain] = False                                    # one row of 384: no share notices it
+    with pytest.raises(AssertionError, match='clear of a tie'):
+        _flow_cmp(m, lr, tr)
+
+
+def test_flow_mh_fails_when_nothing_is_accepted_and_the_case_demands_the_floor():
+    _p, _of, tr = _flow_case(centred=False)
+    assert tr.n_accepted < 0.05 * FN * FT
+    m, lr = _flow_rec(tr)
+    with pytest.raises(AssertionError, match='acceptance'):
+        H.compare_flow_mh(m, lr, tr.flow_steps, 'host', c=H.affine_c(FD), margin=MARGIN, skip_below_minus_50=True, floor=0.05)
+    H.compare_flow_mh(m, lr, tr.flow_steps, 'host', c=H.affine_c(FD), margin=MARGIN, skip_below_minus_50=True)
+    with pytest.raises(AssertionError, match='log ratio'):      # below -50 and not told to skip
+        H.compare_flow_mh(m, lr, tr.flow_steps, 'host', c=H.affine_c(FD), margin=MARGIN, skip_below_minus_50=False)
+
+
+def test_flow_mh_unadjusted_compares_every_row():
+    from oracle import samplers as osamp
+    p, of, _tr = _flow_case()
+    tr = osamp.imh_sample(p.x0.double(), p.target, of, FT, noise=osamp.PhiloxNoise(11, dtype=torch.float64), adjusted=False)
+    m, lr = _flow_rec(tr)
+    assert bool(m.all())
+    for js, kept in zip(tr.flow_steps, tr.samples):
+        assert torch.equal(js.x_prime, kept)                   # every proposal kept
+    assert torch.equal(tr.flow_steps[1].u_x, tr.flow_steps[0].u_xp) and torch.equal(tr.flow_steps[1].f_x, tr.flow_steps[0].f_xp)
+    _flow_cmp(m, lr, tr, adjusted=False)
+    lr[2, 3] += 0.01
+    with pytest.raises(AssertionError):
+        _flow_cmp(m, lr, tr, adjusted=False)
+    m[1, 0] = False
+    with pytest.raises(AssertionError):
+        _flow_cmp(m, _flow_rec(tr)[1], tr, adjusted=False)
+
+
+def test_flow_mh_tolerance_grows_with_the_four_magnitudes():
+    _p, _of, tr = _flow_case()
+    js = tr.flow_steps[0]
+    tol = H.flow_mh_tolerance(tr.flow_steps, 1e-4)[0]
+    want = 1e-4 + 2e-5 * js.log_alpha.abs() + 8 * 2.0 ** -24 * (js.u_x.abs() + js.u_xp.abs() + js.f_x.abs() + js.f_xp.abs())
+    torch.testing.assert_close(tol, want, rtol=1e-12, atol=0)
+
+
+def test_spline_constant_is_measured_on_the_fp32_oracle_and_never_under_the_affine_one():
+    p, of, tr = _flow_case(spline=True)
+    c, worst = H.spline_c(FD, of, tr.flow_steps)
+    print('spline d=%d: fp32 oracle against fp64 %.2e, c = %.2e' % (FD, worst, c))
+    assert 0 < worst < 1e-3 and c == max(H.affine_c(FD), H.SPLINE_C_FACTOR * worst)
+
+
+def test_jump_rows_are_comparable_until_a_state_leaves_the_oracle():
+    want = torch.zeros(6, 3, 2)                                # T = 2, Kin = 2
+    got = want.clone()
+    got[1, 1, 0] = 1.0                                         # chain 1 leaves at inner transition 1: no jump comparable
+    got[2, 2, 0] = 1.0                                         # chain 2 at the first jump itself: that jump still is
+    comparable = H.jump_comparable(got, want, 2, 1e-3, 1e-4)
+    assert comparable.tolist() == [[True, False, True], [True, False, False]]
+
+
+def test_flow_layout_is_the_launchers_rule():
+    assert [H.flow_layout(d, 96) for d in (3, 7, 13, 25, 64, 100, 130, 500)] == \
+        [(4, 1), (4, 2), (4, 4), (4, 8), (4, 16), (4, 32), (4, 64), (8, 64)]
+    assert [H.flow_layout(d, 4160) for d in (25, 64, 100, 130)] == [(4, 8), (8, 8), (8, 16), (8, 32)]
+    assert H.flow_layout(50, 96, (8, 8)) == (8, 8) and H.flow_layout(70, 96, (8, 8)) == (4, 32)
+
+
+FLOW_FILES = ['fullrank', 'gmrf', 'latent_gaussian', 'logreg', 'mixture', 'phi4', 'irt', 'varying_effects', 'rosenbrock', 'sv',
+              'sparse_logreg', 'particles']
+
+
+@pytest.mark.parametrize('name', FLOW_FILES)
+def test_the_flow_mh_cases_of_a_gpu_file_hold_their_input_conditions_on_the_oracle_alone(monkeypatch, name, capsys):
+    """Every case of the tests a GPU file lists in FLOW_TESTS, run on the CPU up to the conditions on its inputs: at least
+    5 % of the proposals accepted at capacities up to 128, under 10 % of the chains near a tie, every compared log ratio
+    finite and above -50 unless the case says skip_below_minus_50.  The printed lines are where the figures in the
+    files' docstrings come from."""
+    import importlib
+    module = importlib.import_module('test_gpu_' + name)
+    count = H.probe_flow_inputs(module, monkeypatch)
+    lines = [ln for ln in capsys.readouterr().out.splitlines() if 'oracle accepts' in ln or 'unadjusted' in ln]
+    acc = [float(ln.split('oracle accepts ')[1].split()[0]) for ln in lines if 'oracle accepts' in ln]
+    assert count >= len(getattr(module, 'FLOW_CASES', ())) and len(lines) >= count
+    print('%s: %d cases, oracle acceptance %.3f .. %.3f' % (name, count, min(acc), max(acc)))
