@@ -240,6 +240,12 @@ int flow_mh_b_launch(const NfmcFlowMhArgs& args, hipStream_t st, int* grid_out, 
     if (const char* e = getenv("NFMC_FLOWB_DUAL"))
         dual = atoi(e) != 0 && fast && c.cpl >= 8 && c.lpc >= 8 && a.pot.kind != NFMC_POT_FUNNEL && !wants_diag(a);
     dual = dual && !rqs;
+    // The jump of a part runs beside the inner kernel of the other parts: on the layout's register-lean form, where it has
+    // one (flow_b_lean.hip).  A call without a part has the SIMDs to itself and keeps the rich schedule.  NFMC_FLOWB_LEAN=0:
+    // never (measurements); NFMC_FLOWB_LEAN=1: calls without a part too (tests compare the two forms on the same call).
+    const char* lean_env = getenv("NFMC_FLOWB_LEAN");
+    const bool lean = (lean_env ? atoi(lean_env) != 0 : part != nullptr) && fast && !rqs && !dual &&
+                      a.pot.kind == NFMC_POT_QUADRATIC && lean_wpe(c, hp) > 0;
     const int cpw = (kWave / c.lpc) * (dual ? 2 : 1);
     const int64_t tiles = (a.n + (int64_t)kWavesPerBlock * cpw - 1) / ((int64_t)kWavesPerBlock * cpw);
     // Persistent workgroups: the weight image is staged once per workgroup and every wave pays a fixed prologue /
@@ -264,6 +270,10 @@ int flow_mh_b_launch(const NfmcFlowMhArgs& args, hipStream_t st, int* grid_out, 
         NFMC_FOR_OWN_UNIT_POT(NFMC_KIND_CASE)
 #undef NFMC_KIND_CASE
     default:
+        if (lean) {
+            rc = launch_b_lean(a, c, hp, wants_diag(a), tiles, grid, st, dry);
+            if (rc != NFMC_EUNSUPPORTED) break;   // no lean form of this request: today's kernel
+        }
 #define M(CPL, LPC)                                                                      \
     if (c.cpl == CPL && c.lpc == LPC)                                                    \
         rc = rqs ? (hp == 4 ? launch_b_rqs<CPL, LPC, 4>(a, fast, tiles, grid, st, dry) : launch_b_rqs<CPL, LPC, 8>(a, fast, tiles, grid, st, dry)) \

@@ -11,18 +11,32 @@ namespace nfmc {
 // spills SGPRs into VGPR lanes there) are compiled out.  The host picks it when all of those arguments are NULL.
 // NB = 8: rational-quadratic spline couplings ('c-rqnsf') on the same skeleton (round 3; before, spline flows ran the jump on
 // the one-chain-per-lane kernel of flow_kernels.hip only).
-template <int CPL, int LPC, int HP, template <int, int, bool> class Pot, bool FAST, bool DIAG, int RR = 10, int NB = 0>
+// WPE: the waves per SIMD that the register allocation has to leave room for (the occupancy argument of
+// __launch_bounds__).  1, the default, is the rich schedule that wins when the kernel has the SIMDs to itself; the lean
+// forms of the pipelined jump (flow_b_lean.hip) ask for more, so that their waves fit beside the inner kernel's, fence
+// the flow's weight loads (FlowB LEAN), form lane addresses and Philox block numbers where they are used instead of
+// holding them across the loops, and raise their waves' issue priority.  None of that changes a floating-point
+// operation, its operands or the order of the operations of a chain.
 #ifndef NFMC_FLOWB_WPE
 #define NFMC_FLOWB_WPE 1
 #endif
-__global__ void __launch_bounds__(kBlock, NFMC_FLOWB_WPE) flow_mh_b_kernel(NfmcFlowMhArgs a, int64_t tiles) {
+#ifndef NFMC_FLOWB_LEAN_PRIO
+#define NFMC_FLOWB_LEAN_PRIO 3   // s_setprio of the lean forms (0 .. 3; every other kernel of the library runs at 0)
+#endif
+template <int CPL, int LPC, int HP, template <int, int, bool> class Pot, bool FAST, bool DIAG, int RR = 10, int NB = 0,
+          int WPE = NFMC_FLOWB_WPE>
+__global__ void __launch_bounds__(kBlock, WPE) flow_mh_b_kernel(NfmcFlowMhArgs a, int64_t tiles) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int CPW = kWave / LPC;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int g = lane % LPC, cw = lane / LPC;
     const int d = a.flow.d;
     const int64_t n = a.n;
-    using Flow = FlowB<CPL, LPC, HP, false, (FAST && CPL >= 8), NB>;
+    // The lean forms run beside another kernel's waves, which were there first.  At equal priority the SIMD issues the
+    // older wave and the younger gets the slots it leaves: beside four MALA waves at 0.9 VALU busy the C3 jump took the
+    // whole inner launch (105 us for 12 us of issue) and kept the other part's inner launch waiting behind it.
+    if constexpr (WPE > 1) __builtin_amdgcn_s_setprio(NFMC_FLOWB_LEAN_PRIO);
+    using Flow = FlowB<CPL, LPC, HP, (WPE > 1), (FAST && CPL >= 8), NB>;   // WPE > 1: no weight loads hoisted en bloc
     Flow::Img::stage(lds, a.flow, kBlock);
     __syncthreads();
     Flow fl;
@@ -46,7 +60,9 @@ __global__ void __launch_bounds__(kBlock, NFMC_FLOWB_WPE) flow_mh_b_kernel(NfmcF
         const bool active = row < n;
         const uint32_t gchain = (uint32_t)(a.rng.chain_offset + (uint64_t)row);
         float x[CPL];
-        load_row<CPL, LPC, FAST>(a.x, row, d, g, active, x);
+        int gr = g;   // lean forms: the lane's address in the row is formed per tile (not held in a VGPR pair across the loop)
+        if constexpr (WPE > 1) asm volatile("" : "+v"(gr));
+        load_row<CPL, LPC, FAST>(a.x, row, d, gr, active, x);
         float u_x;
         {
             const auto ctx = pot.prepare(x, g, d);
@@ -70,8 +86,13 @@ __global__ void __launch_bounds__(kBlock, NFMC_FLOWB_WPE) flow_mh_b_kernel(NfmcF
         StoreCursor keep(a.samples);
         for (int s = 0; s < a.n_steps; ++s) {
             float xp[CPL];
+            // lean forms: the lane's Philox block numbers are formed anew for every transition.  Left visible, the first
+            // round's products of the (loop-invariant) block numbers are hoisted out of the tile loop and held in 4 VGPRs
+            // per block through the whole flow pass.
+            int gl = g;
+            if constexpr (WPE > 1) asm volatile("" : "+v"(gl));
             draw_latent<CPL, LPC, FAST, RR>(xp, (DIAG && a.rng.replay_normals) ? a.rng.replay_normals + (int64_t)s * n * d : nullptr, a.rng.seed,
-                                  a.rng.step0 + (uint32_t)s, gchain, row, n, d, g, revl);  // flow.sample: jump.py:205 / imh.py:221
+                                  a.rng.step0 + (uint32_t)s, gchain, row, n, d, gl, revl);  // flow.sample: jump.py:205 / imh.py:221
             float part = 0.f;
 #pragma unroll
             for (int i = 0; i < CPL; ++i) part = fmaf(-0.5f * xp[i], xp[i], part);
@@ -117,7 +138,9 @@ __global__ void __launch_bounds__(kBlock, NFMC_FLOWB_WPE) flow_mh_b_kernel(NfmcF
                 if (a.log_ratio_out) a.log_ratio_out[(int64_t)s * n + row] = lr;
             }
         }
-        store_row<CPL, LPC, FAST>(a.x, row, d, g, active, x);
+        int gs = g;   // lean forms: the lane's address in the row is formed again here, not held from the load on
+        if constexpr (WPE > 1) asm volatile("" : "+v"(gs));
+        store_row<CPL, LPC, FAST>(a.x, row, d, gs, active, x);
         if (g == 0 && active) a.logq[row] = f_x;
     }
     if (a.stats.sum_x) block_stats_flush<CPL, LPC>(sx, sxx, n_acc, n_bad, a.stats);
@@ -131,6 +154,15 @@ struct BCfg {
 #define NFMC_FOR_FLOWB_CFG(M) M(4, 1) M(4, 2) M(4, 4) M(4, 8) M(8, 8) M(4, 16) M(8, 16) M(4, 32) M(8, 32) M(4, 64) M(8, 64)
 #define NFMC_BCFG_ENTRY(CPL, LPC) {CPL, LPC},
 constexpr BCfg kFlowBCfgs[] = {NFMC_FOR_FLOWB_CFG(NFMC_BCFG_ENTRY)};
+
+// The register-lean forms of the exact-fit quadratic one-chain kernel (flow_b_lean.hip): a part of a
+// split run (run_parts.hpp) launches its jump on them, so that several jump waves fit into the registers that the
+// inner kernel's waves of the other part leave of a SIMD's 512.
+// lean_wpe: the WPE of the lean form of layout c at conditioner bucket hp, 0 when the layout has none.
+// launch_b_lean: that form (diag: with the diagnostics compiled in); arguments and NFMC_EUNSUPPORTED / dry as in
+// flow_mh_b_launch.
+int lean_wpe(BCfg c, int hp);
+int launch_b_lean(const NfmcFlowMhArgs& a, BCfg c, int hp, bool diag, int64_t tiles, int grid, hipStream_t st, bool dry);
 
 // The own_units kinds (kPotKinds): class POT at layout c, conditioner bucket hp (4 / 8), affine (NB = 0) or spline
 // (NB = kRqsBins) couplings; one general kernel (diagnostics compiled in, default stream) per layout and width.  The
