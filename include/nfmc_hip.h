@@ -250,7 +250,7 @@ enum {
        (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32 with conditioners of at most 32 units).
        NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the fit kernels, the Philox4x32-7 stream and the
        NeuTra matrix-core kernels (conditioners wider than 32). */
-    NFMC_POT_LATENT_GMRF = 13
+    NFMC_POT_LATENT_GMRF = 13,
     /* Latent Gaussian Markov random field: n sites with a sparse, symmetric, positive semi-definite structure matrix R
        of rank rho (random-walk smoothers, ICAR / Besag models on an adjacency graph, the SPDE-Matern field on a grid),
        prior x | tau ~ tau^(rho/2) exp(-tau/2 r^T R r), r = x - m, and on every site one of the likelihoods of
@@ -282,6 +282,44 @@ enum {
        (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32 with conditioners of at most 32 units).
        NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the fit kernels, the Philox4x32-7 stream and the
        NeuTra matrix-core kernels (conditioners wider than 32). */
+    NFMC_POT_DIFFUSION_BRIDGE = 14
+    /* Diffusion bridge: the latent path of a stochastic differential equation dX = f(X) dt + sigma dW discretised by
+       Euler-Maruyama, T >= 2 time steps with a state X_t in R^m (m = 1, 2 or 3) and the step dt, partially observed:
+         X_0 ~ N(mu0, s0^2 I),   X_t | X_{t-1} ~ N(X_{t-1} + dt f(X_{t-1}), sigma^2 dt I) (t >= 1),
+         y_{t,c} ~ N(X_{t,c}, tau^2) wherever w_{t,c} != 0 (the caller writes w = 1; w = 0: not observed),
+       and, when the scales are unknown, p = log sigma and q = log tau with p, q ~ N(l, c^2) independently (a
+       LogNormal(l, c) prior on sigma and on tau).  Coordinates time-major: x[t m + c] = X_{t,c}, then x[T m] = p and
+       x[T m + 1] = q when the scales are unknown: d = T m or T m + 2.  With e_t = X_t - X_{t-1} - dt f(X_{t-1}) (t >= 1),
+       om = 1 / (sigma^2 dt), rho = 1 / tau^2, S_e = sum_{t>=1} |e_t|^2, S_v = sum w (X - y)^2, N_o = sum w, constants dropped:
+         U       = 1/2 |X_0 - mu0|^2 / s0^2 + 1/2 om S_e + 1/2 rho S_v
+                   [ + (T-1) m p + N_o q + (p - l)^2 / (2 c^2) + (q - l)^2 / (2 c^2) ]
+         dU/dX_t = [t = 0] (X_0 - mu0) / s0^2 + [t >= 1] om e_t - [t < T-1] om (I + dt J_f(X_t))^T e_{t+1}
+                   + rho w_t o (X_t - y_t)
+         dU/dp   = -om S_e + (T-1) m + (p - l) / c^2,      dU/dq = -rho S_v + N_o + (q - l) / c^2
+       Drift codes, with the drift parameters (p0, p1, p2, p3) of the header:
+         0 cubic (any m, componentwise)  f_c = p0 x_c - p1 x_c^3,  J = diag(p0 - 3 p1 x_c^2)   (p0 = alpha, p1 = beta:
+                                         0, 0 Brownian motion; alpha < 0, 0 Ornstein-Uhlenbeck; alpha = beta > 0 double well)
+         1 fitzhugh_nagumo (m = 2)       f = (x0 - x0^3/3 - x1 + I, eps (x0 + a - b x1)),  J = [[1 - x0^2, -1], [eps, -eps b]]
+                                         (p0, p1, p2, p3) = (a, b, eps, I)
+         2 lorenz63 (m = 3)              f = (s (x1 - x0), x0 (r - x2) - x1, x0 x1 - beta x2),
+                                         J = [[-s, s, 0], [r - x2, -1, -x0], [x1, x0, -beta]],  (p0, p1, p2) = (s, r, beta)
+       n_components = T; a_scalar = drift code + 4 [scales unknown] + 8 (m - 1), an integer-valued float; b_scalar unused.
+       a -> the header, 16 fp32 in device memory, 16-byte aligned: (dt, sigma, tau, mu0, 1/s0^2, l, 1/c^2, N_o, (T-1) m,
+       p0, p1, p2, p3, 0, 0, 0); with unknown scales sigma and tau are ignored (any positive finite values).
+       b -> fp32 in device memory, 16-byte aligned: the rows y and w of n4 = 4 ceil(T m / 4) floats each, time-major like
+       the coordinates, zero past T m.  A NULL a or b, T < 2, an invalid code, an m that does not fit the drift
+       (fitzhugh_nagumo m = 2, lorenz63 m = 3) or d != T m + 2 [scales unknown] is NFMC_EINVAL; a misaligned a or b is
+       NFMC_EALIGN; d > 1024 is NFMC_EUNSUPPORTED.  The check sees host values only.  Nothing is clamped: an overflowing
+       e^(-2p) or cubic term gives a non-finite U or log ratio, the samplers reject the proposal and count it as
+       non-finite, and the chain's state stays finite.  Cost per evaluation: one 16-byte store of each register
+       quad into the chain's own exchange row, then per register quad one window of 6, 8 or 12 reads of that row (m = 1,
+       2, 3) and 5, 3 or 3 drift evaluations, shared by the quad's four coordinates; two all-reduces per chain, no
+       atomics, bitwise repeatable.
+       Served by nfmc_mala_steps_f32 / nfmc_hmc_steps_f32 (general kernels, with or without a jump tail, device warmup
+       tuning included), by the register-layout kernels of nfmc_flow_mh_steps_f32 and by the VALU NeuTra kernels
+       (nfmc_neutra_potential_grad_f32 / nfmc_neutra_hmc_steps_f32 with conditioners of at most 32 units).
+       NFMC_EUNSUPPORTED from nfmc_imh_parallel_f32, nfmc_dlmc_step_f32, the fit kernels, the Philox4x32-7 stream and the
+       NeuTra matrix-core kernels (conditioners wider than 32). */
 };
 
 typedef struct {
@@ -292,6 +330,7 @@ typedef struct {
                              NFMC_POT_ITEM_RESPONSE: S (students); NFMC_POT_VARYING_EFFECTS: C (groups);
                              NFMC_POT_PARTICLES: P (particles); NFMC_POT_LATENT_GAUSSIAN: d;
                              NFMC_POT_LATENT_GMRF: W (ELL width);
+                             NFMC_POT_DIFFUSION_BRIDGE: T (time steps);
                              0 for the other kinds (was `reserved`, same layout) */
     const float* a; /* (d,) or NULL -> a_scalar */
     const float* b; /* (d,) or NULL -> b_scalar */

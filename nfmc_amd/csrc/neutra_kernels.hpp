@@ -637,6 +637,85 @@ __device__ __forceinline__ float gmrf_value_grad_row(const float* __restrict__ r
                     : gmrf_row<2>(row, grow, p, d, tau, scaled);
 }
 
+// Diffusion bridge (NFMC_POT_DIFFUSION_BRIDGE) for the row of one chain, as potential_value_grad_row: U and dU/dx of
+// DiffusionPot (common.hpp), the path time-major and p = log sigma, q = log tau behind it when the scales are unknown.
+// One pass over t: X_{t-1} carries over in registers, and e_t's successor term -om (I + dt J_f(X_{t-1}))^T e_t is added
+// to the gradient of X_{t-1} when t is reached (sv_value_grad_row), so each coordinate reads the row once and the drift
+// is evaluated once per step; S_e and S_v accumulate on the way and the scales' gradients follow the loop.  The header
+// and the rows y, w are wave-uniform (scalar loads).  (drift, m) is chosen outside the loop.  Kept out of
+// potential_value_grad_row, which the fit and DLMC kernels share and which never see kind 14.
+template <int DR, int M>
+__device__ __forceinline__ float diffusion_row(const float* __restrict__ row, float* __restrict__ grow, const NfmcPotential& p,
+                                               bool unk) {
+    const int nt = p.n_components, tm = nt * M, n4 = latent_row(tm);
+    const float* __restrict__ h = p.a;
+    const float* __restrict__ y = p.b;
+    const float* __restrict__ w = p.b + n4;
+    const float dt = h[kDifDt], mu0 = h[kDifMu0], is0 = h[kDifIs0];
+    const float p0 = h[kDifPar0], p1 = h[kDifPar0 + 1], p2 = h[kDifPar0 + 2], p3 = h[kDifPar0 + 3];
+    const float ps = unk ? row[tm] : 0.f, qs = unk ? row[tm + 1] : 0.f;
+    const float om = unk ? fast_exp(-2.f * ps) / dt : 1.f / (h[kDifSigma] * h[kDifSigma] * dt);
+    const float rho = unk ? fast_exp(-2.f * qs) : 1.f / (h[kDifTau] * h[kDifTau]);
+    float xm[M], se = 0.f, sv = 0.f, u0 = 0.f;
+#pragma unroll
+    for (int c = 0; c < M; ++c) xm[c] = 0.f;
+    for (int t = 0; t < nt; ++t) {
+        float xt[M], gr[M];
+#pragma unroll
+        for (int c = 0; c < M; ++c) xt[c] = row[t * M + c];
+        if (t == 0) {
+#pragma unroll
+            for (int c = 0; c < M; ++c) {
+                const float d0 = xt[c] - mu0;
+                gr[c] = is0 * d0;
+                u0 = fmaf(0.5f * is0 * d0, d0, u0);
+            }
+        } else {
+            float fm[M], e[M], jt[M];
+            diffusion_drift<DR, M>(xm, p0, p1, p2, p3, fm);
+#pragma unroll
+            for (int c = 0; c < M; ++c) {
+                e[c] = fmaf(-dt, fm[c], xt[c] - xm[c]);
+                se = fmaf(e[c], e[c], se);
+                gr[c] = om * e[c];
+            }
+            diffusion_jte<DR, M>(xm, e, p0, p1, p2, p3, jt);
+#pragma unroll
+            for (int c = 0; c < M; ++c) grow[(t - 1) * M + c] = fmaf(-om, fmaf(dt, jt[c], e[c]), grow[(t - 1) * M + c]);
+        }
+#pragma unroll
+        for (int c = 0; c < M; ++c) {
+            if (w[t * M + c] != 0.f) {
+                const float r = xt[c] - y[t * M + c];
+                sv = fmaf(r, r, sv);
+                gr[c] = fmaf(rho, r, gr[c]);
+            }
+            grow[t * M + c] = gr[c];
+            xm[c] = xt[c];
+        }
+    }
+    float u = u0 + 0.5f * (om * se + rho * sv);
+    if (unk) {
+        const float loc = h[kDifLoc], ic2 = h[kDifIc2], nobs = h[kDifNobs], tm1m = h[kDifTm1m];
+        const float dp = ps - loc, dq = qs - loc;
+        u += fmaf(tm1m, ps, nobs * qs) + 0.5f * ic2 * fmaf(dp, dp, dq * dq);
+        grow[tm] = fmaf(-om, se, tm1m) + dp * ic2;
+        grow[tm + 1] = fmaf(-rho, sv, nobs) + dq * ic2;
+    }
+    return u;
+}
+__device__ __forceinline__ float diffusion_value_grad_row(const float* __restrict__ row, float* __restrict__ grow,
+                                                          const NfmcPotential& p, int) {
+    int drift = 0, m = 1;
+    bool unk = false;
+    diffusion_code(p.a_scalar, drift, unk, m);
+    return drift == 2 ? diffusion_row<2, 3>(row, grow, p, unk)
+         : drift == 1 ? diffusion_row<1, 2>(row, grow, p, unk)
+         : m == 3     ? diffusion_row<0, 3>(row, grow, p, unk)
+         : m == 2     ? diffusion_row<0, 2>(row, grow, p, unk)
+                      : diffusion_row<0, 1>(row, grow, p, unk);
+}
+
 // U~(z) and grad U~(z) for this lane's chain.  zrow: latent (tile columns in latent order), read only;
 // wrow: scratch, ends holding z again (rebuilt); grow: gradient in the same column order as zrow.
 template <int HP>
@@ -655,6 +734,7 @@ __device__ __forceinline__ float adjusted_potential_grad_row(const float* __rest
                     : pot.kind == NFMC_POT_PARTICLES ? particles_value_grad_row(wrow, grow, pot, g.d)
                     : pot.kind == NFMC_POT_LATENT_GAUSSIAN ? latent_value_grad_row(wrow, grow, pot, g.d)
                     : pot.kind == NFMC_POT_LATENT_GMRF ? gmrf_value_grad_row(wrow, grow, pot, g.d)
+                    : pot.kind == NFMC_POT_DIFFUSION_BRIDGE ? diffusion_value_grad_row(wrow, grow, pot, g.d)
                                                          : potential_value_grad_row(wrow, grow, pot, g.d);  // U(x), dU/dx (neutra.py:62)
     // reverse sweep, mirror image of flow_inverse_row
     for (int c = 0; c < g.d; ++c) {                               // EA0^-1

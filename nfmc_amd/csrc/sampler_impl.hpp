@@ -672,7 +672,7 @@ int launch_hmc_cfg(const NfmcHmcArgs& a, const JumpDev& jd, bool fast, int64_t t
 constexpr Cfg kJumpCfgs[] = {NFMC_FOR_JUMP_CFG(NFMC_CFG_ENTRY)};
 
 // The own_units kinds (kPotKinds): every layout and jump-tail width of one class in a translation unit of its own
-// (sampler_{fullrank,rosenbrock,sv,slr,phi4,irt,vfx,particles,lgm,gmrf}_{mala,hmc}.hip instantiate these explicitly), the layouts kind 3 gets, general
+// (sampler_{fullrank,rosenbrock,sv,slr,phi4,irt,vfx,particles,lgm,gmrf,diffusion}_{mala,hmc}.hip instantiate these explicitly), the layouts kind 3 gets, general
 // kernels on the default Philox4x32-10 stream only
 template <template <int, int, bool> class POT>
 int launch_mala_kind(const NfmcMalaArgs& a, const JumpDev& jd, Cfg c, int jhp, int64_t tiles, int grid, float sqrt2h,

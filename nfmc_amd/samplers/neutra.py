@@ -18,8 +18,8 @@ from tqdm import tqdm
 
 from .. import hip
 from ..containers import MCMCOutput, NFMCKernel, NFMCParameters, Sampler
-from ..potentials import (FullRankGaussian, ItemResponseTheory, LatentGaussianModel, LatentGMRF, LatticePhi4,
-                          ParticleSystem, Rosenbrock, SparseLogisticRegression, StochasticVolatility,
+from ..potentials import (DiffusionBridge, FullRankGaussian, ItemResponseTheory, LatentGaussianModel, LatentGMRF,
+                          LatticePhi4, ParticleSystem, Rosenbrock, SparseLogisticRegression, StochasticVolatility,
                           VaryingEffectsRegression)
 from .common import Run, chunks, imd_tensor, progress, resolve_target
 from .mcmc import (HMC, MH, HMCKernel, HMCParameters, MHKernel, MHParameters, MetropolisKernel, MetropolisParameters,
@@ -100,11 +100,11 @@ class NeuTra(Sampler):
         matrix cores (csrc/neutra_mfma.hip) also when the flow's own conditioner is narrow (zero-padded).  The matrix-core
         kernels evaluate quadratic and funnel targets only: a FullRankGaussian, a Rosenbrock, a StochasticVolatility, a
         SparseLogisticRegression, a LatticePhi4, an ItemResponseTheory, a VaryingEffectsRegression, a ParticleSystem, a
-        LatentGaussianModel or a LatentGMRF keeps the flow's own width (VALU kernels).  The sparse regression has an odd
-        d = 2 D + 1, so it never reaches the d = 64 / 128 test below; it is listed all the same."""
+        LatentGaussianModel, a LatentGMRF or a DiffusionBridge keeps the flow's own width (VALU kernels).  The sparse
+        regression has an odd d = 2 D + 1, so it never reaches the d = 64 / 128 test below; it is listed all the same."""
         if isinstance(self.target, (FullRankGaussian, Rosenbrock, StochasticVolatility, SparseLogisticRegression, LatticePhi4,
                                     ItemResponseTheory, VaryingEffectsRegression, ParticleSystem, LatentGaussianModel,
-                                    LatentGMRF)):
+                                    LatentGMRF, DiffusionBridge)):
             return 0
         bij = self.kernel.flow.bijection
         ok = (getattr(bij, 'd', 0) in (64, 128) and getattr(bij, 'n_hidden_layers', 0) in (1, 2)
