@@ -80,22 +80,28 @@ def _library_digest():
 _INCLUDE = None
 
 
-def _unit_digest(src):
-    """sha256 of one translation unit with the local headers it includes (transitively) and its flags: an object whose
-    stamp matches is reused, so touching one unit does not recompile the other twenty."""
+def _unit_headers(src, csrc=CSRC, include=INCLUDE):
+    """The local headers (paths under csrc and include) that csrc/src includes, transitively."""
     import re
-    seen, todo = [], [os.path.join(CSRC, src)]
+    unit = os.path.join(csrc, src)
+    seen, todo = set(), [unit]
     while todo:
         path = todo.pop()
         if path in seen or not os.path.isfile(path):
             continue
-        seen.append(path)
+        seen.add(path)
         with open(path, 'r', errors='replace') as fh:
             for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', fh.read(), re.M):
-                for root in (CSRC, INCLUDE):
+                for root in (csrc, include):
                     todo.append(os.path.join(root, inc))
+    return seen - {unit}
+
+
+def _unit_digest(src, csrc=CSRC, include=INCLUDE):
+    """sha256 of one translation unit with the local headers it includes (transitively) and its flags: an object whose
+    stamp matches is reused, so touching one unit does not recompile the other twenty."""
     h = hashlib.sha256()
-    for path in sorted(seen):
+    for path in sorted(_unit_headers(src, csrc, include) | {os.path.join(csrc, src)}):
         h.update(os.path.basename(path).encode())
         with open(path, 'rb') as fh:
             h.update(fh.read())

@@ -3,6 +3,7 @@
 // LPC lanes per chain, state and proposal in VGPRs, flow weights in one LDS image per workgroup
 // (flow_b.hpp).  Same skeleton and statistics path as mala_kernel.
 #include "flow_b_mh.hpp"
+#include "pot_basic.hpp"
 #include "run_parts.hpp"
 
 namespace nfmc {

@@ -13,6 +13,7 @@
 // tests/test_host_flow_mh_lean.py holds the forms to their budgets (and to no scratch) on the built library.  A layout
 // without a form here keeps its kernel of the unsplit run: at (8, 32) (the C5 jump) no form shortened the step.
 #include "flow_b_mh.hpp"
+#include "pot_basic.hpp"
 
 namespace nfmc {
 

@@ -1,8 +1,9 @@
 // flow_mh_b_kernel: the flow-proposal Metropolis transitions of flow_b_kernels.hip, in a header of its own so that the
-// instantiations of the own_units kinds (kPotKinds, common.hpp) compile in translation units of their own.
+// instantiations of the own_units kinds (kPotKinds, pot_kinds.hpp) compile in translation units of their own.
 #pragma once
 
 #include "flow_b.hpp"
+#include "pot_shared.hpp"
 
 namespace nfmc {
 
@@ -167,7 +168,7 @@ int launch_b_lean(const NfmcFlowMhArgs& a, BCfg c, int hp, bool diag, int64_t ti
 // The own_units kinds (kPotKinds): class POT at layout c, conditioner bucket hp (4 / 8), affine (NB = 0) or spline
 // (NB = kRqsBins) couplings; one general kernel (diagnostics compiled in, default stream) per layout and width.  The
 // arguments and NFMC_EUNSUPPORTED / dry as in flow_mh_b_launch.  Never exact-fit or dual: their parameters are tables.
-// flow_b_{fullrank,rosenbrock,sv,slr,phi4,irt,vfx,particles,lgm,gmrf,diffusion}{,_rqs}.hip instantiate it explicitly.
+// The flow_b_<kind>{,_rqs}.hip of NFMC_FOR_OWN_UNIT_POT instantiate it explicitly.
 template <template <int, int, bool> class POT, int NB>
 int launch_b_kind(const NfmcFlowMhArgs& a, BCfg c, int hp, int64_t tiles, int grid, hipStream_t st, bool dry) {
     if (rng_rounds(a.rng) != 10) return NFMC_EUNSUPPORTED;

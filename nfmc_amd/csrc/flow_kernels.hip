@@ -9,6 +9,7 @@
 //
 // One wave per workgroup, one chain per lane, the (64, d) tiles of the wave in LDS (flow_device.hpp).
 #include "mfma_device.hpp"
+#include "pot_kinds.hpp"
 #include "run_parts.hpp"
 
 namespace nfmc {
@@ -379,7 +380,7 @@ extern "C" int nfmc_realnvp_inverse_f32(const NfmcRealNVP* flow, const float* z,
 }
 
 // the potential kinds only the register-layout kernels (flow_b_kernels.hip and the own_units kinds' flow_b_*.hip)
-// evaluate: register_only in kPotKinds (common.hpp).  After check_flow_mh, so the kind has a row.
+// evaluate: register_only in kPotKinds (pot_kinds.hpp).  After check_flow_mh, so the kind has a row.
 static bool register_kernels_only(const NfmcPotential& p) { return pot_kind(p.kind)->register_only; }
 
 static int check_flow_mh(const NfmcFlowMhArgs& a) {

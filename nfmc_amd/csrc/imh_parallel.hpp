@@ -11,6 +11,7 @@
 #pragma once
 
 #include "flow_b.hpp"
+#include "pot_basic.hpp"
 
 namespace nfmc {
 

@@ -1,5 +1,6 @@
 // mala sampler kernels of kind 4 (GaussFullPot, the full-rank Gaussian) in a unit of their own, compiled in parallel
 // with the others: launch_mala_kind, sampler_impl.hpp
 #include "sampler_impl.hpp"
+#include "pot_fullrank.hpp"
 
 template int nfmc::launch_mala_kind<nfmc::GaussFullPot>(const NfmcMalaArgs&, const nfmc::JumpDev&, nfmc::Cfg, int, int64_t, int, float, hipStream_t);

@@ -1,5 +1,6 @@
 // hmc sampler kernels, jump-tail conditioner width 4 (0 = no jump tail): see sampler_impl.hpp
 #include "sampler_impl.hpp"
+#include "pot_basic.hpp"
 
 namespace nfmc {
 int launch_hmc_j4(const NfmcHmcArgs& a, const JumpDev& jd, Cfg c, bool fast, int64_t tiles, int grid, hipStream_t st) {

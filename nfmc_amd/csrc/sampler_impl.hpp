@@ -14,6 +14,7 @@
 #pragma once
 
 #include "flow_b.hpp"
+#include "pot_shared.hpp"
 
 namespace nfmc {
 
@@ -592,7 +593,12 @@ int launch_hmc_kernel(const NfmcHmcArgs& a, const JumpDev& jd, size_t lds, int64
     return launch_lds(kern, grid, kBlock, lds, st, a, tiles, jd);
 }
 
-// kinds 0 to 3 at one layout and jump-tail width (launch_{mala,hmc}_j*): the class, and FAST where it has such kernels
+// kinds 0 to 3 at one layout and jump-tail width (launch_{mala,hmc}_j*): the class, and FAST where it has such kernels.
+// The units that instantiate these include pot_basic.hpp; here the classes are names only.
+template <int CPL, int LPC, bool FAST> struct QuadraticPot;
+template <int CPL, int LPC, bool FAST> struct FunnelPot;
+template <int CPL, int LPC, bool FAST> struct MixturePot;
+template <int CPL, int LPC, bool FAST> struct LogRegPot;
 template <int CPL, int LPC, int JHP>
 int launch_mala_cfg(const NfmcMalaArgs& a, const JumpDev& jd, bool fast, int64_t tiles, int grid, float sqrt2h,
                     hipStream_t st) {
@@ -672,7 +678,7 @@ int launch_hmc_cfg(const NfmcHmcArgs& a, const JumpDev& jd, bool fast, int64_t t
 constexpr Cfg kJumpCfgs[] = {NFMC_FOR_JUMP_CFG(NFMC_CFG_ENTRY)};
 
 // The own_units kinds (kPotKinds): every layout and jump-tail width of one class in a translation unit of its own
-// (sampler_{fullrank,rosenbrock,sv,slr,phi4,irt,vfx,particles,lgm,gmrf,diffusion}_{mala,hmc}.hip instantiate these explicitly), the layouts kind 3 gets, general
+// (the sampler_<kind>_{mala,hmc}.hip of NFMC_FOR_OWN_UNIT_POT instantiate these explicitly), the layouts kind 3 gets, general
 // kernels on the default Philox4x32-10 stream only
 template <template <int, int, bool> class POT>
 int launch_mala_kind(const NfmcMalaArgs& a, const JumpDev& jd, Cfg c, int jhp, int64_t tiles, int grid, float sqrt2h,

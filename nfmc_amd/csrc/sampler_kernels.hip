@@ -1,6 +1,6 @@
 // K1/K2 (+K6, K7): C entry points of the fused Langevin / HMC samplers.  Kernels: sampler_impl.hpp; the
 // template instantiations live in sampler_{mala,hmc}_j{0,4,8}.hip (j = conditioner width of the optional
-// jump tail, 0 = none) and, for the kinds whose row in kPotKinds (common.hpp) says own_units, in a mala and an hmc
+// jump tail, 0 = none) and, for the kinds whose row in kPotKinds (pot_kinds.hpp) says own_units, in a mala and an hmc
 // unit per kind, so they compile in parallel.
 #include <mutex>
 

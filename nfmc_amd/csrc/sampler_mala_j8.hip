@@ -1,5 +1,6 @@
 // mala sampler kernels, jump-tail conditioner width 8 (0 = no jump tail): see sampler_impl.hpp
 #include "sampler_impl.hpp"
+#include "pot_basic.hpp"
 
 namespace nfmc {
 int launch_mala_j8(const NfmcMalaArgs& a, const JumpDev& jd, Cfg c, bool fast, int64_t tiles, int grid, float sqrt2h, hipStream_t st) {

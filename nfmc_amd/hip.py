@@ -24,7 +24,7 @@ POT_PARTICLES = 11
 POT_LATENT_GAUSSIAN = 12
 POT_LATENT_GMRF = 13
 POT_DIFFUSION_BRIDGE = 14
-MIXTURE_MAX_COMPONENTS = 8   # kMixMaxK (csrc/common.hpp)
+MIXTURE_MAX_COMPONENTS = 8   # kMixMaxK (csrc/pot_kinds.hpp)
 TAG_NOISE, TAG_ACCEPT, TAG_LATENT, TAG_JUMP = 0, 1, 2, 3
 CNT_ACCEPTED, CNT_ATTEMPTED, CNT_NONFINITE, CNT_WORDS = 0, 1, 2, 4
 MAX_STEPS_PER_CALL = 512

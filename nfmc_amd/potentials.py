@@ -1786,7 +1786,7 @@ class LatentGMRF(Potential):
     LIKELIHOODS = LatentGaussianModel.LIKELIHOODS
     PARAMETERIZATIONS = ('centered', 'scaled')
     SYMMETRY_RTOL = 1e-6
-    MAX_WIDTH = 32           # ELL slots the kernels run (check_gmrf, csrc/common.hpp)
+    MAX_WIDTH = 32           # ELL slots the kernels run (check_gmrf, csrc/pot_kinds.hpp)
 
     def __init__(self, y, structure, likelihood='poisson', mean=0.0, weight=None, observed=None, precision=1.0,
                  precision_prior=None, parameterization='centered', rank=None, dof=4.0, scale=1.0, event_shape=None):
