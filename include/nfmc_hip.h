@@ -671,6 +671,29 @@ int64_t nfmc_neutra_scratch_bytes(int64_t n, int32_t d, int32_t n_hidden, int32_
 
 int nfmc_neutra_hmc_steps_f32(const NfmcNeutraHmcArgs* args, nfmc_stream_t stream);
 
+/* ---- Random-walk Metropolis in latent space on the same U~(z): z' = z + eps * inv_mass_diag (the diagonal itself, not
+ * its square root), accepted iff log u < U~(z) - U~(z').  One flow inverse and one potential value per transition, no
+ * gradient.  Replaces `NeuTra.adjusted_target` under `MH.propose` (neutra.py:147-159; mh.py:44-73).  adjust = 0 keeps
+ * every proposal and never evaluates U~.  The draws are those of the HMC entry point above: its momentum normals and
+ * its accept uniforms, so they are also what nfmc_philox_normals_f32 / nfmc_mh_accept_select_f32 draw for the split path.
+ * VALU kernels only: n_hidden <= 32 and d <= 512; a wider conditioner answers NFMC_EUNSUPPORTED.  No workspace. */
+typedef struct {
+    float* z;                 /* (n, d) latent state in/out */
+    int64_t n;
+    int32_t n_steps;
+    int32_t adjust;
+    const float* inv_mass_diag;   /* (d,) or NULL for all ones */
+    NfmcRealNVP flow;
+    NfmcPotential pot;
+    NfmcRng rng;
+    NfmcStats stats;          /* moments of the latent z (reference quirk) */
+    NfmcSampleStore samples;
+    uint8_t* masks_out;       /* (n_steps, n) or NULL */
+    float* log_ratio_out;     /* (n_steps, n) or NULL */
+} NfmcNeutraMhArgs;
+
+int nfmc_neutra_mh_steps_f32(const NfmcNeutraMhArgs* args, nfmc_stream_t stream);
+
 /* Adjusted potential and its gradient alone (tests; split path).  n_hidden <= 32: every d <= 512.  n_hidden 33..128
  * (matrix cores): d = 64 / 128 register-resident, every other multiple of 32 up to 512 with the state and the gradient
  * streamed through the caller's workspace NfmcRealNVP.scratch (nfmc_flow_scratch_bytes; csrc/mfma_wide.hip); other d:

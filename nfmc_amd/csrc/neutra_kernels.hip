@@ -87,3 +87,38 @@ extern "C" int nfmc_neutra_hmc_steps_f32(const NfmcNeutraHmcArgs* args, nfmc_str
     }
     return NFMC_OK;
 }
+
+// Random-walk Metropolis on U~ (neutra_mh.hpp).  VALU kernels only: a conditioner wider than 32 answers NFMC_EUNSUPPORTED
+// (check_flow_neutra), the caller keeps the split path.
+extern "C" int nfmc_neutra_mh_steps_f32(const NfmcNeutraMhArgs* args, nfmc_stream_t stream) {
+    if (!args) return NFMC_EINVAL;
+    NfmcNeutraMhArgs a = *args;
+    if (a.stats.sum_x && a.stats.defer) return NFMC_EUNSUPPORTED;   // NeuTra folds its statistics per call
+    if (int rr = rng_default_only(a.rng)) return rr;
+    int rc = check_flow_neutra(&a.flow);
+    if (rc) return rc;
+    if (!a.z || a.n <= 0 || a.n_steps <= 0) return NFMC_EINVAL;
+    if (a.n_steps > NFMC_MAX_STEPS_PER_CALL) return NFMC_ESHAPE;
+    if ((rc = check_potential(a.pot, a.flow.d, PotFamily::kNeutraValu))) return rc;
+    if (a.stats.sum_x && (!a.stats.sum_x2 || !a.stats.counters || !a.stats.scratch)) return NFMC_EINVAL;
+    if (a.adjust && (a.rng.replay_normals != nullptr) != (a.rng.replay_uniforms != nullptr)) return NFMC_EINVAL;
+    if (!store_ok(a.samples)) return NFMC_EINVAL;
+    const int d = a.flow.d;
+    const int dp = padded_d(d);
+    const int rpw = neutra_rows_per_wave(d, 4);
+    if (!rpw) return NFMC_ESHAPE;
+    const int64_t tiles = (a.n + rpw - 1) / rpw;
+    const int grid = (int)(tiles < kMaxGrid ? tiles : kMaxGrid);
+    if (a.stats.sum_x && a.stats.scratch_bytes < (int64_t)grid * (2 * dp + kStatTail) * (int64_t)sizeof(double))
+        return NFMC_ESCRATCH;
+    const size_t lds = (size_t)4 * rpw * tile_stride(d) * sizeof(float);
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = NFMC_NEUTRA_RPW_CALL(neutra_mh_launch_r, hp_bucket_n(a.flow.n_hidden), lds, grid, st, a, tiles, dp))) return rc;
+    NFMC_HIP_CHECK_LAUNCH();
+    if (a.stats.sum_x) {
+        hipLaunchKernelGGL(stats_finish_kernel<true>, dim3(stats_finish_grid(dp)), dim3(kFinishBlock), 0, st, a.stats.scratch,
+                           grid, dp, d, a.stats, (unsigned long long)a.n * (unsigned long long)a.n_steps);
+        NFMC_HIP_CHECK_LAUNCH();
+    }
+    return NFMC_OK;
+}

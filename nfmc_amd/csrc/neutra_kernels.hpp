@@ -463,7 +463,8 @@ static int set_lds_n(K kernel, size_t bytes) {
 #define NFMC_NEUTRA_RPW_DECL(RPWV)                                                                                              \
     int neutra_grad_launch_r##RPWV(int hp, size_t lds, int grid, hipStream_t st, const NfmcRealNVP& f, const NfmcPotential& pot, \
                                   const float* z, int64_t n, float* u_out, float* grad_out, int64_t tiles);                      \
-    int neutra_hmc_launch_r##RPWV(int hp, size_t lds, int grid, hipStream_t st, const NfmcNeutraHmcArgs& a, int64_t tiles, int dp);
+    int neutra_hmc_launch_r##RPWV(int hp, size_t lds, int grid, hipStream_t st, const NfmcNeutraHmcArgs& a, int64_t tiles, int dp); \
+    int neutra_mh_launch_r##RPWV(int hp, size_t lds, int grid, hipStream_t st, const NfmcNeutraMhArgs& a, int64_t tiles, int dp);
 NFMC_NEUTRA_RPW_DECL(64)
 NFMC_NEUTRA_RPW_DECL(32)
 NFMC_NEUTRA_RPW_DECL(16)
@@ -495,6 +496,16 @@ NFMC_NEUTRA_RPW_DECL(16)
         })                                                                                                                      \
         return 0;                                                                                                               \
     }                                                                                                                           \
+    int neutra_mh_launch_r##RPWV(int hp, size_t lds, int grid, hipStream_t st, const NfmcNeutraMhArgs& a, int64_t tiles, int dp) { \
+        int rc = 0;                                                                                                             \
+        NFMC_NEUTRA_HP_SWITCH({                                                                                                 \
+            if ((rc = set_lds_n(neutra_mh_kernel<HP, RPWV>, lds))) return rc;                                                   \
+            hipLaunchKernelGGL((neutra_mh_kernel<HP, RPWV>), dim3(grid), dim3(kNeutraBlock), lds, st, a, tiles, dp);            \
+        })                                                                                                                      \
+        return 0;                                                                                                               \
+    }                                                                                                                           \
     }
 
 }  // namespace nfmc
+
+#include "neutra_mh.hpp"   // neutra_mh_kernel, on the tiles and the statistics layout of neutra_hmc_kernel above

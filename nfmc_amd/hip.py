@@ -135,6 +135,12 @@ class NfmcNeutraHmcArgs(C.Structure):
                 ('scratch_bytes', C.c_int64)]
 
 
+class NfmcNeutraMhArgs(C.Structure):
+    _fields_ = [('z', c_fp), ('n', C.c_int64), ('n_steps', C.c_int32), ('adjust', C.c_int32), ('inv_mass_diag', c_fp),
+                ('flow', NfmcRealNVP), ('pot', NfmcPotential), ('rng', NfmcRng), ('stats', NfmcStats),
+                ('samples', NfmcSampleStore), ('masks_out', c_fp), ('log_ratio_out', c_fp)]
+
+
 class NfmcFlowLogqGradArgs(C.Structure):
     _fields_ = [('flow', NfmcRealNVP), ('x', c_fp), ('n', C.c_int64), ('grad_out', c_fp), ('logq_out', c_fp)]
 
@@ -207,6 +213,7 @@ SYMBOLS = [
     ('nfmc_neutra_hmc_steps_f32', C.c_int, [C.POINTER(NfmcNeutraHmcArgs), c_fp]),
     ('nfmc_neutra_potential_grad_f32', C.c_int, [C.POINTER(NfmcRealNVP), C.POINTER(NfmcPotential), c_fp, C.c_int64,
                                                  c_fp, c_fp, c_fp]),
+    ('nfmc_neutra_mh_steps_f32', C.c_int, [C.POINTER(NfmcNeutraMhArgs), c_fp]),
     ('nfmc_flow_logq_grad_f32', C.c_int, [C.POINTER(NfmcFlowLogqGradArgs), c_fp]),
     ('nfmc_flow_logq_grad_supported_f32', C.c_int, [C.POINTER(NfmcFlowLogqGradArgs)]),
     ('nfmc_dlmc_step_f32', C.c_int, [C.POINTER(NfmcDlmcStepArgs), c_fp]),

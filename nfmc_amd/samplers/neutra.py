@@ -1,7 +1,8 @@
 """NeuTra HMC: HMC in the flow's latent space on U~(z) = U(f^-1(z)) - log|det J_{f^-1}(z)|
 (nfmc/algorithms/sampling/nfmc/neutra.py:58-68,109-129).  The adjusted potential, its gradient (a
 hand-written VJP through the coupling stack), the leapfrog integrator and the accept step run inside
-`nfmc_neutra_hmc_steps_f32`.
+`nfmc_neutra_hmc_steps_f32`.  NeuTra MH (neutra.py:147-159): the random-walk proposal, the flow inverse, the potential
+value and the accept step run inside `nfmc_neutra_mh_steps_f32`.
 
 Like the reference, the stored samples and the running moments are those of the LATENT state z: the
 `data_transform` assigned at neutra.py:122 never reaches the moments;
@@ -18,8 +19,8 @@ from tqdm import tqdm
 
 from .. import hip
 from ..containers import MCMCOutput, NFMCKernel, NFMCParameters, Sampler
-from ..potentials import (DiffusionBridge, FullRankGaussian, ItemResponseTheory, LatentGaussianModel, LatentGMRF,
-                          LatticePhi4, ParticleSystem, Rosenbrock, SparseLogisticRegression, StochasticVolatility,
+from ..potentials import (DiffusionBridge, FullRankGaussian, Funnel, ItemResponseTheory, LatentGaussianModel, LatentGMRF,
+                          LatticePhi4, ParticleSystem, QuadraticPotential, Rosenbrock, SparseLogisticRegression, StochasticVolatility,
                           VaryingEffectsRegression)
 from .common import Run, chunks, imd_tensor, progress, resolve_target
 from .mcmc import (HMC, MH, HMCKernel, HMCParameters, MHKernel, MHParameters, MetropolisKernel, MetropolisParameters,
@@ -49,6 +50,15 @@ class NeuTraParameters(NFMCParameters):
             }
 
 
+# The potentials whose NeuTra-MH transitions run on nfmc_neutra_mh_steps_f32: those measured no slower there than on the
+# split path at 65536 and at 1024 chains (tools/probe_neutra_mh.py --kinds).  The kernel evaluates
+# every neutra_valu kind, but SparseLogisticRegression, ItemResponseTheory, LatentGaussianModel and LatentGMRF walk their
+# observations (or a dense covariance) once per chain and lane there, while the split path evaluates the same potential
+# data-parallel over chains x observations from torch: 1.5 to 9 times faster, so those kinds stay split.
+MH_KERNEL_KINDS = (QuadraticPotential, Funnel, FullRankGaussian, Rosenbrock, StochasticVolatility, LatticePhi4,
+                   VaryingEffectsRegression, ParticleSystem, DiffusionBridge)
+
+
 class NeuTra(Sampler):
     def __init__(self, event_shape, target, inner_sampler_class: Type[MetropolisSampler],
                  inner_kernel: MetropolisKernel, inner_params: MetropolisParameters,
@@ -61,6 +71,7 @@ class NeuTra(Sampler):
         inner_params.n_iterations = self.params.n_iterations
         self.inner_sampler = inner_sampler_class(event_shape, self.adjusted_target, inner_kernel, inner_params)
         self.inner_sampler.fuse = False  # adjusted_target is a Python closure; the fused route is sample() below
+        self.mh_kernel_kinds = MH_KERNEL_KINDS   # tools/probe_neutra_mh.py widens it to time the other kinds on the kernel
         self._grad_kernel_ok = True
 
     def adjusted_target(self, _z, return_data: bool = False):
@@ -161,7 +172,7 @@ class NeuTra(Sampler):
         n, d, event_shape = run.n, run.d, run.event_shape
         pot = resolve_target(self.target, event_shape, self.fuse, family='neutra')
         def split():
-            # NeuTraMH / arbitrary targets / shapes without a fused kernel: the inner sampler's split path on the
+            # arbitrary targets / shapes without a fused kernel: the inner sampler's split path on the
             # adjusted target (neutra.py:116-127)
             inner.seed, inner.shard, inner.replay = self.seed, self.shard, self.replay
             inner.rng_rounds = self.rng_rounds
@@ -172,6 +183,8 @@ class NeuTra(Sampler):
             out.kernel.flow = self.kernel.flow
             return out
 
+        if isinstance(inner, MH) and self._mh_on_kernel(pot, run.rounds):
+            return self._sample_mh(run, pot, split, show_progress, time_limit_seconds)
         if not isinstance(inner, HMC) or pot is None or not self._flow_on_kernels():
             return split()
         out = MCMCOutput(event_shape, kernel=inner.kernel, store_samples=self.params.store_samples,
@@ -225,6 +238,61 @@ class NeuTra(Sampler):
         out.kernel.flow = self.kernel.flow  # neutra.py:128
         return out
 
+    def _mh_on_kernel(self, pot, rounds):
+        """Whether a run with an MH inner sampler goes to nfmc_neutra_mh_steps_f32: a closed-form potential of the NeuTra
+        family whose kind was measured no slower on the kernel (`mh_kernel_kinds`), a flow the kernels take, the default Philox rounds and the flow's own conditioner at most 32 wide (there is
+        no matrix-core MH kernel, so the padding of `_min_hidden` is not borrowed).  Everything else keeps the inner
+        sampler's split path."""
+        return (pot is not None and isinstance(pot, self.mh_kernel_kinds) and self._flow_on_kernels() and rounds == 10
+                and int(self.kernel.flow.bijection.n_hidden) <= 32)
+
+    def _sample_mh(self, run, pot, split, show_progress, time_limit_seconds):
+        """neutra.py:147-159 with mh.py:44-73 on the device: proposal, flow inverse, potential value, Metropolis test,
+        statistics and sample store of up to MAX_STEPS_PER_CALL transitions in one launch of neutra_mh_kernel."""
+        inner = self.inner_sampler
+        n = run.n
+        out = MCMCOutput(run.event_shape, kernel=inner.kernel, store_samples=self.params.store_samples,
+                         max_samples=getattr(self.params, 'max_samples', None))
+        T = int(self.params.n_iterations)
+        store = run.sample_store(T)
+        st_flow, _keep = self.kernel.flow.bijection.packed(run.dev, 0)   # the flow's own width: the kernel is a VALU one
+        imd = imd_tensor(inner.kernel, run.dev)
+        t0 = time.time()
+        done = 0
+        limit = hip.MAX_STEPS_PER_CALL if (time_limit_seconds is None and not show_progress) else 4
+        bar = progress(show_progress, total=T, desc='NeuTra MH')
+        while done < T:
+            if run.time_is_up(t0, time_limit_seconds):
+                break
+            k = min(limit, T - done)
+            a = hip.NfmcNeutraMhArgs()
+            a.z, a.n, a.n_steps = hip.ptr(run.x), n, k
+            a.adjust = 1 if inner.params.adjustment else 0
+            a.inv_mass_diag = hip.ptr(imd)
+            a.flow = st_flow
+            a.pot = pot.descriptor(run.dev)
+            a.rng = run.rng(done, k, adjusted=inner.params.adjustment)
+            a.stats = run.stats.struct()
+            seen_before = store.seen if store is not None else 0
+            a.samples = hip.store_struct(store, k)
+            try:
+                with run.timed('neutra_mh_steps'):
+                    hip.check(hip.lib().nfmc_neutra_mh_steps_f32(C.byref(a), hip.stream()), 'nfmc_neutra_mh_steps_f32')
+            except hip.NfmcArgumentError as e:
+                if store is not None:
+                    store.seen = seen_before
+                if done == 0 and e.no_kernel:   # validation precedes every launch: nothing has run yet
+                    bar.close()
+                    return split()
+                raise
+            done += k
+            bar.update(k)
+        bar.close()
+        calls, grads = inner._counts(n, done)
+        run.finish(out, t0, n * done, store, n_target_calls=calls, n_target_gradient_calls=grads)
+        out.kernel.flow = self.kernel.flow  # neutra.py:128
+        return out
+
 
 class _AdjustedPotential(torch.autograd.Function):
     """Autograd view of the HIP adjusted-potential kernel, so `torch.autograd.grad(adjusted_target(z))`
@@ -253,8 +321,12 @@ class NeuTraHMC(NeuTra):
 
 
 class NeuTraMH(NeuTra):
-    """neutra.py:147-159: random-walk MH in latent space (the adjusted potential comes from the HIP kernel,
-    the proposal/test through the inner sampler's split path)."""
+    """neutra.py:147-159: random-walk MH in latent space.  With a closed-form potential of the NeuTra family that is no
+    slower on the kernel than on the split path (MH_KERNEL_KINDS), a flow on
+    the kernels whose conditioner is at most 32 wide and the default Philox rounds, `sample` runs whole chunks of
+    transitions (proposal, flow inverse, potential value, Metropolis test, statistics, sample store) inside
+    `nfmc_neutra_mh_steps_f32`; every other run, and the warmup that tunes the inverse mass diagonal, goes through the
+    inner sampler's split path on `adjusted_target`."""
 
     def __init__(self, event_shape, target, inner_kernel: MHKernel = None, inner_params: MHParameters = None,
                  kernel: NeuTraKernel = None, params: NeuTraParameters = None):
