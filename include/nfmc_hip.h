@@ -367,8 +367,11 @@ typedef struct {
                                      returns control of the stream (one extra small kernel per call).
                                      1: the call only ADDS its per-workgroup partials to `scratch`, which the caller
                                      zeroed once; nfmc_stats_fold_f32 folds them later (one fold per sample() instead
-                                     of one per launch).  Supported by K1, K2, the flow-MH kernels and K7; the NeuTra
-                                     entry points return NFMC_EUNSUPPORTED. */
+                                     of one per launch).  Supported by K1, K2, the flow-MH kernels and K6
+                                     (nfmc_mh_accept_select_f32); the NeuTra entry points and K7 alone
+                                     (nfmc_moments_update_f32) return NFMC_EUNSUPPORTED.  A defer = 0 call WRITES the
+                                     slabs it uses and folds only those: partials still pending in `scratch` must be
+                                     folded (nfmc_stats_fold_f32) before a defer = 0 call on the same scratch. */
     int32_t tail_slot;            /* defer = 1 only: 0 = accepted / non-finite counts are MCMC counts, 2 = this call
                                      is a jump (they go to the jump counters at fold time) */
 } NfmcStats;
@@ -735,7 +738,12 @@ int nfmc_dlmc_step_supported_f32(const NfmcDlmcStepArgs* args);
 
 /* ---- split path for arbitrary Python targets (U and grad U come from torch autograd on the GPU).
  * K6: mask = log(u) < lp_t' - lp_t + lp_q - lp_q' (nfmc/util.py:382-392), x[mask] = x'[mask]
- * (mcmc/base.py:77), optional carried per-chain scalars, counters. */
+ * (mcmc/base.py:77), optional carried per-chain scalars, counters.  log(u) is the hardware log2 (about one ulp of
+ * log2); a NaN ratio rejects, +inf accepts; every row with !(|log_ratio| <= 3.0e38f) counts in NFMC_CNT_NONFINITE
+ * whichever way it went; log_ratio = NULL accepts every row and counts none.  ATTEMPTED += n (defer = 1: what the fold is
+ * told).  sum_x / sum_x2 are the fp64 sums of the fp32 values of x and of their fp32 squares up to 2048 workgroup tiles
+ * of 4 * 64 / (padded_d / 4, at most 64) rows; past that a lane adds the rows of its tiles in fp32 before widening.
+ * d <= 1024 (NFMC_ESHAPE); the default Philox stream only. */
 typedef struct {
     float* x;                 /* (n, d) in/out */
     const float* x_prime;     /* (n, d) */

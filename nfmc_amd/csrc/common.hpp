@@ -285,6 +285,13 @@ __device__ __forceinline__ float cross_chain_reduce(float v) {
     if constexpr (LPC <= 32) v += __shfl_xor(v, 32, kWave);
     return v;
 }
+// the same sum on values already widened to fp64 (plain shuffles: it runs once per launch)
+template <int LPC>
+__device__ __forceinline__ double cross_chain_reduce_f64(double v) {
+#pragma unroll
+    for (int m = LPC; m < kWave; m <<= 1) v += __shfl_xor(v, m, kWave);
+    return v;
+}
 
 // ------------------------------------------------------------------------------------------------
 // Register layout of a chain ("interleaved 4-blocks"): lane g of the chain's LPC lanes holds, in register i,
@@ -401,10 +408,13 @@ inline bool store_ok(const NfmcSampleStore& s) {
 
 // ------------------------------------------------------------------------------------------------
 // Deterministic statistics.  Each lane carries fp32 partial sums over the <= 512 steps of one call;
-// they are widened to fp64, reduced over the chains of the wave by shuffles, over the waves of the
+// they are reduced over the chains of the wave by shuffles, widened to fp64, reduced over the waves of the
 // workgroup through LDS, written to the workgroup's slot of the scratch slab, and a second tiny
 // kernel folds the slab into the accumulators in a fixed order (no atomics: run-to-run bitwise equal).
-template <int CPL, int LPC>
+// WIDE: widen BEFORE the reduction over the wave's chains.  The fused samplers keep the fp32 shuffles (up to six more
+// roundings on sums that already carry up to 512 fp32 additions per lane); K6 sums one row per lane, so with WIDE its
+// totals are the fp64 sums of the fp32 values (tests/test_gpu_split_kernels.py holds it to that).
+template <int CPL, int LPC, bool WIDE = false>
 __device__ __forceinline__ void block_stats_flush(const float (&sx)[CPL], const float (&sxx)[CPL], uint32_t accepted,
                                                   uint32_t nonfinite, const NfmcStats& st,
                                                   uint32_t jump_accepted = 0, uint32_t jump_nonfinite = 0,
@@ -419,8 +429,8 @@ __device__ __forceinline__ void block_stats_flush(const float (&sx)[CPL], const 
     const int g = lane % LPC;
 #pragma unroll
     for (int i = 0; i < CPL; ++i) {
-        const double a = (double)cross_chain_reduce<LPC>(sx[i]);
-        const double b = (double)cross_chain_reduce<LPC>(sxx[i]);
+        const double a = WIDE ? cross_chain_reduce_f64<LPC>((double)sx[i]) : (double)cross_chain_reduce<LPC>(sx[i]);
+        const double b = WIDE ? cross_chain_reduce_f64<LPC>((double)sxx[i]) : (double)cross_chain_reduce<LPC>(sxx[i]);
         if (lane < LPC) {
             red[wave][coord_of<CPL, LPC>(g, i)] = a;
             red[wave][DP + coord_of<CPL, LPC>(g, i)] = b;

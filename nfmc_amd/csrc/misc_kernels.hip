@@ -113,7 +113,9 @@ __global__ void __launch_bounds__(kBlock) select_kernel(NfmcSelectArgs a, int64_
         n_acc += __shfl_xor(n_acc, m, kWave);
         n_bad += __shfl_xor(n_bad, m, kWave);
     }
-    if (a.stats.sum_x) block_stats_flush<CPL, LPC>(sx, sxx, n_acc, n_bad, a.stats);
+    // WIDE: a lane holds one row's values (two or more only past kMaxGrid tiles), so widening them before the
+    // reduction over the wave's chains makes the totals the fp64 sums of the fp32 values
+    if (a.stats.sum_x) block_stats_flush<CPL, LPC, true>(sx, sxx, n_acc, n_bad, a.stats);
 }
 
 // ---- Langevin proposal / log-ratio from external U, grad U ------------------------------------------
