@@ -264,8 +264,8 @@ inline size_t particles_bytes(const NfmcPotential&, int dp, int cpl) { return (s
 //      launch_{mala,hmc}_kind and launch_b_kind{,_rqs} for the class (sampler_slr_mala.hip and its three siblings are
 //      the pattern).  The build picks up every .hip file of this directory; a unit that takes a minute or more also
 //      goes into SLOW_FIRST (nfmc_amd/build.py).  neutra_valu: the header's include and the kind's arm of
-//      adjusted_potential_grad_row in neutra_kernels.hpp, and its class in the tuple of NeuTra._min_hidden
-//      (nfmc_amd/samplers/neutra.py) that keeps it off the matrix-core kernels.
+//      adjusted_potential_grad_row in neutra_kernels.hpp, and `neutra_matrix_cores = False` on its class in
+//      nfmc_amd/potentials.py, which keeps it off the matrix-core kernels (NeuTra._min_hidden reads it).
 //   4. Python: POT_* in nfmc_amd/hip.py, its class in nfmc_amd/potentials.py, an fp64 oracle tests/<kind>_fp64.py and
 //      tests/test_{host,gpu}_<kind>.py, which assert the codes of step 1's check; its units in the table of
 //      tests/test_host_include_structure.py.

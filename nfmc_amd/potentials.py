@@ -37,6 +37,9 @@ class Potential:
     """Base: `event_shape`, `__call__(x) -> (n,)` in torch ops, `descriptor(device)` for the kernels."""
 
     event_shape: Tuple[int, ...]
+    # NeuTra may present this kind to its matrix-core kernels (csrc/neutra_mfma.hip), which evaluate quadratic and funnel
+    # targets only: every other kind of the NeuTra family sets it False and keeps the flow's own width (VALU kernels)
+    neutra_matrix_cores = True
 
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
         raise NotImplementedError
@@ -313,6 +316,7 @@ class FullRankGaussian(Potential):
     family runs on the split or composed path (`fused_in`).  It is never inferred from a plain callable: pass the object
     as the target."""
 
+    neutra_matrix_cores = False
     SYMMETRY_RTOL = 1e-6
 
     def __init__(self, mu, covariance=None, precision=None, event_shape=None):
@@ -396,6 +400,8 @@ class Rosenbrock(Potential):
     nonzero) in fp32; `block` an int in 1 .. d.  The fused kernels evaluate it in the mcmc, flow-MH and NeuTra launch
     families (NeuTra on its VALU kernels, conditioners of at most 32 units); every other family runs on the split or
     composed path (`fused_in`).  It is never inferred from a plain callable: pass the object as the target."""
+
+    neutra_matrix_cores = False
 
     def __init__(self, event_shape, mu=1.0, a=0.05, b=5.0, block=2):
         if event_shape is None:
@@ -481,6 +487,8 @@ class StochasticVolatility(Potential):
     The fused kernels evaluate it in the mcmc, flow-MH and NeuTra launch families (NeuTra on its VALU kernels,
     conditioners of at most 32 units) for d up to 1024 (T up to 1021); every other family runs on the split or composed
     path (`fused_in`).  It is never inferred from a plain callable: pass the object as the target."""
+
+    neutra_matrix_cores = False
 
     def __init__(self, y, mu_scale=10.0, sigma_scale=5.0, phi_prior=(1.0, 1.0)):
         y = y if torch.is_tensor(y) else torch.as_tensor(y, dtype=torch.float64)
@@ -581,6 +589,8 @@ class SparseLogisticRegression(Potential):
     its log ratio as non-finite.  The fused kernels evaluate it in the mcmc, flow-MH and NeuTra launch families (NeuTra
     on its VALU kernels, conditioners of at most 32 units) for d up to 1024 (D up to 511); every other family runs on the
     split or composed path (`fused_in`).  It is never inferred from a plain callable: pass the object as the target."""
+
+    neutra_matrix_cores = False   # its d = 2 D + 1 is odd, so it never meets the d = 64 / 128 test; stated all the same
 
     def __init__(self, X, y, scale_shape=0.5, scale_rate=0.5):
         X = torch.as_tensor(X)
@@ -696,6 +706,7 @@ class LatticePhi4(Potential):
     family, runs on the split or composed path like any callable (`fused_in`).  It is never inferred from a plain
     callable: pass the object as the target."""
 
+    neutra_matrix_cores = False
     BOUNDARIES = ('periodic', 'zero')
 
     def __init__(self, shape, m2=-1.0, lam=1.0, kappa=1.0, boundary='periodic'):
@@ -804,6 +815,8 @@ class ItemResponseTheory(Potential):
     kernels evaluate it in the mcmc, flow-MH and NeuTra launch families (NeuTra on its VALU kernels, conditioners of at
     most 32 units) for d up to 1024, with no cap on S Q; every other family runs on the split or composed path
     (`fused_in`).  It is never inferred from a plain callable: pass the object as the target."""
+
+    neutra_matrix_cores = False
 
     def __init__(self, responses, observed=None, mean_ability_prior=(0.75, 1.0), ability_scale=1.0, difficulty_scale=1.0):
         R = torch.as_tensor(responses)
@@ -954,6 +967,7 @@ class VaryingEffectsRegression(Potential):
     most 32 units) for d <= 1024, and a larger model, and every other family, runs on the split or composed path like
     any callable (`fused_in`).  It is never inferred from a plain callable: pass the object as the target."""
 
+    neutra_matrix_cores = False
     MODES = {'none': 0, 'shared': 1, 'varying': 2}
 
     def __init__(self, y, group, x=None, intercepts='varying', slopes='none', noise_scale=None, centered=True,
@@ -1217,6 +1231,7 @@ class ParticleSystem(Potential):
     callable: pass the object as the target.  The samplers' usual N(0, I) starts put Lennard-Jones particles on top
     of each other: take the initial states from `start_states`."""
 
+    neutra_matrix_cores = False
     PAIRS = ('lennard_jones', 'double_well')
     CHUNK_FLOATS = 1 << 24   # __call__ evaluates at most this many pair-matrix entries (chunk P P D) at once
 
@@ -1408,6 +1423,7 @@ class LatentGaussianModel(Potential):
     its VALU kernels, conditioners of at most 32 units) for d up to 1024; every other family runs on the split or
     composed path (`fused_in`).  It is never inferred from a plain callable: pass the object as the target."""
 
+    neutra_matrix_cores = False
     LIKELIHOODS = ('poisson', 'binomial', 'student_t')
     PARAMETERIZATIONS = ('centered', 'whitened')
     SYMMETRY_RTOL = 1e-6
@@ -1783,6 +1799,7 @@ class LatentGMRF(Potential):
     and NeuTra launch families for d <= 1024 and W <= 32; anything else runs on the split or composed path like any
     callable (`fused_in`).  It is never inferred from a plain callable: pass the object as the target."""
 
+    neutra_matrix_cores = False
     LIKELIHOODS = LatentGaussianModel.LIKELIHOODS
     PARAMETERIZATIONS = ('centered', 'scaled')
     SYMMETRY_RTOL = 1e-6
@@ -2309,6 +2326,7 @@ class DiffusionBridge(Potential):
     (`fused_in`).  It is never inferred from a plain callable: pass the object as the target.  N(0, I) starts sit far in
     the tails (U ~ 1e5 for the Lorenz preset): start from `prior_draws`."""
 
+    neutra_matrix_cores = False
     DRIFTS = ('cubic', 'fitzhugh_nagumo', 'lorenz63')
     DRIFT_DIMS = {'cubic': (1, 2, 3), 'fitzhugh_nagumo': (2,), 'lorenz63': (3,)}
     DRIFT_PARAMS = {'cubic': ('alpha', 'beta'), 'fitzhugh_nagumo': ('a', 'b', 'epsilon', 'current'),

@@ -8,6 +8,7 @@ import torch
 
 from .. import hip
 from ..containers import DeviceSampleStore
+from ..flows import Flow
 from ..potentials import Potential, recognize
 
 
@@ -84,6 +85,8 @@ class Run:
             self.chain_offset = 0
             self.n_global = self.n
         self.x = x0.detach().to(self.dev, torch.float32).reshape(self.n, self.d).contiguous().clone()
+        # stats.struct() has side effects (it folds, or books `attempted` and defers): like `rng` below it is called
+        # exactly once per launch, and only for a launch that runs; a probe takes hip.null_stats()
         self.stats = hip.DeviceStats(self.d, self.dev)
         if sampler.seed is None:
             seed = int(torch.randint(0, 2 ** 62, ()).item())
@@ -113,7 +116,9 @@ class Run:
         return _Timed(self, label)
 
     def rng(self, step0, k=0, adjusted=True):
-        """NfmcRng for a launch of k transitions starting at transition `step0`."""
+        """NfmcRng for a launch of k transitions starting at transition `step0`.  Replay order is draw order: with
+        replayed noise this consumes k normal fields, and k uniform vectors only when `adjusted`, so it is called exactly
+        once per launch, and only for a launch that runs (a `*_supported_f32` probe takes hip.make_rng instead)."""
         if self.replay is not None:
             nz, un = self.replay.take(k, with_uniforms=adjusted)
             self._keep = (nz, un)
@@ -138,6 +143,32 @@ class Run:
     def elapsed(self):
         self.sync()
         return time.time() - self.t0
+
+    def launches(self, total, limit, t0, time_limit_seconds, bar):
+        """The chunk loop of a sample() call whose transitions all run in launches of at most `limit`: yields
+        (done, k) for the launch of transitions done .. done + k - 1, reads the clock (`time_is_up`) before each and
+        moves `bar` after it; the bar is closed when the loop ends, however it ends.  `self.done` counts the
+        transitions of the launches that returned."""
+        self.done = done = 0
+        clock = time_limit_seconds is not None   # without a limit nothing is read, and the stream is never waited for
+        try:
+            while done < total and not (clock and self.time_is_up(t0, time_limit_seconds)):
+                k = min(limit, total - done)
+                yield done, k
+                self.done = done = done + k
+                bar.update(k)
+        finally:
+            bar.close()
+
+    def offer_state(self, sink):
+        """The current state as the one transition a split-path step offers to `sink`: a sample store, a dense
+        (1, n, d) view of a refit block, or None (nothing is kept)."""
+        if sink is None:
+            return
+        if hasattr(sink, 'add_dense'):
+            sink.add_dense(self.x[None])
+        else:
+            sink[0].copy_(self.x)
 
     def sample_store(self, offered):
         """The store of kept states for a run that offers `offered` of them (thinning and `max_samples` applied on the
@@ -204,6 +235,43 @@ def chunks(total, limit=hip.MAX_STEPS_PER_CALL):
         k = min(limit, total - done)
         yield done, k
         done += k
+
+
+def accept_select(run, step, x_prime, log_ratio, uniforms, tag, stats_struct, carry=None, mask_out=None):
+    """The Metropolis test, the masked update of run.x and the moments of one split-path transition
+    (nfmc_mh_accept_select_f32).  log_ratio None accepts every chain; uniforms None draws them on the native stream
+    `tag` (hip.TAG_ACCEPT / TAG_JUMP) of transition `step`; carry = (per-chain values, their values at the proposal)
+    is copied where a chain accepts; mask_out receives the uint8 mask."""
+    st = hip.NfmcSelectArgs()
+    st.x, st.x_prime, st.n, st.d = hip.ptr(run.x), hip.ptr(x_prime), run.n, run.d
+    st.log_ratio = hip.ptr(log_ratio) if log_ratio is not None else None
+    st.uniforms = hip.ptr(uniforms) if uniforms is not None else None
+    st.n_carry = 0
+    if carry is not None:
+        st.n_carry = 1
+        st.carry[0], st.carry_prime[0] = hip.ptr(carry[0]), hip.ptr(carry[1])
+    st.rng = hip.make_rng(run.seed, run.chain_offset, step, rounds=run.rounds)
+    st.rng_tag = tag
+    st.stats = stats_struct
+    st.mask_out = hip.ptr(mask_out, torch.uint8) if mask_out is not None else None
+    hip.check(hip.lib().nfmc_mh_accept_select_f32(C.byref(st), hip.stream()), 'nfmc_mh_accept_select_f32')
+
+
+def launch_limit(watched, show_progress, time_limit_seconds):
+    """Transitions per launch of `Run.launches`: as many as one call takes when nobody watches the run, `watched` (a few,
+    so that the bar moves and the clock is read) under a progress bar or a time limit."""
+    return hip.MAX_STEPS_PER_CALL if time_limit_seconds is None and not show_progress else watched
+
+
+def _refit(sampler, flow, x_train, x_val):
+    """The in-run refit of JumpNFMC and DLMC (jump.py:201, dlmc.py:70: `flow.fit(x_train=..., x_val=...,
+    **flow_fit_kwargs)`).  The build's own Flow takes `defer_check`: the run's kernels are enqueued and the divergence
+    check (ValueError) is made when the next refit starts / when sampling ends, so that the next launch is queued behind
+    the fit without a host round trip; a foreign flow object is called exactly as the reference calls it."""
+    if isinstance(flow, Flow):
+        return flow.fit(x_train=x_train, x_val=x_val, **{'defer_check': True, **sampler.params.flow_fit_kwargs})
+    flow.fit(x_train=x_train, x_val=x_val, **sampler.params.flow_fit_kwargs)
+    return None
 
 
 def imd_tensor(kernel, dev):

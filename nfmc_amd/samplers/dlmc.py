@@ -17,7 +17,7 @@ import torch
 from .. import hip
 from ..containers import MCMCOutput, NFMCKernel, NFMCParameters, Sampler
 from ..tuning import train_val_split
-from .common import Run, progress, resolve_target
+from .common import Run, _refit, progress, resolve_target
 from .jump import flow_is_native, flow_mh_supported, launch_flow_mh, split_flow_mh
 
 
@@ -147,12 +147,7 @@ class DLMC(Sampler):
         out.running_samples.add(x0)
         return out
 
-    def _refit(self, flow, x_train, x_val):
-        from ..flows import Flow
-        if isinstance(flow, Flow):
-            return flow.fit(x_train=x_train, x_val=x_val, **{'defer_check': True, **self.params.flow_fit_kwargs})
-        flow.fit(x_train=x_train, x_val=x_val, **self.params.flow_fit_kwargs)
-        return None
+    _refit = _refit
 
     def _grad_step(self, run, flow, pot, route):
         """x <- x - eps grad_x [U(x) + log q(x)] (dlmc.py:85-87)."""
@@ -241,8 +236,7 @@ class DLMC(Sampler):
                 target_calls += 2 * n
             else:
                 target_calls += split_flow_mh(run, flow, self.target, es, i, True, run.stats.struct())
-                if store is not None:
-                    store.add_dense(run.x[None])
+                run.offer_state(store)
             done = i + 1
             if show_progress:
                 run.sync()

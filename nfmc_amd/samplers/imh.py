@@ -12,7 +12,7 @@ from tqdm import tqdm
 
 from .. import hip
 from ..containers import MCMCOutput, NFMCKernel, NFMCParameters, Sampler
-from .common import Run, chunks, progress, resolve_target
+from .common import Run, launch_limit, progress, resolve_target
 from .jump import (flow_is_native, flow_mh_supported, imh_parallel_ok, launch_flow_mh, launch_imh_parallel,
                    split_flow_mh)
 
@@ -94,20 +94,15 @@ class FixedIMH(AbstractIMH):
         logq = torch.empty(n, dtype=torch.float32, device=run.dev)
         fused = fused and flow_mh_supported(run, flow, pot, logq)
         t0 = time.time()
-        done = 0
-        unlimited = time_limit_seconds is None and not show_progress
-        limit = hip.MAX_STEPS_PER_CALL if unlimited else 16
+        limit = launch_limit(16, show_progress, time_limit_seconds) if fused else 1
         parallel = fused and imh_parallel_ok(run, flow, pot, logq)
+        if parallel and time_limit_seconds is None and not show_progress:
+            # nobody watches: all proposals of the chunk at once: as many steps as 2^26 work items (1 GiB of work arrays) allow
+            limit = min(hip.IMH_PARALLEL_MAX_STEPS, max(16, (1 << 26) // max(n, 1)))
         bar = progress(show_progress, total=T, desc=self.name)
         if not fused:
             logq.copy_(flow.log_prob(run.x.reshape(n, *event_shape)).detach().to(run.dev, torch.float32))  # imh.py:214
-        while done < T:
-            if run.time_is_up(t0, time_limit_seconds):
-                break
-            k = min(limit, T - done) if fused else 1
-            if fused and parallel and unlimited:
-                # all proposals of the chunk at once: as many steps as 2^26 work items (1 GiB of work arrays) allow
-                k = min(T - done, hip.IMH_PARALLEL_MAX_STEPS, max(16, (1 << 26) // max(n, 1)))
+        for done, k in run.launches(T, limit, t0, time_limit_seconds, bar):
             if fused and parallel:
                 launch_imh_parallel(run, flow, pot, logq, k, done, done > 0,
                                     run.stats.struct(defer=True, attempted=n * k), store)
@@ -116,12 +111,8 @@ class FixedIMH(AbstractIMH):
                                run.stats.struct(defer=True, attempted=n * k), store)
             else:
                 split_flow_mh(run, flow, self.target, event_shape, done, True, run.stats.struct(), logq=logq)
-                if store is not None:
-                    store.add_dense(run.x[None])
-            done += k
-            bar.update(k)
-        bar.close()
-        return run.finish(out, t0, n * done, store, n_target_calls=2 * n * done)
+                run.offer_state(store)
+        return run.finish(out, t0, n * run.done, store, n_target_calls=2 * n * run.done)
 
 
 class HostDraws:

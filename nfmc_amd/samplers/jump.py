@@ -20,7 +20,7 @@ from ..containers import (MCMCKernel, MCMCOutput, MCMCParameters, MCMCStatistics
 from ..flows import Flow, RealNVP
 from ..tuning import train_val_split
 from ..util import metropolis_acceptance_log_ratio
-from .common import Run, chunks, progress, resolve_target
+from .common import Run, _refit, accept_select, chunks, progress, resolve_target
 from .mcmc import HMC, MALA, MH, UHMC, ULA, Langevin, TargetFailure, _guarded
 
 
@@ -102,21 +102,21 @@ def flow_mh_supported(run: Run, flow, pot, logq, adjusted=True) -> bool:
 
 
 def flow_mh_args(run: Run, flow, pot, logq, k, step0, cached, adjusted, stats_struct, samples=None, masks_out=None,
-                 log_ratio_out=None):
-    """NfmcFlowMhArgs of k flow-proposal transitions from transition `step0` (+ keep-alive references)."""
+                 log_ratio_out=None, rng=None):
+    """NfmcFlowMhArgs of k flow-proposal transitions from transition `step0`.  The packed flow, whose memory the struct
+    borrows, stays referenced from it (`_keep`) until the launch is enqueued.  It takes the launch's noise (Run.rng, see
+    there) unless the caller hands it an `rng` of its own (the probes)."""
     a = hip.NfmcFlowMhArgs()
-    st, _keep = flow.bijection.packed(run.dev)
+    a.flow, a._keep = flow.bijection.packed(run.dev)
     a.x, a.logq, a.n, a.n_steps = hip.ptr(run.x), hip.ptr(logq), run.n, k
     a.logq_cached = 1 if cached else 0
     a.adjusted = 1 if adjusted else 0
-    a.flow = st
     a.pot = pot.descriptor(run.dev)
-    a.rng = run.rng(step0, k, adjusted=adjusted)
+    a.rng = rng if rng is not None else run.rng(step0, k, adjusted=adjusted)
     a.stats = stats_struct
     a.samples = hip.store_struct(samples, k)
     a.masks_out = hip.ptr(masks_out, torch.uint8) if masks_out is not None else None
     a.log_ratio_out = hip.ptr(log_ratio_out) if log_ratio_out is not None else None
-    a._keep = _keep
     return a
 
 
@@ -153,15 +153,13 @@ def launch_jump_run(run: Run, inner, flow, pot, logq, step0, n_outer, n_inner, n
 
 
 def _flow_mh_probe_args(run: Run, flow, pot, logq, adjusted):
-    a = hip.NfmcFlowMhArgs()
-    st, _keep = flow.bijection.packed(run.dev)
-    a.x, a.logq, a.n, a.n_steps = hip.ptr(run.x), hip.ptr(logq), run.n, 1
-    a.adjusted = 1 if adjusted else 0
-    a.flow = st
-    a.pot = pot.descriptor(run.dev)
-    a.rng = hip.make_rng(run.seed, run.chain_offset, 0, rounds=run.rounds)
-    a.stats = hip.null_stats()
-    return a, _keep
+    """The struct of one transition for a `*_supported_f32` question (+ keep-alive references).  A probe launches
+    nothing, so it differs from a launch's struct in two fields: hip.make_rng instead of Run.rng, hip.null_stats()
+    instead of the run's statistics.  Like a launch that keeps nothing it carries the empty sample store
+    (hip.dense_store(None): no base pointer), where it used to leave the store zeroed."""
+    a = flow_mh_args(run, flow, pot, logq, 1, 0, False, adjusted, hip.null_stats(),
+                     rng=hip.make_rng(run.seed, run.chain_offset, 0, rounds=run.rounds))
+    return a, a._keep
 
 
 def imh_parallel_ok(run: Run, flow, pot, logq) -> bool:
@@ -182,18 +180,7 @@ def imh_parallel_ok(run: Run, flow, pot, logq) -> bool:
 def launch_imh_parallel(run: Run, flow, pot, logq, k, step0, cached, stats_struct, samples=None, masks_out=None,
                         log_ratio_out=None):
     """k IMH transitions of every chain through nfmc_imh_parallel_f32 (same contract as launch_flow_mh)."""
-    a = hip.NfmcFlowMhArgs()
-    st, _keep = flow.bijection.packed(run.dev)
-    a.x, a.logq, a.n, a.n_steps = hip.ptr(run.x), hip.ptr(logq), run.n, k
-    a.logq_cached = 1 if cached else 0
-    a.adjusted = 1
-    a.flow = st
-    a.pot = pot.descriptor(run.dev)
-    a.rng = run.rng(step0, k, adjusted=True)
-    a.stats = stats_struct
-    a.samples = hip.store_struct(samples, k)
-    a.masks_out = hip.ptr(masks_out, torch.uint8) if masks_out is not None else None
-    a.log_ratio_out = hip.ptr(log_ratio_out) if log_ratio_out is not None else None
+    a = flow_mh_args(run, flow, pot, logq, k, step0, cached, True, stats_struct, samples, masks_out, log_ratio_out)
     nbytes = int(hip.lib().nfmc_imh_parallel_work_bytes(run.n, run.d, k))
     work = torch.empty(nbytes, dtype=torch.uint8, device=run.dev)
     with run.timed('imh_parallel'):
@@ -207,25 +194,22 @@ def split_flow_mh(run: Run, flow, target, event_shape, step, adjusted, stats_str
     (jump.py:205-231, imh.py:221-233): flow passes through the flow's own API, target calls in torch on
     the GPU, test + masked update + moments in nfmc_mh_accept_select_f32."""
     n, d = run.n, run.d
+    # this package's flow draws from the run's own noise streams, replayed ones included; a foreign flow object draws its
+    # own latent, and the test then takes native uniforms
+    own = flow_is_native(flow) or isinstance(flow, Flow)
     with torch.no_grad():
-        if flow_is_native(flow) or isinstance(flow, Flow):   # this package's flow: the run's own noise streams
-            rng = hip.make_rng(run.seed, run.chain_offset, step, rounds=run.rounds)
-            if run.replay is not None:
-                nz, _ = run.replay.take(1, with_uniforms=False)
-                x_prime, ld = flow.bijection.inverse(nz[0].reshape(n, *event_shape))
-                zz = nz[0]
-                f_xp = (-0.5 * (zz * zz).sum(-1) - 0.5 * d * 1.8378770664093453) - ld
-                unif = None   # taken below, once the target calls have returned (jump.py:225)
-            else:
-                x_prime, f_xp = flow.sample(n, return_log_prob=True, rng=rng)
-                unif = None
+        if own and run.replay is not None:
+            zz = run.replay.take(1, with_uniforms=False)[0][0]
+            x_prime, ld = flow.bijection.inverse(zz.reshape(n, *event_shape))
+            f_xp = (-0.5 * (zz * zz).sum(-1) - 0.5 * d * 1.8378770664093453) - ld
+        elif own:
+            x_prime, f_xp = flow.sample(n, return_log_prob=True,
+                                        rng=hip.make_rng(run.seed, run.chain_offset, step, rounds=run.rounds))
         else:
             x_prime, f_xp = flow.sample(n, return_log_prob=True)
-            unif = None
         x_prime = x_prime.detach().to(run.dev, torch.float32).reshape(n, d).contiguous()
         f_xp = f_xp.detach().to(run.dev, torch.float32).contiguous()
-        lr = None
-        f_x = None
+        lr = unif = None
         target_calls = 0
         if adjusted:
             # jump.py:210-227 / imh.py:222-237: a ValueError from the target or from flow.log_prob rejects every chain
@@ -237,24 +221,12 @@ def split_flow_mh(run: Run, flow, target, event_shape, step, adjusted, stats_str
                 f_x = logq if logq is not None else _guarded(flow.log_prob, run.x.reshape(n, *event_shape))
                 f_x = f_x.detach().to(run.dev, torch.float32).contiguous()
                 lr = metropolis_acceptance_log_ratio(-u_x, -u_xp, f_x, f_xp).float().contiguous()
-                if run.replay is not None and (flow_is_native(flow) or isinstance(flow, Flow)):
+                if own and run.replay is not None:   # only once the target calls have returned (jump.py:225)
                     unif = run.replay.take_uniforms(1)[0].contiguous()
             except TargetFailure:
                 lr = torch.full((n,), -math.inf, dtype=torch.float32, device=run.dev)
-    st = hip.NfmcSelectArgs()
-    st.x, st.x_prime, st.n, st.d = hip.ptr(run.x), hip.ptr(x_prime), n, d
-    st.log_ratio = hip.ptr(lr) if lr is not None else None
-    st.uniforms = hip.ptr(unif) if unif is not None else None
-    st.n_carry = 0
-    if logq is not None and adjusted:
-        st.n_carry = 1
-        st.carry[0] = hip.ptr(logq)
-        st.carry_prime[0] = hip.ptr(f_xp)
-    st.rng = hip.make_rng(run.seed, run.chain_offset, step, rounds=run.rounds)
-    st.rng_tag = hip.TAG_JUMP
-    st.stats = stats_struct
-    st.mask_out = None
-    hip.check(hip.lib().nfmc_mh_accept_select_f32(C.byref(st), hip.stream()), 'nfmc_mh_accept_select_f32')
+    accept_select(run, step, x_prime, lr, unif, hip.TAG_JUMP, stats_struct,
+                  carry=(logq, f_xp) if logq is not None and adjusted else None)
     return target_calls
 
 
@@ -289,16 +261,7 @@ class JumpNFMC(Sampler):
     def name(self):
         return 'Jump MCMC'
 
-    def _refit(self, flow, x_train, x_val):
-        """jump.py:201 `self.kernel.flow.fit(x_train=..., x_val=..., **flow_fit_kwargs)`.  The build's own Flow takes
-        `defer_check`: the run's kernels are enqueued and the divergence check (ValueError) is made when the next refit
-        starts / when sampling ends, so that the next inner launch is queued behind the fit without a host round trip; a
-        foreign flow object is called exactly as the reference calls it."""
-        from ..flows import Flow
-        if isinstance(flow, Flow):
-            return flow.fit(x_train=x_train, x_val=x_val, **{'defer_check': True, **self.params.flow_fit_kwargs})
-        flow.fit(x_train=x_train, x_val=x_val, **self.params.flow_fit_kwargs)
-        return None
+    _refit = _refit
 
     def _jump_parts(self, inner, n):
         parts = self.jump_parts
@@ -441,8 +404,7 @@ class JumpNFMC(Sampler):
             else:
                 jump_target_calls += split_flow_mh(run, flow, self.target, event_shape, base + K,
                                                    self.params.adjusted_jumps, run.stats.struct(jump=True))
-                if store is not None:
-                    store.add_dense(run.x[None])
+                run.offer_state(store)
             done = i + 1
             if show_progress:
                 run.sync()

@@ -20,7 +20,7 @@ from tqdm import tqdm
 from .. import hip
 from ..containers import MCMCKernel, MCMCOutput, MCMCParameters, Sampler
 from ..tuning import DualAveraging, DualAveragingParams
-from .common import Run, chunks, imd_tensor, progress, resolve_target
+from .common import Run, accept_select, imd_tensor, launch_limit, progress, resolve_target
 
 
 @dataclass
@@ -225,11 +225,10 @@ class MCMCSampler(Sampler):
         run.stats.zero_()
         self._n_divergences = 0
         t0 = time.time()
-        done = 0
         label = f'{self.name} (tuning)' if self.params.tuning else self.name
         bar = progress(show_progress, total=K, desc=label)
         stepwise = self.params.tuning or pot is None
-        limit = 1 if stepwise else (hip.MAX_STEPS_PER_CALL if time_limit_seconds is None and not show_progress else 32)
+        limit = 1 if stepwise else launch_limit(32, show_progress, time_limit_seconds)
         # warmup of a fused sampler on one GPU: kernel state and controller on the device, no host round trip per step
         # (sharded chains keep the host controller: its statistics are all-reduced over the ranks every step)
         tune = None
@@ -243,13 +242,10 @@ class MCMCSampler(Sampler):
             tune = DeviceTuning(self, run)
             # one ABI call enqueues every (kernel, controller) pair of up to 512 transitions: no host work per update
             tune.every = max(1, int(getattr(self.params, 'tune_every', 1)))
-            limit = hip.MAX_STEPS_PER_CALL if time_limit_seconds is None and not show_progress else max(32, tune.every)
+            limit = launch_limit(max(32, tune.every), show_progress, time_limit_seconds)
             # calls of whole pools: the controller updates once per `every` transitions whatever the call size
             limit -= limit % tune.every
-        while done < K:
-            if run.time_is_up(t0, time_limit_seconds):
-                break
-            k = min(limit, K - done)
+        for done, k in run.launches(K, limit, t0, time_limit_seconds, bar):
             if tune is not None:
                 self._launch(run, pot, k, step0 + done, store, tune=tune)
             elif pot is not None:
@@ -261,11 +257,8 @@ class MCMCSampler(Sampler):
             if self.params.tuning and tune is None:
                 with torch.no_grad():
                     self.update_kernel({'x': run.x.reshape(n, *event_shape), 'mask': mask})
-            done += k
-            bar.update(k)
-        bar.close()
-        calls, grads = self._counts(n, done)
-        run.finish(out, t0, n * done, store, n_target_calls=calls, n_target_gradient_calls=grads,
+        calls, grads = self._counts(n, run.done)
+        run.finish(out, t0, n * run.done, store, n_target_calls=calls, n_target_gradient_calls=grads,
                    n_divergences=self._n_divergences)
         if tune is not None:
             # tuning launches fold their statistics per call: the controller state was final before the finish
@@ -284,32 +277,99 @@ class MCMCSampler(Sampler):
 
     # ---- one transition through the propose() seam (arbitrary targets)
     def _split_step(self, run: Run, step, sample_view):
-        n, d = run.n, run.d
         self._cur_run, self._cur_step = run, step
         x_prime, mask_or_lr, n_calls, n_grads, n_divs = self.propose(run.x)
         self._n_divergences = getattr(self, '_n_divergences', 0) + int(n_divs)
-        st = hip.NfmcSelectArgs()
-        st.x, st.x_prime, st.n, st.d = hip.ptr(run.x), hip.ptr(x_prime), n, d
-        st.n_carry = 0
-        lr = self._last_log_ratio
-        st.log_ratio = hip.ptr(lr) if lr is not None else None
-        un = self._last_uniforms
-        st.uniforms = hip.ptr(un) if un is not None else None
-        st.rng = hip.make_rng(run.seed, run.chain_offset, step, rounds=run.rounds)
-        st.rng_tag = hip.TAG_ACCEPT
-        st.stats = run.stats.struct()
-        mask = torch.empty(n, dtype=torch.uint8, device=run.dev)
-        st.mask_out = hip.ptr(mask, torch.uint8)
-        hip.check(hip.lib().nfmc_mh_accept_select_f32(C.byref(st), hip.stream()), 'nfmc_mh_accept_select_f32')
-        if sample_view is not None:
-            if hasattr(sample_view, 'add_dense'):
-                sample_view.add_dense(run.x[None])
-            else:
-                sample_view[0].copy_(run.x)
+        mask = torch.empty(run.n, dtype=torch.uint8, device=run.dev)
+        accept_select(run, step, x_prime, self._last_log_ratio, self._last_uniforms, hip.TAG_ACCEPT, run.stats.struct(),
+                      mask_out=mask)
+        run.offer_state(sample_view)
         return mask.bool()
+
+    # ---- what the propose() bodies share.  Replay order is draw order: the normal field is taken before the first
+    # target call, the uniforms only once the last one has returned, so a step whose target raised consumes none
+    def _seam(self, x):
+        """Start of propose(): (xf, run, rng) -- the state as (n, d) fp32 on the device, the run whose `_split_step`
+        called (None: stand-alone use of the seam) and the NfmcRng of this transition on the native streams."""
+        xf = x.detach().to(hip.require_gpu(), torch.float32).reshape(x.shape[0], -1).contiguous()
+        run = getattr(self, '_cur_run', None)
+        step = getattr(self, '_cur_step', 0)
+        self._last_log_ratio = self._last_uniforms = None
+        if run is None:
+            return xf, None, hip.make_rng(self.seed or 0, 0, step)
+        return xf, run, hip.make_rng(run.seed, run.chain_offset, step, rounds=run.rounds)
+
+    def _seam_normals(self, xf, run, rng, native=True):
+        """The transition's normal field (langevin.py:63, mh.py:50, hmc.py:100): the next replayed one, which `rng`
+        then also points to, else drawn on the native noise stream -- or None with native=False, for a caller whose
+        kernel draws it from `rng` itself."""
+        if run is not None and run.replay is not None:
+            nz, _ = run.replay.take(1, with_uniforms=False)
+            rng.replay_normals = hip.ptr(nz)
+            return nz[0]
+        if not native:
+            return None
+        noise = torch.empty_like(xf)
+        hip.check(hip.lib().nfmc_philox_normals_f32(C.byref(rng), hip.TAG_NOISE, xf.shape[0], xf.shape[1], hip.ptr(noise),
+                                                    hip.stream()), 'nfmc_philox_normals_f32')
+        return noise
+
+    def _seam_accept(self, xf, run, rng, log_ratio):
+        """End of an adjusted propose(), after its last target call (langevin.py:106, mh.py:59, hmc.py:112): leaves the
+        log ratio, and the replayed uniforms if the run has any, to the accept-select kernel of `_split_step` and returns
+        a placeholder mask; outside a run the mask is evaluated here, on the native accept stream."""
+        n = xf.shape[0]
+        self._last_log_ratio = log_ratio
+        if run is None:
+            unif = torch.empty(n, dtype=torch.float32, device=xf.device)
+            hip.check(hip.lib().nfmc_philox_uniforms_f32(C.byref(rng), hip.TAG_ACCEPT, n, hip.ptr(unif), hip.stream()),
+                      'nfmc_philox_uniforms_f32')
+            return torch.log(unif) < log_ratio
+        if run.replay is not None:
+            self._last_uniforms = run.replay.take_uniforms(1)[0].contiguous()
+        return torch.ones(n, dtype=torch.bool, device=xf.device)
 
 
 class MetropolisSampler(MCMCSampler):
+    # a fused sampler names the args struct of its entry point, the entry point and its timing label, and fills the
+    # struct's fields of its own in _own_args
+    _struct = _entry = _label = None
+
+    def _own_args(self, a):
+        pass
+
+    def _args(self, run, pot, k, step0, samples, masks_out=None, log_ratio_out=None, jump=None, rng=None, tune=None,
+              attempted=None):
+        """NfmcMalaArgs / NfmcHmcArgs of a launch of k transitions (`attempted`: chain-transitions to book with deferred
+        statistics when the struct stands for more launches than one, samplers/jump.py: launch_jump_run)."""
+        a = self._struct()
+        a.x, a.n, a.d, a.n_steps = hip.ptr(run.x), run.n, run.d, k
+        a.step_size = float(self.kernel.step_size)
+        a.adjust = 1 if self.params.adjustment else 0
+        self._own_args(a)
+        imd = tune.imd if tune is not None else imd_tensor(self.kernel, run.dev)
+        a.inv_mass_diag = hip.ptr(imd)
+        a.pot = pot.descriptor(run.dev)
+        # `rng`: an NfmcRng prepared by the caller (replay bookkeeping of fused jump tails)
+        a.rng = rng if rng is not None else run.rng(step0, k, adjusted=self.params.adjustment)
+        if tune is not None:   # the controller rides on the per-call statistics fold
+            a.stats = run.stats.struct()
+            a.tune = tune.struct(getattr(tune, 'every', 0), k)
+        else:
+            a.stats = run.stats.struct(defer=True, attempted=run.n * k if attempted is None else attempted,
+                                       jump_attempted=run.n if jump is not None else 0)
+        a.samples = hip.store_struct(samples, k + (1 if jump is not None else 0))
+        a.masks_out = hip.ptr(masks_out, torch.uint8) if masks_out is not None else None
+        a.log_ratio_out = hip.ptr(log_ratio_out) if log_ratio_out is not None else None
+        a.jump = C.pointer(jump) if jump is not None else None
+        a._keep = imd   # the struct borrows its memory until the launch is enqueued
+        return a
+
+    def _launch(self, run, pot, k, step0, samples, **kw):
+        a = self._args(run, pot, k, step0, samples, **kw)
+        with run.timed(self._label):
+            hip.check(getattr(hip.lib(), self._entry)(C.byref(a), hip.stream()), self._entry)
+
     def update_kernel(self, data: Dict[str, Any]):
         """mcmc/base.py:142-161: EMA of the per-coordinate variance + dual-averaging step size.  With sharded chains
         the variance and the acceptance rate are those of ALL chains (one all-reduce of [sum x, sum x^2, n, accepted]),
@@ -344,6 +404,13 @@ class MetropolisSampler(MCMCSampler):
 
 
 class Langevin(MetropolisSampler):
+    _struct, _entry, _label = hip.NfmcMalaArgs, 'nfmc_mala_steps_f32', 'mala_steps'
+    random_walk = False   # MH: the random-walk proposal of the same kernel (NfmcMalaArgs.adjust bit 1)
+
+    def _own_args(self, a):
+        if self.random_walk:
+            a.adjust |= 2
+
     def __init__(self, event_shape, target, kernel: Optional[LangevinKernel] = None,
                  params: Optional[LangevinParameters] = None):
         if kernel is None:
@@ -360,89 +427,39 @@ class Langevin(MetropolisSampler):
         per = 2 * n if self.params.adjustment else n  # langevin.py:116-120
         return per * k, per * k
 
-    def _args(self, run, pot, k, step0, samples, masks_out=None, log_ratio_out=None, jump=None, rng=None, tune=None,
-              attempted=None):
-        """NfmcMalaArgs of a launch of k transitions (`attempted`: chain-transitions to book with deferred statistics when
-        the struct stands for more launches than one, samplers/jump.py: launch_jump_run)."""
-        a = hip.NfmcMalaArgs()
-        a.x, a.n, a.d, a.n_steps = hip.ptr(run.x), run.n, run.d, k
-        a.step_size = float(self.kernel.step_size)
-        a.adjust = (1 if self.params.adjustment else 0) | (2 if getattr(self, 'random_walk', False) else 0)
-        imd = tune.imd if tune is not None else imd_tensor(self.kernel, run.dev)
-        a.inv_mass_diag = hip.ptr(imd)
-        a.pot = pot.descriptor(run.dev)
-        # `rng`: an NfmcRng prepared by the caller (replay bookkeeping of fused jump tails)
-        a.rng = rng if rng is not None else run.rng(step0, k, adjusted=self.params.adjustment)
-        if tune is not None:   # the controller rides on the per-call statistics fold
-            a.stats = run.stats.struct()
-            a.tune = tune.struct(getattr(tune, 'every', 0), k)
-        else:
-            a.stats = run.stats.struct(defer=True, attempted=run.n * k if attempted is None else attempted,
-                                       jump_attempted=run.n if jump is not None else 0)
-        a.samples = hip.store_struct(samples, k + (1 if jump is not None else 0))
-        a.masks_out = hip.ptr(masks_out, torch.uint8) if masks_out is not None else None
-        a.log_ratio_out = hip.ptr(log_ratio_out) if log_ratio_out is not None else None
-        a.jump = C.pointer(jump) if jump is not None else None
-        a._keep = imd   # the struct borrows its memory
-        return a
-
-    def _launch(self, run, pot, k, step0, samples, **kw):
-        a = self._args(run, pot, k, step0, samples, **kw)
-        with run.timed('mala_steps'):
-            hip.check(hip.lib().nfmc_mala_steps_f32(C.byref(a), hip.stream()), 'nfmc_mala_steps_f32')
-
     def propose(self, x):
         """langevin.py:61-122 for an arbitrary target: autograd U/grad U + HIP proposal and log-ratio.
         Returns (x_prime, mask, n_calls, n_grads, n_divergences); mask is evaluated lazily by the
         accept-select kernel when called from `sample()`."""
-        dev = hip.require_gpu()
-        n = x.shape[0]
-        xf = x.detach().to(dev, torch.float32).reshape(n, -1).contiguous()
-        d = xf.shape[1]
-        run = getattr(self, '_cur_run', None)
-        step = getattr(self, '_cur_step', 0)
-        seed = run.seed if run is not None else (self.seed or 0)
-        off = run.chain_offset if run is not None else 0
+        xf, run, rng = self._seam(x)
+        n, d = xf.shape
+        dev = xf.device
         h = float(self.kernel.step_size)
         imd = imd_tensor(self.kernel, dev)
         lib = hip.lib()
-        nz = un = None
-        if run is not None and run.replay is not None:   # the noise is drawn before the first target call (langevin.py:63)
-            nz, _ = run.replay.take(1, with_uniforms=False)
+        # the proposal kernel draws its noise through `rng`: natively, or from the replayed field `rng` then points to,
+        # which `nz` holds until the kernel is enqueued
+        nz = self._seam_normals(xf, run, rng, native=False)
         per = 2 * n if self.params.adjustment else n     # langevin.py:116-120
         try:
             u, g = _guarded(_value_and_grad, self.target, xf, self.event_shape)
         except TargetFailure:
             return self._rejected_step(xf, per, per)
         x_prime = torch.empty_like(xf)
-        rng = hip.make_rng(seed, off, step, nz, None, rounds=run.rounds if run is not None else 0)
         hip.check(lib.nfmc_langevin_propose_f32(hip.ptr(xf), hip.ptr(g), hip.ptr(imd), h, n, d, C.byref(rng),
                                                 hip.ptr(x_prime), hip.stream()), 'nfmc_langevin_propose_f32')
-        n_calls = n_grads = n
-        self._last_log_ratio = None
-        self._last_uniforms = None
-        mask = torch.ones(n, dtype=torch.bool, device=dev)
-        if self.params.adjustment:
-            try:
-                up, gp = _guarded(_value_and_grad, self.target, x_prime, self.event_shape)
-            except TargetFailure:
-                return self._rejected_step(xf, per, per)
-            if nz is not None:
-                un = run.replay.take_uniforms(1)              # drawn after the second target call (langevin.py:106)
-                self._last_uniforms = un[0].contiguous()
-            lr = torch.empty(n, dtype=torch.float32, device=dev)
-            hip.check(lib.nfmc_langevin_log_ratio_f32(hip.ptr(xf), hip.ptr(x_prime), hip.ptr(u), hip.ptr(up),
-                                                      hip.ptr(g), hip.ptr(gp), hip.ptr(imd), h, n, d, hip.ptr(lr),
-                                                      hip.stream()), 'nfmc_langevin_log_ratio_f32')
-            self._last_log_ratio = lr
-            n_calls += n
-            n_grads += n
-            if run is None:  # stand-alone use of the seam: evaluate the mask here
-                unif = torch.empty(n, dtype=torch.float32, device=dev)
-                hip.check(lib.nfmc_philox_uniforms_f32(C.byref(rng), hip.TAG_ACCEPT, n, hip.ptr(unif), hip.stream()),
-                          'nfmc_philox_uniforms_f32')
-                mask = torch.log(unif) < lr
-        return x_prime, mask, n_calls, n_grads, 0
+        del nz
+        if not self.params.adjustment:
+            return x_prime, torch.ones(n, dtype=torch.bool, device=dev), n, n, 0
+        try:
+            up, gp = _guarded(_value_and_grad, self.target, x_prime, self.event_shape)
+        except TargetFailure:
+            return self._rejected_step(xf, per, per)
+        lr = torch.empty(n, dtype=torch.float32, device=dev)
+        hip.check(lib.nfmc_langevin_log_ratio_f32(hip.ptr(xf), hip.ptr(x_prime), hip.ptr(u), hip.ptr(up),
+                                                  hip.ptr(g), hip.ptr(gp), hip.ptr(imd), h, n, d, hip.ptr(lr),
+                                                  hip.stream()), 'nfmc_langevin_log_ratio_f32')
+        return x_prime, self._seam_accept(xf, run, rng, lr), 2 * n, 2 * n, 0
 
 
 class MALA(Langevin):
@@ -496,46 +513,19 @@ class MH(Langevin):
 
     def propose(self, x):
         """mh.py:44-73 for an arbitrary target (split path)."""
-        dev = hip.require_gpu()
-        n = x.shape[0]
-        xf = x.detach().to(dev, torch.float32).reshape(n, -1).contiguous()
-        d = xf.shape[1]
-        run = getattr(self, '_cur_run', None)
-        step = getattr(self, '_cur_step', 0)
-        seed = run.seed if run is not None else (self.seed or 0)
-        off = run.chain_offset if run is not None else 0
-        replayed = run is not None and run.replay is not None
-        if replayed:
-            nz, _ = run.replay.take(1, with_uniforms=False)
-            noise = nz[0]
-        else:
-            noise = torch.empty(n, d, dtype=torch.float32, device=dev)
-            rng = hip.make_rng(seed, off, step, rounds=run.rounds if run is not None else 0)
-            hip.check(hip.lib().nfmc_philox_normals_f32(C.byref(rng), hip.TAG_NOISE, n, d, hip.ptr(noise), hip.stream()),
-                      'nfmc_philox_normals_f32')
-        x_prime = (xf + noise * self.kernel.inv_mass_diag.to(dev, torch.float32)[None]).contiguous()
-        self._last_log_ratio = None
-        self._last_uniforms = None
-        mask = torch.ones(n, dtype=torch.bool, device=dev)
-        n_calls = 0
-        if self.params.adjustment:
-            try:
-                with torch.no_grad():
-                    lr = (_guarded(self.target, xf.reshape(n, *self.event_shape)).reshape(-1)
-                          - _guarded(self.target, x_prime.reshape(n, *self.event_shape)).reshape(-1))
-            except TargetFailure:
-                return self._rejected_step(xf, 2 * n, 0)      # mh.py:63-71
-            self._last_log_ratio = lr.float().contiguous()
-            if replayed:
-                self._last_uniforms = run.replay.take_uniforms(1)[0].contiguous()   # mh.py:59, after both target calls
-            n_calls = 2 * n
-            if run is None:
-                unif = torch.empty(n, dtype=torch.float32, device=dev)
-                rng = hip.make_rng(seed, off, step, rounds=run.rounds if run is not None else 0)
-                hip.check(hip.lib().nfmc_philox_uniforms_f32(C.byref(rng), hip.TAG_ACCEPT, n, hip.ptr(unif), hip.stream()),
-                          'nfmc_philox_uniforms_f32')
-                mask = torch.log(unif) < self._last_log_ratio
-        return x_prime, mask, n_calls, 0, 0
+        xf, run, rng = self._seam(x)
+        n = xf.shape[0]
+        noise = self._seam_normals(xf, run, rng)
+        x_prime = (xf + noise * self.kernel.inv_mass_diag.to(xf.device, torch.float32)[None]).contiguous()
+        if not self.params.adjustment:
+            return x_prime, torch.ones(n, dtype=torch.bool, device=xf.device), 0, 0, 0
+        try:
+            with torch.no_grad():
+                lr = (_guarded(self.target, xf.reshape(n, *self.event_shape)).reshape(-1)
+                      - _guarded(self.target, x_prime.reshape(n, *self.event_shape)).reshape(-1))
+        except TargetFailure:
+            return self._rejected_step(xf, 2 * n, 0)      # mh.py:63-71
+        return x_prime, self._seam_accept(xf, run, rng, lr.float().contiguous()), 2 * n, 0, 0
 
 
 class RandomWalk(MH):
@@ -545,6 +535,11 @@ class RandomWalk(MH):
 
 
 class HMC(MetropolisSampler):
+    _struct, _entry, _label = hip.NfmcHmcArgs, 'nfmc_hmc_steps_f32', 'hmc_steps'
+
+    def _own_args(self, a):
+        a.n_leapfrog = int(self.kernel.n_leapfrog_steps)
+
     def __init__(self, event_shape, target, kernel: Optional[HMCKernel] = None,
                  params: Optional[HMCParameters] = None):
         if kernel is None:
@@ -562,60 +557,13 @@ class HMC(MetropolisSampler):
         calls = grads + (2 * n if self.params.adjustment else 0)
         return calls * k, grads * k
 
-    def _args(self, run, pot, k, step0, samples, masks_out=None, log_ratio_out=None, jump=None, rng=None, tune=None,
-              attempted=None):
-        """NfmcHmcArgs of a launch of k trajectories (`attempted` as in Langevin._args)."""
-        a = hip.NfmcHmcArgs()
-        a.x, a.n, a.d, a.n_steps = hip.ptr(run.x), run.n, run.d, k
-        a.step_size = float(self.kernel.step_size)
-        a.n_leapfrog = int(self.kernel.n_leapfrog_steps)
-        a.adjust = 1 if self.params.adjustment else 0
-        imd = tune.imd if tune is not None else imd_tensor(self.kernel, run.dev)
-        a.inv_mass_diag = hip.ptr(imd)
-        a.pot = pot.descriptor(run.dev)
-        # `rng`: an NfmcRng prepared by the caller (replay bookkeeping of fused jump tails)
-        a.rng = rng if rng is not None else run.rng(step0, k, adjusted=self.params.adjustment)
-        if tune is not None:   # the controller rides on the per-call statistics fold
-            a.stats = run.stats.struct()
-            a.tune = tune.struct(getattr(tune, 'every', 0), k)
-        else:
-            a.stats = run.stats.struct(defer=True, attempted=run.n * k if attempted is None else attempted,
-                                       jump_attempted=run.n if jump is not None else 0)
-        a.samples = hip.store_struct(samples, k + (1 if jump is not None else 0))
-        a.masks_out = hip.ptr(masks_out, torch.uint8) if masks_out is not None else None
-        a.log_ratio_out = hip.ptr(log_ratio_out) if log_ratio_out is not None else None
-        a.jump = C.pointer(jump) if jump is not None else None
-        a._keep = imd   # the struct borrows its memory
-        return a
-
-    def _launch(self, run, pot, k, step0, samples, **kw):
-        a = self._args(run, pot, k, step0, samples, **kw)
-        with run.timed('hmc_steps'):
-            hip.check(hip.lib().nfmc_hmc_steps_f32(C.byref(a), hip.stream()), 'nfmc_hmc_steps_f32')
-
     def propose(self, x):
         """hmc.py:96-126 for an arbitrary target: leapfrog with autograd gradients on the GPU."""
-        dev = hip.require_gpu()
-        n = x.shape[0]
-        xf = x.detach().to(dev, torch.float32).reshape(n, -1).contiguous()
-        d = xf.shape[1]
-        run = getattr(self, '_cur_run', None)
-        step = getattr(self, '_cur_step', 0)
-        seed = run.seed if run is not None else (self.seed or 0)
-        off = run.chain_offset if run is not None else 0
+        xf, run, rng = self._seam(x)
+        n = xf.shape[0]
         h = float(self.kernel.step_size)
-        m = self.kernel.inv_mass_diag.to(dev, torch.float32)
-        lib = hip.lib()
-        replayed = run is not None and run.replay is not None
-        if replayed:
-            nz, _ = run.replay.take(1, with_uniforms=False)
-            noise = nz[0]
-        else:
-            noise = torch.empty(n, d, dtype=torch.float32, device=dev)
-            rng = hip.make_rng(seed, off, step, rounds=run.rounds if run is not None else 0)
-            hip.check(lib.nfmc_philox_normals_f32(C.byref(rng), hip.TAG_NOISE, n, d, hip.ptr(noise), hip.stream()),
-                      'nfmc_philox_normals_f32')
-        p = noise * (1 / m.sqrt())
+        m = self.kernel.inv_mass_diag.to(xf.device, torch.float32)
+        p = self._seam_normals(xf, run, rng) * (1 / m.sqrt())
         p0 = p
         q = xf
         L = self.kernel.n_leapfrog_steps
@@ -645,31 +593,18 @@ class HMC(MetropolisSampler):
                     p = p - h / 2 * _guarded(_value_and_grad, self.target, q, self.event_shape)[1]
         except TargetFailure:
             return self._rejected_step(xf, n_calls, n_grads)  # hmc.py:117-120
-        n_calls = n_grads
-        self._last_log_ratio = None
-        self._last_uniforms = None
-        mask = torch.ones(n, dtype=torch.bool, device=dev)
-        if self.params.adjustment:
-            try:
-                with torch.no_grad():
-                    if not merged:
-                        u0 = _guarded(self.target, xf.reshape(n, *self.event_shape)).reshape(-1)
-                        u1 = _guarded(self.target, q.reshape(n, *self.event_shape)).reshape(-1)
-                    h0 = u0.reshape(-1) + 0.5 * (p0 ** 2 * m).sum(-1)
-                    h1 = u1.reshape(-1) + 0.5 * (p ** 2 * m).sum(-1)
-            except TargetFailure:
-                return self._rejected_step(xf, n_grads + 2 * n, n_grads)
-            self._last_log_ratio = (h0 - h1).float().contiguous()
-            if replayed:
-                self._last_uniforms = run.replay.take_uniforms(1)[0].contiguous()   # hmc.py:112, after both target calls
-            n_calls += 2 * n
-            if run is None:
-                unif = torch.empty(n, dtype=torch.float32, device=dev)
-                rng = hip.make_rng(seed, off, step, rounds=run.rounds if run is not None else 0)
-                hip.check(lib.nfmc_philox_uniforms_f32(C.byref(rng), hip.TAG_ACCEPT, n, hip.ptr(unif), hip.stream()),
-                          'nfmc_philox_uniforms_f32')
-                mask = torch.log(unif) < self._last_log_ratio
-        return q.contiguous(), mask, n_calls, n_grads, 0
+        if not self.params.adjustment:
+            return q.contiguous(), torch.ones(n, dtype=torch.bool, device=xf.device), n_grads, n_grads, 0
+        try:
+            with torch.no_grad():
+                if not merged:
+                    u0 = _guarded(self.target, xf.reshape(n, *self.event_shape)).reshape(-1)
+                    u1 = _guarded(self.target, q.reshape(n, *self.event_shape)).reshape(-1)
+                h0 = u0.reshape(-1) + 0.5 * (p0 ** 2 * m).sum(-1)
+                h1 = u1.reshape(-1) + 0.5 * (p ** 2 * m).sum(-1)
+        except TargetFailure:
+            return self._rejected_step(xf, n_calls, n_grads)
+        return q.contiguous(), self._seam_accept(xf, run, rng, (h0 - h1).float().contiguous()), n_calls, n_grads, 0
 
 
 class UHMC(HMC):

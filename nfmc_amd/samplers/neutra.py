@@ -19,10 +19,9 @@ from tqdm import tqdm
 
 from .. import hip
 from ..containers import MCMCOutput, NFMCKernel, NFMCParameters, Sampler
-from ..potentials import (DiffusionBridge, FullRankGaussian, Funnel, ItemResponseTheory, LatentGaussianModel, LatentGMRF,
-                          LatticePhi4, ParticleSystem, QuadraticPotential, Rosenbrock, SparseLogisticRegression, StochasticVolatility,
-                          VaryingEffectsRegression)
-from .common import Run, chunks, imd_tensor, progress, resolve_target
+from ..potentials import (DiffusionBridge, FullRankGaussian, Funnel, LatticePhi4, ParticleSystem, QuadraticPotential,
+                          Rosenbrock, StochasticVolatility, VaryingEffectsRegression)
+from .common import Run, imd_tensor, launch_limit, progress, resolve_target
 from .mcmc import (HMC, MH, HMCKernel, HMCParameters, MHKernel, MHParameters, MetropolisKernel, MetropolisParameters,
                    MetropolisSampler)
 
@@ -109,13 +108,10 @@ class NeuTra(Sampler):
     def _min_hidden(self):
         """Conditioner width to present to the kernels: d = 64 / 128 with one or two hidden layers runs on the
         matrix cores (csrc/neutra_mfma.hip) also when the flow's own conditioner is narrow (zero-padded).  The matrix-core
-        kernels evaluate quadratic and funnel targets only: a FullRankGaussian, a Rosenbrock, a StochasticVolatility, a
-        SparseLogisticRegression, a LatticePhi4, an ItemResponseTheory, a VaryingEffectsRegression, a ParticleSystem, a
-        LatentGaussianModel, a LatentGMRF or a DiffusionBridge keeps the flow's own width (VALU kernels).  The sparse
-        regression has an odd d = 2 D + 1, so it never reaches the d = 64 / 128 test below; it is listed all the same."""
-        if isinstance(self.target, (FullRankGaussian, Rosenbrock, StochasticVolatility, SparseLogisticRegression, LatticePhi4,
-                                    ItemResponseTheory, VaryingEffectsRegression, ParticleSystem, LatentGaussianModel,
-                                    LatentGMRF, DiffusionBridge)):
+        kernels evaluate quadratic and funnel targets only: a potential class that says so (`neutra_matrix_cores = False`,
+        nfmc_amd/potentials.py) keeps the flow's own width (VALU kernels).  The question goes to the target as given, not to
+        its resolved descriptor: a plain callable that is recognised as a quadratic takes the matrix cores."""
+        if not getattr(self.target, 'neutra_matrix_cores', True):
             return 0
         bij = self.kernel.flow.bijection
         ok = (getattr(bij, 'd', 0) in (64, 128) and getattr(bij, 'n_hidden_layers', 0) in (1, 2)
@@ -169,8 +165,8 @@ class NeuTra(Sampler):
         inner.params.thinning = getattr(self.params, 'thinning', 1)
         inner.params.max_samples = getattr(self.params, 'max_samples', None)
         run = Run(self, x0)
-        n, d, event_shape = run.n, run.d, run.event_shape
-        pot = resolve_target(self.target, event_shape, self.fuse, family='neutra')
+        pot = resolve_target(self.target, run.event_shape, self.fuse, family='neutra')
+
         def split():
             # arbitrary targets / shapes without a fused kernel: the inner sampler's split path on the
             # adjusted target (neutra.py:116-127)
@@ -187,109 +183,80 @@ class NeuTra(Sampler):
             return self._sample_mh(run, pot, split, show_progress, time_limit_seconds)
         if not isinstance(inner, HMC) or pot is None or not self._flow_on_kernels():
             return split()
-        out = MCMCOutput(event_shape, kernel=inner.kernel, store_samples=self.params.store_samples,
-                         max_samples=getattr(self.params, 'max_samples', None))
-        T = int(self.params.n_iterations)
-        store = run.sample_store(T)
-        st_flow, _keep = self.kernel.flow.bijection.packed(run.dev, self._min_hidden())
-        imd = imd_tensor(inner.kernel, run.dev)
-        bij = self.kernel.flow.bijection
-        sbytes = int(hip.lib().nfmc_neutra_scratch_bytes(n, d, max(bij.n_hidden, self._min_hidden()), int(st_flow.n_hidden_layers),
-                                                         int(st_flow.n_coupling)))
-        scratch = torch.empty(max(sbytes // 4, 1), dtype=torch.float32, device=run.dev)
-        if os.environ.get('NFMC_KEEP_SCRATCH'):   # diagnostics only (tools/trace_c4.py reads the marks of a trace build from its tail)
-            self._scratch = scratch
-        t0 = time.time()
-        done = 0
-        limit = hip.MAX_STEPS_PER_CALL if (time_limit_seconds is None and not show_progress) else 4
-        bar = progress(show_progress, total=T, desc='NeuTra HMC')
-        while done < T:
-            if run.time_is_up(t0, time_limit_seconds):
-                break
-            k = min(limit, T - done)
-            a = hip.NfmcNeutraHmcArgs()
-            a.z, a.n, a.n_steps = hip.ptr(run.x), n, k
-            a.n_leapfrog = int(inner.kernel.n_leapfrog_steps)
-            a.step_size = float(inner.kernel.step_size)
-            a.adjust = 1 if inner.params.adjustment else 0
-            a.inv_mass_diag = hip.ptr(imd)
-            a.flow = st_flow
-            a.pot = pot.descriptor(run.dev)
-            a.rng = run.rng(done, k, adjusted=inner.params.adjustment)
-            a.stats = run.stats.struct()
-            seen_before = store.seen if store is not None else 0
-            a.samples = hip.store_struct(store, k)
-            a.scratch, a.scratch_bytes = hip.ptr(scratch), sbytes
-            try:
-                with run.timed('neutra_hmc_steps'):
-                    hip.check(hip.lib().nfmc_neutra_hmc_steps_f32(C.byref(a), hip.stream()), 'nfmc_neutra_hmc_steps_f32')
-            except hip.NfmcArgumentError as e:
-                if done == 0 and e.no_kernel and run.rounds == 10:   # validation precedes every launch: nothing has run yet
-                    bar.close()
-                    return split()
-                if store is not None:
-                    store.seen = seen_before
-                raise
-            done += k
-            bar.update(k)
-        bar.close()
-        calls, grads = inner._counts(n, done)
-        run.finish(out, t0, n * done, store, n_target_calls=calls, n_target_gradient_calls=grads)
-        out.kernel.flow = self.kernel.flow  # neutra.py:128
-        return out
+        return self._kernel_route(run, pot, split, show_progress, time_limit_seconds, struct=hip.NfmcNeutraHmcArgs,
+                                  entry='nfmc_neutra_hmc_steps_f32', label='neutra_hmc_steps', desc='NeuTra HMC',
+                                  hidden=self._min_hidden(), scratch=True,
+                                  own=(('n_leapfrog', int(inner.kernel.n_leapfrog_steps)),
+                                       ('step_size', float(inner.kernel.step_size))))
 
     def _mh_on_kernel(self, pot, rounds):
         """Whether a run with an MH inner sampler goes to nfmc_neutra_mh_steps_f32: a closed-form potential of the NeuTra
-        family whose kind was measured no slower on the kernel (`mh_kernel_kinds`), a flow the kernels take, the default Philox rounds and the flow's own conditioner at most 32 wide (there is
-        no matrix-core MH kernel, so the padding of `_min_hidden` is not borrowed).  Everything else keeps the inner
-        sampler's split path."""
+        family whose kind was measured no slower on the kernel (`mh_kernel_kinds`), a flow the kernels take, the default
+        Philox rounds and the flow's own conditioner at most 32 wide (there is no matrix-core MH kernel, so the padding
+        of `_min_hidden` is not borrowed).  Everything else keeps the inner sampler's split path."""
         return (pot is not None and isinstance(pot, self.mh_kernel_kinds) and self._flow_on_kernels() and rounds == 10
                 and int(self.kernel.flow.bijection.n_hidden) <= 32)
 
     def _sample_mh(self, run, pot, split, show_progress, time_limit_seconds):
         """neutra.py:147-159 with mh.py:44-73 on the device: proposal, flow inverse, potential value, Metropolis test,
-        statistics and sample store of up to MAX_STEPS_PER_CALL transitions in one launch of neutra_mh_kernel."""
+        statistics and sample store of up to MAX_STEPS_PER_CALL transitions in one launch of neutra_mh_kernel, on the
+        flow's own width (the kernel is a VALU one)."""
+        return self._kernel_route(run, pot, split, show_progress, time_limit_seconds, struct=hip.NfmcNeutraMhArgs,
+                                  entry='nfmc_neutra_mh_steps_f32', label='neutra_mh_steps', desc='NeuTra MH', hidden=0)
+
+    def _kernel_route(self, run, pot, split, show_progress, time_limit_seconds, *, struct, entry, label, desc, hidden,
+                      own=(), scratch=False):
+        """A run on one of the NeuTra kernels: launches of `entry` on a `struct` until n_iterations transitions are done
+        or the time is up, then the counts and the finish.  `label` names the launch for kernel timing, `desc` the
+        progress bar; `hidden`: the conditioner width the flow is packed to; `own`: (field, value) pairs of the struct
+        beside the shared fields; `scratch`: the entry point takes a work area (nfmc_neutra_scratch_bytes)."""
         inner = self.inner_sampler
         n = run.n
         out = MCMCOutput(run.event_shape, kernel=inner.kernel, store_samples=self.params.store_samples,
                          max_samples=getattr(self.params, 'max_samples', None))
         T = int(self.params.n_iterations)
         store = run.sample_store(T)
-        st_flow, _keep = self.kernel.flow.bijection.packed(run.dev, 0)   # the flow's own width: the kernel is a VALU one
+        # the struct borrows the packed flow, the mass diagonal and the work area: referenced here until the run's end
+        st_flow, _keep = self.kernel.flow.bijection.packed(run.dev, hidden)
         imd = imd_tensor(inner.kernel, run.dev)
+        if scratch:
+            sbytes = int(hip.lib().nfmc_neutra_scratch_bytes(n, run.d, max(self.kernel.flow.bijection.n_hidden, hidden),
+                                                             int(st_flow.n_hidden_layers), int(st_flow.n_coupling)))
+            work = torch.empty(max(sbytes // 4, 1), dtype=torch.float32, device=run.dev)
+            own = (*own, ('scratch', hip.ptr(work)), ('scratch_bytes', sbytes))
+            if os.environ.get('NFMC_KEEP_SCRATCH'):   # diagnostics only (tools/trace_c4.py reads the marks of a trace build from its tail)
+                self._scratch = work
+        steps = getattr(hip.lib(), entry)
         t0 = time.time()
-        done = 0
-        limit = hip.MAX_STEPS_PER_CALL if (time_limit_seconds is None and not show_progress) else 4
-        bar = progress(show_progress, total=T, desc='NeuTra MH')
-        while done < T:
-            if run.time_is_up(t0, time_limit_seconds):
-                break
-            k = min(limit, T - done)
-            a = hip.NfmcNeutraMhArgs()
+        bar = progress(show_progress, total=T, desc=desc)
+        for done, k in run.launches(T, launch_limit(4, show_progress, time_limit_seconds), t0, time_limit_seconds, bar):
+            a = struct()
             a.z, a.n, a.n_steps = hip.ptr(run.x), n, k
             a.adjust = 1 if inner.params.adjustment else 0
             a.inv_mass_diag = hip.ptr(imd)
             a.flow = st_flow
             a.pot = pot.descriptor(run.dev)
+            for field, value in own:
+                setattr(a, field, value)
             a.rng = run.rng(done, k, adjusted=inner.params.adjustment)
             a.stats = run.stats.struct()
             seen_before = store.seen if store is not None else 0
             a.samples = hip.store_struct(store, k)
             try:
-                with run.timed('neutra_mh_steps'):
-                    hip.check(hip.lib().nfmc_neutra_mh_steps_f32(C.byref(a), hip.stream()), 'nfmc_neutra_mh_steps_f32')
+                with run.timed(label):
+                    hip.check(steps(C.byref(a), hip.stream()), entry)
             except hip.NfmcArgumentError as e:
+                # validation precedes every launch, so nothing has run: the store forgets the offer, and a first launch that
+                # found no kernel hands the run to the split path.  Only on the default Philox rounds: the split path must
+                # not silently answer for the other stream (the MH route is entered at 10 rounds only)
                 if store is not None:
                     store.seen = seen_before
-                if done == 0 and e.no_kernel:   # validation precedes every launch: nothing has run yet
+                if done == 0 and e.no_kernel and run.rounds == 10:
                     bar.close()
                     return split()
                 raise
-            done += k
-            bar.update(k)
-        bar.close()
-        calls, grads = inner._counts(n, done)
-        run.finish(out, t0, n * done, store, n_target_calls=calls, n_target_gradient_calls=grads)
+        calls, grads = inner._counts(n, run.done)
+        run.finish(out, t0, n * run.done, store, n_target_calls=calls, n_target_gradient_calls=grads)
         out.kernel.flow = self.kernel.flow  # neutra.py:128
         return out
 

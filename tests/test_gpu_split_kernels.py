@@ -238,12 +238,26 @@ def test_log_ratio_nonfinite_and_argument_errors(dev):
         assert _log_ratio(hip, t, bad, n, d, out) == hip.EINVAL
 
 
-def test_langevin_propose_seam_stand_alone(dev):
-    """Langevin.propose outside a run (native Philox, d = 300, a mass vector, a callable quadratic target): the oracle's
-    x_prime inside the native proposal bound, and the oracle's mask on every row outside the near-tie margin."""
-    from nfmc_amd.samplers.mcmc import Langevin, LangevinKernel
+L_SEAM = 2    # leapfrog steps of the HMC case
+
+
+@pytest.mark.parametrize('kind, h, seed', [('langevin', 0.02, 4242), ('mh', 0.05, 4244), ('hmc', 0.75, 4242)])
+def test_langevin_propose_seam_stand_alone(dev, kind, h, seed):
+    """Langevin.propose, MH.propose and HMC.propose (2 leapfrog steps) outside a run (native Philox, d = 300, a mass
+    vector, a callable quadratic target):
+      x_prime bit-identical to the state the same sampler's in-run split path proposes in its first transition
+        (fuse='never', same seed, one iteration, `propose` wrapped to record what it returns): the same code on the same
+        Philox stream, so no tolerance; for Langevin also the oracle's x_prime inside the native proposal bound;
+      the counters the reference's formulas: Langevin (2n, 2n, 0), MH (2n, 0, 0), HMC (2 L n + 2n, 2 L n, 0);
+      the oracle's mask (PhiloxNoise(seed, 0)) on every row outside the near-tie margin.
+    MH has no step size: its proposal scale is the mass vector, so that case scales the vector by h.  The MH and HMC
+    seeds and step sizes were picked on the CPU, from the fp64 oracle alone (seeds 4242 .. 4249, a few h each): such that
+    the oracle leaves no row out as a near-tie, accepts some rows but not all (MH 113, HMC 202 of 256), and its smallest
+    |log u - log ratio| / max(1, |log u|) is 0.023 (MH) and 0.091 (HMC), far above the ~1e-4 that fp32 sums of U ~ 300
+    can move the device's log ratio."""
+    from nfmc_amd.samplers import mcmc
     from oracle import samplers as osamp
-    n, d, h, seed = 256, 300, 0.02, 4242
+    n, d = 256, 300
     gen = torch.Generator().manual_seed(9)
     imd = ref.mass_vector(d, gen)
     x = torch.randn(n, d, generator=gen).float()
@@ -251,25 +265,63 @@ def test_langevin_propose_seam_stand_alone(dev):
     def target(v):
         return (v * v).sum(-1)
 
-    s = Langevin((d,), target, kernel=LangevinKernel(event_size=d, step_size=h, inv_mass_diag=torch.from_numpy(imd)))
+    noise = osamp.PhiloxNoise(seed, 0, dtype=torch.float64)
+    if kind == 'langevin':
+        def make():
+            return mcmc.Langevin((d,), target, kernel=mcmc.LangevinKernel(event_size=d, step_size=h,
+                                                                           inv_mass_diag=torch.from_numpy(imd)))
+        counters = (2 * n, 2 * n, 0)
+        want_xp, want_mask, lr, log_u = osamp.langevin_propose(x.double(), target, ref.h32(h),
+                                                               torch.from_numpy(imd).double(), True, noise, 0)
+    elif kind == 'mh':
+        imd = (np.float32(h) * imd).astype(np.float32)
+
+        def make():
+            return mcmc.MH((d,), target, kernel=mcmc.MHKernel(event_size=d, inv_mass_diag=torch.from_numpy(imd)))
+        counters = (2 * n, 0, 0)
+        want_xp, want_mask, lr, log_u = osamp.mh_propose(x.double(), target, torch.from_numpy(imd).double(), True, noise, 0)
+    else:
+        def make():
+            return mcmc.HMC((d,), target, kernel=mcmc.HMCKernel(event_size=d, step_size=h, n_leapfrog_steps=L_SEAM,
+                                                                 inv_mass_diag=torch.from_numpy(imd)))
+        counters = (2 * L_SEAM * n + 2 * n, 2 * L_SEAM * n, 0)
+        want_xp, want_mask, lr, log_u = osamp.hmc_propose(x.double(), target, ref.h32(h), torch.from_numpy(imd).double(),
+                                                          L_SEAM, True, noise, 0)
+    s = make()
     s.seed = seed
     xp, mask, n_calls, n_grads, n_div = s.propose(x.to(dev))
-    assert (n_calls, n_grads, n_div) == (2 * n, 2 * n, 0)
-    info = {}
-    want_xp, want_mask, lr, log_u = osamp.langevin_propose(x.double(), target, ref.h32(h), torch.from_numpy(imd).double(),
-                                                           True, osamp.PhiloxNoise(seed, 0, dtype=torch.float64), 0,
-                                                           info=info)
-    zn = philox.normal_field(seed, np.arange(n), 0, d, philox.TAG_NOISE)
-    bound = ref.propose_bound(x.numpy(), (2 * x).numpy(), imd, h, zn, native=True)
-    ratio = np.abs(xp.cpu().numpy().astype(np.float64) - want_xp.numpy()) / bound
-    assert (ratio <= 1.0).all(), ratio.max()
+    assert (n_calls, n_grads, n_div) == counters
+
+    # the first transition of the in-run split path
+    r = make()
+    r.seed, r.fuse = seed, 'never'
+    r.params.n_iterations = 1
+    proposed, inner = [], r.propose
+
+    def recording(v):
+        proposed.append(inner(v))
+        return proposed[-1]
+
+    r.propose = recording
+    r.sample(x, show_progress=False)
+    assert len(proposed) == 1 and proposed[0][2:] == counters
+    assert torch.equal(xp, proposed[0][0])
+
+    worst = math.nan   # x_prime is held against the oracle for Langevin only
+    if kind == 'langevin':
+        zn = philox.normal_field(seed, np.arange(n), 0, d, philox.TAG_NOISE)
+        bound = ref.propose_bound(x.numpy(), (2 * x).numpy(), imd, h, zn, native=True)
+        ratio = np.abs(xp.cpu().numpy().astype(np.float64) - want_xp.numpy()) / bound
+        assert (ratio <= 1.0).all(), ratio.max()
+        worst = ratio.max()
     lu, lr = log_u.numpy(), lr.numpy()
     keep = np.abs(lu - lr) >= ref.TIE_MARGIN * np.maximum(1.0, np.abs(lu))
+    print('%s.propose stand-alone: worst x_prime |err| / bound = %.3g, rows left out as near-ties: %d of %d, the oracle '
+          'accepts %d, mask rows that differ: %d' % (kind, worst, int((~keep).sum()), n, int(want_mask.sum()),
+                                                     int((mask.cpu().numpy() != want_mask.numpy()).sum())))
     assert keep.mean() >= 0.999
     np.testing.assert_array_equal(mask.cpu().numpy()[keep], want_mask.numpy()[keep])
     assert 0 < int(want_mask.sum()) < n
-    print('Langevin.propose stand-alone: worst x_prime |err| / bound = %.3g, rows left out as near-ties: %d of %d'
-          % (ratio.max(), int((~keep).sum()), n))
 
 
 # ================================================================================================ K6
