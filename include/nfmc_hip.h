@@ -774,6 +774,52 @@ int nfmc_langevin_log_ratio_f32(const float* x, const float* x_prime, const floa
 /* K7 alone: sum_x += sum_rows x, sum_x2 += sum_rows x^2 over a (rows, d) block. */
 int nfmc_moments_update_f32(const float* x, int64_t rows, int32_t d, const NfmcStats* stats, nfmc_stream_t stream);
 
+/* ---- convergence diagnostics of the kept states (split R-hat, nested R-hat, ESS): the per-chain part on the device.
+ * x holds n_draws kept states of n chains in chronological order, row t = n * d contiguous floats.  For every
+ * (chain j, coordinate c) series the kernel takes the mean m_j (fp64), the biased autocovariances about it
+ * a_{j,l} = (1 / n_draws) sum_{t < n_draws - l} (x_t - m_j)(x_{t+l} - m_j), l = 0 .. max_lag (fp32 products of the
+ * centred draws, lagged operands from a window held on chip; lags >= n_draws are empty sums = 0), the means m_h and
+ * unbiased variances s2_h of the two half-chains [0, h) and [n_draws - h, n_draws), h = n_draws / 2, and, per superchain k
+ * of `group` consecutive chains, mu_k = mean of its m_j and Bt_k = their unbiased variance (0 when group = 1).  `sums`
+ * receives per-coordinate fp64 totals, NFMC_DIAG_* + max_lag + 1 rows of d doubles:
+ *     row NFMC_DIAG_SUM_M       sum_j m_j               row NFMC_DIAG_SUM_M2      sum_j m_j^2
+ *     row NFMC_DIAG_SUM_MH      sum_h m_h (2n halves)   row NFMC_DIAG_SUM_MH2     sum_h m_h^2
+ *     row NFMC_DIAG_SUM_S2H     sum_h s2_h
+ *     row NFMC_DIAG_SUM_MU      sum_k mu_k              row NFMC_DIAG_SUM_MU2     sum_k mu_k^2
+ *     row NFMC_DIAG_SUM_BT      sum_k Bt_k
+ *     row NFMC_DIAG_ACOV + l    sum_j a_{j,l}           (sum_j s2_j = row NFMC_DIAG_ACOV * n_draws / (n_draws - 1))
+ * Every row is additive over disjoint sets of chains (whole superchains), so shards combine by one sum.  The totals are
+ * folded in a fixed order through `work` (no atomics: the same input gives the same bits); `sums` is overwritten.  The
+ * slab is read twice (means, centred products).  NFMC_EINVAL: NULL pointer, non-positive size, n_draws < 4, max_lag < 0,
+ * group < 1 or not dividing n; NFMC_ESHAPE: d > 1024 or max_lag > NFMC_DIAG_MAX_LAG; NFMC_ESCRATCH: work too small. */
+#define NFMC_DIAG_MAX_LAG 127
+enum {
+    NFMC_DIAG_SUM_M = 0,
+    NFMC_DIAG_SUM_M2 = 1,
+    NFMC_DIAG_SUM_MH = 2,
+    NFMC_DIAG_SUM_MH2 = 3,
+    NFMC_DIAG_SUM_S2H = 4,
+    NFMC_DIAG_SUM_MU = 5,
+    NFMC_DIAG_SUM_MU2 = 6,
+    NFMC_DIAG_SUM_BT = 7,
+    NFMC_DIAG_ACOV = 8
+};
+typedef struct {
+    const float* x;           /* (n_draws, n, d) */
+    int64_t n_draws;
+    int64_t n;
+    int32_t d;
+    int32_t max_lag;          /* 0 .. NFMC_DIAG_MAX_LAG */
+    int32_t group;            /* chains per superchain; divides n */
+    int32_t reserved;
+    double* sums;             /* out: nfmc_diag_sums_doubles(d, max_lag) doubles */
+    void* work;               /* device scratch, 8-byte aligned, no initialisation needed */
+    int64_t work_bytes;       /* >= nfmc_diag_work_bytes(n, d, max_lag) */
+} NfmcDiagArgs;
+int64_t nfmc_diag_sums_doubles(int32_t d, int32_t max_lag);            /* 0 for arguments out of range */
+int64_t nfmc_diag_work_bytes(int64_t n, int32_t d, int32_t max_lag);   /* 0 for arguments out of range */
+int nfmc_chain_diagnostics_f32(const NfmcDiagArgs* args, nfmc_stream_t stream);
+
 /* Philox normals / uniforms alone (tests pin the native stream against oracle/philox.py). */
 int nfmc_philox_normals_f32(const NfmcRng* rng, int32_t tag, int64_t n, int32_t d, float* out, nfmc_stream_t stream);
 int nfmc_philox_uniforms_f32(const NfmcRng* rng, int32_t tag, int64_t n, float* out, nfmc_stream_t stream);

@@ -426,6 +426,15 @@ class MCMCOutput:
             self.running_samples.spill()
         return self
 
+    def diagnostics(self, max_lag: int = None, superchains: int = None, shard=None):
+        """Split R-hat, ESS (and, with `superchains` = chains per superchain, the nested R-hat) of the kept states, per
+        coordinate: `diagnostics.diagnose` on the device-resident store, no host copy of the states.  A thinned or
+        windowed store is diagnosed as kept (ESS in units of kept draws)."""
+        if not self.store_samples:
+            raise ValueError('diagnostics need the kept states: run with store_samples=True')
+        from . import diagnostics
+        return diagnostics.diagnose(self.samples_device, max_lag=max_lag, superchains=superchains, shard=shard)
+
     def resample(self, n: int) -> torch.Tensor:
         """n draws with replacement from all kept (step, chain) states."""
         pool = self.samples.flatten(0, 1)

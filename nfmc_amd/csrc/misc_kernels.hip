@@ -1,7 +1,9 @@
 // Stand-alone pieces of the path: K6 accept/select, K7 moments, the Langevin proposal / log-ratio for
 // targets whose U and grad U come from outside (arbitrary Python callables differentiated by torch
-// autograd on the GPU), and the native Philox streams on their own (pinned against oracle/philox.py).
+// autograd on the GPU), the native Philox streams on their own (pinned against oracle/philox.py), and the convergence
+// diagnostics of the kept states (diagnostics.hpp).
 #include "common.hpp"
+#include "diagnostics.hpp"
 
 namespace nfmc {
 
@@ -302,6 +304,51 @@ extern "C" int nfmc_langevin_log_ratio_f32(const float* x, const float* x_prime,
     if (n <= 0 || d <= 0 || !(step_size > 0.f)) return NFMC_EINVAL;
     hipLaunchKernelGGL(langevin_log_ratio_kernel, dim3(grid_for(n * 64)), dim3(kBlock), 0, (hipStream_t)stream, x,
                        x_prime, u, u_prime, grad_u, grad_u_prime, inv_mass_diag, step_size, n, (int)d, log_ratio);
+    NFMC_HIP_CHECK_LAUNCH();
+    return NFMC_OK;
+}
+
+static bool diag_shape_ok(int64_t n, int32_t d, int32_t max_lag) {
+    return n > 0 && d > 0 && d <= 1024 && max_lag >= 0 && max_lag <= NFMC_DIAG_MAX_LAG;
+}
+
+extern "C" int64_t nfmc_diag_sums_doubles(int32_t d, int32_t max_lag) {
+    if (!diag_shape_ok(1, d, max_lag)) return 0;
+    return (int64_t)(NFMC_DIAG_ACOV + max_lag + 1) * d;
+}
+
+extern "C" int64_t nfmc_diag_work_bytes(int64_t n, int32_t d, int32_t max_lag) {
+    if (!diag_shape_ok(n, d, max_lag)) return 0;
+    return diag_plan(n, d, max_lag, n).total * (int64_t)sizeof(double);   // group = 1 has the most superchains
+}
+
+extern "C" int nfmc_chain_diagnostics_f32(const NfmcDiagArgs* args, nfmc_stream_t stream) {
+    if (!args || !args->x || !args->sums || !args->work) return NFMC_EINVAL;
+    const NfmcDiagArgs a = *args;
+    if (a.n <= 0 || a.d <= 0 || a.n_draws < 4 || a.max_lag < 0 || a.group < 1 || a.n % a.group != 0) return NFMC_EINVAL;
+    if (a.d > 1024 || a.max_lag > NFMC_DIAG_MAX_LAG) return NFMC_ESHAPE;
+    if (a.work_bytes < nfmc_diag_work_bytes(a.n, a.d, a.max_lag)) return NFMC_ESCRATCH;
+    const int64_t G = a.n / a.group;
+    const DiagPlan p = diag_plan(a.n, a.d, a.max_lag, G);
+    double* work = (double*)a.work;
+    const int nlag = a.max_lag + 1;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(diag_mean_kernel, dim3(grid_for(a.n * a.d)), dim3(kBlock), 0, st, a.x, a.n_draws, a.n * a.d, work);
+    NFMC_HIP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(diag_series_kernel, dim3(p.nb * p.nchunk), dim3(kDiagBlock), 0, st, a.x, a.n_draws, a.n, (int)a.d, nlag,
+                       p.cpt, p.nchunk, p.ntile, p.nb, (const double*)work, work + p.off_main);
+    NFMC_HIP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(diag_group_kernel, dim3(grid_for(p.gs * a.d)), dim3(kBlock), 0, st, work, G, (int64_t)a.group,
+                       (int)a.d, p.gs, work + p.off_group);
+    NFMC_HIP_CHECK_LAUNCH();
+    const int64_t wm = (int64_t)p.rows_main * a.d, wg = (int64_t)kDiagGroup * a.d;
+    // the series kernel's rows are SUM_M .. SUM_S2H then the lags; the group rows sit between them in `sums`
+    const int64_t head = (int64_t)kDiagMain * a.d;
+    hipLaunchKernelGGL(diag_fold_kernel, dim3(grid_for(wm * (kBlock / kDiagFoldCols))), dim3(kBlock), 0, st,
+                       work + p.off_main, (int64_t)p.nb, wm, head, wg, a.sums);
+    NFMC_HIP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(diag_fold_kernel, dim3(grid_for(wg * (kBlock / kDiagFoldCols))), dim3(kBlock), 0, st,
+                       work + p.off_group, p.gs, wg, wg, (int64_t)0, a.sums + head);
     NFMC_HIP_CHECK_LAUNCH();
     return NFMC_OK;
 }

@@ -1,0 +1,184 @@
+"""Convergence diagnostics of a run's kept states: split R-hat, nested R-hat (Margossian et al.) and the effective
+sample size of Stan / Vehtari et al. 2021 (not rank-normalised), per coordinate.
+
+The heavy part -- per-chain means, half-chain moments and lagged autocovariances of the n x d series -- is one HIP call
+over the device-resident slab (nfmc_chain_diagnostics_f32, csrc/diagnostics.hpp).  It returns per-coordinate fp64 sums
+that are additive over chains; everything reported here is a closed-form function of those sums and of
+(n_draws, n_chains, superchain size), evaluated on the host in fp64 (`from_sums`), so chains sharded over GPUs combine
+by one all-reduce of the sums.  DESIGN.md 3.5 has the definitions.
+"""
+import ctypes as C
+import math
+from dataclasses import dataclass
+from typing import Dict, Optional
+
+import torch
+
+from . import hip
+
+DEFAULT_MAX_LAG = hip.DIAG_MAX_LAG
+
+
+@dataclass
+class Diagnostics:
+    """Per-coordinate diagnostics; every tensor is fp64 on the host with the run's event shape."""
+    rhat: torch.Tensor                   # split R-hat over the 2 n half-chains
+    nested_rhat: Optional[torch.Tensor]  # None unless superchains were asked for; NaN with fewer than two superchains
+    ess: torch.Tensor                    # effective sample size, in units of kept draws
+    mcse_mean: torch.Tensor              # Monte Carlo standard error of `mean`
+    mean: torch.Tensor                   # mean over all kept draws of all chains
+    sd: torch.Tensor                     # sqrt of the pooled variance estimate varp
+    truncated: torch.Tensor              # bool: the lags ran out before a negative Geyer pair, `ess` is an upper estimate
+    autocorrelation: torch.Tensor        # (max_lag + 1, *event): rho_l
+    n_draws: int
+    n_chains: int
+    max_lag: int
+
+    def summary(self) -> Dict[str, float]:
+        def worst(t, fn):
+            ok = t[~torch.isnan(t)]
+            return float(fn(ok)) if ok.numel() else math.nan
+        out = {'max_rhat': worst(self.rhat, torch.max), 'min_ess': worst(self.ess, torch.min),
+               'n_truncated': int(self.truncated.sum()), 'n_nan': int(torch.isnan(self.rhat).sum()),
+               'n_draws': self.n_draws, 'n_chains': self.n_chains, 'max_lag': self.max_lag}
+        if self.nested_rhat is not None:
+            out['max_nested_rhat'] = worst(self.nested_rhat, torch.max)
+        return out
+
+
+def _check_counts(n_draws, n_chains, group):
+    if n_draws < 4:
+        raise ValueError('diagnostics need at least 4 kept draws per chain, got %d' % n_draws)
+    if n_chains < 1:
+        raise ValueError('diagnostics need at least one chain')
+    if group < 1 or n_chains % group != 0:
+        raise ValueError('superchains of %d chains do not divide %d chains' % (group, n_chains))
+
+
+def chain_sums(x: torch.Tensor, max_lag: int, group: int = 1) -> Dict[str, torch.Tensor]:
+    """The kernel's sums for kept states x (n_draws, n_chains, *event), a contiguous fp32 CUDA tensor: fp64 CPU tensors
+    `sum_m`, `sum_m2` (chain means), `sum_mh`, `sum_mh2`, `sum_s2h` (half-chains), `sum_mu`, `sum_mu2`, `sum_bt`
+    (superchains of `group` chains), each (d,), and `acov` (max_lag + 1, d) = sum_j a_{j,l}.  One kernel call, one
+    device-to-host copy."""
+    if x.dim() < 2:
+        raise ValueError('expected (n_draws, n_chains, *event), got %s' % (tuple(x.shape),))
+    K, n = int(x.shape[0]), int(x.shape[1])
+    d = int(math.prod(x.shape[2:]))
+    _check_counts(K, n, int(group))
+    lib = hip.lib()
+    count = int(lib.nfmc_diag_sums_doubles(d, int(max_lag)))
+    nbytes = int(lib.nfmc_diag_work_bytes(n, d, int(max_lag)))
+    if count <= 0 or nbytes <= 0:
+        raise hip.NfmcArgumentError('diagnostics: event size %d (<= 1024) or max_lag %d (0 .. %d) outside the kernel\'s range'
+                                    % (d, max_lag, hip.DIAG_MAX_LAG), hip.ESHAPE)
+    sums = torch.empty(count, dtype=torch.float64, device=x.device)
+    work = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device)
+    args = hip.NfmcDiagArgs(hip.ptr(x), K, n, d, int(max_lag), int(group), 0, hip.ptr(sums, torch.float64),
+                            hip.ptr(work, torch.float64), nbytes)
+    with torch.cuda.device(x.device):
+        hip.check(lib.nfmc_chain_diagnostics_f32(C.byref(args), hip.stream()), 'nfmc_chain_diagnostics_f32')
+    return unpack_sums(sums.cpu(), d)
+
+
+def unpack_sums(flat: torch.Tensor, d: int) -> Dict[str, torch.Tensor]:
+    """Name the rows of the kernel's `sums` (include/nfmc_hip.h: NFMC_DIAG_*)."""
+    rows = flat.reshape(-1, d)
+    out = {name: rows[i] for i, name in enumerate(hip.DIAG_ROWS)}
+    out['acov'] = rows[hip.DIAG_ACOV:]
+    return out
+
+
+def pack_sums(sums: Dict[str, torch.Tensor]) -> torch.Tensor:
+    return torch.cat([sums[name].reshape(1, -1) for name in hip.DIAG_ROWS] + [sums['acov']]).reshape(-1)
+
+
+def _var_from_sums(s1, s2, count):
+    """Unbiased variance of `count` values from their sum and sum of squares (0 for a single value)."""
+    if count < 2:
+        return torch.zeros_like(s1)
+    return ((s2 - s1 * s1 / count) / (count - 1)).clamp_min(0.0)
+
+
+def from_sums(sums: Dict[str, torch.Tensor], n_draws: int, n_chains: int, group: Optional[int] = None,
+              event_shape=None) -> Diagnostics:
+    """Host fp64: the diagnostics from the additive sums (of all chains, after any all-reduce).  `group` = chains per
+    superchain, None for no nested R-hat.  A coordinate without within-chain variance gets NaN, never an error."""
+    K, n = int(n_draws), int(n_chains)
+    _check_counts(K, n, 1 if group is None else int(group))
+    s = {k: v.to(torch.float64) for k, v in sums.items()}
+    L = min(int(s['acov'].shape[0]) - 1, K - 1)
+    unb = K / (K - 1.0)
+    nan = torch.full_like(s['sum_m'], math.nan)
+
+    # split R-hat over the 2 n half-chains of h = K // 2 draws
+    h = K // 2
+    ws = s['sum_s2h'] / (2 * n)
+    bs = _var_from_sums(s['sum_mh'], s['sum_mh2'], 2 * n)
+    rhat = torch.where(ws > 0, torch.sqrt(((h - 1.0) / h * ws + bs) / ws), nan)
+
+    # ESS: Geyer's initial monotone sequence on the multi-chain autocorrelation
+    acov = s['acov'][:L + 1] / n                       # mean_j a_{j,l}
+    w = acov[0] * unb
+    varp = (K - 1.0) / K * w + _var_from_sums(s['sum_m'], s['sum_m2'], n)
+    rho = torch.where(w > 0, 1.0 - (w - acov * unb) / varp, nan.expand_as(acov)).clone()
+    rho[0] = torch.where(w > 0, torch.ones_like(w), nan)
+    alive = torch.ones_like(w, dtype=torch.bool)
+    prev = torch.full_like(w, math.inf)
+    total = torch.zeros_like(w)
+    for k in range((L + 1) // 2):
+        pair = rho[2 * k] + rho[2 * k + 1]
+        alive = alive & ~(pair < 0)
+        pair = torch.minimum(pair, prev)
+        total = total + torch.where(alive, pair, torch.zeros_like(pair))
+        prev = torch.where(alive, pair, prev)
+    tau = torch.clamp_min(-1.0 + 2.0 * total, 1.0 / math.log10(n * K))
+    ess = torch.where(w > 0, n * K / tau, nan)
+    mcse = torch.sqrt(varp / ess)
+
+    nested = None
+    if group is not None:
+        M = int(group)
+        G = n // M
+        if G < 2:
+            nested = nan.clone()
+        else:
+            wn = (s['sum_bt'] + acov[0] * n * unb / M) / G      # mean_k (Bt_k + Wt_k)
+            bn = _var_from_sums(s['sum_mu'], s['sum_mu2'], G)
+            nested = torch.where(wn > 0, torch.sqrt(1.0 + bn / wn), nan)
+
+    shape = tuple(event_shape) if event_shape is not None else tuple(s['sum_m'].shape)
+    def ev(t):
+        return t.reshape(shape)
+    return Diagnostics(rhat=ev(rhat), nested_rhat=None if nested is None else ev(nested), ess=ev(ess), mcse_mean=ev(mcse),
+                       mean=ev(s['sum_m'] / n), sd=ev(torch.sqrt(varp)), truncated=ev(alive & (w > 0)),
+                       autocorrelation=rho.reshape((L + 1,) + shape), n_draws=K, n_chains=n, max_lag=L)
+
+
+def diagnose(x: torch.Tensor, max_lag: Optional[int] = None, superchains: Optional[int] = None, shard=None) -> Diagnostics:
+    """Diagnostics of kept states x (n_draws, n_chains, *event), fp32; host-resident states are moved to the device first.
+    `max_lag` defaults to min(n_draws - 1, 127) and is clipped to n_draws - 1.  `superchains` = M consecutive chains
+    per superchain turns the nested R-hat on; M must divide the local chain count (no superchain straddles a shard).
+    With a `dist.Shard` of more than one rank the sums are all-reduced and the result describes all chains, on every
+    rank."""
+    if x.dim() < 2:
+        raise ValueError('expected (n_draws, n_chains, *event), got %s' % (tuple(x.shape),))
+    K, n = int(x.shape[0]), int(x.shape[1])
+    event_shape = tuple(int(v) for v in x.shape[2:])
+    M = 1 if superchains is None else int(superchains)
+    _check_counts(K, n, M)
+    L = min(K - 1, DEFAULT_MAX_LAG if max_lag is None else int(max_lag))
+    if L < 0:
+        raise ValueError('max_lag must not be negative')
+    if not x.is_cuda:
+        x = x.to(hip.require_gpu())
+    x = x.detach().to(torch.float32).contiguous()
+    d = int(math.prod(event_shape))
+    sums = chain_sums(x.reshape(K, n, d), L, M)
+    if shard is not None and shard.world > 1:
+        pack = torch.cat([pack_sums(sums), torch.tensor([float(n)], dtype=torch.float64)])
+        pack = pack.to(x.device)   # Shard moves it to the host itself under a gloo group
+        shard.all_reduce_sum_(pack)
+        pack = pack.cpu()
+        n = int(round(float(pack[-1])))
+        sums = unpack_sums(pack[:-1], d)
+    return from_sums(sums, K, n, None if superchains is None else M, event_shape)

@@ -184,6 +184,17 @@ FIT_BEST_LOSS, FIT_SINCE_BEST, FIT_APPLIED, FIT_STOPPED, FIT_DIVERGED, FIT_LAST_
 FIT_STATE_FLOATS = 8
 
 
+class NfmcDiagArgs(C.Structure):
+    _fields_ = [('x', c_fp), ('n_draws', C.c_int64), ('n', C.c_int64), ('d', C.c_int32), ('max_lag', C.c_int32),
+                ('group', C.c_int32), ('reserved', C.c_int32), ('sums', c_fp), ('work', c_fp), ('work_bytes', C.c_int64)]
+
+
+# rows of NfmcDiagArgs.sums (include/nfmc_hip.h: NFMC_DIAG_*); the lags follow from DIAG_ACOV
+DIAG_MAX_LAG = 127
+DIAG_ROWS = ('sum_m', 'sum_m2', 'sum_mh', 'sum_mh2', 'sum_s2h', 'sum_mu', 'sum_mu2', 'sum_bt')
+DIAG_ACOV = len(DIAG_ROWS)
+
+
 class NfmcLimits(C.Structure):
     _fields_ = [('abi_version', C.c_int32), ('max_d_sampler', C.c_int32), ('max_d_flow', C.c_int32),
                 ('max_hidden_valu', C.c_int32), ('max_hidden', C.c_int32), ('max_steps_per_call', C.c_int32)]
@@ -225,6 +236,9 @@ SYMBOLS = [
                                               C.c_int32, c_fp, c_fp]),
     ('nfmc_moments_update_f32', C.c_int, [c_fp, C.c_int64, C.c_int32, C.POINTER(NfmcStats), c_fp]),
     ('nfmc_stats_fold_f32', C.c_int, [C.POINTER(NfmcStats), C.c_int32, C.c_uint64, c_fp, C.c_uint64, c_fp]),
+    ('nfmc_diag_sums_doubles', C.c_int64, [C.c_int32, C.c_int32]),
+    ('nfmc_diag_work_bytes', C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    ('nfmc_chain_diagnostics_f32', C.c_int, [C.POINTER(NfmcDiagArgs), c_fp]),
     ('nfmc_philox_normals_f32', C.c_int, [C.POINTER(NfmcRng), C.c_int32, C.c_int64, C.c_int32, c_fp, c_fp]),
     ('nfmc_philox_uniforms_f32', C.c_int, [C.POINTER(NfmcRng), C.c_int32, C.c_int64, c_fp, c_fp]),
     ('nfmc_flow_fit_supported_f32', C.c_int, [C.POINTER(NfmcRealNVP)]),

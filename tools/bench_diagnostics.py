@@ -1,0 +1,98 @@
+"""Time nfmc_chain_diagnostics_f32 over a resident slab against the same sums composed from torch ops.
+
+    python tools/bench_diagnostics.py [--shapes 100x65536x64,100x8192x512] [--max-lag 99] [--reps 5]
+
+Per shape: median of `reps` calls after one warm-up, device events around the library call alone (buffers allocated
+before); the bytes of the slab over that time next to the 6.3 TB/s streaming figure (the kernel reads the slab twice, so
+half of it is its ceiling); and the torch composition -- centred draws, one elementwise product and reduction per lag
+-- in the same process.  Prints one JSON line per shape.  Needs the GPU: there is no fallback.
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from nfmc_amd import diagnostics, hip  # noqa: E402
+
+STREAM_TBS = 6.3   # measured float4 copy rate of the MI355X
+
+
+def timed(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b))
+    return statistics.median(out), out
+
+
+def torch_sums(x, max_lag, group):
+    """What a user composes today: every sum of the kernel from torch ops on the device (fp32 centred draws, fp64 totals)."""
+    K, n, d = x.shape
+    h = K // 2
+    m = x.mean(dim=0, dtype=torch.float64)
+    c = (x - m).float()
+    acov = torch.stack([(c[:K - l] * c[l:]).sum(dim=0).double().sum(dim=0) / K for l in range(max_lag + 1)])
+    hx = torch.cat([c[:h], c[K - h:]], dim=1).double()
+    mh = hx.mean(dim=0) + torch.cat([m, m])
+    s2h = hx.var(dim=0, unbiased=True)
+    mg = m.reshape(n // group, group, d)
+    mu = mg.mean(dim=1)
+    bt = mg.var(dim=1, unbiased=True) if group > 1 else torch.zeros_like(mu)
+    head = [m.sum(0), (m * m).sum(0), mh.sum(0), (mh * mh).sum(0), s2h.sum(0), mu.sum(0), (mu * mu).sum(0), bt.sum(0)]
+    return torch.cat([torch.stack(head), acov]).reshape(-1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--shapes', default='100x65536x64,100x8192x512')
+    ap.add_argument('--max-lag', type=int, default=99)
+    ap.add_argument('--group', type=int, default=16)
+    ap.add_argument('--reps', type=int, default=5)
+    a = ap.parse_args()
+    dev = hip.require_gpu()
+    lib = hip.lib()
+    for shape in a.shapes.split(','):
+        K, n, d = (int(v) for v in shape.split('x'))
+        L = min(a.max_lag, K - 1)
+        torch.manual_seed(0)
+        x = torch.randn(K, n, d, device=dev)
+        x[1:] = 0.7 * x[:-1] + 0.5 * x[1:]            # some autocorrelation; the values do not matter for the time
+        sums = torch.empty(int(lib.nfmc_diag_sums_doubles(d, L)), dtype=torch.float64, device=dev)
+        nbytes = int(lib.nfmc_diag_work_bytes(n, d, L))
+        work = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        args = hip.NfmcDiagArgs(hip.ptr(x), K, n, d, L, a.group, 0, hip.ptr(sums, torch.float64),
+                                hip.ptr(work, torch.float64), nbytes)
+
+        def kernel():
+            hip.check(lib.nfmc_chain_diagnostics_f32(C.byref(args), hip.stream()), 'nfmc_chain_diagnostics_f32')
+
+        k_ms, k_all = timed(kernel, a.reps)
+        got = sums.clone()
+        t_ms, t_all = timed(lambda: torch_sums(x, L, a.group), a.reps)
+        want = torch_sums(x, L, a.group)
+        scale = want.reshape(-1, d)[hip.DIAG_ACOV].abs().max()
+        slab = x.numel() * 4
+        print(json.dumps({'shape': [K, n, d], 'max_lag': L, 'group': a.group, 'kernel_ms': round(k_ms, 4),
+                          'kernel_ms_all': [round(v, 4) for v in k_all], 'slab_gb': round(slab / 1e9, 3),
+                          'slab_bytes_over_kernel_time_tbs': round(slab / (k_ms * 1e-3) / 1e12, 3),
+                          'stream_tbs': STREAM_TBS, 'work_mb': round(nbytes / 1e6, 1),
+                          'torch_ms': round(t_ms, 3), 'torch_ms_all': [round(v, 3) for v in t_all],
+                          'speedup': round(t_ms / k_ms, 1),
+                          'acov_max_diff_over_lag0': float(((got - want).reshape(-1, d)[hip.DIAG_ACOV:].abs().max() / scale))}),
+              flush=True)
+        del x, work, sums
+
+
+if __name__ == '__main__':
+    main()
