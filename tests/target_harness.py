@@ -13,6 +13,9 @@ row: FlowRecord hands every launch a mask and a log-ratio buffer, compare_flow_m
 JumpSteps, centred_flow_pair and centred give inputs under which proposals are accepted, and flow_cases is the matrix of
 layouts, widths and couplings that a per-target file runs through run_flow_case.  Every figure about those inputs comes
 from the fp64 (or fp32) oracle on the CPU: oracle_only and probe_flow_inputs run the cases' inputs without a GPU.
+tests/test_gpu_flow_mh_wide.py holds the three kernels of wider conditioners the same way: flow_mh_kernel_of says which
+kernel a launch takes, and _direct_flow_mh's options (cached log q, replayed noise, statistics, a thinned store) reach
+what one nfmc_flow_mh_steps_f32 launch can be asked.
 
 A problem is a `Problem`: the package potential, its fp64 restatement `ref` (U alone, for magnitudes and NeuTra), the
 fp64 target the oracle samplers run on, the fp32 starts x0 (n, d), d and a name for messages.  The `_Problem` classes of
@@ -310,12 +313,16 @@ class FlowRecord:
 
 
 # --------------------------------------------------------------------------------------------- builders
-def _flow_objects(d, n_hidden, spline, n_layers):
-    """(package flow, oracle flow) of one architecture, weights untouched"""
+def _flow_objects(d, n_hidden, spline, n_layers, hidden_layers=None):
+    """(package flow, oracle flow) of one architecture, weights untouched; hidden_layers: the conditioner's hidden-layer
+    count (conditioner_kwargs['n_layers'], the NHL of the matrix-core kernels), None: the architecture's default of 2"""
     from nfmc_amd.flows import Flow, RealNVP
     from nfmc_amd.util import create_flow_object
     from oracle import flow as oflow
-    kw = {} if n_hidden is None else {'conditioner_kwargs': {'n_hidden': n_hidden}}
+    ck = {} if n_hidden is None else {'n_hidden': n_hidden}
+    if hidden_layers is not None:
+        ck['n_layers'] = int(hidden_layers)
+    kw = {'conditioner_kwargs': ck} if ck else {}
     if n_layers is not None:
         kw['n_layers'] = n_layers
     if spline:
@@ -323,19 +330,20 @@ def _flow_objects(d, n_hidden, spline, n_layers):
     return Flow(RealNVP((d,), **kw)), oflow.Flow(oflow.RealNVP((d,), **kw))
 
 
-def flow_pair(d, seed=5, n_hidden=None, spline=False, n_layers=None, init_seed=None):
+def flow_pair(d, seed=5, n_hidden=None, spline=False, n_layers=None, init_seed=None, hidden_layers=None):
     """(package flow, fp64 oracle flow) with the same perturbed weights (oracle.flow.perturb_, every parameter touched);
-    n_hidden and n_layers (coupling layers) for either coupling, None: the architecture's defaults.  The weights that are
+    n_hidden, n_layers (coupling layers) and hidden_layers (the conditioner's hidden layers) for either coupling, None:
+    the architecture's defaults.  The weights that are
     perturbed are torch's default initialisation, drawn from the global generator as it stands; with init_seed they are
     drawn from that seed instead (the global generator is left as it was), which a case whose inputs must satisfy a
     condition needs."""
     from oracle import flow as oflow
     if init_seed is None:
-        f, of = _flow_objects(d, n_hidden, spline, n_layers)
+        f, of = _flow_objects(d, n_hidden, spline, n_layers, hidden_layers)
     else:
         with torch.random.fork_rng(devices=[]):
             torch.manual_seed(init_seed)
-            f, of = _flow_objects(d, n_hidden, spline, n_layers)
+            f, of = _flow_objects(d, n_hidden, spline, n_layers, hidden_layers)
     of = oflow.perturb_(of, seed, 0.3, 0.75) if spline else oflow.perturb_(of, seed, 0.2, 0.7071)
     f.load_state_dict(of.state_dict())
     return f, of.double()
@@ -391,15 +399,15 @@ def local_fit(p, shrink, at='starts'):
     return c, s
 
 
-def centred_flow_pair(p, seed=5, n_hidden=None, spline=False, n_layers=None, *, scale, centre=None):
-    """flow_pair's architecture as the identity map (every weight 0; a spline's interior knot derivatives 1), every
+def centred_flow_pair(p, seed=5, n_hidden=None, spline=False, n_layers=None, *, scale, centre=None, hidden_layers=None):
+    """flow_pair's architecture (hidden_layers: the conditioner's hidden-layer count) as the identity map (every weight 0; a spline's interior knot derivatives 1), every
     parameter perturbed by `scale` (oracle.flow.perturb_), and the data-side ElementwiseAffine set so that the flow's
     forward pass starts z = (x - c) / s, (c, s) = laplace_fit(p) or the `centre` given (local_fit), the perturbation on
     top: a proposal that sits on the target closely enough for the Metropolis test to accept.  Nothing is drawn from
     torch's global generator."""
     from oracle import flow as oflow
     c, s = laplace_fit(p) if centre is None else centre
-    f, of = _flow_objects(p.d, n_hidden, spline, n_layers)
+    f, of = _flow_objects(p.d, n_hidden, spline, n_layers, hidden_layers)
     of = of.double()
     with torch.no_grad():
         for prm in of.parameters():
@@ -836,22 +844,90 @@ def imh_matches_oracle(monkeypatch, p, *, T, seed, flow_seed, spline, what, comp
                            skip_below_minus_50=skip_below_minus_50, floor=floor)
 
 
-def _direct_flow_mh(dev, p, f, T, seed, adjusted):
-    """T transitions of one nfmc_flow_mh_steps_f32 launch from p.x0: (kept states (T, n, d), masks, log ratios), CPU"""
+DirectRun = collections.namedtuple('DirectRun', 'samples masks log_ratios logq x stats')
+
+
+def _direct_flow_mh(dev, p, f, T, seed, adjusted, *, cached=None, replay=None, stats=None, store=None, prefill=None, detail=False):
+    """T transitions of one nfmc_flow_mh_steps_f32 launch from p.x0: (kept states (T, n, d), masks, log ratios), CPU.
+    cached: log q of the starts (n,), computed beforehand (flow.log_prob); the launch runs with logq_cached = 1.
+    replay: (normals (T, n, d), uniforms (T, n) or None), handed to the kernel in place of its Philox streams.
+    stats: 'immediate' (run.stats.struct()) or 'deferred' (struct(defer=True, attempted=n T), then the fold); the totals
+      come back as a dict: accepted, attempted, nonfinite, sum_x, sum_x2 (fp64).  None: immediate, not read back.
+    prefill: a value the run's statistics scratch (every slab) is filled with before the launch: an immediate launch must
+      overwrite its slabs, a deferred one add to them.
+    store: (thinning, max_samples): the kept states go through a DeviceSampleStore of T offered transitions and come
+      back in chronological order (DeviceSampleStore.ordered).
+    With any of these, or detail, the result is a DirectRun: the three above, then logq (n,) as the launch left it, the
+    final states x (n, d) and the statistics (or None)."""
+    from nfmc_amd import hip
+    from nfmc_amd.containers import DeviceSampleStore
     from nfmc_amd.samplers import imh, jump
     from nfmc_amd.samplers.common import Run
     n, d = p.x0.shape[0], p.d
     s = imh.FixedIMH((d,), p.pot, imh.IMHKernel((d,), flow=f), imh.IMHParameters(n_iterations=T))
     s.seed = seed
+    if replay is not None:
+        s.replay = (replay[0].float(), None if replay[1] is None else replay[1].float())
     run = Run(s, p.x0)
     logq = torch.empty(n, dtype=torch.float32, device=dev)
+    if cached is not None:
+        logq.copy_(cached.reshape(n).float())
     masks = torch.zeros(T, n, dtype=torch.uint8, device=dev)
     lr = torch.zeros(T, n, dtype=torch.float32, device=dev)
-    samples = torch.zeros(T, n, d, dtype=torch.float32, device=dev)
+    samples = torch.zeros(T, n, d, dtype=torch.float32, device=dev) if store is None else DeviceSampleStore(n, d, dev, T, *store)
     assert jump.flow_mh_supported(run, f, p.pot, logq, adjusted)
-    jump.launch_flow_mh(run, f, p.pot, logq, T, 0, False, adjusted, run.stats.struct(), samples, masks, lr)
+    assert stats in (None, 'immediate', 'deferred'), stats
+    if prefill is not None:
+        run.stats.scratch.fill_(prefill)
+    st = run.stats.struct(defer=True, attempted=n * T) if stats == 'deferred' else run.stats.struct()
+    jump.launch_flow_mh(run, f, p.pot, logq, T, 0, cached is not None, adjusted, st, samples, masks, lr)
     torch.cuda.synchronize()
-    return samples.cpu(), masks.cpu().bool(), lr.cpu()
+    kept = samples.cpu() if store is None else samples.ordered().cpu().clone()
+    if not (detail or cached is not None or replay is not None or stats is not None or store is not None or prefill is not None):
+        return kept, masks.cpu().bool(), lr.cpu()
+    totals = None
+    if stats is not None:
+        sum_x, sum_x2, cnt, _jc = run.stats.host_totals()
+        totals = {'accepted': int(cnt[hip.CNT_ACCEPTED]), 'attempted': int(cnt[hip.CNT_ATTEMPTED]),
+                  'nonfinite': int(cnt[hip.CNT_NONFINITE]), 'sum_x': sum_x.clone(), 'sum_x2': sum_x2.clone()}
+    return DirectRun(kept, masks.cpu().bool(), lr.cpu(), logq.cpu(), run.x.cpu(), totals)
+
+
+FLOW_MH_KERNELS = ('register', 'mfma', 'wide', 'lane')
+
+
+def flow_mh_kernel_of(dev, p, f, adjusted=True):
+    """Which kernel nfmc_flow_mh_steps_f32 takes for flow f from p's starts under the environment as it stands: 'register'
+    (flow_mh_b_kernel), 'mfma' (flow_mh_mfma_kernel), 'wide' (flow_mh_wide_kernel), 'lane' (flow_mh_kernel<HP>), or None
+    where nfmc_flow_mh_supported_f32 refuses the launch.  csrc/flow_kernels.hip: flow_mh_steps' order, from the library's
+    own answers about the flow as the package presents it (packed: the width it is padded to, the workspace it carries):
+    the probe; nfmc_realnvp_padded_hidden (above 32: a matrix-core weight layout); nfmc_flow_scratch_bytes > 0 (the
+    streamed kernel's shapes) together with a workspace; and the two switches flow_mh_steps reads on every call,
+    NFMC_FLOW_TILE_PATH (no register kernel) and NFMC_FLOW_NO_MFMA (no matrix cores), set to any value."""
+    import os
+    from nfmc_amd import hip
+    from nfmc_amd.samplers import imh
+    from nfmc_amd.samplers.common import Run
+    from nfmc_amd.samplers.jump import _flow_mh_probe_args
+    s = imh.FixedIMH((p.d,), p.pot, imh.IMHKernel((p.d,), flow=f), imh.IMHParameters(n_iterations=1))
+    run = Run(s, p.x0)
+    logq = torch.empty(p.x0.shape[0], device=dev)
+    pa, _keep = _flow_mh_probe_args(run, f, p.pot, logq, adjusted)
+    rc = _rc(hip.lib().nfmc_flow_mh_supported_f32, C.byref(pa))
+    if rc == hip.EUNSUPPORTED:
+        return None
+    assert rc == 0, rc
+    st = pa.flow
+    tile_path, no_mfma = 'NFMC_FLOW_TILE_PATH' in os.environ, 'NFMC_FLOW_NO_MFMA' in os.environ
+    if st.n_hidden <= 8 and not tile_path:
+        return 'register'
+    hp = int(hip.lib().nfmc_realnvp_padded_hidden(st.n_hidden))
+    matrix = hp > 32 and st.n_bins == 0 and st.n_coupling > 0 and st.n_hidden_layers in (1, 2) and not no_mfma
+    if matrix and st.d in (64, 128):
+        return 'mfma'
+    if matrix and int(hip.lib().nfmc_flow_scratch_bytes(C.byref(st), run.n, 1)) > 0 and st.scratch:
+        return 'wide'
+    return 'lane'
 
 
 def flow_mh_unadjusted_matches_oracle(dev, monkeypatch, p, flows, *, T, seed, spline, what, atol, rtol, cfg=None):

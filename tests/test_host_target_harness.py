@@ -308,6 +308,93 @@ def test_flow_layout_is_the_launchers_rule():
     assert H.flow_layout(50, 96, (8, 8)) == (8, 8) and H.flow_layout(70, 96, (8, 8)) == (4, 32)
 
 
+def test_hidden_layer_argument_sets_the_conditioners_depth_in_both_flows():
+    """hidden_layers is conditioner_kwargs['n_layers'] (the NHL of the matrix-core kernels), n_layers stays the coupling
+    count, and leaving it out keeps the architecture's two hidden layers"""
+    p = _Normal(FD)
+    for spline in (False, True):
+        for make in (lambda **kw: H.flow_pair(FD, 3, spline=spline, **kw), lambda **kw: H.centred_flow_pair(p, 3, spline=spline, scale=0.1, **kw)):
+            f, of = make(n_hidden=5, n_layers=3, hidden_layers=1)
+            assert (f.bijection.n_hidden_layers, f.bijection.n_hidden, f.bijection.n_coupling) == (1, 5, 3)
+            assert len(f.bijection.couplings[0].conditioner) == 2 and len(f.state_dict()) == len(of.state_dict())
+            for k, v in f.state_dict().items():
+                assert torch.equal(v.double(), of.state_dict()[k].double()), k
+            f2, _of2 = make(n_hidden=5, n_layers=3)
+            assert f2.bijection.n_hidden_layers == 2 and len(f2.bijection.couplings[0].conditioner) == 3
+
+
+def test_direct_flow_mh_options_reach_the_launch(monkeypatch):
+    """_direct_flow_mh on a stand-in for the run and the launch (no GPU): `cached` arrives as the logq buffer with the
+    cached flag, `replay` as the sampler's replay, stats='deferred' asks struct(defer=True, attempted=n T) and returns the
+    folded totals, `store` hands the launch a DeviceSampleStore of T offered transitions whose kept rows come back in
+    order, `prefill` fills the statistics scratch, and without options the three-tuple of before is returned."""
+    from nfmc_amd import hip
+    from nfmc_amd.potentials import SumOfSquares
+    from nfmc_amd.samplers import common, jump
+    n, d, steps = 5, FD, 7
+    cpu = torch.device('cpu')
+    seen = {}
+
+    class Stats:
+        scratch = torch.zeros(16, dtype=torch.float64)
+
+        def struct(self, defer=False, attempted=0):
+            seen['struct'] = (defer, attempted)
+            return 'stats'
+
+        def host_totals(self):
+            cnt = torch.zeros(8, dtype=torch.int64)
+            cnt[hip.CNT_ACCEPTED], cnt[hip.CNT_ATTEMPTED], cnt[hip.CNT_NONFINITE] = 11, n * steps, 2
+            return torch.full((d,), 3.0, dtype=torch.float64), torch.full((d,), 4.0, dtype=torch.float64), cnt, cnt.clone()
+
+    class Run:
+        def __init__(self, sampler, x0):
+            self.n, self.d, self.dev, self.stats = x0.shape[0], x0.shape[1], cpu, Stats()
+            self.x = x0.clone()
+            seen['replay'], seen['seed'] = sampler.replay, sampler.seed
+
+    def launch(run, flow, pot, logq, k, step0, cached, adjusted, stats_struct, samples, masks_out, log_ratio_out):
+        seen.update(logq=logq.clone(), k=k, cached=cached, adjusted=adjusted, stats=stats_struct, samples=samples)
+        dense = torch.arange(k, dtype=torch.float32)[:, None, None].expand(k, run.n, run.d).contiguous()
+        if hasattr(samples, 'add_dense'):
+            samples.add_dense(dense)
+        else:
+            samples.copy_(dense)
+        masks_out.fill_(1)
+        log_ratio_out.fill_(0.5)
+        logq.fill_(-1.0)
+        run.x.fill_(float(k - 1))
+
+    monkeypatch.setattr(common, 'Run', Run)
+    monkeypatch.setattr(jump, 'flow_mh_supported', lambda *a, **k: True)
+    monkeypatch.setattr(jump, 'launch_flow_mh', launch)
+    monkeypatch.setattr(torch.cuda, 'synchronize', lambda *a, **k: None)
+    f, _of = H.flow_pair(FD, 3)
+    p = H.Problem(SumOfSquares((d,)), _u, _u, torch.zeros(n, d), d, 'stand-in')
+    plain = H._direct_flow_mh(cpu, p, f, steps, 9, False)
+    assert isinstance(plain, tuple) and len(plain) == 3 and plain[0].shape == (steps, n, d) and plain[1].dtype == torch.bool
+    assert seen['seed'] == 9 and seen['replay'] is None and (seen['cached'], seen['adjusted'], seen['k']) == (False, False, steps)
+    assert seen['struct'] == (False, 0) and seen['stats'] == 'stats'
+    lq = torch.linspace(-3.0, -1.0, n)
+    normals, uniforms = torch.randn(steps, n, d, dtype=torch.float64), torch.rand(steps, n, dtype=torch.float64)
+    r = H._direct_flow_mh(cpu, p, f, steps, 9, True, cached=lq, replay=(normals, uniforms), stats='deferred', store=(3, 2))
+    assert isinstance(r, H.DirectRun) and seen['cached'] is True and torch.equal(seen['logq'], lq)
+    assert torch.equal(seen['replay'][0], normals.float()) and torch.equal(seen['replay'][1], uniforms.float())
+    assert seen['struct'] == (True, n * steps)
+    store = seen['samples']
+    assert (store.thinning, store.rows, store.seen) == (3, 2, steps)
+    assert r.samples.shape == (2, n, d) and r.samples[:, 0, 0].tolist() == [3.0, 6.0]          # transitions 0, 3, 6: the last two
+    assert bool(r.masks.all()) and bool((r.log_ratios == 0.5).all()) and bool((r.logq == -1.0).all()) and bool((r.x == steps - 1).all())
+    assert (r.stats['accepted'], r.stats['attempted'], r.stats['nonfinite']) == (11, n * steps, 2)
+    assert bool((r.stats['sum_x'] == 3.0).all()) and bool((r.stats['sum_x2'] == 4.0).all())
+    r = H._direct_flow_mh(cpu, p, f, steps, 9, True, replay=(normals, None), stats='immediate')
+    assert seen['replay'][1] is None and seen['struct'] == (False, 0) and r.samples.shape == (steps, n, d) and r.stats['accepted'] == 11
+    assert H._direct_flow_mh(cpu, p, f, steps, 9, True, detail=True).stats is None
+    assert not bool(Stats.scratch.any())
+    H._direct_flow_mh(cpu, p, f, steps, 9, True, stats='deferred', prefill=1.0)
+    assert bool((Stats.scratch == 1.0).all())
+
+
 FLOW_FILES = ['fullrank', 'gmrf', 'latent_gaussian', 'logreg', 'mixture', 'phi4', 'irt', 'varying_effects', 'rosenbrock', 'sv',
               'sparse_logreg', 'particles']
 
