@@ -15,7 +15,10 @@ layouts, widths and couplings that a per-target file runs through run_flow_case.
 from the fp64 (or fp32) oracle on the CPU: oracle_only and probe_flow_inputs run the cases' inputs without a GPU.
 tests/test_gpu_flow_mh_wide.py holds the three kernels of wider conditioners the same way: flow_mh_kernel_of says which
 kernel a launch takes, and _direct_flow_mh's options (cached log q, replayed noise, statistics, a thinned store) reach
-what one nfmc_flow_mh_steps_f32 launch can be asked.
+what one nfmc_flow_mh_steps_f32 launch can be asked.  tests/test_gpu_neutra_hmc_wide.py does the same for the two
+matrix-core NeuTra-HMC trajectory kernels: neutra_hmc_kernel_of and neutra_hmc_scratch_bytes name the kernel of a launch,
+_direct_neutra_hmc makes one nfmc_neutra_hmc_steps_f32 call, neutra_hmc_figures measures what the oracle itself loses in
+fp32, and compare_neutra_hmc holds a launch to the oracle through compare_states and compare_decisions.
 
 A problem is a `Problem`: the package potential, its fp64 restatement `ref` (U alone, for magnitudes and NeuTra), the
 fp64 target the oracle samplers run on, the fp32 starts x0 (n, d), d and a name for messages.  The `_Problem` classes of
@@ -57,7 +60,7 @@ def compare_states(got, tr, what, *, margin, atol, rtol, cap=0.10):
     return keep
 
 
-def compare_decisions(rec, tr, kind, x0, ref, what, *, mag=None, skip_below_minus_50=False):
+def compare_decisions(rec, tr, kind, x0, ref, what, *, mag=None, skip_below_minus_50=False, at_least=None):
     """The kernel's accept masks and log ratios (rec.stacked()) against the oracle's, transition by transition, on the
     rows before a chain's first disagreeing decision (a near-tie flips it; the states comparison bounds how many).  Log
     ratios to 2e-4 max(1, d / 64) + 1e-4 |log r| + 8 ulp(fp32) mag(x), x the state each transition starts from:
@@ -67,7 +70,11 @@ def compare_decisions(rec, tr, kind, x0, ref, what, *, mag=None, skip_below_minu
     skip_below_minus_50: a proposal whose U overflows, or whose HMC trajectory diverges, has a non-finite or hugely
     negative fp64 log ratio (below -50 no uniform can accept it); the masks already show that the kernel rejected it,
     and the fp32 and fp64 trajectories part there, so only finite ratios above -50 are compared.  Off unless a target
-    has such proposals at its test inputs: every agreeing row is compared, and a non-finite fp64 ratio fails."""
+    has such proposals at its test inputs: every agreeing row is compared, and a non-finite fp64 ratio fails.
+
+    at_least: a measured figure (tests/test_gpu_neutra_hmc_wide.py: four times what the fp32 oracle itself differs from
+    the fp64 one by) that the tolerance of a row is raised to where the formula gives less.  Returns the worst error over
+    tolerance of an adjusted kind."""
     got_m, got_lr = rec.stacked()
     if kind in ('ula', 'uhmc'):
         assert bool(got_m.all()), what                        # unadjusted: every proposal kept
@@ -87,8 +94,11 @@ def compare_decisions(rec, tr, kind, x0, ref, what, *, mag=None, skip_below_minu
         agree = agree & torch.isfinite(want_lr) & (want_lr > -50)
     err = (got_lr.double() - want_lr).abs()
     tol = 2e-4 * max(1.0, d / 64) + 1e-4 * want_lr.abs() + 8 * 2.0 ** -24 * size
+    if at_least is not None:
+        tol = tol.clamp_min(at_least)
     print('%s: worst log-ratio error %.2e' % (what, float(err[agree].max())))
     assert bool((err[agree] <= tol[agree]).all()), (what, float(err[agree].max()))
+    return float((err / tol)[agree].max())
 
 
 def affine_c(d):
@@ -1160,6 +1170,236 @@ def determinism_and_sharding(make, x0, T, d, *, seed, world):
         at += part.shape[1]
     assert at == n
     return dense
+
+
+# ------------------------------------------------------- the matrix-core NeuTra-HMC trajectory kernels
+MFMA_CHAINS, MFMA_WAVES, CK_MAX_GRID = 128, 8, 256    # csrc/mfma_device.hpp: kMfmaChains, kMfmaWaves, kCkMaxGrid
+
+
+def neutra_presented_hidden(d, nh, hl, n_bins=0):
+    """the conditioner width NeuTra presents to nfmc_neutra_hmc_steps_f32 (NeuTra._min_hidden, NFMC_NEUTRA_VALU unset):
+    at d = 64 / 128 with one or two hidden layers and affine couplings at least 64 (zero-padded), else the flow's own"""
+    return max(nh, 64) if d in (64, 128) and hl in (1, 2) and not n_bins else nh
+
+
+def neutra_hmc_kernel_of(d, nh, hl, n_bins=0):
+    """Which kernel nfmc_neutra_hmc_steps_f32 runs a NeuTra-HMC launch on, from the documented shape rules (DESIGN.md
+    section 3.3) for a flow of conditioner width nh, hl hidden layers and n_bins spline bins (0: affine) as the sampler
+    presents it: 'mfma' (neutra_leapfrog_mfma_kernel: d = 64 / 128, width up to 128, 1-2 hidden layers, narrower
+    conditioners padded to 64), 'wide' (neutra_leapfrog_wide_kernel: the other multiples of 32 from 32 to 512 with
+    32 < nh <= 128), 'valu' (the one-chain-per-lane kernels: widths up to 32, and every spline flow, which the entry point
+    sends there whatever its width), None where no kernel takes the shape."""
+    h = neutra_presented_hidden(d, nh, hl, n_bins)
+    if n_bins or h <= 32:
+        return 'valu'
+    if hl not in (1, 2) or h > 128:
+        return None
+    if d in (64, 128):
+        return 'mfma'
+    return 'wide' if d % 32 == 0 and 32 <= d <= 512 else None
+
+
+def _padded_hidden(h):
+    return 64 if h <= 64 else 128                      # nfmc_realnvp_padded_hidden above 32
+
+
+def neutra_hmc_scratch_bytes(kernel, n, d, hidden, hl, cl):
+    """The work area of one launch in bytes, restated per kernel; `hidden` the presented width.
+    'wide' (csrc/mfma_wide.hip: nfmc_neutra_wide_scratch_floats): the gradient (n, d), U~ (n rounded up to 4), and three
+      rows of d floats (position, gradient, momentum) per chain slot of min(tiles, 256) workgroups of 128 chains.
+    'mfma' (csrc/neutra_kernels.hip: nfmc_neutra_scratch_bytes): momentum and gradient (n, d), U~ and H0 (n), and per
+      workgroup slot and wave the checkpoints of every coupling layer: 256 floats per 16-wide tile of the hidden
+      activations (of both hidden layers when there are two) and of the d / 16 output tiles."""
+    tiles = -(-n // MFMA_CHAINS)
+    slots = min(tiles, CK_MAX_GRID)
+    if kernel == 'wide':
+        return 4 * (n * d + (n + 3) // 4 * 4 + 3 * slots * MFMA_CHAINS * d)
+    assert kernel == 'mfma', kernel
+    layer_floats = ((2 if hl > 1 else 1) * (_padded_hidden(hidden) // 16) + d // 16) * 256
+    return 4 * (2 * n * d + 2 * n + slots * MFMA_WAVES * cl * layer_floats)
+
+
+NeutraRun = collections.namedtuple('NeutraRun', 'rc samples masks log_ratios z stats scratch_bytes')
+
+
+def _direct_neutra_hmc(dev, p, f, T, L, h, seed, *, adjust=True, imd=None, step0=0, chain_offset=0, replay=None, stats=None,
+                       store=None, hidden=None, prefill=None, poison=False, edit=None):
+    """One nfmc_neutra_hmc_steps_f32 call of T transitions (L leapfrog steps of size h) from the latents p.x0 through
+    ctypes: a NeutraRun of the return code, the kept states, the masks and log ratios (T, n) the kernel wrote, the final
+    latents and the statistics, on the CPU.  The work area is sized with nfmc_neutra_scratch_bytes (scratch_bytes).
+    imd: the inverse mass diagonal (d,), None: the kernels' unit diagonal.  step0, chain_offset: NfmcRng's.
+    replay: (normals (T, n, d), uniforms (T, n)) in place of the Philox streams.
+    stats: 'immediate' (DeviceStats.struct()) or 'deferred' (struct(defer=True), which the entry point refuses); the
+      totals come back as a dict (accepted, attempted, nonfinite, sum_x, sum_x2) when the call returned 0.
+    prefill: (value, count): sum_x and sum_x2 start at `value`, every counter at `count`.
+    store: (thinning, max_samples) of a DeviceSampleStore of T offered transitions (kept rows in chronological order);
+      None: a dense (T, n, d) store.
+    hidden: the conditioner width the flow is packed to (None: neutra_presented_hidden).
+    poison: the work area and the statistics scratch are filled with NaN before the launch.
+    edit(args, run): spoils the arguments before the call (the refusals).  z, the mass diagonal and the work area each
+      have 16 spare bytes behind them, so a pointer moved by 4 bytes stays inside its allocation."""
+    from nfmc_amd import hip
+    from nfmc_amd.containers import DeviceSampleStore
+    n, d = p.x0.shape[0], p.d
+    bij = f.bijection
+    if hidden is None:
+        hidden = neutra_presented_hidden(d, bij.n_hidden, bij.n_hidden_layers, bij.n_bins)
+    st, _keep = bij.packed(dev, hidden)
+    sbytes = int(hip.lib().nfmc_neutra_scratch_bytes(n, d, max(bij.n_hidden, hidden), int(st.n_hidden_layers), int(st.n_coupling)))
+    zbuf = torch.zeros(n * d + 4, dtype=torch.float32, device=dev)
+    z = zbuf[:n * d].view(n, d)
+    z.copy_(p.x0.reshape(n, d).float())
+    mbuf = None
+    if imd is not None:
+        mbuf = torch.ones(d + 4, dtype=torch.float32, device=dev)
+        mbuf[:d].copy_(imd.float())
+    work = torch.zeros(sbytes // 4 + 4, dtype=torch.float32, device=dev)
+    masks = torch.zeros(T, n, dtype=torch.uint8, device=dev)
+    lr = torch.zeros(T, n, dtype=torch.float32, device=dev)
+    samples = torch.zeros(T, n, d, dtype=torch.float32, device=dev) if store is None else DeviceSampleStore(n, d, dev, T, *store)
+    a = hip.NfmcNeutraHmcArgs()
+    a.z, a.n, a.n_steps, a.n_leapfrog, a.step_size, a.adjust = hip.ptr(z), n, T, L, h, 1 if adjust else 0
+    a.inv_mass_diag = None if mbuf is None else hip.ptr(mbuf)
+    a.flow, a.pot = st, p.pot.descriptor(dev)
+    keep = None
+    if replay is not None:
+        keep = (replay[0].float().reshape(T, n, d).to(dev).contiguous(), None if replay[1] is None else replay[1].float().to(dev).contiguous())
+    a.rng = hip.make_rng(seed, chain_offset, step0, *(keep or ()))
+    assert stats in (None, 'immediate', 'deferred'), stats
+    acc = None
+    if stats is not None:
+        acc = hip.DeviceStats(d, dev)
+        if prefill is not None:
+            acc._buf[:2 * d].fill_(prefill[0])
+            acc._buf[2 * d:].view(torch.int64).fill_(prefill[1])
+        a.stats = acc.struct(defer=True, attempted=n * T) if stats == 'deferred' else acc.struct()
+    if poison:
+        work.fill_(float('nan'))
+        if acc is not None:
+            acc.scratch.fill_(float('nan'))
+    a.samples = hip.store_struct(samples, T)
+    a.masks_out, a.log_ratio_out = hip.ptr(masks, torch.uint8), hip.ptr(lr)
+    a.scratch, a.scratch_bytes = hip.ptr(work), sbytes
+    run = NeutraRun(None, samples, masks, lr, z, acc, sbytes)
+    if edit is not None:
+        edit(a, run)
+    rc = int(hip.lib().nfmc_neutra_hmc_steps_f32(C.byref(a), hip.stream()))
+    torch.cuda.synchronize()
+    kept = samples.cpu() if store is None else samples.ordered().cpu().clone()
+    totals = None
+    if stats is not None and rc == 0:
+        sum_x, sum_x2, cnt, _jc = acc.host_totals()
+        totals = {'accepted': int(cnt[hip.CNT_ACCEPTED]), 'attempted': int(cnt[hip.CNT_ATTEMPTED]),
+                  'nonfinite': int(cnt[hip.CNT_NONFINITE]), 'sum_x': sum_x.clone(), 'sum_x2': sum_x2.clone()}
+    return NeutraRun(rc, kept, masks.cpu().bool(), lr.cpu(), z.cpu().clone(), totals, sbytes)
+
+
+def neutra_hmc_oracle(p, of, T, L, h, seed, *, adjust=True, imd=None, step0=0, chain_offset=0, noise=None, dtype=torch.float64):
+    """oracle.samplers.mcmc_sample on the adjusted target of the oracle flow `of` from the latents p.x0, on the Philox
+    streams of `seed` (or the `noise` given).  dtype float32: the same oracle with the flow, the inputs and the noise
+    cast to float32, which measures what fp32 arithmetic alone does to a trajectory (neutra_hmc_figures)."""
+    from oracle import samplers as osamp
+    if dtype == torch.float32:
+        of = copy.deepcopy(of).float()
+    if noise is None:
+        noise = osamp.PhiloxNoise(seed, chain_offset, dtype=dtype)
+    return osamp.mcmc_sample(p.x0.to(dtype), osamp.neutra_adjusted_target(of, p.target, (p.d,)), 'hmc', T, h,
+                             None if imd is None else imd.to(dtype), L, adjust, noise, step0)
+
+
+def neutra_hmc_figures(tr64, tr32):
+    """(state figure, log-ratio figure): the worst difference of the kept states and of the log ratios between the fp32
+    and the fp64 run of the oracle on the same inputs and noise, over the rows (transition, chain) up to and including
+    a chain's first decision that differs between the two (from there they are on different trajectories).  An
+    unadjusted run has no log ratios: its second figure is 0."""
+    x64, x32 = tr64.stacked().double(), tr32.stacked().double()
+    n = x64.shape[1]
+    m64, m32 = (torch.stack([m.reshape(-1).bool() for m in t.masks]) for t in (tr64, tr32))
+    same = m64 == m32
+    first = torch.ones(1, n, dtype=torch.bool)
+    before = torch.cumprod(torch.cat([first, same[:-1]]).int(), 0).bool()         # the transition starts from a common state
+    state = float(((x64 - x32).abs().amax(2))[before & same].max())
+    if not tr64.log_ratios:
+        return state, 0.0
+    l64, l32 = (torch.stack([v.reshape(-1).double() for v in t.log_ratios]) for t in (tr64, tr32))
+    return state, float((l64 - l32).abs()[before].max())
+
+
+def neutra_hmc_inputs_ok(tr, what, *, margin, lo=0.30, hi=0.95, cap=0.10):
+    """What an oracle-backed NeuTra-HMC case asks of its inputs, from the fp64 oracle alone: an acceptance between lo
+    and hi (both branches of the masked update run), under `cap` of the chains within `margin` (a number or (T, n):
+    neutra_hmc_row_tolerance) of a tie at any transition, every log ratio finite.  Returns (acceptance, tie share)."""
+    lr = torch.stack([v.reshape(-1).double() for v in tr.log_ratios])
+    lu = torch.stack([v.reshape(-1).double() for v in tr.uniforms])
+    acc = tr.n_accepted / tr.n_attempted
+    ties = float(((lu - lr).abs() < margin).any(0).float().mean())
+    print('%s: oracle accepts %.3f, %.1f %% of the chains within %.1e of a tie, log ratios %.2f .. %.2f'
+          % (what, acc, 100 * ties, float(torch.as_tensor(margin).max()), float(lr.min()), float(lr.max())))
+    assert bool(torch.isfinite(lr).all()), (what, 'log ratio')
+    assert lo <= acc <= hi, (what, 'acceptance', acc)
+    assert ties < cap, (what, 'near-ties', ties)
+    return acc, ties
+
+
+class _Stacked:
+    """a NeutraRun as compare_decisions reads a Record"""
+
+    def __init__(self, run):
+        self.run = run
+
+    def stacked(self):
+        return self.run.masks, self.run.log_ratios
+
+
+def neutra_magnitude(p, of):
+    """|U~| of a batch of latents in fp64 on the oracle flow: compare_decisions' `mag`"""
+    from oracle import samplers as osamp
+    adjusted = osamp.neutra_adjusted_target(of, p.ref, (p.d,))
+
+    def mag(z):
+        with torch.no_grad():
+            return adjusted(z).abs()
+    return mag
+
+
+def neutra_hmc_row_tolerance(tr, p, of, lr_figure):
+    """(T, n): compare_decisions' bound on an fp32 log ratio, 2e-4 max(1, d / 64) + 1e-4 |log r| + 8 ulp(fp32) |U~(z)|
+    at the state z each transition starts from, raised to SPLINE_C_FACTOR x lr_figure where that is larger.  It is also
+    the near-tie margin of the run: a kernel whose log ratio is within this of the oracle's may decide a closer call the
+    other way."""
+    states = tr.stacked().double()
+    prev = torch.cat([p.x0.double()[None], states[:-1]]).reshape(-1, p.d)
+    lr = torch.stack([v.reshape(-1).double() for v in tr.log_ratios])
+    tol = 2e-4 * max(1.0, p.d / 64) + 1e-4 * lr.abs() + 8 * 2.0 ** -24 * neutra_magnitude(p, of)(prev).reshape(lr.shape)
+    return tol.clamp_min(SPLINE_C_FACTOR * lr_figure)
+
+
+def compare_neutra_hmc(run, tr, p, of, what, *, atol, lr_figure, adjust=True):
+    """One launch against the oracle trace, row by row: the kept states by compare_states (tie-aware at the rows'
+    tolerance neutra_hmc_row_tolerance, cap 0.10, to atol), the masks and log ratios by compare_decisions at that
+    tolerance; and, what compare_decisions leaves to a share, every decision of a chain that has followed the oracle so
+    far and is further than twice the row's tolerance from a tie equals the oracle's.  Returns (worst state error over
+    atol, worst log-ratio error over tolerance)."""
+    assert run.rc == 0, (what, run.rc)
+    assert torch.equal(run.z, run.samples[-1]), what
+    if not adjust:
+        keep = compare_states(run.samples, tr, what, margin=0.0, atol=atol, rtol=0.0)
+        compare_decisions(_Stacked(run), tr, 'uhmc', p.x0, p.ref, what)
+        assert bool((run.log_ratios == 0).all()), what
+        return float((run.samples.double() - tr.stacked().double()).abs().max()) / atol, 0.0
+    tol = neutra_hmc_row_tolerance(tr, p, of, lr_figure)
+    keep = compare_states(run.samples, tr, what, margin=tol, atol=atol, rtol=0.0)
+    state_ratio = float((run.samples[:, keep].double() - tr.stacked()[:, keep].double()).abs().max()) / atol if bool(keep.any()) else 0.0
+    ratio = compare_decisions(_Stacked(run), tr, 'hmc', p.x0, p.ref, what, mag=neutra_magnitude(p, of),
+                              at_least=SPLINE_C_FACTOR * lr_figure)
+    want_m = torch.stack([m.reshape(-1).bool() for m in tr.masks])
+    want_lr = torch.stack([v.reshape(-1).double() for v in tr.log_ratios])
+    lu = torch.stack([v.reshape(-1).double() for v in tr.uniforms])
+    same = run.masks == want_m
+    follows = torch.cumprod(torch.cat([torch.ones(1, same.shape[1], dtype=torch.bool), same[:-1]]).int(), 0).bool()
+    wrong = follows & ((lu - want_lr).abs() > 2 * tol) & ~same
+    assert not bool(wrong.any()), (what, 'decisions differ on %d rows clear of a tie' % int(wrong.sum()))
+    return state_ratio, ratio
 
 
 # ------------------------------------------------------------------------ the refusing C entry points

@@ -4,6 +4,7 @@ error it exists to catch.  The trace is a real one: oracle.samplers.mcmc_sample,
 chains, 3 transitions) with PhiloxNoise; the flow-proposal comparison (compare_flow_mh) has imh_sample traces of its own
 below, and the last test runs the inputs of every flow-MH case of the GPU files through the fp64 oracle alone."""
 import copy
+import ctypes
 import functools
 
 import pytest
@@ -412,3 +413,211 @@ def test_the_flow_mh_cases_of_a_gpu_file_hold_their_input_conditions_on_the_orac
     acc = [float(ln.split('oracle accepts ')[1].split()[0]) for ln in lines if 'oracle accepts' in ln]
     assert count >= len(getattr(module, 'FLOW_CASES', ())) and len(lines) >= count
     print('%s: %d cases, oracle acceptance %.3f .. %.3f' % (name, count, min(acc), max(acc)))
+
+
+# ------------------------------------------------------------- the NeuTra-HMC comparisons (test_gpu_neutra_hmc_wide.py)
+ND, NN, NT, NL, NH_STEP = 8, 48, 3, 2, 0.55
+
+
+@functools.lru_cache(maxsize=None)
+def _neutra_case():
+    """(problem at its latent starts, oracle flow, fp64 trace, fp32 trace) of a small NeuTra-HMC run on U = sum x^2"""
+    from nfmc_amd.potentials import SumOfSquares
+    from oracle import potentials as opot
+    z0 = 0.5 * torch.randn(NN, ND, generator=torch.Generator().manual_seed(4))
+    p = H.Problem(SumOfSquares((ND,)), opot.sum_squares, opot.sum_squares, z0, ND, 'host neutra')
+    centre = (torch.zeros(ND, dtype=torch.float64), torch.ones(ND, dtype=torch.float64))
+    _f, of = H.centred_flow_pair(p, 5, 8, False, 3, scale=0.1, centre=centre, hidden_layers=1)
+    tr = H.neutra_hmc_oracle(p, of, NT, NL, NH_STEP, 9)
+    tr32 = H.neutra_hmc_oracle(p, of, NT, NL, NH_STEP, 9, dtype=torch.float32)
+    assert 0 < tr.n_accepted < NN * NT
+    return p, of, tr, tr32
+
+
+def _neutra_run(tr, **changed):
+    """the oracle's own output as a NeutraRun, with the fields given replaced"""
+    kept = tr.stacked().float()
+    run = H.NeutraRun(0, kept, torch.stack([m.reshape(-1).bool() for m in tr.masks]),
+                      torch.stack([v.reshape(-1).float() for v in tr.log_ratios]) if tr.log_ratios else torch.zeros(NT, NN), kept[-1].clone(), None, 0)
+    return run._replace(**changed)
+
+
+def _neutra_compare(run, tr, adjust=True):
+    p, of, _tr, _tr32 = _neutra_case()
+    return H.compare_neutra_hmc(run, tr, p, of, 'host neutra', atol=1e-5, lr_figure=1e-6, adjust=adjust)
+
+
+def test_neutra_figures_measure_the_fp32_oracle():
+    """both figures are positive and of the size of fp32 rounding; a trace against itself gives zero; a decision that
+    differs ends a chain's rows, so that its later states do not count"""
+    _p, _of, tr, tr32 = _neutra_case()
+    state, lr = H.neutra_hmc_figures(tr, tr32)
+    assert 1e-8 < state < 1e-5 and 1e-8 < lr < 1e-4, (state, lr)
+    assert H.neutra_hmc_figures(tr, tr) == (0.0, 0.0)
+    other = copy.copy(tr32)
+    other.masks = [m.clone() for m in tr32.masks]
+    other.samples = [s.clone() for s in tr32.samples]
+    other.masks[0][3] ^= True
+    other.samples[1][3] += 5.0                                          # after the differing decision: not measured
+    assert H.neutra_hmc_figures(tr, other)[0] <= state
+    other.samples[0][4] += 5.0                                          # a chain that still follows: measured
+    assert H.neutra_hmc_figures(tr, other)[0] > 4.9
+
+
+def test_neutra_inputs_conditions_fail_when_they_should():
+    p, of, tr, _tr32 = _neutra_case()
+    tol = H.neutra_hmc_row_tolerance(tr, p, of, 1e-6)
+    assert tol.shape == (NT, NN) and float(tol.min()) >= 2e-4
+    assert float(H.neutra_hmc_row_tolerance(tr, p, of, 1.0).min()) == H.SPLINE_C_FACTOR
+    acc, ties = H.neutra_hmc_inputs_ok(tr, 'host', margin=tol)
+    assert acc == tr.n_accepted / (NN * NT) and ties < 0.10
+    for kw in ({'margin': tol, 'lo': acc + 0.01}, {'margin': tol, 'hi': acc - 0.01}, {'margin': 1e3}):
+        with pytest.raises(AssertionError):
+            H.neutra_hmc_inputs_ok(tr, 'host', **kw)
+    bad = copy.copy(tr)
+    bad.log_ratios = [v.clone() for v in tr.log_ratios]
+    bad.log_ratios[1][0] = float('nan')
+    with pytest.raises(AssertionError):
+        H.neutra_hmc_inputs_ok(bad, 'host', margin=tol)
+
+
+def test_neutra_comparison_passes_on_the_oracles_own_and_fails_on_each_error():
+    p, of, tr, _tr32 = _neutra_case()
+    state_ratio, lr_ratio = _neutra_compare(_neutra_run(tr), tr)
+    assert state_ratio < 0.1 and lr_ratio < 0.1
+    tol = H.neutra_hmc_row_tolerance(tr, p, of, 1e-6)
+    lr = torch.stack([v.reshape(-1).double() for v in tr.log_ratios])
+    lu = torch.stack([v.reshape(-1).double() for v in tr.uniforms])
+    clear = int(torch.nonzero(((lu - lr).abs() > 10 * tol).all(0))[0])
+    run = _neutra_run(tr)
+    kept = run.samples.clone()
+    kept[1, clear, 3] += 3e-5                                             # a kept state off by three times atol
+    with pytest.raises(AssertionError):
+        _neutra_compare(run._replace(samples=kept), tr)
+    with pytest.raises(AssertionError):                                   # the final latents are not the last kept row
+        _neutra_compare(run._replace(z=run.z + 1.0), tr)
+    with pytest.raises(AssertionError):
+        _neutra_compare(run._replace(rc=-4), tr)
+    logr = run.log_ratios.clone()
+    logr[2, clear] += 2 * float(tol[2, clear])                            # one log ratio off by twice its tolerance
+    with pytest.raises(AssertionError):
+        _neutra_compare(run._replace(log_ratios=logr), tr)
+    masks = run.masks.clone()
+    masks[NT - 1, clear] ^= True                                          # one decision clear of a tie, the states left alone
+    with pytest.raises(AssertionError):
+        _neutra_compare(run._replace(masks=masks), tr)
+    # the raised tolerance: with the row's tolerance as the log-ratio figure (4 x it allowed) the same error passes
+    H.compare_neutra_hmc(run._replace(log_ratios=logr), tr, p, of, 'host neutra', atol=1e-5, lr_figure=float(tol[2, clear]))
+
+
+def test_neutra_unadjusted_comparison():
+    p, of, _tr, _tr32 = _neutra_case()
+    tr = H.neutra_hmc_oracle(p, of, NT, NL, NH_STEP, 9, adjust=False)
+    run = _neutra_run(tr)
+    assert _neutra_compare(run, tr, adjust=False)[1] == 0.0
+    masks = run.masks.clone()
+    masks[1, 7] = False
+    with pytest.raises(AssertionError):
+        _neutra_compare(run._replace(masks=masks), tr, adjust=False)
+    with pytest.raises(AssertionError):
+        _neutra_compare(run._replace(log_ratios=run.log_ratios + 0.5), tr, adjust=False)
+    kept = run.samples.clone()
+    kept[0, 0, 0] += 3e-5
+    with pytest.raises(AssertionError):
+        _neutra_compare(run._replace(samples=kept), tr, adjust=False)
+
+
+def test_decisions_tolerance_is_raised_to_the_figure_given_and_not_lowered():
+    x0, tr = _case()
+    rec = _oracle_rec(tr)
+    want = float(tr.log_ratios[0].reshape(-1)[5])
+    rec.lr = rec.lr.clone()
+    rec.lr[0, 5] = want + 2 * _tol(D, want, float(_u(x0[5].double())))
+    assert H.compare_decisions(rec, tr, 'mala', x0, _u, 'host', at_least=1.0) < 1.0
+    with pytest.raises(AssertionError):
+        H.compare_decisions(rec, tr, 'mala', x0, _u, 'host', at_least=1e-9)
+    assert H.compare_decisions(_oracle_rec(tr), tr, 'mala', x0, _u, 'host') < 0.05
+
+
+def test_oracle_chain_offset_and_step_offset_are_the_whole_runs():
+    """rows [20, 48) with chain_offset = 20 are those rows of the whole run, and a run from step0 = 1 started at the
+    whole run's first kept states is its transitions 1 and 2: what the GPU tests' offsets are compared with"""
+    p, of, tr, _tr32 = _neutra_case()
+    part = H.neutra_hmc_oracle(H.with_starts(p, p.x0[20:]), of, NT, NL, NH_STEP, 9, chain_offset=20)
+    assert torch.equal(part.stacked(), tr.stacked()[:, 20:])
+    later = H.neutra_hmc_oracle(H.with_starts(p, tr.stacked()[0].float()), of, NT - 1, NL, NH_STEP, 9, step0=1)
+    x1 = tr.stacked()[0]
+    same = (x1.float().double() == x1).all(1)                               # chains whose fp32 restart is exact: the rejected ones
+    assert bool(same.any())
+    assert torch.allclose(later.stacked(), tr.stacked()[1:], atol=1e-5)
+
+
+def test_direct_neutra_hmc_builds_the_call(monkeypatch):
+    """_direct_neutra_hmc against a stand-in library (no GPU): the arguments that reach nfmc_neutra_hmc_steps_f32 (shape,
+    step size, offsets, the work area nfmc_neutra_scratch_bytes sized, a dense store, the (T, n) mask and log-ratio
+    buffers, replayed noise, the packed width), the prefilled accumulators, the edit hook, and what comes back."""
+    from nfmc_amd import hip
+    n, d, steps = 5, ND, 3
+    seen = {}
+
+    class Lib:
+        @staticmethod
+        def nfmc_neutra_scratch_bytes(n_, d_, h_, hl_, cl_):
+            seen['sized'] = (n_, d_, h_, hl_, cl_)
+            return 4096
+
+        @staticmethod
+        def nfmc_stats_scratch_bytes(d_):
+            return 8 * 64
+
+        @staticmethod
+        def nfmc_neutra_hmc_steps_f32(ref, stream):
+            a = ref._obj
+            seen['args'] = {k: getattr(a, k) for k in ('n', 'n_steps', 'n_leapfrog', 'adjust', 'scratch_bytes')}
+            seen['h'] = a.step_size
+            seen['rng'] = (a.rng.seed, a.rng.chain_offset, a.rng.step0, bool(a.rng.replay_normals), bool(a.rng.replay_uniforms))
+            seen['store'] = (a.samples.stride, a.samples.countdown, a.samples.ring_rows, a.samples.row)
+            seen['imd'], seen['defer'] = bool(a.inv_mass_diag), a.stats.defer
+            return seen.get('rc', 0)
+
+    class Bij:
+        n_hidden, n_hidden_layers, n_bins = 6, 2, 0
+
+        def packed(self, dev, hidden):
+            seen['hidden'] = hidden
+            st = hip.NfmcRealNVP()
+            st.n_hidden_layers, st.n_coupling = 2, 3
+            return st, None
+
+    class Flow:
+        bijection = Bij()
+
+    class Pot:
+        def descriptor(self, dev):
+            return hip.NfmcPotential()
+
+    monkeypatch.setattr(hip, 'lib', lambda: Lib)
+    monkeypatch.setattr(hip, 'ptr', lambda t, dtype=torch.float32: None if t is None else ctypes.c_void_p(t.data_ptr()))
+    monkeypatch.setattr(hip, 'stream', lambda: None)
+    monkeypatch.setattr(torch.cuda, 'synchronize', lambda *a, **k: None)
+    cpu = torch.device('cpu')
+    p = H.Problem(Pot(), _u, _u, torch.arange(n * d, dtype=torch.float32).reshape(n, d), d, 'stand-in')
+    r = H._direct_neutra_hmc(cpu, p, Flow(), steps, 2, 0.25, 9)
+    assert r.rc == 0 and r.samples.shape == (steps, n, d) and r.masks.shape == r.log_ratios.shape == (steps, n) and r.stats is None
+    assert torch.equal(r.z, p.x0) and r.scratch_bytes == 4096 and r.masks.dtype == torch.bool
+    assert seen['sized'] == (n, d, 6, 2, 3) and seen['hidden'] == 6           # d = 8: the flow's own width
+    assert seen['args'] == {'n': n, 'n_steps': steps, 'n_leapfrog': 2, 'adjust': 1, 'scratch_bytes': 4096} and seen['h'] == 0.25
+    assert seen['rng'] == (9, 0, 0, False, False) and seen['store'] == (1, 0, steps, 0) and not seen['imd'] and seen['defer'] == 0
+    normals, uniforms = torch.randn(steps, n, d), torch.rand(steps, n)
+    r = H._direct_neutra_hmc(cpu, p, Flow(), steps, 2, 0.25, 9, adjust=False, imd=torch.ones(d), step0=6, chain_offset=75, replay=(normals, uniforms),
+                             stats='immediate', prefill=(2.5, 7), store=(2, None), hidden=64,
+                             edit=lambda a, run: setattr(a, 'scratch_bytes', a.scratch_bytes - 1))
+    assert seen['hidden'] == 64 and seen['sized'] == (n, d, 64, 2, 3)
+    assert seen['args'] == {'n': n, 'n_steps': steps, 'n_leapfrog': 2, 'adjust': 0, 'scratch_bytes': 4095}
+    assert seen['rng'] == (9, 75, 6, True, True) and seen['store'] == (2, 0, 2, 0) and seen['imd'] and seen['defer'] == 0
+    assert r.samples.shape == (2, n, d)
+    assert r.stats['accepted'] == r.stats['attempted'] == r.stats['nonfinite'] == 7 and bool((r.stats['sum_x'] == 2.5).all())
+    seen['rc'] = hip.EUNSUPPORTED
+    r = H._direct_neutra_hmc(cpu, p, Flow(), steps, 2, 0.25, 9, stats='deferred')
+    assert r.rc == hip.EUNSUPPORTED and r.stats is None and seen['defer'] == 1
+
