@@ -820,6 +820,43 @@ int64_t nfmc_diag_sums_doubles(int32_t d, int32_t max_lag);            /* 0 for 
 int64_t nfmc_diag_work_bytes(int64_t n, int32_t d, int32_t max_lag);   /* 0 for arguments out of range */
 int nfmc_chain_diagnostics_f32(const NfmcDiagArgs* args, nfmc_stream_t stream);
 
+/* ---- rank transform for the rank-normalised diagnostics (Vehtari et al. 2021): one of four series of the kept states,
+ * each again an (n_draws, n, d) slab for nfmc_chain_diagnostics_f32.  Per coordinate the S = n_draws * n values
+ * v_1 .. v_S are pooled over draws and chains and compared numerically (-0 = +0); x_(k) is the k-th smallest, k = 0 .. S-1.
+ *     rank       r_i = #{v < v_i} + (#{v = v_i} + 1) / 2                 (1-based average rank)
+ *     score      z_i = Phi^-1((r_i - 3/8) / (S + 1/4)), in fp64 (AS 241 PPND16), rounded to fp32 once
+ *     median     med = (x_(floor((S-1)/2)) + x_(ceil((S-1)/2))) / 2 in fp64
+ *     NFMC_RANK_BULK       z of v
+ *     NFMC_RANK_FOLDED     z of f, f_i = fl32(|fp64(v_i) - med|), ranked anew
+ *     NFMC_RANK_TAIL_LOW   1 where v_i <= x_(floor((S-1)/20)), else 0   (the type-7 5 % quantile on fp32 data)
+ *     NFMC_RANK_TAIL_HIGH  1 where v_i >= x_(ceil(19 (S-1)/20)), else 0 (the type-7 95 % quantile)
+ * A coordinate with a NaN or +-Inf in x is NaN in every series and counted in `nonfinite`; the others are unaffected.
+ * The outputs are functions of the values alone (a keys-only radix sort per coordinate, then two binary searches per
+ * element): no floating-point atomic, the same bits on every call.  x is only read.
+ * work: nfmc_rank_work_bytes = 32 d  +  2 * 4 S d (two key buffers of the slab's size)  +  1024 d ceil(S / 2048) (digit
+ * counts of the sort) bytes, 8-byte aligned, no initialisation needed.
+ * NFMC_EINVAL: NULL x / out / nonfinite / work, out == x, non-positive size, n_draws < 4, unknown series; NFMC_ESHAPE:
+ * d > 1024 or S >= 2^31; NFMC_ESCRATCH: work too small.  All answered before any launch. */
+#define NFMC_RANK_BULK 0
+#define NFMC_RANK_FOLDED 1
+#define NFMC_RANK_TAIL_LOW 2
+#define NFMC_RANK_TAIL_HIGH 3
+typedef struct {
+    const float* x;           /* (n_draws, n, d) kept states */
+    int64_t n_draws;
+    int64_t n;
+    int32_t d;                /* <= 1024, as nfmc_chain_diagnostics_f32 */
+    int32_t series;           /* NFMC_RANK_* */
+    float* out;               /* (n_draws, n, d); must not alias x */
+    double* order_stats;      /* (d, 4) or NULL: x_(floor((S-1)/20)), the two middle order statistics, x_(ceil(19 (S-1)/20)),
+                                 as fp64 (a zero is +0; NaN where the order statistic is not finite) */
+    int32_t* nonfinite;       /* (d,) count of NaN / Inf values per coordinate */
+    void* work;
+    int64_t work_bytes;       /* >= nfmc_rank_work_bytes(n_draws, n, d) */
+} NfmcRankArgs;
+int64_t nfmc_rank_work_bytes(int64_t n_draws, int64_t n, int32_t d);   /* 0 for arguments out of range */
+int nfmc_rank_series_f32(const NfmcRankArgs* args, nfmc_stream_t stream);
+
 /* Philox normals / uniforms alone (tests pin the native stream against oracle/philox.py). */
 int nfmc_philox_normals_f32(const NfmcRng* rng, int32_t tag, int64_t n, int32_t d, float* out, nfmc_stream_t stream);
 int nfmc_philox_uniforms_f32(const NfmcRng* rng, int32_t tag, int64_t n, float* out, nfmc_stream_t stream);

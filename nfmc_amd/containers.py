@@ -426,14 +426,16 @@ class MCMCOutput:
             self.running_samples.spill()
         return self
 
-    def diagnostics(self, max_lag: int = None, superchains: int = None, shard=None):
+    def diagnostics(self, max_lag: int = None, superchains: int = None, shard=None, rank_normalized: bool = False):
         """Split R-hat, ESS (and, with `superchains` = chains per superchain, the nested R-hat) of the kept states, per
         coordinate: `diagnostics.diagnose` on the device-resident store, no host copy of the states.  A thinned or
-        windowed store is diagnosed as kept (ESS in units of kept draws)."""
+        windowed store is diagnosed as kept (ESS in units of kept draws).  `rank_normalized=True` adds the rank-normalised
+        bulk / tail R-hat and ESS (not across shards)."""
         if not self.store_samples:
             raise ValueError('diagnostics need the kept states: run with store_samples=True')
         from . import diagnostics
-        return diagnostics.diagnose(self.samples_device, max_lag=max_lag, superchains=superchains, shard=shard)
+        return diagnostics.diagnose(self.samples_device, max_lag=max_lag, superchains=superchains, shard=shard,
+                                    rank_normalized=rank_normalized)
 
     def resample(self, n: int) -> torch.Tensor:
         """n draws with replacement from all kept (step, chain) states."""

@@ -1,9 +1,10 @@
 // Stand-alone pieces of the path: K6 accept/select, K7 moments, the Langevin proposal / log-ratio for
 // targets whose U and grad U come from outside (arbitrary Python callables differentiated by torch
 // autograd on the GPU), the native Philox streams on their own (pinned against oracle/philox.py), and the convergence
-// diagnostics of the kept states (diagnostics.hpp).
+// diagnostics of the kept states (diagnostics.hpp) with their rank transform (rank_kernels.hpp).
 #include "common.hpp"
 #include "diagnostics.hpp"
+#include "rank_kernels.hpp"
 
 namespace nfmc {
 
@@ -349,6 +350,73 @@ extern "C" int nfmc_chain_diagnostics_f32(const NfmcDiagArgs* args, nfmc_stream_
     NFMC_HIP_CHECK_LAUNCH();
     hipLaunchKernelGGL(diag_fold_kernel, dim3(grid_for(wg * (kBlock / kDiagFoldCols))), dim3(kBlock), 0, st,
                        work + p.off_group, p.gs, wg, wg, (int64_t)0, a.sums + head);
+    NFMC_HIP_CHECK_LAUNCH();
+    return NFMC_OK;
+}
+
+static bool rank_shape_ok(int64_t n_draws, int64_t n, int32_t d) {
+    return n_draws >= 4 && n > 0 && d > 0 && d <= 1024 && n < ((int64_t)1 << 31) / n_draws;   // S < 2^31
+}
+
+extern "C" int64_t nfmc_rank_work_bytes(int64_t n_draws, int64_t n, int32_t d) {
+    if (!rank_shape_ok(n_draws, n, d)) return 0;
+    return rank_plan(n_draws, n, d).total;
+}
+
+// keys (d, S) in `a` sorted per coordinate, through `b` and back: four passes, so the result is in `a` again
+static int rank_sort(uint32_t* a, uint32_t* b, uint32_t* hist, const RankPlan& p, int d, hipStream_t st) {
+    const int grid = (int)(p.tiles < kMaxGrid ? p.tiles : kMaxGrid);
+    for (int pass = 0; pass < kRankPasses; ++pass) {
+        const uint32_t* src = pass & 1 ? b : a;
+        uint32_t* dst = pass & 1 ? a : b;
+        hipLaunchKernelGGL(rank_hist_kernel, dim3(grid), dim3(kBlock), 0, st, src, p.S, p.ntile, p.tiles, 8 * pass, hist);
+        NFMC_HIP_CHECK_LAUNCH();
+        hipLaunchKernelGGL(rank_scan_kernel, dim3(d), dim3(kRankScanBlock), 0, st, hist, p.ntile, d);
+        NFMC_HIP_CHECK_LAUNCH();
+        hipLaunchKernelGGL(rank_scatter_kernel, dim3(grid), dim3(kBlock), 0, st, src, dst, p.S, p.ntile, p.tiles, 8 * pass,
+                           (const uint32_t*)hist);
+        NFMC_HIP_CHECK_LAUNCH();
+    }
+    return NFMC_OK;
+}
+
+extern "C" int nfmc_rank_series_f32(const NfmcRankArgs* args, nfmc_stream_t stream) {
+    if (!args || !args->x || !args->out || !args->nonfinite || !args->work) return NFMC_EINVAL;
+    const NfmcRankArgs a = *args;
+    if (a.out == a.x || a.n <= 0 || a.d <= 0 || a.n_draws < 4 || a.series < NFMC_RANK_BULK || a.series > NFMC_RANK_TAIL_HIGH)
+        return NFMC_EINVAL;
+    if (!rank_shape_ok(a.n_draws, a.n, a.d)) return NFMC_ESHAPE;
+    if (a.work_bytes < nfmc_rank_work_bytes(a.n_draws, a.n, a.d)) return NFMC_ESCRATCH;
+    const RankPlan p = rank_plan(a.n_draws, a.n, a.d);
+    char* base = (char*)a.work;
+    double* ostat = (double*)base;
+    uint32_t* keys = (uint32_t*)(base + p.off_keys);
+    uint32_t* alt = (uint32_t*)(base + p.off_alt);
+    uint32_t* hist = (uint32_t*)(base + p.off_hist);
+    hipStream_t st = (hipStream_t)stream;
+    const int d = (int)a.d;
+    const int64_t total = p.S * d;
+    const int64_t xtiles = ((p.S + kRankXp - 1) / kRankXp) * ((d + kRankXp - 1) / kRankXp);
+    const int xgrid = (int)(xtiles < kMaxGrid ? xtiles : kMaxGrid);
+
+    hipLaunchKernelGGL(rank_key_kernel, dim3(xgrid), dim3(kBlock), 0, st, a.x, p.S, d, keys);
+    NFMC_HIP_CHECK_LAUNCH();
+    if (int rc = rank_sort(keys, alt, hist, p, d, st)) return rc;
+    hipLaunchKernelGGL(rank_stats_kernel, dim3((d + kBlock - 1) / kBlock), dim3(kBlock), 0, st, (const uint32_t*)keys, p.S, d,
+                       ostat, a.order_stats, a.nonfinite);
+    NFMC_HIP_CHECK_LAUNCH();
+    const float* ranked = a.x;
+    if (a.series == NFMC_RANK_FOLDED) {   // the folded values go to `out`, are ranked by a second sort and replaced by their scores
+        hipLaunchKernelGGL(rank_fold_kernel, dim3(grid_for(total)), dim3(kBlock), 0, st, a.x, total, d, (const double*)ostat,
+                           a.out);
+        NFMC_HIP_CHECK_LAUNCH();
+        hipLaunchKernelGGL(rank_key_kernel, dim3(xgrid), dim3(kBlock), 0, st, (const float*)a.out, p.S, d, keys);
+        NFMC_HIP_CHECK_LAUNCH();
+        if (int rc = rank_sort(keys, alt, hist, p, d, st)) return rc;
+        ranked = a.out;
+    }
+    hipLaunchKernelGGL(rank_emit_kernel, dim3(grid_for(total)), dim3(kBlock), 0, st, ranked, p.S, d, (int)a.series,
+                       (const uint32_t*)keys, (const double*)ostat, (const int32_t*)a.nonfinite, a.out);
     NFMC_HIP_CHECK_LAUNCH();
     return NFMC_OK;
 }

@@ -1,5 +1,7 @@
 """Convergence diagnostics of a run's kept states: split R-hat, nested R-hat (Margossian et al.) and the effective
-sample size of Stan / Vehtari et al. 2021 (not rank-normalised), per coordinate.
+sample size of Stan / Vehtari et al. 2021, per coordinate; on request also their rank-normalised forms (bulk and
+folded R-hat, bulk and tail ESS), which are the same definitions applied to four rank series of the states that a
+second HIP call produces on the device (nfmc_rank_series_f32, csrc/rank_kernels.hpp).
 
 The heavy part -- per-chain means, half-chain moments and lagged autocovariances of the n x d series -- is one HIP call
 over the device-resident slab (nfmc_chain_diagnostics_f32, csrc/diagnostics.hpp).  It returns per-coordinate fp64 sums
@@ -33,6 +35,16 @@ class Diagnostics:
     n_draws: int
     n_chains: int
     max_lag: int
+    # rank-normalised (Vehtari et al. 2021), None unless asked for: the definitions above applied to the rank series
+    rhat_bulk: Optional[torch.Tensor] = None         # split R-hat of the normal scores of the pooled ranks
+    rhat_tail: Optional[torch.Tensor] = None         # split R-hat of the scores of the ranks of |x - median|
+    rhat_rank: Optional[torch.Tensor] = None         # max of the two: the paper's R-hat
+    ess_bulk: Optional[torch.Tensor] = None          # `ess` of the scores (unsplit chains, as `ess`)
+    ess_tail: Optional[torch.Tensor] = None          # min of `ess` of the indicators x <= q05 and x >= q95
+    truncated_bulk: Optional[torch.Tensor] = None
+    truncated_tail: Optional[torch.Tensor] = None    # of either indicator
+    nested_rhat_bulk: Optional[torch.Tensor] = None  # with superchains: nested R-hat of the scores
+    n_nonfinite: Optional[torch.Tensor] = None       # int64: NaN / Inf values per coordinate (its rank fields are NaN)
 
     def summary(self) -> Dict[str, float]:
         def worst(t, fn):
@@ -43,6 +55,14 @@ class Diagnostics:
                'n_draws': self.n_draws, 'n_chains': self.n_chains, 'max_lag': self.max_lag}
         if self.nested_rhat is not None:
             out['max_nested_rhat'] = worst(self.nested_rhat, torch.max)
+        if self.rhat_rank is not None:
+            out['max_rhat_rank'] = worst(self.rhat_rank, torch.max)
+        if self.ess_bulk is not None:
+            out['min_ess_bulk'] = worst(self.ess_bulk, torch.min)
+        if self.ess_tail is not None:
+            out['min_ess_tail'] = worst(self.ess_tail, torch.min)
+        if self.n_nonfinite is not None:
+            out['n_nonfinite'] = int((self.n_nonfinite > 0).sum())
         return out
 
 
@@ -78,6 +98,55 @@ def chain_sums(x: torch.Tensor, max_lag: int, group: int = 1) -> Dict[str, torch
     with torch.cuda.device(x.device):
         hip.check(lib.nfmc_chain_diagnostics_f32(C.byref(args), hip.stream()), 'nfmc_chain_diagnostics_f32')
     return unpack_sums(sums.cpu(), d)
+
+
+class _RankTransform:
+    """The buffers of nfmc_rank_series_f32 for one slab x (n_draws, n_chains, d): `run(series)` fills the one output slab
+    `out`, `nonfinite` (d,) int32 and `order_stats` (d, 4) fp64 and returns `out`."""
+
+    def __init__(self, x: torch.Tensor):
+        K, n, d = (int(v) for v in x.shape)
+        _check_counts(K, n, 1)
+        self.lib = hip.lib()
+        nbytes = int(self.lib.nfmc_rank_work_bytes(K, n, d))
+        if nbytes <= 0:
+            raise hip.NfmcArgumentError('rank transform: event size %d (<= 1024) or %d x %d pooled draws (< 2^31) outside '
+                                        'the kernel\'s range' % (d, K, n), hip.ESHAPE)
+        self.x = x
+        self.out = torch.empty_like(x)
+        self.nonfinite = torch.empty(d, dtype=torch.int32, device=x.device)
+        self.order_stats = torch.empty(d, 4, dtype=torch.float64, device=x.device)
+        self.work = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)
+        self.args = hip.NfmcRankArgs(hip.ptr(x), K, n, d, 0, hip.ptr(self.out), hip.ptr(self.order_stats, torch.float64),
+                                     hip.ptr(self.nonfinite, torch.int32), hip.ptr(self.work, torch.float64), nbytes)
+
+    def run(self, series) -> torch.Tensor:
+        if series not in hip.RANK_SERIES:
+            raise ValueError('series must be one of %s, got %r' % (sorted(hip.RANK_SERIES), series))
+        self.args.series = hip.RANK_SERIES[series]
+        with torch.cuda.device(self.x.device):
+            hip.check(self.lib.nfmc_rank_series_f32(C.byref(self.args), hip.stream()), 'nfmc_rank_series_f32')
+        return self.out
+
+
+def _device_slab(x: torch.Tensor) -> torch.Tensor:
+    if not x.is_cuda:
+        x = x.to(hip.require_gpu())
+    return x.detach().to(torch.float32).contiguous()
+
+
+def rank_series(x: torch.Tensor, series: str) -> torch.Tensor:
+    """One series of the rank-normalised diagnostics of kept states x (n_draws, n_chains, *event), as a device slab of
+    x's shape (nfmc_rank_series_f32, include/nfmc_hip.h).  Per coordinate the n_draws * n_chains values are pooled and
+    ranked with average ranks for ties: 'bulk' = the normal scores Phi^-1((r - 3/8) / (S + 1/4)) of the ranks, 'folded' =
+    the scores of the ranks of |x - median|, 'tail_low' / 'tail_high' = the 0 / 1 indicators of x <= its 5 % and x >= its
+    95 % quantile.  A coordinate holding a NaN or Inf is NaN throughout."""
+    if x.dim() < 2:
+        raise ValueError('expected (n_draws, n_chains, *event), got %s' % (tuple(x.shape),))
+    x = _device_slab(x)
+    K, n = int(x.shape[0]), int(x.shape[1])
+    out = _RankTransform(x.reshape(K, n, int(math.prod(x.shape[2:])))).run(series)
+    return out.reshape(x.shape)
 
 
 def unpack_sums(flat: torch.Tensor, d: int) -> Dict[str, torch.Tensor]:
@@ -154,12 +223,39 @@ def from_sums(sums: Dict[str, torch.Tensor], n_draws: int, n_chains: int, group:
                        autocorrelation=rho.reshape((L + 1,) + shape), n_draws=K, n_chains=n, max_lag=L)
 
 
-def diagnose(x: torch.Tensor, max_lag: Optional[int] = None, superchains: Optional[int] = None, shard=None) -> Diagnostics:
+def _rank_fields(x: torch.Tensor, max_lag: int, group: Optional[int], event_shape) -> Dict[str, torch.Tensor]:
+    """The rank-normalised fields of `Diagnostics` for the slab x (n_draws, n_chains, d): the four series one after
+    another through one output slab, each through `chain_sums` / `from_sums`."""
+    K, n = int(x.shape[0]), int(x.shape[1])
+    rt = _RankTransform(x)
+    M = 1 if group is None else int(group)
+    res = {s: from_sums(chain_sums(rt.run(s), max_lag, M), K, n, group, event_shape)
+           for s in ('bulk', 'folded', 'tail_low', 'tail_high')}
+    count = rt.nonfinite.cpu().to(torch.int64).reshape(res['bulk'].rhat.shape)
+    bad = count > 0
+
+    def clean(t):
+        return torch.where(bad, torch.full_like(t, math.nan), t)
+    bulk, folded, low, high = res['bulk'], res['folded'], res['tail_low'], res['tail_high']
+    return dict(rhat_bulk=clean(bulk.rhat), rhat_tail=clean(folded.rhat),
+                rhat_rank=clean(torch.maximum(bulk.rhat, folded.rhat)),   # NaN in either is NaN in the max
+                ess_bulk=clean(bulk.ess), ess_tail=clean(torch.minimum(low.ess, high.ess)),
+                truncated_bulk=bulk.truncated & ~bad, truncated_tail=(low.truncated | high.truncated) & ~bad,
+                nested_rhat_bulk=None if group is None else clean(bulk.nested_rhat), n_nonfinite=count)
+
+
+def diagnose(x: torch.Tensor, max_lag: Optional[int] = None, superchains: Optional[int] = None, shard=None,
+             rank_normalized: bool = False) -> Diagnostics:
     """Diagnostics of kept states x (n_draws, n_chains, *event), fp32; host-resident states are moved to the device first.
     `max_lag` defaults to min(n_draws - 1, 127) and is clipped to n_draws - 1.  `superchains` = M consecutive chains
     per superchain turns the nested R-hat on; M must divide the local chain count (no superchain straddles a shard).
     With a `dist.Shard` of more than one rank the sums are all-reduced and the result describes all chains, on every
-    rank."""
+    rank.
+
+    `rank_normalized=True` adds the rank-normalised diagnostics of Vehtari et al. 2021 (`rhat_bulk`, `rhat_tail`,
+    `rhat_rank`, `ess_bulk`, `ess_tail`, ...): the same definitions applied to the four series of `rank_series`, whose
+    ranks pool all chains, so it raises ValueError with a shard of more than one rank.  `ess_bulk` / `ess_tail` use
+    unsplit chains, as `ess` does; the `posterior` package splits the chains for its ESS as well, so its figures differ."""
     if x.dim() < 2:
         raise ValueError('expected (n_draws, n_chains, *event), got %s' % (tuple(x.shape),))
     K, n = int(x.shape[0]), int(x.shape[1])
@@ -169,10 +265,12 @@ def diagnose(x: torch.Tensor, max_lag: Optional[int] = None, superchains: Option
     L = min(K - 1, DEFAULT_MAX_LAG if max_lag is None else int(max_lag))
     if L < 0:
         raise ValueError('max_lag must not be negative')
-    if not x.is_cuda:
-        x = x.to(hip.require_gpu())
-    x = x.detach().to(torch.float32).contiguous()
+    if rank_normalized and shard is not None and shard.world > 1:
+        raise ValueError('rank_normalized diagnostics rank the values of all chains together; they are not available '
+                         'across a shard of %d ranks' % shard.world)
+    x = _device_slab(x)
     d = int(math.prod(event_shape))
+    group = None if superchains is None else M
     sums = chain_sums(x.reshape(K, n, d), L, M)
     if shard is not None and shard.world > 1:
         pack = torch.cat([pack_sums(sums), torch.tensor([float(n)], dtype=torch.float64)])
@@ -181,4 +279,8 @@ def diagnose(x: torch.Tensor, max_lag: Optional[int] = None, superchains: Option
         pack = pack.cpu()
         n = int(round(float(pack[-1])))
         sums = unpack_sums(pack[:-1], d)
-    return from_sums(sums, K, n, None if superchains is None else M, event_shape)
+    out = from_sums(sums, K, n, group, event_shape)
+    if rank_normalized:   # a single rank here: the local chains are all of them
+        for name, value in _rank_fields(x.reshape(K, n, d), L, group, event_shape).items():
+            setattr(out, name, value)
+    return out

@@ -195,6 +195,16 @@ DIAG_ROWS = ('sum_m', 'sum_m2', 'sum_mh', 'sum_mh2', 'sum_s2h', 'sum_mu', 'sum_m
 DIAG_ACOV = len(DIAG_ROWS)
 
 
+class NfmcRankArgs(C.Structure):
+    _fields_ = [('x', c_fp), ('n_draws', C.c_int64), ('n', C.c_int64), ('d', C.c_int32), ('series', C.c_int32),
+                ('out', c_fp), ('order_stats', c_fp), ('nonfinite', c_fp), ('work', c_fp), ('work_bytes', C.c_int64)]
+
+
+# NfmcRankArgs.series (include/nfmc_hip.h: NFMC_RANK_*)
+RANK_BULK, RANK_FOLDED, RANK_TAIL_LOW, RANK_TAIL_HIGH = range(4)
+RANK_SERIES = {'bulk': RANK_BULK, 'folded': RANK_FOLDED, 'tail_low': RANK_TAIL_LOW, 'tail_high': RANK_TAIL_HIGH}
+
+
 class NfmcLimits(C.Structure):
     _fields_ = [('abi_version', C.c_int32), ('max_d_sampler', C.c_int32), ('max_d_flow', C.c_int32),
                 ('max_hidden_valu', C.c_int32), ('max_hidden', C.c_int32), ('max_steps_per_call', C.c_int32)]
@@ -239,6 +249,8 @@ SYMBOLS = [
     ('nfmc_diag_sums_doubles', C.c_int64, [C.c_int32, C.c_int32]),
     ('nfmc_diag_work_bytes', C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     ('nfmc_chain_diagnostics_f32', C.c_int, [C.POINTER(NfmcDiagArgs), c_fp]),
+    ('nfmc_rank_work_bytes', C.c_int64, [C.c_int64, C.c_int64, C.c_int32]),
+    ('nfmc_rank_series_f32', C.c_int, [C.POINTER(NfmcRankArgs), c_fp]),
     ('nfmc_philox_normals_f32', C.c_int, [C.POINTER(NfmcRng), C.c_int32, C.c_int64, C.c_int32, c_fp, c_fp]),
     ('nfmc_philox_uniforms_f32', C.c_int, [C.POINTER(NfmcRng), C.c_int32, C.c_int64, c_fp, c_fp]),
     ('nfmc_flow_fit_supported_f32', C.c_int, [C.POINTER(NfmcRealNVP)]),

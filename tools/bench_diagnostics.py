@@ -6,6 +6,13 @@ Per shape: median of `reps` calls after one warm-up, device events around the li
 before); the bytes of the slab over that time next to the 6.3 TB/s streaming figure (the kernel reads the slab twice, so
 half of it is its ceiling); and the torch composition -- centred draws, one elementwise product and reduction per lag
 -- in the same process.  Prints one JSON line per shape.  Needs the GPU: there is no fallback.
+
+    python tools/bench_diagnostics.py --rank [--shapes ...]
+
+times the rank transform instead: the four series of nfmc_rank_series_f32 into one slab, and the whole
+`diagnose(..., rank_normalized=True)` call (the plain sums, the four transforms, their four sums, the host part), each next
+to the same results composed from torch ops on the device (torch.sort per coordinate, searchsorted, torch.special.ndtri,
+and `torch_sums` for every series).
 """
 import argparse
 import ctypes as C
@@ -53,15 +60,79 @@ def torch_sums(x, max_lag, group):
     return torch.cat([torch.stack(head), acov]).reshape(-1)
 
 
+def torch_rank_series(x):
+    """The four rank series composed from torch ops on the device: torch.sort per coordinate, searchsorted for the lower and
+    upper bound of every value, torch.special.ndtri in fp64."""
+    K, n, d = x.shape
+    S = K * n
+    v = x.reshape(S, d).t().contiguous()
+
+    def scores(v):
+        s = torch.sort(v, dim=1).values
+        r = (torch.searchsorted(s, v) + torch.searchsorted(s, v, right=True) + 1).double() * 0.5
+        return torch.special.ndtri((r - 0.375) / (S + 0.25)).float(), s
+
+    bulk, s = scores(v)
+    med = (s[:, (S - 1) // 2].double() + s[:, S // 2].double()) / 2
+    folded, _ = scores((v.double() - med[:, None]).abs().float())
+    low = (v <= s[:, (S - 1) // 20, None]).float()
+    high = (v >= s[:, (19 * (S - 1) + 19) // 20, None]).float()
+    return [t.t().reshape(K, n, d) for t in (bulk, folded, low, high)]
+
+
+def bench_rank(a, dev):
+    """--rank: the four-series transform (nfmc_rank_series_f32 four times into one slab) and the whole
+    rank_normalized=True call, each next to the same results composed from torch ops."""
+    for shape in a.shapes.split(','):
+        K, n, d = (int(v) for v in shape.split('x'))
+        L = min(a.max_lag, K - 1)
+        torch.manual_seed(0)
+        x = torch.randn(K, n, d, device=dev)
+        x[1:] = 0.7 * x[:-1] + 0.5 * x[1:]
+        rt = diagnostics._RankTransform(x)
+        kinds = ('bulk', 'folded', 'tail_low', 'tail_high')
+
+        def transform():
+            for kind in kinds:
+                rt.run(kind)
+
+        def whole():
+            return diagnostics.diagnose(x, max_lag=L, superchains=a.group, rank_normalized=True)
+
+        def torch_whole():
+            return [torch_sums(s.contiguous(), L, a.group).cpu() for s in [x] + torch_rank_series(x)]
+
+        k_ms, k_all = timed(transform, a.reps)
+        w_ms, w_all = timed(whole, a.reps)
+        t_ms, t_all = timed(lambda: torch_rank_series(x), a.reps)
+        tw_ms, tw_all = timed(torch_whole, a.reps)
+        diff = {}
+        for kind, want in zip(kinds, torch_rank_series(x)):
+            diff[kind] = float((rt.run(kind) - want).abs().max())
+        print(json.dumps({'shape': [K, n, d], 'max_lag': L, 'group': a.group, 'slab_gb': round(x.numel() * 4 / 1e9, 3),
+                          'work_mb': round(rt.work.numel() * 8 / 1e6, 1),
+                          'transform_ms': round(k_ms, 3), 'transform_ms_all': [round(v, 3) for v in k_all],
+                          'torch_transform_ms': round(t_ms, 3), 'torch_transform_ms_all': [round(v, 3) for v in t_all],
+                          'transform_speedup': round(t_ms / k_ms, 2),
+                          'rank_normalized_call_ms': round(w_ms, 3), 'rank_normalized_call_ms_all': [round(v, 3) for v in w_all],
+                          'torch_call_ms': round(tw_ms, 3), 'torch_call_ms_all': [round(v, 3) for v in tw_all],
+                          'call_speedup': round(tw_ms / w_ms, 2), 'max_abs_diff_to_torch': diff}), flush=True)
+        del x, rt
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--shapes', default='100x65536x64,100x8192x512')
     ap.add_argument('--max-lag', type=int, default=99)
     ap.add_argument('--group', type=int, default=16)
     ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--rank', action='store_true', help='time the rank transform and the rank-normalised call instead')
     a = ap.parse_args()
     dev = hip.require_gpu()
     lib = hip.lib()
+    if a.rank:
+        bench_rank(a, dev)
+        return
     for shape in a.shapes.split(','):
         K, n, d = (int(v) for v in shape.split('x'))
         L = min(a.max_lag, K - 1)
