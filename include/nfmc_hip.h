@@ -820,6 +820,68 @@ int64_t nfmc_diag_sums_doubles(int32_t d, int32_t max_lag);            /* 0 for 
 int64_t nfmc_diag_work_bytes(int64_t n, int32_t d, int32_t max_lag);   /* 0 for arguments out of range */
 int nfmc_chain_diagnostics_f32(const NfmcDiagArgs* args, nfmc_stream_t stream);
 
+/* ---- running diagnostics for runs that keep no states: an accumulator in device memory that is fed every kept draw
+ * exactly once, in blocks, and from which the `sums` of nfmc_chain_diagnostics_f32 (same rows, same layout) can be
+ * produced at any time.  Its size does not grow with the run.  Per series (chain j, coordinate c) it holds the shift s_j
+ * (the first draw), the fp64 sum S_j of the shifted draws y_t = x_t - s_j, the fp64 sum and sum of squares of y over the
+ * half-chains [0, h) and [n_draws_planned - h, n_draws_planned), h = n_draws_planned / 2, the first max_lag and the last
+ * max_lag shifted draws as fp32 (the last ones in a ring: draw t in row t mod max_lag), and per workgroup of the update one
+ * row of fp64 lag products P_l = sum_j sum_t y_t y_{t-l} (fp32 products of the fp32-rounded y; fp32 sums inside one block
+ * of draws, fp64 from there on; no atomics).  With mu_j = S_j / K after K draws, for l < K
+ *     K a_{j,l} = P_{j,l} - mu_j (2 S_j - head_l(j) - tail_l(j)) + (K - l) mu_j^2
+ * (head_l / tail_l: the sum of the first / last l shifted draws) is the autocovariance sum of nfmc_chain_diagnostics_f32;
+ * lags l >= K are exact zeros.  The same draws in the same blocks give the same bits; other blocks differ by the fp32
+ * rounding of the sums inside a block.
+ * state: nfmc_diag_stream_state_bytes = 8 (5 S + nb (max_lag + 1) d) + 4 (1 + 2 max_lag) S bytes rounded up to 8, S = n d,
+ * nb = min(ceil(n / max(1, 64 / d)), 1024 / ceil(d / 64)) workgroup rows; 8-byte aligned, put into the "no draws seen"
+ * condition by nfmc_diag_stream_reset_f32 (which also zeroes n_seen).  The descriptor lives in host memory; the library
+ * keeps n_seen in it, advanced when an update is enqueued (calls on one stream see the draws in that order).  One
+ * descriptor per state: it must not be used from two host threads at once, and a copy made before an update must not be
+ * passed to a later call -- its stale n_seen would pass the first_draw check against the wrong count.  Both size functions return 0 for d > 1024 or max_lag outside 0 .. NFMC_DIAG_MAX_LAG.
+ * Status of every entry point: NFMC_EINVAL: NULL pointer, non-positive size; NFMC_ESHAPE: d > 1024 or max_lag >
+ * NFMC_DIAG_MAX_LAG; NFMC_ESCRATCH: state (or work) too small.  All answered before any launch. */
+typedef struct {
+    void* state;              /* device memory, >= nfmc_diag_stream_state_bytes(n, d, max_lag) */
+    int64_t state_bytes;
+    int64_t n;
+    int32_t d;
+    int32_t max_lag;          /* 0 .. NFMC_DIAG_MAX_LAG */
+    int64_t n_draws_planned;  /* the draws the run will feed: fixes the half-chains */
+    int64_t n_seen;           /* draws fed so far: written by reset and update, read by sums */
+} NfmcDiagStream;
+int64_t nfmc_diag_stream_state_bytes(int64_t n, int32_t d, int32_t max_lag);
+int64_t nfmc_diag_stream_work_bytes(int64_t n, int32_t d, int32_t max_lag);
+int nfmc_diag_stream_reset_f32(NfmcDiagStream* acc, nfmc_stream_t stream);
+/* Folds n_rows new draws into the accumulator.  They sit in a staging ring described like NfmcSampleStore: draw
+ * first_draw + r in ring row (row + r) mod ring_rows, each row n * d floats.  first_draw must equal acc->n_seen -- a
+ * dropped or repeated block is an error, not a silently wrong answer -- and first_draw + n_rows must not pass
+ * n_draws_planned; also NFMC_EINVAL: n_rows > ring_rows, row outside the ring.  The ring is only read. */
+typedef struct {
+    NfmcDiagStream* acc;
+    const float* ring;        /* (ring_rows, n, d) */
+    int32_t ring_rows;
+    int32_t row;              /* ring row of the first new draw */
+    int32_t n_rows;           /* 1 .. ring_rows */
+    int32_t reserved;
+    int64_t first_draw;       /* global index of the first new draw */
+} NfmcDiagStreamArgs;
+int nfmc_diag_stream_update_f32(const NfmcDiagStreamArgs* args, nfmc_stream_t stream);
+/* The `sums` of nfmc_chain_diagnostics_f32 for the acc->n_seen draws fed so far (n_draws there = n_seen here), superchains
+ * of `group` chains through the same group and fold kernels.  The state is only read: it may be called in mid-run and
+ * the run continues to the same bits.  When n_seen != n_draws_planned the half-chain sums do not describe halves of what
+ * was seen: rows NFMC_DIAG_SUM_MH, _MH2 and _S2H are NaN then, every other row is that of the draws seen.
+ * NFMC_EINVAL also: n_seen < 4, group < 1 or not dividing n.  work: nfmc_diag_stream_work_bytes, 8-byte aligned, no
+ * initialisation needed. */
+typedef struct {
+    const NfmcDiagStream* acc;
+    int32_t group;            /* chains per superchain; divides n */
+    int32_t reserved;
+    double* sums;             /* out: nfmc_diag_sums_doubles(d, max_lag) doubles */
+    void* work;
+    int64_t work_bytes;       /* >= nfmc_diag_stream_work_bytes(n, d, max_lag) */
+} NfmcDiagStreamSumsArgs;
+int nfmc_diag_stream_sums_f32(const NfmcDiagStreamSumsArgs* args, nfmc_stream_t stream);
+
 /* ---- rank transform for the rank-normalised diagnostics (Vehtari et al. 2021): one of four series of the kept states,
  * each again an (n_draws, n, d) slab for nfmc_chain_diagnostics_f32.  Per coordinate the S = n_draws * n values
  * v_1 .. v_S are pooled over draws and chains and compared numerically (-0 = +0); x_(k) is the k-th smallest, k = 0 .. S-1.

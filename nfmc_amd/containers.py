@@ -12,7 +12,7 @@ nfmc/algorithms/sampling/base.py use (so results read the same), the implementat
 """
 import math
 from dataclasses import dataclass
-from typing import Any, Callable, Dict, List, Optional, Sequence
+from typing import Any, Callable, Dict, List, Optional, Sequence, Union
 
 import torch
 
@@ -60,8 +60,13 @@ class MCMCParameters:
     thinning: int = 1
     max_samples: Optional[int] = None
     spill_to_host: bool = False   # start the device-to-host copy of the kept states at the end of sample(), asynchronously
+    # R-hat, nested R-hat and ESS of a run that keeps no states (store_samples=False), from an accumulator the kept draws
+    # are fed to while the run goes on (`MCMCOutput.diagnostics`).  True: lags up to min(kept draws - 1, 127); an int L in
+    # 0 .. 127: that many lags (0: no autocovariances beyond the variance).  Ignored while `tuning` is set
+    running_diagnostics: Union[bool, int] = False
 
     def __post_init__(self):
+        running_lags(self, 2)
         return None
 
     def _set_tuning(self, flag: bool):
@@ -72,6 +77,27 @@ class MCMCParameters:
 
     def sampling_mode(self):
         self._set_tuning(False)
+
+
+RUNNING_MAX_LAG = 127     # NFMC_DIAG_MAX_LAG (include/nfmc_hip.h)
+# rows of the staging ring a run's kept draws pass through on their way to the accumulator: per kept draw the update takes
+# 52 us from a block of 128 rows against 110 us from 32 at 65536 x 64 chains and 127 lags
+RUNNING_STAGE_ROWS = 128
+
+
+def running_lags(params, n_kept: int) -> Optional[int]:
+    """The lags `params.running_diagnostics` asks for in a run that keeps `n_kept` draws; None when it is off."""
+    want = getattr(params, 'running_diagnostics', False)
+    if want is False or want is None:
+        return None
+    if params.store_samples:
+        raise ValueError('running_diagnostics is for runs with store_samples=False; with store_samples=True the kept '
+                         'states are there and MCMCOutput.diagnostics() reads them')
+    if want is True:
+        return max(0, min(int(n_kept) - 1, RUNNING_MAX_LAG))
+    if isinstance(want, bool) or int(want) != want or not 0 <= int(want) <= RUNNING_MAX_LAG:
+        raise ValueError('running_diagnostics must be a bool or a number of lags in 0 .. %d, got %r' % (RUNNING_MAX_LAG, want))
+    return int(want)
 
 
 # defaults of the refit inside a run (base.py:46-61): short, early-stopped, quiet
@@ -292,6 +318,47 @@ class DeviceSampleStore:
         return self.buf if start == 0 else torch.cat([self.buf[start:], self.buf[:start]])
 
 
+class StreamingSampleStore(DeviceSampleStore):
+    """The store of a run that keeps no states but diagnoses them (`MCMCParameters.running_diagnostics`): a ring of at
+    most `stage_rows` rows that the launches write their kept states to exactly like a `DeviceSampleStore` (same struct,
+    same thinning), and whose rows are handed to the accumulator `acc` (diagnostics.RunningDiagnostics) -- each kept draw
+    once, in order -- before the next launch is planned and once more by `flush()` at the end.  A launch must not keep
+    more rows than the ring has (`max_offer` transitions at most; Run.launch_cap cuts the launches)."""
+
+    def __init__(self, n, d, device, total, thinning=1, max_lag=0, stage_rows=None, acc=None):
+        stage_rows = RUNNING_STAGE_ROWS if stage_rows is None else stage_rows   # read per run: a measurement may set it
+        super().__init__(n, d, device, total, thinning, max(1, int(stage_rows)))
+        self.planned = -(-int(total) // self.thinning)
+        self.fed = 0   # kept draws handed to the accumulator
+        if acc is None:
+            from .diagnostics import RunningDiagnostics
+            acc = RunningDiagnostics(self.n, self.d, device, max_lag, self.planned)
+        self.acc = acc
+
+    @property
+    def max_offer(self):
+        return self.rows * self.thinning
+
+    def flush(self):
+        """Hand the kept draws the accumulator has not seen (those of the launches planned so far) to it."""
+        kept = -(-self.seen // self.thinning)
+        if kept > self.fed:
+            self.acc.update(self.buf, self.fed % self.rows, kept - self.fed, self.fed)
+            self.fed = kept
+
+    def plan(self, k):
+        self.flush()
+        if -(-(self.seen + int(k)) // self.thinning) - self.fed > self.rows:
+            raise RuntimeError('a launch of %d transitions keeps more draws than the %d rows of the staging ring'
+                               % (k, self.rows))
+        return super().plan(k)
+
+    def add_dense(self, x):
+        for lo in range(0, int(x.shape[0]), self.max_offer):
+            self.flush()
+            super().add_dense(x[lo:lo + self.max_offer])
+
+
 class MCMCSamples:
     """States kept from a run, `(n_kept, n_chains, *event_shape)`."""
 
@@ -396,6 +463,7 @@ class MCMCOutput:
     store_samples: bool = True
     max_samples: int = None
     kernel_events: Any = None   # bench.py: (label, start, end) HIP events of the launches, when kernel timing was on
+    running: Any = None         # diagnostics.RunningDiagnostics of a run with `running_diagnostics` on
 
     def __post_init__(self):
         self.event_shape = _shape(self.event_shape)
@@ -430,7 +498,15 @@ class MCMCOutput:
         """Split R-hat, ESS (and, with `superchains` = chains per superchain, the nested R-hat) of the kept states, per
         coordinate: `diagnostics.diagnose` on the device-resident store, no host copy of the states.  A thinned or
         windowed store is diagnosed as kept (ESS in units of kept draws).  `rank_normalized=True` adds the rank-normalised
-        bulk / tail R-hat and ESS (not across shards)."""
+        bulk / tail R-hat and ESS (not across shards).
+
+        A run with `running_diagnostics` on kept no states: its diagnostics come from the sums of the accumulator it
+        carried (`diagnostics.diagnose_running`), for the draws actually seen; `max_lag` may not exceed the lags
+        accumulated, and the rank-normalised forms, which need the states, raise ValueError."""
+        if self.running is not None:
+            from . import diagnostics
+            return diagnostics.diagnose_running(self.running, max_lag=max_lag, superchains=superchains, shard=shard,
+                                                rank_normalized=rank_normalized, event_shape=self.event_shape)
         if not self.store_samples:
             raise ValueError('diagnostics need the kept states: run with store_samples=True')
         from . import diagnostics

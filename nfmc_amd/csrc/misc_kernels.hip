@@ -5,6 +5,7 @@
 #include "common.hpp"
 #include "diagnostics.hpp"
 #include "rank_kernels.hpp"
+#include "diag_stream.hpp"
 
 namespace nfmc {
 
@@ -350,6 +351,88 @@ extern "C" int nfmc_chain_diagnostics_f32(const NfmcDiagArgs* args, nfmc_stream_
     NFMC_HIP_CHECK_LAUNCH();
     hipLaunchKernelGGL(diag_fold_kernel, dim3(grid_for(wg * (kBlock / kDiagFoldCols))), dim3(kBlock), 0, st,
                        work + p.off_group, p.gs, wg, wg, (int64_t)0, a.sums + head);
+    NFMC_HIP_CHECK_LAUNCH();
+    return NFMC_OK;
+}
+
+extern "C" int64_t nfmc_diag_stream_state_bytes(int64_t n, int32_t d, int32_t max_lag) {
+    if (!diag_shape_ok(n, d, max_lag)) return 0;
+    return stream_plan(n, d, max_lag).state_bytes;
+}
+
+extern "C" int64_t nfmc_diag_stream_work_bytes(int64_t n, int32_t d, int32_t max_lag) {
+    if (!diag_shape_ok(n, d, max_lag)) return 0;
+    return stream_plan(n, d, max_lag).work_doubles * (int64_t)sizeof(double);
+}
+
+// the checks every running-diagnostics entry point makes of its accumulator
+static int stream_check(const NfmcDiagStream* acc) {
+    if (!acc || !acc->state) return NFMC_EINVAL;
+    if (acc->n <= 0 || acc->d <= 0 || acc->max_lag < 0 || acc->n_draws_planned <= 0) return NFMC_EINVAL;
+    if (acc->d > 1024 || acc->max_lag > NFMC_DIAG_MAX_LAG) return NFMC_ESHAPE;
+    if (acc->state_bytes < nfmc_diag_stream_state_bytes(acc->n, acc->d, acc->max_lag)) return NFMC_ESCRATCH;
+    return NFMC_OK;
+}
+
+extern "C" int nfmc_diag_stream_reset_f32(NfmcDiagStream* acc, nfmc_stream_t stream) {
+    if (int rc = stream_check(acc)) return rc;
+    const StreamPlan p = stream_plan(acc->n, acc->d, acc->max_lag);
+    hipError_t e = hipMemsetAsync(acc->state, 0, (size_t)p.state_bytes, (hipStream_t)stream);
+    if (e != hipSuccess) return (int)e;
+    acc->n_seen = 0;
+    return NFMC_OK;
+}
+
+extern "C" int nfmc_diag_stream_update_f32(const NfmcDiagStreamArgs* args, nfmc_stream_t stream) {
+    if (!args || !args->ring) return NFMC_EINVAL;
+    const NfmcDiagStreamArgs a = *args;
+    if (int rc = stream_check(a.acc)) return rc;
+    NfmcDiagStream& acc = *a.acc;
+    if (a.ring_rows <= 0 || a.n_rows <= 0 || a.n_rows > a.ring_rows || a.row < 0 || a.row >= a.ring_rows) return NFMC_EINVAL;
+    if (acc.n_seen < 0 || a.first_draw != acc.n_seen || a.first_draw + a.n_rows > acc.n_draws_planned) return NFMC_EINVAL;
+    const StreamPlan p = stream_plan(acc.n, acc.d, acc.max_lag);
+    hipLaunchKernelGGL(diag_stream_update_kernel, dim3(p.nb * p.nchunk), dim3(kDiagBlock), 0, (hipStream_t)stream, a.ring,
+                       (int)a.ring_rows, (int)a.row, (int)a.n_rows, a.first_draw, acc.n_draws_planned, acc.n, (int)acc.d,
+                       (int)acc.max_lag + 1, p.cpt, p.nchunk, p.ntile, p.nb, stream_state(acc.state, p));
+    NFMC_HIP_CHECK_LAUNCH();
+    acc.n_seen += a.n_rows;
+    return NFMC_OK;
+}
+
+extern "C" int nfmc_diag_stream_sums_f32(const NfmcDiagStreamSumsArgs* args, nfmc_stream_t stream) {
+    if (!args || !args->sums || !args->work) return NFMC_EINVAL;
+    const NfmcDiagStreamSumsArgs a = *args;
+    if (int rc = stream_check(a.acc)) return rc;
+    const NfmcDiagStream& acc = *a.acc;
+    if (acc.n_seen < 4 || acc.n_seen > acc.n_draws_planned || a.group < 1 || acc.n % a.group != 0) return NFMC_EINVAL;
+    if (a.work_bytes < nfmc_diag_stream_work_bytes(acc.n, acc.d, acc.max_lag)) return NFMC_ESCRATCH;
+    const StreamPlan p = stream_plan(acc.n, acc.d, acc.max_lag);
+    const StreamState s = stream_state(acc.state, p);
+    const int d = (int)acc.d, L = (int)acc.max_lag;
+    const int64_t G = acc.n / a.group;
+    const int64_t gcap = kDiagGroupThreads / d > 1 ? kDiagGroupThreads / d : 1;
+    const int64_t gs = G < gcap ? G : gcap;
+    double* work = (double*)a.work;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(diag_stream_rows_kernel, dim3(p.nb2 * p.nchunk, p.rows2), dim3(kBlock), 0, st, s, acc.n_seen,
+                       acc.n_draws_planned, acc.n, d, L, p.cpt, p.nchunk, p.ntile, p.nb2, p.rows2, work, work + p.w_rows);
+    NFMC_HIP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(diag_group_kernel, dim3(grid_for(gs * d)), dim3(kBlock), 0, st, (const double*)work, G, (int64_t)a.group,
+                       d, gs, work + p.w_group);
+    NFMC_HIP_CHECK_LAUNCH();
+    const int64_t w2 = (int64_t)p.rows2 * d, wl = (int64_t)(L + 1) * d, wg = (int64_t)kDiagGroup * d;
+    hipLaunchKernelGGL(diag_fold_kernel, dim3(grid_for(w2 * (kBlock / kDiagFoldCols))), dim3(kBlock), 0, st,
+                       (const double*)(work + p.w_rows), (int64_t)p.nb2, w2, w2, (int64_t)0, work + p.w_fold);
+    NFMC_HIP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(diag_fold_kernel, dim3(grid_for(wl * (kBlock / kDiagFoldCols))), dim3(kBlock), 0, st,
+                       (const double*)s.part, (int64_t)p.nb, wl, wl, (int64_t)0, work + p.w_lags);
+    NFMC_HIP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(diag_fold_kernel, dim3(grid_for(wg * (kBlock / kDiagFoldCols))), dim3(kBlock), 0, st,
+                       (const double*)(work + p.w_group), gs, wg, wg, (int64_t)0, a.sums + (int64_t)kDiagMain * d);
+    NFMC_HIP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(diag_stream_combine_kernel, dim3((d + kBlock - 1) / kBlock), dim3(kBlock), 0, st,
+                       (const double*)(work + p.w_fold), (const double*)(work + p.w_lags), acc.n_seen, acc.n_draws_planned, d, L,
+                       a.sums);
     NFMC_HIP_CHECK_LAUNCH();
     return NFMC_OK;
 }

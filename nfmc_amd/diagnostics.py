@@ -284,3 +284,78 @@ def diagnose(x: torch.Tensor, max_lag: Optional[int] = None, superchains: Option
         for name, value in _rank_fields(x.reshape(K, n, d), L, group, event_shape).items():
             setattr(out, name, value)
     return out
+
+
+class RunningDiagnostics:
+    """The accumulator of a run that keeps no states (include/nfmc_hip.h: nfmc_diag_stream_*): device
+    state of about (2 max_lag + 11) n d floats that is fed each kept draw once, in blocks from a staging ring (`update`),
+    and yields the sums of `chain_sums` for the draws seen so far at any time (`sums`, which only reads the state).
+    `n_draws_planned` fixes the half-chains of the split R-hat before the run."""
+
+    def __init__(self, n, d, device, max_lag, n_draws_planned):
+        self.n, self.d, self.max_lag, self.planned = int(n), int(d), int(max_lag), int(n_draws_planned)
+        self.device = device
+        self.lib = hip.lib()
+        nbytes = int(self.lib.nfmc_diag_stream_state_bytes(self.n, self.d, self.max_lag))
+        if nbytes <= 0:
+            raise hip.NfmcArgumentError('running diagnostics: event size %d (<= 1024) or max_lag %d (0 .. %d) outside the '
+                                        'kernel\'s range' % (self.d, self.max_lag, hip.DIAG_MAX_LAG), hip.ESHAPE)
+        self.state = torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+        self.desc = hip.NfmcDiagStream(hip.ptr(self.state, torch.float64), nbytes, self.n, self.d, self.max_lag,
+                                       self.planned, 0)
+        with torch.cuda.device(device):
+            hip.check(self.lib.nfmc_diag_stream_reset_f32(C.byref(self.desc), hip.stream()), 'nfmc_diag_stream_reset_f32')
+
+    @property
+    def n_seen(self) -> int:
+        return int(self.desc.n_seen)
+
+    def update(self, ring: torch.Tensor, row: int, n_rows: int, first_draw: int):
+        """Fold draws first_draw .. first_draw + n_rows - 1, which sit in rows (row + r) mod ring_rows of `ring`
+        (ring_rows, n, d), into the state, on the current stream."""
+        args = hip.NfmcDiagStreamArgs(C.pointer(self.desc), hip.ptr(ring), int(ring.shape[0]), int(row), int(n_rows), 0,
+                                      int(first_draw))
+        with torch.cuda.device(self.device):
+            hip.check(self.lib.nfmc_diag_stream_update_f32(C.byref(args), hip.stream()), 'nfmc_diag_stream_update_f32')
+
+    def sums(self, group: int = 1) -> Dict[str, torch.Tensor]:
+        """`chain_sums` of the draws seen so far; the half-chain rows are NaN unless all planned draws were seen."""
+        _check_counts(self.n_seen, self.n, int(group))
+        count = int(self.lib.nfmc_diag_sums_doubles(self.d, self.max_lag))
+        nbytes = int(self.lib.nfmc_diag_stream_work_bytes(self.n, self.d, self.max_lag))
+        sums = torch.empty(count, dtype=torch.float64, device=self.device)
+        work = torch.empty(nbytes // 8, dtype=torch.float64, device=self.device)
+        args = hip.NfmcDiagStreamSumsArgs(C.pointer(self.desc), int(group), 0, hip.ptr(sums, torch.float64),
+                                          hip.ptr(work, torch.float64), nbytes)
+        with torch.cuda.device(self.device):
+            hip.check(self.lib.nfmc_diag_stream_sums_f32(C.byref(args), hip.stream()), 'nfmc_diag_stream_sums_f32')
+        return unpack_sums(sums.cpu(), self.d)
+
+
+def diagnose_running(acc, max_lag: Optional[int] = None, superchains: Optional[int] = None, shard=None,
+                     rank_normalized: bool = False, event_shape=None) -> Diagnostics:
+    """`diagnose` for a run that kept no states, from its accumulator (`RunningDiagnostics`): the same sums, the same
+    all-reduce over a shard, the same `from_sums`.  `n_draws` is the number of draws the accumulator saw; when a time limit
+    ended the run before the planned number, `rhat` is NaN (the half-chains were fixed before the run) and everything else
+    describes the draws seen."""
+    if rank_normalized:
+        raise ValueError('rank_normalized diagnostics rank the kept states themselves: run with store_samples=True')
+    L = int(acc.max_lag) if max_lag is None else int(max_lag)
+    if L < 0:
+        raise ValueError('max_lag must not be negative')
+    if L > int(acc.max_lag):
+        raise ValueError('max_lag %d exceeds the %d lags the run accumulated (running_diagnostics)' % (L, acc.max_lag))
+    K, n = int(acc.n_seen), int(acc.n)
+    M = 1 if superchains is None else int(superchains)
+    _check_counts(K, n, M)
+    sums = acc.sums(M)
+    d = int(sums['sum_m'].numel())
+    sums['acov'] = sums['acov'][:L + 1]
+    if shard is not None and shard.world > 1:
+        pack = torch.cat([pack_sums(sums), torch.tensor([float(n)], dtype=torch.float64)])
+        pack = pack.to(acc.device)   # Shard moves it to the host itself under a gloo group
+        shard.all_reduce_sum_(pack)
+        pack = pack.cpu()
+        n = int(round(float(pack[-1])))
+        sums = unpack_sums(pack[:-1], d)
+    return from_sums(sums, K, n, None if superchains is None else M, event_shape)

@@ -195,6 +195,21 @@ DIAG_ROWS = ('sum_m', 'sum_m2', 'sum_mh', 'sum_mh2', 'sum_s2h', 'sum_mu', 'sum_m
 DIAG_ACOV = len(DIAG_ROWS)
 
 
+class NfmcDiagStream(C.Structure):
+    _fields_ = [('state', c_fp), ('state_bytes', C.c_int64), ('n', C.c_int64), ('d', C.c_int32), ('max_lag', C.c_int32),
+                ('n_draws_planned', C.c_int64), ('n_seen', C.c_int64)]
+
+
+class NfmcDiagStreamArgs(C.Structure):
+    _fields_ = [('acc', C.POINTER(NfmcDiagStream)), ('ring', c_fp), ('ring_rows', C.c_int32), ('row', C.c_int32),
+                ('n_rows', C.c_int32), ('reserved', C.c_int32), ('first_draw', C.c_int64)]
+
+
+class NfmcDiagStreamSumsArgs(C.Structure):
+    _fields_ = [('acc', C.POINTER(NfmcDiagStream)), ('group', C.c_int32), ('reserved', C.c_int32), ('sums', c_fp),
+                ('work', c_fp), ('work_bytes', C.c_int64)]
+
+
 class NfmcRankArgs(C.Structure):
     _fields_ = [('x', c_fp), ('n_draws', C.c_int64), ('n', C.c_int64), ('d', C.c_int32), ('series', C.c_int32),
                 ('out', c_fp), ('order_stats', c_fp), ('nonfinite', c_fp), ('work', c_fp), ('work_bytes', C.c_int64)]
@@ -249,6 +264,11 @@ SYMBOLS = [
     ('nfmc_diag_sums_doubles', C.c_int64, [C.c_int32, C.c_int32]),
     ('nfmc_diag_work_bytes', C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     ('nfmc_chain_diagnostics_f32', C.c_int, [C.POINTER(NfmcDiagArgs), c_fp]),
+    ('nfmc_diag_stream_state_bytes', C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    ('nfmc_diag_stream_work_bytes', C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    ('nfmc_diag_stream_reset_f32', C.c_int, [C.POINTER(NfmcDiagStream), c_fp]),
+    ('nfmc_diag_stream_update_f32', C.c_int, [C.POINTER(NfmcDiagStreamArgs), c_fp]),
+    ('nfmc_diag_stream_sums_f32', C.c_int, [C.POINTER(NfmcDiagStreamSumsArgs), c_fp]),
     ('nfmc_rank_work_bytes', C.c_int64, [C.c_int64, C.c_int64, C.c_int32]),
     ('nfmc_rank_series_f32', C.c_int, [C.POINTER(NfmcRankArgs), c_fp]),
     ('nfmc_philox_normals_f32', C.c_int, [C.POINTER(NfmcRng), C.c_int32, C.c_int64, C.c_int32, c_fp, c_fp]),

@@ -7,7 +7,7 @@ from typing import Optional
 import torch
 
 from .. import hip
-from ..containers import DeviceSampleStore
+from ..containers import DeviceSampleStore, StreamingSampleStore, running_lags
 from ..flows import Flow
 from ..potentials import Potential, recognize
 
@@ -150,6 +150,7 @@ class Run:
         moves `bar` after it; the bar is closed when the loop ends, however it ends.  `self.done` counts the
         transitions of the launches that returned."""
         self.done = done = 0
+        limit = min(limit, self.launch_cap())
         clock = time_limit_seconds is not None   # without a limit nothing is read, and the stream is never waited for
         try:
             while done < total and not (clock and self.time_is_up(t0, time_limit_seconds)):
@@ -174,10 +175,26 @@ class Run:
         """The store of kept states for a run that offers `offered` of them (thinning and `max_samples` applied on the
         device), or None when the sampler keeps none."""
         p = self.sampler.params
+        self.streaming = None
+        if offered > 0 and not p.tuning:
+            thinning = max(1, int(getattr(p, 'thinning', 1)))
+            lags = running_lags(p, -(-int(offered) // thinning))
+            if lags is not None:
+                # no states are kept: the kept draws pass through a small ring into the running diagnostics
+                self.streaming = StreamingSampleStore(self.n, self.d, self.dev, offered, thinning, lags)
+                return self.streaming
         if not (p.store_samples and offered > 0):
             return None
         return DeviceSampleStore(self.n, self.d, self.dev, offered, getattr(p, 'thinning', 1),
                                  getattr(p, 'max_samples', None))
+
+    def launch_cap(self, extra=0):
+        """Transitions one launch may offer to the run's store, when the launch offers `extra` more than it is asked for
+        (a jump tail): what one call takes, or what the staging ring of the running diagnostics holds."""
+        streaming = getattr(self, 'streaming', None)
+        if streaming is None:
+            return hip.MAX_STEPS_PER_CALL
+        return max(1, min(hip.MAX_STEPS_PER_CALL, streaming.max_offer - extra))
 
     def finish(self, out, t0, n_moments, store=None, **counters):
         """End of a sample() call: the final state, the statistics over `n_moments` (step, chain) pairs, the kept states
@@ -198,7 +215,10 @@ class Run:
         # only jump launches book into the jump counters: they are zero for every other sampler
         st.n_nonfinite_log_ratios = int(cnt[hip.CNT_NONFINITE]) + int(jc[hip.CNT_NONFINITE])
         st.absorb_device_sums(sum_x.reshape(self.event_shape), sum_x2.reshape(self.event_shape), n_moments)
-        if store is not None:
+        if isinstance(store, StreamingSampleStore):
+            store.flush()
+            out.running = store.acc
+        elif store is not None:
             out.running_samples.adopt_store(store, getattr(self.sampler.params, 'spill_to_host', False))
         out.running_samples.last_sample = last_sample
         st.update_elapsed_time(time.time() - t0)

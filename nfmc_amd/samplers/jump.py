@@ -245,6 +245,10 @@ class JumpNFMC(Sampler):
     # launch does (measured 0.474 vs 0.45 ms per outer iteration at C3).
     fuse_jump_tail = False
 
+    # True: never hand the rest of a run to the library in one call (launch_jump_run); every iteration's launches come from
+    # the host loop, as they do whenever the run has a store.  For measurements that compare like with like.
+    host_loop = False
+
     # Parts of the whole-run call (launch_jump_run): None = NFMC_JUMP_PARTS, else the measured default (JUMP_PARTS)
     jump_parts = None
 
@@ -339,7 +343,7 @@ class JumpNFMC(Sampler):
         # needs the host between launches (refits, kept states, replayed noise, per-launch events, a progress bar)
         whole_run = (pot is not None and not tail_ok and not self.params.fit_nf and store is None and run.replay is None
                      and run.kernel_events is None and not show_progress and isinstance(inner, (Langevin, HMC))
-                     and os.environ.get('NFMC_STATS_DEFER', '1') != '0')
+                     and os.environ.get('NFMC_STATS_DEFER', '1') != '0' and not self.host_loop)
 
         t0 = time.time()
         done = 0
@@ -362,7 +366,8 @@ class JumpNFMC(Sampler):
             # the last inner launch, on the same registers (NfmcJumpTail)
             tail_done = False
             if pot is not None:
-                for off, k in chunks(K):
+                # launches that write to the store are cut to what a streaming store's ring holds; the refit block is dense
+                for off, k in chunks(K, hip.MAX_STEPS_PER_CALL if dense else run.launch_cap(1 if tail_ok else 0)):
                     last = off + k == K
                     tail = None
                     if last and tail_ok:

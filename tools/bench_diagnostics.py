@@ -13,6 +13,14 @@ times the rank transform instead: the four series of nfmc_rank_series_f32 into o
 `diagnose(..., rank_normalized=True)` call (the plain sums, the four transforms, their four sums, the host part), each next
 to the same results composed from torch ops on the device (torch.sort per coordinate, searchsorted, torch.special.ndtri,
 and `torch_sums` for every series).
+
+    python tools/bench_diagnostics.py --running [--shapes 65536x64,8192x512] [--lags 0,31,127] [--stage-rows 32,128]
+
+times the running diagnostics of runs that keep no states: nfmc_diag_stream_update_f32 per kept draw (a block of
+`stage_rows` draws from a resident ring, device events around the call, median of `reps`), and, with --through-sample,
+whole `sample()` calls of jump_mala + RealNVP (d = 64, 65536 chains, 20 x 100 transitions; wall clock with a
+synchronize, median of 3): the option on at thinning 1 and 10, off on the host loop, as an extra off as one native call, and
+store_samples=True followed by diagnostics().
 """
 import argparse
 import ctypes as C
@@ -120,6 +128,71 @@ def bench_rank(a, dev):
         del x, rt
 
 
+def bench_running(a, dev):
+    lib = hip.lib()
+    for shape in a.shapes.split(','):
+        n, d = (int(v) for v in shape.split('x')[-2:])
+        for L in (int(v) for v in a.lags.split(',')):
+            for R in (int(v) for v in a.stage_rows.split(',')):
+                torch.manual_seed(0)
+                ring = torch.randn(R, n, d, device=dev)
+                acc = diagnostics.RunningDiagnostics(n, d, dev, L, R * (a.reps + 1))
+
+                def update():
+                    acc.update(ring, 0, R, acc.n_seen)
+
+                ms, ms_all = timed(update, a.reps)
+                sums_ms, _ = timed(lambda: acc.sums(a.group), 1)
+                state = int(lib.nfmc_diag_stream_state_bytes(n, d, L))
+                print(json.dumps({'shape': [n, d], 'max_lag': L, 'stage_rows': R, 'update_us_per_draw': round(1e3 * ms / R, 2),
+                                  'update_ms_all': [round(v, 4) for v in ms_all], 'state_gb': round(state / 1e9, 3),
+                                  'state_as_kept_draws': round(state / (4.0 * n * d), 1),
+                                  'sums_call_ms': round(sums_ms, 3)}), flush=True)
+                del acc, ring
+    if not a.through_sample:
+        return
+    import time
+    from nfmc_amd import create_sampler
+    from nfmc_amd.potentials import SumOfSquares
+    n, d = 65536, 64
+    x0 = torch.randn(n, d, generator=torch.Generator().manual_seed(1))
+
+    from nfmc_amd import containers
+
+    def call(label, host_loop=False, diagnose=False, stage_rows=None, **params):
+        torch.manual_seed(0)
+        if stage_rows is not None:
+            containers.RUNNING_STAGE_ROWS = stage_rows   # the ring of the runs below (StreamingSampleStore reads it per run)
+            label += ', stage_rows %d' % stage_rows
+        s = create_sampler(target=SumOfSquares((d,)), event_shape=(d,), strategy='jump_mala', flow='realnvp',
+                           param_kwargs=dict(n_iterations=20, **params), inner_param_kwargs=dict(n_iterations=100))
+        s.seed = 5
+        if host_loop:
+            s.host_loop = True   # JumpNFMC.sample: no whole-run call, the launches of every iteration from the host
+        times = []
+        for _ in range(4):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = s.sample(x0, show_progress=False)
+            if diagnose:
+                out.diagnostics(superchains=a.group)
+            torch.cuda.synchronize()
+            times.append(1e3 * (time.perf_counter() - t0))
+            del out
+        print(json.dumps({'sample': label, 'ms': round(statistics.median(times[1:]), 2),
+                          'ms_all': [round(v, 2) for v in times]}), flush=True)
+
+    call('off, one native call (extra: the default path of such a run)', store_samples=False)
+    call('off, host loop', host_loop=True, store_samples=False)
+    for thin in (1, 10):
+        for R in (int(v) for v in a.stage_rows.split(',')):
+            call('running, thinning %d' % thin, diagnose=True, stage_rows=R, store_samples=False, running_diagnostics=True,
+                 thinning=thin)
+            call('running L=31, thinning %d' % thin, diagnose=True, stage_rows=R, store_samples=False, running_diagnostics=31,
+                 thinning=thin)
+        call('stored + diagnostics(), thinning %d' % thin, diagnose=True, store_samples=True, thinning=thin)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--shapes', default='100x65536x64,100x8192x512')
@@ -127,9 +200,18 @@ def main():
     ap.add_argument('--group', type=int, default=16)
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--rank', action='store_true', help='time the rank transform and the rank-normalised call instead')
+    ap.add_argument('--running', action='store_true', help='time the running diagnostics instead')
+    ap.add_argument('--lags', default='0,31,127')
+    ap.add_argument('--stage-rows', default='32,128')
+    ap.add_argument('--through-sample', action='store_true', help='with --running: whole sample() calls as well')
     a = ap.parse_args()
     dev = hip.require_gpu()
     lib = hip.lib()
+    if a.running:
+        if a.shapes == ap.get_default('shapes'):
+            a.shapes = '65536x64,8192x512'
+        bench_running(a, dev)
+        return
     if a.rank:
         bench_rank(a, dev)
         return
