@@ -109,7 +109,7 @@ class NeuTra(Sampler):
         """Conditioner width to present to the kernels: d = 64 / 128 with one or two hidden layers runs on the
         matrix cores (csrc/neutra_mfma.hip) also when the flow's own conditioner is narrow (zero-padded).  The matrix-core
         kernels evaluate quadratic and funnel targets only: a potential class that says so (`neutra_matrix_cores = False`,
-        nfmc_amd/potentials.py) keeps the flow's own width (VALU kernels).  The question goes to the target as given, not to
+        nfmc_amd/potentials/) keeps the flow's own width (VALU kernels).  The question goes to the target as given, not to
         its resolved descriptor: a plain callable that is recognised as a quadratic takes the matrix cores."""
         if not getattr(self.target, 'neutra_matrix_cores', True):
             return 0
