@@ -481,9 +481,69 @@ typedef struct {
                                   transitions.  Otherwise the call enqueues ceil(n_steps / every) kernel + controller
                                   pairs itself (noise, masks and the sample store advance between them), so a whole
                                   warmup is ONE call: no host work between updates */
-    int32_t reserved;
+    int32_t trajectory;        /* nfmc_hmc_steps_f32 only (was `reserved`, same layout): NFMC_TRAJECTORY_*.  Not 0: `state`
+                                  is followed by a trajectory block (below), and adjust must be 1 */
 } NfmcTune;
 int64_t nfmc_tune_state_doubles(int32_t d);
+
+/* ---- Trajectory length of the hmc sampler, adapted in the same warmup (ChEES-HMC: Hoffman, Radul and Sountsov, AISTATS
+ * 2021; all chains share one step size h and one length T).  Per transition with Philox step counter k = rng.step0 + s:
+ *     u = (bitreverse32(k + 1) + 0.5) 2^-32            base-2 radical inverse: the jitter
+ *     L = clamp(ceil(u T / h), 1, L_max)               leapfrog steps of EVERY chain of the transition (fp64, no
+ *                                                      contraction: a host that repeats it gets the same integer)
+ *     t = L h                                          realised length
+ * and per chain, with c the lagged centre (the shift words of the tuning state), x the current state, q the proposal and
+ * v = p * inv_mass_diag the velocity at the end of the trajectory:
+ *     a0 = sum_i (x_i - c_i)^2,  a1 = sum_i (q_i - c_i)^2,  b = sum_i (q_i - c_i) v_i,  g = t (a1 - a0) b,
+ *     alpha = min(1, exp(log ratio));  alpha = 0 where the log ratio, a0, a1 or b is not finite.
+ * The controller update pools g-hat = sum(alpha g) / sum(alpha) over the chains and transitions of the update and runs
+ * Adam with beta1 = 0 on log T (j: the update count from 1):
+ *     v <- b2 v + (1 - b2) g-hat^2;   delta = lr g-hat / (sqrt(v / (1 - b2^j)) + 1e-8), clipped to +-clip
+ *     log T <- clamp(log T + delta, log h, log(L_max h))      h: the step size the same update just set
+ *     log T-bar <- w log T + (1 - w) log T-bar,   w = j^-0.75
+ * An update with sum(alpha) == 0 (or a g-hat that is not finite) leaves all of that alone.  Deviation from the paper: both
+ * centres are the lagged pooled mean c, not the batch means of the current states and of this transition's proposals (the
+ * latter needs every chain's proposal before any chain's term: a grid-wide barrier per transition).
+ * NfmcTune.trajectory: */
+enum {
+    NFMC_TRAJECTORY_OFF = 0,     /* n_leapfrog steps per transition; no trajectory block is read */
+    NFMC_TRAJECTORY_ADAPT = 1,   /* jittered L, T adapted by every controller update */
+    NFMC_TRAJECTORY_FROZEN = 2   /* jittered L at the block's T; only the leapfrog total is written */
+};
+/* The trajectory block: fp64 words at state + nfmc_tune_state_doubles(d), nfmc_tune_trajectory_doubles(history_rows) of
+ * them, caller-allocated and caller-initialised (the library never allocates). */
+enum {
+    NFMC_TRAJ_LENGTH = 0,          /* T the next launch runs on = exp(log T) as the controller evaluated it (in) */
+    NFMC_TRAJ_LOG_LENGTH = 1,      /* log T (in: log of the word above) */
+    NFMC_TRAJ_LOG_AVERAGED = 2,    /* log T-bar (in: log T) */
+    NFMC_TRAJ_V = 3,               /* second-moment estimate (in: 0) */
+    NFMC_TRAJ_COUNT = 4,           /* j: updates applied (in: 0) */
+    NFMC_TRAJ_LEARNING_RATE = 5,   /* lr (0.025) */
+    NFMC_TRAJ_BETA2 = 6,           /* b2 (0.95) */
+    NFMC_TRAJ_CLIP = 7,            /* clip (0.35) */
+    NFMC_TRAJ_MAX_LEAPFROG = 8,    /* L_max (128) */
+    NFMC_TRAJ_LEAPFROG_TOTAL = 9,  /* leapfrog steps per chain taken so far, all launches (in: 0) */
+    NFMC_TRAJ_G_HAT = 10,          /* last update's g-hat (out) */
+    NFMC_TRAJ_ALPHA_SUM = 11,      /* ... and its sum(alpha) (out) */
+    NFMC_TRAJ_HISTORY_ROWS = 12,   /* capacity of the history below, in rows */
+    NFMC_TRAJ_HISTORY_USED = 13,   /* NFMC_TRAJECTORY_ADAPT updates so far; rows beyond the capacity are not written (in: 0) */
+    NFMC_TRAJ_WORDS = 16           /* followed by the history: one row per update */
+};
+/* A history row: T and h the update's transitions ran with, what they measured, and what the update left */
+enum {
+    NFMC_TRAJ_ROW_LENGTH = 0,
+    NFMC_TRAJ_ROW_STEP_SIZE = 1,
+    NFMC_TRAJ_ROW_G_HAT = 2,
+    NFMC_TRAJ_ROW_ALPHA_SUM = 3,
+    NFMC_TRAJ_ROW_LEAPFROGS = 4,       /* leapfrog steps per chain of the update's transitions */
+    NFMC_TRAJ_ROW_LOG_LENGTH = 5,
+    NFMC_TRAJ_ROW_V = 6,
+    NFMC_TRAJ_ROW_LOG_AVERAGED = 7,
+    NFMC_TRAJ_ROW_NEXT_STEP_SIZE = 8,  /* h the update set */
+    NFMC_TRAJ_ROW_WORDS = 9
+};
+/* NFMC_TRAJ_WORDS + history_rows * NFMC_TRAJ_ROW_WORDS; 0 for history_rows < 0 */
+int64_t nfmc_tune_trajectory_doubles(int32_t history_rows);
 
 /* The register layout nfmc_mala_steps_f32 / nfmc_hmc_steps_f32 run a call without a jump tail on, for event size d and
  * potential kind `pot_kind`: *cpl coordinates per lane, *lpc lanes per chain (a workgroup holds 256 / lpc chains).  Host

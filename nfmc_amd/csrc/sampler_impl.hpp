@@ -97,6 +97,101 @@ struct StatShift {
     }
 };
 
+// Leapfrog steps of the transition with Philox step counter k under a jittered trajectory (NfmcTune.trajectory, header
+// comment in nfmc_hip.h): clamp(ceil(u T / h), 1, L_max), u the base-2 radical inverse of k + 1 plus half a grid step.
+// THE definition: the hmc kernel, the controller's leapfrog total (tune_finish_kernel) and tuning.leapfrog_count on the
+// host all evaluate these fp64 operations in this order, without contraction, so they agree to the integer.
+__host__ __device__ inline int trajectory_leapfrog_count(uint32_t k, double T, double h, double lmax) {
+#pragma clang fp contract(off)
+    const double u = ((double)__builtin_bitreverse32(k + 1u) + 0.5) * 0x1p-32;
+    const double r = ceil(u * T / h);
+    const double cap = lmax >= 1.0 ? (lmax < 1048576.0 ? lmax : 1048576.0) : 1.0;
+    return r >= 1.0 ? (int)(r < cap ? r : cap) : 1;   // NaN -> 1
+}
+
+// The jittered trajectory of the TUNE instantiations of hmc_kernel (ON; every other kernel carries nothing of it): the
+// leapfrog count of each transition and, while the length adapts, this lane's fp32 sums over the launch's transitions
+// and tiles of alpha g and alpha, the ChEES terms about the lagged centre (StatShift's c).  Every lane of a chain holds
+// the chain's sums; flush() adds the group leaders' in fp64 into the two jump columns of the workgroup's statistics
+// slab, which a tuning launch (no jump tail) leaves zero, so the fold kernels total them with the other columns.
+template <int CPL, int LPC, bool ON>
+struct Trajectory {
+    int mode, L;   // L: the leapfrog count of the transition in flight
+    double T, h, lmax;
+    float sum_g, sum_alpha;
+    __device__ __forceinline__ void init(const NfmcTune& tn) {
+        if constexpr (ON) {
+            mode = tn.trajectory;
+            sum_g = sum_alpha = 0.f;
+            if (mode) {
+                const double* __restrict__ tr = tn.state + NFMC_TUNE_WORDS + 3 * CPL * LPC + kStatTail;
+                T = tr[NFMC_TRAJ_LENGTH];
+                lmax = tr[NFMC_TRAJ_MAX_LEAPFROG];
+                h = tn.state[NFMC_TUNE_STEP_SIZE];
+            }
+        }
+    }
+    // wave-uniform: every chain of a launch runs the same trajectory
+    __device__ __forceinline__ int leapfrogs(int fixed, uint32_t k) {
+        if constexpr (ON) {
+            L = mode ? __builtin_amdgcn_readfirstlane(trajectory_leapfrog_count(k, T, h, lmax)) : fixed;
+            return L;
+        }
+        return fixed;
+    }
+    // after the Metropolis test, before the state moves: x the current state, q the proposal, p the final momentum
+    template <class Shift, class Mass>
+    __device__ __forceinline__ void accumulate(const float (&x)[CPL], const float (&q)[CPL], const float (&p)[CPL],
+                                               const Shift& shift, const Mass& mc, float lr, bool active) {
+        if constexpr (ON) {
+            if (mode != NFMC_TRAJECTORY_ADAPT) return;
+            float a0 = 0.f, a1 = 0.f, b = 0.f;   // padded coordinates: x = q = c = 0 and zero mass
+#pragma unroll
+            for (int i = 0; i < CPL; ++i) {
+                const float dx = x[i] - shift.c[i], dq = q[i] - shift.c[i];
+                a0 = fmaf(dx, dx, a0);
+                a1 = fmaf(dq, dq, a1);
+                b = fmaf(dq, p[i] * mc.M(i), b);
+            }
+            a0 = group_allreduce<LPC>(a0);
+            a1 = group_allreduce<LPC>(a1);
+            b = group_allreduce<LPC>(b);
+            const float t = (float)((double)L * h);
+            const bool ok = active && fabsf(lr) <= 3.0e38f && a0 <= 3.0e38f && a1 <= 3.0e38f && fabsf(b) <= 3.0e38f;
+            const float alpha = ok ? fast_exp(fminf(lr, 0.f)) : 0.f;
+            const float g = ok ? t * (a1 - a0) * b : 0.f;
+            sum_g = fmaf(alpha, g, sum_g);
+            sum_alpha += alpha;
+        }
+    }
+    // behind block_stats_flush, whose owner threads have written this workgroup's slab (the jump columns as zeros)
+    __device__ __forceinline__ void flush(const NfmcStats& st) {
+        if constexpr (ON) {
+            if (mode != NFMC_TRAJECTORY_ADAPT) return;
+            __shared__ double tail[kWavesPerBlock][2];
+            const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+            const double wg = cross_chain_reduce_f64<LPC>((double)sum_g);       // lane 0: the sum over the group leaders
+            const double wa = cross_chain_reduce_f64<LPC>((double)sum_alpha);
+            if (lane == 0) {
+                tail[wave][0] = wg;
+                tail[wave][1] = wa;
+            }
+            __syncthreads();   // also orders the owner threads' stores of the two columns before the stores below
+            if (threadIdx.x == 0) {
+                double sg = 0.0, sa = 0.0;
+#pragma unroll
+                for (int w = 0; w < kWavesPerBlock; ++w) {
+                    sg += tail[w][0];
+                    sa += tail[w][1];
+                }
+                double* out = st.scratch + (size_t)blockIdx.x * (2 * CPL * LPC + kStatTail) + 2 * CPL * LPC;
+                out[2] = sg;
+                out[3] = sa;
+            }
+        }
+    }
+};
+
 // noise for this lane's CPL coordinates of (chain, step): native Philox or (REPLAY) replay from HBM
 template <int CPL, int LPC, int R = 10, bool REPLAY = true>
 __device__ __forceinline__ void draw_normals(const NfmcRng& rng, uint32_t tag, uint32_t gchain, int64_t row, int64_t n,
@@ -426,6 +521,8 @@ __global__ void __launch_bounds__(kBlock, NFMC_WPE) hmc_kernel(NfmcHmcArgs a, in
 #pragma unroll
     for (int i = 0; i < CPL; ++i) sx[i] = sxx[i] = 0.f;
     StatShift<CPL, LPC, TUNE> shift;
+    Trajectory<CPL, LPC, TUNE> traj;
+    traj.init(a.tune);
     uint32_t n_acc = 0, n_bad = 0, j_acc = 0, j_bad = 0;
     constexpr unsigned long long leaders = group_leaders(LPC);
 
@@ -478,7 +575,7 @@ __global__ void __launch_bounds__(kBlock, NFMC_WPE) hmc_kernel(NfmcHmcArgs a, in
                     }
                 }
             } else {
-                const int L = a.n_leapfrog;
+                const int L = traj.leapfrogs(a.n_leapfrog, a.rng.step0 + (uint32_t)s);
                 if (L > 0) {
                     const auto c0 = pot.prepare(q, g, d);
 #pragma unroll
@@ -503,6 +600,7 @@ __global__ void __launch_bounds__(kBlock, NFMC_WPE) hmc_kernel(NfmcHmcArgs a, in
                 accept = au.draw(a.rng, gchain, row, n, g, s) < lr;  // ln u < log r, hmc.py:111-113
                 n_bad += (uint32_t)__popcll(__ballot(active && !(fabsf(lr) <= 3.0e38f)) & leaders);
             }
+            traj.accumulate(x, q, p, shift, mc, lr, active);
             accept = accept && active;
             const uint64_t am = __ballot(accept);
             n_acc += (uint32_t)__popcll(am & leaders);
@@ -541,7 +639,10 @@ __global__ void __launch_bounds__(kBlock, NFMC_WPE) hmc_kernel(NfmcHmcArgs a, in
         }
         store_row<CPL, LPC, FAST>(a.x, row, d, g, active, x);
     }
-    if (a.stats.sum_x) block_stats_flush<CPL, LPC>(sx, sxx, n_acc, n_bad, a.stats, j_acc, j_bad);
+    if (a.stats.sum_x) {
+        block_stats_flush<CPL, LPC>(sx, sxx, n_acc, n_bad, a.stats, j_acc, j_bad);
+        traj.flush(a.stats);
+    }
 }
 
 

@@ -3,6 +3,7 @@
 // jump tail, 0 = none) and, for the kinds whose row in kPotKinds (pot_kinds.hpp) says own_units, in a mala and an hmc
 // unit per kind, so they compile in parallel.
 #include <mutex>
+#include <type_traits>
 
 #include "run_parts.hpp"
 #include "sampler_impl.hpp"
@@ -79,7 +80,8 @@ static bool fast_path(const Args* a, const Cfg& c) {
 constexpr int kTuneGrid = 256;   // one load round trip of the folding workgroup (two need more than its 128 VGPRs per thread)
 template <int NCHUNK>   // round trips: slabs / 256
 __global__ void __launch_bounds__(kFinishBlock) tune_finish_kernel(double* __restrict__ scratch, int nblocks, int dp, int d,
-                                                                   NfmcStats st, NfmcTune tn, unsigned long long attempted) {
+                                                                   NfmcStats st, NfmcTune tn, unsigned long long attempted,
+                                                                   uint32_t step0, int pool) {
     __shared__ double part[kFinishSlices][kFinishCols];
     const int width = 2 * dp + kStatTail;
     const int col = threadIdx.x % kFinishCols, slice = threadIdx.x / kFinishCols;
@@ -158,7 +160,9 @@ __global__ void __launch_bounds__(kFinishBlock) tune_finish_kernel(double* __res
         }
         if (n_tot > 0.0) shift[j] = (double)(float)(c + s1 / n_tot);
     }
-    if (threadIdx.x == 0 && tn.tune_step_size) {                                   // mcmc/base.py:153-161, tuning.py:22-38
+    if (threadIdx.x != 0) return;
+    const double h_used = tn.trajectory ? tn.state[NFMC_TUNE_STEP_SIZE] : 0.0;   // what the update's transitions ran with
+    if (tn.tune_step_size) {                                                       // mcmc/base.py:153-161, tuning.py:22-38
         const double acc = totals[2 * dp];
         const double err = tn.state[NFMC_TUNE_TARGET] - acc / n_tot;
         const double S = tn.state[NFMC_TUNE_ERROR_SUM] + err;
@@ -171,6 +175,55 @@ __global__ void __launch_bounds__(kFinishBlock) tune_finish_kernel(double* __res
         tn.state[NFMC_TUNE_LOG_SMOOTH] = log_smooth;
         tn.state[NFMC_TUNE_ITERATION] = it + 1.0;
         tn.state[NFMC_TUNE_STEP_SIZE] = exp(log_smooth);
+    }
+    // Trajectory length (NfmcTune.trajectory; estimator and controller in the header comment): the leapfrog steps of the
+    // update's transitions [step0, step0 + pool) recounted as the kernel counted them, then, while T adapts, one Adam step
+    // on log T from the pooled sums the launch left in the two jump columns, with the step size set just above.
+    if (tn.trajectory) {
+        double* __restrict__ tr = tn.state + NFMC_TUNE_WORDS + 3 * dp + kStatTail;
+        const double T_used = tr[NFMC_TRAJ_LENGTH], lmax = tr[NFMC_TRAJ_MAX_LEAPFROG];
+        double steps = 0.0;
+        for (int s = 0; s < pool; ++s) steps += (double)trajectory_leapfrog_count(step0 + (uint32_t)s, T_used, h_used, lmax);
+        tr[NFMC_TRAJ_LEAPFROG_TOTAL] += steps;
+        if (tn.trajectory == NFMC_TRAJECTORY_ADAPT) {
+            const double h_new = tn.state[NFMC_TUNE_STEP_SIZE];
+            const double sum_g = totals[2 * dp + 2], sum_alpha = totals[2 * dp + 3];
+            const double g_hat = sum_alpha > 0.0 ? sum_g / sum_alpha : 0.0;
+            double log_T = tr[NFMC_TRAJ_LOG_LENGTH], v = tr[NFMC_TRAJ_V], log_bar = tr[NFMC_TRAJ_LOG_AVERAGED];
+            if (sum_alpha > 0.0 && fabs(g_hat) <= 1.7e308) {   // else: the update leaves T alone
+                const double j = tr[NFMC_TRAJ_COUNT] + 1.0, b2 = tr[NFMC_TRAJ_BETA2], clip = tr[NFMC_TRAJ_CLIP];
+                v = b2 * v + (1.0 - b2) * g_hat * g_hat;
+                double delta = tr[NFMC_TRAJ_LEARNING_RATE] * g_hat / (sqrt(v / (1.0 - pow(b2, j))) + 1e-8);
+                delta = delta > clip ? clip : (delta < -clip ? -clip : delta);
+                const double lo = log(h_new), hi = log(lmax * h_new);
+                log_T += delta;
+                log_T = log_T < lo ? lo : log_T;
+                log_T = log_T > hi ? hi : log_T;
+                const double w = pow(j, -0.75);
+                log_bar = w * log_T + (1.0 - w) * log_bar;
+                tr[NFMC_TRAJ_COUNT] = j;
+                tr[NFMC_TRAJ_V] = v;
+                tr[NFMC_TRAJ_LOG_LENGTH] = log_T;
+                tr[NFMC_TRAJ_LOG_AVERAGED] = log_bar;
+                tr[NFMC_TRAJ_LENGTH] = exp(log_T);
+            }
+            tr[NFMC_TRAJ_G_HAT] = g_hat;
+            tr[NFMC_TRAJ_ALPHA_SUM] = sum_alpha;
+            const double used = tr[NFMC_TRAJ_HISTORY_USED];
+            if (used < tr[NFMC_TRAJ_HISTORY_ROWS]) {   // updates beyond the capacity overwrite nothing
+                double* __restrict__ row = tr + NFMC_TRAJ_WORDS + (size_t)used * NFMC_TRAJ_ROW_WORDS;
+                row[NFMC_TRAJ_ROW_LENGTH] = T_used;
+                row[NFMC_TRAJ_ROW_STEP_SIZE] = h_used;
+                row[NFMC_TRAJ_ROW_G_HAT] = g_hat;
+                row[NFMC_TRAJ_ROW_ALPHA_SUM] = sum_alpha;
+                row[NFMC_TRAJ_ROW_LEAPFROGS] = steps;
+                row[NFMC_TRAJ_ROW_LOG_LENGTH] = log_T;
+                row[NFMC_TRAJ_ROW_V] = v;
+                row[NFMC_TRAJ_ROW_LOG_AVERAGED] = log_bar;
+                row[NFMC_TRAJ_ROW_NEXT_STEP_SIZE] = h_new;
+            }
+            tr[NFMC_TRAJ_HISTORY_USED] = used + 1.0;
+        }
     }
 }
 
@@ -233,20 +286,25 @@ static int tune_grid(int64_t tiles, int dp, int64_t scratch_bytes, bool* two_lev
 
 // the fold + controller of one update behind a tuning launch of `grid` workgroups
 static void tune_update(const NfmcStats& stats, const NfmcTune& tune, int grid, bool two_level, int dp, int d, unsigned long long attempted,
-                        hipStream_t st) {
+                        uint32_t step0, int pool, hipStream_t st) {
     const int width = 2 * dp + kStatTail;
     if (two_level) {
         double* partial = stats.scratch + (size_t)(kMaxGrid - kTuneFoldWgs) * width;
         const int wgs = (grid + kTuneFoldSlabs - 1) / kTuneFoldSlabs;
         hipLaunchKernelGGL(tune_fold_kernel, dim3(wgs), dim3(kFinishBlock), 0, st, stats.scratch, grid, width, partial);
-        hipLaunchKernelGGL(tune_finish_kernel<1>, dim3(1), dim3(kFinishBlock), 0, st, partial, wgs, dp, d, stats, tune, attempted);
+        hipLaunchKernelGGL(tune_finish_kernel<1>, dim3(1), dim3(kFinishBlock), 0, st, partial, wgs, dp, d, stats, tune, attempted, step0, pool);
     } else {
-        hipLaunchKernelGGL(tune_finish_kernel<1>, dim3(1), dim3(kFinishBlock), 0, st, stats.scratch, grid, dp, d, stats, tune, attempted);
+        hipLaunchKernelGGL(tune_finish_kernel<1>, dim3(1), dim3(kFinishBlock), 0, st, stats.scratch, grid, dp, d, stats, tune, attempted, step0, pool);
     }
 }
 
 template <class Args>
-static int check_tune(const Args& a, int dp) {
+static int check_tune(const Args& a, int dp, bool hmc) {
+    // the jittered trajectory: the hmc kernel with a tuning state, a trajectory block behind it and the Metropolis test
+    if (a.tune.trajectory != NFMC_TRAJECTORY_OFF) {
+        if (!hmc || !a.tune.state || !(a.adjust & 1)) return NFMC_EINVAL;
+        if (a.tune.trajectory != NFMC_TRAJECTORY_ADAPT && a.tune.trajectory != NFMC_TRAJECTORY_FROZEN) return NFMC_EINVAL;
+    }
     if (!a.tune.state) return NFMC_OK;
     if (!a.stats.sum_x || a.stats.defer || a.jump) return NFMC_EINVAL;   // the controller rides on the per-call fold
     if (a.tune.tune_inv_mass_diag && (!a.tune.inv_mass_diag || a.tune.inv_mass_diag != a.inv_mass_diag)) return NFMC_EINVAL;
@@ -305,6 +363,11 @@ extern "C" int64_t nfmc_tune_state_doubles(int32_t d) {
     return NFMC_TUNE_WORDS + 3 * padded_d(d) + kStatTail;   // controller words, column totals, shift
 }
 
+extern "C" int64_t nfmc_tune_trajectory_doubles(int32_t history_rows) {
+    if (history_rows < 0) return 0;
+    return NFMC_TRAJ_WORDS + (int64_t)history_rows * NFMC_TRAJ_ROW_WORDS;
+}
+
 extern "C" int nfmc_sampler_layout(int32_t d, int32_t pot_kind_id, int32_t* cpl, int32_t* lpc) {
     if (!cpl || !lpc || d <= 0) return NFMC_EINVAL;
     if (d > 1024) return NFMC_ESHAPE;
@@ -337,7 +400,7 @@ static int sampler_steps(const Args* args, hipStream_t st, Launch launch, const 
     if (a.stats.sum_x && a.stats.scratch_bytes < (int64_t)grid * (2 * dp + kStatTail) * (int64_t)sizeof(double))
         return NFMC_ESCRATCH;
     if (check_defer(a.stats, dp, a.d)) return NFMC_EINVAL;
-    if (int rc = check_tune(a, dp)) return rc;
+    if (int rc = check_tune(a, dp, std::is_same<Args, NfmcHmcArgs>::value)) return rc;
     if (part && a.stats.sum_x) a.stats.scratch += (size_t)part->slab0 * (2 * dp + kStatTail);   // checked as the caller gave it
     const JumpDev jd = jump_dev(a.jump);
     unsigned long long* jc = a.jump ? a.jump->counters : nullptr;
@@ -355,7 +418,7 @@ static int sampler_steps(const Args* args, hipStream_t st, Launch launch, const 
             if (a.masks_out) b.masks_out = a.masks_out + (int64_t)s0 * a.n;
             if (a.log_ratio_out) b.log_ratio_out = a.log_ratio_out + (int64_t)s0 * a.n;
             if (int rc = launch(b, jd, c, 0, fast, tiles, grid)) return rc;
-            tune_update(a.stats, a.tune, grid, two_level, dp, a.d, (unsigned long long)a.n * (unsigned long long)k, st);
+            tune_update(a.stats, a.tune, grid, two_level, dp, a.d, (unsigned long long)a.n * (unsigned long long)k, b.rng.step0, k, st);
             NFMC_HIP_CHECK_LAUNCH();
             store_advance(a.samples, k);
         }

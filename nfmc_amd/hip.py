@@ -68,12 +68,21 @@ class NfmcJumpTail(C.Structure):
 
 class NfmcTune(C.Structure):
     _fields_ = [('state', c_fp), ('inv_mass_diag', c_fp), ('tune_step_size', C.c_int32), ('tune_inv_mass_diag', C.c_int32),
-                ('every', C.c_int32), ('reserved', C.c_int32)]
+                ('every', C.c_int32), ('trajectory', C.c_int32)]
 
 
 TUNE_STEP_SIZE, TUNE_LOG_SMOOTH, TUNE_ERROR_SUM, TUNE_ITERATION, TUNE_ANCHOR, TUNE_LOG_RAW = 0, 1, 2, 3, 4, 5
 TUNE_TARGET, TUNE_KAPPA, TUNE_GAMMA, TUNE_IMD_ADJUSTMENT, TUNE_TICKET, TUNE_WORDS = 6, 7, 8, 9, 10, 12
 STAT_TAIL = 4
+# NfmcTune.trajectory and the words of the trajectory block behind the tuning state (include/nfmc_hip.h: NFMC_TRAJ_*)
+TRAJECTORY_OFF, TRAJECTORY_ADAPT, TRAJECTORY_FROZEN = 0, 1, 2
+(TRAJ_LENGTH, TRAJ_LOG_LENGTH, TRAJ_LOG_AVERAGED, TRAJ_V, TRAJ_COUNT, TRAJ_LEARNING_RATE, TRAJ_BETA2, TRAJ_CLIP,
+ TRAJ_MAX_LEAPFROG, TRAJ_LEAPFROG_TOTAL, TRAJ_G_HAT, TRAJ_ALPHA_SUM, TRAJ_HISTORY_ROWS, TRAJ_HISTORY_USED) = range(14)
+TRAJ_WORDS = 16
+# columns of a history row: what the pool ran with, what it measured, and the controller state its update left
+(TRAJ_ROW_LENGTH, TRAJ_ROW_STEP_SIZE, TRAJ_ROW_G_HAT, TRAJ_ROW_ALPHA_SUM, TRAJ_ROW_LEAPFROGS, TRAJ_ROW_LOG_LENGTH,
+ TRAJ_ROW_V, TRAJ_ROW_LOG_AVERAGED, TRAJ_ROW_NEXT_STEP_SIZE) = range(9)
+TRAJ_ROW_WORDS = 9
 
 
 def padded_d(d):
@@ -229,6 +238,7 @@ class NfmcLimits(C.Structure):
 SYMBOLS = [
     ('nfmc_stats_scratch_bytes', C.c_int64, [C.c_int32]),
     ('nfmc_tune_state_doubles', C.c_int64, [C.c_int32]),
+    ('nfmc_tune_trajectory_doubles', C.c_int64, [C.c_int32]),
     ('nfmc_sampler_layout', C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ('nfmc_mala_steps_f32', C.c_int, [C.POINTER(NfmcMalaArgs), c_fp]),
     ('nfmc_hmc_steps_f32', C.c_int, [C.POINTER(NfmcHmcArgs), c_fp]),

@@ -21,7 +21,7 @@ from ..flows import Flow, RealNVP
 from ..tuning import train_val_split
 from ..util import metropolis_acceptance_log_ratio
 from .common import Run, _refit, accept_select, chunks, progress, resolve_target
-from .mcmc import HMC, MALA, MH, UHMC, ULA, Langevin, TargetFailure, _guarded
+from .mcmc import HMC, MALA, MH, UHMC, ULA, Langevin, TargetFailure, _guarded, refuse_inner_trajectory
 
 
 @dataclass
@@ -281,6 +281,7 @@ class JumpNFMC(Sampler):
 
     def warmup(self, x0, show_progress: bool = True, time_limit_seconds=None) -> MCMCOutput:
         """jump.py:104-154: tune the inner sampler, then MLE-fit the flow on its samples (rollback on ValueError)."""
+        refuse_inner_trajectory(self.inner_sampler, type(self).__name__)
         inner_limit = 0.7 * time_limit_seconds if time_limit_seconds is not None else None
         t0 = time.time()
         self.inner_sampler.params.store_samples = True
@@ -302,6 +303,7 @@ class JumpNFMC(Sampler):
     def sample(self, x0, show_progress: bool = True, time_limit_seconds=None) -> MCMCOutput:
         """jump.py:156-246 on the device."""
         inner = self.inner_sampler
+        refuse_inner_trajectory(inner, type(self).__name__)
         if not inner.params.store_samples:
             raise ValueError("Inner sampler in jump HMC must store samples")
         run = Run(self, x0)

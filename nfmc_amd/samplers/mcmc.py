@@ -19,7 +19,7 @@ from tqdm import tqdm
 
 from .. import hip
 from ..containers import MCMCKernel, MCMCOutput, MCMCParameters, Sampler
-from ..tuning import DualAveraging, DualAveragingParams
+from ..tuning import DualAveraging, DualAveragingParams, TrajectoryAdaptationParams
 from .common import Run, accept_select, imd_tensor, launch_limit, progress, resolve_target
 
 
@@ -65,9 +65,30 @@ class DeviceTuning:
     include/nfmc_hip.h): the controller (mcmc/base.py:142-161, tuning.py:15-41) runs inside each call's statistics fold
     and the next call reads what it wrote, so the warmup loop never waits for the GPU."""
 
-    def __init__(self, sampler, run):
+    def __init__(self, sampler, run, trajectory=hip.TRAJECTORY_OFF):
+        """trajectory: NfmcTune.trajectory of the launches (hmc).  TRAJECTORY_ADAPT: the state carries the trajectory block
+        with one history row per expected controller update; TRAJECTORY_FROZEN: the block alone, the length held."""
         k, p, da = sampler.kernel, sampler.params, sampler.kernel.da
-        st = torch.zeros(int(hip.lib().nfmc_tune_state_doubles(run.d)), dtype=torch.float64)
+        self.trajectory = int(trajectory)
+        base = int(hip.lib().nfmc_tune_state_doubles(run.d))
+        self.trajectory_offset, self.history_rows = base, 0
+        if self.trajectory:
+            if self.trajectory == hip.TRAJECTORY_ADAPT:
+                every = max(1, int(getattr(p, 'tune_every', 1)))
+                self.history_rows = -(-int(p.n_iterations) // every)
+            base += int(hip.lib().nfmc_tune_trajectory_doubles(self.history_rows))
+        st = torch.zeros(base, dtype=torch.float64)
+        if self.trajectory:
+            ap = getattr(p, 'trajectory_adaptation', None) or TrajectoryAdaptationParams()
+            length = k.trajectory_length
+            if length is None:
+                length = int(k.n_leapfrog_steps) * float(k.step_size)
+            tr = st[self.trajectory_offset:]
+            tr[hip.TRAJ_LENGTH] = float(length)
+            tr[hip.TRAJ_LOG_LENGTH] = tr[hip.TRAJ_LOG_AVERAGED] = math.log(float(length))
+            tr[hip.TRAJ_LEARNING_RATE], tr[hip.TRAJ_BETA2], tr[hip.TRAJ_CLIP] = ap.learning_rate, ap.beta2, ap.clip
+            tr[hip.TRAJ_MAX_LEAPFROG] = int(getattr(p, 'max_leapfrog_steps', 128))
+            tr[hip.TRAJ_HISTORY_ROWS] = self.history_rows
         st[hip.TUNE_STEP_SIZE] = float(k.step_size)
         st[hip.TUNE_LOG_SMOOTH] = da.log_smooth
         st[hip.TUNE_ERROR_SUM] = da.error_sum
@@ -83,8 +104,8 @@ class DeviceTuning:
         st[c0:c0 + run.d] = run.x.double().mean(0).float().double()
         self.state = st.to(run.dev)
         self.imd = k.inv_mass_diag.detach().to(run.dev, torch.float32).contiguous().clone()
-        self.tune_step = bool(p.tune_step_size and p.adjustment)            # mcmc/base.py:153
-        self.tune_imd = bool(p.tune_inv_mass_diag and run.n > 1)            # mcmc/base.py:146
+        self.tune_step = bool(p.tuning and p.tune_step_size and p.adjustment)            # mcmc/base.py:153
+        self.tune_imd = bool(p.tuning and p.tune_inv_mass_diag and run.n > 1)            # mcmc/base.py:146
         self.updates = 0
 
     def struct(self, every=0, n_steps=1):
@@ -92,11 +113,21 @@ class DeviceTuning:
         every = int(every) if every and every < n_steps else 0
         self.updates += -(-n_steps // every) if every else 1
         return hip.NfmcTune(hip.ptr(self.state, torch.float64), hip.ptr(self.imd), int(self.tune_step), int(self.tune_imd),
-                            every, 0)
+                            every, self.trajectory)
+
+    def leapfrog_total(self):
+        """Leapfrog steps per chain the launches took so far (the device word; synchronises the stream)."""
+        return int(round(float(self.state[self.trajectory_offset + hip.TRAJ_LEAPFROG_TOTAL].item())))
 
     def download(self, kernel):
         """The tuned kernel back on the host (one copy, at the end of the warmup)."""
         st = self.state.cpu()
+        if self.trajectory == hip.TRAJECTORY_ADAPT and self.updates:
+            tr = st[self.trajectory_offset:]
+            kernel.trajectory_length = math.exp(float(tr[hip.TRAJ_LOG_AVERAGED]))
+            used = min(self.history_rows, int(round(float(tr[hip.TRAJ_HISTORY_USED]))))
+            kernel.trajectory_history = tr[hip.TRAJ_WORDS:hip.TRAJ_WORDS + used * hip.TRAJ_ROW_WORDS].reshape(
+                used, hip.TRAJ_ROW_WORDS).clone()
         if self.tune_imd:
             kernel.inv_mass_diag = self.imd.cpu().to(kernel.inv_mass_diag.dtype)
         if self.tune_step and self.updates:
@@ -130,16 +161,36 @@ class LangevinParameters(MetropolisParameters):
 class HMCKernel(MetropolisKernel):
     event_size: int
     n_leapfrog_steps: int = 20
+    # Set (by a warmup with `tune_trajectory_length`, or by hand): sampling runs jittered trajectories of this mean
+    # length, L = clamp(ceil(u T / h), 1, max_leapfrog_steps) per transition, and ignores n_leapfrog_steps
+    trajectory_length: float = None
+    # (updates, hip.TRAJ_ROW_WORDS) fp64: one row per controller update of the last adaptive warmup (DeviceTuning.download)
+    trajectory_history: Any = None
 
     def __repr__(self):
+        if self.trajectory_length is not None:
+            steps = f'trajectory: {self.trajectory_length:.3g} (jittered; n_leapfrog_steps = {self.n_leapfrog_steps} ignored)'
+        else:
+            steps = f'leapfrogs: {self.n_leapfrog_steps}'
         return (f'log step: {math.log(self.step_size):.2f}, '
-                f'leapfrogs: {self.n_leapfrog_steps}, '
+                f'{steps}, '
                 f'mass norm: {torch.max(torch.abs(self.inv_mass_diag)):.2f}')
 
 
 @dataclass
 class HMCParameters(MetropolisParameters):
-    pass
+    # warmup adapts the trajectory length T on the device (ChEES-HMC; tuning.TrajectoryAdaptation) and leaves its iterate
+    # average in kernel.trajectory_length
+    tune_trajectory_length: bool = False
+    max_leapfrog_steps: int = 128
+    trajectory_adaptation: TrajectoryAdaptationParams = None
+
+
+def refuse_inner_trajectory(inner, outer):
+    """Jump samplers and NeuTra run their inner hmc at a fixed leapfrog count: the jittered trajectory is not built there."""
+    if getattr(inner.params, 'tune_trajectory_length', False) or getattr(inner.kernel, 'trajectory_length', None) is not None:
+        raise ValueError('%s: the inner hmc kernel runs a fixed number of leapfrog steps; tune_trajectory_length / '
+                         'trajectory_length are supported by the plain hmc sampler only' % outer)
 
 
 class TargetFailure(Exception):
@@ -191,6 +242,10 @@ class MCMCSampler(Sampler):
     def _counts(self, n, k):
         raise NotImplementedError
 
+    def _trajectory_mode(self, run, pot):
+        """NfmcTune.trajectory of this run's launches (hmc); raises ValueError before any launch where the mode cannot run."""
+        return hip.TRAJECTORY_OFF
+
     def warmup(self, x0, show_progress: bool = True, time_limit_seconds=None) -> MCMCOutput:
         # mcmc/base.py:39-54
         with torch.no_grad():
@@ -232,6 +287,7 @@ class MCMCSampler(Sampler):
         # warmup of a fused sampler on one GPU: kernel state and controller on the device, no host round trip per step
         # (sharded chains keep the host controller: its statistics are all-reduced over the ranks every step)
         tune = None
+        trajectory = self._trajectory_mode(run, pot)
         if self.params.tuning:
             # warmup ALWAYS draws from the default Philox4x32-10 stream, whichever controller runs (device, host,
             # sharded): tuning launches use the general kernels, which carry that stream only, and a warmup must not
@@ -239,12 +295,17 @@ class MCMCSampler(Sampler):
             run.rounds = 10
         if (self.params.tuning and pot is not None and isinstance(self, MetropolisSampler)
                 and (run.shard is None or run.shard.world == 1) and os.environ.get('NFMC_TUNE_DEVICE', '1') != '0'):
-            tune = DeviceTuning(self, run)
+            tune = DeviceTuning(self, run, trajectory)
             # one ABI call enqueues every (kernel, controller) pair of up to 512 transitions: no host work per update
             tune.every = max(1, int(getattr(self.params, 'tune_every', 1)))
             limit = launch_limit(max(32, tune.every), show_progress, time_limit_seconds)
             # calls of whole pools: the controller updates once per `every` transitions whatever the call size
             limit -= limit % tune.every
+        elif trajectory:
+            # jittered trajectories at a frozen length: the tuning path (general kernels, per-call fold) with the tuners off
+            tune = DeviceTuning(self, run, trajectory)
+            tune.every = 0
+            limit = launch_limit(32, show_progress, time_limit_seconds)
         for done, k in run.launches(K, limit, t0, time_limit_seconds, bar):
             if tune is not None:
                 self._launch(run, pot, k, step0 + done, store, tune=tune)
@@ -257,6 +318,8 @@ class MCMCSampler(Sampler):
             if self.params.tuning and tune is None:
                 with torch.no_grad():
                     self.update_kernel({'x': run.x.reshape(n, *event_shape), 'mask': mask})
+        # what ran: with a jittered trajectory the leapfrog steps are counted on the device, read once here
+        self._leapfrog_total = tune.leapfrog_total() if tune is not None and tune.trajectory else None
         calls, grads = self._counts(n, run.done)
         run.finish(out, t0, n * run.done, store, n_target_calls=calls, n_target_gradient_calls=grads,
                    n_divergences=self._n_divergences)
@@ -553,9 +616,37 @@ class HMC(MetropolisSampler):
         return "HMC"
 
     def _counts(self, n, k):
+        total = getattr(self, '_leapfrog_total', None)
+        if total is not None:   # jittered trajectories: 2 n gradient calls per leapfrog step taken
+            return 2 * n * total + (2 * n * k if self.params.adjustment else 0), 2 * n * total
         grads = 2 * self.kernel.n_leapfrog_steps * n  # hmc.py:122-125
         calls = grads + (2 * n if self.params.adjustment else 0)
         return calls * k, grads * k
+
+    def _trajectory_mode(self, run, pot):
+        p, k = self.params, self.kernel
+        adapt = bool(p.tuning and getattr(p, 'tune_trajectory_length', False))
+        if not adapt and getattr(k, 'trajectory_length', None) is None:
+            return hip.TRAJECTORY_OFF
+        what = 'tune_trajectory_length' if adapt else 'trajectory_length'
+        if not p.adjustment:
+            raise ValueError('%s: uhmc has no acceptance probabilities to weight the criterion with; use hmc' % what)
+        if pot is None:
+            raise ValueError('%s: the target takes the split path (no closed-form potential); the jittered trajectory '
+                             'runs in the fused hmc kernel only' % what)
+        if run.shard is not None and run.shard.world > 1:
+            raise ValueError('%s: sharded chains keep the host controller, which does not adapt the trajectory length' % what)
+        if os.environ.get('NFMC_TUNE_DEVICE', '1') == '0':
+            raise ValueError('%s: NFMC_TUNE_DEVICE=0 selects the host controller, which does not adapt the trajectory '
+                             'length' % what)
+        if int(getattr(self, 'rng_rounds', 10) or 10) == 7:
+            raise ValueError('%s: rng_rounds=7 runs the exact-fit kernels; the jittered trajectory runs in the general '
+                             'kernels on the Philox4x32-10 stream' % what)
+        if not float(k.step_size) > 0 or (k.trajectory_length is not None and not float(k.trajectory_length) > 0):
+            raise ValueError('%s: step_size and trajectory_length must be positive' % what)
+        if int(getattr(p, 'max_leapfrog_steps', 128)) < 1:
+            raise ValueError('%s: max_leapfrog_steps must be at least 1' % what)
+        return hip.TRAJECTORY_ADAPT if adapt else hip.TRAJECTORY_FROZEN
 
     def propose(self, x):
         """hmc.py:96-126 for an arbitrary target: leapfrog with autograd gradients on the GPU."""

@@ -23,7 +23,7 @@ from ..potentials import (DiffusionBridge, FullRankGaussian, Funnel, LatticePhi4
                           Rosenbrock, StochasticVolatility, VaryingEffectsRegression)
 from .common import Run, imd_tensor, launch_limit, progress, resolve_target
 from .mcmc import (HMC, MH, HMCKernel, HMCParameters, MHKernel, MHParameters, MetropolisKernel, MetropolisParameters,
-                   MetropolisSampler)
+                   MetropolisSampler, refuse_inner_trajectory)
 
 
 @dataclass
@@ -142,6 +142,7 @@ class NeuTra(Sampler):
 
     def warmup(self, x0, show_progress: bool = True, time_limit_seconds=None) -> MCMCOutput:
         """neutra.py:70-107: variational fit, then tune the inner sampler."""
+        refuse_inner_trajectory(self.inner_sampler, type(self).__name__)
         fit_limit = 0.3 * time_limit_seconds if time_limit_seconds is not None else None
         t0 = time.time()
         from .imh import _accepts_potential
@@ -159,6 +160,7 @@ class NeuTra(Sampler):
     def sample(self, x0, show_progress: bool = True, time_limit_seconds=None) -> MCMCOutput:
         """neutra.py:109-129 on the device."""
         inner = self.inner_sampler
+        refuse_inner_trajectory(inner, type(self).__name__)
         inner.params.n_iterations = self.params.n_iterations
         inner.params.sampling_mode()
         inner.params.store_samples = self.params.store_samples

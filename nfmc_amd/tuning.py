@@ -48,6 +48,75 @@ class DualAveraging:
         return 'DualAveraging(step=%.4g, error_sum=%.2f, t=%d)' % (self.value, self.error_sum, self.iteration)
 
 
+@dataclass
+class TrajectoryAdaptationParams:
+    """Constants of the trajectory-length controller (ChEES-HMC, Hoffman, Radul and Sountsov, AISTATS 2021)."""
+    learning_rate: float = 0.025
+    beta2: float = 0.95    # decay of the second-moment estimate
+    clip: float = 0.35     # largest move of log T per update
+
+
+def radical_inverse(k: int) -> float:
+    """Base-2 radical inverse of k + 1, offset by half an ulp of the 32-bit grid: (bitreverse32(k + 1) + 0.5) 2^-32, the
+    jitter of the transition with Philox step counter k (1/2, 1/4, 3/4, 1/8, ... from k = 0).  Exact in fp64."""
+    i = (int(k) + 1) & 0xffffffff
+    return (int('{:032b}'.format(i)[::-1], 2) + 0.5) * 2.0 ** -32
+
+
+def leapfrog_count(k: int, trajectory_length: float, step_size: float, max_leapfrog_steps: int = 128) -> int:
+    """Leapfrog steps of the transition with step counter k: clamp(ceil(u T / h), 1, L_max) in fp64, u = radical_inverse(k).
+    The same operations in the same order as the device's trajectory_leapfrog_count (csrc/sampler_impl.hpp): both sides
+    agree to the integer when fed the same fp64 T and h."""
+    r = math.ceil(radical_inverse(k) * float(trajectory_length) / float(step_size)) if step_size > 0 else 1
+    return int(max(1, min(int(max_leapfrog_steps), r)))
+
+
+class TrajectoryAdaptation:
+    """Stochastic gradient ascent on log T of the ChEES criterion: Adam with beta1 = 0, driven by
+    `step(g_hat, alpha_sum, step_size)` once per controller update.  With j the update count from 1:
+      v        <- b2 v + (1 - b2) g_hat^2
+      delta     = lr g_hat / (sqrt(v / (1 - b2^j)) + 1e-8), clipped to +-clip
+      log T    <- clamp(log T + delta, log h, log(L_max h))       h: the step size the same update just set
+      log Tbar <- w log T + (1 - w) log Tbar,   w = j^-0.75
+    An update whose pooled weight `alpha_sum` is zero (or whose g_hat is not finite) changes nothing.  `value` is the
+    length the warmup runs on, `averaged` the one handed to sampling.  The controller on the device
+    (tune_finish_kernel, csrc/sampler_kernels.hip) is this recurrence on fp64 words of the trajectory block."""
+
+    def __init__(self, initial_length, params: TrajectoryAdaptationParams = None, max_leapfrog_steps: int = 128):
+        self.params = params if params is not None else TrajectoryAdaptationParams()
+        self.max_leapfrog_steps = int(max_leapfrog_steps)
+        self.log_length = math.log(initial_length)
+        self.log_averaged = self.log_length
+        self.v = 0.0
+        self.count = 0
+
+    def step(self, g_hat, alpha_sum, step_size):
+        if not (alpha_sum > 0) or not math.isfinite(g_hat):
+            return
+        p = self.params
+        j = self.count + 1
+        self.v = p.beta2 * self.v + (1 - p.beta2) * g_hat * g_hat
+        delta = p.learning_rate * g_hat / (math.sqrt(self.v / (1 - p.beta2 ** j)) + 1e-8)
+        delta = max(-p.clip, min(p.clip, delta))
+        lo = math.log(step_size)
+        hi = math.log(self.max_leapfrog_steps * step_size)
+        self.log_length = min(max(self.log_length + delta, lo), hi)
+        w = j ** -0.75
+        self.log_averaged = w * self.log_length + (1 - w) * self.log_averaged
+        self.count = j
+
+    @property
+    def value(self) -> float:
+        return math.exp(self.log_length)
+
+    @property
+    def averaged(self) -> float:
+        return math.exp(self.log_averaged)
+
+    def __repr__(self):
+        return 'TrajectoryAdaptation(T=%.4g, averaged=%.4g, updates=%d)' % (self.value, self.averaged, self.count)
+
+
 def _shuffled(rows: torch.Tensor) -> torch.Tensor:
     return rows[torch.randperm(rows.shape[0], device=rows.device)]
 
