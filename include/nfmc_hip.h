@@ -615,6 +615,89 @@ typedef struct {
 
 int nfmc_hmc_steps_f32(const NfmcHmcArgs* args, nfmc_stream_t stream);
 
+/* ---- Microcanonical Langevin Monte Carlo (Robnik, De Luca, Silverstein and Seljak, JMLR 2023; Robnik and Seljak 2024;
+ * blackjax `mclmc`).  State of a chain: x in R^d and a unit velocity u in R^d, d >= 2; parameters: step size eps,
+ * decoherence length L, per-coordinate scales sigma_j = sqrt(inv_mass_diag_j).  One step is B(eps/2) A(eps) B(eps/2) O:
+ *     B(e), g = grad U(x):  gt = sigma * g, gn = |gt|, e_hat = -gt / gn, ue = u . e_hat, delta = e gn / (d - 1),
+ *                           zeta = exp(-delta), uu = e_hat (1 - zeta)(1 + zeta + ue (1 - zeta)) + 2 zeta u, u <- uu / |uu|,
+ *                           dK = (d - 1) [delta - ln 2 + log(1 + ue + (1 - ue) zeta^2)];  gn = 0: u unchanged, dK = 0
+ *     A(eps):               x <- x + eps sigma * u
+ *     O:                    nu = sqrt((exp(2 eps / L) - 1) / d);  u <- (u + nu z) / |u + nu z|, z ~ N(0, I) from the chain's
+ *                           Philox stream at step counter rng.step0 + s on the noise stream (tag 0)
+ * and the energy error of the step is dE = U(x') - U(x) + dK_1 + dK_2.  There is no Metropolis test: ACCEPTED = ATTEMPTED.
+ * A step whose dE or new x is not finite is not taken: x keeps its value, u takes the O update from its value before the
+ * step, and the chain is counted in NFMC_CNT_NONFINITE.  The second B of a step and the first B of the next share one
+ * gradient, so a step costs one gradient and one value of U; every launch evaluates both once more at its starting x.
+ * General kernels on the Philox4x32-10 stream at the default register layouts, every potential kind, d = 2 .. 1024.
+ *
+ * Warmup on the device (NfmcMclmcTune): after every `every` steps of a call a controller kernel pools the update's
+ * n x every steps and rewrites the state words the next launch reads:
+ *     V = sum of finite dE^2 / (count d)                         count: the update's steps with a finite dE and x'
+ *     count = 0 or V not finite:  eps <- eps / 2, nothing else moves
+ *     else  log eps <- log eps + clamp(log(target / V) / 6, -ln 2, ln 2)        (tune_step_size)
+ *           s_j <- (1 - beta) s_j + beta v_j                                    (tune_inv_mass_diag; s = inv_mass_diag,
+ *                                       v_j: unbiased variance of coordinate j over the update's states)
+ *           L <- factor sqrt(sum_j v_j / s_j), s_j after its own update          (tune_decoherence_length)
+ * `state` words (fp64), nfmc_mclmc_state_doubles(d, history_rows) of them, caller-allocated and caller-initialised: */
+enum {
+    NFMC_MCLMC_STEP_SIZE = 0,           /* eps: read by the kernel, rewritten by the controller */
+    NFMC_MCLMC_DECOHERENCE_LENGTH = 1,  /* L: likewise */
+    NFMC_MCLMC_TARGET = 2,              /* target of V (5e-4) */
+    NFMC_MCLMC_IMD_ADJUSTMENT = 3,      /* beta */
+    NFMC_MCLMC_DECOHERENCE_FACTOR = 4,  /* factor */
+    NFMC_MCLMC_ENERGY_VARIANCE = 5,     /* V of the last update (out) */
+    NFMC_MCLMC_COUNT = 6,               /* its count (out) */
+    NFMC_MCLMC_HISTORY_ROWS = 7,        /* capacity of the history, in rows */
+    NFMC_MCLMC_HISTORY_USED = 8,        /* updates so far; rows beyond the capacity are not written (in: 0) */
+    NFMC_MCLMC_WORDS = 12               /* = NFMC_TUNE_WORDS: followed, as there, by 2 * padded_d + 4 words of column totals
+                                           and padded_d words of the per-coordinate shift c (the caller initialises c: the
+                                           column means of x0; zeros are valid), nfmc_tune_state_doubles(d) in all; then the
+                                           history, one row per update */
+};
+/* A history row: eps and L the update's steps ran with, what they measured, and what the update left */
+enum {
+    NFMC_MCLMC_ROW_STEP_SIZE = 0,
+    NFMC_MCLMC_ROW_DECOHERENCE_LENGTH = 1,
+    NFMC_MCLMC_ROW_ENERGY_VARIANCE = 2,
+    NFMC_MCLMC_ROW_COUNT = 3,
+    NFMC_MCLMC_ROW_NEXT_STEP_SIZE = 4,
+    NFMC_MCLMC_ROW_NEXT_DECOHERENCE_LENGTH = 5,
+    NFMC_MCLMC_ROW_WORDS = 6
+};
+typedef struct {
+    double* state;                  /* NULL: no tuning (step_size / decoherence_length / inv_mass_diag as given) */
+    float* inv_mass_diag;           /* (d,) device, updated in place when tune_inv_mass_diag; must be the call's inv_mass_diag */
+    int32_t tune_step_size;
+    int32_t tune_decoherence_length;
+    int32_t tune_inv_mass_diag;
+    int32_t every;                  /* steps per controller update, as NfmcTune.every: the call enqueues every (kernel,
+                                       controller) pair itself */
+} NfmcMclmcTune;
+/* nfmc_tune_state_doubles(d) + history_rows * NFMC_MCLMC_ROW_WORDS; 0 for arguments out of range */
+int64_t nfmc_mclmc_state_doubles(int32_t d, int32_t history_rows);
+
+typedef struct {
+    float* x;                    /* (n, d) in/out */
+    float* velocity;             /* (n, d) in/out: unit rows */
+    int64_t n;
+    int32_t d;                   /* 2 .. 1024 */
+    int32_t n_steps;             /* 1..NFMC_MAX_STEPS_PER_CALL */
+    float step_size;
+    float decoherence_length;
+    const float* inv_mass_diag;  /* (d,) or NULL = ones */
+    NfmcPotential pot;
+    NfmcRng rng;                 /* rounds 0 or 10; replay_normals as for the other samplers, no uniforms are drawn */
+    NfmcStats stats;             /* defer must be 0: the call folds its partials itself */
+    NfmcSampleStore samples;     /* state after every step */
+    float* energy_out;           /* NULL or (n_steps, n): dE of every step */
+    double* energy_sums;         /* NULL or 3 doubles, += sum of finite dE^2, sum of finite dE, count of finite steps; needs
+                                    `stats` (the sums travel through its per-workgroup partials, folded in a fixed order) */
+    NfmcMclmcTune tune;          /* warmup on the device; needs `stats` */
+} NfmcMclmcArgs;
+
+/* Status codes as nfmc_hmc_steps_f32; in addition d < 2 is NFMC_EINVAL and rng.rounds == 7 NFMC_EUNSUPPORTED. */
+int nfmc_mclmc_steps_f32(const NfmcMclmcArgs* args, nfmc_stream_t stream);
+
 /* K4: x -> z, logdet_forward; log_prob = N(z;0,I) + logdet (either output may be NULL).
  * Replaces `bijection.forward` / `Flow.log_prob` (jump.py:218, imh.py:214). */
 int nfmc_realnvp_forward_f32(const NfmcRealNVP* flow, const float* x, int64_t n, float* z, float* logdet,

@@ -41,7 +41,7 @@ UNIT_FLAGS = {'neutra_mfma.hip': ['-mllvm', '-amdgpu-promote-alloca-to-vector-li
 SLOW_FIRST = ['flow_b_kernels.hip', 'neutra_kernels_r64.hip', 'neutra_kernels_r32.hip', 'neutra_kernels_r16.hip',
               'imh_parallel_rqs.hip', 'imh_parallel.hip', 'fit_kernels.hip', 'neutra_mfma.hip', 'fit_mfma.hip',
               'sampler_particles_hmc.hip', 'sampler_particles_mala.hip', 'sampler_irt_hmc.hip', 'sampler_irt_mala.hip',
-              'sampler_lgm_hmc.hip', 'sampler_lgm_mala.hip']
+              'sampler_lgm_hmc.hip', 'sampler_lgm_mala.hip', 'sampler_hmc_j0.hip', 'sampler_diffusion_hmc.hip']
 
 
 def sources():

@@ -7,6 +7,7 @@
 
 #include "run_parts.hpp"
 #include "sampler_impl.hpp"
+#include "sampler_mclmc.hpp"
 
 namespace nfmc {
 
@@ -336,6 +337,137 @@ static int launch_hmc(const NfmcHmcArgs& a, const JumpDev& jd, Cfg c, int jhp, b
 }
 #undef NFMC_KIND_CASE
 
+#define NFMC_KIND_CASE(KIND, POT) \
+    case KIND: return launch_mclmc_kind<POT>(a, c, tiles, grid, st);
+static int launch_mclmc(const NfmcMclmcArgs& a, Cfg c, int64_t tiles, int grid, hipStream_t st) {
+    switch (a.pot.kind) { NFMC_FOR_OWN_UNIT_POT(NFMC_KIND_CASE) }
+    return launch_mclmc_j0(a, c, tiles, grid, st);
+}
+#undef NFMC_KIND_CASE
+
+// ------------------------------------------------------------------------------------------------
+// mclmc (sampler_mclmc.hpp).  The kernel leaves, per workgroup slab, the sums of x and x^2, the steps taken and not
+// taken, and in the two jump columns the fp64 sums of the finite dE^2 and dE.
+//
+// A call without tuning: the three energy columns of the call's slabs into energy_sums (+=), by one workgroup in a fixed
+// order, ahead of stats_finish_kernel, which zeroes the slabs.
+__global__ void __launch_bounds__(kBlock) mclmc_energy_fold_kernel(const double* __restrict__ scratch, int nblocks, int width,
+                                                                   double* __restrict__ energy_sums, unsigned long long attempted) {
+    __shared__ double red[3][kBlock];
+    double s[3] = {0.0, 0.0, 0.0};   // not taken, sum dE^2, sum dE
+    for (int b = threadIdx.x; b < nblocks; b += kBlock) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) s[k] += scratch[(size_t)b * width + (width - 3 + k)];
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) red[k][threadIdx.x] = s[k];
+    __syncthreads();
+    for (int off = kBlock / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + off];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        energy_sums[0] += red[1][0];
+        energy_sums[1] += red[2][0];
+        energy_sums[2] += (double)attempted - red[0][0];
+    }
+}
+
+// Warmup: statistics fold and the controller of NfmcMclmcTune in one launch of one workgroup, behind a tuning launch of
+// at most kTuneGrid slabs (or behind tune_fold_kernel's partial slabs), as tune_finish_kernel is for mala / hmc.  A thread
+// owns a column and adds its rows in row order.  imd: the call's inv_mass_diag (NULL = ones).
+__global__ void __launch_bounds__(kFinishBlock) mclmc_tune_finish_kernel(double* __restrict__ scratch, int nblocks, int dp, int d,
+                                                                         NfmcStats st, NfmcMclmcTune tn, const float* imd,
+                                                                         double* __restrict__ energy_sums,
+                                                                         unsigned long long attempted) {
+    __shared__ double red[kFinishBlock];
+    const int width = 2 * dp + kStatTail;
+    double* __restrict__ totals = tn.state + NFMC_MCLMC_WORDS;
+    for (int t = threadIdx.x; t < width; t += kFinishBlock) {
+        double s = 0.0;
+#pragma unroll 8
+        for (int b = 0; b < nblocks; ++b) {
+            s += scratch[(size_t)b * width + t];
+            scratch[(size_t)b * width + t] = 0.0;
+        }
+        totals[t] = s;
+    }
+    __syncthreads();   // totals[] written by this workgroup's own threads: workgroup scope is enough
+    const double n_tot = (double)attempted;
+    const double bad = totals[2 * dp + 1], se2 = totals[2 * dp + 2], se = totals[2 * dp + 3];
+    const double count = n_tot - bad;
+    const double V = count > 0.0 ? se2 / (count * (double)d) : 0.0;
+    const bool good = count > 0.0 && fabs(V) <= 1.7e308;
+    const bool tune_imd = good && tn.tune_inv_mass_diag && tn.inv_mass_diag && n_tot > 1.0;
+    const double beta = tn.state[NFMC_MCLMC_IMD_ADJUSTMENT];
+    double* __restrict__ shift = totals + width;
+    double ratio = 0.0;   // this thread's share of sum_j v_j / s_j
+    for (int j = threadIdx.x; j < d; j += kFinishBlock) {
+        const double c = shift[j], s1 = totals[j], s2 = totals[dp + j];
+        st.sum_x[j] += s1 + n_tot * c;
+        st.sum_x2[j] += s2 + c * (2.0 * s1 + n_tot * c);
+        double var = n_tot > 1.0 ? (s2 - s1 * s1 / n_tot) / (n_tot - 1.0) : 0.0;   // unbiased, about the lagged centre
+        var = var > 0.0 ? var : 0.0;
+        double sj = imd ? (double)imd[j] : 1.0;
+        if (tune_imd) {
+            const float next = (float)((1.0 - beta) * sj + beta * var);
+            tn.inv_mass_diag[j] = next;
+            sj = (double)next;   // what the next launch reads
+        }
+        ratio += var / sj;
+        if (n_tot > 0.0) shift[j] = (double)(float)(c + s1 / n_tot);
+    }
+    red[threadIdx.x] = ratio;
+    __syncthreads();
+    for (int off = kFinishBlock / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    st.counters[NFMC_CNT_ACCEPTED] += (unsigned long long)(totals[2 * dp] + 0.5);
+    st.counters[NFMC_CNT_ATTEMPTED] += attempted;
+    st.counters[NFMC_CNT_NONFINITE] += (unsigned long long)(bad + 0.5);
+    if (energy_sums) {
+        energy_sums[0] += se2;
+        energy_sums[1] += se;
+        energy_sums[2] += count;
+    }
+    const double eps_used = tn.state[NFMC_MCLMC_STEP_SIZE], len_used = tn.state[NFMC_MCLMC_DECOHERENCE_LENGTH];
+    double eps = eps_used, len = len_used;
+    if (!good) {
+        if (tn.tune_step_size) eps = 0.5 * eps_used;
+    } else {
+        if (tn.tune_step_size) {
+            const double ln2 = 0.6931471805599453;
+            double move = log(tn.state[NFMC_MCLMC_TARGET] / V) / 6.0;   // the local energy error is of third order in eps
+            move = move > ln2 ? ln2 : (move < -ln2 ? -ln2 : move);
+            eps = exp(log(eps_used) + move);
+        }
+        if (tn.tune_decoherence_length && n_tot > 1.0) {
+            const double next = tn.state[NFMC_MCLMC_DECOHERENCE_FACTOR] * sqrt(red[0]);
+            if (next > 0.0 && next <= 1.7e308) len = next;   // all variances zero: L stays
+        }
+    }
+    tn.state[NFMC_MCLMC_STEP_SIZE] = eps;
+    tn.state[NFMC_MCLMC_DECOHERENCE_LENGTH] = len;
+    tn.state[NFMC_MCLMC_ENERGY_VARIANCE] = V;
+    tn.state[NFMC_MCLMC_COUNT] = count;
+    const double used = tn.state[NFMC_MCLMC_HISTORY_USED];
+    if (used < tn.state[NFMC_MCLMC_HISTORY_ROWS]) {   // updates beyond the capacity overwrite nothing
+        double* __restrict__ row = shift + dp + (size_t)used * NFMC_MCLMC_ROW_WORDS;
+        row[NFMC_MCLMC_ROW_STEP_SIZE] = eps_used;
+        row[NFMC_MCLMC_ROW_DECOHERENCE_LENGTH] = len_used;
+        row[NFMC_MCLMC_ROW_ENERGY_VARIANCE] = V;
+        row[NFMC_MCLMC_ROW_COUNT] = count;
+        row[NFMC_MCLMC_ROW_NEXT_STEP_SIZE] = eps;
+        row[NFMC_MCLMC_ROW_NEXT_DECOHERENCE_LENGTH] = len;
+    }
+    tn.state[NFMC_MCLMC_HISTORY_USED] = used + 1.0;
+}
+
 static JumpDev jump_dev(const NfmcJumpTail* j) {
     JumpDev jd = {};
     if (j) {
@@ -457,6 +589,81 @@ extern "C" int nfmc_mala_steps_f32(const NfmcMalaArgs* args, nfmc_stream_t strea
 
 extern "C" int nfmc_hmc_steps_f32(const NfmcHmcArgs* args, nfmc_stream_t stream) {
     return hmc_steps(args, (hipStream_t)stream, nullptr);
+}
+
+extern "C" int64_t nfmc_mclmc_state_doubles(int32_t d, int32_t history_rows) {
+    if (d <= 0 || d > 1024 || history_rows < 0) return 0;
+    return nfmc_tune_state_doubles(d) + (int64_t)history_rows * NFMC_MCLMC_ROW_WORDS;
+}
+
+// The argument checks in the order of check_common, then the layout, tile and grid arithmetic of sampler_steps: one launch
+// and the folds, or the warmup loop of one launch + controller update per `every` steps, all of the call enqueued here.
+extern "C" int nfmc_mclmc_steps_f32(const NfmcMclmcArgs* args, nfmc_stream_t stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!args || !args->x || !args->velocity) return NFMC_EINVAL;
+    NfmcMclmcArgs a = *args;
+    if (a.n <= 0 || a.d <= 0 || a.n_steps <= 0 || a.d < 2) return NFMC_EINVAL;
+    if (a.n_steps > NFMC_MAX_STEPS_PER_CALL) return NFMC_ESHAPE;
+    if (a.d > 1024) return NFMC_ESHAPE;
+    if (!(a.step_size > 0.f) || !(a.decoherence_length > 0.f)) return NFMC_EINVAL;
+    if (int rc = check_potential(a.pot, a.d, PotFamily::kRegister)) return rc;
+    if ((((uintptr_t)a.x) & 3u) != 0 || (((uintptr_t)a.velocity) & 3u) != 0) return NFMC_EALIGN;
+    if (!store_ok(a.samples)) return NFMC_EINVAL;
+    if (int rc = rng_default_only(a.rng)) return rc;
+    if (a.stats.sum_x && (!a.stats.sum_x2 || !a.stats.counters || !a.stats.scratch)) return NFMC_EINVAL;
+    if (a.stats.defer) return NFMC_EINVAL;   // the energy columns are folded by the call itself
+    if ((a.energy_sums || a.tune.state) && !a.stats.sum_x) return NFMC_EINVAL;
+    if (a.tune.state && a.tune.tune_inv_mass_diag && (!a.tune.inv_mass_diag || a.tune.inv_mass_diag != a.inv_mass_diag))
+        return NFMC_EINVAL;
+    const Cfg c = choose_cfg(a.d, false, true);   // the default layouts: the only ones with mclmc kernels
+    if (!c.cpl) return NFMC_ESHAPE;
+    const int dp = c.cpl * c.lpc;
+    if (dp != padded_d(a.d)) return NFMC_EINVAL;
+    const int cpw = kWave / c.lpc;
+    const int64_t tiles = (a.n + (int64_t)kWavesPerBlock * cpw - 1) / ((int64_t)kWavesPerBlock * cpw);
+    bool two_level = false;
+    const int grid = a.tune.state ? tune_grid(tiles, dp, a.stats.scratch_bytes, &two_level) : (int)(tiles < kMaxGrid ? tiles : kMaxGrid);
+    const int width = 2 * dp + kStatTail;
+    if (a.stats.sum_x && a.stats.scratch_bytes < (int64_t)grid * width * (int64_t)sizeof(double)) return NFMC_ESCRATCH;
+    if (a.tune.state) {
+        const int every = (a.tune.every > 0 && a.tune.every < a.n_steps) ? a.tune.every : a.n_steps;
+        const int total = a.n_steps;
+        for (int s0 = 0; s0 < total; s0 += every) {
+            const int k = total - s0 < every ? total - s0 : every;
+            NfmcMclmcArgs b = a;
+            b.n_steps = k;
+            b.rng.step0 = a.rng.step0 + (uint32_t)s0;
+            if (a.rng.replay_normals) b.rng.replay_normals = a.rng.replay_normals + (int64_t)s0 * a.n * a.d;
+            if (a.energy_out) b.energy_out = a.energy_out + (int64_t)s0 * a.n;
+            if (int rc = launch_mclmc(b, c, tiles, grid, st)) return rc;
+            NFMC_HIP_CHECK_LAUNCH();
+            const unsigned long long attempted = (unsigned long long)a.n * (unsigned long long)k;
+            double* slabs = a.stats.scratch;
+            int nslabs = grid;
+            if (two_level) {
+                slabs = a.stats.scratch + (size_t)(kMaxGrid - kTuneFoldWgs) * width;
+                nslabs = (grid + kTuneFoldSlabs - 1) / kTuneFoldSlabs;
+                hipLaunchKernelGGL(tune_fold_kernel, dim3(nslabs), dim3(kFinishBlock), 0, st, a.stats.scratch, grid, width, slabs);
+            }
+            hipLaunchKernelGGL(mclmc_tune_finish_kernel, dim3(1), dim3(kFinishBlock), 0, st, slabs, nslabs, dp, a.d, a.stats,
+                               a.tune, a.inv_mass_diag, a.energy_sums, attempted);
+            NFMC_HIP_CHECK_LAUNCH();
+            store_advance(a.samples, k);
+        }
+        return NFMC_OK;
+    }
+    if (int rc = launch_mclmc(a, c, tiles, grid, st)) return rc;
+    NFMC_HIP_CHECK_LAUNCH();
+    if (a.stats.sum_x) {
+        const unsigned long long attempted = (unsigned long long)a.n * (unsigned long long)a.n_steps;
+        if (a.energy_sums)
+            hipLaunchKernelGGL(mclmc_energy_fold_kernel, dim3(1), dim3(kBlock), 0, st, a.stats.scratch, grid, width, a.energy_sums,
+                               attempted);
+        hipLaunchKernelGGL(stats_finish_kernel<true>, dim3(stats_finish_grid(dp)), dim3(kFinishBlock), 0, st, a.stats.scratch,
+                           grid, dp, a.d, a.stats, attempted, (unsigned long long*)nullptr, 0ull);
+        NFMC_HIP_CHECK_LAUNCH();
+    }
+    return NFMC_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -120,6 +120,29 @@ class NfmcHmcArgs(C.Structure):
                 ('tune', NfmcTune)]
 
 
+class NfmcMclmcTune(C.Structure):
+    _fields_ = [('state', c_fp), ('inv_mass_diag', c_fp), ('tune_step_size', C.c_int32),
+                ('tune_decoherence_length', C.c_int32), ('tune_inv_mass_diag', C.c_int32), ('every', C.c_int32)]
+
+
+class NfmcMclmcArgs(C.Structure):
+    _fields_ = [('x', c_fp), ('velocity', c_fp), ('n', C.c_int64), ('d', C.c_int32), ('n_steps', C.c_int32),
+                ('step_size', C.c_float), ('decoherence_length', C.c_float), ('inv_mass_diag', c_fp),
+                ('pot', NfmcPotential), ('rng', NfmcRng), ('stats', NfmcStats), ('samples', NfmcSampleStore),
+                ('energy_out', c_fp), ('energy_sums', c_fp), ('tune', NfmcMclmcTune)]
+
+
+# words of the mclmc tuning state and of its history rows (include/nfmc_hip.h: NFMC_MCLMC_*); the column totals and the
+# shift follow the words as in the mala / hmc tuning state (tune_shift_offset), the history follows the shift
+(MCLMC_STEP_SIZE, MCLMC_DECOHERENCE_LENGTH, MCLMC_TARGET, MCLMC_IMD_ADJUSTMENT, MCLMC_DECOHERENCE_FACTOR,
+ MCLMC_ENERGY_VARIANCE, MCLMC_COUNT, MCLMC_HISTORY_ROWS, MCLMC_HISTORY_USED) = range(9)
+MCLMC_WORDS = 12
+(MCLMC_ROW_STEP_SIZE, MCLMC_ROW_DECOHERENCE_LENGTH, MCLMC_ROW_ENERGY_VARIANCE, MCLMC_ROW_COUNT, MCLMC_ROW_NEXT_STEP_SIZE,
+ MCLMC_ROW_NEXT_DECOHERENCE_LENGTH) = range(6)
+MCLMC_ROW_WORDS = 6
+TAG_VELOCITY = 4   # Philox stream of the initial velocity of an mclmc run (nfmc_philox_normals_f32)
+
+
 class NfmcFlowMhArgs(C.Structure):
     _fields_ = [('x', c_fp), ('logq', c_fp), ('n', C.c_int64), ('n_steps', C.c_int32), ('logq_cached', C.c_int32),
                 ('adjusted', C.c_int32), ('reserved', C.c_int32), ('flow', NfmcRealNVP), ('pot', NfmcPotential),
@@ -242,6 +265,8 @@ SYMBOLS = [
     ('nfmc_sampler_layout', C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ('nfmc_mala_steps_f32', C.c_int, [C.POINTER(NfmcMalaArgs), c_fp]),
     ('nfmc_hmc_steps_f32', C.c_int, [C.POINTER(NfmcHmcArgs), c_fp]),
+    ('nfmc_mclmc_state_doubles', C.c_int64, [C.c_int32, C.c_int32]),
+    ('nfmc_mclmc_steps_f32', C.c_int, [C.POINTER(NfmcMclmcArgs), c_fp]),
     ('nfmc_realnvp_padded_hidden', C.c_int32, [C.c_int32]),
     ('nfmc_realnvp_layer_floats', C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     ('nfmc_coupling_layer_floats', C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),

@@ -1,7 +1,7 @@
 """Public entry points `sample()` / `create_sampler()` with the reference's signature and keyword
 plumbing (nfmc/sample.py:20-30, 243-314) for the strategies on this build's path:
 
-    mala, ula, hmc, uhmc, mh                              (inner samplers)
+    mala, ula, hmc, uhmc, mh, mclmc                       (inner samplers)
     imh / fixed_imh, jump_mala, jump_ula, jump_hmc, jump_uhmc, jump_mh, neutra_hmc, neutra_mh
 
     adaptive_imh, dlmc (needs `negative_log_likelihood`, like the reference)
@@ -19,8 +19,8 @@ from .potentials import Potential
 from .samplers.dlmc import DLMC, DLMCKernel, DLMCParameters
 from .samplers.imh import AdaptiveIMH, FixedIMH, IMHKernel, IMHParameters
 from .samplers.jump import JumpHMC, JumpMALA, JumpMH, JumpNFMCParameters, JumpUHMC, JumpULA
-from .samplers.mcmc import (HMC, MALA, MH, UHMC, ULA, HMCKernel, HMCParameters, LangevinKernel, LangevinParameters,
-                            MHKernel, MHParameters)
+from .samplers.mcmc import (HMC, MALA, MCLMC, MH, UHMC, ULA, HMCKernel, HMCParameters, LangevinKernel, LangevinParameters,
+                            MCLMCKernel, MCLMCParameters, MHKernel, MHParameters)
 from .samplers.neutra import NeuTraHMC, NeuTraKernel, NeuTraMH, NeuTraParameters
 from .util import create_flow_object, get_supported_samplers
 
@@ -63,6 +63,8 @@ def create_sampler(target: callable,
                    LangevinParameters(**param_kwargs))
     if strategy == "mh":
         return MH(event_shape, target, MHKernel(event_size=event_size, **kernel_kwargs), MHParameters(**param_kwargs))
+    if strategy == "mclmc":
+        return MCLMC(event_shape, target, MCLMCKernel(event_size=event_size, **kernel_kwargs), MCLMCParameters(**param_kwargs))
 
     if strategy == "dlmc" and negative_log_likelihood is None:
         raise ValueError("Unsupported sampling strategy: dlmc without a negative_log_likelihood "

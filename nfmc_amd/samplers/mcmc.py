@@ -702,3 +702,295 @@ class UHMC(HMC):
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
         self.params.adjustment = False
+
+
+# ------------------------------------------------------------------------------------------------ mclmc
+@dataclass
+class MCLMCKernel(MCMCKernel):
+    """Microcanonical Langevin Monte Carlo (Robnik and Seljak 2024): step size eps, decoherence length L and the
+    per-coordinate scales sigma_j = sqrt(inv_mass_diag_j)."""
+    event_size: int
+    step_size: Optional[float] = None            # default 0.25 sqrt(d)
+    decoherence_length: Optional[float] = None   # default sqrt(d)
+    inv_mass_diag: torch.Tensor = None
+    # (updates, hip.MCLMC_ROW_WORDS) fp64, one row per controller update of the last warmup: the eps and L it ran with, V,
+    # the count of finite steps, the eps and L it left
+    adaptation_history: Any = None
+    # V = sum of finite dE^2 / (count d): of the last controller update after a warmup, of the whole run after sampling --
+    # the bias diagnostic of an unadjusted run (the warmup steers it to MCLMCParameters.energy_variance_target)
+    energy_variance: Optional[float] = None
+
+    def __post_init__(self):
+        super().__post_init__()
+        d = int(self.event_size)
+        if d < 2:
+            raise ValueError('mclmc needs an event size of at least 2 (the velocity lives on the unit sphere of R^d), got %d' % d)
+        if self.step_size is None:
+            self.step_size = 0.25 * math.sqrt(d)
+        if self.decoherence_length is None:
+            self.decoherence_length = math.sqrt(d)
+        if self.inv_mass_diag is None:
+            self.inv_mass_diag = torch.ones(d)
+        else:
+            self.inv_mass_diag = torch.as_tensor(self.inv_mass_diag, dtype=torch.float32)
+            if tuple(self.inv_mass_diag.shape) != (d,):
+                raise ValueError('inv_mass_diag must have event_size = %d entries, got shape %s'
+                                 % (d, tuple(self.inv_mass_diag.shape)))
+
+    def __repr__(self):
+        return (f'log step: {math.log(self.step_size):.2f}, decoherence length: {self.decoherence_length:.3g}, '
+                f'mass norm: {torch.max(torch.abs(self.inv_mass_diag)):.2f}')
+
+
+@dataclass
+class MCLMCParameters(MCMCParameters):
+    tune_step_size: bool = True
+    tune_decoherence_length: bool = True
+    tune_inv_mass_diag: bool = False
+    imd_adjustment: float = 0.25
+    energy_variance_target: float = 5e-4    # blackjax's default
+    decoherence_factor: float = 1.0
+    tune_every: int = 8                     # steps per controller update, pooled over the chains
+
+
+def mclmc_kick(u, g, sigma, e, d):
+    """B(e) of the mclmc step on (n, d) tensors: the velocity after a kick of length e along -sigma g and the change dK
+    of the kinetic energy.  A zero force leaves u alone with dK = 0."""
+    gt = sigma * g
+    gn = gt.norm(dim=1)
+    still = gn == 0
+    safe = torch.where(still, torch.ones_like(gn), gn)
+    e_hat = -gt / safe[:, None]
+    ue = (u * e_hat).sum(1)
+    delta = e * gn / (d - 1)
+    zeta = torch.exp(-delta)
+    uu = e_hat * ((1 - zeta) * (1 + zeta + ue * (1 - zeta)))[:, None] + 2 * zeta[:, None] * u
+    un = uu / uu.norm(dim=1, keepdim=True)
+    dk = (d - 1) * (delta - math.log(2.0) + torch.log(1 + ue + (1 - ue) * zeta * zeta))
+    return torch.where(still[:, None], u, un), torch.where(still, torch.zeros_like(dk), dk)
+
+
+def mclmc_refresh(u, z, eps, length, d):
+    """O of the mclmc step: partial refreshment of the unit velocity with the normals z."""
+    nu = math.sqrt(math.expm1(2.0 * eps / length) / d)
+    w = u + nu * z
+    return w / w.norm(dim=1, keepdim=True)
+
+
+class MclmcTuning:
+    """eps, L, the scales and the controller's words in device memory for the length of a warmup (NfmcMclmcTune,
+    include/nfmc_hip.h): the controller runs behind every `tune_every` steps of a call and the next launch reads what it
+    wrote, so the warmup loop never waits for the GPU."""
+
+    def __init__(self, sampler, run, n_updates):
+        k, p, lib = sampler.kernel, sampler.params, hip.lib()
+        self.rows = int(n_updates)
+        self.history_offset = int(lib.nfmc_tune_state_doubles(run.d))
+        st = torch.zeros(int(lib.nfmc_mclmc_state_doubles(run.d, self.rows)), dtype=torch.float64)
+        st[hip.MCLMC_STEP_SIZE] = float(k.step_size)
+        st[hip.MCLMC_DECOHERENCE_LENGTH] = float(k.decoherence_length)
+        st[hip.MCLMC_TARGET] = float(p.energy_variance_target)
+        st[hip.MCLMC_IMD_ADJUSTMENT] = float(p.imd_adjustment)
+        st[hip.MCLMC_DECOHERENCE_FACTOR] = float(p.decoherence_factor)
+        st[hip.MCLMC_HISTORY_ROWS] = self.rows
+        c0 = hip.tune_shift_offset(run.d)
+        st[c0:c0 + run.d] = run.x.double().mean(0).float().double()
+        self.state = st.to(run.dev)
+        self.imd = k.inv_mass_diag.detach().to(run.dev, torch.float32).contiguous().clone()
+        self.flags = (int(bool(p.tune_step_size)), int(bool(p.tune_decoherence_length)), int(bool(p.tune_inv_mass_diag)))
+        self.every = max(1, int(p.tune_every))
+
+    def struct(self, n_steps):
+        every = self.every if self.every < n_steps else 0
+        return hip.NfmcMclmcTune(hip.ptr(self.state, torch.float64), hip.ptr(self.imd), *self.flags, every)
+
+    def download(self, kernel):
+        st = self.state.cpu()
+        used = min(self.rows, int(round(float(st[hip.MCLMC_HISTORY_USED]))))
+        o = self.history_offset
+        kernel.adaptation_history = st[o:o + used * hip.MCLMC_ROW_WORDS].reshape(used, hip.MCLMC_ROW_WORDS).clone()
+        if used:
+            kernel.step_size = float(st[hip.MCLMC_STEP_SIZE])
+            kernel.decoherence_length = float(st[hip.MCLMC_DECOHERENCE_LENGTH])
+            kernel.energy_variance = float(st[hip.MCLMC_ENERGY_VARIANCE])
+            if self.flags[2]:
+                kernel.inv_mass_diag = self.imd.cpu().to(kernel.inv_mass_diag.dtype)
+
+
+class MCLMC(MCMCSampler):
+    """Unadjusted microcanonical Langevin Monte Carlo.  A closed-form target runs nfmc_mclmc_steps_f32 (every step of a
+    launch in one HIP kernel, the warmup controller on the device); any other callable runs the same step from torch ops
+    on the device -- autograd gradient, the same Philox draws, the controller on the host (tuning.MicrocanonicalAdaptation):
+    slow but complete.  A step costs one gradient and one value; every launch evaluates both once more at its starting
+    state, which the call counters do not book."""
+
+    def __init__(self, event_shape, target, kernel: Optional[MCLMCKernel] = None,
+                 params: Optional[MCLMCParameters] = None):
+        if kernel is None:
+            kernel = MCLMCKernel(event_size=int(torch.prod(torch.as_tensor(event_shape))))
+        if params is None:
+            params = MCLMCParameters()
+        super().__init__(event_shape, target, kernel, params)
+        self._next_velocity = None
+
+    @property
+    def name(self):
+        return 'MCLMC'
+
+    def warmup(self, x0, show_progress: bool = True, time_limit_seconds=None) -> MCMCOutput:
+        with torch.no_grad():
+            warmup_copy = deepcopy(self)
+        warmup_copy.params.tuning_mode()
+        warmup_copy.params.n_iterations = self.params.n_warmup_iterations
+        out = warmup_copy.sample(x0, show_progress=show_progress, time_limit_seconds=time_limit_seconds)
+        self.kernel = warmup_copy.kernel
+        new_params = warmup_copy.params
+        new_params.n_iterations = self.params.n_iterations
+        self.params = new_params
+        self.params.sampling_mode()
+        self._next_velocity = warmup_copy._last_velocity   # handed to the sampling run
+        return out
+
+    def _velocity(self, run, step0):
+        """The run's unit velocities: those a warmup left, else normals of Philox stream 4 at the run's first step counter,
+        normalised here."""
+        u, self._next_velocity = self._next_velocity, None
+        if u is not None and tuple(u.shape) == (run.n, run.d) and u.device == run.dev:
+            return u.clone()
+        u = torch.empty(run.n, run.d, dtype=torch.float32, device=run.dev)
+        rng = hip.make_rng(run.seed, run.chain_offset, step0)
+        hip.check(hip.lib().nfmc_philox_normals_f32(C.byref(rng), hip.TAG_VELOCITY, run.n, run.d, hip.ptr(u), hip.stream()),
+                  'nfmc_philox_normals_f32')
+        return (u / u.norm(dim=1, keepdim=True)).contiguous()
+
+    def _launch_fused(self, run, pot, u, k, step0, store, esums, tune, energy_out=None):
+        a = hip.NfmcMclmcArgs()
+        a.x, a.velocity, a.n, a.d, a.n_steps = hip.ptr(run.x), hip.ptr(u), run.n, run.d, k
+        a.step_size, a.decoherence_length = float(self.kernel.step_size), float(self.kernel.decoherence_length)
+        imd = tune.imd if tune is not None else imd_tensor(self.kernel, run.dev)
+        a.inv_mass_diag = hip.ptr(imd)
+        a.pot = pot.descriptor(run.dev)
+        a.rng = run.rng(step0, k, adjusted=False)
+        a.stats = run.stats.struct()
+        a.samples = hip.store_struct(store, k)
+        a.energy_out = hip.ptr(energy_out) if energy_out is not None else None
+        a.energy_sums = hip.ptr(esums, torch.float64)
+        if tune is not None:
+            a.tune = tune.struct(k)
+        with run.timed('mclmc_steps'):
+            hip.check(hip.lib().nfmc_mclmc_steps_f32(C.byref(a), hip.stream()), 'nfmc_mclmc_steps_f32')
+
+    def _torch_step(self, run, u, step, store, esums, cache, ctl):
+        """One step from torch ops (targets with no closed form): returns the new velocity."""
+        k = self.kernel
+        n, d = run.n, run.d
+        eps = float(torch.tensor(float(k.step_size), dtype=torch.float32))   # the kernels integrate with the fp32 value
+        length = float(torch.tensor(float(k.decoherence_length), dtype=torch.float32))
+        sigma = k.inv_mass_diag.to(run.dev, torch.float32).sqrt()[None]
+        if 'g' not in cache:
+            cache['U'], cache['g'] = _value_and_grad(self.target, run.x, self.event_shape)
+        x, g, U = run.x, cache['g'], cache['U']
+        u1, dk1 = mclmc_kick(u, g, sigma, 0.5 * eps, d)
+        xn = x + eps * sigma * u1
+        Un, gn = _value_and_grad(self.target, xn, self.event_shape)
+        u2, dk2 = mclmc_kick(u1, gn, sigma, 0.5 * eps, d)
+        de = (Un - U) + dk1 + dk2
+        ok = torch.isfinite(de) & torch.isfinite(xn).all(1)
+        run.x = torch.where(ok[:, None], xn, x).contiguous()
+        cache['g'], cache['U'] = torch.where(ok[:, None], gn, g), torch.where(ok, Un, U)
+        z = torch.empty(n, d, dtype=torch.float32, device=run.dev)
+        rng = run.rng(step, 1, adjusted=False)
+        if run.replay is not None:
+            z = run._keep[0][0]
+        else:
+            hip.check(hip.lib().nfmc_philox_normals_f32(C.byref(rng), hip.TAG_NOISE, n, d, hip.ptr(z), hip.stream()),
+                      'nfmc_philox_normals_f32')
+        u = mclmc_refresh(torch.where(ok[:, None], u2, u), z, eps, length, d).contiguous()
+        dee = torch.where(ok, de, torch.zeros_like(de)).double()
+        esums += torch.stack([(dee * dee).sum(), dee.sum(), ok.sum().double()])
+        st = run.stats.struct()
+        hip.check(hip.lib().nfmc_moments_update_f32(hip.ptr(run.x), n, d, C.byref(st), hip.stream()), 'nfmc_moments_update_f32')
+        run.stats._counters[hip.CNT_NONFINITE] += (~ok).sum()
+        run.offer_state(store)
+        if ctl is not None:
+            ctl['e2'] += float((dee * dee).sum())
+            ctl['count'] += float(ok.sum())
+            ctl['states'].append(run.x.double())
+            if len(ctl['states']) == ctl['every']:
+                self._host_update(ctl)
+        return u
+
+    def _host_update(self, ctl):
+        states = torch.cat(ctl['states'], 0)
+        var = states.var(0, unbiased=True) if states.shape[0] > 1 else None
+        ad = ctl['adaptation']
+        ad.step(ctl['e2'], ctl['count'], var)
+        k = self.kernel
+        k.step_size, k.decoherence_length, k.energy_variance = ad.step_size, ad.decoherence_length, ad.energy_variance
+        if ad.tune_inv_mass_diag:
+            k.inv_mass_diag = ad.inv_mass_diag.clone()
+        ctl['e2'], ctl['count'], ctl['states'] = 0.0, 0.0, []
+
+    def sample(self, x0, show_progress: bool = True, time_limit_seconds=None) -> MCMCOutput:
+        from ..tuning import MicrocanonicalAdaptation
+        p, k = self.params, self.kernel
+        if p.tuning and not 1 <= int(p.tune_every) <= hip.MAX_STEPS_PER_CALL:
+            raise ValueError('tune_every must be in 1 .. %d, got %d' % (hip.MAX_STEPS_PER_CALL, int(p.tune_every)))
+        if not (float(k.step_size) > 0 and float(k.decoherence_length) > 0):
+            raise ValueError('mclmc: step_size and decoherence_length must be positive')
+        run = Run(self, x0)
+        if run.d < 2 or run.d != int(k.event_size):
+            raise ValueError('mclmc: the chains have event size %d, the kernel %d (at least 2)' % (run.d, int(k.event_size)))
+        if run.rounds == 7:
+            raise ValueError('mclmc: rng_rounds=7 runs the exact-fit kernels; mclmc runs in the general kernels on the '
+                             'Philox4x32-10 stream')
+        if p.tuning and run.shard is not None and run.shard.world > 1:
+            raise ValueError('mclmc: a sharded warmup is not supported (the controller pools the chains of one device); '
+                             'warm up on one device and shard the sampling run')
+        step0 = hip.WARMUP_STEP0 if p.tuning else 0
+        n, event_shape = run.n, run.event_shape
+        out = MCMCOutput(event_shape, kernel=k, store_samples=p.store_samples, max_samples=getattr(p, 'max_samples', None))
+        out.statistics.data_transform = self.data_transform
+        K = int(p.n_iterations)
+        pot = resolve_target(self.target, event_shape, self.fuse, run.x, family='mcmc')
+        store = run.sample_store(K)
+        run.stats.zero_()
+        t0 = time.time()
+        bar = progress(show_progress, total=K, desc=f'{self.name} (tuning)' if p.tuning else self.name)
+        u = self._velocity(run, step0)
+        esums = torch.zeros(3, dtype=torch.float64, device=run.dev)
+        tune, ctl, cache = None, None, {}
+        if pot is not None:
+            limit = launch_limit(32, show_progress, time_limit_seconds)
+            if p.tuning:
+                every = max(1, int(p.tune_every))
+                tune = MclmcTuning(self, run, -(-K // every) + 1)
+                limit = launch_limit(max(32, every), show_progress, time_limit_seconds)
+                limit -= limit % every   # calls of whole pools
+        else:
+            limit = 1
+            if p.tuning:
+                ctl = {'every': max(1, int(p.tune_every)), 'e2': 0.0, 'count': 0.0, 'states': [],
+                       'adaptation': MicrocanonicalAdaptation(
+                           k.step_size, k.decoherence_length, k.inv_mass_diag, run.d, p.energy_variance_target,
+                           p.imd_adjustment, p.decoherence_factor, p.tune_step_size, p.tune_decoherence_length,
+                           p.tune_inv_mass_diag)}
+        for done, kk in run.launches(K, limit, t0, time_limit_seconds, bar):
+            if pot is not None:
+                self._launch_fused(run, pot, u, kk, step0 + done, store, esums, tune)
+            else:
+                u = self._torch_step(run, u, step0 + done, store, esums, cache, ctl)
+        if ctl is not None:
+            if ctl['states']:
+                self._host_update(ctl)   # the steps left over the last whole pool
+            k.adaptation_history = torch.tensor(ctl['adaptation'].history, dtype=torch.float64).reshape(-1, hip.MCLMC_ROW_WORDS)
+        run.finish(out, t0, n * run.done, store, n_target_calls=n * run.done, n_target_gradient_calls=n * run.done,
+                   n_accepted_trajectories=n * run.done, n_attempted_trajectories=n * run.done, n_divergences=0)
+        if tune is not None:
+            tune.download(k)
+        elif not p.tuning:
+            s2, _, cnt = (float(v) for v in esums.cpu())
+            k.energy_variance = s2 / (cnt * run.d) if cnt > 0 else math.nan
+        self._last_velocity = u
+        self._cur_run = None
+        return out

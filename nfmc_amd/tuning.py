@@ -117,6 +117,59 @@ class TrajectoryAdaptation:
         return 'TrajectoryAdaptation(T=%.4g, averaged=%.4g, updates=%d)' % (self.value, self.averaged, self.count)
 
 
+class MicrocanonicalAdaptation:
+    """The warmup controller of the mclmc sampler, driven by `step(energy_sq_sum, count, variance)` once per update over
+    the update's pooled steps (count of them with a finite energy error dE, energy_sq_sum the sum of their dE^2):
+      V = energy_sq_sum / (count d)
+      count = 0 or V not finite:   eps <- eps / 2, nothing else moves
+      else   log eps <- log eps + clamp(log(target / V) / 6, -ln 2, ln 2)      (the local error is of third order in eps)
+             s_j <- (1 - beta) s_j + beta v_j                                   (tune_inv_mass_diag; rounded to fp32)
+             L <- factor sqrt(sum_j v_j / s_j), s_j after its own update         (tune_decoherence_length)
+    v_j (`variance`, fp64): the unbiased variance of coordinate j over the update's states; None where there is one state
+    or less, which leaves s and L alone.  `history` holds one row per update: the eps and L it ran with, V, count, the eps
+    and L it left.  The controller on the device (mclmc_tune_finish_kernel, csrc/sampler_kernels.hip) is this recurrence
+    on fp64 words."""
+
+    def __init__(self, step_size, decoherence_length, inv_mass_diag, event_size, target=5e-4, imd_adjustment=0.25,
+                 decoherence_factor=1.0, tune_step_size=True, tune_decoherence_length=True, tune_inv_mass_diag=False):
+        self.step_size = float(step_size)
+        self.decoherence_length = float(decoherence_length)
+        self.inv_mass_diag = torch.as_tensor(inv_mass_diag, dtype=torch.float32).detach().cpu().clone()
+        self.event_size = int(event_size)
+        self.target, self.imd_adjustment, self.decoherence_factor = float(target), float(imd_adjustment), float(decoherence_factor)
+        self.tune_step_size, self.tune_decoherence_length = bool(tune_step_size), bool(tune_decoherence_length)
+        self.tune_inv_mass_diag = bool(tune_inv_mass_diag)
+        self.energy_variance = None
+        self.history = []
+
+    def step(self, energy_sq_sum, count, variance=None):
+        eps0, len0 = self.step_size, self.decoherence_length
+        count = float(count)
+        V = float(energy_sq_sum) / (count * self.event_size) if count > 0 else 0.0
+        if not (count > 0 and math.isfinite(V)):
+            if self.tune_step_size:
+                self.step_size = 0.5 * eps0
+        else:
+            if self.tune_step_size:
+                move = math.log(self.target / V) / 6.0 if V > 0 else math.inf
+                self.step_size = math.exp(math.log(eps0) + max(-math.log(2.0), min(math.log(2.0), move)))
+            if variance is not None:
+                var = torch.as_tensor(variance, dtype=torch.float64).cpu().clamp(min=0.0)
+                if self.tune_inv_mass_diag:
+                    b = self.imd_adjustment
+                    self.inv_mass_diag = ((1.0 - b) * self.inv_mass_diag.double() + b * var).float()
+                if self.tune_decoherence_length:
+                    nxt = self.decoherence_factor * math.sqrt(float((var / self.inv_mass_diag.double()).sum()))
+                    if nxt > 0 and math.isfinite(nxt):
+                        self.decoherence_length = nxt
+        self.energy_variance = V
+        self.history.append([eps0, len0, V, count, self.step_size, self.decoherence_length])
+
+    def __repr__(self):
+        return 'MicrocanonicalAdaptation(eps=%.4g, L=%.4g, updates=%d)' % (self.step_size, self.decoherence_length,
+                                                                           len(self.history))
+
+
 def _shuffled(rows: torch.Tensor) -> torch.Tensor:
     return rows[torch.randperm(rows.shape[0], device=rows.device)]
 

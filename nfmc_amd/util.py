@@ -55,7 +55,7 @@ def metropolis_acceptance_log_ratio(log_prob_target_curr, log_prob_target_prime,
 
 
 def get_supported_mcmc_samplers() -> List[str]:
-    return ['hmc', 'uhmc', 'ula', 'mala', 'mh']
+    return ['hmc', 'uhmc', 'ula', 'mala', 'mh', 'mclmc']
 
 
 def get_supported_nfmc_samplers() -> List[str]:

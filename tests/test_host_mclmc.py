@@ -1,0 +1,228 @@
+"""CPU: the surface of the mclmc sampler (nfmc_mclmc_steps_f32): the header's struct against the ctypes mirror, the
+controller recurrence (tuning.MicrocanonicalAdaptation) against hand-computed updates, two properties of the fp64 step of
+tests/mclmc_fp64.py, and the plumbing of create_sampler.  tests/test_gpu_mclmc.py runs the kernels."""
+import ctypes as C
+import math
+import os
+import re
+import subprocess
+
+import pytest
+import torch
+
+import mclmc_fp64 as M
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, 'include', 'nfmc_hip.h')
+FIELDS = ['x', 'velocity', 'n', 'd', 'n_steps', 'step_size', 'decoherence_length', 'inv_mass_diag', 'pot', 'rng', 'stats',
+          'samples', 'energy_out', 'energy_sums', 'tune']
+TUNE_FIELDS = ['state', 'inv_mass_diag', 'tune_step_size', 'tune_decoherence_length', 'tune_inv_mass_diag', 'every']
+LN2 = math.log(2.0)
+
+
+def test_the_header_declares_the_symbol_once_and_the_table_names_it():
+    from nfmc_amd import hip
+    header = open(HEADER).read()
+    assert len(re.findall(r'\bnfmc_mclmc_steps_f32\s*\(', header)) == 1
+    assert re.search(r'int\s+nfmc_mclmc_steps_f32\(const NfmcMclmcArgs\*\s*args,\s*nfmc_stream_t\s+stream\);', header)
+    rows = [s for s in hip.SYMBOLS if s[0] == 'nfmc_mclmc_steps_f32']
+    assert len(rows) == 1
+    assert rows[0][1] is C.c_int and rows[0][2][0]._type_ is hip.NfmcMclmcArgs and len(rows[0][2]) == 2
+    assert hasattr(hip.lib(), 'nfmc_mclmc_steps_f32')
+    assert hip.NFMC_ABI_VERSION == 4 == hip.limits().abi_version
+    assert re.search(r'#define NFMC_ABI_VERSION 4\b', header)
+
+
+@pytest.mark.parametrize('name,fields', [('NfmcMclmcArgs', FIELDS), ('NfmcMclmcTune', TUNE_FIELDS)])
+def test_the_ctypes_structs_have_the_c_structs_size_and_field_order(tmp_path, name, fields):
+    from nfmc_amd import hip
+    cls = getattr(hip, name)
+    assert [f[0] for f in cls._fields_] == fields
+    src = '#include <stdio.h>\n#include <stddef.h>\n#include "nfmc_hip.h"\nint main(){printf("%%zu\\n", sizeof(%s));' % name \
+        + ''.join('printf("%%zu\\n", offsetof(%s, %s));' % (name, f) for f in fields) + 'return 0;}'
+    c = tmp_path / 's.c'
+    c.write_text(src)
+    exe = str(tmp_path / 's')
+    subprocess.check_call(['gcc', '-I', os.path.join(ROOT, 'include'), str(c), '-o', exe])
+    got = [int(v) for v in subprocess.check_output([exe]).split()]
+    assert got[0] == C.sizeof(cls)
+    assert got[1:] == [getattr(cls, f).offset for f in fields]
+    body = re.search(r'typedef struct \{([^}]*)\} %s;' % name, open(HEADER).read()).group(1)
+    body = re.sub(r'/\*.*?\*/', '', body, flags=re.S)
+    assert re.findall(r'(\w+);', body) == fields
+
+
+def test_the_state_words_mirror_the_header():
+    from nfmc_amd import hip
+    header = open(HEADER).read()
+    for name in ('STEP_SIZE', 'DECOHERENCE_LENGTH', 'TARGET', 'IMD_ADJUSTMENT', 'DECOHERENCE_FACTOR', 'ENERGY_VARIANCE', 'COUNT',
+                 'HISTORY_ROWS', 'HISTORY_USED', 'WORDS', 'ROW_STEP_SIZE', 'ROW_DECOHERENCE_LENGTH', 'ROW_ENERGY_VARIANCE',
+                 'ROW_COUNT', 'ROW_NEXT_STEP_SIZE', 'ROW_NEXT_DECOHERENCE_LENGTH', 'ROW_WORDS'):
+        m = re.search(r'NFMC_MCLMC_%s = (\d+)' % name, header)
+        assert m and int(m.group(1)) == getattr(hip, 'MCLMC_' + name), name
+    assert hip.MCLMC_WORDS == hip.TUNE_WORDS   # StatShift finds the shift words where the mala / hmc state keeps them
+    lib = hip.lib()
+    assert lib.nfmc_mclmc_state_doubles(10, 3) == lib.nfmc_tune_state_doubles(10) + 3 * hip.MCLMC_ROW_WORDS
+    assert lib.nfmc_mclmc_state_doubles(0, 3) == 0 and lib.nfmc_mclmc_state_doubles(10, -1) == 0
+
+
+# ---- the controller, against updates computed by hand
+def test_an_update_moves_log_eps_by_a_sixth_of_the_log_error_ratio():
+    from nfmc_amd.tuning import MicrocanonicalAdaptation
+    d, count = 4, 100.0
+    c = MicrocanonicalAdaptation(0.5, 2.0, torch.ones(d), d, target=5e-4)
+    V = 1e-3                                        # twice the target: eps shrinks by 2^(1/6)
+    c.step(V * count * d, count, None)
+    assert c.step_size == pytest.approx(0.5 * 2.0 ** (-1.0 / 6.0), rel=1e-14)
+    assert c.decoherence_length == 2.0 and c.energy_variance == pytest.approx(V, rel=1e-14)
+    assert c.history == [[0.5, 2.0, c.energy_variance, count, c.step_size, 2.0]]
+
+
+@pytest.mark.parametrize('V,factor', [(5e-4 * 1e9, 0.5), (5e-4 * 1e-9, 2.0), (0.0, 2.0)])
+def test_both_clamps(V, factor):
+    from nfmc_amd.tuning import MicrocanonicalAdaptation
+    c = MicrocanonicalAdaptation(0.3, 1.0, torch.ones(3), 3)
+    c.step(V * 30.0, 10.0, None)
+    assert c.step_size == pytest.approx(0.3 * factor, rel=1e-14)
+
+
+@pytest.mark.parametrize('e2,count', [(1.0, 0.0), (math.inf, 5.0), (math.nan, 5.0)])
+def test_an_update_without_finite_steps_halves_eps_and_moves_nothing_else(e2, count):
+    from nfmc_amd.tuning import MicrocanonicalAdaptation
+    s = torch.tensor([1.0, 2.0, 3.0])
+    c = MicrocanonicalAdaptation(0.3, 1.5, s, 3, tune_inv_mass_diag=True)
+    c.step(e2, count, torch.tensor([9.0, 9.0, 9.0], dtype=torch.float64))
+    assert c.step_size == 0.15 and c.decoherence_length == 1.5 and torch.equal(c.inv_mass_diag, s)
+
+
+def test_the_scales_and_the_length_follow_the_variance():
+    from nfmc_amd.tuning import MicrocanonicalAdaptation
+    d = 3
+    s0, v = torch.tensor([1.0, 2.0, 4.0]), torch.tensor([4.0, 2.0, 1.0], dtype=torch.float64)
+    c = MicrocanonicalAdaptation(0.3, 1.5, s0, d, imd_adjustment=0.25, decoherence_factor=2.0, tune_inv_mass_diag=True)
+    c.step(5e-4 * 10 * d, 10.0, v)                  # V on target: eps stays
+    s1 = torch.tensor([0.75 * 1 + 0.25 * 4, 0.75 * 2 + 0.25 * 2, 0.75 * 4 + 0.25 * 1])
+    assert c.step_size == pytest.approx(0.3, rel=1e-14)
+    assert torch.allclose(c.inv_mass_diag, s1, rtol=0, atol=1e-7)
+    assert c.decoherence_length == pytest.approx(2.0 * math.sqrt(4 / 1.75 + 2 / 2.0 + 1 / 3.25), rel=1e-7)
+    # the tuners off: with the scales held, L takes them as they are; with L held, nothing but eps moves
+    c = MicrocanonicalAdaptation(0.3, 1.5, s0, d, tune_inv_mass_diag=False)
+    c.step(5e-4 * 10 * d, 10.0, v)
+    assert torch.equal(c.inv_mass_diag, s0) and c.decoherence_length == pytest.approx(math.sqrt(4 + 1 + 0.25), rel=1e-12)
+    c = MicrocanonicalAdaptation(0.3, 1.5, s0, d, tune_decoherence_length=False, tune_step_size=False)
+    c.step(1.0, 10.0, v)
+    assert (c.step_size, c.decoherence_length) == (0.3, 1.5)
+
+
+# ---- the fp64 step
+def _gauss_inputs(n, d, seed):
+    g = torch.Generator().manual_seed(seed)
+    x0 = torch.randn(n, d, generator=g, dtype=torch.float64)
+    return x0, M.initial_velocity(n, d, seed, 0)
+
+
+def test_the_fp64_step_conserves_the_unit_velocity():
+    x0, u0 = _gauss_inputs(32, 7, 3)
+    assert torch.allclose(u0.norm(dim=1), torch.ones(32, dtype=torch.float64), atol=1e-14)
+    imd = torch.linspace(0.5, 2.0, 7)
+    _, us, _, ok = M.steps(M.quadratic(torch.linspace(0.3, 2.0, 7), 0.1), x0, u0, 0.4, 2.0, imd, 3, 0, 16)
+    assert ok.all()
+    assert torch.allclose(us.norm(dim=2), torch.ones(16, 32, dtype=torch.float64), atol=1e-13)
+
+
+def test_the_fp64_energy_error_is_of_third_order_in_eps():
+    """dE of one step on a standard Gaussian between eps and eps / 2: the root mean square falls by 2^3."""
+    n, d = 4096, 16
+    x0, u0 = _gauss_inputs(n, d, 5)
+    target = M.quadratic(0.5, 0.0)
+    rms = []
+    for eps in (0.25, 0.125):
+        de = M.steps(target, x0, u0, eps, 1e6, None, 5, 0, 1)[2]
+        rms.append(float((de ** 2).mean().sqrt()))
+    assert 6.0 <= rms[0] / rms[1] <= 10.0, rms
+
+
+def test_a_zero_force_leaves_the_velocity_and_the_kinetic_energy_alone():
+    u = M.initial_velocity(4, 5, 1, 0)
+    un, dk = M.kick(u, torch.zeros(4, 5, dtype=torch.float64), torch.ones(1, 5, dtype=torch.float64), 0.3, 5)
+    assert torch.equal(un, u) and torch.equal(dk, torch.zeros(4, dtype=torch.float64))
+
+
+def test_the_package_step_is_the_reference_step():
+    """samplers.mcmc.mclmc_kick (the torch path of targets with no closed form) against the restatement here, in fp64"""
+    from nfmc_amd.samplers.mcmc import mclmc_kick
+    x0, u0 = _gauss_inputs(16, 6, 9)
+    sigma = torch.linspace(0.5, 1.5, 6, dtype=torch.float64)[None]
+    a, b = mclmc_kick(u0, x0, sigma, 0.2, 6), M.kick(u0, x0, sigma, 0.2, 6)
+    assert torch.allclose(a[0], b[0], atol=1e-14) and torch.allclose(a[1], b[1], atol=1e-13)
+
+
+# ---- plumbing
+def test_create_sampler_builds_an_mclmc_sampler_with_the_documented_defaults():
+    from nfmc_amd import create_sampler
+    from nfmc_amd.potentials import SumOfSquares
+    from nfmc_amd.samplers.mcmc import MCLMC, MCLMCKernel, MCLMCParameters
+    s = create_sampler(SumOfSquares((16,)), strategy='mclmc', flow=None, param_kwargs={'n_iterations': 7, 'tune_every': 4},
+                       kernel_kwargs={'decoherence_length': 3.0})
+    assert isinstance(s, MCLMC) and isinstance(s.kernel, MCLMCKernel) and isinstance(s.params, MCLMCParameters)
+    assert s.kernel.step_size == pytest.approx(0.25 * 4.0) and s.kernel.decoherence_length == 3.0
+    assert torch.equal(s.kernel.inv_mass_diag, torch.ones(16))
+    p = MCLMCParameters()
+    assert (p.tune_step_size, p.tune_decoherence_length, p.tune_inv_mass_diag) == (True, True, False)
+    assert (p.imd_adjustment, p.energy_variance_target, p.decoherence_factor, p.tune_every) == (0.25, 5e-4, 1.0, 8)
+    assert MCLMCKernel(event_size=9).decoherence_length == pytest.approx(3.0)
+    assert 'log step' in repr(s.kernel)
+
+
+def test_an_event_size_of_one_is_a_value_error():
+    from nfmc_amd import create_sampler
+    from nfmc_amd.potentials import SumOfSquares
+    with pytest.raises(ValueError, match='at least 2'):
+        create_sampler(SumOfSquares((1,)), strategy='mclmc', flow=None)
+
+
+def test_mclmc_is_a_supported_strategy_and_the_others_stay_out():
+    from nfmc_amd import create_sampler
+    from nfmc_amd.potentials import SumOfSquares
+    from nfmc_amd.util import get_supported_mcmc_samplers, get_supported_samplers
+    assert 'mclmc' in get_supported_samplers() and 'mclmc' in get_supported_mcmc_samplers()
+    for strategy in ('ess', 'jump_ess', 'tess', 'nuts'):
+        with pytest.raises(ValueError, match='Unsupported sampling strategy'):
+            create_sampler(SumOfSquares((4,)), strategy=strategy, flow=None)
+
+
+def test_the_entry_point_refuses_with_the_codes_of_the_hmc_entry_point():
+    """Every refusal is decided before the first launch, from host values alone: no device is needed to ask."""
+    from nfmc_amd import hip
+
+    def rc(**kw):
+        a = hip.NfmcMclmcArgs()
+        a.x, a.velocity, a.n, a.d, a.n_steps, a.step_size, a.decoherence_length = 4096, 8192, 8, 4, 2, 0.1, 2.0
+        a.pot = hip.NfmcPotential(hip.POT_QUADRATIC, 0, None, None, 1.0, 0.0)
+        a.rng = hip.make_rng(1, 0, 0)
+        a.stats = hip.null_stats()
+        a.samples = hip.dense_store(None)
+        for k, v in kw.items():
+            obj, name = a, k
+            while '.' in name:
+                head, name = name.split('.', 1)
+                obj = getattr(obj, head)
+            setattr(obj, name, v)
+        return hip.lib().nfmc_mclmc_steps_f32(C.byref(a), None)
+
+    assert hip.lib().nfmc_mclmc_steps_f32(None, None) == hip.EINVAL
+    assert rc(x=None) == hip.EINVAL and rc(velocity=None) == hip.EINVAL
+    assert rc(d=1) == hip.EINVAL and rc(d=0) == hip.EINVAL and rc(n=0) == hip.EINVAL and rc(n_steps=0) == hip.EINVAL
+    assert rc(n_steps=hip.MAX_STEPS_PER_CALL + 1) == hip.ESHAPE and rc(d=1025) == hip.ESHAPE
+    assert rc(step_size=0.0) == hip.EINVAL and rc(decoherence_length=0.0) == hip.EINVAL
+    assert rc(**{'pot.kind': 99}) == hip.EUNSUPPORTED
+    assert rc(x=4098) == hip.EALIGN and rc(velocity=8194) == hip.EALIGN
+    assert rc(**{'rng.rounds': 7}) == hip.EUNSUPPORTED and rc(**{'rng.rounds': 3}) == hip.EINVAL
+    assert rc(**{'samples.base': 4096, 'samples.stride': 0}) == hip.EINVAL
+    assert rc(**{'stats.sum_x': 4096}) == hip.EINVAL                      # statistics without their other buffers
+    assert rc(energy_sums=4096) == hip.EINVAL                             # the energy sums travel through the statistics
+    assert rc(**{'tune.state': 4096}) == hip.EINVAL
+    full = {'stats.sum_x': 4096, 'stats.sum_x2': 4096, 'stats.counters': 4096, 'stats.scratch': 4096}
+    assert rc(**full, **{'stats.defer': 1, 'stats.scratch_bytes': 1 << 30}) == hip.EINVAL
+    assert rc(**full, **{'stats.scratch_bytes': 8}) == hip.ESCRATCH
+    assert rc(**full, **{'stats.scratch_bytes': 1 << 30, 'tune.state': 4096, 'tune.tune_inv_mass_diag': 1}) == hip.EINVAL
