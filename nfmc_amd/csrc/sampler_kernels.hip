@@ -35,6 +35,7 @@ static Cfg choose_cfg(int d, bool with_jump, bool default_only) {
 
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
+// the argument checks of every sampler entry point (mala, hmc, mclmc); each adds its own behind them
 template <class Args>
 static int check_common(const Args* a) {
     if (!a || !a->x) return NFMC_EINVAL;
@@ -45,9 +46,15 @@ static int check_common(const Args* a) {
     if (int rc = check_potential(a->pot, a->d, PotFamily::kRegister)) return rc;
     if (((uintptr_t)a->x & 3u) != 0) return NFMC_EALIGN;
     if (!store_ok(a->samples)) return NFMC_EINVAL;
+    if (a->stats.sum_x && (!a->stats.sum_x2 || !a->stats.counters || !a->stats.scratch)) return NFMC_EINVAL;
+    return NFMC_OK;
+}
+
+template <class Args>   // mala, hmc
+static int check_metropolis(const Args* a) {
+    if (int rc = check_common(a)) return rc;
     if (!rng_rounds_ok(a->rng, true)) return NFMC_EINVAL;
     if ((a->rng.replay_normals == nullptr) != (a->rng.replay_uniforms == nullptr) && (a->adjust & 1)) return NFMC_EINVAL;
-    if (a->stats.sum_x && (!a->stats.sum_x2 || !a->stats.counters || !a->stats.scratch)) return NFMC_EINVAL;
     if (a->jump) {
         const NfmcJumpTail& j = *a->jump;
         if (j.flow.d != a->d || !j.counters) return NFMC_EINVAL;
@@ -285,29 +292,25 @@ static int tune_grid(int64_t tiles, int dp, int64_t scratch_bytes, bool* two_lev
     return (int)(tiles < cap ? tiles : cap);
 }
 
-// the fold + controller of one update behind a tuning launch of `grid` workgroups
-static void tune_update(const NfmcStats& stats, const NfmcTune& tune, int grid, bool two_level, int dp, int d, unsigned long long attempted,
-                        uint32_t step0, int pool, hipStream_t st) {
-    const int width = 2 * dp + kStatTail;
-    if (two_level) {
-        double* partial = stats.scratch + (size_t)(kMaxGrid - kTuneFoldWgs) * width;
-        const int wgs = (grid + kTuneFoldSlabs - 1) / kTuneFoldSlabs;
-        hipLaunchKernelGGL(tune_fold_kernel, dim3(wgs), dim3(kFinishBlock), 0, st, stats.scratch, grid, width, partial);
-        hipLaunchKernelGGL(tune_finish_kernel<1>, dim3(1), dim3(kFinishBlock), 0, st, partial, wgs, dp, d, stats, tune, attempted, step0, pool);
-    } else {
-        hipLaunchKernelGGL(tune_finish_kernel<1>, dim3(1), dim3(kFinishBlock), 0, st, stats.scratch, grid, dp, d, stats, tune, attempted, step0, pool);
-    }
+// The slabs a controller kernel is to finish behind a tuning launch of `grid` workgroups, *count of them: the launch's own,
+// or, behind a two-level launch, the partial slabs that tune_fold_kernel, enqueued here, folds them into
+static double* tune_fold(double* scratch, int grid, bool two_level, int width, hipStream_t st, int* count) {
+    *count = two_level ? (grid + kTuneFoldSlabs - 1) / kTuneFoldSlabs : grid;
+    if (!two_level) return scratch;
+    double* partial = scratch + (size_t)(kMaxGrid - kTuneFoldWgs) * width;
+    hipLaunchKernelGGL(tune_fold_kernel, dim3(*count), dim3(kFinishBlock), 0, st, scratch, grid, width, partial);
+    return partial;
 }
 
 template <class Args>
-static int check_tune(const Args& a, int dp, bool hmc) {
+static int check_tune(const Args& a, const NfmcJumpTail* jump, int dp, bool hmc) {
     // the jittered trajectory: the hmc kernel with a tuning state, a trajectory block behind it and the Metropolis test
     if (a.tune.trajectory != NFMC_TRAJECTORY_OFF) {
         if (!hmc || !a.tune.state || !(a.adjust & 1)) return NFMC_EINVAL;
         if (a.tune.trajectory != NFMC_TRAJECTORY_ADAPT && a.tune.trajectory != NFMC_TRAJECTORY_FROZEN) return NFMC_EINVAL;
     }
     if (!a.tune.state) return NFMC_OK;
-    if (!a.stats.sum_x || a.stats.defer || a.jump) return NFMC_EINVAL;   // the controller rides on the per-call fold
+    if (!a.stats.sum_x || a.stats.defer || jump) return NFMC_EINVAL;   // the controller rides on the per-call fold
     if (a.tune.tune_inv_mass_diag && (!a.tune.inv_mass_diag || a.tune.inv_mass_diag != a.inv_mass_diag)) return NFMC_EINVAL;
     // the state holds 2 * padded_d(d) + kStatTail column totals and padded_d(d) shift words (nfmc_tune_state_doubles):
     // a layout override of a larger capacity would not fit them
@@ -512,15 +515,58 @@ extern "C" int nfmc_sampler_layout(int32_t d, int32_t pot_kind_id, int32_t* cpl,
     return NFMC_OK;
 }
 
-// The part the two sampler entry points share, behind their own argument checks: layout, tile and grid arithmetic, the
+// What differs between the samplers behind sampler_steps, beside the launch.  mala and hmc:
+template <class Args>
+struct MetropolisParts {
+    static constexpr bool kJumpTail = true, kDefaultCfgOnly = false;
+    static const NfmcJumpTail* take_jump(Args& a) {   // a host pointer: never dereferenced on the device
+        const NfmcJumpTail* jump = a.jump;
+        a.jump = nullptr;
+        return jump;
+    }
+    static int check(const Args& a, const NfmcJumpTail* jump, int dp) {
+        return check_tune(a, jump, dp, std::is_same<Args, NfmcHmcArgs>::value);
+    }
+    // the per-step outputs of the pool that starts `off` chain-steps into the call (the driver moves the replay normals)
+    static void advance(Args& b, const Args& a, int64_t off) {
+        if (a.rng.replay_uniforms) b.rng.replay_uniforms = a.rng.replay_uniforms + off;
+        if (a.masks_out) b.masks_out = a.masks_out + off;
+        if (a.log_ratio_out) b.log_ratio_out = a.log_ratio_out + off;
+    }
+    // the controller behind a pool, over the slabs tune_fold left
+    static void update(const Args& a, double* slabs, int count, int dp, unsigned long long attempted, uint32_t step0, int pool, hipStream_t st) {
+        hipLaunchKernelGGL(tune_finish_kernel<1>, dim3(1), dim3(kFinishBlock), 0, st, slabs, count, dp, a.d, a.stats, a.tune, attempted, step0, pool);
+    }
+    static void fold(const Args&, int, int, unsigned long long, hipStream_t) {}   // ahead of stats_finish_kernel, without tuning
+};
+
+struct MclmcParts {
+    static constexpr bool kJumpTail = false, kDefaultCfgOnly = true;   // the default layouts: the only ones with mclmc kernels
+    static const NfmcJumpTail* take_jump(NfmcMclmcArgs&) { return nullptr; }
+    static int check(const NfmcMclmcArgs& a, const NfmcJumpTail*, int dp) { return dp != padded_d(a.d) ? NFMC_EINVAL : NFMC_OK; }
+    static void advance(NfmcMclmcArgs& b, const NfmcMclmcArgs& a, int64_t off) {
+        if (a.energy_out) b.energy_out = a.energy_out + off;
+    }
+    static void update(const NfmcMclmcArgs& a, double* slabs, int count, int dp, unsigned long long attempted, uint32_t, int, hipStream_t st) {
+        hipLaunchKernelGGL(mclmc_tune_finish_kernel, dim3(1), dim3(kFinishBlock), 0, st, slabs, count, dp, a.d, a.stats, a.tune,
+                           a.inv_mass_diag, a.energy_sums, attempted);
+    }
+    static void fold(const NfmcMclmcArgs& a, int grid, int width, unsigned long long attempted, hipStream_t st) {
+        if (a.energy_sums)
+            hipLaunchKernelGGL(mclmc_energy_fold_kernel, dim3(1), dim3(kBlock), 0, st, a.stats.scratch, grid, width, a.energy_sums, attempted);
+    }
+};
+
+// The part the sampler entry points share, behind their own argument checks: layout, tile and grid arithmetic, the
 // scratch / defer / tune checks, then either the warmup loop (one launch + controller update per `every` transitions, all
-// of the call enqueued here) or one launch and the statistics finish.  launch(args, jd, c, jhp, fast, tiles, grid).
-// part: the call is one part of a split run (run_parts.hpp).
-template <class Args, class Launch>
+// of the call enqueued here) or one launch and the statistics finish.  launch(args, jd, c, jhp, fast, tiles, grid);
+// P: the sampler's parts above.  part: the call is one part of a split run (run_parts.hpp).
+template <class P, class Args, class Launch>
 static int sampler_steps(const Args* args, hipStream_t st, Launch launch, const LaunchPart* part = nullptr) {
     Args a = *args;
-    const int jhp = a.jump ? (a.jump->flow.n_hidden <= 4 ? 4 : 8) : 0;
-    const Cfg c = choose_cfg(a.d, jhp > 0, pot_kind(a.pot.kind)->default_cfg_only);
+    const NfmcJumpTail* jump = P::take_jump(a);
+    const int jhp = jump ? (jump->flow.n_hidden <= 4 ? 4 : 8) : 0;
+    const Cfg c = choose_cfg(a.d, jhp > 0, P::kDefaultCfgOnly || pot_kind(a.pot.kind)->default_cfg_only);
     if (!c.cpl) return NFMC_ESHAPE;
     const bool fast = fast_path(&a, c) && !a.tune.state;   // tuning launches sum about a shift (StatShift): general kernels
     const int dp = c.cpl * c.lpc;
@@ -532,11 +578,10 @@ static int sampler_steps(const Args* args, hipStream_t st, Launch launch, const 
     if (a.stats.sum_x && a.stats.scratch_bytes < (int64_t)grid * (2 * dp + kStatTail) * (int64_t)sizeof(double))
         return NFMC_ESCRATCH;
     if (check_defer(a.stats, dp, a.d)) return NFMC_EINVAL;
-    if (int rc = check_tune(a, dp, std::is_same<Args, NfmcHmcArgs>::value)) return rc;
-    if (part && a.stats.sum_x) a.stats.scratch += (size_t)part->slab0 * (2 * dp + kStatTail);   // checked as the caller gave it
-    const JumpDev jd = jump_dev(a.jump);
-    unsigned long long* jc = a.jump ? a.jump->counters : nullptr;
-    a.jump = nullptr;  // host pointer: never dereferenced on the device
+    if (int rc = P::check(a, jump, dp)) return rc;
+    const int width = 2 * dp + kStatTail;
+    if (part && a.stats.sum_x) a.stats.scratch += (size_t)part->slab0 * width;   // checked as the caller gave it
+    const JumpDev jd = jump_dev(jump);
     if (a.tune.state) {
         const int every = (a.tune.every > 0 && a.tune.every < a.n_steps) ? a.tune.every : a.n_steps;
         const int total = a.n_steps;
@@ -546,11 +591,11 @@ static int sampler_steps(const Args* args, hipStream_t st, Launch launch, const 
             b.n_steps = k;
             b.rng.step0 = a.rng.step0 + (uint32_t)s0;
             if (a.rng.replay_normals) b.rng.replay_normals = a.rng.replay_normals + (int64_t)s0 * a.n * a.d;
-            if (a.rng.replay_uniforms) b.rng.replay_uniforms = a.rng.replay_uniforms + (int64_t)s0 * a.n;
-            if (a.masks_out) b.masks_out = a.masks_out + (int64_t)s0 * a.n;
-            if (a.log_ratio_out) b.log_ratio_out = a.log_ratio_out + (int64_t)s0 * a.n;
+            P::advance(b, a, (int64_t)s0 * a.n);
             if (int rc = launch(b, jd, c, 0, fast, tiles, grid)) return rc;
-            tune_update(a.stats, a.tune, grid, two_level, dp, a.d, (unsigned long long)a.n * (unsigned long long)k, b.rng.step0, k, st);
+            int count = 0;
+            double* slabs = tune_fold(a.stats.scratch, grid, two_level, width, st, &count);
+            P::update(a, slabs, count, dp, (unsigned long long)a.n * (unsigned long long)k, b.rng.step0, k, st);
             NFMC_HIP_CHECK_LAUNCH();
             store_advance(a.samples, k);
         }
@@ -559,26 +604,28 @@ static int sampler_steps(const Args* args, hipStream_t st, Launch launch, const 
     if (int rc = launch(a, jd, c, jhp, fast, tiles, grid)) return rc;
     NFMC_HIP_CHECK_LAUNCH();
     if (a.stats.sum_x && !a.stats.defer) {
+        const unsigned long long attempted = (unsigned long long)a.n * (unsigned long long)a.n_steps;
+        P::fold(a, grid, width, attempted, st);
         hipLaunchKernelGGL(stats_finish_kernel<true>, dim3(stats_finish_grid(dp)), dim3(kFinishBlock), 0, st, a.stats.scratch,
-                           grid, dp, a.d, a.stats, (unsigned long long)a.n * (unsigned long long)a.n_steps, jc,
-                           (unsigned long long)a.n);
+                           grid, dp, a.d, a.stats, attempted, jump ? jump->counters : nullptr,
+                           P::kJumpTail ? (unsigned long long)a.n : 0ull);
         NFMC_HIP_CHECK_LAUNCH();
     }
     return NFMC_OK;
 }
 
 static int mala_steps(const NfmcMalaArgs* args, hipStream_t st, const LaunchPart* part) {
-    if (int rc = check_common(args)) return rc;
+    if (int rc = check_metropolis(args)) return rc;
     const float sqrt2h = (float)sqrt(2.0 * (double)args->step_size);  // math.sqrt(2*step_size), langevin.py:75
-    return sampler_steps(args, st, [=](const NfmcMalaArgs& a, const JumpDev& jd, Cfg c, int jhp, bool fast, int64_t tiles, int grid) {
+    return sampler_steps<MetropolisParts<NfmcMalaArgs>>(args, st, [=](const NfmcMalaArgs& a, const JumpDev& jd, Cfg c, int jhp, bool fast, int64_t tiles, int grid) {
         return launch_mala(a, jd, c, jhp, fast, tiles, grid, sqrt2h, st);
     }, part);
 }
 
 static int hmc_steps(const NfmcHmcArgs* args, hipStream_t st, const LaunchPart* part) {
-    if (int rc = check_common(args)) return rc;
+    if (int rc = check_metropolis(args)) return rc;
     if (args->n_leapfrog <= 0) return NFMC_EINVAL;
-    return sampler_steps(args, st, [=](const NfmcHmcArgs& a, const JumpDev& jd, Cfg c, int jhp, bool fast, int64_t tiles, int grid) {
+    return sampler_steps<MetropolisParts<NfmcHmcArgs>>(args, st, [=](const NfmcHmcArgs& a, const JumpDev& jd, Cfg c, int jhp, bool fast, int64_t tiles, int grid) {
         return launch_hmc(a, jd, c, jhp, fast, tiles, grid, st);
     }, part);
 }
@@ -596,74 +643,21 @@ extern "C" int64_t nfmc_mclmc_state_doubles(int32_t d, int32_t history_rows) {
     return nfmc_tune_state_doubles(d) + (int64_t)history_rows * NFMC_MCLMC_ROW_WORDS;
 }
 
-// The argument checks in the order of check_common, then the layout, tile and grid arithmetic of sampler_steps: one launch
-// and the folds, or the warmup loop of one launch + controller update per `every` steps, all of the call enqueued here.
 extern "C" int nfmc_mclmc_steps_f32(const NfmcMclmcArgs* args, nfmc_stream_t stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (!args || !args->x || !args->velocity) return NFMC_EINVAL;
-    NfmcMclmcArgs a = *args;
-    if (a.n <= 0 || a.d <= 0 || a.n_steps <= 0 || a.d < 2) return NFMC_EINVAL;
-    if (a.n_steps > NFMC_MAX_STEPS_PER_CALL) return NFMC_ESHAPE;
-    if (a.d > 1024) return NFMC_ESHAPE;
-    if (!(a.step_size > 0.f) || !(a.decoherence_length > 0.f)) return NFMC_EINVAL;
-    if (int rc = check_potential(a.pot, a.d, PotFamily::kRegister)) return rc;
-    if ((((uintptr_t)a.x) & 3u) != 0 || (((uintptr_t)a.velocity) & 3u) != 0) return NFMC_EALIGN;
-    if (!store_ok(a.samples)) return NFMC_EINVAL;
+    if (int rc = check_common(args)) return rc;
+    const NfmcMclmcArgs& a = *args;
+    if (!a.velocity) return NFMC_EINVAL;
+    if (((uintptr_t)a.velocity & 3u) != 0) return NFMC_EALIGN;
+    if (a.d < 2 || !(a.decoherence_length > 0.f)) return NFMC_EINVAL;
     if (int rc = rng_default_only(a.rng)) return rc;
-    if (a.stats.sum_x && (!a.stats.sum_x2 || !a.stats.counters || !a.stats.scratch)) return NFMC_EINVAL;
     if (a.stats.defer) return NFMC_EINVAL;   // the energy columns are folded by the call itself
     if ((a.energy_sums || a.tune.state) && !a.stats.sum_x) return NFMC_EINVAL;
     if (a.tune.state && a.tune.tune_inv_mass_diag && (!a.tune.inv_mass_diag || a.tune.inv_mass_diag != a.inv_mass_diag))
         return NFMC_EINVAL;
-    const Cfg c = choose_cfg(a.d, false, true);   // the default layouts: the only ones with mclmc kernels
-    if (!c.cpl) return NFMC_ESHAPE;
-    const int dp = c.cpl * c.lpc;
-    if (dp != padded_d(a.d)) return NFMC_EINVAL;
-    const int cpw = kWave / c.lpc;
-    const int64_t tiles = (a.n + (int64_t)kWavesPerBlock * cpw - 1) / ((int64_t)kWavesPerBlock * cpw);
-    bool two_level = false;
-    const int grid = a.tune.state ? tune_grid(tiles, dp, a.stats.scratch_bytes, &two_level) : (int)(tiles < kMaxGrid ? tiles : kMaxGrid);
-    const int width = 2 * dp + kStatTail;
-    if (a.stats.sum_x && a.stats.scratch_bytes < (int64_t)grid * width * (int64_t)sizeof(double)) return NFMC_ESCRATCH;
-    if (a.tune.state) {
-        const int every = (a.tune.every > 0 && a.tune.every < a.n_steps) ? a.tune.every : a.n_steps;
-        const int total = a.n_steps;
-        for (int s0 = 0; s0 < total; s0 += every) {
-            const int k = total - s0 < every ? total - s0 : every;
-            NfmcMclmcArgs b = a;
-            b.n_steps = k;
-            b.rng.step0 = a.rng.step0 + (uint32_t)s0;
-            if (a.rng.replay_normals) b.rng.replay_normals = a.rng.replay_normals + (int64_t)s0 * a.n * a.d;
-            if (a.energy_out) b.energy_out = a.energy_out + (int64_t)s0 * a.n;
-            if (int rc = launch_mclmc(b, c, tiles, grid, st)) return rc;
-            NFMC_HIP_CHECK_LAUNCH();
-            const unsigned long long attempted = (unsigned long long)a.n * (unsigned long long)k;
-            double* slabs = a.stats.scratch;
-            int nslabs = grid;
-            if (two_level) {
-                slabs = a.stats.scratch + (size_t)(kMaxGrid - kTuneFoldWgs) * width;
-                nslabs = (grid + kTuneFoldSlabs - 1) / kTuneFoldSlabs;
-                hipLaunchKernelGGL(tune_fold_kernel, dim3(nslabs), dim3(kFinishBlock), 0, st, a.stats.scratch, grid, width, slabs);
-            }
-            hipLaunchKernelGGL(mclmc_tune_finish_kernel, dim3(1), dim3(kFinishBlock), 0, st, slabs, nslabs, dp, a.d, a.stats,
-                               a.tune, a.inv_mass_diag, a.energy_sums, attempted);
-            NFMC_HIP_CHECK_LAUNCH();
-            store_advance(a.samples, k);
-        }
-        return NFMC_OK;
-    }
-    if (int rc = launch_mclmc(a, c, tiles, grid, st)) return rc;
-    NFMC_HIP_CHECK_LAUNCH();
-    if (a.stats.sum_x) {
-        const unsigned long long attempted = (unsigned long long)a.n * (unsigned long long)a.n_steps;
-        if (a.energy_sums)
-            hipLaunchKernelGGL(mclmc_energy_fold_kernel, dim3(1), dim3(kBlock), 0, st, a.stats.scratch, grid, width, a.energy_sums,
-                               attempted);
-        hipLaunchKernelGGL(stats_finish_kernel<true>, dim3(stats_finish_grid(dp)), dim3(kFinishBlock), 0, st, a.stats.scratch,
-                           grid, dp, a.d, a.stats, attempted, (unsigned long long*)nullptr, 0ull);
-        NFMC_HIP_CHECK_LAUNCH();
-    }
-    return NFMC_OK;
+    return sampler_steps<MclmcParts>(args, st, [=](const NfmcMclmcArgs& b, const JumpDev&, Cfg c, int, bool, int64_t tiles, int grid) {
+        return launch_mclmc(b, c, tiles, grid, st);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------

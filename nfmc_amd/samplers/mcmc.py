@@ -23,6 +23,16 @@ from ..tuning import DualAveraging, DualAveragingParams, TrajectoryAdaptationPar
 from .common import Run, accept_select, imd_tensor, launch_limit, progress, resolve_target
 
 
+def inv_mass_diag_of(value, event_size):
+    """A kernel dataclass's inv_mass_diag: ones by default, else `value` (lists / fp64 / any device) as (event_size,) fp32."""
+    if value is None:
+        return torch.ones(event_size)
+    value = torch.as_tensor(value, dtype=torch.float32)
+    if tuple(value.shape) != (event_size,):
+        raise ValueError('inv_mass_diag must have event_size = %d entries, got shape %s' % (event_size, tuple(value.shape)))
+    return value
+
+
 @dataclass
 class MetropolisKernel(MCMCKernel):
     event_size: int
@@ -33,13 +43,7 @@ class MetropolisKernel(MCMCKernel):
 
     def __post_init__(self):
         super().__post_init__()
-        if self.inv_mass_diag is None:
-            self.inv_mass_diag = torch.ones(self.event_size)
-        else:
-            self.inv_mass_diag = torch.as_tensor(self.inv_mass_diag, dtype=torch.float32)   # lists / fp64 / any device
-            if tuple(self.inv_mass_diag.shape) != (self.event_size,):
-                raise ValueError('inv_mass_diag must have event_size = %d entries, got shape %s'
-                                 % (self.event_size, tuple(self.inv_mass_diag.shape)))
+        self.inv_mass_diag = inv_mass_diag_of(self.inv_mass_diag, self.event_size)
         if self.da_params is None:
             self.da_params = DualAveragingParams()
         if self.da is None:
@@ -60,6 +64,16 @@ class MetropolisParameters(MCMCParameters):
     tune_every: int = 1
 
 
+def tuning_state(run, kernel, words):
+    """What the device controllers of a warmup start from: `words` fp64 state words on the host, zero but for the shift of
+    the variance sums -- the column means of x0 (fp32 values), moved to the folded mean by every update -- and the
+    kernel's inv_mass_diag cloned on the device, where the controller rewrites it."""
+    st = torch.zeros(int(words), dtype=torch.float64)
+    c0 = hip.tune_shift_offset(run.d)
+    st[c0:c0 + run.d] = run.x.double().mean(0).float().double()
+    return st, kernel.inv_mass_diag.detach().to(run.dev, torch.float32).contiguous().clone()
+
+
 class DeviceTuning:
     """Step size, mass diagonal and dual-averaging state in device memory for the length of a warmup (NfmcTune,
     include/nfmc_hip.h): the controller (mcmc/base.py:142-161, tuning.py:15-41) runs inside each call's statistics fold
@@ -77,7 +91,7 @@ class DeviceTuning:
                 every = max(1, int(getattr(p, 'tune_every', 1)))
                 self.history_rows = -(-int(p.n_iterations) // every)
             base += int(hip.lib().nfmc_tune_trajectory_doubles(self.history_rows))
-        st = torch.zeros(base, dtype=torch.float64)
+        st, self.imd = tuning_state(run, k, base)
         if self.trajectory:
             ap = getattr(p, 'trajectory_adaptation', None) or TrajectoryAdaptationParams()
             length = k.trajectory_length
@@ -99,11 +113,7 @@ class DeviceTuning:
         st[hip.TUNE_KAPPA] = da.params.kappa
         st[hip.TUNE_GAMMA] = da.params.gamma
         st[hip.TUNE_IMD_ADJUSTMENT] = p.imd_adjustment
-        # shift of the variance sums: the column means of x0 (fp32 values), moved to the folded mean by every update
-        c0 = hip.tune_shift_offset(run.d)
-        st[c0:c0 + run.d] = run.x.double().mean(0).float().double()
         self.state = st.to(run.dev)
-        self.imd = k.inv_mass_diag.detach().to(run.dev, torch.float32).contiguous().clone()
         self.tune_step = bool(p.tuning and p.tune_step_size and p.adjustment)            # mcmc/base.py:153
         self.tune_imd = bool(p.tuning and p.tune_inv_mass_diag and run.n > 1)            # mcmc/base.py:146
         self.updates = 0
@@ -258,6 +268,61 @@ class MCMCSampler(Sampler):
         new_params.n_iterations = self.params.n_iterations
         self.params = new_params
         self.params.sampling_mode()
+        self._after_warmup(warmup_copy)
+        return out
+
+    def _after_warmup(self, warmup_copy):
+        """What a warmup hands the sampling run beside its kernel and parameters (mclmc: the velocity)."""
+
+    # ---- what the sample() bodies share
+    def _refuse(self, run):
+        """Raises ValueError where this sampler cannot run `run`; called before anything else is set up."""
+
+    def _begin(self, x0, show_progress):
+        """The prologue of sample(): (run, step0, out, K, pot, store, t0, bar)."""
+        run = Run(self, x0)
+        self._refuse(run)
+        # a warmup draws from its own part of the Philox stream: with an explicit seed, the sampling run that follows
+        # it must not reuse the innovations that produced its starting state
+        step0 = hip.WARMUP_STEP0 if self.params.tuning else 0
+        out = MCMCOutput(run.event_shape, kernel=self.kernel, store_samples=self.params.store_samples,
+                         max_samples=getattr(self.params, 'max_samples', None))
+        out.statistics.data_transform = self.data_transform
+        K = int(self.params.n_iterations)
+        pot = resolve_target(self.target, run.event_shape, self.fuse, run.x, family='mcmc')
+        store = run.sample_store(K)
+        run.stats.zero_()
+        self._n_divergences = 0
+        t0 = time.time()
+        label = f'{self.name} (tuning)' if self.params.tuning else self.name
+        return run, step0, out, K, pot, store, t0, progress(show_progress, total=K, desc=label)
+
+    @staticmethod
+    def _pool_limit(every, show_progress, time_limit_seconds):
+        """Transitions per call of a device warmup with one controller update per `every` of them: calls of whole pools,
+        so that the controller updates once per `every` transitions whatever the call size."""
+        limit = launch_limit(max(32, every), show_progress, time_limit_seconds)
+        return limit - limit % every
+
+    def _common_args(self, a, run, pot, k, step0, samples, rows, adjusted, rng=None, tune=None, **deferred):
+        """The fields every fused sampler's args struct has, for a launch of k transitions that offers `rows` states.
+        `deferred`: the DeviceStats.struct arguments of a launch whose statistics are folded later (none: by the call)."""
+        a.x, a.n, a.d, a.n_steps, a.step_size = hip.ptr(run.x), run.n, run.d, k, float(self.kernel.step_size)
+        a._keep = tune.imd if tune is not None else imd_tensor(self.kernel, run.dev)   # borrowed until the launch is enqueued
+        a.inv_mass_diag = hip.ptr(a._keep)
+        a.pot = pot.descriptor(run.dev)
+        # `rng`: an NfmcRng prepared by the caller (replay bookkeeping of fused jump tails)
+        a.rng = rng if rng is not None else run.rng(step0, k, adjusted=adjusted)
+        a.stats = run.stats.struct(**deferred)
+        a.samples = hip.store_struct(samples, rows)
+
+    def _end(self, run, out, t0, store, tune, **counters):
+        """The tail of sample(): the run's results into `out`, then the tuned kernel back from the device."""
+        run.finish(out, t0, run.n * run.done, store, **counters)
+        if tune is not None:
+            # tuning launches fold their statistics per call: the controller state was final before the finish
+            tune.download(self.kernel)
+        self._cur_run = None
         return out
 
     def sample(self, x0, show_progress: bool = True, time_limit_seconds=None) -> MCMCOutput:
@@ -265,23 +330,8 @@ class MCMCSampler(Sampler):
         if self.params.tuning and int(getattr(self.params, 'tune_every', 1)) > hip.MAX_STEPS_PER_CALL:
             raise ValueError('tune_every must be at most %d, got %d'
                              % (hip.MAX_STEPS_PER_CALL, int(self.params.tune_every)))
-        run = Run(self, x0)
-        # a warmup draws from its own part of the Philox stream: with an explicit seed, the sampling run that follows
-        # it must not reuse the innovations that produced its starting state
-        step0 = hip.WARMUP_STEP0 if self.params.tuning else 0
-        n = run.n
-        event_shape = run.event_shape
-        out = MCMCOutput(event_shape, kernel=self.kernel, store_samples=self.params.store_samples,
-                         max_samples=getattr(self.params, 'max_samples', None))
-        out.statistics.data_transform = self.data_transform
-        K = int(self.params.n_iterations)
-        pot = resolve_target(self.target, event_shape, self.fuse, run.x, family='mcmc')
-        store = run.sample_store(K)
-        run.stats.zero_()
-        self._n_divergences = 0
-        t0 = time.time()
-        label = f'{self.name} (tuning)' if self.params.tuning else self.name
-        bar = progress(show_progress, total=K, desc=label)
+        run, step0, out, K, pot, store, t0, bar = self._begin(x0, show_progress)
+        n, event_shape = run.n, run.event_shape
         stepwise = self.params.tuning or pot is None
         limit = 1 if stepwise else launch_limit(32, show_progress, time_limit_seconds)
         # warmup of a fused sampler on one GPU: kernel state and controller on the device, no host round trip per step
@@ -298,9 +348,7 @@ class MCMCSampler(Sampler):
             tune = DeviceTuning(self, run, trajectory)
             # one ABI call enqueues every (kernel, controller) pair of up to 512 transitions: no host work per update
             tune.every = max(1, int(getattr(self.params, 'tune_every', 1)))
-            limit = launch_limit(max(32, tune.every), show_progress, time_limit_seconds)
-            # calls of whole pools: the controller updates once per `every` transitions whatever the call size
-            limit -= limit % tune.every
+            limit = self._pool_limit(tune.every, show_progress, time_limit_seconds)
         elif trajectory:
             # jittered trajectories at a frozen length: the tuning path (general kernels, per-call fold) with the tuners off
             tune = DeviceTuning(self, run, trajectory)
@@ -321,13 +369,8 @@ class MCMCSampler(Sampler):
         # what ran: with a jittered trajectory the leapfrog steps are counted on the device, read once here
         self._leapfrog_total = tune.leapfrog_total() if tune is not None and tune.trajectory else None
         calls, grads = self._counts(n, run.done)
-        run.finish(out, t0, n * run.done, store, n_target_calls=calls, n_target_gradient_calls=grads,
-                   n_divergences=self._n_divergences)
-        if tune is not None:
-            # tuning launches fold their statistics per call: the controller state was final before the finish
-            tune.download(self.kernel)
-        self._cur_run = None
-        return out
+        return self._end(run, out, t0, store, tune, n_target_calls=calls, n_target_gradient_calls=grads,
+                         n_divergences=self._n_divergences)
 
     def _rejected_step(self, xf, n_calls, n_grads):
         """What propose() returns when the target raised ValueError: x' = x, nobody accepts (log ratio -inf, also for
@@ -406,26 +449,18 @@ class MetropolisSampler(MCMCSampler):
         """NfmcMalaArgs / NfmcHmcArgs of a launch of k transitions (`attempted`: chain-transitions to book with deferred
         statistics when the struct stands for more launches than one, samplers/jump.py: launch_jump_run)."""
         a = self._struct()
-        a.x, a.n, a.d, a.n_steps = hip.ptr(run.x), run.n, run.d, k
-        a.step_size = float(self.kernel.step_size)
         a.adjust = 1 if self.params.adjustment else 0
         self._own_args(a)
-        imd = tune.imd if tune is not None else imd_tensor(self.kernel, run.dev)
-        a.inv_mass_diag = hip.ptr(imd)
-        a.pot = pot.descriptor(run.dev)
-        # `rng`: an NfmcRng prepared by the caller (replay bookkeeping of fused jump tails)
-        a.rng = rng if rng is not None else run.rng(step0, k, adjusted=self.params.adjustment)
-        if tune is not None:   # the controller rides on the per-call statistics fold
-            a.stats = run.stats.struct()
+        # with a tuning state the controller rides on the per-call statistics fold
+        deferred = {} if tune is not None else dict(defer=True, attempted=run.n * k if attempted is None else attempted,
+                                                    jump_attempted=run.n if jump is not None else 0)
+        self._common_args(a, run, pot, k, step0, samples, k + (1 if jump is not None else 0), self.params.adjustment, rng, tune,
+                          **deferred)
+        if tune is not None:
             a.tune = tune.struct(getattr(tune, 'every', 0), k)
-        else:
-            a.stats = run.stats.struct(defer=True, attempted=run.n * k if attempted is None else attempted,
-                                       jump_attempted=run.n if jump is not None else 0)
-        a.samples = hip.store_struct(samples, k + (1 if jump is not None else 0))
         a.masks_out = hip.ptr(masks_out, torch.uint8) if masks_out is not None else None
         a.log_ratio_out = hip.ptr(log_ratio_out) if log_ratio_out is not None else None
         a.jump = C.pointer(jump) if jump is not None else None
-        a._keep = imd   # the struct borrows its memory until the launch is enqueued
         return a
 
     def _launch(self, run, pot, k, step0, samples, **kw):
@@ -729,13 +764,7 @@ class MCLMCKernel(MCMCKernel):
             self.step_size = 0.25 * math.sqrt(d)
         if self.decoherence_length is None:
             self.decoherence_length = math.sqrt(d)
-        if self.inv_mass_diag is None:
-            self.inv_mass_diag = torch.ones(d)
-        else:
-            self.inv_mass_diag = torch.as_tensor(self.inv_mass_diag, dtype=torch.float32)
-            if tuple(self.inv_mass_diag.shape) != (d,):
-                raise ValueError('inv_mass_diag must have event_size = %d entries, got shape %s'
-                                 % (d, tuple(self.inv_mass_diag.shape)))
+        self.inv_mass_diag = inv_mass_diag_of(self.inv_mass_diag, d)
 
     def __repr__(self):
         return (f'log step: {math.log(self.step_size):.2f}, decoherence length: {self.decoherence_length:.3g}, '
@@ -786,17 +815,14 @@ class MclmcTuning:
         k, p, lib = sampler.kernel, sampler.params, hip.lib()
         self.rows = int(n_updates)
         self.history_offset = int(lib.nfmc_tune_state_doubles(run.d))
-        st = torch.zeros(int(lib.nfmc_mclmc_state_doubles(run.d, self.rows)), dtype=torch.float64)
+        st, self.imd = tuning_state(run, k, lib.nfmc_mclmc_state_doubles(run.d, self.rows))
         st[hip.MCLMC_STEP_SIZE] = float(k.step_size)
         st[hip.MCLMC_DECOHERENCE_LENGTH] = float(k.decoherence_length)
         st[hip.MCLMC_TARGET] = float(p.energy_variance_target)
         st[hip.MCLMC_IMD_ADJUSTMENT] = float(p.imd_adjustment)
         st[hip.MCLMC_DECOHERENCE_FACTOR] = float(p.decoherence_factor)
         st[hip.MCLMC_HISTORY_ROWS] = self.rows
-        c0 = hip.tune_shift_offset(run.d)
-        st[c0:c0 + run.d] = run.x.double().mean(0).float().double()
         self.state = st.to(run.dev)
-        self.imd = k.inv_mass_diag.detach().to(run.dev, torch.float32).contiguous().clone()
         self.flags = (int(bool(p.tune_step_size)), int(bool(p.tune_decoherence_length)), int(bool(p.tune_inv_mass_diag)))
         self.every = max(1, int(p.tune_every))
 
@@ -837,19 +863,19 @@ class MCLMC(MCMCSampler):
     def name(self):
         return 'MCLMC'
 
-    def warmup(self, x0, show_progress: bool = True, time_limit_seconds=None) -> MCMCOutput:
-        with torch.no_grad():
-            warmup_copy = deepcopy(self)
-        warmup_copy.params.tuning_mode()
-        warmup_copy.params.n_iterations = self.params.n_warmup_iterations
-        out = warmup_copy.sample(x0, show_progress=show_progress, time_limit_seconds=time_limit_seconds)
-        self.kernel = warmup_copy.kernel
-        new_params = warmup_copy.params
-        new_params.n_iterations = self.params.n_iterations
-        self.params = new_params
-        self.params.sampling_mode()
+    def _after_warmup(self, warmup_copy):
         self._next_velocity = warmup_copy._last_velocity   # handed to the sampling run
-        return out
+
+    def _refuse(self, run):
+        k, p = self.kernel, self.params
+        if run.d < 2 or run.d != int(k.event_size):
+            raise ValueError('mclmc: the chains have event size %d, the kernel %d (at least 2)' % (run.d, int(k.event_size)))
+        if run.rounds == 7:
+            raise ValueError('mclmc: rng_rounds=7 runs the exact-fit kernels; mclmc runs in the general kernels on the '
+                             'Philox4x32-10 stream')
+        if p.tuning and run.shard is not None and run.shard.world > 1:
+            raise ValueError('mclmc: a sharded warmup is not supported (the controller pools the chains of one device); '
+                             'warm up on one device and shard the sampling run')
 
     def _velocity(self, run, step0):
         """The run's unit velocities: those a warmup left, else normals of Philox stream 4 at the run's first step counter,
@@ -865,14 +891,8 @@ class MCLMC(MCMCSampler):
 
     def _launch_fused(self, run, pot, u, k, step0, store, esums, tune, energy_out=None):
         a = hip.NfmcMclmcArgs()
-        a.x, a.velocity, a.n, a.d, a.n_steps = hip.ptr(run.x), hip.ptr(u), run.n, run.d, k
-        a.step_size, a.decoherence_length = float(self.kernel.step_size), float(self.kernel.decoherence_length)
-        imd = tune.imd if tune is not None else imd_tensor(self.kernel, run.dev)
-        a.inv_mass_diag = hip.ptr(imd)
-        a.pot = pot.descriptor(run.dev)
-        a.rng = run.rng(step0, k, adjusted=False)
-        a.stats = run.stats.struct()
-        a.samples = hip.store_struct(store, k)
+        self._common_args(a, run, pot, k, step0, store, k, False, tune=tune)
+        a.velocity, a.decoherence_length = hip.ptr(u), float(self.kernel.decoherence_length)
         a.energy_out = hip.ptr(energy_out) if energy_out is not None else None
         a.energy_sums = hip.ptr(esums, torch.float64)
         if tune is not None:
@@ -938,35 +958,15 @@ class MCLMC(MCMCSampler):
             raise ValueError('tune_every must be in 1 .. %d, got %d' % (hip.MAX_STEPS_PER_CALL, int(p.tune_every)))
         if not (float(k.step_size) > 0 and float(k.decoherence_length) > 0):
             raise ValueError('mclmc: step_size and decoherence_length must be positive')
-        run = Run(self, x0)
-        if run.d < 2 or run.d != int(k.event_size):
-            raise ValueError('mclmc: the chains have event size %d, the kernel %d (at least 2)' % (run.d, int(k.event_size)))
-        if run.rounds == 7:
-            raise ValueError('mclmc: rng_rounds=7 runs the exact-fit kernels; mclmc runs in the general kernels on the '
-                             'Philox4x32-10 stream')
-        if p.tuning and run.shard is not None and run.shard.world > 1:
-            raise ValueError('mclmc: a sharded warmup is not supported (the controller pools the chains of one device); '
-                             'warm up on one device and shard the sampling run')
-        step0 = hip.WARMUP_STEP0 if p.tuning else 0
-        n, event_shape = run.n, run.event_shape
-        out = MCMCOutput(event_shape, kernel=k, store_samples=p.store_samples, max_samples=getattr(p, 'max_samples', None))
-        out.statistics.data_transform = self.data_transform
-        K = int(p.n_iterations)
-        pot = resolve_target(self.target, event_shape, self.fuse, run.x, family='mcmc')
-        store = run.sample_store(K)
-        run.stats.zero_()
-        t0 = time.time()
-        bar = progress(show_progress, total=K, desc=f'{self.name} (tuning)' if p.tuning else self.name)
+        run, step0, out, K, pot, store, t0, bar = self._begin(x0, show_progress)
         u = self._velocity(run, step0)
         esums = torch.zeros(3, dtype=torch.float64, device=run.dev)
         tune, ctl, cache = None, None, {}
         if pot is not None:
             limit = launch_limit(32, show_progress, time_limit_seconds)
             if p.tuning:
-                every = max(1, int(p.tune_every))
-                tune = MclmcTuning(self, run, -(-K // every) + 1)
-                limit = launch_limit(max(32, every), show_progress, time_limit_seconds)
-                limit -= limit % every   # calls of whole pools
+                tune = MclmcTuning(self, run, -(-K // max(1, int(p.tune_every))) + 1)
+                limit = self._pool_limit(tune.every, show_progress, time_limit_seconds)
         else:
             limit = 1
             if p.tuning:
@@ -984,13 +984,11 @@ class MCLMC(MCMCSampler):
             if ctl['states']:
                 self._host_update(ctl)   # the steps left over the last whole pool
             k.adaptation_history = torch.tensor(ctl['adaptation'].history, dtype=torch.float64).reshape(-1, hip.MCLMC_ROW_WORDS)
-        run.finish(out, t0, n * run.done, store, n_target_calls=n * run.done, n_target_gradient_calls=n * run.done,
-                   n_accepted_trajectories=n * run.done, n_attempted_trajectories=n * run.done, n_divergences=0)
-        if tune is not None:
-            tune.download(k)
-        elif not p.tuning:
+        steps = run.n * run.done
+        self._end(run, out, t0, store, tune, n_target_calls=steps, n_target_gradient_calls=steps,
+                  n_accepted_trajectories=steps, n_attempted_trajectories=steps, n_divergences=0)
+        if tune is None and not p.tuning:
             s2, _, cnt = (float(v) for v in esums.cpu())
             k.energy_variance = s2 / (cnt * run.d) if cnt > 0 else math.nan
         self._last_velocity = u
-        self._cur_run = None
         return out

@@ -403,7 +403,47 @@ def test_7_one_call_enqueues_every_update(dev):
     assert all(torch.equal(a, b) for a, b in zip(*words))
 
 
-# ------------------------------------------------------------------------------------------------ 8 / 9. behaviour
+def test_7_the_two_level_fold_leaves_what_the_one_level_fold_leaves(dev, monkeypatch):
+    """Above 256 workgroup tiles a tuning launch runs on the full grid and its slabs are folded in two levels: 20000
+    chains at d = 13 (layout (4, 4), 64 chains per workgroup) are 313 tiles.  NFMC_TUNE_ONE_LEVEL=1, read per call, holds
+    the same call to 256 workgroups and one fold.  A chain's arithmetic does not depend on the grid, so its outputs are the
+    same bits; the two folds add the same 160 000 fp64 addends per column in another order, at most 160 000 x 2^-53 ~ 2e-11
+    relative apart, held to 1e-9; the scales are those fp64 values rounded to fp32: one ulp."""
+    from nfmc_amd import hip
+    from nfmc_amd.samplers import mcmc
+    from nfmc_amd.samplers.common import Run
+    d, n, every = 13, 20000, 8
+    pot, _, imd0 = _quadratic_case(d)
+    x0, u0 = starts(n, d, 5), velocity(n, d)
+    monkeypatch.delenv('NFMC_TUNE_ONE_LEVEL', raising=False)
+    runs = []
+    for one_level in (False, True):
+        if one_level:
+            monkeypatch.setenv('NFMC_TUNE_ONE_LEVEL', '1')
+        s = mcmc.MCLMC((d,), pot, mcmc.MCLMCKernel(d, step_size=0.6, decoherence_length=2.0, inv_mass_diag=imd0),
+                       mcmc.MCLMCParameters(n_iterations=every, tune_every=every, tune_inv_mass_diag=True, tuning=True))
+        s.seed, s.shard, s.fuse, s.replay = SEED, None, 'auto', None
+        tune = mcmc.MclmcTuning(s, Run(s, x0), 1)
+        stats = hip.DeviceStats(d, dev)
+        esums = torch.zeros(3, dtype=torch.float64, device=dev)
+        r = launch(dev, pot, x0, u0, every, 0.6, 2.0, tune=tune, stats=stats, esums=esums, dense=False)
+        runs.append((r, tune.state.cpu()[:hip.MCLMC_WORDS].clone(), tune.imd.cpu().clone(), stats.host_totals()[2].clone(),
+                     esums.cpu().clone()))
+    (ra, sa, ia, ca, ea), (rb, sb, ib, cb, eb) = runs
+    assert all(torch.equal(ra[k], rb[k]) for k in ('x', 'u', 'de'))
+    assert torch.equal(ca, cb) and int(ca[hip.CNT_ATTEMPTED]) == n * every
+    assert float(sa[hip.MCLMC_COUNT]) == float(sb[hip.MCLMC_COUNT]) == n * every
+    assert float(sa[hip.MCLMC_HISTORY_USED]) == 1 == float(sb[hip.MCLMC_HISTORY_USED])
+    words = [hip.MCLMC_STEP_SIZE, hip.MCLMC_DECOHERENCE_LENGTH, hip.MCLMC_ENERGY_VARIANCE]
+    rel = float(((sa[words] - sb[words]).abs() / sb[words].abs()).max())
+    rel_e = float(((ea - eb).abs() / eb.abs()).max())
+    ulp = 2.0 ** (torch.floor(torch.log2(torch.minimum(ia, ib).abs().double())) - 23)   # of the smaller: the finer spacing
+    ulps = float(((ia.double() - ib.double()).abs() / ulp).max())
+    print('two-level against one-level fold: eps, L, V differ by %.3g relative, the energy sums by %.3g, the scales by %.3g ulp'
+          % (rel, rel_e, ulps))
+    assert rel <= 1e-9 and rel_e <= 1e-9
+    assert ulps <= 1.0
+
 def test_8_the_warmup_finds_the_step_size_of_the_reference_on_a_standard_gaussian(dev):
     from nfmc_amd import hip, sample
     from nfmc_amd.potentials import DiagonalGaussian

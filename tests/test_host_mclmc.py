@@ -226,3 +226,46 @@ def test_the_entry_point_refuses_with_the_codes_of_the_hmc_entry_point():
     assert rc(**full, **{'stats.defer': 1, 'stats.scratch_bytes': 1 << 30}) == hip.EINVAL
     assert rc(**full, **{'stats.scratch_bytes': 8}) == hip.ESCRATCH
     assert rc(**full, **{'stats.scratch_bytes': 1 << 30, 'tune.state': 4096, 'tune.tune_inv_mass_diag': 1}) == hip.EINVAL
+
+
+@pytest.mark.parametrize('entry', ['nfmc_mala_steps_f32', 'nfmc_hmc_steps_f32'])
+def test_the_mala_and_hmc_entry_points_refuse_the_same_single_faults_with_the_same_codes(entry):
+    """The faults of the test above that the mala and hmc structs can carry, one at a time: the three entry points share
+    these checks, and a fault has one code whichever of them meets it."""
+    from nfmc_amd import hip
+    EINVAL, ESHAPE, EALIGN, EUNSUPPORTED, ESCRATCH = -1, -2, -3, -4, -5
+    assert (hip.OK, hip.EINVAL, hip.ESHAPE, hip.EALIGN, hip.EUNSUPPORTED, hip.ESCRATCH) == (0, -1, -2, -3, -4, -5)
+    hmc = entry == 'nfmc_hmc_steps_f32'
+    fn = getattr(hip.lib(), entry)
+
+    def rc(**kw):
+        a = (hip.NfmcHmcArgs if hmc else hip.NfmcMalaArgs)()
+        a.x, a.n, a.d, a.n_steps, a.step_size, a.adjust = 4096, 8, 4, 2, 0.1, 1
+        if hmc:
+            a.n_leapfrog = 3
+        a.pot = hip.NfmcPotential(hip.POT_QUADRATIC, 0, None, None, 1.0, 0.0)
+        a.rng = hip.make_rng(1, 0, 0)
+        a.stats = hip.null_stats()
+        a.samples = hip.dense_store(None)
+        for k, v in kw.items():
+            obj, name = a, k
+            while '.' in name:
+                head, name = name.split('.', 1)
+                obj = getattr(obj, head)
+            setattr(obj, name, v)
+        return fn(C.byref(a), None)
+
+    assert fn(None, None) == EINVAL and rc(x=None) == EINVAL
+    assert rc(n=0) == EINVAL and rc(d=0) == EINVAL and rc(n_steps=0) == EINVAL
+    assert rc(n_steps=513) == ESHAPE and rc(d=1025) == ESHAPE
+    assert rc(step_size=0.0) == EINVAL
+    assert rc(**{'pot.kind': 99}) == EUNSUPPORTED
+    assert rc(x=4098) == EALIGN
+    assert rc(**{'rng.rounds': 3}) == EINVAL
+    assert rc(**{'samples.base': 4096, 'samples.stride': 0}) == EINVAL
+    assert rc(**{'stats.sum_x': 4096}) == EINVAL                          # statistics without their other buffers
+    full = {'stats.sum_x': 4096, 'stats.sum_x2': 4096, 'stats.counters': 4096, 'stats.scratch': 4096}
+    assert rc(**full, **{'stats.scratch_bytes': 8}) == ESCRATCH
+    assert rc(**{'tune.state': 4096}) == EINVAL                           # the controller rides on the statistics fold
+    if hmc:
+        assert rc(n_leapfrog=0) == EINVAL
