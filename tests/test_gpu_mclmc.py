@@ -5,7 +5,6 @@ between the reference run in torch fp32 and in fp64 on the CPU for the case's ow
 the kernels' butterfly association and fused multiply-adds, which torch does not share.  Every case prints what it
 measured (pytest -s); DESIGN.md 3.7 records the figures.
 """
-import ctypes as C
 import functools
 import math
 
@@ -13,79 +12,15 @@ import pytest
 import torch
 
 import mclmc_fp64 as M
+from mclmc_cases import MARGIN, N, SEED, T, _figures, compare, launch, starts, velocity
 
 pytestmark = pytest.mark.gpu
-
-N, T, SEED = 96, 8, 77
-MARGIN = 4.0
 
 
 @pytest.fixture(scope='module')
 def dev():
     from nfmc_amd import hip
     return hip.require_gpu()
-
-
-# ------------------------------------------------------------------------------------------------ direct launches
-def launch(dev, pot, x0, u0, n_steps, eps, L, imd=None, *, seed=SEED, step0=0, chain_offset=0, stats=None, store=None,
-           esums=None, tune=None, energy=True, dense=True):
-    """One call of nfmc_mclmc_steps_f32: dict(x, u, kept (n_steps, n, d) or None, de (n_steps, n) or None)."""
-    from nfmc_amd import hip
-    x = x0.detach().to(dev, torch.float32).contiguous().clone()
-    u = u0.detach().to(dev, torch.float32).contiguous().clone()
-    n, d = x.shape
-    a = hip.NfmcMclmcArgs()
-    a.x, a.velocity, a.n, a.d, a.n_steps = hip.ptr(x), hip.ptr(u), n, d, n_steps
-    a.step_size, a.decoherence_length = float(eps), float(L)
-    imd_dev = None
-    if tune is not None:
-        imd_dev = tune.imd
-    elif imd is not None:
-        imd_dev = torch.as_tensor(imd).to(dev, torch.float32).contiguous()
-    a.inv_mass_diag = hip.ptr(imd_dev)
-    a.pot = pot.descriptor(dev)
-    a.rng = hip.make_rng(seed, chain_offset, step0)
-    a.stats = stats.struct() if stats is not None else hip.null_stats()
-    kept = torch.full((n_steps, n, d), float('nan'), device=dev) if (dense and store is None) else None
-    a.samples = hip.store_struct(store if store is not None else kept, n_steps)
-    de = torch.full((n_steps, n), float('nan'), device=dev) if energy else None
-    a.energy_out = hip.ptr(de)
-    a.energy_sums = hip.ptr(esums, torch.float64) if esums is not None else None
-    if tune is not None:
-        a.tune = tune.struct(n_steps)
-    hip.check(hip.lib().nfmc_mclmc_steps_f32(C.byref(a), hip.stream()), 'nfmc_mclmc_steps_f32')
-    torch.cuda.synchronize()
-    return {'x': x, 'u': u, 'kept': kept, 'de': de, 'imd': imd_dev}
-
-
-def starts(n, d, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return (scale * torch.randn(n, d, generator=g, dtype=torch.float64)).float()
-
-
-def _figures(target, x0, u0, eps, L, imd, n_steps, seed=SEED, step0=0):
-    """(fp64 run, tolerances): per quantity the largest |fp32 - fp64| of the reference's own two runs, x MARGIN"""
-    r64 = M.steps(target, x0.double(), u0.double(), eps, L, imd, seed, step0, n_steps, torch.float64)
-    r32 = M.steps(target, x0.float(), u0.float(), eps, L, imd, seed, step0, n_steps, torch.float32)
-    assert r64[3].all() and r32[3].all(), 'the case is meant to take every step'
-    fig = [float((a.double() - b).abs().max()) for a, b in zip(r32[:3], r64[:3])]
-    return r64, {'x': MARGIN * fig[0], 'u': MARGIN * fig[1], 'de': MARGIN * fig[2]}
-
-
-def compare(run, r64, tol, what):
-    xs, us, des, _ = r64
-    got = {'x': float((run['kept'].cpu().double() - xs).abs().max()),
-           'u': float((run['u'].cpu().double() - us[-1]).abs().max()),
-           'de': float((run['de'].cpu().double() - des).abs().max())}
-    print('%s: |x| <= %.3g  states %.3g (tol %.3g)  velocity %.3g (tol %.3g)  dE %.3g (tol %.3g)'
-          % (what, float(xs.abs().max()), got['x'], tol['x'], got['u'], tol['u'], got['de'], tol['de']))
-    assert torch.equal(run['kept'][-1], run['x'])
-    for k in ('x', 'u', 'de'):
-        assert got[k] <= tol[k], (what, k, got[k], tol[k])
-
-
-def velocity(n, d, seed=SEED, step0=0):
-    return M.initial_velocity(n, d, seed, step0).float()
 
 
 # ------------------------------------------------------------------------------------------------ 1. step by step
@@ -97,7 +32,21 @@ def _quadratic_case(d):
     return QuadraticPotential((d,), a.float(), b.float()), M.quadratic(a.float().double(), b.float().double()), imd
 
 
-@pytest.mark.parametrize('d', [2, 3, 5, 13, 33, 100, 200, 300, 1000])
+TEST_1_DS = [2, 3, 5, 13, 24, 33, 100, 200, 300, 1000]
+
+
+def test_1_the_dimensions_reach_all_nine_default_layouts():
+    import ctypes as C
+    from nfmc_amd import hip
+    got = set()
+    for d in TEST_1_DS:
+        cpl, lpc = C.c_int32(0), C.c_int32(0)
+        assert hip.lib().nfmc_sampler_layout(d, hip.POT_QUADRATIC, C.byref(cpl), C.byref(lpc)) == hip.OK
+        got.add((cpl.value, lpc.value))
+    assert got == {(4, 1), (4, 2), (4, 4), (4, 8), (8, 8), (8, 16), (8, 32), (8, 64), (16, 64)}
+
+
+@pytest.mark.parametrize('d', TEST_1_DS)
 def test_1_every_step_follows_the_fp64_reference_at_every_layout(dev, d):
     pot, target, imd = _quadratic_case(d)
     x0, u0 = starts(N, d, 100 + d), velocity(N, d)
