@@ -1520,6 +1520,7 @@ def bad_descriptors_are_refused(dev, pot, x0, f, bad, ok=(), *, event_shape=None
 
     def changed(field, value):
         q = pot.descriptor(dev)
+        assert hasattr(type(q), field), field      # a name the struct lacks would set nothing and leave q well formed
         setattr(q, field, q.a + 4 if value == 'misaligned' else value)
         return q
     bad = [(changed(field, value), code, (field, value)) for field, value, code in bad]

@@ -430,7 +430,7 @@ def test_refusing_entry_points_answer_unsupported(dev, unknown):
     d = 63 + (2 if unknown else 0)
     p = _Problem(d, 'lorenz63', 3, unknown, 4, 256, 4)
     pd = p.pot.descriptor(dev)
-    assert pd.kind == hip.POT_DIFFUSION_BRIDGE == 14 and pd.reserved == 21
+    assert pd.kind == hip.POT_DIFFUSION_BRIDGE == 14 and pd.n_components == 21
     assert pd.a_scalar == (22.0 if unknown else 18.0)
     H.refusing_entry_points(dev, p.pot, p.x0, functools.partial(_flow_pair, d))
     H.fit_step_refuses(dev, p.pot, p.x0, _flow_pair(d)[0])
@@ -446,8 +446,8 @@ def test_philox7_and_bad_descriptors_are_refused(dev):
     b = p.pot.descriptor(dev).b
     assert p.pot.descriptor(dev).a_scalar == 20.0
     bad = [('a', 0, hip.EINVAL), ('b', 0, hip.EINVAL), ('a', 'misaligned', hip.EALIGN), ('b', b + 4, hip.EALIGN),
-           ('b', b + 8, hip.EALIGN), ('reserved', 0, hip.EINVAL), ('reserved', 1, hip.EINVAL), ('reserved', -3, hip.EINVAL),
-           ('reserved', 7, hip.EINVAL), ('reserved', 9, hip.EINVAL),                      # d != T m + 2
+           ('b', b + 8, hip.EALIGN), ('n_components', 0, hip.EINVAL), ('n_components', 1, hip.EINVAL), ('n_components', -3, hip.EINVAL),
+           ('n_components', 7, hip.EINVAL), ('n_components', 9, hip.EINVAL),                      # d != T m + 2
            ('a_scalar', 16.0, hip.EINVAL),                                                # fixed scales: d != T m
            ('a_scalar', 3.0, hip.EINVAL), ('a_scalar', 7.0, hip.EINVAL), ('a_scalar', 23.0, hip.EINVAL),   # drift code 3
            ('a_scalar', 21.0, hip.EINVAL), ('a_scalar', 5.0, hip.EINVAL),                 # fitzhugh_nagumo at m = 3, m = 1

@@ -203,7 +203,7 @@ def test_refusing_entry_points_answer_unsupported(dev):
     d = 64
     pot, ref = _problem(d, 4)
     pd = pot.descriptor(dev)
-    assert pd.kind == hip.POT_GAUSSIAN_FULL and pd.reserved == d
+    assert pd.kind == hip.POT_GAUSSIAN_FULL and pd.n_components == d
     H.refusing_entry_points(dev, pot, _x0(ref, 256, 4), functools.partial(_flow_pair, d))
 
 
@@ -212,7 +212,7 @@ def test_philox7_and_bad_descriptors_are_refused(dev):
     from nfmc_amd import hip
     d = 25
     pot, ref = _problem(d, 8)
-    bad = [('a', 0), ('b', 0), ('a', 'misaligned'), ('reserved', d - 1), ('reserved', d + 1)]
+    bad = [('a', 0), ('b', 0), ('a', 'misaligned'), ('n_components', d - 1), ('n_components', d + 1)]
     H.bad_descriptors_are_refused(dev, pot, _x0(ref, 128, 8), _flow_pair(d)[0], [(f, v, hip.EINVAL) for f, v in bad])
 
 

@@ -274,7 +274,7 @@ def test_refusing_entry_points_answer_unsupported(dev, mode):
     d = 64
     p = _Problem(d, 'poisson', mode, 4, 256, 4)
     pd = p.pot.descriptor(dev)
-    assert pd.kind == hip.POT_LATENT_GMRF and pd.reserved == p.pot.width
+    assert pd.kind == hip.POT_LATENT_GMRF and pd.n_components == p.pot.width
     assert pd.a_scalar == {'fixed': 0.0, 'centered': 4.0, 'scaled': 12.0}[mode]
     H.refusing_entry_points(dev, p.pot, p.x0, functools.partial(_flow_pair, d))
     H.fit_step_refuses(dev, p.pot, p.x0, _flow_pair(d)[0])
@@ -288,11 +288,11 @@ def test_philox7_and_bad_descriptors_are_refused(dev):
     p = _Problem(d, 'student_t', 'scaled', 8, 128, 8)
     b = p.pot.descriptor(dev).b
     bad = [('a', 0, hip.EINVAL), ('b', 0, hip.EINVAL), ('a', 'misaligned', hip.EALIGN), ('b', b + 4, hip.EALIGN),
-           ('b', b + 8, hip.EALIGN), ('reserved', 0, hip.EINVAL), ('reserved', -3, hip.EINVAL),
-           ('reserved', 33, hip.EUNSUPPORTED), ('a_scalar', 3.0, hip.EINVAL), ('a_scalar', 7.0, hip.EINVAL),
+           ('b', b + 8, hip.EALIGN), ('n_components', 0, hip.EINVAL), ('n_components', -3, hip.EINVAL),
+           ('n_components', 33, hip.EUNSUPPORTED), ('a_scalar', 3.0, hip.EINVAL), ('a_scalar', 7.0, hip.EINVAL),
            ('a_scalar', 8.0, hip.EINVAL), ('a_scalar', 10.0, hip.EINVAL), ('a_scalar', 15.0, hip.EINVAL),
            ('a_scalar', 16.0, hip.EINVAL), ('a_scalar', 4.5, hip.EINVAL), ('a_scalar', -1.0, hip.EINVAL)]
-    ok = [('a_scalar', float(c)) for c in (0, 1, 2, 4, 5, 6, 12, 13, 14)] + [('reserved', 32), ('reserved', 1)]
+    ok = [('a_scalar', float(c)) for c in (0, 1, 2, 4, 5, 6, 12, 13, 14)] + [('n_components', 32), ('n_components', 1)]
     H.bad_descriptors_are_refused(dev, p.pot, p.x0, _flow_pair(d)[0], bad, ok)
 
 

@@ -253,7 +253,7 @@ def test_refusing_entry_points_answer_unsupported(dev):
     from nfmc_amd import hip
     p = _problem(30, 20, 256)
     pd = p.pot.descriptor(dev)
-    assert pd.kind == hip.POT_ITEM_RESPONSE == 9 and pd.reserved == 30
+    assert pd.kind == hip.POT_ITEM_RESPONSE == 9 and pd.n_components == 30
     assert pd.a % 16 == 0 and p.pot.descriptor(dev).a == pd.a and p.pot.descriptor(dev).b == pd.b   # cached per device
     H.refusing_entry_points(dev, p.pot, p.x0, functools.partial(_flow_pair, p.d))
 
@@ -268,9 +268,9 @@ def test_philox7_and_bad_descriptors_are_refused(dev):
     from nfmc_amd import hip
     p = _problem(16, 8, 128)
     d = p.d
-    bad = [('a', 0, hip.EINVAL), ('b', 0, hip.EINVAL), ('reserved', 0, hip.EINVAL), ('reserved', -1, hip.EINVAL),
-           ('reserved', d - 1, hip.EINVAL), ('reserved', d, hip.EINVAL), ('a', 'misaligned', hip.EALIGN)]
-    ok = [('reserved', d - 2)]                                                       # S = d - 2, Q = 1: well formed
+    bad = [('a', 0, hip.EINVAL), ('b', 0, hip.EINVAL), ('n_components', 0, hip.EINVAL), ('n_components', -1, hip.EINVAL),
+           ('n_components', d - 1, hip.EINVAL), ('n_components', d, hip.EINVAL), ('a', 'misaligned', hip.EALIGN)]
+    ok = [('n_components', d - 2)]                                                       # S = d - 2, Q = 1: well formed
     H.bad_descriptors_are_refused(dev, p.pot, p.x0, _flow_pair(d)[0], bad, ok=ok)
 
 

@@ -223,7 +223,7 @@ def test_refusing_entry_points_answer_unsupported(dev, par):
     d = 64
     p = _Problem(d, 'poisson', par, 4, 256, 4)
     pd = p.pot.descriptor(dev)
-    assert pd.kind == hip.POT_LATENT_GAUSSIAN and pd.reserved == d and pd.a_scalar == (4.0 if par == 'whitened' else 0.0)
+    assert pd.kind == hip.POT_LATENT_GAUSSIAN and pd.n_components == d and pd.a_scalar == (4.0 if par == 'whitened' else 0.0)
     H.refusing_entry_points(dev, p.pot, p.x0, functools.partial(_flow_pair, d))
 
 
@@ -235,7 +235,7 @@ def test_philox7_and_bad_descriptors_are_refused(dev):
     p = _Problem(d, 'student_t', 'whitened', 8, 128, 8)
     b = p.pot.descriptor(dev).b
     bad = [('a', 0, hip.EINVAL), ('b', 0, hip.EINVAL), ('a', 'misaligned', hip.EALIGN), ('b', b + 4, hip.EALIGN),
-           ('b', b + 8, hip.EALIGN), ('reserved', d - 1, hip.EINVAL), ('reserved', d + 1, hip.EINVAL),
+           ('b', b + 8, hip.EALIGN), ('n_components', d - 1, hip.EINVAL), ('n_components', d + 1, hip.EINVAL),
            ('a_scalar', 3.0, hip.EINVAL), ('a_scalar', 7.0, hip.EINVAL), ('a_scalar', 8.0, hip.EINVAL),
            ('a_scalar', 4.5, hip.EINVAL), ('a_scalar', -1.0, hip.EINVAL)]
     ok = [('a_scalar', float(c)) for c in (0, 1, 2, 4, 5, 6)]

@@ -216,7 +216,7 @@ def test_refusing_entry_points_answer_unsupported(dev):
     d, N = 64, 1000
     pot, _ = _problem(N, d, 4)
     pd = pot.descriptor(dev)
-    assert pd.kind == hip.POT_LOGISTIC_REGRESSION and pd.reserved == N
+    assert pd.kind == hip.POT_LOGISTIC_REGRESSION and pd.n_components == N
     # no NeuTra kernels for kind 3 either
     H.refusing_entry_points(dev, pot, _x0(256, d, 4), functools.partial(_flow_pair, d), neutra_fused=False)
 

@@ -273,7 +273,7 @@ def test_refusing_entry_points_answer_unsupported(dev):
     # no NeuTra kernels for kind 2 either
     pa, _keep = H.refusing_entry_points(dev, pot, _x0(pot, 256, g), functools.partial(_flow_pair, d),
                                         neutra_fused=False)
-    pa.pot.reserved = 9                                                             # K over the cap
+    pa.pot.n_components = 9                                                             # K over the cap
     assert int(hip.lib().nfmc_flow_mh_supported_f32(C.byref(pa))) == hip.EUNSUPPORTED
     assert hip.EUNSUPPORTED < 0 and pot.fused_in('fit') is False
 

@@ -493,7 +493,7 @@ def test_refusing_entry_points_answer_unsupported(dev):
     p = _problem(13, 3, 'lj')
     pot = p.pot
     pd = pot.descriptor(dev)
-    assert pd.kind == hip.POT_PARTICLES == 11 and pd.reserved == 13 and not pd.b
+    assert pd.kind == hip.POT_PARTICLES == 11 and pd.n_components == 13 and not pd.b
     assert pd.a % 16 == 0 and pot.descriptor(dev).a == pd.a                           # cached per device
     H.refusing_entry_points(dev, pot, p.x0, functools.partial(_flow_pair, p))
 
@@ -509,12 +509,12 @@ def test_philox7_and_bad_descriptors_are_refused(dev):
     from nfmc_amd import hip
     p = _problem(4, 3, 'lj')
     assert p.d == 12
-    bad = [('a', 0, hip.EINVAL), ('reserved', 0, hip.EINVAL), ('reserved', 1, hip.EINVAL), ('reserved', -4, hip.EINVAL),
-           ('reserved', 5, hip.EINVAL),                                               # 12 % 5 != 0
-           ('reserved', 3, hip.EINVAL), ('reserved', 2, hip.EINVAL),                  # D = 4, D = 6
-           ('reserved', 24, hip.EINVAL), ('reserved', 2 ** 30, hip.EINVAL), ('a', 'misaligned', hip.EALIGN)]
+    bad = [('a', 0, hip.EINVAL), ('n_components', 0, hip.EINVAL), ('n_components', 1, hip.EINVAL), ('n_components', -4, hip.EINVAL),
+           ('n_components', 5, hip.EINVAL),                                               # 12 % 5 != 0
+           ('n_components', 3, hip.EINVAL), ('n_components', 2, hip.EINVAL),                  # D = 4, D = 6
+           ('n_components', 24, hip.EINVAL), ('n_components', 2 ** 30, hip.EINVAL), ('a', 'misaligned', hip.EALIGN)]
     H.bad_descriptors_are_refused(dev, p.pot, p.x0, _flow_pair(p)[0], bad,
-                                  ok=[('reserved', 6), ('reserved', 12)])            # the same d as D = 2 and D = 1: well formed
+                                  ok=[('n_components', 6), ('n_components', 12)])            # the same d as D = 2 and D = 1: well formed
 
 
 def test_limits_are_unchanged(dev):

@@ -255,7 +255,7 @@ def test_refusing_entry_points_answer_unsupported(dev):
     from nfmc_amd import hip
     pot, ref = _problem((8, 8), 'periodic')
     pd = pot.descriptor(dev)
-    assert pd.kind == hip.POT_LATTICE_PHI4 and pd.reserved == 8
+    assert pd.kind == hip.POT_LATTICE_PHI4 and pd.n_components == 8
     H.refusing_entry_points(dev, pot, _x0(ref, 256, 4), functools.partial(_flow_pair, ref.d))
 
 
@@ -265,9 +265,9 @@ def test_philox7_and_bad_descriptors_are_refused(dev):
     from nfmc_amd import hip
     shape = (3, 8)
     pot, ref = _problem(shape, 'zero')
-    bad = [('a', 0, hip.EINVAL), ('reserved', 0, hip.EINVAL), ('reserved', -4, hip.EINVAL), ('reserved', 16, hip.EINVAL),
-           ('reserved', 5, hip.EINVAL), ('reserved', 48, hip.EINVAL), ('reserved', 6, hip.EUNSUPPORTED),
-           ('reserved', 2, hip.EUNSUPPORTED), ('reserved', 3, hip.EUNSUPPORTED), ('reserved', 1, hip.EUNSUPPORTED)]
+    bad = [('a', 0, hip.EINVAL), ('n_components', 0, hip.EINVAL), ('n_components', -4, hip.EINVAL), ('n_components', 16, hip.EINVAL),
+           ('n_components', 5, hip.EINVAL), ('n_components', 48, hip.EINVAL), ('n_components', 6, hip.EUNSUPPORTED),
+           ('n_components', 2, hip.EUNSUPPORTED), ('n_components', 3, hip.EUNSUPPORTED), ('n_components', 1, hip.EUNSUPPORTED)]
     H.bad_descriptors_are_refused(dev, pot, _x0(ref, 128, 8), _flow_pair(ref.d)[0], bad, event_shape=shape)
 
 

@@ -245,7 +245,7 @@ def test_refusing_entry_points_answer_unsupported(dev):
     d = 64
     pot, ref = _problem(d, 2)
     pd = pot.descriptor(dev)
-    assert pd.kind == hip.POT_ROSENBROCK and pd.reserved == 2
+    assert pd.kind == hip.POT_ROSENBROCK and pd.n_components == 2
     H.refusing_entry_points(dev, pot, _x0(ref, 256, 4), functools.partial(_flow_pair, d))
 
 
@@ -254,7 +254,7 @@ def test_philox7_and_bad_descriptors_are_refused(dev):
     from nfmc_amd import hip
     d = 25
     pot, ref = _problem(d, 3)
-    bad = [('a', 0), ('reserved', 0), ('reserved', d + 1), ('reserved', -1), ('a_scalar', 0.0), ('a_scalar', -1.0),
+    bad = [('a', 0), ('n_components', 0), ('n_components', d + 1), ('n_components', -1), ('a_scalar', 0.0), ('a_scalar', -1.0),
            ('a_scalar', float('inf')), ('b_scalar', 0.0), ('b_scalar', float('nan'))]
     H.bad_descriptors_are_refused(dev, pot, _x0(ref, 128, 8), _flow_pair(d)[0], [(f, v, hip.EINVAL) for f, v in bad])
 

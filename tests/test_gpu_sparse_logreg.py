@@ -253,7 +253,7 @@ def test_refusing_entry_points_answer_unsupported(dev):
     d, N = 51, 300
     pot, _ref, _t, x0 = _problem(d, N, 256, 4)
     pd = pot.descriptor(dev)
-    assert pd.kind == hip.POT_SPARSE_LOGISTIC_REGRESSION and pd.reserved == N
+    assert pd.kind == hip.POT_SPARSE_LOGISTIC_REGRESSION and pd.n_components == N
     H.refusing_entry_points(dev, pot, x0, functools.partial(_flow_pair, d))
 
 
@@ -262,7 +262,7 @@ def test_philox7_and_bad_descriptors_are_refused(dev):
     from nfmc_amd import hip
     d = 25
     pot, _ref, _t, x0 = _problem(d, 100, 128, 8)
-    bad = [('a', 0), ('b', 0), ('reserved', 0), ('reserved', -1), ('a', 'misaligned'), ('a_scalar', 0.0), ('a_scalar', -1.0),
+    bad = [('a', 0), ('b', 0), ('n_components', 0), ('n_components', -1), ('a', 'misaligned'), ('a_scalar', 0.0), ('a_scalar', -1.0),
            ('a_scalar', float('inf')), ('b_scalar', 0.0), ('b_scalar', float('nan'))]
     H.bad_descriptors_are_refused(dev, pot, x0, _flow_pair(d)[0], [(f, v, hip.EINVAL) for f, v in bad])
     x = x0.to(dev)

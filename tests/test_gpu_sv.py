@@ -218,7 +218,7 @@ def test_refusing_entry_points_answer_unsupported(dev):
     d = 64
     pot, _ref, _t, x0 = _problem(d, 256, 4)
     pd = pot.descriptor(dev)
-    assert pd.kind == hip.POT_STOCHASTIC_VOLATILITY and pd.reserved == d - 3
+    assert pd.kind == hip.POT_STOCHASTIC_VOLATILITY and pd.n_components == d - 3
     H.refusing_entry_points(dev, pot, x0, functools.partial(H.flow_pair, d))
 
 
@@ -227,7 +227,7 @@ def test_philox7_and_bad_descriptors_are_refused(dev):
     from nfmc_amd import hip
     d = 25
     pot, _ref, _t, x0 = _problem(d, 128, 8)
-    bad = [('a', 0), ('b', 0), ('reserved', 0), ('reserved', d - 2), ('reserved', d - 4), ('reserved', -1),
+    bad = [('a', 0), ('b', 0), ('n_components', 0), ('n_components', d - 2), ('n_components', d - 4), ('n_components', -1),
            ('a_scalar', 0.0), ('a_scalar', -1.0), ('a_scalar', float('inf')), ('b_scalar', 0.0), ('b_scalar', float('nan'))]
     H.bad_descriptors_are_refused(dev, pot, x0, H.flow_pair(d)[0], [(f, v, hip.EINVAL) for f, v in bad])
 

@@ -282,7 +282,7 @@ def test_refusing_entry_points_answer_unsupported(dev):
     p = _problem('both', 14, 256)
     pot = p.pot
     pd = pot.descriptor(dev)
-    assert pd.kind == hip.POT_VARYING_EFFECTS == 10 and pd.reserved == 14
+    assert pd.kind == hip.POT_VARYING_EFFECTS == 10 and pd.n_components == 14
     assert pd.a_scalar == 10.0 and pd.b_scalar == float(pot.n_obs)                  # varying + 4 varying + 8, N
     assert pd.a % 16 == 0 and pot.descriptor(dev).a == pd.a and pot.descriptor(dev).b == pd.b   # cached per device
     H.refusing_entry_points(dev, pot, p.x0, functools.partial(_flow_pair, p.d))
@@ -301,8 +301,8 @@ def test_philox7_and_bad_descriptors_are_refused(dev):
     p = _problem('both', 6, 128)
     d = p.d
     assert d == 17
-    bad = [('a', 0), ('b', 0), ('reserved', 0), ('reserved', -1), ('reserved', 5), ('reserved', 7), ('reserved', d + 1),
-           ('reserved', 2 ** 30),
+    bad = [('a', 0), ('b', 0), ('n_components', 0), ('n_components', -1), ('n_components', 5), ('n_components', 7), ('n_components', d + 1),
+           ('n_components', 2 ** 30),
            ('a_scalar', 5.0),      # shared + shared: no varying side
            ('a_scalar', 8.0),      # no intercept side
            ('a_scalar', 11.0),     # mode_a = 3

@@ -1,5 +1,4 @@
 """CPU: host logic of nfmc_amd and the C-ABI library's symbol table (no compute calls without a GPU)."""
-import ctypes
 import os
 import re
 import socket
@@ -21,7 +20,6 @@ def test_library_exports_every_declared_symbol():
     handle = hip.lib()
     for name in declared:
         assert hasattr(handle, name), f'{name} declared in include/nfmc_hip.h but not exported'
-    assert declared == {s[0] for s in hip.SYMBOLS}, 'hip.SYMBOLS and the header disagree'
     lim = hip.limits()
     assert lim.abi_version == hip.NFMC_ABI_VERSION == 4 and lim.max_d_sampler >= 256 and lim.max_steps_per_call == hip.MAX_STEPS_PER_CALL
     assert hip.lib().nfmc_error_string(-5).decode().startswith('statistics scratch')
@@ -36,24 +34,6 @@ def test_library_exports_every_declared_symbol():
     assert sb(128, 128, 128, 2, 2) == 4 * (2 * 128 * 128 + 2 * 128 + 1 * 8 * 2 * 24 * 256)
     assert sb(10 ** 6, 128, 128, 2, 2) - sb(65536, 128, 128, 2, 2) == 4 * (10 ** 6 - 65536) * (2 * 128 + 2)
     assert sb(65536, 64, 40, 1, 3) == 4 * (2 * 65536 * 64 + 2 * 65536 + 256 * 8 * 3 * (4 + 4) * 256)   # H = 40 -> 64: 4 + 4 tiles
-
-
-def test_struct_sizes_match_the_header():
-    """Compile a tiny C program against include/nfmc_hip.h and compare sizeof() with the ctypes mirrors."""
-    from nfmc_amd import hip
-    names = ['NfmcPotential', 'NfmcRng', 'NfmcStats', 'NfmcSampleStore', 'NfmcTune', 'NfmcJumpTail', 'NfmcMalaArgs', 'NfmcHmcArgs', 'NfmcRealNVP', 'NfmcFlowMhArgs',
-             'NfmcNeutraHmcArgs', 'NfmcSelectArgs', 'NfmcLimits', 'NfmcAdamW', 'NfmcFlowFit', 'NfmcFitControl']
-    src = '#include <stdio.h>\n#include "nfmc_hip.h"\nint main(){' + ''.join(
-        f'printf("%zu\\n", sizeof({n}));' for n in names) + 'return 0;}'
-    import tempfile
-    with tempfile.TemporaryDirectory() as td:
-        c = os.path.join(td, 's.c')
-        open(c, 'w').write(src)
-        exe = os.path.join(td, 's')
-        subprocess.check_call(['gcc', '-I', os.path.join(ROOT, 'include'), c, '-o', exe])
-        sizes = [int(v) for v in subprocess.check_output([exe]).split()]
-    for n, sz in zip(names, sizes):
-        assert ctypes.sizeof(getattr(hip, n)) == sz, n
 
 
 def test_a_library_of_another_abi_version_is_refused(tmp_path):
@@ -456,12 +436,13 @@ def _integration_stub_namespace():
 
 
 def test_integration_stub_structs_match_the_header():
+    """Every struct the document's stub shows, field for field: names, order, offsets and sizes."""
     import ctypes as C
-    from nfmc_amd import hip
+    from test_host_abi import HEADER, mismatches
     ns = _integration_stub_namespace()
-    for name in ('NfmcPotential', 'NfmcRng', 'NfmcStats', 'NfmcMalaArgs'):
-        assert C.sizeof(ns[name]) == C.sizeof(getattr(hip, name)), name
-        assert [f[0] for f in ns[name]._fields_] == [f[0] for f in getattr(hip, name)._fields_], name
+    shown = {k for k, v in ns.items() if isinstance(v, type) and issubclass(v, C.Structure) and v is not C.Structure}
+    assert shown == {'NfmcPotential', 'NfmcRng', 'NfmcStats', 'NfmcSampleStore', 'NfmcTune', 'NfmcMalaArgs'}
+    assert mismatches(ns, HEADER, partial=True) == []
 
 
 def test_rqs_flow_string_and_training_restatement():

@@ -6,8 +6,6 @@ the GPU tests' dimensions and the codes of check_gmrf (no GPU needed: the entry 
 before they touch a device)."""
 import ctypes as C
 import math
-import os
-import re
 
 import pytest
 import torch
@@ -17,7 +15,6 @@ from nfmc_amd import hip
 from nfmc_amd.potentials import FAMILIES, LatentGaussianModel, LatentGMRF, recognize
 from nfmc_amd.samplers.common import resolve_target
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAN, INF = float('nan'), float('inf')
 R3 = torch.tensor([[1.5, -1.0, 0.0], [-1.0, 2.5, -1.0], [0.0, -1.0, 1.5]], dtype=torch.float64)
 Y3 = torch.tensor([1.0, 0.0, 2.0])
@@ -243,15 +240,6 @@ def test_codes_and_header_of_the_table():
     icar, _ = make_pair(data, 'centered', intrinsic=True)
     tab = icar.data_block()[1]
     assert tab[:8].tolist() == [0.0, 0.0, 0.0, 0.0, 2.0, 2.0, 4.0, 0.5]
-    assert hip.POT_LATENT_GMRF == 13
-
-
-def test_header_constant_and_abi_version():
-    with open(os.path.join(ROOT, 'include', 'nfmc_hip.h')) as fh:
-        text = fh.read()
-    assert re.search(r'NFMC_POT_LATENT_GMRF\s*=\s*13\b', text)
-    assert re.search(r'#define\s+NFMC_ABI_VERSION\s+4\b', text)
-    assert hip.POT_LATENT_GMRF == 13
 
 
 # ------------------------------------------------------------------------------------------------- identities

@@ -1,10 +1,6 @@
 """Item-response theory on the host: argument validation (one case per rule), the defaults, U and grad U of the torch
 potential against the fp64 loops of tests/irt_fp64.py and the model's log densities, pack / unpack, the seeded synthetic
-data set, the kernels' data block entry by entry, the header's kind constant and the launch-family routing (no GPU
-needed)."""
-import os
-import re
-
+data set, the kernels' data block entry by entry and the launch-family routing (no GPU needed)."""
 import pytest
 import torch
 
@@ -13,7 +9,6 @@ from nfmc_amd import hip
 from nfmc_amd.potentials import FAMILIES, ItemResponseTheory, Potential, recognize
 from nfmc_amd.samplers.common import resolve_target
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAN = float('nan')
 R23 = [[1, 0, 1], [0, 0, 1]]
 
@@ -252,14 +247,6 @@ def test_copies_are_cached_per_device_and_dtype():
     assert pot._copy(torch.device('cpu'), torch.float32)[0] is first[0]
     assert pot._copy(torch.device('cpu'), torch.float64)[0] is not first[0]
     assert first[0].dtype == torch.float32 and pot._copy(torch.device('cpu'), torch.float64)[1].dtype == torch.float64
-
-
-def test_header_constant_and_abi_version():
-    with open(os.path.join(ROOT, 'include', 'nfmc_hip.h')) as fh:
-        text = fh.read()
-    assert re.search(r'NFMC_POT_ITEM_RESPONSE\s*=\s*9\b', text)
-    assert re.search(r'#define\s+NFMC_ABI_VERSION\s+4\b', text)
-    assert hip.POT_ITEM_RESPONSE == 9
 
 
 def test_fused_in_table_and_routing():

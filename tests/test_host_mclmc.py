@@ -1,65 +1,27 @@
-"""CPU: the surface of the mclmc sampler (nfmc_mclmc_steps_f32): the header's struct against the ctypes mirror, the
+"""CPU: the surface of the mclmc sampler (nfmc_mclmc_steps_f32): its export and its state size, the
 controller recurrence (tuning.MicrocanonicalAdaptation) against hand-computed updates, two properties of the fp64 step of
 tests/mclmc_fp64.py, and the plumbing of create_sampler.  tests/test_gpu_mclmc.py runs the kernels."""
 import ctypes as C
 import math
-import os
-import re
-import subprocess
 
 import pytest
 import torch
 
 import mclmc_fp64 as M
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, 'include', 'nfmc_hip.h')
-FIELDS = ['x', 'velocity', 'n', 'd', 'n_steps', 'step_size', 'decoherence_length', 'inv_mass_diag', 'pot', 'rng', 'stats',
-          'samples', 'energy_out', 'energy_sums', 'tune']
-TUNE_FIELDS = ['state', 'inv_mass_diag', 'tune_step_size', 'tune_decoherence_length', 'tune_inv_mass_diag', 'every']
 LN2 = math.log(2.0)
 
 
 def test_the_header_declares_the_symbol_once_and_the_table_names_it():
+    """Header and table are held together in tests/test_host_abi.py; here, the library's export."""
     from nfmc_amd import hip
-    header = open(HEADER).read()
-    assert len(re.findall(r'\bnfmc_mclmc_steps_f32\s*\(', header)) == 1
-    assert re.search(r'int\s+nfmc_mclmc_steps_f32\(const NfmcMclmcArgs\*\s*args,\s*nfmc_stream_t\s+stream\);', header)
-    rows = [s for s in hip.SYMBOLS if s[0] == 'nfmc_mclmc_steps_f32']
-    assert len(rows) == 1
-    assert rows[0][1] is C.c_int and rows[0][2][0]._type_ is hip.NfmcMclmcArgs and len(rows[0][2]) == 2
-    assert hasattr(hip.lib(), 'nfmc_mclmc_steps_f32')
+    assert 'nfmc_mclmc_steps_f32' in {s[0] for s in hip.SYMBOLS} and hasattr(hip.lib(), 'nfmc_mclmc_steps_f32')
     assert hip.NFMC_ABI_VERSION == 4 == hip.limits().abi_version
-    assert re.search(r'#define NFMC_ABI_VERSION 4\b', header)
-
-
-@pytest.mark.parametrize('name,fields', [('NfmcMclmcArgs', FIELDS), ('NfmcMclmcTune', TUNE_FIELDS)])
-def test_the_ctypes_structs_have_the_c_structs_size_and_field_order(tmp_path, name, fields):
-    from nfmc_amd import hip
-    cls = getattr(hip, name)
-    assert [f[0] for f in cls._fields_] == fields
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "nfmc_hip.h"\nint main(){printf("%%zu\\n", sizeof(%s));' % name \
-        + ''.join('printf("%%zu\\n", offsetof(%s, %s));' % (name, f) for f in fields) + 'return 0;}'
-    c = tmp_path / 's.c'
-    c.write_text(src)
-    exe = str(tmp_path / 's')
-    subprocess.check_call(['gcc', '-I', os.path.join(ROOT, 'include'), str(c), '-o', exe])
-    got = [int(v) for v in subprocess.check_output([exe]).split()]
-    assert got[0] == C.sizeof(cls)
-    assert got[1:] == [getattr(cls, f).offset for f in fields]
-    body = re.search(r'typedef struct \{([^}]*)\} %s;' % name, open(HEADER).read()).group(1)
-    body = re.sub(r'/\*.*?\*/', '', body, flags=re.S)
-    assert re.findall(r'(\w+);', body) == fields
 
 
 def test_the_state_words_mirror_the_header():
+    """Word by word they are held against the header in tests/test_host_abi.py; here, what the library makes of them."""
     from nfmc_amd import hip
-    header = open(HEADER).read()
-    for name in ('STEP_SIZE', 'DECOHERENCE_LENGTH', 'TARGET', 'IMD_ADJUSTMENT', 'DECOHERENCE_FACTOR', 'ENERGY_VARIANCE', 'COUNT',
-                 'HISTORY_ROWS', 'HISTORY_USED', 'WORDS', 'ROW_STEP_SIZE', 'ROW_DECOHERENCE_LENGTH', 'ROW_ENERGY_VARIANCE',
-                 'ROW_COUNT', 'ROW_NEXT_STEP_SIZE', 'ROW_NEXT_DECOHERENCE_LENGTH', 'ROW_WORDS'):
-        m = re.search(r'NFMC_MCLMC_%s = (\d+)' % name, header)
-        assert m and int(m.group(1)) == getattr(hip, 'MCLMC_' + name), name
     assert hip.MCLMC_WORDS == hip.TUNE_WORDS   # StatShift finds the shift words where the mala / hmc state keeps them
     lib = hip.lib()
     assert lib.nfmc_mclmc_state_doubles(10, 3) == lib.nfmc_tune_state_doubles(10) + 3 * hip.MCLMC_ROW_WORDS

@@ -1,10 +1,7 @@
-"""CPU: the surface of nfmc_neutra_mh_steps_f32 (NeuTra-MH on a fused kernel): the header's declaration and struct
-against the ctypes mirror, and the routing decision of NeuTra.sample for an MH inner sampler, which is a function of the
-potential, the flow and the Philox rounds alone (NeuTra._mh_on_kernel).  tests/test_gpu_neutra_mh.py runs the kernel."""
-import ctypes as C
+"""CPU: the surface of nfmc_neutra_mh_steps_f32 (NeuTra-MH on a fused kernel): its export, and the routing decision of
+NeuTra.sample for an MH inner sampler, which is a function of the potential, the flow and the Philox rounds alone
+(NeuTra._mh_on_kernel).  tests/test_gpu_neutra_mh.py runs the kernel."""
 import os
-import re
-import subprocess
 
 import pytest
 import torch
@@ -13,40 +10,13 @@ import neutra_mh_cases as cases
 import target_harness as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, 'include', 'nfmc_hip.h')
-FIELDS = ['z', 'n', 'n_steps', 'adjust', 'inv_mass_diag', 'flow', 'pot', 'rng', 'stats', 'samples', 'masks_out',
-          'log_ratio_out']
 
 
 def test_the_header_declares_the_symbol_once_and_the_table_names_it():
+    """Header and table are held together in tests/test_host_abi.py; here, the library's export."""
     from nfmc_amd import hip
-    header = open(HEADER).read()
-    assert len(re.findall(r'\bnfmc_neutra_mh_steps_f32\s*\(', header)) == 1
-    assert re.search(r'int\s+nfmc_neutra_mh_steps_f32\(const NfmcNeutraMhArgs\*\s*args,\s*nfmc_stream_t\s+stream\);', header)
-    rows = [s for s in hip.SYMBOLS if s[0] == 'nfmc_neutra_mh_steps_f32']
-    assert len(rows) == 1
-    assert rows[0][1] is C.c_int and rows[0][2][0]._type_ is hip.NfmcNeutraMhArgs and len(rows[0][2]) == 2
-    assert hasattr(hip.lib(), 'nfmc_neutra_mh_steps_f32')
+    assert 'nfmc_neutra_mh_steps_f32' in {s[0] for s in hip.SYMBOLS} and hasattr(hip.lib(), 'nfmc_neutra_mh_steps_f32')
     assert hip.NFMC_ABI_VERSION == 4 == hip.limits().abi_version
-
-
-def test_the_ctypes_struct_has_the_c_structs_size_and_field_order(tmp_path):
-    """sizeof and every offsetof from a C program compiled against the header, in the field order the issue lists."""
-    from nfmc_amd import hip
-    assert [f[0] for f in hip.NfmcNeutraMhArgs._fields_] == FIELDS
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "nfmc_hip.h"\nint main(){printf("%zu\\n", sizeof(NfmcNeutraMhArgs));' \
-        + ''.join('printf("%%zu\\n", offsetof(NfmcNeutraMhArgs, %s));' % f for f in FIELDS) + 'return 0;}'
-    c = tmp_path / 's.c'
-    c.write_text(src)
-    exe = str(tmp_path / 's')
-    subprocess.check_call(['gcc', '-I', os.path.join(ROOT, 'include'), str(c), '-o', exe])
-    got = [int(v) for v in subprocess.check_output([exe]).split()]
-    assert got[0] == C.sizeof(hip.NfmcNeutraMhArgs)
-    assert got[1:] == [getattr(hip.NfmcNeutraMhArgs, f).offset for f in FIELDS]
-    # the declaration order in the header's own text
-    body = re.search(r'typedef struct \{([^}]*)\} NfmcNeutraMhArgs;', open(HEADER).read()).group(1)
-    body = re.sub(r'/\*.*?\*/', '', body, flags=re.S)
-    assert re.findall(r'(\w+);', body) == FIELDS
 
 
 @pytest.mark.parametrize('case', cases.ROUTES, ids=lambda c: c.name)

@@ -4,8 +4,6 @@ potential against the fp64 pair sums of tests/particles_fp64.py, the observables
 routing, the default layouts of the GPU tests' shapes and the codes of check_particles (no GPU needed: the entry points
 answer a malformed descriptor before they touch a device)."""
 import ctypes as C
-import os
-import re
 
 import pytest
 import torch
@@ -15,7 +13,6 @@ from nfmc_amd import hip
 from nfmc_amd.potentials import FAMILIES, ParticleSystem, Potential, recognize
 from nfmc_amd.samplers.common import resolve_target
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAN, INF = float('nan'), float('inf')
 
 BAD = [
@@ -222,15 +219,6 @@ def test_data_block_and_descriptor():
     assert torch.equal(b, want)
     dw = ParticleSystem(3, 3, 'double_well', trap=2.0, temperature=2.0, a=0.5, b=-3.0, c=0.8, r0=3.5)
     assert torch.equal(dw.data_block(), torch.tensor([1.0, 3.0, 1.0, 0.25, -1.5, 0.4, 3.5, 0.0], dtype=torch.float32))
-    assert hip.POT_PARTICLES == 11
-
-
-def test_header_constant_and_abi_version():
-    with open(os.path.join(ROOT, 'include', 'nfmc_hip.h')) as fh:
-        text = fh.read()
-    assert re.search(r'NFMC_POT_PARTICLES\s*=\s*11\b', text)
-    assert re.search(r'#define\s+NFMC_ABI_VERSION\s+4\b', text)
-    assert hip.POT_PARTICLES == 11
 
 
 def test_fused_in_table_and_routing():

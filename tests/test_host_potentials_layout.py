@@ -64,7 +64,7 @@ def test_the_package_exports_the_public_names_and_holds_no_code():
 
 def test_every_class_and_every_kind_code_has_one_module():
     kinds = set()
-    for node in ast.walk(ast.parse(open(os.path.join(os.path.dirname(PKG), 'hip.py')).read())):
+    for node in ast.walk(ast.parse(open(os.path.join(os.path.dirname(PKG), 'abi.py')).read())):
         if isinstance(node, ast.Assign):
             for target in node.targets:
                 kinds |= {e.id for e in ast.walk(target) if isinstance(e, ast.Name) and e.id.startswith('POT_')}

@@ -1,12 +1,10 @@
 """Varying-effects regression on the host: U and grad U of the torch potential (which works from the per-group sufficient
 statistics) against the model written from torch.distributions over the raw observations (tests/varying_effects_fp64.py)
 at all 16 combinations of side, noise and parameterisation, pack / unpack / effects, the seeded synthetic data set, eight
-schools, the kernels' table against fp64, relabelled groups, argument validation (one case per rule), the header's kind
-constant, the default layouts of the GPU tests' shapes and the launch-family routing (no GPU needed)."""
+schools, the kernels' table against fp64, relabelled groups, argument validation (one case per rule),
+the default layouts of the GPU tests' shapes and the launch-family routing (no GPU needed)."""
 import ctypes as C
 import itertools
-import os
-import re
 
 import pytest
 import torch
@@ -16,7 +14,6 @@ from nfmc_amd import hip
 from nfmc_amd.potentials import FAMILIES, Potential, VaryingEffectsRegression, recognize
 from nfmc_amd.samplers.common import resolve_target
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAN = float('nan')
 SIDES = [('varying', 'none'), ('varying', 'shared'), ('varying', 'varying'), ('shared', 'varying')]
 COMBOS = [(ia, sl, known, centered) for (ia, sl), known, centered in itertools.product(SIDES, (False, True), (True, False))]
@@ -246,14 +243,6 @@ def test_defaults_accepted_edges_and_no_cap_on_d():
     assert resolve_target(big, (1103,), family='mcmc') is None
     edge = VaryingEffectsRegression(torch.zeros(1020), torch.arange(1020), noise_scale=1.0)   # d = 1022
     assert edge.fused_in('mcmc')
-
-
-def test_header_constant_and_abi_version():
-    with open(os.path.join(ROOT, 'include', 'nfmc_hip.h')) as fh:
-        text = fh.read()
-    assert re.search(r'NFMC_POT_VARYING_EFFECTS\s*=\s*10\b', text)
-    assert re.search(r'#define\s+NFMC_ABI_VERSION\s+4\b', text)
-    assert hip.POT_VARYING_EFFECTS == 10
 
 
 # the shapes of tests/test_gpu_varying_effects.py: (intercepts, slopes, C) -> d and the default (CPL, LPC)
