@@ -368,6 +368,24 @@ struct StoreCursor {
         return p;
     }
 };
+// the same rule on the host, for the entry points that launch once per transition and hand each launch its row
+struct HostStoreCursor {
+    float* base;
+    int stride, countdown, ring, row;
+    explicit HostStoreCursor(const NfmcSampleStore& s)
+        : base(s.base), stride(s.stride), countdown(s.countdown), ring(s.ring_rows), row(s.row) {}
+    float* next(int64_t nd) {
+        if (!base) return nullptr;
+        if (countdown > 0) {
+            --countdown;
+            return nullptr;
+        }
+        float* p = base + (int64_t)row * nd;
+        row = row + 1 == ring ? 0 : row + 1;
+        countdown = stride - 1;
+        return p;
+    }
+};
 // the same for transition t of the call, out of order (the data-parallel IMH replay writes runs of equal states)
 __device__ __forceinline__ float* store_row_of(const NfmcSampleStore& s, int t, int64_t nd) {
     const int k = t - s.countdown;

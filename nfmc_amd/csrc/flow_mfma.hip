@@ -282,23 +282,12 @@ static int launch_flow_mh(const NfmcFlowMhArgs& a, int64_t tiles, int grid, int 
 
 using namespace nfmc;
 
-#define NFMC_FLOW_MFMA_DISPATCH(TDV, THV, NHLV, CALL)                                   \
-    if (TDV == 4 && THV == 4 && NHLV == 1) { constexpr int TD = 4, TH = 4, NHL = 1; CALL; }      \
-    else if (TDV == 4 && THV == 4 && NHLV == 2) { constexpr int TD = 4, TH = 4, NHL = 2; CALL; } \
-    else if (TDV == 4 && THV == 8 && NHLV == 1) { constexpr int TD = 4, TH = 8, NHL = 1; CALL; } \
-    else if (TDV == 4 && THV == 8 && NHLV == 2) { constexpr int TD = 4, TH = 8, NHL = 2; CALL; } \
-    else if (TDV == 8 && THV == 4 && NHLV == 1) { constexpr int TD = 8, TH = 4, NHL = 1; CALL; } \
-    else if (TDV == 8 && THV == 4 && NHLV == 2) { constexpr int TD = 8, TH = 4, NHL = 2; CALL; } \
-    else if (TDV == 8 && THV == 8 && NHLV == 1) { constexpr int TD = 8, TH = 8, NHL = 1; CALL; } \
-    else if (TDV == 8 && THV == 8 && NHLV == 2) { constexpr int TD = 8, TH = 8, NHL = 2; CALL; } \
-    else return NFMC_EUNSUPPORTED;
-
 int nfmc::nfmc_realnvp_forward_mfma_f32(const NfmcRealNVP* f, const float* x, int64_t n, float* z, float* logdet,
                                         float* log_prob, nfmc_stream_t stream) {
     const int td = f->d / 16, th = nfmc_realnvp_padded_hidden(f->n_hidden) / 16, nhl = f->n_hidden_layers;
     const int64_t tiles = (n + kMfmaChains - 1) / kMfmaChains;
     int rc = 0;
-    NFMC_FLOW_MFMA_DISPATCH(td, th, nhl, rc = (launch_forward<TD, TH, NHL>(*f, x, n, z, logdet, log_prob, tiles, (hipStream_t)stream)))
+    NFMC_MFMA_DISPATCH(td, th, nhl, rc = (launch_forward<TD, TH, NHL>(*f, x, n, z, logdet, log_prob, tiles, (hipStream_t)stream)))
     if (rc) return rc;
     NFMC_HIP_CHECK_LAUNCH();
     return NFMC_OK;
@@ -311,7 +300,7 @@ int nfmc::nfmc_realnvp_inverse_mfma_f32(const NfmcRealNVP* f, const float* z, in
     NfmcRng r = {};
     if (rng) r = *rng;
     int rc = 0;
-    NFMC_FLOW_MFMA_DISPATCH(td, th, nhl, rc = (launch_inverse<TD, TH, NHL>(*f, z, n, x, logdet, log_q, r, tiles, (hipStream_t)stream)))
+    NFMC_MFMA_DISPATCH(td, th, nhl, rc = (launch_inverse<TD, TH, NHL>(*f, z, n, x, logdet, log_q, r, tiles, (hipStream_t)stream)))
     if (rc) return rc;
     NFMC_HIP_CHECK_LAUNCH();
     return NFMC_OK;
@@ -326,7 +315,7 @@ int nfmc::nfmc_flow_mh_steps_mfma_f32(const NfmcFlowMhArgs& a, nfmc_stream_t str
         return NFMC_ESCRATCH;
     if (check_defer(a.stats, dp, d)) return NFMC_EINVAL;
     int rc = 0;
-    NFMC_FLOW_MFMA_DISPATCH(td, th, nhl, rc = (launch_flow_mh<TD, TH, NHL>(a, tiles, grid, dp, (hipStream_t)stream)))
+    NFMC_MFMA_DISPATCH(td, th, nhl, rc = (launch_flow_mh<TD, TH, NHL>(a, tiles, grid, dp, (hipStream_t)stream)))
     if (rc) return rc;
     *grid_out = grid;
     *dp_out = dp;

@@ -297,3 +297,16 @@ __device__ __forceinline__ float potential_value_grad_c(const f32x4 (&x)[TD], f3
 }
 
 }  // namespace nfmc
+
+// The register-resident kernels are instantiated at (TD, TH, NHL) = (d / 16, padded hidden width / 16, hidden layers): CALL
+// with those as constants for the run-time values, or NFMC_EUNSUPPORTED from the calling entry point.
+#define NFMC_MFMA_DISPATCH(TDV, THV, NHLV, CALL)                                                  \
+    if (TDV == 4 && THV == 4 && NHLV == 1) { constexpr int TD = 4, TH = 4, NHL = 1; CALL; }      \
+    else if (TDV == 4 && THV == 4 && NHLV == 2) { constexpr int TD = 4, TH = 4, NHL = 2; CALL; } \
+    else if (TDV == 4 && THV == 8 && NHLV == 1) { constexpr int TD = 4, TH = 8, NHL = 1; CALL; } \
+    else if (TDV == 4 && THV == 8 && NHLV == 2) { constexpr int TD = 4, TH = 8, NHL = 2; CALL; } \
+    else if (TDV == 8 && THV == 4 && NHLV == 1) { constexpr int TD = 8, TH = 4, NHL = 1; CALL; } \
+    else if (TDV == 8 && THV == 4 && NHLV == 2) { constexpr int TD = 8, TH = 4, NHL = 2; CALL; } \
+    else if (TDV == 8 && THV == 8 && NHLV == 1) { constexpr int TD = 8, TH = 8, NHL = 1; CALL; } \
+    else if (TDV == 8 && THV == 8 && NHLV == 2) { constexpr int TD = 8, TH = 8, NHL = 2; CALL; } \
+    else return NFMC_EUNSUPPORTED;

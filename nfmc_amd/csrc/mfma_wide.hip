@@ -24,6 +24,15 @@
 // MFMAs.  Round 4: 0.756 -> 0.745 ms for the d = 256 gradient, 0.279 -> 0.272 ms forward, 0.503 -> 0.480 ms for the d = 512
 // inverse -- as in the register-resident kernels, the barriers were not the main loss.  The reverse sweep recomputes the
 // hidden stack (no checkpoints).
+//
+// Layout of the unit.  GEMM level: stage_any, wide_hidden, wide_coupling, wide_coupling_backward, wide_ea.  Stages, one
+// definition each, which the five kernels compose: wide_forward_sweep / wide_inverse_sweep, wide_potential<GRAD>,
+// wide_adjusted_grad (U~ and its gradient on the slab), wide_normal4 / wide_accept_uniform (the draws, native or replayed),
+// wide_stats_tile / _flush / _tail (per-transition statistics), wide_store_tile / wide_store_row (slab -> (n, d) arrays),
+// wide_slab_row / wide_chain_row (a lane's slab rows, its chain of a chain tile).  Host: WidePlan (tiles, grid, checked slab).
+// Two places keep a stage written out, because the kernel measured slower through the helpers (DESIGN.md has the figures):
+// the momentum draw of neutra_leapfrog_wide_kernel, and flow_mh_wide_kernel, which takes wide_potential and
+// wide_accept_uniform only -- with those two its device code is the same as before the stages were shared.
 #include "mfma_flow.hpp"
 
 namespace nfmc {
@@ -151,14 +160,38 @@ __device__ __forceinline__ float wide_sum_squares(const WideCtx& c) {
     return chain_sum(ss);
 }
 
-// slab row -> (n, d) array; `rev`: the array is in LOGICAL latent order and tile position p holds logical d - 1 - p
+// the lane's four values at tile positions p0 .. p0 + 3 -> a row of an (n, d) array; `rev`: the array is in LOGICAL latent
+// order and tile position p holds logical d - 1 - p
+__device__ __forceinline__ void wide_store_tile(float* dst_row, int d, int p0, const f32x4 v, bool rev) {
+    if (!rev) *reinterpret_cast<f32x4*>(dst_row + p0) = v;
+    else *reinterpret_cast<f32x4*>(dst_row + (d - 4 - p0)) = rev4(v);
+}
+// a whole slab row -> its row of the array
 __device__ __forceinline__ void wide_store_row(const float* src, float* __restrict__ dst_row, int d, int q, bool rev) {
     wide_tiles(d / 16, [&](int m) { return tile_ld(src, m); },
-               [&](int m, const f32x4& v) {
-                   const int p0 = 16 * m + 4 * q;
-                   if (!rev) *reinterpret_cast<f32x4*>(dst_row + p0) = v;
-                   else *reinterpret_cast<f32x4*>(dst_row + (d - 4 - p0)) = rev4(v);
-               });
+               [&](int m, const f32x4& v) { wide_store_tile(dst_row, d, 16 * m + 4 * q, v, rev); });
+}
+
+// A lane group's private slab rows belong to the workgroup SLOT, not to the chain: the next chain tile of the grid-stride
+// loop reuses them (a tile's results have left for the output arrays by then), so the slab is bounded by the grid.  The
+// slab holds grid * 128 rows of d floats per copy (state; gradient or current state; momentum), in tile-position order:
+// this lane's four floats of tile 0 in the slot's row of copy `copy`.
+__device__ __forceinline__ float* wide_slab_row(const WideCtx& c, float* slab, int copy, int wave) {
+    const int64_t srow = (int64_t)blockIdx.x * kMfmaChains + wave * 16 + c.col;
+    return slab + ((int64_t)copy * gridDim.x * kMfmaChains + srow) * c.d + 4 * c.q;
+}
+// The lane's chain in chain tile `tile`: lanes past n in the last tile run on a copy of row n - 1 (`rrow`: the row to READ)
+// and write nothing (`active`).
+struct WideRow {
+    int64_t row, rrow;
+    bool active;
+};
+__device__ __forceinline__ WideRow wide_chain_row(const WideCtx& c, int64_t tile, int wave, int64_t n) {
+    WideRow r;
+    r.row = tile * kMfmaChains + wave * 16 + c.col;
+    r.active = r.row < n;
+    r.rrow = r.active ? r.row : n - 1;
+    return r;
 }
 
 // h1 = tanh(W1 x_src + b1), hl = the last hidden layer's activations (h1 itself with one hidden layer)
@@ -406,12 +439,14 @@ __device__ __forceinline__ float wide_ea(const WideCtx& c, const float* __restri
     return ld;
 }
 
-// closed-form potential and its gradient on the streamed state (potential_value_grad_c's arithmetic, tile by tile)
-__device__ __forceinline__ float wide_potential_grad(const WideCtx& c, const NfmcPotential& p, int lane) {
+// closed-form potential of the streamed row `row` (a slab row: x-space, tile position = coordinate) and, GRAD, its
+// gradient into the gradient slab (potential_value_c's / potential_value_grad_c's arithmetic, tile by tile)
+template <bool GRAD>
+__device__ __forceinline__ float wide_potential(const WideCtx& c, const float* row, const NfmcPotential& p, int lane) {
     const int TD = c.d / 16;
-    auto xtile = [&](int m) { return tile_ld(c.xs, m); };
+    auto xtile = [&](int m) { return tile_ld(row, m); };
     if (p.kind == NFMC_POT_FUNNEL) {
-        const f32x4 t0 = tile_ld(c.xs, 0);
+        const f32x4 t0 = tile_ld(row, 0);
         const float x0 = __shfl(t0[0], lane & 15, kWave);   // coordinate 0 = tile 0, register 0, lane group 0
         float s = 0.f;
         wide_tiles(TD, xtile, [&](int m, const f32x4& x) {
@@ -422,13 +457,14 @@ __device__ __forceinline__ float wide_potential_grad(const WideCtx& c, const Nfm
         const float inv_s2 = 1.f / (p.a_scalar * p.a_scalar);
         const float e = fast_exp(-x0);
         const float hd = 0.5f * (float)(c.d - 1);
-        wide_tiles(TD, xtile, [&](int m, const f32x4& x) {
-            f32x4 g;
+        if constexpr (GRAD)
+            wide_tiles(TD, xtile, [&](int m, const f32x4& x) {
+                f32x4 g;
 #pragma unroll
-            for (int t = 0; t < 4; ++t) g[t] = x[t] * e;
-            if (m == 0 && c.q == 0) g[0] = x0 * inv_s2 - 0.5f * e * s + hd;
-            tile_st(c.gs, m, g);
-        });
+                for (int t = 0; t < 4; ++t) g[t] = x[t] * e;
+                if (m == 0 && c.q == 0) g[0] = x0 * inv_s2 - 0.5f * e * s + hd;
+                tile_st(c.gs, m, g);
+            });
         return 0.5f * x0 * x0 * inv_s2 + 0.5f * e * s + hd * x0;
     }
     float u = 0.f;
@@ -448,88 +484,194 @@ __device__ __forceinline__ float wide_potential_grad(const WideCtx& c, const Nfm
             u = fmaf(a[t] * dlt, dlt, u);
             g[t] = 2.f * a[t] * dlt;
         }
-        tile_st(c.gs, m, g);
+        if constexpr (GRAD) tile_st(c.gs, m, g);
     });
     return chain_sum(u);
 }
 
-// slab: (grid * 128) private rows of d floats for the state, then as many for the gradient, one row per lane group of a
-// workgroup slot (lanes past n in the last tile run on a copy of row n - 1 and are never read)
+// ---- x -> z on the streamed state (z left at tile positions in latent order) and z -> x: the counterparts of
+// flow_forward_sweep_c / flow_inverse_sweep_c.  Each returns this lane's share of the logdet in ITS direction; `rev_last`:
+// the flow has an odd number of reversals, so EA1 (which acts on logical latent coordinates) sees position p as d - 1 - p.
+template <int TH, int NHL, int SB>
+__device__ __forceinline__ float wide_forward_sweep(const WideCtx& c, const NfmcRealNVP& f, bool rev_last) {
+    float ldp = wide_ea<kEaForward>(c, f.ea0_log_scale, f.ea0_shift, false);
+    for (int l = 0; l < f.n_coupling; ++l)
+        ldp += wide_coupling<TH, NHL, false, SB>(c, mfma_layer(f.weights + l * f.layer_stride, f.d, 16 * TH, NHL), (l & 1) == 0);
+    ldp += wide_ea<kEaForward>(c, f.ea1_log_scale, f.ea1_shift, rev_last);
+    return ldp;
+}
+template <int TH, int NHL, int SB>
+__device__ __forceinline__ float wide_inverse_sweep(const WideCtx& c, const NfmcRealNVP& f, bool rev_last) {
+    float ldp = wide_ea<kEaInverse>(c, f.ea1_log_scale, f.ea1_shift, rev_last);
+    for (int l = f.n_coupling - 1; l >= 0; --l)
+        ldp += wide_coupling<TH, NHL, true, SB>(c, mfma_layer(f.weights + l * f.layer_stride, f.d, 16 * TH, NHL), (l & 1) == 0);
+    ldp += wide_ea<kEaInverse>(c, f.ea0_log_scale, f.ea0_shift, false);
+    return ldp;
+}
+
+// ---- the adjusted potential U~(z) = U(f^-1(z)) - logdet_inv(z) of the z in the state slab (tile positions in latent
+// order; rebuilt on return) and its gradient into the gradient slab: inverse sweep, potential, then the reverse sweep
+// through EA0, the couplings first to last and EA1 (neutra.py:58-68).  Returns U~.
+template <int TH, int NHL, int SB>
+__device__ __forceinline__ float wide_adjusted_grad(const WideCtx& c, const NfmcRealNVP& f, const NfmcPotential& pot, int lane,
+                                                    bool rev_last) {
+    const float ldp = wide_inverse_sweep<TH, NHL, SB>(c, f, rev_last);
+    const float u = wide_potential<true>(c, c.xs, pot, lane);
+    wide_ea<kEaBackward>(c, f.ea0_log_scale, f.ea0_shift, false);
+    for (int l = 0; l < f.n_coupling; ++l)
+        wide_coupling_backward<TH, NHL, SB>(c, mfma_layer(f.weights + l * f.layer_stride, f.d, 16 * TH, NHL), (l & 1) == 0);
+    wide_ea<kEaBackward>(c, f.ea1_log_scale, f.ea1_shift, rev_last);
+    return u - chain_sum(ldp);
+}
+
+// ---- the lane's four normals at tile positions p0 .. p0 + 3, in latent order (`rev`: position p holds logical d - 1 - p):
+// block `logical coordinate / 4` of the chain's Philox stream `tag` at `step` (draw_latent_c's rule), or, where `replay`
+// is given, read from it: the chain's row of a replayed field, in logical order.
+__device__ __forceinline__ f32x4 wide_normal4(const NfmcRng& rng, uint32_t gchain, uint32_t step, uint32_t tag, const float* replay, int d,
+                                              int p0, bool rev) {
+    f32x4 v;
+    if (replay) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = replay[rev ? d - 1 - (p0 + j) : p0 + j];
+    } else {
+        const int blk = rev ? (d - 4 - p0) >> 2 : p0 >> 2;
+        float w[4];
+        philox_normal4(gchain, step, (uint32_t)blk, tag, (uint32_t)rng.seed, (uint32_t)(rng.seed >> 32), w);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = rev ? w[3 - j] : w[j];
+    }
+    return v;
+}
+
+// ---- the uniform of the Metropolis test of transition s of the call: element (s, rrow) of the replayed field, or the
+// chain's Philox stream TAG -- kTagJump: one block per step, word x; kTagAccept: block step >> 2, word step & 3
+template <uint32_t TAG>
+__device__ __forceinline__ float wide_accept_uniform(const NfmcRng& rng, uint32_t gchain, int s, int64_t n, int64_t rrow) {
+    static_assert(TAG == kTagJump || TAG == kTagAccept, "the two accept streams");
+    if (rng.replay_uniforms) return rng.replay_uniforms[(int64_t)s * n + rrow];
+    const uint32_t step = rng.step0 + (uint32_t)s;
+    if constexpr (TAG == kTagJump) {
+        const uint4 r = philox4x32_10(gchain, step, 0u, kTagJump, (uint32_t)rng.seed, (uint32_t)(rng.seed >> 32));
+        return u32_to_uniform(r.x);
+    } else {
+        const uint4 r = philox4x32_10(gchain, step >> 2, 0u, kTagAccept, (uint32_t)rng.seed, (uint32_t)(rng.seed >> 32));
+        return u32_to_uniform(pick_word(r, step & 3u));
+    }
+}
+
+// ---- per-transition statistics of the one-launch samplers.  The weight images are idle at the end of a transition and
+// their memory takes `red`: [8 waves][2 d] doubles.  Between the barrier that closes the transition's last GEMM and the
+// one that frees the images again: wide_stats_tile per kept tile, then wide_stats_flush; after the last chain tile,
+// wide_stats_tail.
+// kept tile m (`v`; a lane past n counts as 0) summed over the wave's 16 chains -> sum and sum of squares at the tile's
+// coordinates (`rev`: the tile is in latent order and position p is logical coordinate d - 1 - p)
+__device__ __forceinline__ void wide_stats_tile(double* red, const WideCtx& c, int wave, int m, const f32x4 v, bool active, bool rev) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const float xv = active ? v[t] : 0.f;
+        double v1 = (double)xv, v2 = (double)xv * (double)xv;
+        for (int k = 1; k < 16; k <<= 1) {
+            v1 += __shfl_xor(v1, k, kWave);
+            v2 += __shfl_xor(v2, k, kWave);
+        }
+        if (c.col == 0) {
+            const int pos = 16 * m + 4 * c.q + t;
+            const int cc = rev ? c.d - 1 - pos : pos;
+            red[wave * 2 * c.d + cc] = v1;
+            red[wave * 2 * c.d + c.d + cc] = v2;
+        }
+    }
+}
+// the transition's sums over the waves -> the workgroup's slab `out` (2 dp doubles, zeros past d); `first`: store, else add
+__device__ __forceinline__ void wide_stats_flush(const double* red, double* out, int d, int dp, bool first) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < 2 * dp; i += kMfmaBlock) {
+        const int half = i / dp, cc = i - half * dp;
+        double v = 0.0;
+        if (cc < d)
+            for (int w8 = 0; w8 < kMfmaWaves; ++w8) v += red[w8 * 2 * d + half * d + cc];
+        out[i] = first ? v : out[i] + v;
+    }
+}
+// the workgroup's accepted / non-finite counts (counted on lane group 0 only) -> words slot, slot + 1 of the slab's
+// kStatTail tail words, zeros in the others; `defer`: added to the caller-zeroed slab (nfmc_stats_fold_f32) instead of
+// stored.  `first` still set: a workgroup without a tile (never launched: grid <= tiles) zero-fills the sums, so that the
+// slab stays well defined.  flow_mh_wide_kernel keeps its own copy of these three, without that fill.
+__device__ __forceinline__ void wide_stats_tail(double* red, double* out, int dp, int lane, int wave, uint32_t n_acc, uint32_t n_bad,
+                                                bool defer, int slot, bool first) {
+    for (int m = 1; m < 16; m <<= 1) {
+        n_acc += __shfl_xor(n_acc, m, kWave);
+        n_bad += __shfl_xor(n_bad, m, kWave);
+    }
+    __syncthreads();
+    if (lane == 0) {
+        red[2 * wave] = (double)n_acc;
+        red[2 * wave + 1] = (double)n_bad;
+    }
+    __syncthreads();
+    if (threadIdx.x < kStatTail) {
+        double v = 0.0;
+        const int k = (int)threadIdx.x - slot;
+        if (k == 0 || k == 1)
+            for (int w8 = 0; w8 < kMfmaWaves; ++w8) v += red[2 * w8 + k];
+        out[2 * dp + threadIdx.x] = defer ? out[2 * dp + threadIdx.x] + v : v;
+    }
+    if (first)
+        for (int i = threadIdx.x; i < 2 * dp; i += kMfmaBlock) out[i] = 0.0;
+}
+
+// U~ and its gradient of n latent rows; slab: state and gradient rows of the workgroup slots (wide_slab_row)
 template <int TH, int NHL>
 __global__ void __launch_bounds__(kMfmaBlock, 2) neutra_grad_wide_kernel(NfmcRealNVP f, NfmcPotential pot, const float* __restrict__ z,
                                                                       int64_t n, float* __restrict__ u_out, float* __restrict__ grad_out,
                                                                       float* __restrict__ slab, int64_t tiles) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int hp = 16 * TH;
-    constexpr int kSB = kWideGradSB;
     const int d = f.d;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool rev_last = (f.n_coupling & 1) != 0;
     WideCtx c;
     wide_ctx_init(c, lds, f, lane);
-    // the lane group's private slab row belongs to the workgroup SLOT, not to the chain: the next chain tile of the grid-stride
-    // loop reuses it (a tile's results have left for the output arrays by then), so the slab is bounded by the grid
-    const int64_t srow = (int64_t)blockIdx.x * kMfmaChains + wave * 16 + c.col;
+    c.xs = wide_slab_row(c, slab, 0, wave);
+    c.gs = wide_slab_row(c, slab, 1, wave);
     for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const int64_t row = tile * kMfmaChains + wave * 16 + c.col;
-        const bool active = row < n;
-        const float* zr = z + (active ? row : n - 1) * d;
-        c.xs = slab + srow * d + 4 * c.q;
-        c.gs = slab + ((int64_t)gridDim.x * kMfmaChains + srow) * d + 4 * c.q;
+        const WideRow r = wide_chain_row(c, tile, wave, n);
+        const float* zr = z + r.rrow * d;
         // z at tile positions in latent order (flows with an odd number of reversals: position p holds logical d - 1 - p)
         wide_tiles(d / 16, [&](int m) { return rev_last ? vec_tile_rev(zr, m, c.q, d) : vec_tile(zr, m, c.q); },
                    [&](int m, const f32x4& v) { tile_st(c.xs, m, v); });
-        float ldp = wide_ea<kEaInverse>(c, f.ea1_log_scale, f.ea1_shift, rev_last);
-        for (int l = f.n_coupling - 1; l >= 0; --l)
-            ldp += wide_coupling<TH, NHL, true, kSB>(c, mfma_layer(f.weights + l * f.layer_stride, d, hp, NHL), (l & 1) == 0);
-        ldp += wide_ea<kEaInverse>(c, f.ea0_log_scale, f.ea0_shift, false);
-        const float u = wide_potential_grad(c, pot, lane);
-        wide_ea<kEaBackward>(c, f.ea0_log_scale, f.ea0_shift, false);
-        for (int l = 0; l < f.n_coupling; ++l)
-            wide_coupling_backward<TH, NHL, kSB>(c, mfma_layer(f.weights + l * f.layer_stride, d, hp, NHL), (l & 1) == 0);
-        wide_ea<kEaBackward>(c, f.ea1_log_scale, f.ea1_shift, rev_last);
-        const float ut = u - chain_sum(ldp);
-        if (active) {
-            if (u_out && c.q == 0) u_out[row] = ut;
-            if (grad_out) wide_store_row(c.gs, grad_out + row * d, d, c.q, rev_last);
+        const float ut = wide_adjusted_grad<TH, NHL, kWideGradSB>(c, f, pot, lane, rev_last);
+        if (r.active) {
+            if (u_out && c.q == 0) u_out[r.row] = ut;
+            if (grad_out) wide_store_row(c.gs, grad_out + r.row * d, d, c.q, rev_last);
         }
     }
 }
 
-// x -> z, logdet_forward, log_prob (realnvp_forward_mfma_kernel's contract); slab: grid * 128 private rows of d floats
+// x -> z, logdet_forward, log_prob (realnvp_forward_mfma_kernel's contract); slab: the state rows
 template <int TH, int NHL>
 __global__ void __launch_bounds__(kMfmaBlock, 2) realnvp_forward_wide_kernel(NfmcRealNVP f, const float* __restrict__ x, int64_t n,
                                                                           float* __restrict__ z, float* __restrict__ logdet,
                                                                           float* __restrict__ log_prob, float* __restrict__ slab,
                                                                           int64_t tiles) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int hp = 16 * TH;
     const int d = f.d;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool rev_last = (f.n_coupling & 1) != 0;
     WideCtx c;
     wide_ctx_init(c, lds, f, lane);
-    // the lane group's private slab row belongs to the workgroup SLOT, not to the chain: the next chain tile of the grid-stride
-    // loop reuses it (a tile's results have left for the output arrays by then), so the slab is bounded by the grid
-    const int64_t srow = (int64_t)blockIdx.x * kMfmaChains + wave * 16 + c.col;
+    c.xs = wide_slab_row(c, slab, 0, wave);
     for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const int64_t row = tile * kMfmaChains + wave * 16 + c.col;
-        const bool active = row < n;
-        const float* xr = x + (active ? row : n - 1) * d;
-        c.xs = slab + srow * d + 4 * c.q;
+        const WideRow r = wide_chain_row(c, tile, wave, n);
+        const float* xr = x + r.rrow * d;
         wide_tiles(d / 16, [&](int m) { return vec_tile(xr, m, c.q); }, [&](int m, const f32x4& v) { tile_st(c.xs, m, v); });
-        float ldp = wide_ea<kEaForward>(c, f.ea0_log_scale, f.ea0_shift, false);
-        for (int l = 0; l < f.n_coupling; ++l)
-            ldp += wide_coupling<TH, NHL, false, kWideFlowSB>(c, mfma_layer(f.weights + l * f.layer_stride, d, hp, NHL), (l & 1) == 0);
-        ldp += wide_ea<kEaForward>(c, f.ea1_log_scale, f.ea1_shift, rev_last);
-        const float ld = chain_sum(ldp);
+        const float ld = chain_sum(wide_forward_sweep<TH, NHL, kWideFlowSB>(c, f, rev_last));
         const float ss = wide_sum_squares(c);
-        if (active) {
+        if (r.active) {
             if (c.q == 0) {
-                if (logdet) logdet[row] = ld;
-                if (log_prob) log_prob[row] = -0.5f * ss - 0.5f * (float)d * kLog2Pi + ld;
+                if (logdet) logdet[r.row] = ld;
+                if (log_prob) log_prob[r.row] = -0.5f * ss - 0.5f * (float)d * kLog2Pi + ld;
             }
-            if (z) wide_store_row(c.xs, z + row * d, d, c.q, rev_last);
+            if (z) wide_store_row(c.xs, z + r.row * d, d, c.q, rev_last);
         }
     }
 }
@@ -541,49 +683,31 @@ __global__ void __launch_bounds__(kMfmaBlock, 2) realnvp_inverse_wide_kernel(Nfm
                                                                           float* __restrict__ log_q, NfmcRng rng, float* __restrict__ slab,
                                                                           int64_t tiles) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int hp = 16 * TH;
     const int d = f.d;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool rev_last = (f.n_coupling & 1) != 0;
     WideCtx c;
     wide_ctx_init(c, lds, f, lane);
-    // the lane group's private slab row belongs to the workgroup SLOT, not to the chain: the next chain tile of the grid-stride
-    // loop reuses it (a tile's results have left for the output arrays by then), so the slab is bounded by the grid
-    const int64_t srow = (int64_t)blockIdx.x * kMfmaChains + wave * 16 + c.col;
+    c.xs = wide_slab_row(c, slab, 0, wave);
     for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const int64_t row = tile * kMfmaChains + wave * 16 + c.col;
-        const bool active = row < n;
-        const int64_t rrow = active ? row : n - 1;
-        c.xs = slab + srow * d + 4 * c.q;
+        const WideRow r = wide_chain_row(c, tile, wave, n);
         if (z) {
-            const float* zr = z + rrow * d;
+            const float* zr = z + r.rrow * d;
             wide_tiles(d / 16, [&](int m) { return rev_last ? vec_tile_rev(zr, m, c.q, d) : vec_tile(zr, m, c.q); },
                        [&](int m, const f32x4& v) { tile_st(c.xs, m, v); });
-        } else {   // Philox stream kTagLatent, one block per 4 consecutive logical coordinates (draw_latent_c's rule)
-            const uint32_t gchain = (uint32_t)(rng.chain_offset + (uint64_t)rrow);
-            for (int m = 0; m < d / 16; ++m) {
-                const int p0 = 16 * m + 4 * c.q;
-                const int blk = rev_last ? (d - 4 - p0) >> 2 : p0 >> 2;
-                float w[4];
-                philox_normal4(gchain, rng.step0, (uint32_t)blk, kTagLatent, (uint32_t)rng.seed, (uint32_t)(rng.seed >> 32), w);
-                f32x4 v;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = rev_last ? w[3 - j] : w[j];
-                tile_st(c.xs, m, v);
-            }
+        } else {   // the chain's latent stream at the call's step; this entry point has no replayed field
+            const uint32_t gchain = (uint32_t)(rng.chain_offset + (uint64_t)r.rrow);
+            for (int m = 0; m < d / 16; ++m)
+                tile_st(c.xs, m, wide_normal4(rng, gchain, rng.step0, kTagLatent, nullptr, d, 16 * m + 4 * c.q, rev_last));
         }
         const float ss = wide_sum_squares(c);
-        float ldp = wide_ea<kEaInverse>(c, f.ea1_log_scale, f.ea1_shift, rev_last);
-        for (int l = f.n_coupling - 1; l >= 0; --l)
-            ldp += wide_coupling<TH, NHL, true, kWideFlowSB>(c, mfma_layer(f.weights + l * f.layer_stride, d, hp, NHL), (l & 1) == 0);
-        ldp += wide_ea<kEaInverse>(c, f.ea0_log_scale, f.ea0_shift, false);
-        const float ld = chain_sum(ldp);
-        if (active) {
+        const float ld = chain_sum(wide_inverse_sweep<TH, NHL, kWideFlowSB>(c, f, rev_last));
+        if (r.active) {
             if (c.q == 0) {
-                if (logdet) logdet[row] = ld;
-                if (log_q) log_q[row] = -0.5f * ss - 0.5f * (float)d * kLog2Pi - ld;
+                if (logdet) logdet[r.row] = ld;
+                if (log_q) log_q[r.row] = -0.5f * ss - 0.5f * (float)d * kLog2Pi - ld;
             }
-            if (x) wide_store_row(c.xs, x + row * d, d, c.q, false);
+            if (x) wide_store_row(c.xs, x + r.row * d, d, c.q, false);
         }
     }
 }
@@ -593,7 +717,7 @@ __global__ void __launch_bounds__(kMfmaBlock, 2) realnvp_inverse_wide_kernel(Nfm
 // Round 4: ONE launch per NeuTra-HMC transition at these shapes too (neutra_leapfrog_mfma_kernel's structure on the streamed
 // state).  A workgroup slot's slab holds THREE private rows per lane group -- position, gradient, momentum -- in tile-position
 // order; a chain tile's whole trajectory runs on them: momentum draw + H0 + the first half / full step, n_leapfrog times
-// {gradient of the adjusted potential on the slab (the body of neutra_grad_wide_kernel), the steps between two gradients},
+// {gradient of the adjusted potential on the slab (wide_adjusted_grad), the steps between two gradients},
 // the Hamiltonian test, the masked update of (z, grad, U~) in the caller's arrays, the kept row and the statistics.  What
 // the composed version (round 3: a gradient launch + an elementwise launch per leapfrog step, 2 L + 3 launches per
 // transition) paid for between the gradients -- launch gaps, the ramp and tail of 2 L + 3 grids, z and the gradient through
@@ -609,8 +733,6 @@ struct WideLeapArgs {
 template <int TH, int NHL>
 __global__ void __launch_bounds__(kMfmaBlock, 2) neutra_leapfrog_wide_kernel(WideLeapArgs A, int64_t tiles, int dp) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int hp = 16 * TH;
-    constexpr int kSB = kWideLeapSB;
     const NfmcNeutraHmcArgs& a = A.a;
     const NfmcRealNVP& f = a.flow;
     const int d = f.d, TD = f.d / 16;
@@ -621,12 +743,10 @@ __global__ void __launch_bounds__(kMfmaBlock, 2) neutra_leapfrog_wide_kernel(Wid
     const int s = A.step;
     WideCtx c;
     wide_ctx_init(c, lds, f, lane);
-    const int64_t srow = (int64_t)blockIdx.x * kMfmaChains + wave * 16 + c.col;
-    const int64_t slot_rows = (int64_t)gridDim.x * kMfmaChains;
-    c.xs = A.slab + srow * d + 4 * c.q;
-    c.gs = A.slab + (slot_rows + srow) * d + 4 * c.q;
-    float* const ps = A.slab + (2 * slot_rows + srow) * d + 4 * c.q;
-    double* const red = reinterpret_cast<double*>(lds);   // per-tile statistics: [8 waves][2 d] doubles over the (idle) weight images
+    c.xs = wide_slab_row(c, A.slab, 0, wave);
+    c.gs = wide_slab_row(c, A.slab, 1, wave);
+    float* const ps = wide_slab_row(c, A.slab, 2, wave);
+    double* const red = reinterpret_cast<double*>(lds);   // wide_stats_*: over the (idle) weight images
     double* const out = a.stats.sum_x ? a.stats.scratch + (size_t)blockIdx.x * (2 * dp + kStatTail) : nullptr;
     auto mass_tile = [&](int m) {
         f32x4 one;
@@ -637,22 +757,22 @@ __global__ void __launch_bounds__(kMfmaBlock, 2) neutra_leapfrog_wide_kernel(Wid
     uint32_t n_acc = 0, n_bad = 0;
     bool first = true;
     for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const int64_t row = tile * kMfmaChains + wave * 16 + c.col;
-        const bool active = row < n;
-        const int64_t rrow = active ? row : n - 1;
-        const float* zr = a.z + rrow * d;
-        const float* gr = A.gz + rrow * d;
-        const uint32_t gchain = (uint32_t)(a.rng.chain_offset + (uint64_t)rrow);
+        const WideRow r = wide_chain_row(c, tile, wave, n);
+        const float* zr = a.z + r.rrow * d;
+        const float* gr = A.gz + r.rrow * d;
+        const uint32_t gchain = (uint32_t)(a.rng.chain_offset + (uint64_t)r.rrow);
         // ---- start of the trajectory: state and gradient into the slab (tile positions in latent order), momentum draw,
         // H0, the first half step and the first position (hmc.py:100-106, 68-70)
         float kin = 0.f;
         for (int m = 0; m < TD; ++m) {
-            const int p0 = 16 * m + 4 * c.q;
             f32x4 x = rev ? vec_tile_rev(zr, m, c.q, d) : vec_tile(zr, m, c.q);
             const f32x4 g = rev ? vec_tile_rev(gr, m, c.q, d) : vec_tile(gr, m, c.q);
+            // the momentum draw stays written out here: through wide_normal4 this kernel spilled 116-117 registers at
+            // TH = 8, NHL = 2 instead of 108 (either form of the helper: value or array result, row address inside or outside)
+            const int p0 = 16 * m + 4 * c.q;
             float zz[4];
             if (a.rng.replay_normals) {
-                const float* src = a.rng.replay_normals + ((int64_t)s * n + rrow) * d;
+                const float* src = a.rng.replay_normals + ((int64_t)s * n + r.rrow) * d;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) zz[j] = src[rev ? d - 1 - (p0 + j) : p0 + j];
             } else {
@@ -677,20 +797,10 @@ __global__ void __launch_bounds__(kMfmaBlock, 2) neutra_leapfrog_wide_kernel(Wid
             tile_st(ps, m, p);
         }
         kin = chain_sum(kin);
-        const float h0 = A.uz[rrow] + 0.5f * kin;   // hmc.py:103-106
+        const float h0 = A.uz[r.rrow] + 0.5f * kin;   // hmc.py:103-106
         float u = 0.f;
         for (int l = 0; l < a.n_leapfrog; ++l) {
-            // ---- U~ and its gradient at the position in the slab (neutra_grad_wide_kernel's body; the position is rebuilt)
-            float ldp = wide_ea<kEaInverse>(c, f.ea1_log_scale, f.ea1_shift, rev);
-            for (int ll = f.n_coupling - 1; ll >= 0; --ll)
-                ldp += wide_coupling<TH, NHL, true, kSB>(c, mfma_layer(f.weights + ll * f.layer_stride, d, hp, NHL), (ll & 1) == 0);
-            ldp += wide_ea<kEaInverse>(c, f.ea0_log_scale, f.ea0_shift, false);
-            const float ux = wide_potential_grad(c, a.pot, lane);
-            wide_ea<kEaBackward>(c, f.ea0_log_scale, f.ea0_shift, false);
-            for (int ll = 0; ll < f.n_coupling; ++ll)
-                wide_coupling_backward<TH, NHL, kSB>(c, mfma_layer(f.weights + ll * f.layer_stride, d, hp, NHL), (ll & 1) == 0);
-            wide_ea<kEaBackward>(c, f.ea1_log_scale, f.ea1_shift, rev);
-            u = ux - chain_sum(ldp);
+            u = wide_adjusted_grad<TH, NHL, kWideLeapSB>(c, f, a.pot, lane, rev);   // at the position in the slab
             // ---- the closing half step and, unless this was the last, the next step's opening half and position
             const bool last = l + 1 == a.n_leapfrog;
             for (int m0 = 0; m0 < TD; m0 += 4) {
@@ -733,25 +843,17 @@ __global__ void __launch_bounds__(kMfmaBlock, 2) neutra_leapfrog_wide_kernel(Wid
                        });
             k2 = chain_sum(k2);
             lr = h0 - (u + 0.5f * k2);   // hmc.py:107-111
-            float uni;
-            if (a.rng.replay_uniforms) {
-                uni = a.rng.replay_uniforms[(int64_t)s * n + rrow];
-            } else {
-                const uint32_t step = a.rng.step0 + (uint32_t)s;
-                const uint4 r = philox4x32_10(gchain, step >> 2, 0u, kTagAccept, (uint32_t)a.rng.seed, (uint32_t)(a.rng.seed >> 32));
-                uni = u32_to_uniform(pick_word(r, step & 3u));
-            }
-            accept = fast_ln(uni) < lr;   // hmc.py:112-113
-            if (active && c.q == 0 && !(fabsf(lr) <= 3.0e38f)) n_bad++;
+            accept = fast_ln(wide_accept_uniform<kTagAccept>(a.rng, gchain, s, n, r.rrow)) < lr;   // hmc.py:112-113
+            if (r.active && c.q == 0 && !(fabsf(lr) <= 3.0e38f)) n_bad++;
         }
-        accept = accept && active;
-        if (active && c.q == 0) {
+        accept = accept && r.active;
+        if (r.active && c.q == 0) {
             if (accept) {
-                A.uz[row] = u;
+                A.uz[r.row] = u;
                 n_acc++;
             }
-            if (a.masks_out) a.masks_out[(int64_t)s * n + row] = accept ? 1 : 0;
-            if (a.log_ratio_out) a.log_ratio_out[(int64_t)s * n + row] = lr;
+            if (a.masks_out) a.masks_out[(int64_t)s * n + r.row] = accept ? 1 : 0;
+            if (a.log_ratio_out) a.log_ratio_out[(int64_t)s * n + r.row] = lr;
         }
         __syncthreads();   // the weight images are idle: their memory takes this tile's statistics
         for (int m = 0; m < TD; ++m) {
@@ -759,114 +861,26 @@ __global__ void __launch_bounds__(kMfmaBlock, 2) neutra_leapfrog_wide_kernel(Wid
             f32x4 zc;
             if (accept) {
                 zc = tile_ld(c.xs, m);
-                const f32x4 gc = tile_ld(c.gs, m);
-                if (!rev) {
-                    *reinterpret_cast<f32x4*>(a.z + row * d + p0) = zc;
-                    *reinterpret_cast<f32x4*>(A.gz + row * d + p0) = gc;
-                } else {
-                    *reinterpret_cast<f32x4*>(a.z + row * d + (d - 4 - p0)) = rev4(zc);
-                    *reinterpret_cast<f32x4*>(A.gz + row * d + (d - 4 - p0)) = rev4(gc);
-                }
+                wide_store_tile(a.z + r.row * d, d, p0, zc, rev);
+                wide_store_tile(A.gz + r.row * d, d, p0, tile_ld(c.gs, m), rev);
             } else {
                 zc = rev ? vec_tile_rev(zr, m, c.q, d) : vec_tile(zr, m, c.q);
             }
-            if (active && A.sample_row) {
-                if (!rev) *reinterpret_cast<f32x4*>(A.sample_row + row * d + p0) = zc;
-                else *reinterpret_cast<f32x4*>(A.sample_row + row * d + (d - 4 - p0)) = rev4(zc);
-            }
-            if (a.stats.sum_x) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const float zv = active ? zc[t] : 0.f;
-                    double v1 = (double)zv, v2 = (double)zv * (double)zv;
-                    for (int k = 1; k < 16; k <<= 1) {
-                        v1 += __shfl_xor(v1, k, kWave);
-                        v2 += __shfl_xor(v2, k, kWave);
-                    }
-                    if (c.col == 0) {
-                        const int pos = p0 + t;
-                        const int cc = rev ? d - 1 - pos : pos;  // logical latent coordinate
-                        red[wave * 2 * d + cc] = v1;
-                        red[wave * 2 * d + d + cc] = v2;
-                    }
-                }
-            }
+            if (r.active && A.sample_row) wide_store_tile(A.sample_row + r.row * d, d, p0, zc, rev);
+            if (a.stats.sum_x) wide_stats_tile(red, c, wave, m, zc, r.active, rev);   // at logical latent coordinates
         }
-        if (a.stats.sum_x) {
-            __syncthreads();
-            for (int i = threadIdx.x; i < 2 * dp; i += kMfmaBlock) {
-                const int half = i / dp, cc = i - half * dp;
-                double v = 0.0;
-                if (cc < d)
-                    for (int w8 = 0; w8 < kMfmaWaves; ++w8) v += red[w8 * 2 * d + half * d + cc];
-                out[i] = first ? v : out[i] + v;
-            }
-        }
+        if (a.stats.sum_x) wide_stats_flush(red, out, d, dp, first);
         __syncthreads();   // the images are free again for the next tile's stagings
         first = false;
     }
-    if (a.stats.sum_x) {
-        for (int m = 1; m < 16; m <<= 1) {   // counted on lane group 0 only
-            n_acc += __shfl_xor(n_acc, m, kWave);
-            n_bad += __shfl_xor(n_bad, m, kWave);
-        }
-        __syncthreads();
-        if (lane == 0) {
-            red[2 * wave] = (double)n_acc;
-            red[2 * wave + 1] = (double)n_bad;
-        }
-        __syncthreads();
-        if (threadIdx.x < 2) {
-            double v = 0.0;
-            for (int w8 = 0; w8 < kMfmaWaves; ++w8) v += red[2 * w8 + threadIdx.x];
-            out[2 * dp + threadIdx.x] = v;
-        }
-        if (first)   // a workgroup without a tile (never launched: grid <= tiles): keep the slab well defined
-            for (int i = threadIdx.x; i < 2 * dp; i += kMfmaBlock) out[i] = 0.0;
-        if (threadIdx.x >= 2 && threadIdx.x < kStatTail) out[2 * dp + threadIdx.x] = 0.0;
-    }
+    if (a.stats.sum_x) wide_stats_tail(red, out, dp, lane, wave, n_acc, n_bad, false, 0, first);
 }
-
 
 // ------------------------------------------------------------------------------------------------
 // Round 4: the flow-proposal Metropolis step (the jump of jump.py:205-243, the loop body of imh.py:214-249) at these shapes
 // in ONE launch (flow_mh_mfma_kernel's contract on the streamed state).  Until now a wide conditioner at d = 256 / 512
 // composed the transition from three launches (inverse pass, forward pass, accept / select).  The slab of a workgroup slot
 // holds two private rows per lane group: the working row of the flow passes and the chain's current state.
-__device__ __forceinline__ float wide_potential_value(const WideCtx& c, const float* row, const NfmcPotential& p, int lane) {
-    const int TD = c.d / 16;
-    auto xtile = [&](int m) { return tile_ld(row, m); };
-    if (p.kind == NFMC_POT_FUNNEL) {
-        const f32x4 t0 = tile_ld(row, 0);
-        const float x0 = __shfl(t0[0], lane & 15, kWave);   // coordinate 0 = tile 0, register 0, lane group 0
-        float s = 0.f;
-        wide_tiles(TD, xtile, [&](int m, const f32x4& x) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) s = fmaf(x[t], (m == 0 && t == 0 && c.q == 0) ? 0.f : x[t], s);
-        });
-        s = chain_sum(s);
-        const float inv_s2 = 1.f / (p.a_scalar * p.a_scalar);
-        return 0.5f * x0 * x0 * inv_s2 + 0.5f * fast_exp(-x0) * s + 0.5f * (float)(c.d - 1) * x0;
-    }
-    float u = 0.f;
-    wide_tiles(TD, xtile, [&](int m, const f32x4& x) {
-        f32x4 a, b;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            a[t] = p.a_scalar;
-            b[t] = p.b_scalar;
-        }
-        if (p.a) a = vec_tile(p.a, m, c.q);
-        if (p.b) b = vec_tile(p.b, m, c.q);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const float dlt = x[t] - b[t];
-            u = fmaf(a[t] * dlt, dlt, u);
-        }
-    });
-    return chain_sum(u);
-}
-
 template <int TH, int NHL>
 __global__ void __launch_bounds__(kMfmaBlock, 2) flow_mh_wide_kernel(NfmcFlowMhArgs a, float* __restrict__ slab, int64_t tiles, int dp) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -898,7 +912,7 @@ __global__ void __launch_bounds__(kMfmaBlock, 2) flow_mh_wide_kernel(NfmcFlowMhA
                        tile_st(cs, m, v);
                        tile_st(c.xs, m, v);
                    });
-        float u_x = wide_potential_value(c, cs, a.pot, lane);                       // jump.py:212 / imh.py:224
+        float u_x = wide_potential<false>(c, cs, a.pot, lane);                       // jump.py:212 / imh.py:224
         float f_x;
         if (a.logq_cached) {
             f_x = a.logq[rrow];
@@ -939,18 +953,11 @@ __global__ void __launch_bounds__(kMfmaBlock, 2) flow_mh_wide_kernel(NfmcFlowMhA
                 ldp += wide_coupling<TH, NHL, true, kWideFlowSB>(c, mfma_layer(f.weights + l * f.layer_stride, d, hp, NHL), (l & 1) == 0);
             ldp += wide_ea<kEaInverse>(c, f.ea0_log_scale, f.ea0_shift, false);
             const float f_xp = -0.5f * ss + base_c - chain_sum(ldp);
-            const float u_xp = wide_potential_value(c, c.xs, a.pot, lane);            // jump.py:213 / imh.py:225
+            const float u_xp = wide_potential<false>(c, c.xs, a.pot, lane);            // jump.py:213 / imh.py:225
             const float lr = (-u_xp) - (-u_x) + f_x - f_xp;                           // util.py:392
             bool accept = true;
             if (a.adjusted) {
-                float u;
-                if (a.rng.replay_uniforms) {
-                    u = a.rng.replay_uniforms[(int64_t)s * n + rrow];
-                } else {
-                    const uint4 r = philox4x32_10(gchain, a.rng.step0 + (uint32_t)s, 0u, kTagJump, (uint32_t)a.rng.seed, (uint32_t)(a.rng.seed >> 32));
-                    u = u32_to_uniform(r.x);
-                }
-                accept = fast_ln(u) < lr;                                             // jump.py:225 / imh.py:229-230
+                accept = fast_ln(wide_accept_uniform<kTagJump>(a.rng, gchain, s, n, rrow)) < lr;                                             // jump.py:225 / imh.py:229-230
                 if (active && c.q == 0 && !(fabsf(lr) <= 3.0e38f)) n_bad++;
             }
             accept = accept && active;
@@ -1044,7 +1051,7 @@ int nfmc::nfmc_mfma_wide_supported(int32_t d, int32_t n_hidden, int32_t n_hidden
 
 // The scratch slab of a launch comes from the caller (NfmcRealNVP.scratch; SURVEY 8b: the library never allocates): one
 // private row of d floats per lane group of a workgroup SLOT -- at most kCkMaxGrid slots whatever n -- times `copies`
-// (1: state; 2: state and gradient).
+// (1: state; 2: state and gradient, or working row and current state; 3: position, gradient and momentum).
 static int wide_grid(int64_t n) {
     const int64_t tiles = (n + kMfmaChains - 1) / kMfmaChains;
     return (int)(tiles < kCkMaxGrid ? tiles : kCkMaxGrid);
@@ -1052,13 +1059,26 @@ static int wide_grid(int64_t n) {
 int64_t nfmc::nfmc_wide_slab_floats(int64_t n, int32_t d, int32_t copies) {
     return n > 0 ? (int64_t)copies * wide_grid(n) * kMfmaChains * d : 0;
 }
-static int wide_slab(float** slab, const NfmcRealNVP* flow, int64_t n, int copies) {
-    const int64_t need = nfmc_wide_slab_floats(n, flow->d, copies) * (int64_t)sizeof(float);
-    if (!flow->scratch || flow->scratch_bytes < need || (((uintptr_t)flow->scratch) & 15u)) return NFMC_ESCRATCH;
-    *slab = flow->scratch;
-    return NFMC_OK;
-}
 
+// What a launch over n chains is shaped by: chain tiles, grid, the padded width of a statistics slab and the slab of
+// `copies` rows in the flow's workspace -- `rc`: NFMC_ESCRATCH where that is missing, short or not 16-byte aligned.
+// `own`: the caller brings the slab in scratch of its own, sized and checked there.
+struct WidePlan {
+    int64_t tiles;
+    int grid, dp, rc;
+    float* slab;
+    WidePlan(const NfmcRealNVP& flow, int64_t n, int copies, float* own = nullptr)
+        : tiles((n + kMfmaChains - 1) / kMfmaChains), grid(wide_grid(n)), dp(padded_d(flow.d)), rc(NFMC_OK), slab(own ? own : flow.scratch) {
+        const int64_t need = nfmc_wide_slab_floats(n, flow.d, copies) * (int64_t)sizeof(float);
+        if (!own && (!flow.scratch || flow.scratch_bytes < need || (((uintptr_t)flow.scratch) & 15u))) rc = NFMC_ESCRATCH;
+    }
+    // the statistics scratch holds one slab per workgroup
+    bool stats_fit(const NfmcStats& s) const {
+        return !s.sum_x || s.scratch_bytes >= (int64_t)grid * (2 * dp + kStatTail) * (int64_t)sizeof(double);
+    }
+};
+
+// launches KERNEL<TH, NHL> of `flow` on `plan.grid` workgroups of stream `st`; the outcome goes to `rc`
 #define NFMC_WIDE_DISPATCH(KERNEL, ...)                                                                                        \
     {                                                                                                                           \
         const int th = nfmc_realnvp_padded_hidden(flow->n_hidden) / 16, nhl = flow->n_hidden_layers;                            \
@@ -1071,12 +1091,12 @@ static int wide_slab(float** slab, const NfmcRealNVP* flow, int64_t n, int copie
         if (rc == NFMC_OK && e != hipSuccess) rc = (int)e;                                                                      \
         if (rc == NFMC_OK && (e = hipGetLastError()) != hipSuccess) rc = (int)e;                                                \
     }
-#define NFMC_WIDE_LAUNCH(KERNEL, THV, NHLV, ...)                                                                       \
-    {                                                                                                                   \
-        auto kern = KERNEL<THV, NHLV>;                                                                                  \
-        /* per call: the attribute belongs to the (kernel, device) pair, and a process may drive several devices */     \
-        e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWideLdsBytes);     \
-        if (e == hipSuccess) hipLaunchKernelGGL(kern, dim3(grid), dim3(kMfmaBlock), kWideLdsBytes, st, __VA_ARGS__);    \
+#define NFMC_WIDE_LAUNCH(KERNEL, THV, NHLV, ...)                                                                          \
+    {                                                                                                                      \
+        auto kern = KERNEL<THV, NHLV>;                                                                                     \
+        /* per call: the attribute belongs to the (kernel, device) pair, and a process may drive several devices */        \
+        e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWideLdsBytes);        \
+        if (e == hipSuccess) hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(kMfmaBlock), kWideLdsBytes, st, __VA_ARGS__);  \
     }
 
 int nfmc::nfmc_realnvp_forward_wide_f32(const NfmcRealNVP* flow, const float* x, int64_t n, float* z, float* logdet, float* log_prob,
@@ -1084,12 +1104,10 @@ int nfmc::nfmc_realnvp_forward_wide_f32(const NfmcRealNVP* flow, const float* x,
     if (!flow || !x || n <= 0) return NFMC_EINVAL;
     if (!nfmc_mfma_wide_supported(flow->d, flow->n_hidden, flow->n_hidden_layers)) return NFMC_EUNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    const int64_t tiles = (n + kMfmaChains - 1) / kMfmaChains;
-    const int grid = wide_grid(n);
-    float* slab = nullptr;
-    int rc = wide_slab(&slab, flow, n, 1);
+    const WidePlan plan(*flow, n, 1);
+    int rc = plan.rc;
     if (rc) return rc;
-    NFMC_WIDE_DISPATCH(realnvp_forward_wide_kernel, *flow, x, n, z, logdet, log_prob, slab, tiles)
+    NFMC_WIDE_DISPATCH(realnvp_forward_wide_kernel, *flow, x, n, z, logdet, log_prob, plan.slab, plan.tiles)
     return rc;
 }
 
@@ -1100,22 +1118,18 @@ int nfmc::nfmc_realnvp_inverse_wide_f32(const NfmcRealNVP* flow, const float* z,
     NfmcRng r = {};
     if (rng) r = *rng;
     hipStream_t st = (hipStream_t)stream;
-    const int64_t tiles = (n + kMfmaChains - 1) / kMfmaChains;
-    const int grid = wide_grid(n);
-    float* slab = nullptr;
-    int rc = wide_slab(&slab, flow, n, 1);
+    const WidePlan plan(*flow, n, 1);
+    int rc = plan.rc;
     if (rc) return rc;
-    NFMC_WIDE_DISPATCH(realnvp_inverse_wide_kernel, *flow, z, n, x, logdet, log_q, r, slab, tiles)
+    NFMC_WIDE_DISPATCH(realnvp_inverse_wide_kernel, *flow, z, n, x, logdet, log_q, r, plan.slab, plan.tiles)
     return rc;
 }
 
-// the gradient kernel on a slab the caller holds (2 x grid x 128 x d floats)
+// the gradient kernel on the first two copies of the plan's slab
 static int grad_wide_launch(const NfmcRealNVP* flow, const NfmcPotential* pot, const float* z, int64_t n, float* u_out, float* grad_out,
-                            float* slab, hipStream_t st) {
-    const int64_t tiles = (n + kMfmaChains - 1) / kMfmaChains;
-    const int grid = wide_grid(n);
+                            const WidePlan& plan, hipStream_t st) {
     int rc = NFMC_OK;
-    NFMC_WIDE_DISPATCH(neutra_grad_wide_kernel, *flow, *pot, z, n, u_out, grad_out, slab, tiles)
+    NFMC_WIDE_DISPATCH(neutra_grad_wide_kernel, *flow, *pot, z, n, u_out, grad_out, plan.slab, plan.tiles)
     return rc;
 }
 
@@ -1129,13 +1143,11 @@ static int grad_wide_check(const NfmcRealNVP* flow, const NfmcPotential* pot, co
 
 int nfmc::nfmc_neutra_potential_grad_wide_f32(const NfmcRealNVP* flow, const NfmcPotential* pot, const float* z, int64_t n,
                                                    float* u_out, float* grad_out, nfmc_stream_t stream) {
-    int rc = grad_wide_check(flow, pot, z, n, grad_out);
+    const int rc = grad_wide_check(flow, pot, z, n, grad_out);
     if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    float* slab = nullptr;
-    rc = wide_slab(&slab, flow, n, 2);   // state and gradient
-    if (rc) return rc;
-    return grad_wide_launch(flow, pot, z, n, u_out, grad_out, slab, st);
+    const WidePlan plan(*flow, n, 2);   // state and gradient
+    if (plan.rc) return plan.rc;
+    return grad_wide_launch(flow, pot, z, n, u_out, grad_out, plan, (hipStream_t)stream);
 }
 
 // scratch of the fused trajectory: the gradient at the state (n d floats), U~ at the state (n, rounded up to a multiple of
@@ -1147,6 +1159,7 @@ int64_t nfmc::nfmc_neutra_wide_scratch_floats(int64_t n, int32_t d) {
 int nfmc::nfmc_neutra_hmc_steps_wide_f32(const NfmcNeutraHmcArgs* args, float* scratch, int64_t scratch_bytes, nfmc_stream_t stream) {
     if (!args || !scratch) return NFMC_EINVAL;
     const NfmcNeutraHmcArgs& a = *args;
+    const NfmcRealNVP* flow = &a.flow;
     const int d = a.flow.d;
     const int64_t n = a.n;
     if (!nfmc_mfma_wide_supported(d, a.flow.n_hidden, a.flow.n_hidden_layers)) return NFMC_EUNSUPPORTED;
@@ -1159,32 +1172,20 @@ int nfmc::nfmc_neutra_hmc_steps_wide_f32(const NfmcNeutraHmcArgs* args, float* s
     A.gz = scratch;
     A.uz = A.gz + n * d;
     A.slab = A.uz + (n + 3) / 4 * 4;
-    const int dp = padded_d(d);
-    const int64_t tiles = (n + kMfmaChains - 1) / kMfmaChains;
-    const int grid = wide_grid(n);
-    if (a.stats.sum_x && a.stats.scratch_bytes < (int64_t)grid * (2 * dp + kStatTail) * (int64_t)sizeof(double)) return NFMC_ESCRATCH;
-    int rc = grad_wide_check(&a.flow, &a.pot, a.z, n, A.gz);
+    const WidePlan plan(a.flow, n, 3, A.slab);   // the slab came in `scratch`, sized above
+    if (!plan.stats_fit(a.stats)) return NFMC_ESCRATCH;
+    int rc = grad_wide_check(flow, &a.pot, a.z, n, A.gz);
     if (rc) return rc;
-    // U~ and its gradient at the state (also after the caller changed z), on the first two copies of the slab
-    rc = grad_wide_launch(&a.flow, &a.pot, a.z, n, A.uz, A.gz, A.slab, st);
-    const NfmcRealNVP* flow = &a.flow;
-    int countdown = a.samples.countdown, srow = a.samples.row;   // one launch per transition: the store cursor runs here
+    // U~ and its gradient at the state (also after the caller changed z)
+    rc = grad_wide_launch(flow, &a.pot, a.z, n, A.uz, A.gz, plan, st);
+    HostStoreCursor keep(a.samples);   // one launch per transition: the store cursor runs here
     for (int s = 0; s < a.n_steps && rc == NFMC_OK; ++s) {
         A.step = s;
-        A.sample_row = nullptr;
-        if (a.samples.base) {
-            if (countdown > 0) {
-                --countdown;
-            } else {
-                A.sample_row = a.samples.base + (int64_t)srow * n * d;
-                srow = srow + 1 == a.samples.ring_rows ? 0 : srow + 1;
-                countdown = a.samples.stride - 1;
-            }
-        }
-        NFMC_WIDE_DISPATCH(neutra_leapfrog_wide_kernel, A, tiles, dp)
+        A.sample_row = keep.next(n * (int64_t)d);
+        NFMC_WIDE_DISPATCH(neutra_leapfrog_wide_kernel, A, plan.tiles, plan.dp)
         if (rc == NFMC_OK && a.stats.sum_x)
-            hipLaunchKernelGGL(stats_finish_kernel<true>, dim3(stats_finish_grid(dp)), dim3(kFinishBlock), 0, st, a.stats.scratch, grid, dp, d,
-                               a.stats, (unsigned long long)n);
+            hipLaunchKernelGGL(stats_finish_kernel<true>, dim3(stats_finish_grid(plan.dp)), dim3(kFinishBlock), 0, st, a.stats.scratch,
+                               plan.grid, plan.dp, d, a.stats, (unsigned long long)n);
     }
     const hipError_t le = hipGetLastError();
     if (rc) return rc;
@@ -1193,20 +1194,17 @@ int nfmc::nfmc_neutra_hmc_steps_wide_f32(const NfmcNeutraHmcArgs* args, float* s
 
 int nfmc::nfmc_flow_mh_steps_wide_f32(const NfmcFlowMhArgs& a, nfmc_stream_t stream, int* grid_out, int* dp_out) {
     const NfmcRealNVP* flow = &a.flow;
-    const int d = a.flow.d;
-    if (!nfmc_mfma_wide_supported(d, a.flow.n_hidden, a.flow.n_hidden_layers)) return NFMC_EUNSUPPORTED;
+    if (!nfmc_mfma_wide_supported(flow->d, flow->n_hidden, flow->n_hidden_layers)) return NFMC_EUNSUPPORTED;
     if ((((uintptr_t)a.x) | ((uintptr_t)a.samples.base)) & 15u) return NFMC_EUNSUPPORTED;   // 16-byte tiles
     hipStream_t st = (hipStream_t)stream;
-    const int64_t tiles = (a.n + kMfmaChains - 1) / kMfmaChains;
-    const int grid = wide_grid(a.n), dp = padded_d(d);
-    if (a.stats.sum_x && a.stats.scratch_bytes < (int64_t)grid * (2 * dp + kStatTail) * (int64_t)sizeof(double)) return NFMC_ESCRATCH;
-    if (check_defer(a.stats, dp, d)) return NFMC_EINVAL;
-    float* slab = nullptr;
-    int rc = wide_slab(&slab, flow, a.n, 2);   // working row + current state: what nfmc_flow_scratch_bytes(.., with_gradient = 1) sizes
+    const WidePlan plan(a.flow, a.n, 2);   // working row + current state: what nfmc_flow_scratch_bytes(.., with_gradient = 1) sizes
+    if (!plan.stats_fit(a.stats)) return NFMC_ESCRATCH;
+    if (check_defer(a.stats, plan.dp, flow->d)) return NFMC_EINVAL;
+    int rc = plan.rc;
     if (rc) return rc;
-    NFMC_WIDE_DISPATCH(flow_mh_wide_kernel, a, slab, tiles, dp)
+    NFMC_WIDE_DISPATCH(flow_mh_wide_kernel, a, plan.slab, plan.tiles, plan.dp)
     if (rc) return rc;
-    *grid_out = grid;
-    *dp_out = dp;
+    *grid_out = plan.grid;
+    *dp_out = plan.dp;
     return NFMC_OK;
 }

@@ -524,19 +524,10 @@ static int run_hmc(const NfmcNeutraHmcArgs& a, float* scratch, hipStream_t st) {
     auto kern = neutra_leapfrog_mfma_kernel<TD, TH, NHL>;
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLeapLdsBytes);
     if (e != hipSuccess) return (int)e;
-    int countdown = a.samples.countdown, srow = a.samples.row;   // one launch per transition: the store cursor runs here
+    HostStoreCursor keep(a.samples);   // one launch per transition: the store cursor runs here
     for (int s = 0; s < a.n_steps; ++s) {
         A.step = s;
-        A.sample_row = nullptr;
-        if (a.samples.base) {
-            if (countdown > 0) {
-                --countdown;
-            } else {
-                A.sample_row = a.samples.base + (int64_t)srow * n * d;
-                srow = srow + 1 == a.samples.ring_rows ? 0 : srow + 1;
-                countdown = a.samples.stride - 1;
-            }
-        }
+        A.sample_row = keep.next(n * (int64_t)d);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(kMfmaBlock), kLeapLdsBytes, st, A, tiles, dp);
         if (a.stats.sum_x) {
             hipLaunchKernelGGL(stats_finish_kernel<true>, dim3(stats_finish_grid(dp)), dim3(kFinishBlock), 0, st,
@@ -550,17 +541,6 @@ static int run_hmc(const NfmcNeutraHmcArgs& a, float* scratch, hipStream_t st) {
 }  // namespace nfmc
 
 using namespace nfmc;
-
-#define NFMC_MFMA_DISPATCH(TDV, THV, NHLV, CALL)                                        \
-    if (TDV == 4 && THV == 4 && NHLV == 1) { constexpr int TD = 4, TH = 4, NHL = 1; CALL; }      \
-    else if (TDV == 4 && THV == 4 && NHLV == 2) { constexpr int TD = 4, TH = 4, NHL = 2; CALL; } \
-    else if (TDV == 4 && THV == 8 && NHLV == 1) { constexpr int TD = 4, TH = 8, NHL = 1; CALL; } \
-    else if (TDV == 4 && THV == 8 && NHLV == 2) { constexpr int TD = 4, TH = 8, NHL = 2; CALL; } \
-    else if (TDV == 8 && THV == 4 && NHLV == 1) { constexpr int TD = 8, TH = 4, NHL = 1; CALL; } \
-    else if (TDV == 8 && THV == 4 && NHLV == 2) { constexpr int TD = 8, TH = 4, NHL = 2; CALL; } \
-    else if (TDV == 8 && THV == 8 && NHLV == 1) { constexpr int TD = 8, TH = 8, NHL = 1; CALL; } \
-    else if (TDV == 8 && THV == 8 && NHLV == 2) { constexpr int TD = 8, TH = 8, NHL = 2; CALL; } \
-    else return NFMC_EUNSUPPORTED;
 
 // shapes the matrix-core path covers
 int nfmc::nfmc_mfma_supported(int32_t d, int32_t n_hidden, int32_t n_hidden_layers) {
